@@ -23,6 +23,11 @@ inside the timed region, its own cost reported as `gather_ms`.  Rank 0 prints ON
                1e-3 under both readings); `within_1e-3` = {precision: {mean_abs, rel_rms}} (same K steps, same barriers for each leg).
   stages       per-stage times from a pass with FOUR events only (profiling level 1); the per-kernel sums of `roofline` come from a second,
                per-launch-instrumented pass whose ~500 event pairs cost ~7 % and must not leak into `unet_mfma_util`.
+
+--dump-outputs DIR writes, on rank 0, the maps each timed leg returned in its LAST timed step as DIR/<mode>_<precision>.npy (float32, [B,C,H,W];
+rank 0's shard, or the gathered batch when N > 1).  Inputs, weights and context are seeded, so two builds run with the same arguments can be
+compared array for array.  The files hold at most DUMP_BUDGET_BYTES together: a leg whose map exceeds its equal share is stored as a fixed,
+seeded sample (flat indices torch.randperm(numel, seed DUMP_SEED)[:k], sorted; 1-D).
 """
 import argparse
 import contextlib
@@ -40,6 +45,8 @@ sys.path.insert(0, ROOT)
 TFLOP_PER_IMAGE_768_DPT = 5.473  # VAE-enc 2.609 + UNet 2.137 + DPT head 0.726
 TFLOP_PER_IMAGE_768 = 10.50  # VAE-enc 2.609 + UNet 2.137 + VAE-dec 5.754 (2*MAC of conv/linear/QK^T/PV)
 PEAK_BF16_TFLOPS = 2500.0    # MI355X dense bf16 / fp16 MFMA (MI355X_MICROARCH.md)
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all arrays together
+DUMP_SEED = 0
 
 
 def synthetic_rgb(batch: int, res: int, seed: int, device) -> torch.Tensor:
@@ -87,6 +94,26 @@ def parity_vs(ref, out) -> dict:
     return {"mean_abs": float(d.mean()), "max_abs": float(d.max()), "rel_rms": rel_rms,
             "absrel_ls": float(abs_relative_difference(np.clip(aligned, 1e-3, None), gt)), "ref": "fp32 oracle (oracle/), image 0 of the benched batch",
             "within_1e-3": {"mean_abs": bool(d.mean() <= 1e-3), "rel_rms": bool(rel_rms <= 1e-3)}}
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """Write each host tensor of `arrays` as out_dir/<name>.npy in float32 within DUMP_BUDGET_BYTES in all (module docstring); returns
+    {name: {"shape": full shape, "stored": elements written, "sampled": bool}}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1) // 4  # float32 elements per array
+    info = {}
+    for name, t in arrays.items():
+        flat = t.detach().float().cpu().contiguous().reshape(-1)
+        sampled = flat.numel() > share
+        if sampled:
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(DUMP_SEED))[:share].sort().values
+            a = flat[idx].numpy()
+        else:
+            a = flat.numpy().reshape(tuple(t.shape))
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32, copy=False))
+        info[name] = {"shape": list(t.shape), "stored": int(a.size), "sampled": sampled}
+    return info
 
 
 def respawn_under_torchrun(n: int):
@@ -218,7 +245,11 @@ def main(argv=None, engine_factory=None, device=None):
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-fp16", action="store_true", help="skip the second timed leg with the fp16 library")
     ap.add_argument("--no-fp32c", action="store_true", help="skip the third timed leg with the contract precision (fp32 storage, split-bf16 products)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write each timed leg's last-step maps as DIR/<mode>_<precision>.npy (float32, <= 64 MB in all; see the module docstring)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         respawn_under_torchrun(args.gpus)  # does not return
@@ -275,7 +306,9 @@ def main(argv=None, engine_factory=None, device=None):
     rgb = synthetic_rgb(n_total, args.res, 1234, "cpu")[lo:hi].to(dev)
     do_gather = n_gpus > 1 and not args.no_gather
 
-    def timed(engine):
+    dumps = {}  # --dump-outputs: {"<mode>_<precision>": last timed step's maps}, rank 0 only
+
+    def timed(engine, precision):
         """one step = one pass of the hot path over this rank's shard (+ the result gather of configs[4] when N > 1)"""
         def step():
             o = engine.infer(rgb, args.mode)
@@ -289,9 +322,11 @@ def main(argv=None, engine_factory=None, device=None):
             assert torch.isfinite(o).all()
             if do_gather:
                 assert o.shape[0] == n_total
+            if args.dump_outputs and rank == 0:
+                dumps[f"{args.mode}_{precision}"] = o.detach().cpu()
         return el, o
 
-    elapsed, out = timed(eng)
+    elapsed, out = timed(eng, args.precision)
     step_stats = timed.stats
     ms_per_step = elapsed / args.steps * 1e3
     images = n_total * args.steps
@@ -409,7 +444,7 @@ def main(argv=None, engine_factory=None, device=None):
     if args.precision == "bf16" and not args.no_fp16 and n_gpus == 1:  # (N > 1 measures scaling of the headline dtype only: no second engine build per rank)
         eng.close()
         eng = build_engine("fp16")
-        el16, o16 = timed(eng)
+        el16, o16 = timed(eng, "fp16")
         if o16 is not None and rank == 0:
             out0_f16 = o16[0].float().cpu()
         fp16 = {"value_fp16": round(images / el16, 3), "ms_per_step_fp16": round(el16 / args.steps * 1e3, 3),
@@ -432,7 +467,7 @@ def main(argv=None, engine_factory=None, device=None):
     if args.precision == "bf16" and not args.no_fp32c and n_gpus == 1:
         eng.close()
         eng = build_engine("fp32c")
-        elc, oc = timed(eng)
+        elc, oc = timed(eng, "fp32c")
         if oc is not None and rank == 0:
             out0_c = oc[0].float().cpu()
         fp32c = {"value_fp32c": round(images / elc, 3), "ms_per_step_fp32c": round(elc / args.steps * 1e3, 3),
@@ -483,6 +518,8 @@ def main(argv=None, engine_factory=None, device=None):
                "seconds": round(dt, 2)}
         assert torch.isfinite(ref).all()
 
+    dumped = dump_outputs(args.dump_outputs, dumps) if (args.dump_outputs and rank == 0) else None
+
     if rank == 0:
         head_name = "DPT disparity head" if dpt else f"{args.mode} head"
         cfg_idx = 3 if dpt else (1 if args.mode == "depth" else 2)
@@ -506,6 +543,8 @@ def main(argv=None, engine_factory=None, device=None):
                 "roofline": roofline, "cpu_baseline": cpu, "stages": stages, "parity": parity,
                 # does `value` (the benched dtype) meet north_star's 1e-3 tolerance?  per metric; null when the oracle leg did not run
                 "value_within_tolerance": parity[args.precision]["within_1e-3"] if parity else None}
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
         if parity and "fp16" in parity:
             line["value_fp16_within_tolerance"] = parity["fp16"]["within_1e-3"]
         if fp16:

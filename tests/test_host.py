@@ -148,12 +148,12 @@ def test_pipeline_validation_without_gpu():
 
 def test_v1_empty_text_embed_fixture_shape():
     """The only fixture-like artefact of the reference (GenPercept_v1/empty_text_embed.npy) is [77,1024] fp16; rows [0:2]
-    are what the v2 pipeline's do_not_pad tokenisation yields.  Only checked where the reference tree is mounted."""
-    p = "/root/reference/GenPercept_v1/empty_text_embed.npy"
-    if not os.path.exists(p):
-        pytest.skip("reference tree not mounted")
-    e = np.load(p)
+    are what the v2 pipeline's do_not_pad tokenisation yields.  tests/golden/refexec_v1_tiny.npz stores it whole (`embed_77`, written
+    by make_goldens.py from that file) beside the rows [0:2] it was run with."""
+    g = np.load(os.path.join(ROOT, "tests", "golden", "refexec_v1_tiny.npz"))
+    e = g["embed_77"]
     assert e.shape == (77, 1024) and e.dtype == np.float16
+    assert np.array_equal(g["embed_rows_0_2"], e[:2]) and np.isfinite(e).all()
 
 
 def test_shard_range_partitions_the_batch():
@@ -669,6 +669,49 @@ def test_bench_single_rank_precision_legs_with_a_stub_engine(capsys):
     assert built == ["fp32c"] and line["dtype"] == "fp32c" and "NOT BASELINE" in line["metric"] and "value_fp16" not in line and "value_fp32c" not in line
 
 
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path, capsys, monkeypatch):
+    """--dump-outputs DIR: each timed leg's maps of its LAST timed step (the stub returns a new value per call) as DIR/<mode>_<precision>.npy
+    float32; --steps sets the number of timed calls exactly; a map above its share of the byte budget is a fixed seeded sample, the same
+    from run to run."""
+    import bench
+
+    class Stub:
+        def __init__(self, local_rank, precision):
+            self.calls = 0
+
+        def infer(self, rgb, mode):
+            self.calls += 1
+            stub.last = self
+            b, _, h, w = rgb.shape
+            return torch.arange(b * 3 * h * w, dtype=torch.float32).reshape(b, 3, h, w) / (b * 3 * h * w) + self.calls
+
+        def close(self):
+            pass
+
+    stub = Stub(0, "bf16")
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "2", "--res", "16", "--mode", "normal", "--no-cpu", "--no-profile"]
+    line = bench.main(argv + ["--no-fp16", "--dump-outputs", str(tmp_path / "a")], engine_factory=Stub, device="cpu")
+    capsys.readouterr()
+    assert stub.last.calls == 2 + 3 and line["steps"] == 3 and line["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path / "a")) == ["normal_bf16.npy", "normal_fp32c.npy"]
+    for name in ("normal_bf16", "normal_fp32c"):
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (4, 3, 16, 16) and line["dumped_outputs"]["arrays"][name]["sampled"] is False
+        np.testing.assert_array_equal(a, (np.arange(4 * 3 * 16 * 16, dtype=np.float32).reshape(4, 3, 16, 16) / (4 * 3 * 16 * 16) + 5))
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 3 * 4 * 1000)  # three legs, 1000 float32 elements each
+    for d in ("b", "c"):
+        line = bench.main(argv + ["--dump-outputs", str(tmp_path / d)], engine_factory=Stub, device="cpu")
+        capsys.readouterr()
+    assert sorted(os.listdir(tmp_path / "b")) == ["normal_bf16.npy", "normal_fp16.npy", "normal_fp32c.npy"]
+    for name in ("normal_bf16", "normal_fp16", "normal_fp32c"):
+        b, c = np.load(tmp_path / "b" / f"{name}.npy"), np.load(tmp_path / "c" / f"{name}.npy")
+        assert b.shape == (1000,) and b.dtype == np.float32 and np.array_equal(b, c)
+        assert line["dumped_outputs"]["arrays"][name] == {"shape": [4, 3, 16, 16], "stored": 1000, "sampled": True}
+        assert np.all(np.diff(b) > 0) and b.min() >= 5 and b.max() < 6  # sorted flat indices into the last step's map
+    with pytest.raises(SystemExit):
+        bench.main(argv[:2] + ["--steps", "0"], engine_factory=Stub, device="cpu")
+
+
 def test_bench_multi_gpu_path_world_size_2_gloo(tmp_path):
     """bench.py's own N > 1 code (init_process_group from the torchrun environment, WORLD_SIZE == --gpus check, contiguous shards, the timed
     loop with barrier + max over ranks, the in-step result gather to rank 0, the gather-alone leg, ONE JSON line from rank 0) executed on
@@ -678,7 +721,8 @@ def test_bench_multi_gpu_path_world_size_2_gloo(tmp_path):
     port = 31500 + (os.getpid() % 2000)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            str(script)]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    # CPU only, also on a GPU machine: with a device visible init_process_group would pick nccl and bind rank r to GPU r
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES=""))
     assert r.returncode == 0, r.stdout + r.stderr
     assert "<rank0:OK>" in r.stderr and "<rank1:OK>" in r.stderr, r.stdout + r.stderr
     # a launcher whose WORLD_SIZE disagrees with --gpus is refused (r1 silently measured one GPU)

@@ -28,8 +28,23 @@ def test_scheduler_tables_equal_the_reference_class():
     g, cfgs = _ref_cfgs()
     assert len(cfgs) == 9
     pairs = g["variance_pairs"]
+    # torch's float32 Tensor.sqrt is not correctly rounded on every CPU and differs between CPUs by up to 1 ulp; the zero-SNR rescale's
+    # 1 - abar[t] / abar[t-1] turns that into thousands of ulp of `betas`.  The fixture records the one sqrt of those tables (input: the
+    # cumprod, identical everywhere; output: what the machine that ran the reference produced).  Where this machine's sqrt gives other
+    # bits for that tensor, it must be within 1 ulp, and the recorded result is replayed for that tensor alone: everything else is compared bit for bit.
+    sqrt_in, sqrt_out = torch.from_numpy(g["power_3.0_zero_snr/sqrt_in"]), torch.from_numpy(g["power_3.0_zero_snr/sqrt_out"])
+    here = torch.Tensor.sqrt(sqrt_in)
+    replay = not torch.equal(here, sqrt_out)
+    if replay:
+        assert np.abs(here.numpy().view(np.int32) - sqrt_out.numpy().view(np.int32)).max() <= 1
+    orig_sqrt = torch.Tensor.sqrt
     for name, cfg in cfgs:
-        s = DDIMSchedulerCustomized(**cfg)
+        if replay and cfg.get("rescale_betas_zero_snr"):
+            torch.Tensor.sqrt = lambda t: sqrt_out.clone() if (t.dtype == sqrt_in.dtype and torch.equal(t, sqrt_in)) else orig_sqrt(t)
+        try:
+            s = DDIMSchedulerCustomized(**cfg)
+        finally:
+            torch.Tensor.sqrt = orig_sqrt
         assert np.array_equal(s.betas.numpy(), g[name + "/betas"]), name
         assert np.array_equal(s.alphas_cumprod.numpy(), g[name + "/alphas_cumprod"]), name
         assert np.float32(s.final_alpha_cumprod) == g[name + "/final_alpha_cumprod"], name

@@ -40,8 +40,14 @@ SEEDS = dict(unet=101, vae=102, inputs=103)
 
 
 def _checksums(sd):
+    """per tensor: sum and sum of squares in float64, each correctly rounded (math.fsum), so that no thread count or reduction order moves a bit"""
+    import math
     import numpy as np
-    return np.array([[float(v.double().sum()), float((v.double() ** 2).sum())] for v in sd.values()], dtype=np.float64)
+    rows = []
+    for v in sd.values():
+        a = v.double().numpy().ravel()
+        rows.append([math.fsum(a), math.fsum(a * a)])
+    return np.array(rows, dtype=np.float64)
 
 
 def build_fixture():
