@@ -95,34 +95,56 @@ void launch_c_rgb_split(const void* rgb, int is_u8, h16_t* out, int B, int H, in
     hipLaunchKernelGGL(c_rgb_split_kernel, dim3(cgrid((long long)B * H * W * 8)), dim3(256), 0, s, rgb, is_u8, out, B, (long long)H * W);
 }
 
-// ---- GroupNorm statistics of an fp32 NHWC tensor: per (row of `bm` consecutive pixels, channel) {sum, sum of squares}, in the "mode 2" layout
-// of gn_finalize_tiles_kernel (norm.hip): [B][R][C][2] sums followed by [B][R] pixel counts (the last row of an image may be short).  A thread
-// owns one 4-channel vector and every TY-th pixel of the row; the TY partials meet in LDS in a fixed order: deterministic. -------------------
+// ---- GroupNorm statistics of an fp32 NHWC tensor: per (row of `bm` consecutive pixels, channel) {sum, M2}, M2 = sum (x - row mean)^2 the
+// CENTRED second moment, in the "mode 3" layout of gn_finalize_tiles_kernel (norm.hip): [B][R][C][2] partials followed by [B][R] pixel counts
+// (the last row of an image may be short).  Two passes over the row (the second one is L2-hot): a single-pass {sum, sum of squares} loses
+// eps * (mean / std)^2 of the variance to cancellation (2e-4 relative at mean / std = 100), the centred form does not.  A thread owns one
+// 4-channel vector and every TY-th pixel of the row; the TY partials meet in LDS in a fixed order: deterministic. ---------------------------
 __global__ __launch_bounds__(256) void c_gn_stats_kernel(const float* __restrict__ x, float* __restrict__ part, int HW, int C, int bm, int R, int TX) {
-    __shared__ float red[256 * 8];
+    __shared__ float red[256 * 4];
+    __shared__ float mu[256 * 4];
     const int r = blockIdx.x, b = blockIdx.y, vb = blockIdx.z;
     const int TY = 256 / TX, tx = threadIdx.x % TX, ty = threadIdx.x / TX;
     const int nv = C >> 2, v = vb * TX + tx;
     const int p0 = r * bm, cnt = min(bm, HW - p0);
-    float s[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
+    const float* xp = x + ((long long)b * HW + p0) * C + v * 4;
+    float s[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f}, ss[4] = {0.f, 0.f, 0.f, 0.f};
     if (v < nv) {
-        const float* xp = x + ((long long)b * HW + p0) * C + v * 4;
         for (int p = ty; p < cnt; p += TY) {
             const float4 a = *(const float4*)(xp + (long long)p * C);
             s[0] += a.x; s[1] += a.y; s[2] += a.z; s[3] += a.w;
-            q[0] += a.x * a.x; q[1] += a.y * a.y; q[2] += a.z * a.z; q[3] += a.w * a.w;
         }
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { red[threadIdx.x * 8 + e] = s[e]; red[threadIdx.x * 8 + 4 + e] = q[e]; }
+    for (int e = 0; e < 4; ++e) red[threadIdx.x * 4 + e] = s[e];
+    __syncthreads();
+    if (ty == 0 && v < nv) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            for (int k = 0; k < TY; ++k) ss[e] += red[(k * TX + tx) * 4 + e];
+            mu[tx * 4 + e] = ss[e] / (float)cnt;
+        }
+    }
+    __syncthreads();
+    if (v < nv) {
+        const float m[4] = {mu[tx * 4], mu[tx * 4 + 1], mu[tx * 4 + 2], mu[tx * 4 + 3]};
+        for (int p = ty; p < cnt; p += TY) {
+            const float4 a = *(const float4*)(xp + (long long)p * C);
+            const float d[4] = {a.x - m[0], a.y - m[1], a.z - m[2], a.w - m[3]};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) q[e] += d[e] * d[e];
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) red[threadIdx.x * 4 + e] = q[e];
     __syncthreads();
     if (ty == 0 && v < nv) {
         float* o = part + (((long long)b * R + r) * C + v * 4) * 2;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            float ss = 0.f, qq = 0.f;
-            for (int k = 0; k < TY; ++k) { ss += red[(k * TX + tx) * 8 + e]; qq += red[(k * TX + tx) * 8 + 4 + e]; }
-            o[2 * e] = ss;
+            float qq = 0.f;
+            for (int k = 0; k < TY; ++k) qq += red[(k * TX + tx) * 4 + e];
+            o[2 * e] = ss[e];
             o[2 * e + 1] = qq;
         }
     }
@@ -145,6 +167,15 @@ void launch_c_gn_stats(const float* x, float* part, int B, int HW, int C, hipStr
     int TX = 16;
     while (TX < nv && TX < 256) TX <<= 1;
     hipLaunchKernelGGL(c_gn_stats_kernel, dim3(R, B, (nv + TX - 1) / TX), dim3(256), 0, s, x, part, HW, C, bm, R, TX);
+}
+
+// the contract precision's GroupNorm statistics: the centred per-row partials above, Chan-combined across rows by the finaliser (mode 3) into
+// scale[b][c] / shift[b][c] of y = x * scale + shift.  part: B * c_gn_stat_rows(HW, C) * (2 C + 1) floats of scratch.
+void launch_c_groupnorm_scale_shift(const float* x, float* part, int B, int H, int W, int C, int G, float eps, const float* gamma, const float* beta,
+                                    float* scale, float* shift, hipStream_t s) {
+    const int R = c_gn_stat_rows(H * W, C, nullptr);
+    launch_c_gn_stats(x, part, B, H * W, C, s);
+    launch_groupnorm_from_partials(part, 3, R, B, H, W, C, G, eps, gamma, beta, scale, shift, s);
 }
 
 // ---- GroupNorm apply (+ SiLU) of an fp32 tensor, written as a split A-order operand: y = act(x * scale[b][c] + shift[b][c]) --------------

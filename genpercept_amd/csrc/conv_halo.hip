@@ -770,10 +770,8 @@ __global__ __launch_bounds__(512) void conv3x3_halo3_kernel(const IGemmParams p)
                         float* o = outf + m * p.ldo + col;
                         *(f32x4_t*)o = f32x4_t{v[0], v[1], v[2], v[3]};
                         *(f32x4_t*)(o + 4) = f32x4_t{v[4], v[5], v[6], v[7]};
-                        if (STATS) {  // the stored values are the fp32 values themselves
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) { st_s[e] += v[e]; st_q[e] += v[e] * v[e]; }
-                        }
+                        // (no statistics of fp32 rows: single-pass sums lose eps (mean / std)^2 of the variance on fp32 data, so
+                        // igemm_tile_info refuses them and the contract precision's GroupNorms use c_gn_stats, contract.hip)
                     }
                     if (RES && h == 1 && j + 1 < FM) res_f32_load(j + 1);  // (both pixels of row j have consumed rf)
                     continue;
@@ -1179,6 +1177,14 @@ int conv_halo_stat_rows(const IGemmParams& p) {
     const int ncols = p.N > p.n_store ? p.N : p.n_store;
     int tr;
     return halo_plan(p, &tr) / ((ncols + 127) / 128);
+}
+
+// output rows per tile of the halo kernel this problem takes: 16 or 12 (persistent conv3x3_halo3_kernel), 0 (conv3x3_halo2_kernel)
+int conv_halo_tile_rows(const IGemmParams& p) {
+    if (!halo_persistent(p)) return 0;
+    int tr;
+    halo_plan(p, &tr);
+    return tr == 3 ? 12 : 16;
 }
 
 void launch_conv_halo(const IGemmParams& p, hipStream_t s) {

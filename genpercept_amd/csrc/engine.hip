@@ -744,8 +744,10 @@ struct gp_engine {
         return y;
     }
     // ask the kernel that is about to write `y` to leave per-tile channel statistics behind (next GroupNorm skips its read pass)
+    // (not in contract precision: the epilogues' single-pass {sum, sum of squares} partials would lose eps * (mean / std)^2 of a group's variance
+    // on fp32 data, igemm_tile_info refuses fp32 rows; the GroupNorm re-reads the tensor instead, contract.hip: c_gn_stats_kernel)
     void attach_stats(Act& y, IGemmParams& p) {
-        if (!fuse_stats) return;
+        if (!fuse_stats || contract) return;
         int mode = 0, bm = 0;
         const int nt = igemm_tile_info(p, 0, &mode, &bm);
         if (nt <= 0) return;
@@ -830,7 +832,8 @@ struct gp_engine {
         int n_store = 0;        // 0: cout
         bool want_stats = false;  // the output feeds a GroupNorm
     };
-    IGemmParams conv_params(const Act& x, const PackedW& w, const ConvOpt& o, h16_t* out) {
+    IGemmParams conv_params(const Act& x, const PackedW& w, const ConvOpt& o, h16_t* out) { return conv_params_of(x, w, o, out, zero); }
+    static IGemmParams conv_params_of(const Act& x, const PackedW& w, const ConvOpt& o, h16_t* out, h16_t* zero) {
         if (x.C != w.cin_pad) throw std::logic_error("conv: channel mismatch (" + std::to_string(x.C) + " vs " + std::to_string(w.cin_pad) + ")");
         const int Hin = o.ups_h ? o.ups_h : x.H, Win = o.ups_w ? o.ups_w : x.W;
         const int Ho = o.Ho ? o.Ho : Hin, Wo = o.Wo ? o.Wo : Win;
@@ -847,15 +850,32 @@ struct gp_engine {
         p.batch = 1;
         return p;
     }
+    // contract precision: the launch of conv_c / linear_c on a split operand xs (also what the gp_c_conv2d test entry launches)
+    static IGemmParams conv_c_params(const Act& xs, const PackedW& w, const ConvOpt& o, float* out, h16_t* zero) {
+        IGemmParams p = conv_params_of(xs, w, o, nullptr, zero);
+        p.out = out; p.out_fp32 = 1;
+        p.res = (const h16_t*)o.res_f; p.res_f32 = o.res_f ? 1 : 0;
+        return p;
+    }
+    static IGemmParams linear_c_params(const Act& xs, const PackedW& w, const float* res, int act, float* out, h16_t* zero) {
+        if (xs.C != w.cin_pad) throw std::logic_error("linear: channel mismatch");
+        const int nout = act == GP_ACT_GEGLU ? w.cout / 2 : w.cout;
+        IGemmParams p{};
+        p.in = xs.p; p.wt = w.w; p.bias = w.bias; p.res = (const h16_t*)res; p.res_f32 = res ? 1 : 0; p.out = out; p.out_fp32 = 1; p.zero = zero;
+        p.M = (int)xs.pixels(); p.N = w.cout; p.Cin = w.cin_pad; p.n_rows = w.n_rows; p.ks = 1;
+        p.B = xs.B; p.Hi = xs.H; p.Wi = xs.W; p.Ho = xs.H; p.Wo = xs.W; p.stride = 1;
+        p.lda = xs.C; p.ldo = nout; p.ldres = nout; p.ldw = w.cin_pad; p.n_store = nout; p.act = act;
+        p.bias_mode = w.bias ? GP_BIAS_COL : GP_BIAS_NONE; p.batch = 1;
+        return p;
+    }
     // contract precision: split operand in (made here when x is a stored tensor), fp32 rows out, fp32 residual
     Act conv_c(const Act& x0, const PackedW& w, const ConvOpt& o) {
         Act xs = x0;
         const bool tmp = x0.p == nullptr;
         if (tmp) xs = split_operand(x0);
-        IGemmParams p = conv_params(xs, w, o, nullptr);
+        IGemmParams p = conv_c_params(xs, w, o, nullptr, zero);
         Act y = new_act_f(xs.B, p.Ho, p.Wo, p.n_store);
-        p.out = y.f; p.out_fp32 = 1;
-        p.res = (const h16_t*)o.res_f; p.res_f32 = o.res_f ? 1 : 0;
+        p.out = y.f;
         if (o.want_stats) attach_stats(y, p);
         run_igemm(p);
         if (tmp) drop(xs);
@@ -883,12 +903,7 @@ struct gp_engine {
         Act y;
         if (out_inplace) { y.B = xs.B; y.H = xs.H; y.W = xs.W; y.C = nout; y.f = out_inplace; }
         else y = new_act_f(xs.B, xs.H, xs.W, nout);
-        IGemmParams p{};
-        p.in = xs.p; p.wt = w.w; p.bias = w.bias; p.res = (const h16_t*)res; p.res_f32 = res ? 1 : 0; p.out = y.f; p.out_fp32 = 1; p.zero = zero;
-        p.M = (int)xs.pixels(); p.N = w.cout; p.Cin = w.cin_pad; p.n_rows = w.n_rows; p.ks = 1;
-        p.B = xs.B; p.Hi = xs.H; p.Wi = xs.W; p.Ho = xs.H; p.Wo = xs.W; p.stride = 1;
-        p.lda = xs.C; p.ldo = nout; p.ldres = nout; p.ldw = w.cin_pad; p.n_store = nout; p.act = act;
-        p.bias_mode = w.bias ? GP_BIAS_COL : GP_BIAS_NONE; p.batch = 1;
+        IGemmParams p = linear_c_params(xs, w, res, act, y.f, zero);
         if (want_stats && !out_inplace) attach_stats(y, p);
         run_igemm(p);
         if (tmp) drop(xs);
@@ -938,12 +953,11 @@ struct gp_engine {
         float* ws = gn_workspace(x);
         scale = ws + groupnorm_ws_floats(x.B, x.H * x.W, x.C, cfg.norm_groups);
         shift = scale + (size_t)x.B * x.C;
-        if (contract && !x.st) {  // statistics pass over the fp32 tensor: per-row partials in the layout the tile finaliser reads ("mode 2")
+        if (contract) {  // statistics pass over the fp32 tensor: centred per-row partials, Chan-combined by the tile finaliser ("mode 3")
             const int R = c_gn_stat_rows(x.H * x.W, x.C, nullptr);
             float* part = (float*)pool.alloc((size_t)x.B * R * (2 * x.C + 1) * sizeof(float));
             mark("c_gn_stats+finalize " + dims(x), 0.0, 2);
-            launch_c_gn_stats(x.f, part, x.B, x.H * x.W, x.C, st);
-            launch_groupnorm_from_partials(part, 2, R, x.B, x.H, x.W, x.C, cfg.norm_groups, eps, n.g, n.b, scale, shift, st);
+            launch_c_groupnorm_scale_shift(x.f, part, x.B, x.H, x.W, x.C, cfg.norm_groups, eps, n.g, n.b, scale, shift, st);
             pool.release(part);
             return;
         }
@@ -1095,6 +1109,7 @@ struct gp_engine {
         const int B = qkv.B, T = qkv.H * qkv.W, Tpad = round_up(T, 64), Z = B * heads;
         if (hd % 64 || qkv.C != 3 * heads * hd) throw std::logic_error("attention_c: layout");
         if (hd == 64 && !gp_sw().c_no_flash && (long long)T * qkv.C * 2 < 0x7fffffffll) {  // flash attention over split operands (attention.hip)
+            if (scale != 0.125f) throw std::logic_error("attention_c: the split flash kernel computes softmax(q k^T / 8), scale must be 0.125");
             const int C = heads * hd;
             h16_t* qk_hi = (h16_t*)pool.alloc((size_t)B * T * 2 * C * sizeof(h16_t));
             h16_t* qk_lo = (h16_t*)pool.alloc((size_t)B * T * 2 * C * sizeof(h16_t));
@@ -1725,6 +1740,7 @@ static float* scratch_floats(int which, size_t need) {
     }
     return d.bufs[which];
 }
+static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }  // (nullptr passes: optional arguments are checked for presence separately)
 // split-K workspace for a per-kernel call (engines take theirs from the pool)
 static void attach_splitk_scratch(IGemmParams& p, int tile_hint) {
     const int S = igemm_ksplit(p, tile_hint);
@@ -2392,7 +2408,8 @@ gp_status gp_flash_attention(const void* q, const void* k, const void* vt, void*
 }
 
 gp_status gp_flash_attention_split(const float* qkv, int ld, void* out_split, int B, int T, int heads, void* stream) {
-    if (!qkv || !out_split || B < 1 || T < 1 || heads < 1 || ld < 3 * heads * 64 || GP_F16) return GP_ERR_INVALID;
+    if (!qkv || !out_split || B < 1 || T < 1 || heads < 1 || ld < 3 * heads * 64 || (ld % 4) || !al16(qkv) || !al16(out_split) || GP_F16)
+        return GP_ERR_INVALID;  // (c_qk_planes_kernel reads float4 pairs: 16-byte aligned rows)
     try {
         KernelEntry lk;
         const int C = heads * 64, Tpad = (T + 63) / 64 * 64;
@@ -2408,6 +2425,106 @@ gp_status gp_flash_attention_split(const float* qkv, int ld, void* out_split, in
         HIPCHK(hipGetLastError());
         return GP_OK;
     } catch (...) { return GP_ERR_HIP; }
+}
+
+// ---- contract-precision test entry points (bf16 library only): the launchers the engine's conv_c / linear_c / groupnorm use ---------------
+gp_status gp_c_split3(const float* x, int ldx, void* out, long long rows, int C, int b_order, int act, float scale, void* stream) {
+    if (GP_F16 || !x || !out || rows < 1 || C < 8 || (C % 8) || ldx < C || (ldx % 4) || !al16(x) || !al16(out) || (b_order != 0 && b_order != 1) ||
+        (act != GP_ACT_NONE && act != GP_ACT_RELU))  // (the acts the engine splits with: split_operand)
+        return GP_ERR_INVALID;
+    launch_c_split3(x, ldx, (h16_t*)out, rows, C, b_order, act, scale, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
+}
+
+gp_status gp_c_groupnorm_split(const float* x, void* out, const float* gamma, const float* beta, int B, int HW, int C, int G, float eps, int silu,
+                               float* scale_out, float* shift_out, void* stream) {
+    if (GP_F16 || !x || !out || !gamma || !beta || !scale_out || !shift_out || B < 1 || HW < 1 || C < 8 || (C % 8) || G < 1 || (C % G) || !al16(x) ||
+        !al16(out) || !al16(scale_out) || !al16(shift_out))
+        return GP_ERR_INVALID;
+    try {
+        KernelEntry lk;
+        float* part = scratch_floats(1, (size_t)B * c_gn_stat_rows(HW, C, nullptr) * (2 * C + 1));
+        launch_c_groupnorm_scale_shift(x, part, B, HW, 1, C, G, eps, gamma, beta, scale_out, shift_out, (hipStream_t)stream);
+        launch_c_gn_apply_split(x, (h16_t*)out, scale_out, shift_out, B, HW, C, silu ? 1 : 0, (hipStream_t)stream);
+        HIPCHK(hipGetLastError());
+        return GP_OK;
+    } catch (...) { return GP_ERR_HIP; }
+}
+
+gp_status gp_pack_weight_split(const float* w, int cout, int cin, int ks, int cin_pad, int geglu, void* dev_out) {
+    if (GP_F16 || !w || !dev_out || cout < 1 || cin < 1 || (ks != 1 && ks != 3) || cin_pad < cin || (cin_pad % 64)) return GP_ERR_INVALID;
+    try {
+        const int n_rows = gp_packed_rows(cout);
+        std::vector<h16_t> buf((size_t)n_rows * ks * ks * 3 * cin_pad, 0);
+        gp_engine::pack_rows(w, cout, cin, ks, cin_pad, geglu != 0, buf, 0, n_rows, true);
+        HIPCHK(hipMemcpy(dev_out, buf.data(), buf.size() * 2, hipMemcpyHostToDevice));
+        return GP_OK;
+    } catch (...) { return GP_ERR_HIP; }
+}
+
+gp_status gp_pack_weight_phases_split(const float* w, int cout, int cin, int cin_pad, void* dev_out) {
+    if (GP_F16 || !w || !dev_out || cout < 1 || cin < 1 || cin_pad < cin || (cin_pad % 64)) return GP_ERR_INVALID;
+    try {
+        std::vector<h16_t> buf((size_t)gp_packed_rows(cout) * 16 * 3 * cin_pad, 0);
+        gp_engine::pack_phase_rows(w, cout, cin, cin_pad, buf, true);
+        HIPCHK(hipMemcpy(dev_out, buf.data(), buf.size() * 2, hipMemcpyHostToDevice));
+        return GP_OK;
+    } catch (...) { return GP_ERR_HIP; }
+}
+
+gp_status gp_c_conv2d(const void* in_split, const void* w_packed, const void* w_phases, const float* bias, const float* residual, float* out, int B,
+                      int Hi, int Wi, int Cin, int Cout, int ks, int stride, int pad_t, int pad_l, int Ho, int Wo, int ups, int act, int tile_hint,
+                      const float* gamma, const float* beta, int groups, float eps, float* scale_out, float* shift_out, int* path_out, void* stream) {
+    const int nout = act == GP_ACT_GEGLU ? Cout / 2 : Cout;
+    if (GP_F16 || !in_split || !w_packed || !out || B < 1 || Hi < 1 || Wi < 1 || Ho < 1 || Wo < 1 || Cin < 64 || (Cin % 64) || Cout < 8 || (nout % 8) ||
+        (ks != 1 && ks != 3) || (stride != 1 && stride != 2) || (ups && (ks != 3 || stride != 1)) || (act == GP_ACT_GEGLU && (ks != 1 || (Cout % 16))) ||
+        (act != GP_ACT_NONE && act != GP_ACT_GEGLU && act != GP_ACT_SILU && act != GP_ACT_RELU) || !al16(in_split) || !al16(w_packed) || !al16(out) ||
+        !al16(residual) || !al16(bias) || !al16(w_phases))
+        return GP_ERR_INVALID;
+    const bool stats = gamma != nullptr;
+    if (stats && (!beta || !scale_out || !shift_out || groups < 1 || (nout % groups) || act == GP_ACT_GEGLU || !al16(scale_out) || !al16(shift_out)))
+        return GP_ERR_INVALID;
+    try {
+        KernelEntry lk;
+        // the engine's own parameter setup (gp_engine::conv_c / linear_c) on stand-ins for its operand and packed weight
+        Act xs;
+        xs.p = (h16_t*)in_split; xs.B = B; xs.H = Hi; xs.W = Wi; xs.C = 3 * Cin;
+        PackedW pw;
+        pw.w = (h16_t*)w_packed; pw.w_ph = (h16_t*)w_phases; pw.bias = (float*)bias; pw.cout = Cout; pw.cin_pad = 3 * Cin; pw.ks = ks;
+        pw.n_rows = gp_packed_rows(Cout);
+        IGemmParams p;
+        if (ks == 1 && stride == 1 && !ups && Ho == Hi && Wo == Wi) {  // a linear layer (linear_c)
+            p = gp_engine::linear_c_params(xs, pw, residual, act, out, zero_page());
+        } else {
+            gp_engine::ConvOpt o;
+            o.stride = stride; o.pad_t = pad_t; o.pad_l = pad_l; o.Ho = Ho; o.Wo = Wo; o.ups_h = ups ? 2 * Hi : 0; o.ups_w = ups ? 2 * Wi : 0;
+            o.res_f = residual; o.act = act;
+            p = gp_engine::conv_c_params(xs, pw, o, out, zero_page());
+        }
+        p.dbg = gp_sw().igemm_dbg;
+        attach_splitk_scratch(p, tile_hint);
+        if (path_out) *path_out = igemm_path(p, tile_hint);
+        launch_igemm(p, tile_hint, (hipStream_t)stream);
+        if (stats) {
+            float* part = scratch_floats(1, (size_t)B * c_gn_stat_rows(Ho * Wo, nout, nullptr) * (2 * nout + 1));
+            launch_c_groupnorm_scale_shift(out, part, B, Ho, Wo, nout, groups, eps, gamma, beta, scale_out, shift_out, (hipStream_t)stream);
+        }
+        HIPCHK(hipGetLastError());
+        return GP_OK;
+    } catch (...) { return GP_ERR_HIP; }
+}
+
+gp_status gp_c_layernorm_split(const float* x, void* out, const float* gamma, const float* beta, int rows, int C, float eps, void* stream) {
+    if (GP_F16 || !x || !out || !gamma || !beta || rows < 1 || C < 8 || (C % 8) || !al16(x) || !al16(out) || !al16(gamma) || !al16(beta))
+        return GP_ERR_INVALID;
+    launch_c_layernorm_split(x, (h16_t*)out, gamma, beta, rows, C, eps, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
+}
+
+gp_status gp_c_softmax_split(const float* in, void* out, int rows, int T, int ld, float scale, void* stream) {
+    if (GP_F16 || !in || !out || rows < 1 || T < 1 || ld < T || !c_softmax_split_supported(ld) || !al16(in) || !al16(out)) return GP_ERR_INVALID;
+    launch_c_softmax_split(in, (h16_t*)out, rows, T, ld, scale, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
 }
 
 gp_status gp_flash_attention_hd512(const void* q, const void* k, const void* vt, void* out, int B, int T, int ldq, int ldk, int Tpad, int ldo,

@@ -97,11 +97,7 @@ GP_DEV void conv_epilogue(const IGemmParams& p, f32x4_t (&acc)[(BN / WN) / 16][(
                     for (int e = 0; e < 8; ++e)
                         if (col + e < p.n_store) o[e] = v[e];
                 }
-                if (want_stats) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) { st_s[e] += v[e]; st_q[e] += v[e] * v[e]; }
-                }
-                continue;
+                continue;  // (no statistics of fp32 rows: igemm_tile_info refuses them, see conv_halo.hip)
             }
             h16_t* o = outp + (long long)m * p.ldo + col;
             uint4 pk;

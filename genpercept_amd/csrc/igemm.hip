@@ -407,7 +407,9 @@ static int select_cfg(const IGemmParams& p, int tile_hint) {
 
 int igemm_tile_info(const IGemmParams& p, int tile_hint, int* mode, int* bm) {
     // the staged epilogue is the only one that accumulates statistics (epilogue.h)
-    if (p.out_fp32 > 1 || p.act == GP_ACT_GEGLU || (p.ldo & 7) || p.batch > 1 || p.N != p.n_store) return 0;  // (fp32 rows, out_fp32 == 1, are staged too: contract precision)
+    // (none for fp32 rows either: single-pass {sum, sum of squares} partials lose eps (mean / std)^2 of the variance on fp32 data; the contract
+    // precision's GroupNorms take centred statistics from c_gn_stats, contract.hip)
+    if (p.out_fp32 || p.act == GP_ACT_GEGLU || (p.ldo & 7) || p.batch > 1 || p.N != p.n_store) return 0;
     if (igemm_ksplit(p, tile_hint) > 1) return 0;  // partial sums: no epilogue statistics
     if (conv_uses_halo(p, tile_hint)) {
         const int R = conv_halo_stat_rows(p);
@@ -428,21 +430,36 @@ int igemm_tile_info(const IGemmParams& p, int tile_hint, int* mode, int* bm) {
     return p.M / *bm;
 }
 
-void launch_igemm(const IGemmParams& p, int tile_hint, hipStream_t s) {
+// the kernel launch_igemm dispatches p to (IGEMM_PATH_*, kernels.h); launch_igemm itself branches on this
+int igemm_path(const IGemmParams& p, int tile_hint) {
     if (conv_uses_halo(p, tile_hint)) {
+        if (conv_halo_uses_phases(p)) return IGEMM_PATH_HALO_PHASES;
+        const int tr = conv_halo_tile_rows(p);
+        return tr == 12 ? IGEMM_PATH_HALO_12ROW : tr == 16 ? IGEMM_PATH_HALO_16ROW : IGEMM_PATH_HALO_TILES;
+    }
+    if (igemm_uses_pgemm(p, tile_hint)) return IGEMM_PATH_PGEMM;
+    const int S = igemm_ksplit(p, tile_hint);
+    if (S > 1 && p.splitk_ws && (size_t)p.splitk_ws_floats >= (size_t)p.M * p.n_store * S)  // (the workspace the CALLER owns)
+        return (tile_hint == 0 && conv_img_applicable(p)) ? IGEMM_PATH_CONV_IMG : IGEMM_PATH_SPLITK;
+    return IGEMM_PATH_IGEMM;
+}
+
+void launch_igemm(const IGemmParams& p, int tile_hint, hipStream_t s) {
+    const int path = igemm_path(p, tile_hint);
+    if (path == IGEMM_PATH_HALO_16ROW || path == IGEMM_PATH_HALO_12ROW || path == IGEMM_PATH_HALO_PHASES || path == IGEMM_PATH_HALO_TILES) {
         launch_conv_halo(p, s);
         return;
     }
-    if (igemm_uses_pgemm(p, tile_hint)) {
+    if (path == IGEMM_PATH_PGEMM) {
         launch_pgemm(p, s);
         return;
     }
-    const int S = igemm_ksplit(p, tile_hint);
-    if (S > 1) {
+    if (path == IGEMM_PATH_CONV_IMG || path == IGEMM_PATH_SPLITK) {
         // the partial sums live in a workspace the CALLER owns (an engine takes it from its pool): no process-global state here
-        const size_t slice = (size_t)p.M * p.n_store, need = slice * S;
-        float* ws = (p.splitk_ws && (size_t)p.splitk_ws_floats >= need) ? p.splitk_ws : nullptr;
-        if (ws && tile_hint == 0 && conv_img_applicable(p)) {
+        const int S = igemm_ksplit(p, tile_hint);
+        const size_t slice = (size_t)p.M * p.n_store;
+        float* ws = p.splitk_ws;
+        if (path == IGEMM_PATH_CONV_IMG) {
             launch_conv_img(p, ws, S, s);
             const long long total = (long long)p.M * (p.n_store >> 2);
             int blocks = (int)((total + 255) / 256);
@@ -451,18 +468,16 @@ void launch_igemm(const IGemmParams& p, int tile_hint, hipStream_t s) {
                                p.bias_mode == GP_BIAS_COL ? p.bias : nullptr, p.res, p.ldres, p.act, (h16_t*)p.out, p.ldo, p.out_fp32 == 1 ? 1 : 0);
             return;
         }
-        if (ws) {
-            IGemmParams q = p;
-            q.out = ws; q.out_fp32 = 1; q.ldo = p.n_store; q.bias = nullptr; q.bias_mode = GP_BIAS_NONE; q.res = nullptr; q.act = GP_ACT_NONE;
-            q.stats_out = nullptr; q.ksplit = S; q.split_bs = (long long)slice;
-            launch_cfg<64, 64, 2, 2, 3>(q, s);
-            const long long total = (long long)p.M * (p.n_store >> 2);
-            int blocks = (int)((total + 255) / 256);
-            if (blocks > 2048) blocks = 2048;
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, ws, S, (long long)slice, p.M, p.N, p.n_store,
-                               p.bias_mode == GP_BIAS_COL ? p.bias : nullptr, p.res, p.ldres, p.act, (h16_t*)p.out, p.ldo, p.out_fp32 == 1 ? 1 : 0);
-            return;
-        }
+        IGemmParams q = p;
+        q.out = ws; q.out_fp32 = 1; q.ldo = p.n_store; q.bias = nullptr; q.bias_mode = GP_BIAS_NONE; q.res = nullptr; q.act = GP_ACT_NONE;
+        q.stats_out = nullptr; q.ksplit = S; q.split_bs = (long long)slice;
+        launch_cfg<64, 64, 2, 2, 3>(q, s);
+        const long long total = (long long)p.M * (p.n_store >> 2);
+        int blocks = (int)((total + 255) / 256);
+        if (blocks > 2048) blocks = 2048;
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, ws, S, (long long)slice, p.M, p.N, p.n_store,
+                           p.bias_mode == GP_BIAS_COL ? p.bias : nullptr, p.res, p.ldres, p.act, (h16_t*)p.out, p.ldo, p.out_fp32 == 1 ? 1 : 0);
+        return;
     }
     const int cfg = select_cfg(p, tile_hint);
     if (cfg == 1) launch_cfg<128, 128, 2, 2, 2>(p, s);

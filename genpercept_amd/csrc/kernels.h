@@ -111,6 +111,11 @@ void launch_conv_halo(const IGemmParams& p, hipStream_t s);
 bool conv_uses_halo(const IGemmParams& p, int tile_hint);
 bool conv_halo_uses_phases(const IGemmParams& p);   // the x2-upsample conv will run as four phase convolutions (p.wt_ph set, exact x2, plain input)
 int conv_halo_stat_rows(const IGemmParams& p);     // > 0: statistics rows per image (per-workgroup partials + pixel counts, mode 2)
+int conv_halo_tile_rows(const IGemmParams& p);     // 16 / 12: rows per tile of the persistent halo kernel; 0: the per-tile halo2 kernel
+// the kernel launch_igemm(p, tile_hint) runs (igemm_path; the values are what gp_c_conv2d reports in *path_out)
+enum { IGEMM_PATH_HALO_16ROW = 1, IGEMM_PATH_HALO_PHASES = 2, IGEMM_PATH_PGEMM = 3, IGEMM_PATH_CONV_IMG = 4, IGEMM_PATH_SPLITK = 5, IGEMM_PATH_IGEMM = 6,
+       IGEMM_PATH_HALO_12ROW = 7, IGEMM_PATH_HALO_TILES = 8 };
+int igemm_path(const IGemmParams& p, int tile_hint);
 // Statistics layout launch_igemm(p, tile_hint) will write: mode 0 = rows of BM consecutive pixels, mode 1 = 16x16 halo tiles per image,
 // mode 2 = *bm rows per image, each with its own pixel count appended after the [rows][N][2] sums; returns the number of rows (callers
 // allocate rows * (2 N + 1) floats), or 0 when that kernel path cannot produce stats_out (direct epilogue, GEGLU, fp32 output, ...).
@@ -209,8 +214,10 @@ void launch_quantize(const float* x, void* q, long long n, int bits, hipStream_t
 // A order [hi | lo | hi], B order [hi | hi | lo] over a tripled K).  Split tensors have 3 * C elements per row.
 void launch_c_split3(const float* x, int ldx, h16_t* out, long long rows, int C, int b_order, int act, float scale, hipStream_t s);
 void launch_c_rgb_split(const void* rgb, int is_u8, h16_t* out, int B, int H, int W, hipStream_t s);  // -> [B*H*W][192]
-int c_gn_stat_rows(int HW, int C, int* bm_out);  // statistics rows per image of launch_c_gn_stats ("mode 2" partials: B * R * (2 C + 1) floats)
+int c_gn_stat_rows(int HW, int C, int* bm_out);  // statistics rows per image of launch_c_gn_stats ("mode 3" partials: B * R * (2 C + 1) floats)
 void launch_c_gn_stats(const float* x, float* part, int B, int HW, int C, hipStream_t s);
+void launch_c_groupnorm_scale_shift(const float* x, float* part, int B, int H, int W, int C, int G, float eps, const float* gamma, const float* beta,
+                                    float* scale, float* shift, hipStream_t s);
 void launch_c_gn_apply_split(const float* x, h16_t* out, const float* scale, const float* shift, int B, int HW, int C, int silu, hipStream_t s);
 void launch_c_layernorm_split(const float* x, h16_t* out, const float* gamma, const float* beta, int rows, int C, float eps, hipStream_t s);
 void launch_c_concat(const float* a, int Ca, const float* b, int Cb, float* out, long long pixels, hipStream_t s);

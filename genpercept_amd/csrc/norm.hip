@@ -396,7 +396,9 @@ void launch_groupnorm(const h16_t* x, h16_t* y, const float* gamma, const float*
 
 // ---- scale/shift from the per-(pixel tile, channel) partials a conv epilogue wrote (IGemmParams::stats_out) --------------------
 // One workgroup per (group, image): 256 threads walk the group's (tile, channel) partials in a fixed order; tile pixel counts
-// come from the tiling (mode 0: bm consecutive rows; mode 1: 16x16 tiles clipped at the image edge); Chan-combined variance.
+// come from the tiling (mode 0: bm consecutive rows; mode 1: 16x16 tiles clipped at the image edge; mode 2: bm rows per image with their
+// counts stored after the partials); Chan-combined variance.  Partials are {sum, sum of squares} in modes 0-2; mode 3 has mode 2's layout
+// with {sum, CENTRED second moment} partials (contract.hip: c_gn_stats_kernel), free of the qk - sk * mk cancellation.
 __global__ __launch_bounds__(256) void gn_finalize_tiles_kernel(const float* __restrict__ part, int mode, int bm, int H, int W, int C, int G,
                                                                  float eps, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                  float* __restrict__ scale, float* __restrict__ shift) {
@@ -405,6 +407,8 @@ __global__ __launch_bounds__(256) void gn_finalize_tiles_kernel(const float* __r
     const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int cpg = C / G;
     const int tiles_x = (W + 15) >> 4, tiles_y = (H + 15) >> 4;
+    const bool centred = mode == 3;
+    if (centred) mode = 2;
     const int ntile = mode == 2 ? bm : mode ? tiles_x * tiles_y : (H * W) / bm;
     const float* pb = part + (long long)b * ntile * C * 2;
     const float* cnt = part + (long long)gridDim.y * ntile * C * 2 + (long long)b * ntile;  // mode 2: pixel count of every row
@@ -431,7 +435,7 @@ __global__ __launch_bounds__(256) void gn_finalize_tiles_kernel(const float* __r
         const int t = i / cpg, c = g * cpg + (i - t * cpg);
         const float nk = tile_px(t), sk = pb[((long long)t * C + c) * 2], qk = pb[((long long)t * C + c) * 2 + 1];
         const float mk = sk / nk;
-        m2 += fmaxf(qk - sk * mk, 0.f) + nk * (mk - mean) * (mk - mean);
+        m2 += (centred ? qk : fmaxf(qk - sk * mk, 0.f)) + nk * (mk - mean) * (mk - mean);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m2 += __shfl_xor(m2, o);

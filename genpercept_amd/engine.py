@@ -131,6 +131,13 @@ SYMBOLS = {
     "gp_layernorm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "gp_flash_attention": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "gp_flash_attention_split": (_i, [_vp, _i, _vp, _i, _i, _i, _vp]),
+    "gp_c_split3": (_i, [_vp, _i, _vp, _ll, _i, _i, _i, _f, _vp]),
+    "gp_c_groupnorm_split": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
+    "gp_pack_weight_split": (_i, [_vp, _i, _i, _i, _i, _i, _vp]),
+    "gp_pack_weight_phases_split": (_i, [_vp, _i, _i, _i, _vp]),
+    "gp_c_conv2d": (_i, [_vp] * 6 + [_i] * 14 + [_vp, _vp, _i, _f, _vp, _vp, C.POINTER(_i), _vp]),
+    "gp_c_layernorm_split": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
+    "gp_c_softmax_split": (_i, [_vp, _vp, _i, _i, _i, _f, _vp]),
     "gp_flash_attention_hd512": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "gp_cross_attention": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "gp_resize_max_res_size": (None, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
@@ -637,6 +644,98 @@ def flash_attention_split(qkv: torch.Tensor, batch: int, tokens: int, heads: int
         raise RuntimeError(f"gp_flash_attention_split failed ({st})")
     assert torch.equal(out[:, :c], out[:, 2 * c:])  # [hi | lo | hi]
     return out[:, :c].float() + out[:, c:2 * c].float()
+
+
+# ---- contract precision (bf16 library): split operands are bf16 [rows][3 C], A order [hi | lo | hi], B order [hi | hi | lo] ----------------------
+def _c_check(st: int, name: str):
+    if st != GP_OK:
+        raise RuntimeError(f"{name} failed ({st})")
+
+
+def c_split3(x: torch.Tensor, b_order: bool = False, act: str = "none", scale: float = 1.0) -> torch.Tensor:
+    """fp32 [rows, C] (row stride may exceed C) -> split bf16 [rows, 3C] of act(x * scale) (gp_c_split3)."""
+    lib = load_library("bf16")
+    rows, c = x.shape
+    out = torch.empty((rows, 3 * c), dtype=torch.bfloat16, device=x.device)
+    _c_check(lib.gp_c_split3(x.data_ptr(), x.stride(0), out.data_ptr(), rows, c, int(b_order), ACT[act], float(scale), _stream_ptr(x.device)), "gp_c_split3")
+    return out
+
+
+def c_groupnorm_split(x_nhwc: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, eps: float, silu: bool = False):
+    """fp32 NHWC [B,H,W,C] -> (split bf16 [B,H,W,3C] of act(GroupNorm(x)), scale [B,C], shift [B,C]) (gp_c_groupnorm_split)."""
+    lib = load_library("bf16")
+    b, h, w, c = x_nhwc.shape
+    out = torch.empty((b, h, w, 3 * c), dtype=torch.bfloat16, device=x_nhwc.device)
+    sc = torch.empty((b, c), dtype=torch.float32, device=x_nhwc.device)
+    sh = torch.empty_like(sc)
+    _c_check(lib.gp_c_groupnorm_split(x_nhwc.data_ptr(), out.data_ptr(), gamma.data_ptr(), beta.data_ptr(), b, h * w, c, groups, float(eps), int(silu),
+                                      sc.data_ptr(), sh.data_ptr(), _stream_ptr(x_nhwc.device)), "gp_c_groupnorm_split")
+    return out, sc, sh
+
+
+def pack_weight_split(w: torch.Tensor, geglu: bool = False, device="cuda") -> torch.Tensor:
+    """OIHW (or [out, in]) fp32 -> B-order split packing [rows, taps, 3 cin_pad] (gp_pack_weight_split)."""
+    lib = load_library("bf16")
+    w = w.detach().float().cpu().contiguous()
+    if w.dim() == 2:
+        w = w[:, :, None, None]
+    cout, cin, ks, _ = w.shape
+    cp = (cin + 63) // 64 * 64
+    out = torch.empty((lib.gp_packed_rows(cout), ks * ks, 3 * cp), dtype=torch.bfloat16, device=device)
+    _c_check(lib.gp_pack_weight_split(w.data_ptr(), cout, cin, ks, cp, int(geglu), out.data_ptr()), "gp_pack_weight_split")
+    return out
+
+
+def pack_weight_phases_split(w: torch.Tensor, device="cuda") -> torch.Tensor:
+    lib = load_library("bf16")
+    w = w.detach().float().cpu().contiguous()
+    cout, cin = w.shape[:2]
+    cp = (cin + 63) // 64 * 64
+    out = torch.empty((lib.gp_packed_rows(cout), 16, 3 * cp), dtype=torch.bfloat16, device=device)
+    _c_check(lib.gp_pack_weight_phases_split(w.data_ptr(), cout, cin, cp, out.data_ptr()), "gp_pack_weight_phases_split")
+    return out
+
+
+def c_conv2d(x_split: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], cout: int, ks: int, stride: int = 1, pad=(1, 1), out_hw=None,
+             ups: bool = False, w_phases: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, act: str = "none", tile: int = 0,
+             out: Optional[torch.Tensor] = None, gn=None):
+    """contract-precision conv / linear (gp_c_conv2d): split NHWC [B,Hi,Wi,3 Cin] -> fp32 [B,Ho,Wo,N].  `out` may be `residual` (in place).
+    gn = (gamma, beta, groups, eps): also the GroupNorm scale / shift of the output.  Returns (y, path, scale, shift)."""
+    lib = load_library("bf16")
+    b, hi, wi, c3 = x_split.shape
+    ho, wo = out_hw if out_hw else ((2 * hi, 2 * wi) if ups else (hi, wi))
+    nout = cout // 2 if act == "geglu" else cout
+    if out is None:
+        out = torch.empty((b, ho, wo, nout), dtype=torch.float32, device=x_split.device)
+    path = C.c_int(0)
+    sc = sh = None
+    g = (None, None, 0, 0.0)
+    if gn is not None:
+        sc = torch.empty((b, nout), dtype=torch.float32, device=x_split.device)
+        sh = torch.empty_like(sc)
+        g = gn
+    _c_check(lib.gp_c_conv2d(x_split.data_ptr(), w_packed.data_ptr(), _ptr(w_phases), _ptr(bias), _ptr(residual), out.data_ptr(), b, hi, wi, c3 // 3, cout,
+                             ks, stride, pad[0], pad[1], ho, wo, int(ups), ACT[act], tile, _ptr(g[0]), _ptr(g[1]), int(g[2]), float(g[3]), _ptr(sc), _ptr(sh),
+                             C.byref(path), _stream_ptr(x_split.device)), "gp_c_conv2d")
+    return out, path.value, sc, sh
+
+
+def c_layernorm_split(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
+    lib = load_library("bf16")
+    rows, c = x.shape
+    out = torch.empty((rows, 3 * c), dtype=torch.bfloat16, device=x.device)
+    _c_check(lib.gp_c_layernorm_split(x.data_ptr(), out.data_ptr(), gamma.data_ptr(), beta.data_ptr(), rows, c, float(eps), _stream_ptr(x.device)),
+             "gp_c_layernorm_split")
+    return out
+
+
+def c_softmax_split(x: torch.Tensor, tokens: int, scale: float) -> torch.Tensor:
+    """fp32 logits [rows, ld] (first `tokens` valid) -> split probabilities bf16 [rows, 3 ld] (gp_c_softmax_split)."""
+    lib = load_library("bf16")
+    rows, ld = x.shape
+    out = torch.empty((rows, 3 * ld), dtype=torch.bfloat16, device=x.device)
+    _c_check(lib.gp_c_softmax_split(x.data_ptr(), out.data_ptr(), rows, tokens, ld, float(scale), _stream_ptr(x.device)), "gp_c_softmax_split")
+    return out
 
 
 def cross_attention(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor) -> torch.Tensor:

@@ -256,8 +256,33 @@ gp_status gp_flash_attention(const void* q, const void* k, const void* vt, void*
 /* Contract precision (gp_set_precision; csrc/contract.hip, attention.hip: flash_attn64_split_kernel): the UNet's self-attention core over SPLIT operands.
  * qkv: DEVICE fp32 [B*T][ld] with q | k | v at columns 0 | C | 2C (C = heads * 64; the output of the stacked attn1.to_q / to_k / to_v projection);
  * out_split: DEVICE 16-bit [B*T][3C] = the A-order split operand [hi | lo | hi] of softmax(q k^T / 8) v that the output projection reads (value = hi + lo).
- * bf16 library only.  Synchronises the stream (test entry point). */
+ * ld % 4 == 0 and 16-byte aligned qkv / out_split (GP_ERR_INVALID otherwise).  bf16 library only.  Synchronises the stream (test entry point). */
 gp_status gp_flash_attention_split(const float* qkv, int ld, void* out_split, int B, int T, int heads, void* stream);
+/* ---- contract-precision test entry points (bf16 library only; GP_ERR_INVALID from the fp16 library) -------------------------------------------
+ * The launchers the engine's contract path uses (csrc/contract.hip), with every argument checked on the host first: fp32 rows with ld % 4 == 0,
+ * 16-byte aligned pointers.  A "split" operand is 16-bit [rows][3 C]: A order [hi | lo | hi], B order [hi | hi | lo], hi = bf16(x), lo = bf16(x - hi).
+ * gp_c_split3: out = split(act(x * scale)) (act: none or ReLU, the engine's split_operand).
+ * gp_c_groupnorm_split: GroupNorm(G, eps) (+ SiLU) of fp32 NHWC x [B][HW][C] -> A-order split out; the centred statistics pass and the finaliser
+ *   also leave the affine form in scale_out / shift_out [B][C] (DEVICE fp32): y = x * scale + shift.
+ * gp_pack_weight_split / gp_pack_weight_phases_split: gp_pack_weight / gp_pack_weight_phases in B order (3 cin_pad elements per tap).
+ * gp_c_conv2d: conv (3x3 or 1x1, stride 1 or 2, optional nearest x2 upsample with the phase packing in w_phases) or linear (ks = 1; act may be
+ *   GEGLU) on an A-order split input [B][Hi][Wi][3 Cin], fp32 out [B][Ho][Wo][Cout or Cout / 2] (+ bias, + fp32 residual; residual may be out);
+ *   with gamma non-null also the GroupNorm scale / shift of the output as the engine computes them.  The launch parameters are the engine's own
+ *   (conv_c; linear_c for ks = 1 without stride / upsample).  path_out (optional) reports the kernel launch_igemm dispatched to: 1 halo conv
+ *   with 16-row tiles, 2 halo phase conv, 3 persistent GEMM, 4 conv_img + split-K reduce, 5 split-K igemm + reduce, 6 igemm, 7 halo conv with
+ *   12-row tiles, 8 per-tile halo conv.
+ * gp_c_layernorm_split: LayerNorm over the last dim of fp32 [rows][C] -> A-order split.
+ * gp_c_softmax_split: row softmax of scale * x over the first T of ld columns -> A-order split probabilities [rows][3 ld] (zero beyond T). */
+gp_status gp_c_split3(const float* x, int ldx, void* out, long long rows, int C, int b_order, int act, float scale, void* stream);
+gp_status gp_c_groupnorm_split(const float* x, void* out, const float* gamma, const float* beta, int B, int HW, int C, int G, float eps, int silu,
+                               float* scale_out, float* shift_out, void* stream);
+gp_status gp_pack_weight_split(const float* w_oihw_host, int cout, int cin, int ks, int cin_pad, int geglu, void* dev_out);
+gp_status gp_pack_weight_phases_split(const float* w_oihw_host, int cout, int cin, int cin_pad, void* dev_out);
+gp_status gp_c_conv2d(const void* in_split, const void* w_packed, const void* w_phases, const float* bias, const float* residual, float* out, int B,
+                      int Hi, int Wi, int Cin, int Cout, int ks, int stride, int pad_t, int pad_l, int Ho, int Wo, int ups, int act, int tile_hint,
+                      const float* gamma, const float* beta, int groups, float eps, float* scale_out, float* shift_out, int* path_out, void* stream);
+gp_status gp_c_layernorm_split(const float* x, void* out, const float* gamma, const float* beta, int rows, int C, float eps, void* stream);
+gp_status gp_c_softmax_split(const float* in, void* out, int rows, int T, int ld, float scale, void* stream);
 /* The VAE mid-block attention's core (one head, head_dim 512; diffusers Attention inside AutoencoderKL, call sites
  * genpercept_pipeline.py:500-501,521-522), fused: softmax(scale * q k^T) v with scores and probabilities kept on the CU.  q, k: [B][T][ld]
  * (512 channels), vt: [B][512][Tpad] zero beyond T, out [B][T][ldo].  ncu: persistent workgroups to size the launch for (0 = the device's CU

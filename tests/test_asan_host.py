@@ -44,6 +44,24 @@ assert lib.gp_latent_size(768) == 96 and lib.gp_dpt_out_size(96) == 768 and lib.
 # argument checks
 assert lib.gp_create(None, None) != 0
 assert lib.gp_get_timings(None, None) != 0 and lib.gp_reset_timings(None) != 0 and lib.gp_get_launch_log(None, None, 0) == -1
+# the contract-precision entries reject a row stride that is not a multiple of 4 floats and pointers that are not 16-byte aligned on the
+# host, before anything is launched (the kernels issue float4 loads): the addresses below are never dereferenced
+A16, A8 = C.c_void_p(1 << 20), C.c_void_p((1 << 20) + 8)
+INV = 1  # GP_ERR_INVALID
+assert lib.gp_flash_attention_split(A16, 3 * 64 + 2, A16, 1, 64, 1, None) == INV
+assert lib.gp_flash_attention_split(A8, 3 * 64, A16, 1, 64, 1, None) == INV
+assert lib.gp_flash_attention_split(A16, 3 * 64, A8, 1, 64, 1, None) == INV
+assert lib.gp_c_split3(A16, 66, A16, 4, 64, 0, 0, 1.0, None) == INV and lib.gp_c_split3(A8, 64, A16, 4, 64, 0, 0, 1.0, None) == INV
+assert lib.gp_c_split3(A16, 64, A16, 4, 60, 0, 0, 1.0, None) == INV and lib.gp_c_split3(A16, 64, A16, 4, 64, 2, 0, 1.0, None) == INV
+assert lib.gp_c_split3(A16, 64, A16, 4, 64, 0, 1, 1.0, None) == INV  # SiLU: not an act the engine splits with
+assert lib.gp_c_groupnorm_split(A8, A16, A16, A16, 1, 64, 64, 32, 1e-6, 0, A16, A16, None) == INV
+assert lib.gp_c_groupnorm_split(A16, A16, A16, A16, 1, 64, 64, 30, 1e-6, 0, A16, A16, None) == INV
+assert lib.gp_c_layernorm_split(A16, A16, A8, A16, 4, 64, 1e-5, None) == INV
+assert lib.gp_c_softmax_split(A16, A16, 4, 70, 70, 0.125, None) == INV and lib.gp_c_softmax_split(A16, A16, 4, 80, 72, 0.125, None) == INV
+_path = C.c_int(0)
+_conv = lambda x, res, cin, ks, act: lib.gp_c_conv2d(x, A16, None, None, res, A16, 1, 8, 8, cin, 64, ks, 1, 1, 1, 8, 8, 0, act, 0,
+                                                     None, None, 0, 0.0, None, None, C.byref(_path), None)
+assert _conv(A8, None, 64, 3, 0) == INV and _conv(A16, A8, 64, 3, 0) == INV and _conv(A16, None, 96, 3, 0) == INV and _conv(A16, None, 64, 3, 3) == INV
 hdl = C.c_void_p()
 cfg.device = 0
 st = lib.gp_create(C.byref(cfg), C.byref(hdl))
