@@ -4,13 +4,20 @@ decoder) at 768x768, bf16 elements / fp32 accumulate, batch 4 per GPU, synthetic
 of the exact SD2.1 architecture (BASELINE.json configs[1]; no checkpoints exist offline).
 
   python bench.py --gpus 1 --steps 5 --warmup 2
-  python bench.py --gpus 8 ...                     # spawns its own 8 ranks (re-executes itself under torch.distributed.run)
+  python bench.py --gpus 1 --steps 5 --warmup 2 --full   # + the other precisions, profiles, roofline, CPU baseline and parity
+  python bench.py --gpus 8 ...                           # spawns its own 8 ranks (re-executes itself under torch.distributed.run)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one batch per GPU (gp_infer).  N > 1: one process per GPU, the batch of N*B
 independent images is sharded contiguously, weights replicated, no collective on the data path ("weak" scaling); the step
 then ends with the optional result gather of BASELINE.json configs[4] (RCCL gather of the fp32 maps to rank 0 over xGMI),
-inside the timed region, its own cost reported as `gather_ms`.  Rank 0 prints ONE JSON line.
+inside the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: it builds the engine of --precision, runs the warm-up and the timed steps,
+writes the maps of --dump-outputs when it is given and prints the line (`value`, `ms_per_step`, per-step min / median / max,
+`clock_power`).  Everything else runs only with --full, each part still switchable off by its --no-* option, and is null
+(or absent) in a plain line:
+  gather_ms    N > 1: the result gather alone (same tensors, 5 calls), max over ranks.
   roofline     the dominant kernel, conv3x3_halo3_kernel: algorithmic flops of its launches / their summed duration, from HIP events
                on the engine's stream in an instrumented pass right after the timed region (events around ~300 launches would perturb
                the timed region itself); `family_*` = the whole implicit-GEMM conv / linear family; `peak` = the nominal 2.5 PFLOP/s,
@@ -23,11 +30,15 @@ inside the timed region, its own cost reported as `gather_ms`.  Rank 0 prints ON
                1e-3 under both readings); `within_1e-3` = {precision: {mean_abs, rel_rms}} (same K steps, same barriers for each leg).
   stages       per-stage times from a pass with FOUR events only (profiling level 1); the per-kernel sums of `roofline` come from a second,
                per-launch-instrumented pass whose ~500 event pairs cost ~7 % and must not leak into `unet_mfma_util`.
+  value_fp16, value_fp32c
+               N = 1, --precision bf16: the fp16 library and the contract precision, each built and timed like the headline leg.
 
 --dump-outputs DIR writes, on rank 0, the maps each timed leg returned in its LAST timed step as DIR/<mode>_<precision>.npy (float32, [B,C,H,W];
 rank 0's shard, or the gathered batch when N > 1).  Inputs, weights and context are seeded, so two builds run with the same arguments can be
 compared array for array.  The files hold at most DUMP_BUDGET_BYTES together: a leg whose map exceeds its equal share is stored as a fixed,
-seeded sample (flat indices torch.randperm(numel, seed DUMP_SEED)[:k], sorted; 1-D).
+seeded sample (flat indices torch.randperm(numel, seed DUMP_SEED)[:k], sorted; 1-D).  The set of legs, and so of files, does not depend on
+--full: a plain run with --dump-outputs also runs the fp16 and contract-precision legs (same warm-up and steps) for their maps, and reports
+nothing of them in its line.
 """
 import argparse
 import contextlib
@@ -241,10 +252,13 @@ def main(argv=None, engine_factory=None, device=None):
                     help="precision of the benched engine (bf16 = BASELINE.json's dtype; fp16 = the reference's --half_precision; fp32c = the contract "
                          "precision: fp32 storage + split-bf16 matrix products, what torch_dtype=float32 selects)")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: leave the result maps on their GPUs")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-fp16", action="store_true", help="skip the second timed leg with the fp16 library")
-    ap.add_argument("--no-fp32c", action="store_true", help="skip the third timed leg with the contract precision (fp32 storage, split-bf16 products)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline (module docstring): gather_ms, the profiled passes (stages, roofline), "
+                         "the fp16 and contract-precision legs, the CPU oracle baseline and parity; the --no-* options below drop single parts")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU oracle baseline and parity")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the profiled passes (stages, roofline, measured MFMA peaks)")
+    ap.add_argument("--no-fp16", action="store_true", help="skip the second timed leg with the fp16 library (--full, or --dump-outputs: its map)")
+    ap.add_argument("--no-fp32c", action="store_true", help="skip the third timed leg with the contract precision (fp32 storage, split-bf16 products; --full, or --dump-outputs: its map)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write each timed leg's last-step maps as DIR/<mode>_<precision>.npy (float32, <= 64 MB in all; see the module docstring)")
     args = ap.parse_args(argv)
@@ -331,16 +345,16 @@ def main(argv=None, engine_factory=None, device=None):
     ms_per_step = elapsed / args.steps * 1e3
     images = n_total * args.steps
     value = images / elapsed
-    out0 = out[0].float().cpu() if (out is not None and rank == 0) else None  # image 0 of the benched batch: the parity sample
+    out0 = out[0].float().cpu() if (args.full and out is not None and rank == 0) else None  # image 0 of the benched batch: the parity sample
 
     gather_ms = None
-    if do_gather:  # the gather alone (same tensors), max over ranks
+    if do_gather and args.full:  # the gather alone (same tensors), max over ranks
         loc = eng.infer(rgb, args.mode)
         gather_ms = round(timed_steps(lambda: gd.gather_results(loc, n_total, dst=0), 0, 5, dev)[0] / 5 * 1e3, 3)
 
     roofline = None
     stages = None
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         eng.set_profile(1)  # four events per pass: the stage times are not perturbed by per-launch instrumentation
         eng.reset_timings()
         eng.infer(rgb, args.mode)
@@ -441,52 +455,56 @@ def main(argv=None, engine_factory=None, device=None):
     # ---- second timed leg: the fp16 library (the build that meets north_star's 1e-3), same steps / barriers ---------------------------
     fp16 = None
     out0_f16 = None
-    if args.precision == "bf16" and not args.no_fp16 and n_gpus == 1:  # (N > 1 measures scaling of the headline dtype only: no second engine build per rank)
+    # a plain run with --dump-outputs runs the fp16 and contract-precision legs too, for their maps alone: the dumped set does not depend on --full
+    other_legs = args.precision == "bf16" and n_gpus == 1 and (args.full or args.dump_outputs is not None)
+    if other_legs and not args.no_fp16:  # (N > 1 measures scaling of the headline dtype only: no second engine build per rank)
         eng.close()
         eng = build_engine("fp16")
         el16, o16 = timed(eng, "fp16")
-        if o16 is not None and rank == 0:
-            out0_f16 = o16[0].float().cpu()
-        fp16 = {"value_fp16": round(images / el16, 3), "ms_per_step_fp16": round(el16 / args.steps * 1e3, 3),
-                "ms_per_step_fp16_min": timed.stats.get("ms_per_step_min"), "ms_per_step_fp16_median": timed.stats.get("ms_per_step_median")}
-        if rank == 0 and dev.type == "cuda":  # the chip's own back-to-back-MFMA rate with fp16 operands (the bf16 figure is roofline.peak_measured): same instruction
-            pk16 = ge.mfma_peak_tflops(local_rank, "fp16")  # count, lower sustained clock -- the guide's micro-benchmarks show the same 6-9 % gap
-            fp16["peak_measured_fp16"] = round(pk16, 1) if pk16 and pk16 > 0 else None
-        if not args.no_profile:
-            eng.set_profile(1)
-            eng.reset_timings()
-            eng.infer(rgb, args.mode)
-            t16 = eng.timings()
-            eng.set_profile(0)
-            fp16["stages_fp16"] = {"ms_encode": round(t16["ms_encode"], 3), "ms_unet": round(t16["ms_unet"], 3), "ms_head": round(t16["ms_head"], 3)}
+        if args.full:
+            if o16 is not None and rank == 0:
+                out0_f16 = o16[0].float().cpu()
+            fp16 = {"value_fp16": round(images / el16, 3), "ms_per_step_fp16": round(el16 / args.steps * 1e3, 3),
+                    "ms_per_step_fp16_min": timed.stats.get("ms_per_step_min"), "ms_per_step_fp16_median": timed.stats.get("ms_per_step_median")}
+            if rank == 0 and dev.type == "cuda":  # the chip's own back-to-back-MFMA rate with fp16 operands (the bf16 figure is roofline.peak_measured): same instruction
+                pk16 = ge.mfma_peak_tflops(local_rank, "fp16")  # count, lower sustained clock -- the guide's micro-benchmarks show the same 6-9 % gap
+                fp16["peak_measured_fp16"] = round(pk16, 1) if pk16 and pk16 > 0 else None
+            if not args.no_profile:
+                eng.set_profile(1)
+                eng.reset_timings()
+                eng.infer(rgb, args.mode)
+                t16 = eng.timings()
+                eng.set_profile(0)
+                fp16["stages_fp16"] = {"ms_encode": round(t16["ms_encode"], 3), "ms_unet": round(t16["ms_unet"], 3), "ms_head": round(t16["ms_head"], 3)}
 
     # ---- third timed leg: the CONTRACT precision (gp_set_precision(GP_PREC_CONTRACT): fp32 storage, split-bf16 matrix products -- three MFMAs
     # per product), the build torch_dtype=float32 selects and the one inside north_star's 1e-3 under BOTH readings; same steps / barriers -------
     fp32c = None
     out0_c = None
-    if args.precision == "bf16" and not args.no_fp32c and n_gpus == 1:
+    if other_legs and not args.no_fp32c:
         eng.close()
         eng = build_engine("fp32c")
         elc, oc = timed(eng, "fp32c")
-        if oc is not None and rank == 0:
-            out0_c = oc[0].float().cpu()
-        fp32c = {"value_fp32c": round(images / elc, 3), "ms_per_step_fp32c": round(elc / args.steps * 1e3, 3),
-                 "ms_per_step_fp32c_min": timed.stats.get("ms_per_step_min"), "ms_per_step_fp32c_median": timed.stats.get("ms_per_step_median")}
-        if not args.no_profile:
-            eng.set_profile(1)
-            eng.reset_timings()
-            eng.infer(rgb, args.mode)
-            tc = eng.timings()
-            eng.set_profile(0)
-            fp32c["stages_fp32c"] = {"ms_encode": round(tc["ms_encode"], 3), "ms_unet": round(tc["ms_unet"], 3), "ms_head": round(tc["ms_head"], 3)}
-            # useful (algorithmic) flops per second of the whole pass; the matrix cores execute three times that in this precision
-            sc = (args.res / 768.0) ** 2 * ((TFLOP_PER_IMAGE_768_DPT / TFLOP_PER_IMAGE_768) if dpt else 1.0)
-            fp32c["pipeline_achieved_fp32c"] = round(TFLOP_PER_IMAGE_768 * sc * args.batch / (elc / args.steps), 2)
-            fp32c["pipeline_executed_frac_fp32c"] = round(3.0 * TFLOP_PER_IMAGE_768 * sc * args.batch / (elc / args.steps) / PEAK_BF16_TFLOPS, 4)
+        if args.full:
+            if oc is not None and rank == 0:
+                out0_c = oc[0].float().cpu()
+            fp32c = {"value_fp32c": round(images / elc, 3), "ms_per_step_fp32c": round(elc / args.steps * 1e3, 3),
+                     "ms_per_step_fp32c_min": timed.stats.get("ms_per_step_min"), "ms_per_step_fp32c_median": timed.stats.get("ms_per_step_median")}
+            if not args.no_profile:
+                eng.set_profile(1)
+                eng.reset_timings()
+                eng.infer(rgb, args.mode)
+                tc = eng.timings()
+                eng.set_profile(0)
+                fp32c["stages_fp32c"] = {"ms_encode": round(tc["ms_encode"], 3), "ms_unet": round(tc["ms_unet"], 3), "ms_head": round(tc["ms_head"], 3)}
+                # useful (algorithmic) flops per second of the whole pass; the matrix cores execute three times that in this precision
+                sc = (args.res / 768.0) ** 2 * ((TFLOP_PER_IMAGE_768_DPT / TFLOP_PER_IMAGE_768) if dpt else 1.0)
+                fp32c["pipeline_achieved_fp32c"] = round(TFLOP_PER_IMAGE_768 * sc * args.batch / (elc / args.steps), 2)
+                fp32c["pipeline_executed_frac_fp32c"] = round(3.0 * TFLOP_PER_IMAGE_768 * sc * args.batch / (elc / args.steps) / PEAK_BF16_TFLOPS, 4)
 
     cpu = None
     parity = None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu and not dpt:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu and not dpt:
         from oracle import pipeline as opipe  # CPU baseline leg only: the oracle is the checker and the reported baseline, never the product
         from oracle import sd21 as osd
         nthr = max(1, min(os.cpu_count(), args.cpu_threads))

@@ -615,14 +615,15 @@ class StubEngine:                      # stands in for genpercept_amd.engine.Eng
 
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
-    line = bench.main(["--gpus", "2", "--steps", "3", "--warmup", "1", "--res", "32", "--no-cpu", "--no-profile", "--no-fp16"],
-                      engine_factory=StubEngine, device="cpu")
+    line = bench.main(["--gpus", "2", "--steps", "3", "--warmup", "1", "--res", "32"] + {extra!r}, engine_factory=StubEngine, device="cpu")
 rank = int(os.environ["RANK"])
-ok = StubEngine.calls == 1 + 3 + 1        # warm-up + timed steps + the gather-alone leg's one infer
+full = "--full" in {extra!r}
+ok = StubEngine.calls == 1 + 3 + full     # warm-up + timed steps (+ with --full the gather-alone leg's one infer)
 if rank == 0:
     printed = json.loads(buf.getvalue().strip().splitlines()[-1])
     ok = ok and printed == line and line["n_gpus"] == 2 and line["steps"] == 3 and line["warmup"] == 1 and line["scaling"] == "weak"
-    ok = ok and line["config"]["global_batch"] == 8 and line["config"]["gather_ms"] is not None and line["config"]["gather_ms"] >= 0
+    g = line["config"]["gather_ms"]
+    ok = ok and line["config"]["global_batch"] == 8 and ((g is not None and g >= 0) if full else g is None)
     ok = ok and abs(line["value"] - 8 * 3 / (line["ms_per_step"] * 3e-3)) <= 1e-2 * line["value"] and line["higher_is_better"] is True
 else:
     ok = ok and line is None and buf.getvalue().strip() == ""   # ONE JSON line, from rank 0 only
@@ -634,7 +635,8 @@ sys.exit(0 if ok else 1)
 
 def test_bench_single_rank_precision_legs_with_a_stub_engine(capsys):
     """bench.py's N = 1 control flow around the engine -- the benched bf16 leg, then the fp16 library, then the contract precision, each timed with the same
-    steps -- executed on CPU with a stub engine: ONE JSON line carrying value / value_fp16 / value_fp32c, and no profile / parity fields when those legs are off."""
+    steps -- executed on CPU with a stub engine: ONE JSON line carrying value / value_fp16 / value_fp32c, and no profile / parity fields when those legs are off.
+    Those legs run with --full only: a plain run builds the benched engine alone and calls it for the warm-up and the timed steps, nothing more."""
     import json
     import time
     import bench
@@ -654,7 +656,23 @@ def test_bench_single_rank_precision_legs_with_a_stub_engine(capsys):
         def close(self):
             self.closed = True
 
-    line = bench.main(["--gpus", "1", "--steps", "2", "--warmup", "1", "--res", "32", "--no-cpu", "--no-profile"], engine_factory=Stub, device="cpu")
+    engines = []
+
+    class Counted(Stub):
+        def __init__(self, local_rank, precision):
+            super().__init__(local_rank, precision)
+            engines.append(self)
+
+    # plain run: no --no-* option needed (the stub has no set_profile and there are no weights for the CPU oracle: either leg would raise)
+    line = bench.main(["--gpus", "1", "--steps", "2", "--warmup", "1", "--res", "32"], engine_factory=Counted, device="cpu")
+    printed = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert printed == line and built == ["bf16"] and engines[0].calls == 1 + 2 and engines[0].closed
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["dtype"] == "bf16" and line["higher_is_better"] is True
+    assert abs(line["value"] - 4 * 2 / (line["ms_per_step"] * 2e-3)) <= 1e-2 * line["value"]
+    assert line["roofline"] is None and line["stages"] is None and line["cpu_baseline"] is None and line["parity"] is None
+    assert line["config"]["gather_ms"] is None and not any(k.endswith(("_fp16", "_fp32c")) for k in line)
+    built.clear()
+    line = bench.main(["--gpus", "1", "--steps", "2", "--warmup", "1", "--res", "32", "--full", "--no-cpu", "--no-profile"], engine_factory=Stub, device="cpu")
     printed = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
     assert printed == line and built == ["bf16", "fp16", "fp32c"]
     assert line["n_gpus"] == 1 and line["dtype"] == "bf16" and line["metric"].startswith("images/sec at 768x768 bf16")
@@ -664,7 +682,8 @@ def test_bench_single_rank_precision_legs_with_a_stub_engine(capsys):
     assert abs(line["value"] - 4 * 2 / (line["ms_per_step"] * 2e-3)) <= 1e-2 * line["value"]
     # a non-default precision is labelled as such and runs no other leg
     built.clear()
-    line = bench.main(["--gpus", "1", "--steps", "1", "--warmup", "0", "--res", "32", "--no-cpu", "--no-profile", "--precision", "fp32c"], engine_factory=Stub, device="cpu")
+    line = bench.main(["--gpus", "1", "--steps", "1", "--warmup", "0", "--res", "32", "--full", "--no-cpu", "--no-profile", "--precision", "fp32c"],
+                      engine_factory=Stub, device="cpu")
     capsys.readouterr()
     assert built == ["fp32c"] and line["dtype"] == "fp32c" and "NOT BASELINE" in line["metric"] and "value_fp16" not in line and "value_fp32c" not in line
 
@@ -672,7 +691,7 @@ def test_bench_single_rank_precision_legs_with_a_stub_engine(capsys):
 def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path, capsys, monkeypatch):
     """--dump-outputs DIR: each timed leg's maps of its LAST timed step (the stub returns a new value per call) as DIR/<mode>_<precision>.npy
     float32; --steps sets the number of timed calls exactly; a map above its share of the byte budget is a fixed seeded sample, the same
-    from run to run."""
+    from run to run.  The legs, and so the files, are the same with and without --full; a plain line reports the headline leg alone."""
     import bench
 
     class Stub:
@@ -708,6 +727,12 @@ def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path, capsys, monkeyp
         assert b.shape == (1000,) and b.dtype == np.float32 and np.array_equal(b, c)
         assert line["dumped_outputs"]["arrays"][name] == {"shape": [4, 3, 16, 16], "stored": 1000, "sampled": True}
         assert np.all(np.diff(b) > 0) and b.min() >= 5 and b.max() < 6  # sorted flat indices into the last step's map
+    assert not any(k.endswith(("_fp16", "_fp32c")) for k in line) and line["stages"] is None
+    line = bench.main(argv + ["--full", "--dump-outputs", str(tmp_path / "d")], engine_factory=Stub, device="cpu")
+    capsys.readouterr()
+    assert sorted(os.listdir(tmp_path / "d")) == sorted(os.listdir(tmp_path / "b")) and line["value_fp16"] > 0 and line["value_fp32c"] > 0
+    for name in ("normal_bf16", "normal_fp16", "normal_fp32c"):
+        assert np.array_equal(np.load(tmp_path / "b" / f"{name}.npy"), np.load(tmp_path / "d" / f"{name}.npy"))
     with pytest.raises(SystemExit):
         bench.main(argv[:2] + ["--steps", "0"], engine_factory=Stub, device="cpu")
 
@@ -715,16 +740,18 @@ def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path, capsys, monkeyp
 def test_bench_multi_gpu_path_world_size_2_gloo(tmp_path):
     """bench.py's own N > 1 code (init_process_group from the torchrun environment, WORLD_SIZE == --gpus check, contiguous shards, the timed
     loop with barrier + max over ranks, the in-step result gather to rank 0, the gather-alone leg, ONE JSON line from rank 0) executed on
-    CPU with gloo and a stub engine -- VERDICT r3 item 8: that code had never run anywhere."""
-    script = tmp_path / "bench_worker.py"
-    script.write_text(_BENCH_WORKER.format(root=ROOT))
-    port = 31500 + (os.getpid() % 2000)
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           str(script)]
-    # CPU only, also on a GPU machine: with a device visible init_process_group would pick nccl and bind rank r to GPU r
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES=""))
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "<rank0:OK>" in r.stderr and "<rank1:OK>" in r.stderr, r.stdout + r.stderr
+    CPU with gloo and a stub engine -- VERDICT r3 item 8: that code had never run anywhere.  Once with --full (+ the gather-alone leg) and once
+    as a plain run (the timed steps, their in-step gather included, and nothing else)."""
+    for i, extra in enumerate((["--full", "--no-cpu", "--no-profile", "--no-fp16"], [])):
+        script = tmp_path / f"bench_worker{i}.py"
+        script.write_text(_BENCH_WORKER.format(root=ROOT, extra=extra))
+        port = 31500 + (os.getpid() % 2000) + 2 * i
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(port),
+               str(script)]
+        # CPU only, also on a GPU machine: with a device visible init_process_group would pick nccl and bind rank r to GPU r
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES=""))
+        assert r.returncode == 0, (extra, r.stdout + r.stderr)
+        assert "<rank0:OK>" in r.stderr and "<rank1:OK>" in r.stderr, r.stdout + r.stderr
     # a launcher whose WORLD_SIZE disagrees with --gpus is refused (r1 silently measured one GPU)
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], capture_output=True, text=True,

@@ -1,5 +1,6 @@
 #!/bin/bash
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out
+set -- --full "$@"  # the summary below reads `stages` and `roofline`, which only bench.py --full measures
 timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu --no-fp16 "$@" 2>&1 | tail -1 > gpurun_out/bench_quick.log
 python3 - <<'PY'
 import json
