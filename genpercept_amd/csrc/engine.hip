@@ -2162,6 +2162,7 @@ gp_status gp_dpt_head(gp_engine* e, const float* const* feats, int B, int h, int
 
 // ---- per-kernel entry points --------------------------------------------------------------------------------------
 int gp_packed_rows(int cout) { return (cout + 255) / 256 * 256; }
+int gp_last_igemm_path(int* pgemm_rows) { return igemm_last_path(pgemm_rows); }
 int gp_latent_size(int x) { for (int i = 0; i < 3; ++i) x = (x - 2) / 2 + 1; return x; }
 int gp_dpt_out_size(int latent) { for (int i = 0; i < 2; ++i) latent = (latent - 1) / 2 + 1; return 32 * latent; }
 

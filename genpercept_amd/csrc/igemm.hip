@@ -444,8 +444,19 @@ int igemm_path(const IGemmParams& p, int tile_hint) {
     return IGEMM_PATH_IGEMM;
 }
 
+// what the last launch_igemm of this host thread ran (gp_last_igemm_path: the tests pin every case to its kernel)
+static thread_local int t_last_path = 0, t_last_pgemm_bm = 0;
+int igemm_last_path(int* pgemm_rows) {
+    const int path = t_last_path;
+    if (pgemm_rows) *pgemm_rows = t_last_pgemm_bm;
+    t_last_path = t_last_pgemm_bm = 0;
+    return path;
+}
+
 void launch_igemm(const IGemmParams& p, int tile_hint, hipStream_t s) {
     const int path = igemm_path(p, tile_hint);
+    t_last_path = path;
+    t_last_pgemm_bm = path == IGEMM_PATH_PGEMM ? pgemm_bm(p) : 0;
     if (path == IGEMM_PATH_HALO_16ROW || path == IGEMM_PATH_HALO_12ROW || path == IGEMM_PATH_HALO_PHASES || path == IGEMM_PATH_HALO_TILES) {
         launch_conv_halo(p, s);
         return;

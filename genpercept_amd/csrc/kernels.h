@@ -39,7 +39,8 @@ struct IGemmParams {
     int lda, ldo, ldres;  // element strides of in (ks==1), out, res
     int ldw;              // element stride between rows of `wt` (taps*Cin for packed weights)
     int n_store;          // columns written (>= N_out; columns in [N_out, n_store) are written as 0)
-    int out_fp32;         // 1: fp32 output, 2: fp16 output (direct epilogue path)
+    int out_fp32;         // 0: 16-bit output, 1: fp32 output (fp32 residual when res_f32), 2: fp16 output;
+                          //   0 / 1 take the staged epilogue when ldo % 8 == 0 and not GEGLU, 2 always the direct one (epilogue.h)
     int act, bias_mode;
     int dbg;              // ablation bits for profiling only (1: no DMA in the loop, 2: no MFMA work, 4: no waits/barriers)
     float* splitk_ws;     // caller-owned fp32 workspace for split-K partial sums (>= igemm_ksplit() * M * n_store floats) or nullptr: no split-K
@@ -116,6 +117,7 @@ int conv_halo_tile_rows(const IGemmParams& p);     // 16 / 12: rows per tile of 
 enum { IGEMM_PATH_HALO_16ROW = 1, IGEMM_PATH_HALO_PHASES = 2, IGEMM_PATH_PGEMM = 3, IGEMM_PATH_CONV_IMG = 4, IGEMM_PATH_SPLITK = 5, IGEMM_PATH_IGEMM = 6,
        IGEMM_PATH_HALO_12ROW = 7, IGEMM_PATH_HALO_TILES = 8 };
 int igemm_path(const IGemmParams& p, int tile_hint);
+int igemm_last_path(int* pgemm_rows);  // igemm_path of this host thread's last launch_igemm (0: none since the previous call, which it clears)
 // Statistics layout launch_igemm(p, tile_hint) will write: mode 0 = rows of BM consecutive pixels, mode 1 = 16x16 halo tiles per image,
 // mode 2 = *bm rows per image, each with its own pixel count appended after the [rows][N][2] sums; returns the number of rows (callers
 // allocate rows * (2 N + 1) floats), or 0 when that kernel path cannot produce stats_out (direct epilogue, GEGLU, fp32 output, ...).

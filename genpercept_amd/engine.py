@@ -114,6 +114,7 @@ SYMBOLS = {
     "gp_saturation_events": (_i, [_vp, C.POINTER(C.c_longlong), _i]),
     "gp_get_launch_log": (_i, [_vp, C.c_char_p, _i]),
     "gp_packed_rows": (_i, [_i]),
+    "gp_last_igemm_path": (_i, [C.POINTER(_i)]),
     "gp_latent_size": (_i, [_i]),
     "gp_dpt_out_size": (_i, [_i]),
     "gp_pack_weight": (_i, [_vp, _i, _i, _i, _i, _i, _vp]),
@@ -422,6 +423,14 @@ def to_nhwc_h16(x: torch.Tensor, cpad: Optional[int] = None) -> torch.Tensor:
 
 
 to_nhwc_bf16 = to_nhwc_h16  # (name kept for the bf16-era call sites)
+
+
+def last_igemm_path():
+    """(path, pgemm row tile) of the last conv / GEMM launch of this thread (`gp_last_igemm_path`; reading clears it): 1 halo 16-row tiles,
+    2 halo phases, 3 persistent GEMM, 4 conv_img + split-K reduce, 5 split-K igemm + reduce, 6 igemm, 7 halo 12-row tiles, 8 per-tile halo."""
+    rows = C.c_int(0)
+    path = load_library().gp_last_igemm_path(C.byref(rows))
+    return int(path), int(rows.value)
 
 
 def pack_weight(w: torch.Tensor, cin_pad: Optional[int] = None, geglu: bool = False, device="cuda") -> torch.Tensor:

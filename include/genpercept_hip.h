@@ -237,6 +237,10 @@ gp_status gp_conv2d_stats(const void* in, const void* w_packed, const float* bia
 gp_status gp_gemm(const void* a, int lda, const void* bt, int ldb, const float* bias, int bias_mode, const void* residual, int ldres, void* out,
                   int ldo, int M, int N, int K, int n_rows_bt, int n_store, int act, int out_fp32 /* 0 bf16, 1 fp32, 2 fp16 */, int batch, long long a_bs, long long bt_bs,
                   long long out_bs, int tile_hint, void* stream);
+/* Test entry point: the kernel the last conv / GEMM launcher call (gp_conv2d, gp_conv2d_up2, gp_conv2d_gn, gp_conv2d_stats, gp_gemm, gp_gemm_qkv,
+ * gp_c_conv2d) of the CALLING host thread dispatched to, with the numbering of gp_c_conv2d's path_out; with the persistent GEMM (3) also its
+ * row tile (128 or 256) in *pgemm_rows (0 otherwise).  Reading clears it: 0 = no such launch since the previous call. */
+int gp_last_igemm_path(int* pgemm_rows);
 /* The VAE decoder's tail in one kernel (diffusers AutoencoderKL.decoder conv_norm_out -> SiLU -> conv_out, call site
  * genpercept_pipeline.py:521-522; channel mean :523-525; clip / shift :469-472): in NHWC [B][H][W][128] (this library's element type),
  * w_packed = gp_pack_weight(conv_out.weight [3][128][3][3]), GroupNorm(groups, eps) statistics computed here, out fp32 NCHW

@@ -64,33 +64,41 @@ def check(name, out, ref, log, fp32=False, mean_factor=1.0):
         assert mean <= mean_factor * t[1] * rmean + 1e-6, f"{name}: mean err {mean:.3e} vs ref mean {rmean:.3e}"
 
 
+def pin_path(name, want, log):
+    """the kernel the last conv / GEMM entry of this thread ran (gp_last_igemm_path: 1 halo 16-row tiles, 2 halo phases, 3 persistent GEMM,
+    4 conv_img, 5 split-K igemm, 6 igemm, 7 halo 12-row tiles, 8 per-tile halo) must be the one the case was written for"""
+    path, bm = _eng().last_igemm_path()
+    log(name + ("" if _eng().act_dtype() == torch.bfloat16 else "[fp16]"), path=path, pgemm_bm=bm)
+    assert path == want, f"{name}: kernel path {path}, expected {want}"
+
+
 def nhwc_to_nchw(y, c=None):
     y = y.float().permute(0, 3, 1, 2)
     return y if c is None else y[:, :c]
 
 
 CONV_CASES = [
-    # B, H, W, Cin, Cout, tile
-    (2, 16, 16, 64, 64, 1), (2, 16, 16, 64, 64, 2), (2, 16, 16, 64, 64, 3),
-    (1, 24, 20, 128, 320, 0), (1, 13, 15, 192, 100, 1), (3, 9, 7, 64, 3, 0), (1, 12, 12, 1280, 1280, 0), (1, 40, 36, 256, 128, 1),
-    (2, 16, 16, 64, 64, 4), (1, 40, 36, 256, 128, 4), (2, 33, 31, 128, 320, 4), (1, 96, 96, 128, 128, 0), (1, 17, 19, 64, 200, 2),
+    # B, H, W, Cin, Cout, tile, path (gp_last_igemm_path: 4 conv_img, 5 split-K igemm, 6 igemm)
+    (2, 16, 16, 64, 64, 1, 6), (2, 16, 16, 64, 64, 2, 6), (2, 16, 16, 64, 64, 3, 6),
+    (1, 24, 20, 128, 320, 0, 6), (1, 13, 15, 192, 100, 1, 6), (3, 9, 7, 64, 3, 0, 6), (1, 12, 12, 1280, 1280, 0, 5), (1, 40, 36, 256, 128, 1, 6),
+    (2, 16, 16, 64, 64, 4, 6), (1, 40, 36, 256, 128, 4, 6), (2, 33, 31, 128, 320, 4, 6), (1, 96, 96, 128, 128, 0, 6), (1, 17, 19, 64, 200, 2, 6),
     # split-K path (tiny maps, long K): 4 / 8 / 2 slices, ragged rows and columns
-    (4, 12, 12, 1280, 1280, 0), (1, 12, 12, 2560, 1280, 0), (2, 12, 12, 640, 320, 0), (1, 9, 11, 1280, 200, 2),
+    (4, 12, 12, 1280, 1280, 0, 4), (1, 12, 12, 2560, 1280, 0, 5), (2, 12, 12, 640, 320, 0, 5), (1, 9, 11, 1280, 200, 2, 5),
     # whole-image tiles (conv_img.hip): 24x24 maps (one image per 576-pixel unit) and 12x12 maps (four per unit), K slices of uneven length,
     # one and several units, odd chunk counts; (4, 12, 12, 1280, 1280, 0) above takes this path too
-    (4, 24, 24, 128, 128, 0), (1, 24, 24, 640, 64, 0), (2, 24, 24, 1280, 320, 0), (8, 12, 12, 192, 192, 0),
+    (4, 24, 24, 128, 128, 0, 4), (1, 24, 24, 640, 64, 0, 4), (2, 24, 24, 1280, 320, 0, 4), (8, 12, 12, 192, 192, 0, 4),
     # (ADVICE r3: (4, 12, 12, 64, 64) and (4, 6, 24, 320, 128) did not qualify -- one chunk per slice forces S = 1, 4 x 8 x 26 halo rows exceed
-    #  CI_HROWS_MAX -- and fell back to the generic path; kept as fall-back cases, with two shapes that DO reach conv_img: the minimum of two
+    #  CI_HROWS_MAX -- and fell back: the first to the generic path, the second to split-K igemm; kept as fall-back cases, with two shapes that DO reach conv_img: the minimum of two
     #  chunks per K slice, and a non-square map with two images per unit)
-    (4, 12, 12, 64, 64, 0), (4, 6, 24, 320, 128, 0), (4, 12, 12, 128, 64, 0), (2, 12, 24, 320, 128, 0),
+    (4, 12, 12, 64, 64, 0, 6), (4, 6, 24, 320, 128, 0, 5), (4, 12, 12, 128, 64, 0, 4), (2, 12, 24, 320, 128, 0, 4),
 ]
 
 
 @pytest.mark.parametrize("case", CONV_CASES)
 def test_conv3x3_s1(case, metric_log):
     e = _eng()
-    b, h, w, cin, cout, tile = case
-    g = torch.Generator().manual_seed(hash(case) % 1000)
+    b, h, w, cin, cout, tile, want = case
+    g = torch.Generator().manual_seed(hash(case[:6]) % 1000)
     x = rbf(torch.randn(b, cin, h, w, generator=g))
     wt = rbf(torch.randn(cout, cin, 3, 3, generator=g) / math.sqrt(cin * 9))
     bias = torch.randn(cout, generator=g)
@@ -98,7 +106,9 @@ def test_conv3x3_s1(case, metric_log):
     ref = F.conv2d(x, wt, bias, padding=1) + res
     d = _dev()
     wp = e.pack_weight(wt, device=d)
+    e.last_igemm_path()
     y = e.conv2d(e.to_nhwc_bf16(x.to(d)), wp, bias.to(d), cout, 3, residual=e.to_nhwc_bf16(res.to(d)), tile=tile)
+    pin_path(f"conv3x3_s1_path{case}", want, metric_log)
     check(f"conv3x3_s1{case}", nhwc_to_nchw(y), ref, metric_log)
 
 
@@ -123,18 +133,19 @@ def test_rgb_conv_in_fused_prologue(case, metric_log):
 
 
 HALO_CASES = [
-    # B, H, W, Cin, Cout, ups, act, residual
-    (1, 16, 16, 64, 128, False, "none", False), (2, 32, 48, 128, 128, False, "none", True), (1, 40, 36, 256, 320, False, "none", True),
-    (1, 17, 23, 64, 64, False, "relu", False), (3, 16, 20, 192, 200, False, "silu", True), (1, 96, 96, 128, 128, False, "none", False),
-    (1, 8, 8, 128, 128, True, "none", False), (2, 12, 10, 64, 256, True, "none", False), (1, 24, 24, 320, 320, True, "relu", False),
+    # B, H, W, Cin, Cout, ups, act, residual, path (7: the persistent kernel picks 12-row tiles for every plain case here; 1: 16-row tiles, x2 upsample)
+    (1, 16, 16, 64, 128, False, "none", False, 7), (2, 32, 48, 128, 128, False, "none", True, 7), (1, 40, 36, 256, 320, False, "none", True, 7),
+    (1, 17, 23, 64, 64, False, "relu", False, 7), (3, 16, 20, 192, 200, False, "silu", True, 7), (1, 96, 96, 128, 128, False, "none", False, 7),
+    (1, 8, 8, 128, 128, True, "none", False, 1), (2, 12, 10, 64, 256, True, "none", False, 1), (1, 24, 24, 320, 320, True, "relu", False, 1),
 ]
 
 
 @pytest.mark.parametrize("case", HALO_CASES)
 def test_conv3x3_halo_kernel(case, metric_log):
-    """conv_halo.hip (tile hint 5): 16x16-pixel tiles with the input halo staged once per channel chunk; also x2-upsample form."""
+    """conv_halo.hip (tile hint 5): persistent tiles with the input halo staged once per channel chunk (12 x 16 pixels for the plain cases,
+    16 x 16 for the x2-upsample form)."""
     e = _eng()
-    b, h, w, cin, cout, ups, act, with_res = case
+    b, h, w, cin, cout, ups, act, with_res, want = case
     g = torch.Generator().manual_seed(sum(int(v) for v in case[:5]))
     x = rbf(torch.randn(b, cin, h, w, generator=g))
     wt = rbf(torch.randn(cout, cin, 3, 3, generator=g) / math.sqrt(cin * 9))
@@ -146,25 +157,27 @@ def test_conv3x3_halo_kernel(case, metric_log):
         ref = ref + res
     ref = {"none": lambda t: t, "relu": F.relu, "silu": F.silu}[act](ref)
     d = _dev()
+    e.last_igemm_path()
     y = e.conv2d(e.to_nhwc_bf16(x.to(d)), e.pack_weight(wt, device=d), bias.to(d), cout, 3, ups_hw=(2 * h, 2 * w) if ups else None,
                  residual=e.to_nhwc_bf16(res.to(d)) if with_res else None, act=act, tile=5)
+    pin_path(f"conv_halo_path{case}", want, metric_log)
     check(f"conv_halo{case}", nhwc_to_nchw(y), ref, metric_log)
 
 
 @pytest.mark.parametrize("case", [
-    # (B, H, W, Cin, Cout, ks, ups, residual, tile hint): halo kernels (5: persistent, several tiles per workgroup when B*tiles > #CU) and
-    # the generic implicit GEMM (0 -> heuristic tile, 1 = 128x128, 4 = 256x128)
-    (2, 32, 32, 128, 128, 3, False, True, 5), (1, 40, 24, 64, 192, 3, False, False, 5), (4, 144, 160, 64, 128, 3, False, True, 5),
-    (1, 24, 24, 128, 128, 3, True, True, 5), (3, 112, 112, 64, 256, 3, False, False, 5),
-    (2, 32, 32, 128, 128, 3, False, True, 4), (2, 32, 32, 128, 256, 1, False, True, 1), (1, 16, 16, 320, 320, 3, False, False, 1),
+    # (B, H, W, Cin, Cout, ks, ups, residual, tile hint, path): halo kernels (5: persistent, several tiles per workgroup when B*tiles > #CU; 12-row
+    # tiles = path 7 except the x2 upsample, 16-row = 1) and the generic implicit GEMM (path 6; 0 -> heuristic tile, 1 = 128x128, 4 = 256x128)
+    (2, 32, 32, 128, 128, 3, False, True, 5, 7), (1, 40, 24, 64, 192, 3, False, False, 5, 7), (4, 144, 160, 64, 128, 3, False, True, 5, 7),
+    (1, 24, 24, 128, 128, 3, True, True, 5, 1), (3, 112, 112, 64, 256, 3, False, False, 5, 7),
+    (2, 32, 32, 128, 128, 3, False, True, 4, 6), (2, 32, 32, 128, 256, 1, False, True, 1, 6), (1, 16, 16, 320, 320, 3, False, False, 1, 6),
     # persistent GEMM (hint 7): 128-row and 256-row tiles
-    (4, 48, 48, 320, 640, 1, False, True, 7), (2, 96, 96, 320, 320, 1, False, False, 7), (4, 224, 224, 64, 128, 1, False, True, 7),
+    (4, 48, 48, 320, 640, 1, False, True, 7, 3), (2, 96, 96, 320, 320, 1, False, False, 7, 3), (4, 224, 224, 64, 128, 1, False, True, 7, 3),
 ])
 def test_conv_epilogue_groupnorm_statistics(case, metric_log):
     """GroupNorm statistics accumulated in the conv epilogue (per-tile channel sums of the bf16 values as stored) and finalised to
     scale/shift: must equal the statistics of the tensor the conv wrote (diffusers resnet.py: norm2(conv1(...)) etc.)."""
     e = _eng()
-    b, h, w, cin, cout, ks, ups, with_res, tile = case
+    b, h, w, cin, cout, ks, ups, with_res, tile, want = case
     groups, eps = 32, 1e-6
     g = torch.Generator().manual_seed(cin + cout + h)
     x = rbf(torch.randn(b, cin, h, w, generator=g))
@@ -177,8 +190,10 @@ def test_conv_epilogue_groupnorm_statistics(case, metric_log):
     if with_res:
         ref = ref + res
     d = _dev()
+    e.last_igemm_path()
     y, scale, shift = e.conv2d_stats(e.to_nhwc_bf16(x.to(d)), e.pack_weight(wt, device=d), bias.to(d), cout, ks, gamma.to(d), beta.to(d), groups, eps,
                                      ups=ups, residual=e.to_nhwc_bf16(res.to(d)) if with_res else None, tile=tile)
+    pin_path(f"conv_stats_path{case}", want, metric_log)
     check(f"conv_stats_out{case}", nhwc_to_nchw(y), ref, metric_log)
     # statistics of exactly what was stored
     ys = nhwc_to_nchw(y).float().cpu()
@@ -198,9 +213,9 @@ def test_conv_epilogue_groupnorm_statistics(case, metric_log):
 # source map -- 4/9 of the MFMA work.  The reference is built from the SAME operands the kernel sees (source pixels and the phase-summed weights, each
 # rounded once to the element type), so the per-kernel tolerance applies; the un-decomposed conv of the upsampled map (fp32 weights) is checked beside it.
 UP2_CASES = [
-    # B, Hi, Wi, Cin, Cout, residual
-    (1, 16, 16, 64, 128, False), (2, 24, 40, 128, 128, True), (1, 17, 33, 64, 64, False), (2, 31, 47, 192, 320, True), (1, 48, 48, 512, 512, False),
-    (4, 96, 96, 128, 256, False), (1, 20, 16, 1280, 200, False),
+    # B, Hi, Wi, Cin, Cout, residual, path of the nine-tap comparison (1: 16-row halo tiles; the phase kernel itself is path 2)
+    (1, 16, 16, 64, 128, False, 1), (2, 24, 40, 128, 128, True, 1), (1, 17, 33, 64, 64, False, 1), (2, 31, 47, 192, 320, True, 1), (1, 48, 48, 512, 512, False, 1),
+    (4, 96, 96, 128, 256, False, 1), (1, 20, 16, 1280, 200, False, 1),
 ]
 
 
@@ -221,7 +236,7 @@ def _phase_weights(wt):
 @pytest.mark.parametrize("case", UP2_CASES)
 def test_conv_upsample_x2_phase_kernel(case, metric_log):
     e = _eng()
-    b, h, w, cin, cout, with_res = case
+    b, h, w, cin, cout, with_res, want = case
     g = torch.Generator().manual_seed(sum(int(v) for v in case[:5]) + 22)
     x = rbf(torch.randn(b, cin, h, w, generator=g))
     wt = torch.randn(cout, cin, 3, 3, generator=g) / math.sqrt(cin * 9)
@@ -235,8 +250,10 @@ def test_conv_upsample_x2_phase_kernel(case, metric_log):
     if with_res:
         ref, exact = ref + res, exact + res
     d = _dev()
+    e.last_igemm_path()
     y = e.conv2d_up2(e.to_nhwc_bf16(x.to(d)), e.pack_weight(wt, device=d), e.pack_weight_phases(wt, device=d), bias.to(d), cout,
                      residual=e.to_nhwc_bf16(res.to(d)) if with_res else None)
+    pin_path(f"conv_up2_path{case}", 2, metric_log)
     check(f"conv_up2_phases{case}", nhwc_to_nchw(y), ref, metric_log)
     # against the un-decomposed conv: the only extra difference is where the weights are rounded (after the sum instead of before)
     rel = ((nhwc_to_nchw(y).float().cpu() - exact).abs().mean() / exact.abs().mean()).item()
@@ -245,6 +262,7 @@ def test_conv_upsample_x2_phase_kernel(case, metric_log):
     # and against the nine-tap upsample kernel on the same input
     y9 = e.conv2d(e.to_nhwc_bf16(x.to(d)), e.pack_weight(wt, device=d), bias.to(d), cout, 3, ups_hw=(2 * h, 2 * w),
                   residual=e.to_nhwc_bf16(res.to(d)) if with_res else None, tile=5)
+    pin_path(f"conv_up2_ninetap_path{case}", want, metric_log)
     rel9 = ((nhwc_to_nchw(y).float() - nhwc_to_nchw(y9).float()).abs().mean() / exact.abs().mean()).item()
     metric_log(f"conv_up2_vs_ninetap{case}", rel_mean=rel9)
     assert rel9 <= 4 * _tol16()[1], rel9
@@ -258,16 +276,16 @@ def test_conv_upsample_x2_phase_kernel(case, metric_log):
 # chunk counts 1 .. 8, with and without residual.  Every output pixel is accumulated in the same (chunk, tap, k) order as in the 16-row kernel, so
 # the two must agree BIT FOR BIT.
 TR3_CASES = [
-    # B, H, W, Cin, Cout, residual
-    (1, 16, 16, 64, 128, False), (2, 24, 48, 64, 128, True), (1, 48, 96, 128, 256, True), (1, 17, 33, 64, 64, True), (3, 40, 72, 192, 320, False),
-    (1, 19, 40, 320, 200, True), (4, 96, 96, 512, 512, True), (2, 31, 95, 256, 128, True), (4, 144, 160, 64, 128, False),
+    # B, H, W, Cin, Cout, residual, path (7: 12-row tiles, forced)
+    (1, 16, 16, 64, 128, False, 7), (2, 24, 48, 64, 128, True, 7), (1, 48, 96, 128, 256, True, 7), (1, 17, 33, 64, 64, True, 7), (3, 40, 72, 192, 320, False, 7),
+    (1, 19, 40, 320, 200, True, 7), (4, 96, 96, 512, 512, True, 7), (2, 31, 95, 256, 128, True, 7), (4, 144, 160, 64, 128, False, 7),
 ]
 
 
 @pytest.mark.parametrize("case", TR3_CASES)
 def test_conv3x3_halo3_12row_tiles(case, metric_log, monkeypatch):
     e = _eng()
-    b, h, w, cin, cout, with_res = case
+    b, h, w, cin, cout, with_res, want = case
     g = torch.Generator().manual_seed(sum(int(v) for v in case[:5]) + 12)
     x = rbf(torch.randn(b, cin, h, w, generator=g))
     wt = rbf(torch.randn(cout, cin, 3, 3, generator=g) / math.sqrt(cin * 9))
@@ -280,21 +298,24 @@ def test_conv3x3_halo3_12row_tiles(case, metric_log, monkeypatch):
     args = (e.to_nhwc_bf16(x.to(d)), e.pack_weight(wt, device=d), bias.to(d), cout, 3)
     kw = dict(residual=e.to_nhwc_bf16(res.to(d)) if with_res else None, tile=5)
     monkeypatch.setenv("GENPERCEPT_IGEMM_DBG", str(1 << 20))
+    e.last_igemm_path()
     y12 = e.conv2d(*args, **kw)
+    pin_path(f"conv_halo3_tr3_path{case}", want, metric_log)
     check(f"conv_halo3_tr3{case}", nhwc_to_nchw(y12), ref, metric_log)
     monkeypatch.setenv("GENPERCEPT_IGEMM_DBG", str(2 << 20))
     y16 = e.conv2d(*args, **kw)
+    pin_path(f"conv_halo3_tr16_path{case}", 1, metric_log)
     assert torch.equal(y12, y16), "12-row and 16-row tiles must give identical outputs (same per-pixel summation order)"
     monkeypatch.setenv("GENPERCEPT_IGEMM_DBG", str(1 << 20))
     assert torch.equal(e.conv2d(*args, **kw), y12)
 
 
-@pytest.mark.parametrize("case", [(2, 24, 64, 128, 128, True), (1, 40, 72, 64, 192, False), (4, 96, 96, 64, 256, True), (1, 17, 33, 64, 320, True)])
+@pytest.mark.parametrize("case", [(2, 24, 64, 128, 128, True, 7), (1, 40, 72, 64, 192, False, 7), (4, 96, 96, 64, 256, True, 7), (1, 17, 33, 64, 320, True, 7)])
 def test_conv_halo3_12row_tiles_groupnorm_statistics(case, metric_log, monkeypatch):
     """the statistics the 12-row-tile kernel leaves for the next GroupNorm (per-workgroup partial rows + pixel counts) are those of the tensor it stored"""
     monkeypatch.setenv("GENPERCEPT_IGEMM_DBG", str(1 << 20))
     e = _eng()
-    b, h, w, cin, cout, with_res = case
+    b, h, w, cin, cout, with_res, want = case
     groups, eps = 32, 1e-6
     g = torch.Generator().manual_seed(cin + cout + h + 12)
     x = rbf(torch.randn(b, cin, h, w, generator=g))
@@ -306,8 +327,10 @@ def test_conv_halo3_12row_tiles_groupnorm_statistics(case, metric_log, monkeypat
     if with_res:
         ref = ref + res
     d = _dev()
+    e.last_igemm_path()
     y, scale, shift = e.conv2d_stats(e.to_nhwc_bf16(x.to(d)), e.pack_weight(wt, device=d), bias.to(d), cout, 3, gamma.to(d), beta.to(d), groups, eps,
                                      ups=False, residual=e.to_nhwc_bf16(res.to(d)) if with_res else None, tile=5)
+    pin_path(f"conv_halo3_tr3_stats_path{case}", want, metric_log)
     check(f"conv_halo3_tr3_stats_out{case}", nhwc_to_nchw(y), ref, metric_log)
     yg = nhwc_to_nchw(y).float().cpu().reshape(b, groups, -1)
     mean, var = yg.mean(dim=2), yg.var(dim=2, unbiased=False)
@@ -320,12 +343,12 @@ def test_conv_halo3_12row_tiles_groupnorm_statistics(case, metric_log, monkeypat
     assert e_sc < 2e-4 and e_sh < 2e-4, (e_sc, e_sh)
 
 
-@pytest.mark.parametrize("case", [(1, 16, 16, 64, 128, False), (2, 24, 40, 128, 128, True), (2, 31, 47, 192, 320, False), (4, 96, 96, 128, 256, False)])
+@pytest.mark.parametrize("case", [(1, 16, 16, 64, 128, False, 2), (2, 24, 40, 128, 128, True, 2), (2, 31, 47, 192, 320, False, 2), (4, 96, 96, 128, 256, False, 2)])
 def test_conv_upsample_x2_phase_kernel_groupnorm_statistics(case, metric_log):
     """the phase kernel's statistics path is live in the product (the VAE decoder's upsampler convs feed the next resnet's norm1): per (tile,
     phase) unit sums and pixel counts, partial tiles at the edges -- the scale / shift finalised from them are those of the tensor it stored."""
     e = _eng()
-    b, h, w, cin, cout, with_res = case
+    b, h, w, cin, cout, with_res, want = case
     groups, eps = 32, 1e-6
     g = torch.Generator().manual_seed(sum(int(v) for v in case[:5]) + 77)
     x = rbf(torch.randn(b, cin, h, w, generator=g))
@@ -334,8 +357,10 @@ def test_conv_upsample_x2_phase_kernel_groupnorm_statistics(case, metric_log):
     gamma, beta = 1 + 0.2 * torch.randn(cout, generator=g), 0.3 * torch.randn(cout, generator=g)
     res = rbf(torch.randn(b, cout, 2 * h, 2 * w, generator=g)) if with_res else None
     d = _dev()
+    e.last_igemm_path()
     y, scale, shift = e.conv2d_up2_stats(e.to_nhwc_bf16(x.to(d)), e.pack_weight(wt, device=d), e.pack_weight_phases(wt, device=d), bias.to(d), cout,
                                          gamma.to(d), beta.to(d), groups, eps, residual=e.to_nhwc_bf16(res.to(d)) if with_res else None)
+    pin_path(f"conv_up2_phase_stats_path{case}", want, metric_log)
     y0 = e.conv2d_up2(e.to_nhwc_bf16(x.to(d)), e.pack_weight(wt, device=d), e.pack_weight_phases(wt, device=d), bias.to(d), cout,
                       residual=e.to_nhwc_bf16(res.to(d)) if with_res else None)
     assert torch.equal(y, y0), "the statistics epilogue changed the stored tensor"
@@ -370,22 +395,25 @@ def test_flash_attention_split_operands(case, metric_log):
     assert torch.isfinite(out).all() and rel <= 3e-5, rel
 
 
-@pytest.mark.parametrize("case", [(2, 32, 32, 128, 128, 0), (1, 40, 24, 192, 320, 0), (4, 96, 96, 512, 512, 1), (1, 50, 70, 64, 200, 0), (2, 48, 48, 640, 640, 1)])
+@pytest.mark.parametrize("case", [(2, 32, 32, 128, 128, 0, 7), (1, 40, 24, 192, 320, 0, 7), (4, 96, 96, 512, 512, 1, 7), (1, 50, 70, 64, 200, 0, 7), (2, 48, 48, 640, 640, 1, 7),
+                                  (2, 32, 32, 128, 128, 2, 1), (1, 50, 70, 64, 200, 2, 1)])
 def test_conv_halo3_fp32_rows_epilogue(case, metric_log, monkeypatch):
     """conv3x3_halo3_kernel<..., HALO_F32O> (r6, the contract precision's conv epilogue: fp32 rows out instead of 16-bit): same operands as the 16-bit kernel, so the
-    result is the fp32 accumulator itself -- against fp32 torch on identical 16-bit operands it must agree to fp32 summation-order noise, for 16-row and (case[5] = 1:
-    forced) 12-row tiles, ragged tiles and channel counts that are not multiples of 128."""
+    result is the fp32 accumulator itself -- against fp32 torch on identical 16-bit operands it must agree to fp32 summation-order noise, for 12-row tiles (case[5] = 1: forced;
+    the unforced cases reach them too, path 7) and 16-row tiles (case[5] = 2: forced, path 1), ragged tiles and channel counts that are not multiples of 128."""
     e = _eng()
-    b, h, w, cin, cout, tr3 = case
+    b, h, w, cin, cout, tr3, want = case
     if tr3:
-        monkeypatch.setenv("GENPERCEPT_IGEMM_DBG", str(1 << 20))
+        monkeypatch.setenv("GENPERCEPT_IGEMM_DBG", str(tr3 << 20))   # 1: 12-row tiles forced, 2: 16-row tiles forced
     g = torch.Generator().manual_seed(cin + cout + h + 5)
     x = rbf(torch.randn(b, cin, h, w, generator=g))
     wt = rbf(torch.randn(cout, cin, 3, 3, generator=g) / math.sqrt(cin * 9))
     bias = torch.randn(cout, generator=g)
     ref = F.conv2d(x.double(), wt.double(), bias.double(), padding=1).float()
     d = _dev()
+    e.last_igemm_path()
     y = e.conv2d(e.to_nhwc_bf16(x.to(d)), e.pack_weight(wt, device=d), bias.to(d), cout, 3, out_fp32=True, tile=5)
+    pin_path(f"conv_halo3_f32o_path{case}", want, metric_log)
     assert y.dtype == torch.float32
     out = y.permute(0, 3, 1, 2).cpu()
     err = (out - ref).abs()
@@ -475,17 +503,17 @@ def test_conv_fused_nearest_upsample(sizes, metric_log):
     check(f"conv_ups{sizes}", nhwc_to_nchw(y), ref, metric_log)
 
 
-GEMM_CASES = [(64, 64, 64, 0), (576, 1280, 320, 0), (100, 72, 128, 2), (1000, 320, 1280, 1), (36, 2560, 320, 0), (300, 24, 192, 3), (4800, 320, 320, 1),
-              (4800, 320, 320, 4), (1000, 130, 64, 4), (36864, 320, 320, 0), (70, 64, 2304, 4),
+GEMM_CASES = [(64, 64, 64, 0, 6), (576, 1280, 320, 0, 6), (100, 72, 128, 2, 6), (1000, 320, 1280, 1, 6), (36, 2560, 320, 0, 6), (300, 24, 192, 3, 6), (4800, 320, 320, 1, 6),
+              (4800, 320, 320, 4, 6), (1000, 130, 64, 4, 6), (36864, 320, 320, 0, 3), (70, 64, 2304, 4, 6),
               # tile hint 7: persistent GEMM (pgemm.hip); 128-row tiles, several tiles per workgroup, ragged last tile, K up to 40 steps,
               # and (last case) the 256-row form with a ragged tail
-              (36864, 320, 320, 7), (4801, 320, 320, 7), (2304, 1280, 1280, 7), (9216, 640, 2560, 7), (300, 64, 64, 7), (200003, 128, 128, 7)]
+              (36864, 320, 320, 7, 3), (4801, 320, 320, 7, 3), (2304, 1280, 1280, 7, 3), (9216, 640, 2560, 7, 3), (300, 64, 64, 7, 3), (200003, 128, 128, 7, 3)]
 
 
 @pytest.mark.parametrize("case", GEMM_CASES)
 def test_gemm_bias_residual(case, metric_log):
     e = _eng()
-    m, n, k, tile = case
+    m, n, k, tile, want = case
     g = torch.Generator().manual_seed(m + n + k)
     a = rbf(torch.randn(m, k, generator=g))
     bt = rbf(torch.randn(n, k, generator=g) / math.sqrt(k))
@@ -496,7 +524,9 @@ def test_gemm_bias_residual(case, metric_log):
     nst = (n + 3) // 4 * 4
     resd = torch.zeros(m, nst, dtype=_eng().act_dtype(), device=d)
     resd[:, :n] = res.to(d).to(_eng().act_dtype())
+    e.last_igemm_path()
     y = e.gemm(ad, bd, bias=bias.to(d), residual=resd, n_store=nst, tile=tile)
+    pin_path(f"gemm_path{case}", want, metric_log)
     check(f"gemm{case}", y[:, :n], a @ bt.t() + bias + res, metric_log)
     y32 = e.gemm(ad, bd, out_fp32=True, n_store=nst, tile=tile)
     check(f"gemm_f32{case}", y32[:, :n], a @ bt.t(), metric_log, fp32=True)
@@ -557,19 +587,21 @@ def test_decoder_tail_fused(case, mean3, metric_log):
     assert (raw.cpu() - y).abs().mean().item() <= 2 * tol
 
 
-@pytest.mark.parametrize("case", [(4, 576, 320), (2, 2304, 640), (4, 144, 1280), (1, 400, 64), (3, 272, 128)])
+@pytest.mark.parametrize("case", [(4, 576, 320, 3), (2, 2304, 640, 3), (4, 144, 1280, 3), (1, 400, 64, 3), (3, 272, 128, 3)])
 def test_gemm_qkv_fused_projection(case, metric_log):
     """gp_gemm_qkv: attn1.to_q | to_k | to_v of a BasicTransformerBlock as one GEMM -- q | k row-major, V written transposed [B][C][Tpad] with
     zero padding beyond T (the operand layouts of gp_flash_attention); 128- and 256-row tiles, T with and without padding columns, a ragged
     last V slice (3C not a multiple of 128)."""
     e = _eng()
-    b, t, c = case
+    b, t, c, want = case
     g = torch.Generator().manual_seed(b * 1000 + t + c)
     x = rbf(torch.randn(b * t, c, generator=g))
     w = rbf(torch.randn(3 * c, c, generator=g) / math.sqrt(c))
     d = _dev()
     wp = e.pack_weight(w, device=d)
+    e.last_igemm_path()
     qk, vt = e.gemm_qkv(x.to(d).to(e.act_dtype()), wp.reshape(wp.shape[0], -1), b, t, c)
+    pin_path(f"gemm_qkv_path{case}", want, metric_log)
     ref = x @ w.t()
     check(f"gemm_qkv_qk{case}", qk, ref[:, :2 * c], metric_log)
     vref = ref[:, 2 * c:].reshape(b, t, c).permute(0, 2, 1)
@@ -581,12 +613,12 @@ def test_gemm_qkv_fused_projection(case, metric_log):
     assert torch.equal(qk2, qk)
 
 
-@pytest.mark.parametrize("mc", [(200, 128), (4801, 128), (36864, 320), (2304, 64)])
+@pytest.mark.parametrize("mc", [(200, 128, 6), (4801, 128, 3), (36864, 320, 3), (2304, 64, 3)])
 def test_gemm_geglu(mc, metric_log):
     """GEGLU feed-forward GEMM: M = 200 stays on igemm_kernel's direct path, the larger ones run the persistent GEMM's GEGLU epilogue."""
     e = _eng()
     g = torch.Generator().manual_seed(4)
-    m, c = mc
+    m, c, want = mc
     a = rbf(torch.randn(m, c, generator=g))
     w = rbf(torch.randn(8 * c, c, generator=g) / math.sqrt(c))
     bias = torch.randn(8 * c, generator=g)
@@ -602,7 +634,9 @@ def test_gemm_geglu(mc, metric_log):
     dst = (r // 16) * 32 + ((r % 16) // 4) * 8 + (idx >= half).long() * 4 + (r % 4)
     pb = torch.empty_like(bias)
     pb[dst] = bias
+    e.last_igemm_path()
     y = e.conv2d(a.to(d).to(_eng().act_dtype()).reshape(1, 1, m, c), wp, pb.to(d), 8 * c, 1, act="geglu")
+    pin_path(f"gemm_geglu_path{mc}", want, metric_log)
     check(f"gemm_geglu{mc}", y.reshape(m, 4 * c), ref, metric_log)
 
 
