@@ -15,8 +15,12 @@ static inline int gn_nchunk(int HW) {
 }
 int groupnorm_ws_floats(int B, int HW, int C, int G) { return B * gn_nchunk(HW) * G * 2; }
 
-// ---- pass 1: per (image, pixel-chunk, group) partial sum / sum of squares -----------------------------------------
+// ---- pass 1: per (image, pixel-chunk, group) partial {sum, CENTRED second moment} -----------------------------------------
 // Thread t owns VPT fixed 8-channel vectors (v = tv, tv + tpp, ...) and walks pixels p = pl, pl + PL, ... of the chunk.
+// Shifted data: every channel subtracts its value at the chunk's first pixel (the pivot) before it sums and squares, so the sums are those of
+// deviations of the order of the spread, whatever the mean -- raw sum x^2 partials finalised as qk - sk * mk lost (mean / std)^2 * 2^-24 * (growth
+// of the sum) of the variance: fp16 inputs at mean / std >= 32 missed their float64 interval (tests/test_kernels_interval_gpu.py, gate ratio up to
+// 31 at 256).  The per-channel shifted sums meet in LDS; one thread per group reduces them to the chunk's {sum, second moment about the chunk mean}.
 template <int VPT>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const h16_t* __restrict__ x, float* __restrict__ ws, int HW, int C, int G,
                                                         int nchunk, int tpp, int PL) {
@@ -26,14 +30,26 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const h16_t* __restrict__
     const int tid = threadIdx.x;
     const int pl = tid / tpp, tv = tid - pl * tpp;
     const int per = (HW + nchunk - 1) / nchunk;
-    const int p0 = ck * per, p1 = min(HW, p0 + per);
-    float s[VPT][8], q[VPT][8];
+    const int p0 = ck * per, p1 = min(HW, p0 + per);   // (trailing chunks can be empty: p0 >= HW)
+    const h16_t* xb = x + (long long)b * HW * C;
+    float s[VPT][8], q[VPT][8], kv[VPT][8];
 #pragma unroll
     for (int u = 0; u < VPT; ++u)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) s[u][e] = q[u][e] = 0.f;
+        for (int e = 0; e < 8; ++e) s[u][e] = q[u][e] = kv[u][e] = 0.f;
     if (pl < PL) {
-        const h16_t* xb = x + (long long)b * HW * C;
+        if (p0 < p1) {
+#pragma unroll
+            for (int u = 0; u < VPT; ++u) {
+                const int v = tv + u * tpp;
+                if (v < nvec) {
+                    const uint4 raw = *(const uint4*)(xb + (long long)p0 * C + v * 8);
+                    const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { kv[u][2 * e] = h16_lo(w[e]); kv[u][2 * e + 1] = h16_hi(w[e]); }
+                }
+            }
+        }
         for (int p = p0 + pl; p < p1; p += PL) {
 #pragma unroll
             for (int u = 0; u < VPT; ++u) {
@@ -43,7 +59,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const h16_t* __restrict__
                     const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const float lo = h16_lo(w[e]), hi = h16_hi(w[e]);
+                        const float lo = h16_lo(w[e]) - kv[u][2 * e], hi = h16_hi(w[e]) - kv[u][2 * e + 1];
                         s[u][2 * e] += lo; q[u][2 * e] += lo * lo;
                         s[u][2 * e + 1] += hi; q[u][2 * e + 1] += hi * hi;
                     }
@@ -65,12 +81,27 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const h16_t* __restrict__
     __syncthreads();
     if (tid < G) {
         const int cpg = C / G;
-        float ss = 0.f, qq = 0.f;
-        for (int c = tid * cpg; c < (tid + 1) * cpg; ++c)
-            for (int l = 0; l < PL; ++l) { ss += sred[(l * C + c) * 2]; qq += sred[(l * C + c) * 2 + 1]; }
         float* o = ws + (((long long)b * nchunk + ck) * G + tid) * 2;
-        o[0] = ss;
-        o[1] = qq;
+        if (p0 >= p1) {
+            o[0] = 0.f;
+            o[1] = 0.f;
+            return;
+        }
+        const h16_t* xp = xb + (long long)p0 * C;          // the pivots
+        const float cnt = (float)(p1 - p0);
+        const float kg = h16_to_f(xp[tid * cpg]);          // group pivot: the first channel's
+        float sa = 0.f, sa2 = 0.f, m2 = 0.f;
+        for (int c = tid * cpg; c < (tid + 1) * cpg; ++c) {
+            float ss = 0.f, qq = 0.f;
+            for (int l = 0; l < PL; ++l) { ss += sred[(l * C + c) * 2]; qq += sred[(l * C + c) * 2 + 1]; }
+            const float dm = ss / cnt;                     // channel mean - channel pivot
+            m2 += fmaxf(qq - ss * dm, 0.f);                // about the channel mean
+            const float a = (h16_to_f(xp[c]) - kg) + dm;   // channel mean - group pivot
+            sa += a;
+            sa2 += a * a;
+        }
+        o[0] = cnt * ((float)cpg * kg + sa);
+        o[1] = m2 + cnt * fmaxf(sa2 - sa * (sa / (float)cpg), 0.f);   // + the channel means about the chunk mean
     }
 }
 
@@ -101,9 +132,9 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
             const int cnt_px = min(HW, (k + 1) * per) - min(HW, k * per);
             if (cnt_px <= 0) continue;
             const float nk = (float)cnt_px * (float)cpg;
-            const float sk = w[(long long)k * G * 2], qk = w[(long long)k * G * 2 + 1];
+            const float sk = w[(long long)k * G * 2], qk = w[(long long)k * G * 2 + 1];   // {sum, second moment about the chunk mean}
             const float mk = sk / nk;
-            m2 += fmaxf(qk - sk * mk, 0.f) + nk * (mk - mean) * (mk - mean);
+            m2 += qk + nk * (mk - mean) * (mk - mean);
         }
     m2 += __shfl_xor(m2, 1); m2 += __shfl_xor(m2, 2); m2 += __shfl_xor(m2, 4);
     if (act && sub == 0) {

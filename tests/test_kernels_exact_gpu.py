@@ -15,8 +15,9 @@ assert instead that the output is RNE16 of some value within the kernel's own er
 Paths (gp_last_igemm_path): 1 halo 16-row tiles, 2 halo phases (x2 upsample), 3 persistent GEMM (+ row tile), 4 conv_img + split-K
 reduce, 5 split-K igemm + reduce, 6 generic igemm, 7 halo 12-row tiles, 8 per-tile halo; 0 = no conv / GEMM launcher ran.
 
-Not here: the non-matrix 16-bit kernels (GroupNorm, LayerNorm, row softmax, flash attention, the GroupNorm-fused conv input), which exact
-operands cannot express; their gates remain the tolerance tests of tests/test_kernels_gpu.py.
+The non-matrix 16-bit kernels (GroupNorm, LayerNorm, the cross-attention fold, row softmax, flash attention, the GroupNorm statistics of the
+conv epilogues), which exact operands cannot express, are held to per-element float64 intervals in tests/test_kernels_interval_gpu.py; its
+docstring lists what remains out of scope (the outputs of the GroupNorm-fused conv input and of the decoder tail among them).
 """
 import math
 import zlib
