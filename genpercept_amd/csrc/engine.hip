@@ -1,6 +1,7 @@
 // Engine: weight ingestion / constant folding / bf16 packing, activation pool, and the static forward schedules of
 // the SD2.1 VAE encoder, UNet single step (t fixed, context fixed), VAE decoder and DPT head, all enqueued on one
-// HIP stream.  Exposed through the C-ABI of include/genpercept_hip.h.
+// HIP stream.  Exposed through the gp_engine* part of the C-ABI of include/genpercept_hip.h (the stateless per-kernel entry points are
+// kernel_abi.hip); every conv / GEMM launch is filled by a builder of igemm_problem.h, the same one the matching entry point calls.
 //
 // Control flow mirrors (never copies) the reference: genpercept/genpercept_pipeline.py:399-526 (single_infer,
 // encode_rgb, decode_pred), genpercept/models/custom_unet.py:109-119,146-170,273,305-415 (UNet forward, skip order,
@@ -23,69 +24,12 @@
 #include <vector>
 
 #include "../../include/genpercept_hip.h"
-#include "kernels.h"
-
-#define HIPCHK(x)                                                                                         \
-    do {                                                                                                  \
-        hipError_t _e = (x);                                                                              \
-        if (_e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + " at " #x); \
-    } while (0)
+#include "host_pack.h"
+#include "igemm_problem.h"
 
 namespace {
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
-// fp32 -> the library's 16-bit element (common.h), round-to-nearest-even
-inline h16_t f_to_h16_host(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-#if GP_F16
-    const uint32_t sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
-    if (a > 0x7f800000u) return (h16_t)(sign | 0x7e00u);                    // NaN
-    if (a >= 0x477ff000u) return (h16_t)(sign | 0x7bffu);                   // >= 65520 rounds past the largest finite value: saturate
-    if (a < 0x33000001u) return (h16_t)sign;                                // <= 2^-25: rounds to zero
-    if (a < 0x38800000u) {                                                  // subnormal result: value = m * 2^-24
-        const int e = (int)(a >> 23);                                       // biased fp32 exponent, 102 .. 112
-        const uint32_t m = (a & 0x7fffffu) | 0x800000u;
-        const int sh = 126 - e;                                             // 14 .. 24: bits dropped from the 24-bit significand
-        const uint32_t q = m >> sh, rem = m & ((1u << sh) - 1u), half = 1u << (sh - 1);
-        return (h16_t)(sign | (q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u)));
-    }
-    const uint32_t r = a + 0xfffu + ((a >> 13) & 1u);                       // round the 13 dropped bits to nearest even
-    return (h16_t)(sign | ((r - 0x38000000u) >> 13));
-#else
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (h16_t)((u >> 16) | 0x40);  // NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (h16_t)(u >> 16);
-#endif
-}
-inline float half_to_float(uint16_t h) {
-    const uint32_t s = (h & 0x8000u) << 16, e = (h >> 10) & 0x1f, m = h & 0x3ff;
-    uint32_t u;
-    if (e == 0) {
-        if (m == 0) u = s;
-        else {
-            int sh = 0;
-            uint32_t mm = m;
-            while (!(mm & 0x400)) { mm <<= 1; ++sh; }
-            u = s | ((uint32_t)(113 - sh) << 23) | ((mm & 0x3ff) << 13);
-        }
-    } else if (e == 31) u = s | 0x7f800000u | (m << 13);
-    else u = s | ((e + 112) << 23) | (m << 13);
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
-inline float h16_to_float_host(h16_t h) {
-#if GP_F16
-    return half_to_float(h);
-#else
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-#endif
-}
 
 struct HostTensor {
     std::vector<float> v;
@@ -142,12 +86,6 @@ struct Act {
     long long pixels() const { return (long long)B * H * W; }
 };
 
-struct PackedW {
-    h16_t* w = nullptr;   // [n_rows][taps][cin_pad]
-    h16_t* w_ph = nullptr;  // x2-upsample convs only: [n_rows][4 phases][2 x 2 taps][cin_pad], kernel rows / columns on the same source pixel summed (pack_phases)
-    float* bias = nullptr; // [cout] or null
-    int cout = 0, cin_pad = 0, ks = 1, n_rows = 0;
-};
 struct NormW {
     float* g = nullptr;
     float* b = nullptr;
@@ -269,67 +207,6 @@ struct gp_engine {
         return d;
     }
 
-    // GEGLU projection rows [value(0..C4) ; gate(0..C4)] -> packed order: every 32-row block holds 16 outputs, value j at
-    // 8*(j%16/4) + j%4 and its gate 4 rows further, which is where the igemm epilogue finds them in one lane.
-    static int geglu_row(int n, int cout) {
-        const int half = cout / 2;
-        const bool gate = n >= half;
-        const int r = gate ? n - half : n;
-        return (r / 16) * 32 + ((r % 16) / 4) * 8 + (gate ? 4 : 0) + (r % 4);
-    }
-    // Pack [cout][cin][ks][ks] fp32 -> [n_rows][taps][cin_pad] bf16 (+ optional GEGLU row interleave).
-    // split: cin_pad is the logical padded width, the row holds 3 cin_pad elements per tap in B order [hi | hi | lo] (contract precision)
-    static void pack_rows(const float* w, int cout, int cin, int ks, int cin_pad, bool geglu, std::vector<h16_t>& out, int row0, int n_rows_total,
-                          bool split = false) {
-        const int taps = ks * ks;
-        (void)n_rows_total;
-        const size_t kw = split ? (size_t)3 * cin_pad : (size_t)cin_pad;  // elements per tap
-        for (int n = 0; n < cout; ++n) {
-            int dst = n;
-            if (geglu) {
-                dst = geglu_row(n, cout);
-            }
-            h16_t* o = out.data() + (size_t)(row0 + dst) * taps * kw;
-            const float* wi = w + (size_t)n * cin * taps;
-            for (int c = 0; c < cin; ++c)
-                for (int t = 0; t < taps; ++t) {
-                    const float x = wi[(size_t)c * taps + t];
-                    const h16_t hi = f_to_h16_host(x);
-                    o[(size_t)t * kw + c] = hi;
-                    if (split) {
-                        o[(size_t)t * kw + cin_pad + c] = hi;
-                        o[(size_t)t * kw + 2 * cin_pad + c] = f_to_h16_host(x - h16_to_float_host(hi));
-                    }
-                }
-        }
-    }
-    // The x2-nearest-upsample 3x3 conv as four 2 x 2-tap phase convolutions on the source map (conv_halo.hip, PH): output pixel (2y + a, 2x + b) reads
-    // source rows {y - 1 + a, y + a} with the kernel rows that fall onto the same source row summed -- a = 0: {w[0]}, {w[1] + w[2]}; a = 1: {w[0] + w[1]},
-    // {w[2]} -- and the same along x.  Sums in fp32, ONE rounding to the element type.  Layout [n_rows][phase = 2 a + b][tap = 2 ty + tx][cin_pad].
-    // split (contract precision): 3 cin_pad elements per tap in B order [hi | hi | lo] of the fp32 sum, like pack_rows
-    static void pack_phase_rows(const float* w, int cout, int cin, int cin_pad, std::vector<h16_t>& out, bool split = false) {
-        static const int lo[2][2] = {{0, 1}, {0, 2}}, hi[2][2] = {{0, 2}, {1, 2}};  // [phase][tap]: kernel index range [lo, hi]
-        const size_t kw = split ? (size_t)3 * cin_pad : (size_t)cin_pad;
-        for (int n = 0; n < cout; ++n)
-            for (int a = 0; a < 2; ++a)
-                for (int b = 0; b < 2; ++b)
-                    for (int ty = 0; ty < 2; ++ty)
-                        for (int tx = 0; tx < 2; ++tx) {
-                            h16_t* o = out.data() + (((size_t)n * 4 + (2 * a + b)) * 4 + (2 * ty + tx)) * kw;
-                            for (int c = 0; c < cin; ++c) {
-                                const float* wi = w + ((size_t)n * cin + c) * 9;
-                                float acc = 0.f;
-                                for (int ky = lo[a][ty]; ky <= hi[a][ty]; ++ky)
-                                    for (int kx = lo[b][tx]; kx <= hi[b][tx]; ++kx) acc += wi[ky * 3 + kx];
-                                const h16_t h = f_to_h16_host(acc);
-                                o[c] = h;
-                                if (split) {
-                                    o[cin_pad + c] = h;
-                                    o[2 * cin_pad + c] = f_to_h16_host(acc - h16_to_float_host(h));
-                                }
-                            }
-                        }
-    }
     void pack_phases(PackedW& pw, const std::string& name) {
         const HostTensor& w = H(name + ".weight");
         if (w.shape.size() != 4 || w.shape[2] != 3 || w.shape[3] != 3) throw std::invalid_argument(name + ": not a 3x3 conv");
@@ -822,58 +699,18 @@ struct gp_engine {
         if (ws) pool.release(ws);
     }
 
-    struct ConvOpt {
-        int stride = 1, pad_t = 1, pad_l = 1;
-        int Ho = 0, Wo = 0;     // 0: same as input (or upsampled size)
-        int ups_h = 0, ups_w = 0;
-        const h16_t* res = nullptr;
+    struct ConvOpt : ConvForm {
         const float* res_f = nullptr;  // contract precision: the residual is a stored fp32 tensor
-        int act = GP_ACT_NONE;
-        int n_store = 0;        // 0: cout
         bool want_stats = false;  // the output feeds a GroupNorm
     };
-    IGemmParams conv_params(const Act& x, const PackedW& w, const ConvOpt& o, h16_t* out) { return conv_params_of(x, w, o, out, zero); }
-    static IGemmParams conv_params_of(const Act& x, const PackedW& w, const ConvOpt& o, h16_t* out, h16_t* zero) {
-        if (x.C != w.cin_pad) throw std::logic_error("conv: channel mismatch (" + std::to_string(x.C) + " vs " + std::to_string(w.cin_pad) + ")");
-        const int Hin = o.ups_h ? o.ups_h : x.H, Win = o.ups_w ? o.ups_w : x.W;
-        const int Ho = o.Ho ? o.Ho : Hin, Wo = o.Wo ? o.Wo : Win;
-        const int nst = o.n_store ? o.n_store : w.cout;
-        IGemmParams p{};
-        p.in = x.p; p.wt = w.w; p.bias = w.bias; p.res = o.res; p.out = out; p.zero = zero;
-        p.M = x.B * Ho * Wo; p.N = w.cout; p.Cin = w.cin_pad; p.n_rows = w.n_rows; p.ks = w.ks;
-        p.B = x.B; p.Hi = x.H; p.Wi = x.W; p.Ho = Ho; p.Wo = Wo;
-        p.stride = o.stride; p.pad_t = w.ks == 3 ? o.pad_t : 0; p.pad_l = w.ks == 3 ? o.pad_l : 0;
-        p.ups = o.ups_h ? 1 : 0; p.Hu = o.ups_h; p.Wu = o.ups_w;
-        p.wt_ph = o.ups_h ? w.w_ph : nullptr;  // (used where the size is exactly x2: conv_halo_uses_phases)
-        p.lda = x.C; p.ldo = nst; p.ldres = nst; p.ldw = (w.ks == 3 ? 9 : 1) * w.cin_pad;
-        p.n_store = nst; p.out_fp32 = 0; p.act = o.act; p.bias_mode = w.bias ? GP_BIAS_COL : GP_BIAS_NONE;
-        p.batch = 1;
-        return p;
-    }
-    // contract precision: the launch of conv_c / linear_c on a split operand xs (also what the gp_c_conv2d test entry launches)
-    static IGemmParams conv_c_params(const Act& xs, const PackedW& w, const ConvOpt& o, float* out, h16_t* zero) {
-        IGemmParams p = conv_params_of(xs, w, o, nullptr, zero);
-        p.out = out; p.out_fp32 = 1;
-        p.res = (const h16_t*)o.res_f; p.res_f32 = o.res_f ? 1 : 0;
-        return p;
-    }
-    static IGemmParams linear_c_params(const Act& xs, const PackedW& w, const float* res, int act, float* out, h16_t* zero) {
-        if (xs.C != w.cin_pad) throw std::logic_error("linear: channel mismatch");
-        const int nout = act == GP_ACT_GEGLU ? w.cout / 2 : w.cout;
-        IGemmParams p{};
-        p.in = xs.p; p.wt = w.w; p.bias = w.bias; p.res = (const h16_t*)res; p.res_f32 = res ? 1 : 0; p.out = out; p.out_fp32 = 1; p.zero = zero;
-        p.M = (int)xs.pixels(); p.N = w.cout; p.Cin = w.cin_pad; p.n_rows = w.n_rows; p.ks = 1;
-        p.B = xs.B; p.Hi = xs.H; p.Wi = xs.W; p.Ho = xs.H; p.Wo = xs.W; p.stride = 1;
-        p.lda = xs.C; p.ldo = nout; p.ldres = nout; p.ldw = w.cin_pad; p.n_store = nout; p.act = act;
-        p.bias_mode = w.bias ? GP_BIAS_COL : GP_BIAS_NONE; p.batch = 1;
-        return p;
-    }
+    static Nhwc nhwc(const Act& a) { return {a.p, a.B, a.H, a.W, a.C}; }
     // contract precision: split operand in (made here when x is a stored tensor), fp32 rows out, fp32 residual
     Act conv_c(const Act& x0, const PackedW& w, const ConvOpt& o) {
         Act xs = x0;
         const bool tmp = x0.p == nullptr;
         if (tmp) xs = split_operand(x0);
-        IGemmParams p = conv_c_params(xs, w, o, nullptr, zero);
+        IGemmParams p = igemm_conv(nhwc(xs), w, o, nullptr, zero);
+        igemm_contract(p, o.res_f);
         Act y = new_act_f(xs.B, p.Ho, p.Wo, p.n_store);
         p.out = y.f;
         if (o.want_stats) attach_stats(y, p);
@@ -883,7 +720,7 @@ struct gp_engine {
     }
     Act conv(const Act& x, const PackedW& w, const ConvOpt& o, const float* in_scale = nullptr, const float* in_shift = nullptr, bool in_silu = false) {
         if (contract) return conv_c(x, w, o);
-        IGemmParams p = conv_params(x, w, o, nullptr);
+        IGemmParams p = igemm_conv(nhwc(x), w, o, nullptr, zero);
         Act y = new_act(x.B, p.Ho, p.Wo, p.n_store);
         p.out = y.p;
         p.in_scale = in_scale; p.in_shift = in_shift; p.in_silu = in_silu ? 1 : 0;
@@ -898,12 +735,12 @@ struct gp_engine {
         Act xs = x0;
         const bool tmp = x0.p == nullptr;
         if (tmp) xs = split_operand(x0);
-        if (xs.C != w.cin_pad) throw std::logic_error("linear: channel mismatch");
-        const int nout = act == GP_ACT_GEGLU ? w.cout / 2 : w.cout;
+        IGemmParams p = igemm_linear(nhwc(xs), w, nullptr, act, out_inplace, zero);
+        igemm_contract(p, res);
         Act y;
-        if (out_inplace) { y.B = xs.B; y.H = xs.H; y.W = xs.W; y.C = nout; y.f = out_inplace; }
-        else y = new_act_f(xs.B, xs.H, xs.W, nout);
-        IGemmParams p = linear_c_params(xs, w, res, act, y.f, zero);
+        if (out_inplace) { y.B = xs.B; y.H = xs.H; y.W = xs.W; y.C = p.n_store; y.f = out_inplace; }
+        else y = new_act_f(xs.B, xs.H, xs.W, p.n_store);
+        p.out = y.f;
         if (want_stats && !out_inplace) attach_stats(y, p);
         run_igemm(p);
         if (tmp) drop(xs);
@@ -915,17 +752,11 @@ struct gp_engine {
             if (res || out_inplace) throw std::logic_error("linear: 16-bit residual in contract precision");
             return linear_c(x, w, nullptr, act, nullptr, want_stats);
         }
-        if (x.C != w.cin_pad) throw std::logic_error("linear: channel mismatch");
-        const int nout = act == GP_ACT_GEGLU ? w.cout / 2 : w.cout;
+        IGemmParams p = igemm_linear(nhwc(x), w, res, act, out_inplace, zero);
         Act y;
-        if (out_inplace) { y = x; y.C = nout; y.p = out_inplace; }
-        else y = new_act(x.B, x.H, x.W, nout);
-        IGemmParams p{};
-        p.in = x.p; p.wt = w.w; p.bias = w.bias; p.res = res; p.out = y.p; p.zero = zero;
-        p.M = (int)x.pixels(); p.N = w.cout; p.Cin = w.cin_pad; p.n_rows = w.n_rows; p.ks = 1;
-        p.B = x.B; p.Hi = x.H; p.Wi = x.W; p.Ho = x.H; p.Wo = x.W; p.stride = 1;
-        p.lda = x.C; p.ldo = nout; p.ldres = nout; p.ldw = w.cin_pad; p.n_store = nout; p.act = act;
-        p.bias_mode = w.bias ? GP_BIAS_COL : GP_BIAS_NONE; p.batch = 1;
+        if (out_inplace) { y = x; y.C = p.n_store; y.p = out_inplace; }
+        else y = new_act(x.B, x.H, x.W, p.n_store);
+        p.out = y.p;
         if (want_stats && !out_inplace) attach_stats(y, p);
         run_igemm(p);
         return y;
@@ -934,12 +765,8 @@ struct gp_engine {
     h16_t* v_transposed(const Act& x, const PackedW& wv, int T, int Tpad) {
         const int C = wv.cout;
         h16_t* vt = (h16_t*)pool.alloc((size_t)x.B * C * Tpad * sizeof(h16_t));
-        IGemmParams p{};
-        p.in = wv.w; p.wt = x.p; p.bias = wv.bias; p.out = vt; p.zero = zero;
-        p.M = C; p.N = T; p.Cin = wv.cin_pad; p.n_rows = T; p.ks = 1; p.stride = 1;
-        p.lda = wv.cin_pad; p.ldw = x.C; p.ldo = Tpad; p.n_store = Tpad;
-        p.bias_mode = wv.bias ? GP_BIAS_ROW : GP_BIAS_NONE;
-        p.batch = x.B; p.in_bs = 0; p.wt_bs = (long long)T * x.C; p.out_bs = (long long)C * Tpad; p.bias_bs = 0;
+        const IGemmParams p = igemm_bgemm({wv.w, wv.cin_pad, 0}, {x.p, x.C, (long long)T * x.C}, {vt, Tpad, (long long)C * Tpad}, C, T, wv.cin_pad, T, Tpad, x.B,
+                                          wv.bias, GP_BIAS_ROW, 0, zero);
         // rows = channels (320 ... 1280), columns = tokens: 64x64 tiles when there are few tokens or the channel count is not a multiple of 128
         // (320 rows leave a 128-row tile half empty), 128x64 tiles otherwise -- measured per shape with GENPERCEPT_VT_TILE (igemm.hip: tile_hint),
         // 0.77 -> 0.67 ms per pass over the 18 projections
@@ -951,8 +778,7 @@ struct gp_engine {
     void gn_scale_shift(const Act& x, const NormW& n, float eps, float*& scale, float*& shift) {
         if (x.C != n.C) throw std::logic_error("groupnorm: channel mismatch");
         float* ws = gn_workspace(x);
-        scale = ws + groupnorm_ws_floats(x.B, x.H * x.W, x.C, cfg.norm_groups);
-        shift = scale + (size_t)x.B * x.C;
+        groupnorm_ws_layout(x.B, x.H * x.W, x.C, cfg.norm_groups, ws, &scale, &shift);
         if (contract) {  // statistics pass over the fp32 tensor: centred per-row partials, Chan-combined by the tile finaliser ("mode 3")
             const int R = c_gn_stat_rows(x.H * x.W, x.C, nullptr);
             float* part = (float*)pool.alloc((size_t)x.B * R * (2 * x.C + 1) * sizeof(float));
@@ -994,7 +820,7 @@ struct gp_engine {
         return y;
     }
     float* gn_workspace(const Act& x) {  // partial statistics + per-(image, channel) scale / shift
-        const size_t need = (size_t)groupnorm_ws_floats(x.B, x.H * x.W, x.C, cfg.norm_groups) + 2 * (size_t)x.B * x.C;
+        const size_t need = groupnorm_ws_layout(x.B, x.H * x.W, x.C, cfg.norm_groups);
         if (need > gn_ws_floats) {
             if (gn_ws) { pool.live_[gn_ws] = 1; pool.release(gn_ws); }
             gn_ws = (float*)pool.alloc(need * 4 * 2);
@@ -1013,7 +839,7 @@ struct gp_engine {
             return out;
         }
         if (gn_small(x)) {
-            IGemmParams p0 = conv_params(x, w, o, nullptr);
+            const IGemmParams p0 = igemm_conv(nhwc(x), w, o, nullptr, zero);
             if (!conv_uses_halo(p0, 0)) {  // (a halo conv would fuse the apply: keep the statistics path for it)
                 Act y = groupnorm_small(x, n, eps, silu);
                 Act out = conv(y, w, o);
@@ -1023,7 +849,7 @@ struct gp_engine {
         }
         float *scale, *shift;
         gn_scale_shift(x, n, eps, scale, shift);
-        IGemmParams p = conv_params(x, w, o, nullptr);
+        IGemmParams p = igemm_conv(nhwc(x), w, o, nullptr, zero);
         p.in_scale = scale; p.in_shift = shift; p.in_silu = silu ? 1 : 0;
         // The fused transform is redone by every 128-channel slice of the output (each slice's workgroup stages its own halo) and it is
         // bound by the two quarter-rate transcendentals per element inside the conv.  One separate apply pass -- 2 x tensor bytes of HBM
@@ -1078,27 +904,15 @@ struct gp_engine {
         const bool f32_scores = gp_sw().fp32_scores;
         const bool half_scores = !f32_scores && softmax_rows_f16_supported(Tpad);
         float* S = (float*)pool.alloc((size_t)B * T * Tpad * (half_scores ? 2 : 4));
-        {
-            IGemmParams p{};
-            p.in = qk.p; p.wt = qk.p + C; p.out = S; p.zero = zero;
-            p.M = T; p.N = T; p.Cin = C; p.n_rows = T; p.ks = 1; p.stride = 1;
-            p.lda = 2 * C; p.ldw = 2 * C; p.ldo = Tpad; p.n_store = T; p.out_fp32 = half_scores ? 2 : 1;
-            p.batch = B; p.in_bs = (long long)T * 2 * C; p.wt_bs = (long long)T * 2 * C; p.out_bs = (long long)T * Tpad;
-            run_igemm(p);
-        }
+        run_igemm(igemm_bgemm({qk.p, 2 * C, (long long)T * 2 * C}, {qk.p + C, 2 * C, (long long)T * 2 * C}, {S, Tpad, (long long)T * Tpad}, T, T, C, T, T, B,
+                              nullptr, GP_BIAS_NONE, half_scores ? 2 : 1, zero));
         h16_t* P = (h16_t*)pool.alloc((size_t)B * T * Tpad * sizeof(h16_t));
         mark("softmax_rows T=" + std::to_string(T));
         if (half_scores) launch_softmax_rows_f16(S, P, B * T, T, Tpad, 1.0f, st);
         else launch_softmax_rows(S, P, B * T, T, Tpad, 1.0f, st);
         pool.release(S);
-        {
-            IGemmParams p{};
-            p.in = P; p.wt = vt; p.out = o.p; p.zero = zero;
-            p.M = T; p.N = C; p.Cin = Tpad; p.n_rows = C; p.ks = 1; p.stride = 1;
-            p.lda = Tpad; p.ldw = Tpad; p.ldo = C; p.n_store = C;
-            p.batch = B; p.in_bs = (long long)T * Tpad; p.wt_bs = (long long)C * Tpad; p.out_bs = (long long)T * C;
-            run_igemm(p);
-        }
+        run_igemm(igemm_bgemm({P, Tpad, (long long)T * Tpad}, {vt, Tpad, (long long)C * Tpad}, {o.p, C, (long long)T * C}, T, C, Tpad, C, C, B, nullptr,
+                              GP_BIAS_NONE, 0, zero));
         pool.release(P);
     }
 
@@ -1135,14 +949,8 @@ struct gp_engine {
         mark("c_heads_split T=" + std::to_string(T) + " heads=" + std::to_string(heads), 0.0, 2);
         launch_c_heads_split(qkv.f, qkv.C, Qs, Ks, Vts, B, T, Tpad, heads, hd, st);
         float* S = (float*)pool.alloc((size_t)Z * T * Tpad * sizeof(float));
-        {
-            IGemmParams p{};
-            p.in = Qs; p.wt = Ks; p.out = S; p.zero = zero;
-            p.M = T; p.N = T; p.Cin = 3 * hd; p.n_rows = T; p.ks = 1; p.stride = 1;
-            p.lda = 3 * hd; p.ldw = 3 * hd; p.ldo = Tpad; p.n_store = T; p.out_fp32 = 1;
-            p.batch = Z; p.in_bs = (long long)T * 3 * hd; p.wt_bs = (long long)T * 3 * hd; p.out_bs = (long long)T * Tpad;
-            run_igemm(p);
-        }
+        run_igemm(igemm_bgemm({Qs, 3 * hd, (long long)T * 3 * hd}, {Ks, 3 * hd, (long long)T * 3 * hd}, {S, Tpad, (long long)T * Tpad}, T, T, 3 * hd, T, T, Z,
+                              nullptr, GP_BIAS_NONE, 1, zero));
         pool.release(Qs);
         pool.release(Ks);
         h16_t* P = (h16_t*)pool.alloc((size_t)Z * T * 3 * Tpad * sizeof(h16_t));
@@ -1150,14 +958,8 @@ struct gp_engine {
         launch_c_softmax_split(S, P, (long long)Z * T, T, Tpad, scale, st);
         pool.release(S);
         float* O = (float*)pool.alloc((size_t)Z * T * hd * sizeof(float));
-        {
-            IGemmParams p{};
-            p.in = P; p.wt = Vts; p.out = O; p.zero = zero;
-            p.M = T; p.N = hd; p.Cin = 3 * Tpad; p.n_rows = hd; p.ks = 1; p.stride = 1;
-            p.lda = 3 * Tpad; p.ldw = 3 * Tpad; p.ldo = hd; p.n_store = hd; p.out_fp32 = 1;
-            p.batch = Z; p.in_bs = (long long)T * 3 * Tpad; p.wt_bs = (long long)hd * 3 * Tpad; p.out_bs = (long long)T * hd;
-            run_igemm(p);
-        }
+        run_igemm(igemm_bgemm({P, 3 * Tpad, (long long)T * 3 * Tpad}, {Vts, 3 * Tpad, (long long)hd * 3 * Tpad}, {O, hd, (long long)T * hd}, T, hd, 3 * Tpad, hd,
+                              hd, Z, nullptr, GP_BIAS_NONE, 1, zero));
         pool.release(P);
         pool.release(Vts);
         Act a = new_operand(qkv.B, qkv.H, qkv.W, heads * hd);
@@ -1265,14 +1067,8 @@ struct gp_engine {
         h16_t* vt = nullptr;
         {   // q | k | V^T in ONE launch when the persistent GEMM takes it (T % 16 == 0 ...), else the q | k GEMM + the transposed V GEMM
             const bool no_fuse = gp_sw().no_qkv_fuse;  // A/B switch
-            IGemmParams p{};
-            p.in = l1.p; p.wt = t.qkv.w; p.zero = zero;
-            p.M = (int)l1.pixels(); p.N = 3 * C; p.Cin = t.qkv.cin_pad; p.n_rows = t.qkv.n_rows; p.ks = 1;
-            p.B = x.B; p.Hi = x.H; p.Wi = x.W; p.Ho = x.H; p.Wo = x.W; p.stride = 1;
-            p.lda = l1.C; p.ldo = 2 * C; p.ldres = 2 * C; p.ldw = t.qkv.cin_pad; p.n_store = 2 * C; p.act = GP_ACT_NONE;
-            p.bias_mode = GP_BIAS_NONE; p.batch = 1;
-            p.vt_col0 = 2 * C; p.vt_T = T; p.vt_Tpad = Tpad;
-            p.vt_out = (h16_t*)zero;  // (non-null for the applicability test)
+            IGemmParams p = igemm_qkv(nhwc(l1), t.qkv.w, t.qkv.cin_pad, t.qkv.n_rows, t.qkv.cin_pad, C, Tpad, nullptr,
+                                      (h16_t*)zero /* (non-null for the applicability test) */, zero);
             // measured (tools/kbench, weight-cold): 4 x 2304 tokens, C = 640: 43 us fused vs 25 + 25; 4 x 576, C = 1280: 46 vs 29 + 25; at
             // 4 x 9216 tokens, C = 320 the transposed stores of the V third (16 bytes per channel row and lane) eat the saving: 55 vs 29 + 25
             // (same-box pipeline A/B, tools/gpu_ab_r03.sh: fusing every level is 0.1-0.2 ms per pass ahead of fusing none, the 4 x 9216 level
@@ -1281,8 +1077,8 @@ struct gp_engine {
             if (!no_fuse && p.M <= fuse_max_rows && !t.qkv.bias && l1.C == t.qkv.cin_pad && igemm_uses_pgemm(p, 0)) {
                 qk = new_act(x.B, x.H, x.W, 2 * C);
                 vt = (h16_t*)pool.alloc((size_t)x.B * C * Tpad * sizeof(h16_t));
-                if (Tpad != T) HIPCHK(hipMemsetAsync(vt, 0, (size_t)x.B * C * Tpad * sizeof(h16_t), st));  // keys beyond T must read as zero
                 p.out = qk.p; p.vt_out = vt;
+                igemm_qkv_clear_pad(p, st);
                 run_igemm(p);
             } else {
                 qk = linear(l1, t.qk);
@@ -1704,52 +1500,6 @@ static gp_status guard(gp_engine* e, F&& f) {
     return st;
 }
 
-// Scratch of the per-kernel entry points (the parity-test interface below; engines use their own pool): one set per DEVICE, and the
-// entry points that use it hold g_scratch_mu for the duration of their enqueue, so two host threads cannot resize it under each other.
-struct DevScratch {
-    h16_t* zero = nullptr;
-    float* bufs[3] = {nullptr, nullptr, nullptr};  // 0: GroupNorm workspace, 1: statistics partials, 2: split-K partial sums
-    size_t floats[3] = {0, 0, 0};
-};
-static std::mutex g_scratch_mu;
-// what every per-kernel (test / tool) entry point opens with: the scratch lock, and the A/B switches as the environment has them NOW
-struct KernelEntry {
-    std::lock_guard<std::mutex> g;
-    KernelEntry() : g(g_scratch_mu) { gp_switches_reload(); }
-};
-static std::map<int, DevScratch> g_scratch;
-static DevScratch& dev_scratch() {  // call with g_scratch_mu held
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    return g_scratch[dev];
-}
-static h16_t* zero_page() {
-    DevScratch& d = dev_scratch();
-    if (!d.zero) {
-        HIPCHK(hipMalloc((void**)&d.zero, 4096));
-        HIPCHK(hipMemset(d.zero, 0, 4096));
-    }
-    return d.zero;
-}
-static float* scratch_floats(int which, size_t need) {
-    DevScratch& d = dev_scratch();
-    if (need > d.floats[which]) {
-        if (d.bufs[which]) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(d.bufs[which])); d.bufs[which] = nullptr; d.floats[which] = 0; }
-        HIPCHK(hipMalloc((void**)&d.bufs[which], need * sizeof(float)));
-        d.floats[which] = need;
-    }
-    return d.bufs[which];
-}
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }  // (nullptr passes: optional arguments are checked for presence separately)
-// split-K workspace for a per-kernel call (engines take theirs from the pool)
-static void attach_splitk_scratch(IGemmParams& p, int tile_hint) {
-    const int S = igemm_ksplit(p, tile_hint);
-    if (S > 1) {
-        p.splitk_ws_floats = (long long)S * p.M * p.n_store;
-        p.splitk_ws = scratch_floats(2, (size_t)p.splitk_ws_floats);
-    }
-}
-
 extern "C" {
 
 const char* gp_version(void) { return GP_F16 ? "genpercept_hip 0.3 (gfx950, fp16 elements)" : "genpercept_hip 0.3 (gfx950, bf16 elements)"; }
@@ -2158,481 +1908,6 @@ gp_status gp_dpt_head(gp_engine* e, const float* const* feats, int B, int h, int
         e->collect_saturation();
         HIPCHK(hipGetLastError());
     });
-}
-
-// ---- per-kernel entry points --------------------------------------------------------------------------------------
-int gp_packed_rows(int cout) { return (cout + 255) / 256 * 256; }
-int gp_last_igemm_path(int* pgemm_rows) { return igemm_last_path(pgemm_rows); }
-int gp_latent_size(int x) { for (int i = 0; i < 3; ++i) x = (x - 2) / 2 + 1; return x; }
-int gp_dpt_out_size(int latent) { for (int i = 0; i < 2; ++i) latent = (latent - 1) / 2 + 1; return 32 * latent; }
-
-gp_status gp_pack_weight(const float* w, int cout, int cin, int ks, int cin_pad, int geglu, void* dev_out) {
-    if (!w || !dev_out || cout < 1 || cin < 1 || (ks != 1 && ks != 3) || cin_pad < cin || (cin_pad % 64)) return GP_ERR_INVALID;
-    try {
-        const int n_rows = gp_packed_rows(cout);
-        std::vector<h16_t> buf((size_t)n_rows * ks * ks * cin_pad, 0);
-        gp_engine::pack_rows(w, cout, cin, ks, cin_pad, geglu != 0, buf, 0, n_rows);
-        HIPCHK(hipMemcpy(dev_out, buf.data(), buf.size() * 2, hipMemcpyHostToDevice));
-        return GP_OK;
-    } catch (...) { return GP_ERR_HIP; }
-}
-
-gp_status gp_conv2d(const void* in, const void* w_packed, const float* bias, const void* residual, void* out, int B, int Hi, int Wi, int Cin,
-                    int Cout, int ks, int stride, int pad_t, int pad_l, int Ho, int Wo, int ups_h, int ups_w, int act, int n_store,
-                    int out_fp32, int tile_hint, void* stream) {
-    if (!in || !w_packed || !out || (Cin % 64) || (ks != 1 && ks != 3)) return GP_ERR_INVALID;
-    try {
-        KernelEntry lk;
-        IGemmParams p{};
-        p.in = (const h16_t*)in; p.wt = (const h16_t*)w_packed; p.bias = bias; p.res = (const h16_t*)residual; p.out = out; p.zero = zero_page();
-        p.M = B * Ho * Wo; p.N = Cout; p.Cin = Cin; p.n_rows = gp_packed_rows(Cout); p.ks = ks;
-        p.B = B; p.Hi = Hi; p.Wi = Wi; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
-        p.ups = ups_h > 0; p.Hu = ups_h; p.Wu = ups_w;
-        const int nout = act == GP_ACT_GEGLU ? Cout / 2 : Cout;
-        const int nst = n_store > 0 ? n_store : nout;
-        p.lda = Cin; p.ldo = nst; p.ldres = nst; p.ldw = (ks == 3 ? 9 : 1) * Cin; p.n_store = nst; p.out_fp32 = out_fp32; p.act = act;
-        p.bias_mode = bias ? GP_BIAS_COL : GP_BIAS_NONE; p.batch = 1;
-        p.dbg = gp_sw().igemm_dbg;  // profiling ablations (tools/conv_bench.py)
-        attach_splitk_scratch(p, tile_hint);
-        launch_igemm(p, tile_hint, (hipStream_t)stream);
-        HIPCHK(hipGetLastError());
-        return GP_OK;
-    } catch (...) { return GP_ERR_HIP; }
-}
-
-gp_status gp_pack_weight_phases(const float* w, int cout, int cin, int cin_pad, void* dev_out) {
-    if (!w || !dev_out || cout < 1 || cin < 1 || cin_pad < cin || (cin_pad % 64)) return GP_ERR_INVALID;
-    try {
-        std::vector<h16_t> buf((size_t)gp_packed_rows(cout) * 16 * cin_pad, 0);
-        gp_engine::pack_phase_rows(w, cout, cin, cin_pad, buf);
-        HIPCHK(hipMemcpy(dev_out, buf.data(), buf.size() * 2, hipMemcpyHostToDevice));
-        return GP_OK;
-    } catch (...) { return GP_ERR_HIP; }
-}
-
-gp_status gp_conv2d_up2(const void* in, const void* w_packed, const void* w_phases, const float* bias, const void* residual, void* out, int B, int Hi, int Wi,
-                        int Cin, int Cout, void* stream) {
-    if (!in || !w_packed || !w_phases || !out || (Cin % 64) || (Cout % 8)) return GP_ERR_INVALID;
-    try {
-        KernelEntry lk;
-        IGemmParams p{};
-        p.in = (const h16_t*)in; p.wt = (const h16_t*)w_packed; p.wt_ph = (const h16_t*)w_phases; p.bias = bias; p.res = (const h16_t*)residual; p.out = out;
-        p.zero = zero_page();
-        p.M = B * 4 * Hi * Wi; p.N = Cout; p.Cin = Cin; p.n_rows = gp_packed_rows(Cout); p.ks = 3;
-        p.B = B; p.Hi = Hi; p.Wi = Wi; p.Ho = 2 * Hi; p.Wo = 2 * Wi; p.stride = 1; p.pad_t = 1; p.pad_l = 1;
-        p.ups = 1; p.Hu = 2 * Hi; p.Wu = 2 * Wi;
-        p.lda = Cin; p.ldo = Cout; p.ldres = Cout; p.ldw = 9 * Cin; p.n_store = Cout; p.bias_mode = bias ? GP_BIAS_COL : GP_BIAS_NONE; p.batch = 1;
-        p.dbg = gp_sw().igemm_dbg;
-        if (!conv_uses_halo(p, 5) || !conv_halo_uses_phases(p)) return GP_ERR_INVALID;  // (this entry point exists to test the phase kernel)
-        launch_igemm(p, 5, (hipStream_t)stream);
-        HIPCHK(hipGetLastError());
-        return GP_OK;
-    } catch (...) { return GP_ERR_HIP; }
-}
-
-gp_status gp_conv2d_up2_stats(const void* in, const void* w_packed, const void* w_phases, const float* bias, const void* residual, void* out, int B, int Hi,
-                              int Wi, int Cin, int Cout, const float* gamma, const float* beta, int groups, float eps, float* scale_out, float* shift_out,
-                              void* stream) {
-    if (!in || !w_packed || !w_phases || !out || !gamma || !beta || !scale_out || !shift_out || (Cin % 64) || (Cout % 8) || groups < 1 || (Cout % groups))
-        return GP_ERR_INVALID;
-    try {
-        KernelEntry lk;
-        IGemmParams p{};
-        p.in = (const h16_t*)in; p.wt = (const h16_t*)w_packed; p.wt_ph = (const h16_t*)w_phases; p.bias = bias; p.res = (const h16_t*)residual; p.out = out;
-        p.zero = zero_page();
-        p.M = B * 4 * Hi * Wi; p.N = Cout; p.Cin = Cin; p.n_rows = gp_packed_rows(Cout); p.ks = 3;
-        p.B = B; p.Hi = Hi; p.Wi = Wi; p.Ho = 2 * Hi; p.Wo = 2 * Wi; p.stride = 1; p.pad_t = 1; p.pad_l = 1;
-        p.ups = 1; p.Hu = 2 * Hi; p.Wu = 2 * Wi;
-        p.lda = Cin; p.ldo = Cout; p.ldres = Cout; p.ldw = 9 * Cin; p.n_store = Cout; p.bias_mode = bias ? GP_BIAS_COL : GP_BIAS_NONE; p.batch = 1;
-        if (!conv_uses_halo(p, 5) || !conv_halo_uses_phases(p)) return GP_ERR_INVALID;
-        int mode = 0, bm = 0;
-        const int nt = igemm_tile_info(p, 5, &mode, &bm);
-        if (nt <= 0) return GP_ERR_INVALID;
-        float* part = scratch_floats(1, (size_t)nt * (Cout * 2 + 1));
-        p.stats_out = part;
-        launch_igemm(p, 5, (hipStream_t)stream);
-        launch_groupnorm_from_partials(part, mode, bm, B, 2 * Hi, 2 * Wi, Cout, groups, eps, gamma, beta, scale_out, shift_out, (hipStream_t)stream);
-        HIPCHK(hipGetLastError());
-        return GP_OK;
-    } catch (...) { return GP_ERR_HIP; }
-}
-
-gp_status gp_conv2d_gn(const void* in, const void* w_packed, const float* bias, const void* residual, void* out, int B, int H, int W, int Cin,
-                       int Cout, int ups, int act, const float* gamma, const float* beta, int groups, float eps, int silu, void* stream) {
-    if (!in || !w_packed || !out || !gamma || !beta || (Cin % 64) || (Cin % groups)) return GP_ERR_INVALID;
-    try {
-        KernelEntry lk;
-        const int Ho = ups ? 2 * H : H, Wo = ups ? 2 * W : W;
-        IGemmParams p{};
-        p.in = (const h16_t*)in; p.wt = (const h16_t*)w_packed; p.bias = bias; p.res = (const h16_t*)residual; p.out = out; p.zero = zero_page();
-        p.M = B * Ho * Wo; p.N = Cout; p.Cin = Cin; p.n_rows = gp_packed_rows(Cout); p.ks = 3;
-        p.B = B; p.Hi = H; p.Wi = W; p.Ho = Ho; p.Wo = Wo; p.stride = 1; p.pad_t = 1; p.pad_l = 1;
-        p.ups = ups ? 1 : 0; p.Hu = ups ? Ho : 0; p.Wu = ups ? Wo : 0;
-        p.lda = Cin; p.ldo = Cout; p.ldres = Cout; p.ldw = 9 * Cin; p.n_store = Cout; p.act = act;
-        p.bias_mode = bias ? GP_BIAS_COL : GP_BIAS_NONE; p.batch = 1;
-        const size_t need = (size_t)groupnorm_ws_floats(B, H * W, Cin, groups) + 2 * (size_t)B * Cin;
-        float* g_gn_ws = scratch_floats(0, need);
-        float* scale = g_gn_ws + groupnorm_ws_floats(B, H * W, Cin, groups);
-        float* shift = scale + (size_t)B * Cin;
-        launch_groupnorm_stats((const h16_t*)in, gamma, beta, B, H * W, Cin, groups, eps, g_gn_ws, scale, shift, (hipStream_t)stream);
-        p.in_scale = scale; p.in_shift = shift; p.in_silu = silu;
-        if (!conv_uses_halo(p, 5)) return GP_ERR_INVALID;
-        launch_igemm(p, 5, (hipStream_t)stream);
-        HIPCHK(hipGetLastError());
-        return GP_OK;
-    } catch (...) { return GP_ERR_HIP; }
-}
-
-gp_status gp_rgb_conv_in(const void* rgb, int is_u8, const void* w_packed, const float* bias, void* out, int B, int H, int W, int Cout, void* stream) {
-    if (!rgb || !w_packed || !out || B < 1 || H < 1 || W < 1 || (Cout % 32)) return GP_ERR_INVALID;
-    h16_t* w27 = nullptr;
-    if (hipMalloc((void**)&w27, (size_t)Cout * 32 * sizeof(h16_t)) != hipSuccess) return GP_ERR_HIP;
-    launch_pack_k27((const h16_t*)w_packed, 9 * 64, Cout, w27, (hipStream_t)stream);
-    launch_rgb_conv_in(rgb, is_u8, w27, bias, (h16_t*)out, nullptr, B, H, W, Cout, (hipStream_t)stream);
-    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-    (void)hipFree(w27);
-    return (e == hipSuccess && hipGetLastError() == hipSuccess) ? GP_OK : GP_ERR_HIP;
-}
-
-gp_status gp_conv2d_stats(const void* in, const void* w_packed, const float* bias, const void* residual, void* out, int B, int H, int W, int Cin,
-                          int Cout, int ks, int ups, int tile_hint, const float* gamma, const float* beta, int groups, float eps,
-                          float* scale_out, float* shift_out, void* stream) {
-    if (!in || !w_packed || !out || !gamma || !beta || !scale_out || !shift_out || (Cin % 64) || (ks != 1 && ks != 3) || groups < 1 || (Cout % groups))
-        return GP_ERR_INVALID;
-    try {
-        KernelEntry lk;
-        const int Ho = ups ? 2 * H : H, Wo = ups ? 2 * W : W;
-        IGemmParams p{};
-        p.in = (const h16_t*)in; p.wt = (const h16_t*)w_packed; p.bias = bias; p.res = (const h16_t*)residual; p.out = out; p.zero = zero_page();
-        p.M = B * Ho * Wo; p.N = Cout; p.Cin = Cin; p.n_rows = gp_packed_rows(Cout); p.ks = ks;
-        p.B = B; p.Hi = H; p.Wi = W; p.Ho = Ho; p.Wo = Wo; p.stride = 1; p.pad_t = ks == 3; p.pad_l = ks == 3;
-        p.ups = ups ? 1 : 0; p.Hu = ups ? Ho : 0; p.Wu = ups ? Wo : 0;
-        p.lda = Cin; p.ldo = Cout; p.ldres = Cout; p.ldw = (ks == 3 ? 9 : 1) * Cin; p.n_store = Cout;
-        p.bias_mode = bias ? GP_BIAS_COL : GP_BIAS_NONE; p.batch = 1;
-        p.dbg = gp_sw().igemm_dbg;
-        int mode = 0, bm = 0;
-        const int nt = igemm_tile_info(p, tile_hint, &mode, &bm);
-        if (nt <= 0) return GP_ERR_INVALID;
-        const size_t need = (size_t)nt * (Cout * 2 + 1);
-        float* part = scratch_floats(1, need);
-        p.stats_out = part;
-        launch_igemm(p, tile_hint, (hipStream_t)stream);
-        launch_groupnorm_from_partials(part, mode, bm, B, Ho, Wo, Cout, groups, eps, gamma, beta, scale_out, shift_out, (hipStream_t)stream);
-        HIPCHK(hipGetLastError());
-        return GP_OK;
-    } catch (...) { return GP_ERR_HIP; }
-}
-
-gp_status gp_gemm(const void* a, int lda, const void* bt, int ldb, const float* bias, int bias_mode, const void* residual, int ldres, void* out,
-                  int ldo, int M, int N, int K, int n_rows_bt, int n_store, int act, int out_fp32, int batch, long long a_bs, long long bt_bs,
-                  long long out_bs, int tile_hint, void* stream) {
-    if (!a || !bt || !out || (K % 64)) return GP_ERR_INVALID;
-    try {
-        KernelEntry lk;
-        IGemmParams p{};
-        p.in = (const h16_t*)a; p.wt = (const h16_t*)bt; p.bias = bias; p.res = (const h16_t*)residual; p.out = out; p.zero = zero_page();
-        p.M = M; p.N = N; p.Cin = K; p.n_rows = n_rows_bt; p.ks = 1; p.stride = 1;
-        p.lda = lda; p.ldw = ldb; p.ldo = ldo; p.ldres = ldres; p.n_store = n_store > 0 ? n_store : N; p.out_fp32 = out_fp32; p.act = act;
-        p.bias_mode = bias ? bias_mode : GP_BIAS_NONE; p.batch = batch > 0 ? batch : 1; p.in_bs = a_bs; p.wt_bs = bt_bs; p.out_bs = out_bs;
-        p.dbg = gp_sw().igemm_dbg;  // profiling ablations (tools/kbench)
-        attach_splitk_scratch(p, tile_hint);
-        launch_igemm(p, tile_hint, (hipStream_t)stream);
-        HIPCHK(hipGetLastError());
-        return GP_OK;
-    } catch (...) { return GP_ERR_HIP; }
-}
-
-gp_status gp_decoder_tail(const void* in, const void* w_packed, const float* bias, const float* gamma, const float* beta, int groups, float eps,
-                          int B, int H, int W, int Cin, int mean3, int raw, float* out, void* stream) {
-    if (!in || !w_packed || !gamma || !beta || !out || B < 1 || !conv_few_applicable(Cin, 3, H, W) || (Cin % groups)) return GP_ERR_INVALID;
-    try {
-        KernelEntry lk;
-        const size_t need = (size_t)groupnorm_ws_floats(B, H * W, Cin, groups) + 2 * (size_t)B * Cin;
-        float* ws = scratch_floats(0, need);
-        float* scale = ws + groupnorm_ws_floats(B, H * W, Cin, groups);
-        float* shift = scale + (size_t)B * Cin;
-        launch_groupnorm_stats((const h16_t*)in, gamma, beta, B, H * W, Cin, groups, eps, ws, scale, shift, (hipStream_t)stream);
-        launch_conv_few((const h16_t*)in, (const h16_t*)w_packed, bias, scale, shift, zero_page(), out, B, H, W, 1, mean3, raw, 0, (hipStream_t)stream);
-        HIPCHK(hipGetLastError());
-        return GP_OK;
-    } catch (...) { return GP_ERR_HIP; }
-}
-
-gp_status gp_gemm_qkv(const void* a, int lda, const void* w_packed, int ldw, int n_rows_w, int K, void* qk_out, void* vt_out, int B, int T, int C,
-                      int Tpad, void* stream) {
-    if (!a || !w_packed || !qk_out || !vt_out || (K % 64) || B < 1 || T < 1 || C < 1 || Tpad < T) return GP_ERR_INVALID;
-    try {
-        KernelEntry lk;
-        IGemmParams p{};
-        p.in = (const h16_t*)a; p.wt = (const h16_t*)w_packed; p.out = qk_out; p.zero = zero_page();
-        p.M = B * T; p.N = 3 * C; p.Cin = K; p.n_rows = n_rows_w; p.ks = 1; p.stride = 1;
-        p.lda = lda; p.ldw = ldw; p.ldo = 2 * C; p.ldres = 2 * C; p.n_store = 2 * C; p.act = GP_ACT_NONE; p.bias_mode = GP_BIAS_NONE; p.batch = 1;
-        p.vt_out = (h16_t*)vt_out; p.vt_col0 = 2 * C; p.vt_T = T; p.vt_Tpad = Tpad;
-        p.dbg = gp_sw().igemm_dbg;
-        if (!igemm_uses_pgemm(p, 0)) return GP_ERR_INVALID;  // only the persistent GEMM has the transposed epilogue
-        if (Tpad != T) HIPCHK(hipMemsetAsync(vt_out, 0, (size_t)B * C * Tpad * sizeof(h16_t), (hipStream_t)stream));
-        launch_igemm(p, 0, (hipStream_t)stream);
-        HIPCHK(hipGetLastError());
-        return GP_OK;
-    } catch (...) { return GP_ERR_HIP; }
-}
-
-gp_status gp_groupnorm(const void* x, void* y, const float* gamma, const float* beta, int B, int HW, int C, int G, float eps, int silu, void* stream) {
-    if (!x || !y || !gamma || !beta || (C % 8) || (C % G)) return GP_ERR_INVALID;
-    try {
-        KernelEntry lk;
-        const size_t need = (size_t)groupnorm_ws_floats(B, HW, C, G) + 2 * (size_t)B * C;
-        float* g_gn_ws = scratch_floats(0, need);
-        if (groupnorm_small_applicable(B, HW, C, G)) launch_groupnorm_small((const h16_t*)x, (h16_t*)y, gamma, beta, B, HW, C, G, eps, silu, (hipStream_t)stream);
-        else launch_groupnorm((const h16_t*)x, (h16_t*)y, gamma, beta, B, HW, C, G, eps, silu, g_gn_ws, (hipStream_t)stream);
-        HIPCHK(hipGetLastError());
-        return GP_OK;
-    } catch (...) { return GP_ERR_HIP; }
-}
-
-gp_status gp_layernorm(const void* x, void* y, const float* gamma, const float* beta, int rows, int C, float eps, void* stream) {
-    if (!x || !y || (C % 8) || C > 4096) return GP_ERR_INVALID;
-    launch_layernorm((const h16_t*)x, (h16_t*)y, gamma, beta, rows, C, eps, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
-}
-
-gp_status gp_flash_attention(const void* q, const void* k, const void* vt, void* out, int B, int T, int heads, int ldq, int ldk, int Tpad, int ldo,
-                             void* stream) {
-    if (!q || !k || !vt || !out || (Tpad % 64) || Tpad < T) return GP_ERR_INVALID;
-    try {
-        KernelEntry lk;
-        launch_flash_attn64((const h16_t*)q, (const h16_t*)k, (const h16_t*)vt, (h16_t*)out, B, T, heads, ldq, ldk, Tpad, ldo,
-                            (hipStream_t)stream);
-        HIPCHK(hipGetLastError());
-        return GP_OK;
-    } catch (...) { return GP_ERR_HIP; }
-}
-
-gp_status gp_flash_attention_split(const float* qkv, int ld, void* out_split, int B, int T, int heads, void* stream) {
-    if (!qkv || !out_split || B < 1 || T < 1 || heads < 1 || ld < 3 * heads * 64 || (ld % 4) || !al16(qkv) || !al16(out_split) || GP_F16)
-        return GP_ERR_INVALID;  // (c_qk_planes_kernel reads float4 pairs: 16-byte aligned rows)
-    try {
-        KernelEntry lk;
-        const int C = heads * 64, Tpad = (T + 63) / 64 * 64;
-        const size_t n_qk = (size_t)B * T * 2 * C, n_vt = (size_t)B * heads * 64 * Tpad;
-        h16_t* buf = nullptr;
-        HIPCHK(hipMalloc((void**)&buf, (2 * n_qk + 2 * n_vt) * sizeof(h16_t)));
-        h16_t *qk_hi = buf, *qk_lo = buf + n_qk, *vt_hi = buf + 2 * n_qk, *vt_lo = vt_hi + n_vt;
-        launch_c_qkv_planes(qkv, ld, qk_hi, qk_lo, vt_hi, vt_lo, B, T, Tpad, heads, 64, (hipStream_t)stream);
-        launch_flash_attn64_split(qk_hi, qk_lo, vt_hi, vt_lo, (h16_t*)out_split, B, T, heads, 2 * C, Tpad, (hipStream_t)stream);
-        const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-        (void)hipFree(buf);
-        if (e != hipSuccess) return GP_ERR_HIP;
-        HIPCHK(hipGetLastError());
-        return GP_OK;
-    } catch (...) { return GP_ERR_HIP; }
-}
-
-// ---- contract-precision test entry points (bf16 library only): the launchers the engine's conv_c / linear_c / groupnorm use ---------------
-gp_status gp_c_split3(const float* x, int ldx, void* out, long long rows, int C, int b_order, int act, float scale, void* stream) {
-    if (GP_F16 || !x || !out || rows < 1 || C < 8 || (C % 8) || ldx < C || (ldx % 4) || !al16(x) || !al16(out) || (b_order != 0 && b_order != 1) ||
-        (act != GP_ACT_NONE && act != GP_ACT_RELU))  // (the acts the engine splits with: split_operand)
-        return GP_ERR_INVALID;
-    launch_c_split3(x, ldx, (h16_t*)out, rows, C, b_order, act, scale, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
-}
-
-gp_status gp_c_groupnorm_split(const float* x, void* out, const float* gamma, const float* beta, int B, int HW, int C, int G, float eps, int silu,
-                               float* scale_out, float* shift_out, void* stream) {
-    if (GP_F16 || !x || !out || !gamma || !beta || !scale_out || !shift_out || B < 1 || HW < 1 || C < 8 || (C % 8) || G < 1 || (C % G) || !al16(x) ||
-        !al16(out) || !al16(scale_out) || !al16(shift_out))
-        return GP_ERR_INVALID;
-    try {
-        KernelEntry lk;
-        float* part = scratch_floats(1, (size_t)B * c_gn_stat_rows(HW, C, nullptr) * (2 * C + 1));
-        launch_c_groupnorm_scale_shift(x, part, B, HW, 1, C, G, eps, gamma, beta, scale_out, shift_out, (hipStream_t)stream);
-        launch_c_gn_apply_split(x, (h16_t*)out, scale_out, shift_out, B, HW, C, silu ? 1 : 0, (hipStream_t)stream);
-        HIPCHK(hipGetLastError());
-        return GP_OK;
-    } catch (...) { return GP_ERR_HIP; }
-}
-
-gp_status gp_pack_weight_split(const float* w, int cout, int cin, int ks, int cin_pad, int geglu, void* dev_out) {
-    if (GP_F16 || !w || !dev_out || cout < 1 || cin < 1 || (ks != 1 && ks != 3) || cin_pad < cin || (cin_pad % 64)) return GP_ERR_INVALID;
-    try {
-        const int n_rows = gp_packed_rows(cout);
-        std::vector<h16_t> buf((size_t)n_rows * ks * ks * 3 * cin_pad, 0);
-        gp_engine::pack_rows(w, cout, cin, ks, cin_pad, geglu != 0, buf, 0, n_rows, true);
-        HIPCHK(hipMemcpy(dev_out, buf.data(), buf.size() * 2, hipMemcpyHostToDevice));
-        return GP_OK;
-    } catch (...) { return GP_ERR_HIP; }
-}
-
-gp_status gp_pack_weight_phases_split(const float* w, int cout, int cin, int cin_pad, void* dev_out) {
-    if (GP_F16 || !w || !dev_out || cout < 1 || cin < 1 || cin_pad < cin || (cin_pad % 64)) return GP_ERR_INVALID;
-    try {
-        std::vector<h16_t> buf((size_t)gp_packed_rows(cout) * 16 * 3 * cin_pad, 0);
-        gp_engine::pack_phase_rows(w, cout, cin, cin_pad, buf, true);
-        HIPCHK(hipMemcpy(dev_out, buf.data(), buf.size() * 2, hipMemcpyHostToDevice));
-        return GP_OK;
-    } catch (...) { return GP_ERR_HIP; }
-}
-
-gp_status gp_c_conv2d(const void* in_split, const void* w_packed, const void* w_phases, const float* bias, const float* residual, float* out, int B,
-                      int Hi, int Wi, int Cin, int Cout, int ks, int stride, int pad_t, int pad_l, int Ho, int Wo, int ups, int act, int tile_hint,
-                      const float* gamma, const float* beta, int groups, float eps, float* scale_out, float* shift_out, int* path_out, void* stream) {
-    const int nout = act == GP_ACT_GEGLU ? Cout / 2 : Cout;
-    if (GP_F16 || !in_split || !w_packed || !out || B < 1 || Hi < 1 || Wi < 1 || Ho < 1 || Wo < 1 || Cin < 64 || (Cin % 64) || Cout < 8 || (nout % 8) ||
-        (ks != 1 && ks != 3) || (stride != 1 && stride != 2) || (ups && (ks != 3 || stride != 1)) || (act == GP_ACT_GEGLU && (ks != 1 || (Cout % 16))) ||
-        (act != GP_ACT_NONE && act != GP_ACT_GEGLU && act != GP_ACT_SILU && act != GP_ACT_RELU) || !al16(in_split) || !al16(w_packed) || !al16(out) ||
-        !al16(residual) || !al16(bias) || !al16(w_phases))
-        return GP_ERR_INVALID;
-    const bool stats = gamma != nullptr;
-    if (stats && (!beta || !scale_out || !shift_out || groups < 1 || (nout % groups) || act == GP_ACT_GEGLU || !al16(scale_out) || !al16(shift_out)))
-        return GP_ERR_INVALID;
-    try {
-        KernelEntry lk;
-        // the engine's own parameter setup (gp_engine::conv_c / linear_c) on stand-ins for its operand and packed weight
-        Act xs;
-        xs.p = (h16_t*)in_split; xs.B = B; xs.H = Hi; xs.W = Wi; xs.C = 3 * Cin;
-        PackedW pw;
-        pw.w = (h16_t*)w_packed; pw.w_ph = (h16_t*)w_phases; pw.bias = (float*)bias; pw.cout = Cout; pw.cin_pad = 3 * Cin; pw.ks = ks;
-        pw.n_rows = gp_packed_rows(Cout);
-        IGemmParams p;
-        if (ks == 1 && stride == 1 && !ups && Ho == Hi && Wo == Wi) {  // a linear layer (linear_c)
-            p = gp_engine::linear_c_params(xs, pw, residual, act, out, zero_page());
-        } else {
-            gp_engine::ConvOpt o;
-            o.stride = stride; o.pad_t = pad_t; o.pad_l = pad_l; o.Ho = Ho; o.Wo = Wo; o.ups_h = ups ? 2 * Hi : 0; o.ups_w = ups ? 2 * Wi : 0;
-            o.res_f = residual; o.act = act;
-            p = gp_engine::conv_c_params(xs, pw, o, out, zero_page());
-        }
-        p.dbg = gp_sw().igemm_dbg;
-        attach_splitk_scratch(p, tile_hint);
-        if (path_out) *path_out = igemm_path(p, tile_hint);
-        launch_igemm(p, tile_hint, (hipStream_t)stream);
-        if (stats) {
-            float* part = scratch_floats(1, (size_t)B * c_gn_stat_rows(Ho * Wo, nout, nullptr) * (2 * nout + 1));
-            launch_c_groupnorm_scale_shift(out, part, B, Ho, Wo, nout, groups, eps, gamma, beta, scale_out, shift_out, (hipStream_t)stream);
-        }
-        HIPCHK(hipGetLastError());
-        return GP_OK;
-    } catch (...) { return GP_ERR_HIP; }
-}
-
-gp_status gp_c_layernorm_split(const float* x, void* out, const float* gamma, const float* beta, int rows, int C, float eps, void* stream) {
-    if (GP_F16 || !x || !out || !gamma || !beta || rows < 1 || C < 8 || (C % 8) || !al16(x) || !al16(out) || !al16(gamma) || !al16(beta))
-        return GP_ERR_INVALID;
-    launch_c_layernorm_split(x, (h16_t*)out, gamma, beta, rows, C, eps, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
-}
-
-gp_status gp_c_softmax_split(const float* in, void* out, int rows, int T, int ld, float scale, void* stream) {
-    if (GP_F16 || !in || !out || rows < 1 || T < 1 || ld < T || !c_softmax_split_supported(ld) || !al16(in) || !al16(out)) return GP_ERR_INVALID;
-    launch_c_softmax_split(in, (h16_t*)out, rows, T, ld, scale, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
-}
-
-gp_status gp_flash_attention_hd512(const void* q, const void* k, const void* vt, void* out, int B, int T, int ldq, int ldk, int Tpad, int ldo,
-                                   float scale, int ncu, void* stream) {
-    if (!q || !k || !vt || !out || (Tpad % 64) || Tpad < T || B < 1 || T < 1 || ncu < 0) return GP_ERR_INVALID;
-    try {
-        KernelEntry lk;
-        if (ncu == 0) {
-            int dev = 0;
-            hipDeviceProp_t pr;
-            HIPCHK(hipGetDevice(&dev));
-            HIPCHK(hipGetDeviceProperties(&pr, dev));
-            ncu = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
-        }
-        const long long wsf = flash_attn512_workspace_floats(B, T, ncu);
-        float* ws = wsf ? scratch_floats(2, (size_t)wsf) : nullptr;
-        launch_flash_attn512((const h16_t*)q, (const h16_t*)k, (const h16_t*)vt, (h16_t*)out, ws, B, T, ldq, ldk, Tpad, ldo, scale,
-                             ncu, (hipStream_t)stream);
-        HIPCHK(hipGetLastError());
-        return GP_OK;
-    } catch (...) { return GP_ERR_HIP; }
-}
-
-gp_status gp_cross_attention(const void* q, const float* kc, const float* vc, void* out, int rows, int C, int L, void* stream) {
-    if (!q || !kc || !vc || !out || (C % 64)) return GP_ERR_INVALID;
-    launch_cross_attn_small((const h16_t*)q, kc, vc, (h16_t*)out, rows, C, L, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
-}
-
-gp_status gp_cross_attention_fold(const void* y, void* y_out, void* n3_out, const float* U, const float* u0, const float* G, const float* c0,
-                                  const float* g3, const float* b3, int rows, int C, int heads, float eps, void* stream) {
-    if (!y || !y_out || !U || !u0 || !G || !c0 || !cross_attn_fold_supported(C, heads) || (n3_out && (!g3 || !b3))) return GP_ERR_INVALID;
-    gp_switches_reload();
-    launch_cross_attn_fold((const h16_t*)y, (h16_t*)y_out, (h16_t*)n3_out, U, u0, G, c0, g3, b3, rows, C, heads, eps, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
-}
-
-void gp_resize_max_res_size(int H0, int W0, int max_edge, int* h, int* w) {
-    // image_util.py:95-101: downscale_factor = min(max / W, max / H) in double, new size by int() truncation
-    const double f = std::min((double)max_edge / (double)W0, (double)max_edge / (double)H0);
-    if (h) *h = (int)((double)H0 * f);
-    if (w) *w = (int)((double)W0 * f);
-}
-
-gp_status gp_preprocess(const void* rgb_u8, int B, int H0, int W0, void* out_u8, int h, int w, int resample, float* tmp, void* stream) {
-    if (!rgb_u8 || !out_u8 || B < 1 || H0 < 1 || W0 < 1 || h < 1 || w < 1 || resample < 0 || resample > 2 || (resample != 1 && !tmp)) return GP_ERR_INVALID;
-    launch_resize(rgb_u8, out_u8, tmp, (long long)B * 3, H0, W0, h, w, resample, 1, 0, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
-}
-
-gp_status gp_preprocess_f32(const float* rgb, int B, int C, int H0, int W0, float* out, int h, int w, int resample, int normalize, float* tmp, void* stream) {
-    if (!rgb || !out || B < 1 || C < 1 || H0 < 1 || W0 < 1 || h < 1 || w < 1 || resample < 0 || resample > 2) return GP_ERR_INVALID;
-    const bool same = h == H0 && w == W0;
-    if (!same && resample != 1 && !tmp) return GP_ERR_INVALID;
-    if (same && !normalize && rgb != out) return GP_ERR_INVALID;  // nothing to do but a copy: the caller keeps its tensor
-    hipStream_t s = (hipStream_t)stream;
-    if (!same) launch_resize(rgb, out, tmp, (long long)B * C, H0, W0, h, w, resample, 0, 0, s);
-    if (normalize) launch_normalize_rgb(same ? rgb : out, out, (long long)B * C * h * w, s);
-    return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
-}
-
-gp_status gp_postprocess(const float* pred, int B, int C, int h, int w, float* pred_out, int Ho, int Wo, int resample, float* tmp,
-                         const unsigned char* lut_dev, void* colored_out, void* q_out, int q_bits, void* stream) {
-    if (!pred || !pred_out || B < 1 || C < 1 || h < 1 || w < 1 || Ho < 1 || Wo < 1 || resample < 0 || resample > 2) return GP_ERR_INVALID;
-    if (colored_out && (!lut_dev || C != 1)) return GP_ERR_INVALID;
-    if (q_out && q_bits != 16 && q_bits != 8) return GP_ERR_INVALID;
-    const bool same = h == Ho && w == Wo;
-    if (!same && resample != 1 && !tmp) return GP_ERR_INVALID;
-    hipStream_t s = (hipStream_t)stream;
-    const long long n = (long long)B * C * Ho * Wo;
-    if (same) launch_clip01(pred, pred_out, n, s);
-    else launch_resize(pred, pred_out, tmp, (long long)B * C, h, w, Ho, Wo, resample, 0, 1, s);
-    if (colored_out) launch_colorize_lut(pred_out, lut_dev, (unsigned char*)colored_out, n, s);
-    if (q_out) launch_quantize(pred_out, q_out, n, q_bits, s);
-    return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
-}
-
-double gp_mfma_peak_tflops(int device, void* stream) {
-    if (hipSetDevice(device) != hipSuccess) return -1.0;
-    return mfma_peak_tflops(20, (hipStream_t)stream);
-}
-double gp_mfma_peak_tflops_shape(int device, int shape, void* stream) {
-    if (hipSetDevice(device) != hipSuccess || (shape != 0 && shape != 1)) return -1.0;
-    return mfma_peak_tflops(20, (hipStream_t)stream, shape);
-}
-
-double gp_mfma_lds_probe(int device, int reads_per_16_mfma, int waves_per_simd, int mode, void* stream) {
-    if (hipSetDevice(device) != hipSuccess) return -1.0;
-    return mfma_lds_probe_tflops(reads_per_16_mfma, waves_per_simd, mode, (hipStream_t)stream);
-}
-
-gp_status gp_softmax_rows(const float* in, void* out, int rows, int T, int ld, float scale, void* stream) {
-    if (!in || !out || ld < T) return GP_ERR_INVALID;
-    launch_softmax_rows(in, (h16_t*)out, rows, T, ld, scale, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
-}
-
-gp_status gp_softmax_rows_f16(const void* in_f16, void* out, int rows, int T, int ld, float scale, void* stream) {
-    if (!in_f16 || !out || ld < T || !softmax_rows_f16_supported(ld) || scale <= 0.f) return GP_ERR_INVALID;
-    launch_softmax_rows_f16(in_f16, (h16_t*)out, rows, T, ld, scale, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
-}
-
-gp_status gp_bilinear(const void* in, void* out, int B, int Hi, int Wi, int Ho, int Wo, int C, int align_corners, void* stream) {
-    if (!in || !out || (C % 8)) return GP_ERR_INVALID;
-    launch_bilinear((const h16_t*)in, (h16_t*)out, B, Hi, Wi, Ho, Wo, C, align_corners, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
 }
 
 }  // extern "C"

@@ -135,6 +135,13 @@ void launch_groupnorm_apply(const h16_t* x, h16_t* y, const float* scale, const 
 void launch_groupnorm(const h16_t* x, h16_t* y, const float* gamma, const float* beta, int B, int HW, int C, int G, float eps,
                       int silu, float* ws, hipStream_t s);
 int groupnorm_ws_floats(int B, int HW, int C, int G);
+// The workspace of launch_groupnorm / launch_groupnorm_stats: [partial statistics | scale [B][C] | shift [B][C]].  Returns the floats it needs; with
+// `ws` given also where scale and shift live in it.
+inline size_t groupnorm_ws_layout(int B, int HW, int C, int G, float* ws = nullptr, float** scale = nullptr, float** shift = nullptr) {
+    const size_t part = (size_t)groupnorm_ws_floats(B, HW, C, G), bc = (size_t)B * C;
+    if (ws) { *scale = ws + part; *shift = *scale + bc; }
+    return part + 2 * bc;
+}
 // small maps (a group's HW x C/G block fits one workgroup's loop; (C / G) % 8 == 0): statistics + apply in one launch
 bool groupnorm_small_applicable(int B, int HW, int C, int G);
 void launch_groupnorm_small(const h16_t* x, h16_t* y, const float* gamma, const float* beta, int B, int HW, int C, int G, float eps, int silu,

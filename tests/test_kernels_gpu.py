@@ -220,7 +220,7 @@ UP2_CASES = [
 
 
 def _phase_weights(wt):
-    """[O][C][3][3] -> {(a, b): [O][C][2][2]}: kernel rows / columns that fall onto the same source pixel summed (engine.hip: pack_phase_rows)"""
+    """[O][C][3][3] -> {(a, b): [O][C][2][2]}: kernel rows / columns that fall onto the same source pixel summed (host_pack.h: pack_phase_rows)"""
     rng = {0: [(0, 0), (1, 2)], 1: [(0, 1), (2, 2)]}
     out = {}
     for a in (0, 1):

@@ -122,7 +122,7 @@ def gn_ratios(dtype):
     return (0, 8, 32) if dtype == torch.bfloat16 else (0, 8, 32, 256)
 
 
-# (name, B, C, HW, silu, sigma, env) -- the kernel each case is for, with the launcher's selecting condition (norm.hip, engine.hip gp_groupnorm:
+# (name, B, C, HW, silu, sigma, env) -- the kernel each case is for, with the launcher's selecting condition (norm.hip, kernel_abi.hip gp_groupnorm:
 # one-launch kernels iff (C / 32) % 8 == 0 and items = HW * (C / 32 / 8) <= 8192; statistics pass <1> iff C / 8 <= 256, else <2>).
 # sigma = spread of the data (2^-6: the variance is comparable to eps, so eps 1e-5 and 1e-6 differ visibly).
 GN_CASES = [

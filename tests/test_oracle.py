@@ -217,7 +217,7 @@ def test_upsample_conv_phase_identity(shape):
     custom_unet.py:372-400's up blocks and the VAE decoder): output pixel (2y + a, 2x + b) of conv3x3(upsample2(s)) is a 2 x 2-tap convolution of the
     SOURCE map with the kernel rows / columns that fall onto the same source pixel summed -- a = 0: {w0}, {w1 + w2}; a = 1: {w0 + w1}, {w2} -- and the
     zero padding of the upsampled map is the zero padding of the source map.  Checked in float64 on maps with odd sizes down to one pixel; the kernel's
-    own packing (engine.hip: pack_phase_rows) is checked against this construction on the GPU (tests/test_kernels_gpu.py)."""
+    own packing (host_pack.h: pack_phase_rows) is checked against this construction on the GPU (tests/test_kernels_gpu.py)."""
     import torch.nn.functional as F
     b, c, h, w = shape
     g = torch.Generator().manual_seed(h * 100 + w)
