@@ -3,6 +3,10 @@
 // HIP stream.  Exposed through the gp_engine* part of the C-ABI of include/genpercept_hip.h (the stateless per-kernel entry points are
 // kernel_abi.hip); every conv / GEMM launch is filled by a builder of igemm_problem.h, the same one the matching entry point calls.
 //
+// Both precisions run ONE set of layer ops and schedules.  An `Act` is either a 16-bit tensor / split operand (`p`) or a stored fp32 tensor (`f`);
+// new_stored / new_product_input allocate the form the precision uses, conv / linear pick `.p` or `.f` of their input, residual and in-place target,
+// and each kernel pair (X / c_X) is chosen in one small op.  Only attention_c, the split-operand attention, has no 16-bit twin.
+//
 // Control flow mirrors (never copies) the reference: genpercept/genpercept_pipeline.py:399-526 (single_infer,
 // encode_rgb, decode_pred), genpercept/models/custom_unet.py:109-119,146-170,273,305-415 (UNet forward, skip order,
 // upsample_size, multi_level_feats), genpercept/models/dpt_head.py:213-335,443-582 (DPT neck/head); module internals
@@ -472,7 +476,6 @@ struct gp_engine {
             std::vector<h16_t> z(2048, 0);
             zero = upload(z.data(), z.size());
         }
-        const bool have_vae = has("vae.encoder.conv_in.weight") || has("vae.decoder.conv_in.weight");
         const bool have_unet = has("unet.conv_in.weight");
         // ---------------- VAE ----------------
         if (has("vae.encoder.conv_in.weight")) {
@@ -583,7 +586,6 @@ struct gp_engine {
             dpt_w_dev = upload(w4.v.data(), w4.v.size());
             dpt_b = H("dpt.head.head.4.bias").v[0];
         }
-        (void)have_vae;
         host.clear();
         finalized = true;
     }
@@ -612,6 +614,18 @@ struct gp_engine {
         return a;
     }
     Act new_operand(int B, int H, int W, int C_logical) { return new_act(B, H, W, 3 * C_logical); }
+    // ---- the two allocation verbs of the layer ops and stages -----------------------------------------------------------------------------
+    // a tensor this precision STORES: 16-bit `p`, or fp32 `f` in contract precision
+    Act new_stored(int B, int H, int W, int C) {
+        if (contract) return new_act_f(B, H, W, C);
+        return new_act(B, H, W, C);
+    }
+    // the input of a matrix product over C channels: 16-bit `p` of width C, or the split operand of width 3 C
+    Act new_product_input(int B, int H, int W, int C) {
+        if (contract) return new_operand(B, H, W, C);
+        return new_act(B, H, W, C);
+    }
+    static void* data(const Act& a) { return a.f ? (void*)a.f : (void*)a.p; }
     // A-order split of a stored tensor (optionally through ReLU): the operand form a conv / linear layer reads
     Act split_operand(const Act& x, int act = GP_ACT_NONE) {
         if (!x.f) throw std::logic_error("split_operand: not a stored fp32 tensor");
@@ -700,65 +714,45 @@ struct gp_engine {
     }
 
     struct ConvOpt : ConvForm {
-        const float* res_f = nullptr;  // contract precision: the residual is a stored fp32 tensor
-        bool want_stats = false;  // the output feeds a GroupNorm
+        const Act* residual = nullptr;  // added to the output; conv fills ConvForm::res (16-bit) or the fp32 residual (contract precision) from it
+        bool want_stats = false;        // the output feeds a GroupNorm
     };
     static Nhwc nhwc(const Act& a) { return {a.p, a.B, a.H, a.W, a.C}; }
-    // contract precision: split operand in (made here when x is a stored tensor), fp32 rows out, fp32 residual
-    Act conv_c(const Act& x0, const PackedW& w, const ConvOpt& o) {
-        Act xs = x0;
-        const bool tmp = x0.p == nullptr;
-        if (tmp) xs = split_operand(x0);
-        IGemmParams p = igemm_conv(nhwc(xs), w, o, nullptr, zero);
-        igemm_contract(p, o.res_f);
-        Act y = new_act_f(xs.B, p.Ho, p.Wo, p.n_store);
-        p.out = y.f;
-        if (o.want_stats) attach_stats(y, p);
-        run_igemm(p);
-        if (tmp) drop(xs);
-        return y;
+    ConvForm conv_form(const ConvOpt& o) const {
+        ConvForm f = o;
+        if (o.residual && !contract) f.res = o.residual->p;
+        return f;
     }
-    Act conv(const Act& x, const PackedW& w, const ConvOpt& o, const float* in_scale = nullptr, const float* in_shift = nullptr, bool in_silu = false) {
-        if (contract) return conv_c(x, w, o);
-        IGemmParams p = igemm_conv(nhwc(x), w, o, nullptr, zero);
-        Act y = new_act(x.B, p.Ho, p.Wo, p.n_store);
-        p.out = y.p;
-        p.in_scale = in_scale; p.in_shift = in_shift; p.in_silu = in_silu ? 1 : 0;
-        if (in_scale && !conv_uses_halo(p, 0)) throw std::logic_error("fused GroupNorm input needs the halo conv kernel");
-        if (o.want_stats) attach_stats(y, p);
-        run_igemm(p);
-        return y;
-    }
-    // y[M][N] = x[M][K] W^T (+bias) (+res), N = w.cout (GEGLU halves it)
-    // contract precision: y fp32 [M][N] = split(x) W^T (+bias) (+res fp32); out_inplace: write into that fp32 buffer (it may be `res`)
-    Act linear_c(const Act& x0, const PackedW& w, const float* res = nullptr, int act = GP_ACT_NONE, float* out_inplace = nullptr, bool want_stats = false) {
-        Act xs = x0;
-        const bool tmp = x0.p == nullptr;
-        if (tmp) xs = split_operand(x0);
-        IGemmParams p = igemm_linear(nhwc(xs), w, nullptr, act, out_inplace, zero);
-        igemm_contract(p, res);
-        Act y;
-        if (out_inplace) { y.B = xs.B; y.H = xs.H; y.W = xs.W; y.C = p.n_store; y.f = out_inplace; }
-        else y = new_act_f(xs.B, xs.H, xs.W, p.n_store);
-        p.out = y.f;
-        if (want_stats && !out_inplace) attach_stats(y, p);
-        run_igemm(p);
-        if (tmp) drop(xs);
-        return y;
-    }
-    Act linear(const Act& x, const PackedW& w, const h16_t* res = nullptr, int act = GP_ACT_NONE, h16_t* out_inplace = nullptr,
-               bool want_stats = false) {
-        if (contract) {
-            if (res || out_inplace) throw std::logic_error("linear: 16-bit residual in contract precision");
-            return linear_c(x, w, nullptr, act, nullptr, want_stats);
+    // Contract precision, in both ops: the product reads a split operand (a stored input is split on entry and the temporary dropped after the
+    // launch), writes fp32 rows and adds an fp32 residual (igemm_contract).
+    // in_scale / in_shift / in_silu: GroupNorm(+SiLU) applied to the staged input inside the halo conv kernel (16-bit only, see conv_gn)
+    Act conv(const Act& x0, const PackedW& w, const ConvOpt& o, const float* in_scale = nullptr, const float* in_shift = nullptr, bool in_silu = false) {
+        const bool split = contract && !x0.p;
+        Act x = split ? split_operand(x0) : x0;
+        IGemmParams p = igemm_conv(nhwc(x), w, conv_form(o), nullptr, zero);
+        if (contract) igemm_contract(p, o.residual ? o.residual->f : nullptr);
+        Act y = new_stored(x.B, p.Ho, p.Wo, p.n_store);
+        p.out = data(y);
+        if (!contract) {
+            p.in_scale = in_scale; p.in_shift = in_shift; p.in_silu = in_silu ? 1 : 0;
+            if (in_scale && !conv_uses_halo(p, 0)) throw std::logic_error("fused GroupNorm input needs the halo conv kernel");
         }
-        IGemmParams p = igemm_linear(nhwc(x), w, res, act, out_inplace, zero);
-        Act y;
-        if (out_inplace) { y = x; y.C = p.n_store; y.p = out_inplace; }
-        else y = new_act(x.B, x.H, x.W, p.n_store);
-        p.out = y.p;
-        if (want_stats && !out_inplace) attach_stats(y, p);
+        if (o.want_stats) attach_stats(y, p);
         run_igemm(p);
+        if (split) drop(x);
+        return y;
+    }
+    // y[M][N] = x[M][K] W^T (+bias) (+res), N = w.cout (GEGLU halves it); inplace: write into that tensor (it may be `res`) instead of a new one
+    Act linear(const Act& x0, const PackedW& w, const Act* res = nullptr, int act = GP_ACT_NONE, const Act* inplace = nullptr, bool want_stats = false) {
+        const bool split = contract && !x0.p;
+        Act x = split ? split_operand(x0) : x0;
+        IGemmParams p = igemm_linear(nhwc(x), w, res && !contract ? res->p : nullptr, act, nullptr, zero);
+        if (contract) igemm_contract(p, res ? res->f : nullptr);
+        Act y = inplace ? *inplace : new_stored(x.B, x.H, x.W, p.n_store);
+        p.out = data(y);
+        if (want_stats && !inplace) attach_stats(y, p);
+        run_igemm(p);
+        if (split) drop(x);
         return y;
     }
     // V^T[b][c][t] = sum_k Wv[c][k] x[b][t][k] (+ bias[c]); zero-filled up to Tpad
@@ -804,20 +798,19 @@ struct gp_engine {
         launch_groupnorm_small(x.p, y.p, n.g, n.b, x.B, x.H * x.W, x.C, cfg.norm_groups, eps, silu ? 1 : 0, st);
         return y;
     }
+    // x * scale + shift (+ SiLU); the normalised tensor only ever feeds a matrix product (contract precision: written as its split operand)
+    Act gn_apply(const Act& x, const float* scale, const float* shift, bool silu) {
+        Act y = new_product_input(x.B, x.H, x.W, x.C);
+        mark((contract ? "c_gn_apply_split " : "gn_apply ") + dims(x));
+        if (contract) launch_c_gn_apply_split(x.f, y.p, scale, shift, x.B, x.H * x.W, x.C, silu ? 1 : 0, st);
+        else launch_groupnorm_apply(x.p, y.p, scale, shift, x.B, x.H * x.W, x.C, silu ? 1 : 0, st);
+        return y;
+    }
     Act groupnorm(const Act& x, const NormW& n, float eps, bool silu) {
         if (gn_small(x)) return groupnorm_small(x, n, eps, silu);
         float *scale, *shift;
         gn_scale_shift(x, n, eps, scale, shift);
-        if (contract) {  // the normalised tensor only ever feeds a matrix product: written as its split operand
-            Act y = new_operand(x.B, x.H, x.W, x.C);
-            mark("c_gn_apply_split " + dims(x));
-            launch_c_gn_apply_split(x.f, y.p, scale, shift, x.B, x.H * x.W, x.C, silu ? 1 : 0, st);
-            return y;
-        }
-        Act y = new_act(x.B, x.H, x.W, x.C);
-        mark("gn_apply " + dims(x));
-        launch_groupnorm_apply(x.p, y.p, scale, shift, x.B, x.H * x.W, x.C, silu ? 1 : 0, st);
-        return y;
+        return gn_apply(x, scale, shift, silu);
     }
     float* gn_workspace(const Act& x) {  // partial statistics + per-(image, channel) scale / shift
         const size_t need = groupnorm_ws_layout(x.B, x.H * x.W, x.C, cfg.norm_groups);
@@ -832,24 +825,17 @@ struct gp_engine {
     // conv(act(GroupNorm(x))): statistics pass, then the normalisation is applied either inside the conv kernel on the staged
     // input halo (conv_halo.hip) or, when that kernel does not take the layer, by the separate apply pass.
     Act conv_gn(const Act& x, const NormW& n, float eps, bool silu, const PackedW& w, const ConvOpt& o) {
-        if (contract) {
+        // the separate GroupNorm (contract precision: it writes the split operand; small maps without statistics: one launch) unless a halo
+        // conv would fuse the apply: keep the statistics path for that
+        if (contract || (gn_small(x) && !conv_uses_halo(igemm_conv(nhwc(x), w, conv_form(o), nullptr, zero), 0))) {
             Act y = groupnorm(x, n, eps, silu);
             Act out = conv(y, w, o);
             drop(y);
             return out;
         }
-        if (gn_small(x)) {
-            const IGemmParams p0 = igemm_conv(nhwc(x), w, o, nullptr, zero);
-            if (!conv_uses_halo(p0, 0)) {  // (a halo conv would fuse the apply: keep the statistics path for it)
-                Act y = groupnorm_small(x, n, eps, silu);
-                Act out = conv(y, w, o);
-                drop(y);
-                return out;
-            }
-        }
         float *scale, *shift;
         gn_scale_shift(x, n, eps, scale, shift);
-        IGemmParams p = igemm_conv(nhwc(x), w, o, nullptr, zero);
+        IGemmParams p = igemm_conv(nhwc(x), w, conv_form(o), nullptr, zero);
         p.in_scale = scale; p.in_shift = shift; p.in_silu = silu ? 1 : 0;
         // The fused transform is redone by every 128-channel slice of the output (each slice's workgroup stages its own halo) and it is
         // bound by the two quarter-rate transcendentals per element inside the conv.  One separate apply pass -- 2 x tensor bytes of HBM
@@ -858,23 +844,16 @@ struct gp_engine {
         const int slices = (w.cout + 127) / 128;
         const bool fuse_here = slices <= gn_fuse_max_slices || x.H * x.W < gn_fuse_always_below_px;
         if (fuse_gn && fuse_here && conv_uses_halo(p, 0)) return conv(x, w, o, scale, shift, silu);
-        Act y = new_act(x.B, x.H, x.W, x.C);
-        mark("gn_apply " + dims(x));
-        launch_groupnorm_apply(x.p, y.p, scale, shift, x.B, x.H * x.W, x.C, silu ? 1 : 0, st);
+        Act y = gn_apply(x, scale, shift, silu);
         Act out = conv(y, w, o);
         drop(y);
         return out;
     }
     Act layernorm(const Act& x, const NormW& n) {
-        if (contract) {
-            Act y = new_operand(x.B, x.H, x.W, x.C);
-            mark("c_layernorm_split " + dims(x));
-            launch_c_layernorm_split(x.f, y.p, n.g, n.b, (int)x.pixels(), x.C, 1e-5f, st);
-            return y;
-        }
-        Act y = new_act(x.B, x.H, x.W, x.C);
-        mark("layernorm " + dims(x));
-        launch_layernorm(x.p, y.p, n.g, n.b, (int)x.pixels(), x.C, 1e-5f, st);
+        Act y = new_product_input(x.B, x.H, x.W, x.C);
+        mark((contract ? "c_layernorm_split " : "layernorm ") + dims(x));
+        if (contract) launch_c_layernorm_split(x.f, y.p, n.g, n.b, (int)x.pixels(), x.C, 1e-5f, st);
+        else launch_layernorm(x.p, y.p, n.g, n.b, (int)x.pixels(), x.C, 1e-5f, st);
         return y;
     }
 
@@ -886,8 +865,7 @@ struct gp_engine {
         Act sc = x;
         if (r.has_sc) sc = linear(x, r.sc);
         ConvOpt o;
-        o.res = sc.p;
-        o.res_f = sc.f;
+        o.residual = &sc;
         o.want_stats = true;
         Act y = conv_gn(h, r.n2, eps, true, r.c2, o);
         drop(h);
@@ -970,64 +948,20 @@ struct gp_engine {
         tm.n_attn++;
         return a;
     }
-    Act vae_attention_c(const Act& x, const VaeAttnW& a) {
-        Act n = groupnorm(x, a.gn, cfg.vae_norm_eps, false);
-        Act qkv = linear_c(n, a.qkv);
-        drop(n);
-        Act o = attention_c(qkv, 1, a.C, 1.0f / std::sqrt((float)a.C));
-        drop(qkv);
-        Act y = linear_c(o, a.o, x.f, GP_ACT_NONE, nullptr, true);
-        drop(o);
-        return y;
-    }
-    // BasicTransformerBlock inside Transformer2DModel (custom_unet.py call sites :305-327,341-352), contract precision
-    Act transformer_c(const Act& x, const TfW& t) {
-        const int C = t.C;
-        Act n = groupnorm(x, t.gn, 1e-6f, false);
-        Act y = linear_c(n, t.proj_in);
-        drop(n);
-        Act l1 = layernorm(y, t.ln1);
-        Act qkv = linear_c(l1, t.qkv);
-        drop(l1);
-        Act a = attention_c(qkv, t.heads, 64, 0.125f);
-        drop(qkv);
-        linear_c(a, t.o1, y.f, GP_ACT_NONE, y.f);  // y += to_out(attn), in place
-        drop(a);
-        Act l3;
-        if (t.fU && c_cross_fold_supported(C)) {
-            l3 = new_operand(x.B, x.H, x.W, C);
-            mark("c_cross_fold " + dims(y));
-            launch_c_cross_fold(y.f, y.f, l3.p, t.fU, t.fu0, t.fG, t.fc0, t.ln3.g, t.ln3.b, (int)x.pixels(), C, t.heads, 1e-5f, st);
-        } else {
-            Act l2 = layernorm(y, t.ln2);
-            Act q2 = linear_c(l2, t.q2);
-            drop(l2);
-            Act a2 = new_operand(x.B, x.H, x.W, C);
-            mark("c_cross_attn_small " + dims(q2));
-            launch_c_cross_attn_small(q2.f, t.kc, t.vc, a2.p, (int)x.pixels(), C, ctx_L, st);
-            drop(q2);
-            linear_c(a2, t.o2, y.f, GP_ACT_NONE, y.f);
-            drop(a2);
-            l3 = layernorm(y, t.ln3);
+    // VAE self-attention, head_dim 512 = C, one head: the GroupNorm output (released here, as soon as q, k and v are enqueued) -> the input of to_out
+    Act vae_self_attention(Act& n, const VaeAttnW& a) {
+        if (contract) {  // stacked q | k | v, stored, then the split attention
+            Act qkv = linear(n, a.qkv);
+            drop(n);
+            Act o = attention_c(qkv, 1, a.C, 1.0f / std::sqrt((float)a.C));
+            drop(qkv);
+            return o;
         }
-        Act ff = linear_c(l3, t.ff1, nullptr, GP_ACT_GEGLU);
-        drop(l3);
-        linear_c(ff, t.ff2, y.f, GP_ACT_NONE, y.f);
-        drop(ff);
-        Act out = linear_c(y, t.proj_out, x.f, GP_ACT_NONE, nullptr, true);
-        drop(y);
-        return out;
-    }
-
-    Act vae_attention(const Act& x, const std::string& name) {
-        const VaeAttnW& a = vattn.at(name);
-        if (contract) return vae_attention_c(x, a);
-        const int T = x.H * x.W, C = a.C, Tpad = round_up(T, 64), B = x.B;
-        Act n = groupnorm(x, a.gn, cfg.vae_norm_eps, false);
+        const int T = n.H * n.W, C = a.C, Tpad = round_up(T, 64), B = n.B;
         Act qk = linear(n, a.qk);  // [B*T][2C]
         h16_t* vt = v_transposed(n, a.v, T, Tpad);
         drop(n);
-        Act o = new_act(x.B, x.H, x.W, C);
+        Act o = new_act(qk.B, qk.H, qk.W, C);
         if (flash_attn512_supported(C)) {
             // fused: scores and probabilities never leave the CU (attention.hip: flash_attn512_kernel).  The softmax scale 1/sqrt(C) is
             // folded into the query projection (build_vae_attn), logits exist in fp32 registers only.
@@ -1041,28 +975,32 @@ struct gp_engine {
             launch_flash_attn512(qk.p, qk.p + C, vt, o.p, ws, B, T, 2 * C, 2 * C, Tpad, C, 1.0f, ncu, st);
             prof_end();
             if (ws) pool.release(ws);
-            drop(qk);
-            pool.release(vt);
         } else {
             vae_attention_unfused(qk, vt, o, B, T, Tpad, C);
-            drop(qk);
-            pool.release(vt);
         }
-        Act y = linear(o, a.o, x.p, GP_ACT_NONE, nullptr, true);
+        drop(qk);
+        pool.release(vt);
+        return o;
+    }
+    Act vae_attention(const Act& x, const std::string& name) {
+        const VaeAttnW& a = vattn.at(name);
+        Act n = groupnorm(x, a.gn, cfg.vae_norm_eps, false);
+        Act o = vae_self_attention(n, a);
+        Act y = linear(o, a.o, &x, GP_ACT_NONE, nullptr, true);
         drop(o);
         return y;
     }
 
-    Act transformer(const Act& x, const std::string& name) {
-        const TfW& t = tfs.at(name);
-        if (!t.kc) throw std::logic_error("gp_set_context has not been called");
-        if (contract) return transformer_c(x, t);
-        const int T = x.H * x.W, C = t.C, Tpad = round_up(T, 64);
-        Act n = groupnorm(x, t.gn, 1e-6f, false);
-        Act y = linear(n, t.proj_in);
-        drop(n);
-        // self-attention
-        Act l1 = layernorm(y, t.ln1);
+    // UNet self-attention, head_dim 64: the LayerNorm output (released here, as soon as q, k and v are enqueued) -> the input of to_out
+    Act self_attention64(Act& l1, const TfW& t) {
+        if (contract) {  // stacked q | k | v, stored, then the split attention
+            Act qkv = linear(l1, t.qkv);
+            drop(l1);
+            Act a = attention_c(qkv, t.heads, 64, 0.125f);
+            drop(qkv);
+            return a;
+        }
+        const int B = l1.B, T = l1.H * l1.W, C = t.C, Tpad = round_up(T, 64);
         Act qk;
         h16_t* vt = nullptr;
         {   // q | k | V^T in ONE launch when the persistent GEMM takes it (T % 16 == 0 ...), else the q | k GEMM + the transposed V GEMM
@@ -1075,8 +1013,8 @@ struct gp_engine {
             // included: one launch and one pass over the LayerNorm output less outweigh the slower V slices)
             const int fuse_max_rows = gp_sw().qkv_fuse_max_rows;
             if (!no_fuse && p.M <= fuse_max_rows && !t.qkv.bias && l1.C == t.qkv.cin_pad && igemm_uses_pgemm(p, 0)) {
-                qk = new_act(x.B, x.H, x.W, 2 * C);
-                vt = (h16_t*)pool.alloc((size_t)x.B * C * Tpad * sizeof(h16_t));
+                qk = new_act(l1.B, l1.H, l1.W, 2 * C);
+                vt = (h16_t*)pool.alloc((size_t)B * C * Tpad * sizeof(h16_t));
                 p.out = qk.p; p.vt_out = vt;
                 igemm_qkv_clear_pad(p, st);
                 run_igemm(p);
@@ -1086,41 +1024,59 @@ struct gp_engine {
             }
         }
         drop(l1);
-        Act a = new_act(x.B, x.H, x.W, C);
-        tm.flops_attn += 4.0 * x.B * t.heads * (double)T * T * 64;
+        Act a = new_act(qk.B, qk.H, qk.W, C);
+        const double fl = 4.0 * B * t.heads * (double)T * T * 64;
+        tm.flops_attn += fl;
         tm.n_attn++;
-        mark("flash_attn64 T=" + std::to_string(T) + " heads=" + std::to_string(t.heads), 4.0 * x.B * t.heads * (double)T * T * 64);
+        mark("flash_attn64 T=" + std::to_string(T) + " heads=" + std::to_string(t.heads), fl);
         prof_begin(1);
-        launch_flash_attn64(qk.p, qk.p + C, vt, a.p, x.B, T, t.heads, 2 * C, 2 * C, Tpad, C, st);
+        launch_flash_attn64(qk.p, qk.p + C, vt, a.p, B, T, t.heads, 2 * C, 2 * C, Tpad, C, st);
         prof_end();
         drop(qk);
         pool.release(vt);
-        linear(a, t.o1, y.p, GP_ACT_NONE, y.p);  // y += to_out(attn), in place
-        drop(a);
-        // cross-attention against the folded constant context
-        Act l3;
-        if (t.fU) {  // two context tokens: LayerNorm + to_q + attention + to_out + residual + the feed-forward's LayerNorm in ONE pass
-            l3 = new_act(x.B, x.H, x.W, C);
-            mark("cross_attn_fold " + dims(y));
-            launch_cross_attn_fold(y.p, y.p, l3.p, t.fU, t.fu0, t.fG, t.fc0, t.ln3.g, t.ln3.b, (int)x.pixels(), C, t.heads, 1e-5f, st);
-        } else {
-            Act l2 = layernorm(y, t.ln2);
-            Act q2 = linear(l2, t.q2);
-            drop(l2);
-            Act a2 = new_act(x.B, x.H, x.W, C);
-            mark("cross_attn_small " + dims(q2));
-            launch_cross_attn_small(q2.p, t.kc, t.vc, a2.p, (int)x.pixels(), C, ctx_L, st);
-            drop(q2);
-            linear(a2, t.o2, y.p, GP_ACT_NONE, y.p);
-            drop(a2);
-            l3 = layernorm(y, t.ln3);
+        return a;
+    }
+    // cross-attention against the folded constant context: y += to_out(attn2(LN2(y))) in place; returns LN3(y), the feed-forward's input
+    Act cross_attention(const Act& y, const TfW& t) {
+        const int C = t.C, M = (int)y.pixels();
+        // two context tokens: LayerNorm + to_q + attention + to_out + residual + the feed-forward's LayerNorm in ONE pass
+        if (t.fU && (!contract || c_cross_fold_supported(C))) {
+            Act l3 = new_product_input(y.B, y.H, y.W, C);
+            mark((contract ? "c_cross_fold " : "cross_attn_fold ") + dims(y));
+            if (contract) launch_c_cross_fold(y.f, y.f, l3.p, t.fU, t.fu0, t.fG, t.fc0, t.ln3.g, t.ln3.b, M, C, t.heads, 1e-5f, st);
+            else launch_cross_attn_fold(y.p, y.p, l3.p, t.fU, t.fu0, t.fG, t.fc0, t.ln3.g, t.ln3.b, M, C, t.heads, 1e-5f, st);
+            return l3;
         }
+        Act l2 = layernorm(y, t.ln2);
+        Act q2 = linear(l2, t.q2);
+        drop(l2);
+        Act a2 = new_product_input(y.B, y.H, y.W, C);
+        mark((contract ? "c_cross_attn_small " : "cross_attn_small ") + dims(q2));
+        if (contract) launch_c_cross_attn_small(q2.f, t.kc, t.vc, a2.p, M, C, ctx_L, st);
+        else launch_cross_attn_small(q2.p, t.kc, t.vc, a2.p, M, C, ctx_L, st);
+        drop(q2);
+        linear(a2, t.o2, &y, GP_ACT_NONE, &y);
+        drop(a2);
+        return layernorm(y, t.ln3);
+    }
+    // BasicTransformerBlock inside Transformer2DModel (custom_unet.py call sites :305-327,341-352)
+    Act transformer(const Act& x, const std::string& name) {
+        const TfW& t = tfs.at(name);
+        if (!t.kc) throw std::logic_error("gp_set_context has not been called");
+        Act n = groupnorm(x, t.gn, 1e-6f, false);
+        Act y = linear(n, t.proj_in);
+        drop(n);
+        Act l1 = layernorm(y, t.ln1);
+        Act a = self_attention64(l1, t);
+        linear(a, t.o1, &y, GP_ACT_NONE, &y);  // y += to_out(attn), in place
+        drop(a);
+        Act l3 = cross_attention(y, t);
         // GEGLU feed-forward
         Act ff = linear(l3, t.ff1, nullptr, GP_ACT_GEGLU);
         drop(l3);
-        linear(ff, t.ff2, y.p, GP_ACT_NONE, y.p);
+        linear(ff, t.ff2, &y, GP_ACT_NONE, &y);
         drop(ff);
-        Act out = linear(y, t.proj_out, x.p, GP_ACT_NONE, nullptr, true);
+        Act out = linear(y, t.proj_out, &x, GP_ACT_NONE, nullptr, true);
         drop(y);
         return out;
     }
@@ -1130,15 +1086,7 @@ struct gp_engine {
     Act vae_encode(const void* rgb, int is_u8, int B, int Hh, int Ww) {
         const PackedW& win = convs.at("vae.encoder.conv_in");
         Act h;
-        if (contract) {  // x / 255 * 2 - 1 is not a bf16 number: the image itself enters as a split operand
-            Act xs = new_operand(B, Hh, Ww, 64);
-            mark("c_rgb_split");
-            launch_c_rgb_split(rgb, is_u8, xs.p, B, Hh, Ww, st);
-            ConvOpt oin;
-            oin.want_stats = true;
-            h = conv(xs, win, oin);
-            drop(xs);
-        } else if (win.cout % 32 == 0 && win.cin_pad == 64 && !gp_sw().no_rgb_conv) {
+        if (!contract && win.cout % 32 == 0 && win.cin_pad == 64 && !gp_sw().no_rgb_conv) {
             // u8 image -> conv_in output in one kernel (K = 27), statistics for the first resnet's norm1 included
             h = new_act(B, Hh, Ww, win.cout);
             if (fuse_stats) {
@@ -1158,9 +1106,11 @@ struct gp_engine {
             launch_rgb_conv_in(rgb, is_u8, conv_in_w27, win.bias, h.p, h.st, B, Hh, Ww, win.cout, st);
             prof_end();
         } else {
-            Act x = new_act(B, Hh, Ww, 64);
-            mark("rgb_prologue");
-            launch_rgb_prologue(rgb, is_u8, x.p, B, Hh, Ww, 64, st);
+            Act x = new_product_input(B, Hh, Ww, 64);
+            mark(contract ? "c_rgb_split" : "rgb_prologue");
+            // (contract precision: x / 255 * 2 - 1 is not a bf16 number: the image itself enters as a split operand)
+            if (contract) launch_c_rgb_split(rgb, is_u8, x.p, B, Hh, Ww, st);
+            else launch_rgb_prologue(rgb, is_u8, x.p, B, Hh, Ww, 64, st);
             ConvOpt oin;
             oin.want_stats = true;
             h = conv(x, win, oin);
@@ -1193,6 +1143,23 @@ struct gp_engine {
         return lat;
     }
 
+    // [h | skip] along the channels
+    Act concat(const Act& h, const Act& skip) {
+        Act cat = new_stored(h.B, h.H, h.W, h.C + skip.C);
+        const int cbm = (fuse_stats && !contract) ? concat_stats_bm((long long)h.H * h.W, h.pixels(), h.C + skip.C) : 0;
+        mark("concat " + dims(cat));
+        if (contract) {
+            launch_c_concat(h.f, h.C, skip.f, skip.C, cat.f, h.pixels(), st);
+        } else if (cbm) {  // the copy also leaves the statistics the resnet's first GroupNorm needs
+            cat.st = (float*)pool.alloc((size_t)(h.pixels() / cbm) * cat.C * 2 * sizeof(float));
+            cat.st_mode = 0;
+            cat.st_bm = cbm;
+            launch_concat_stats(h.p, h.C, skip.p, skip.C, cat.p, h.pixels(), cbm, cat.st, st);
+        } else {
+            launch_concat(h.p, h.C, skip.p, skip.C, cat.p, h.pixels(), st);
+        }
+        return cat;
+    }
     // latent NHWC (64 allocated channels) -> sample NHWC (64 allocated, unet_out_channels real) and/or the 4 up-block features
     Act unet(const Act& latent, Act* feats /* [4] or null */, bool want_sample) {
         std::vector<Act> skips;
@@ -1239,19 +1206,7 @@ struct gp_engine {
             for (int j = 0; j < nres; ++j) {
                 Act skip = skips.back();
                 skips.pop_back();
-                Act cat = contract ? new_act_f(h.B, h.H, h.W, h.C + skip.C) : new_act(h.B, h.H, h.W, h.C + skip.C);
-                const int cbm = (fuse_stats && !contract) ? concat_stats_bm((long long)h.H * h.W, h.pixels(), h.C + skip.C) : 0;
-                mark("concat " + dims(cat));
-                if (contract) {
-                    launch_c_concat(h.f, h.C, skip.f, skip.C, cat.f, h.pixels(), st);
-                } else if (cbm) {  // the copy also leaves the statistics the resnet's first GroupNorm needs
-                    cat.st = (float*)pool.alloc((size_t)(h.pixels() / cbm) * cat.C * 2 * sizeof(float));
-                    cat.st_mode = 0;
-                    cat.st_bm = cbm;
-                    launch_concat_stats(h.p, h.C, skip.p, skip.C, cat.p, h.pixels(), cbm, cat.st, st);
-                } else {
-                    launch_concat(h.p, h.C, skip.p, skip.C, cat.p, h.pixels(), st);
-                }
+                Act cat = concat(h, skip);
                 if (!h_is_feat) drop(h);
                 else if (h.st) pool.release(h.st);
                 h_is_feat = false;
@@ -1292,15 +1247,20 @@ struct gp_engine {
         return out;
     }
 
-    // z_in: NHWC with 64 allocated channels holding the UNet output v (in_scale = -1/scaling) or a pred latent (1/scaling)
-    // out_dev != nullptr: the caller wants the fp32 NCHW result of decode_pred (+ clip / shift unless raw); when the fused tail kernel takes
-    // the last three layers (conv_few.hip) it is written directly and the returned Act is empty, else the caller runs launch_decode_epilogue
-    Act vae_decode(const Act& z_in, float in_scale, float* out_dev = nullptr, int mean3 = 0, int raw = 0) {
+    // post_quant_conv (1x1 over the latent channels) of in_scale * z_in
+    Act post_quant(const Act& z_in, float in_scale) {
         const int L = cfg.vae_latent_channels;
-        Act z = contract ? new_act_f(z_in.B, z_in.H, z_in.W, 64) : new_act(z_in.B, z_in.H, z_in.W, 64);
+        Act z = new_stored(z_in.B, z_in.H, z_in.W, 64);
         mark("post_quant_conv");
         if (contract) launch_c_pointwise_small(z_in.f, z.f, pq_w_dev, pq_b_dev, z_in.pixels(), L, L, z_in.C, 64, in_scale, st);
         else launch_pointwise_small(z_in.p, z.p, pq_w_dev, pq_b_dev, z_in.pixels(), L, L, z_in.C, 64, in_scale, st);
+        return z;
+    }
+    // z_in: NHWC with 64 allocated channels holding the UNet output v (in_scale = -1/scaling) or a pred latent (1/scaling)
+    // out_dev != nullptr: the caller wants the fp32 NCHW result of decode_pred (+ clip / shift unless raw); when the fused tail kernel takes
+    // the last three layers (conv_few.hip) it is written directly and the returned Act is empty, else decode_to runs decode_epilogue
+    Act vae_decode(const Act& z_in, float in_scale, float* out_dev = nullptr, int mean3 = 0, int raw = 0) {
+        Act z = post_quant(z_in, in_scale);
         ConvOpt oin;
         oin.want_stats = true;
         Act h = conv(z, convs.at("vae.decoder.conv_in"), oin);
@@ -1351,30 +1311,49 @@ struct gp_engine {
         if (dec.f) launch_c_decode_epilogue(dec.f, out, dec.B, dec.H, dec.W, dec.C, mean3, raw, st);
         else launch_decode_epilogue(dec.p, out, dec.B, dec.H, dec.W, dec.C, mean3, raw, st);
     }
+    // the decode tail of an entry point: latent -> the caller's map (the fused tail kernel of vae_decode wrote `out` itself when no tensor comes back)
+    void decode_to(const Act& z, float in_scale, float* out, int mean3, int raw) {
+        Act dec = vae_decode(z, in_scale, out, mean3, raw);
+        if (dec.p || dec.f) {
+            decode_epilogue(dec, out, mean3, raw);
+            drop(dec);
+        }
+    }
 
     Act bilinear(const Act& x, int Ho, int Wo, int align_corners) {
-        Act y = contract ? new_act_f(x.B, Ho, Wo, x.C) : new_act(x.B, Ho, Wo, x.C);
+        Act y = new_stored(x.B, Ho, Wo, x.C);
         mark("bilinear " + dims(y));
         if (contract) launch_c_bilinear(x.f, y.f, x.B, x.H, x.W, Ho, Wo, x.C, align_corners, st);
         else launch_bilinear(x.p, y.p, x.B, x.H, x.W, Ho, Wo, x.C, align_corners, st);
         return y;
     }
+    Act relu_input(const Act& x) {  // ReLU(x) as the input of a matrix product
+        if (contract) return split_operand(x, GP_ACT_RELU);
+        Act r = new_act(x.B, x.H, x.W, x.C);
+        mark("relu " + dims(x));
+        launch_relu(x.p, r.p, x.pixels() * x.C, st);
+        return r;
+    }
+    Act add(const Act& a, const Act& b) {
+        Act y = new_stored(a.B, a.H, a.W, a.C);
+        mark("add " + dims(a));
+        if (contract) launch_c_add(a.f, b.f, y.f, a.pixels() * a.C, st);
+        else launch_add(a.p, b.p, y.p, a.pixels() * a.C, st);
+        return y;
+    }
+    void dpt_final(const Act& z, float* out_dev) {  // head.head.4 (1x1 to one channel), fp32 [B][H * W]
+        mark("dpt_final " + dims(z));
+        if (contract) launch_c_dpt_final(z.f, dpt_w_dev, dpt_b, out_dev, z.B, z.H * z.W, z.C, st);
+        else launch_dpt_final(z.p, dpt_w_dev, dpt_b, out_dev, z.B, z.H * z.W, z.C, st);
+    }
     Act rcu(const Act& x, const std::string& p) {  // pre-activation residual unit (dpt_head.py:256-271)
-        Act r;
-        if (contract) {
-            r = split_operand(x, GP_ACT_RELU);
-        } else {
-            r = new_act(x.B, x.H, x.W, x.C);
-            mark("relu " + dims(x));
-            launch_relu(x.p, r.p, x.pixels() * x.C, st);
-        }
+        Act r = relu_input(x);
         ConvOpt o1;
         o1.act = GP_ACT_RELU;
         Act h = conv(r, convs.at(p + ".convolution1"), o1);
         drop(r);
         ConvOpt o2;
-        o2.res = x.p;
-        o2.res_f = x.f;
+        o2.residual = &x;
         Act y = conv(h, convs.at(p + ".convolution2"), o2);
         drop(h);
         return y;
@@ -1397,20 +1376,14 @@ struct gp_engine {
                 x = hsrc;
             } else {
                 Act r = hsrc;
-                bool resized = false;
                 if (r.H != fused.H || r.W != fused.W) {
                     Act rr = bilinear(r, fused.H, fused.W, 0);
                     drop(r);
                     r = rr;
-                    resized = true;
                 }
-                (void)resized;
                 Act rc = rcu(r, lp + ".residual_layer1");
                 drop(r);
-                x = contract ? new_act_f(fused.B, fused.H, fused.W, fused.C) : new_act(fused.B, fused.H, fused.W, fused.C);
-                mark("add " + dims(fused));
-                if (contract) launch_c_add(fused.f, rc.f, x.f, fused.pixels() * fused.C, st);
-                else launch_add(fused.p, rc.p, x.p, fused.pixels() * fused.C, st);
+                x = add(fused, rc);
                 drop(rc);
                 drop(fused);
             }
@@ -1436,14 +1409,12 @@ struct gp_engine {
         o32.act = GP_ACT_RELU;
         Act z = conv(up, convs.at("dpt.head.head.2"), o32);
         drop(up);
-        mark("dpt_final " + dims(z));
-        if (contract) launch_c_dpt_final(z.f, dpt_w_dev, dpt_b, out_dev, z.B, z.H * z.W, z.C, st);
-        else launch_dpt_final(z.p, dpt_w_dev, dpt_b, out_dev, z.B, z.H * z.W, z.C, st);
+        dpt_final(z, out_dev);
         drop(z);
     }
 
     Act from_nchw_f32(const float* src, int B, int C, int Hh, int Ww, int Cpad) {
-        Act a = contract ? new_act_f(B, Hh, Ww, Cpad) : new_act(B, Hh, Ww, Cpad);
+        Act a = new_stored(B, Hh, Ww, Cpad);
         mark("nchw_f32_to_nhwc");
         if (contract) launch_c_nchw_to_nhwc(src, a.f, B, C, Hh, Ww, Cpad, st);
         else launch_nchw_f32_to_nhwc(src, a.p, B, C, Hh, Ww, Cpad, st);
@@ -1453,6 +1424,18 @@ struct gp_engine {
         mark("nhwc_to_nchw_f32");
         if (a.f) launch_c_nhwc_to_nchw(a.f, dst, a.B, C, a.H, a.W, a.C, st);
         else launch_nhwc_to_nchw_f32(a.p, dst, a.B, C, a.H, a.W, a.C, st);
+    }
+
+    // multi-step archs: the fp32 denoising state `sample` and the UNet input `lat` (channels [off, off + L) hold the sample)
+    void ddim_init(const float* noise_dev, const Act& lat, float* sample, int L, int off) {
+        mark("ddim_init");
+        if (contract) launch_c_ddim_init(noise_dev, lat.f, sample, lat.B, lat.H, lat.W, L, lat.C, off, st);
+        else launch_ddim_init(noise_dev, lat.p, sample, lat.B, lat.H, lat.W, L, lat.C, off, st);
+    }
+    void ddim_step(const Act& v, float* sample, const Act& lat, int L, int off, const Act& x0, bool last /* pred_x0 goes to x0 */, const DdimCoef& k) {
+        mark("ddim_step");
+        if (contract) launch_c_ddim_step(v.f, v.C, sample, lat.f, lat.C, off, last ? x0.f : nullptr, x0.C, lat.pixels(), L, k, st);
+        else launch_ddim_step(v.p, v.C, sample, lat.p, lat.C, off, last ? x0.p : nullptr, x0.C, lat.pixels(), L, k, st);
     }
 
     void collect_profile() {
@@ -1705,36 +1688,53 @@ static void check_ready(gp_engine* e, void* stream) {
     e->st = (hipStream_t)stream;
 }
 
+// stage events of a whole pass (profiling level >= 1): 0 = start, 1 = encoded, 2 = UNet done, 3 = end
+static void stage(gp_engine* e, int i) {
+    if (e->prof < 1) return;
+    if (!e->ev[i]) HIPCHK(hipEventCreate(&e->ev[i]));
+    HIPCHK(hipEventRecord(e->ev[i], e->st));
+}
+static void begin_pass(gp_engine* e) {
+    stage(e, 0);
+    e->marks_used = 0;
+}
+static void end_pass(gp_engine* e) {
+    e->mark("END", 0.0, 0);
+    stage(e, 3);
+    if (e->prof < 1) return;
+    HIPCHK(hipEventSynchronize(e->ev[3]));
+    HIPCHK(hipEventElapsedTime(&e->tm.ms_encode, e->ev[0], e->ev[1]));
+    HIPCHK(hipEventElapsedTime(&e->tm.ms_unet, e->ev[1], e->ev[2]));
+    HIPCHK(hipEventElapsedTime(&e->tm.ms_head, e->ev[2], e->ev[3]));
+    HIPCHK(hipEventElapsedTime(&e->tm.ms_total, e->ev[0], e->ev[3]));
+}
+// the last thing every entry point that enqueues work does
+static void finish_call(gp_engine* e) {
+    e->collect_saturation();
+    HIPCHK(hipGetLastError());
+}
+
 gp_status gp_infer(gp_engine* e, const void* rgb_dev, int is_u8, int B, int H, int W, gp_mode mode, float* out_dev, void* stream) {
     if (!e || !rgb_dev || !out_dev) return GP_ERR_INVALID;
     return guard(e, [&] {
         check_ready(e, stream);
         if (B < 1 || H < 8 || W < 8) throw std::invalid_argument("need B >= 1 and H, W >= 8");
-        const bool stage_ev = e->prof >= 1;
-        if (stage_ev) {
-            for (int i = 0; i < 4; ++i) if (!e->ev[i]) HIPCHK(hipEventCreate(&e->ev[i]));
-            HIPCHK(hipEventRecord(e->ev[0], e->st));
-        }
-        e->marks_used = 0;
+        begin_pass(e);
         Act lat = e->vae_encode(rgb_dev, is_u8, B, H, W);
-        if (stage_ev) HIPCHK(hipEventRecord(e->ev[1], e->st));
+        stage(e, 1);
         if (!e->cfg.dpt_enabled) {
             Act v = e->unet(lat, nullptr, true);
             e->drop(lat);
-            if (stage_ev) HIPCHK(hipEventRecord(e->ev[2], e->st));
+            stage(e, 2);
             // scheduler step with beta == 1: pred_x0 = -v (F5); decode_pred divides by the scaling factor
             const int mean3 = !(mode == GP_MODE_NORMAL || mode == GP_MODE_SEG);
-            Act dec = e->vae_decode(v, -1.0f / e->cfg.vae_scaling_factor, out_dev, mean3, 0);
+            e->decode_to(v, -1.0f / e->cfg.vae_scaling_factor, out_dev, mean3, 0);
             e->drop(v);
-            if (dec.p || dec.f) {  // (the fused tail kernel wrote out_dev itself otherwise)
-                e->decode_epilogue(dec, out_dev, mean3, 0);
-                e->drop(dec);
-            }
         } else {
             Act feats[4];
             e->unet(lat, feats, false);
             e->drop(lat);
-            if (stage_ev) HIPCHK(hipEventRecord(e->ev[2], e->st));
+            stage(e, 2);
             Act rev[4] = {feats[3], feats[2], feats[1], feats[0]};
             const long long out_px = (long long)gp_dpt_out_size(rev[0].H) * gp_dpt_out_size(rev[0].W);
             e->dpt_head(rev, out_dev);
@@ -1744,17 +1744,8 @@ gp_status gp_infer(gp_engine* e, const void* rgb_dev, int is_u8, int B, int H, i
             launch_minmax_norm(out_dev, B, out_px, mm_ws, e->st);
             e->pool.release(mm_ws);
         }
-        e->mark("END", 0.0, 0);
-        if (stage_ev) {
-            HIPCHK(hipEventRecord(e->ev[3], e->st));
-            HIPCHK(hipEventSynchronize(e->ev[3]));
-            HIPCHK(hipEventElapsedTime(&e->tm.ms_encode, e->ev[0], e->ev[1]));
-            HIPCHK(hipEventElapsedTime(&e->tm.ms_unet, e->ev[1], e->ev[2]));
-            HIPCHK(hipEventElapsedTime(&e->tm.ms_head, e->ev[2], e->ev[3]));
-            HIPCHK(hipEventElapsedTime(&e->tm.ms_total, e->ev[0], e->ev[3]));
-        }
-        e->collect_saturation();
-        HIPCHK(hipGetLastError());
+        end_pass(e);
+        finish_call(e);
     });
 }
 
@@ -1769,30 +1760,21 @@ gp_status gp_infer_steps(gp_engine* e, const void* rgb_dev, int is_u8, int B, in
         if (e->cfg.unet_in_channels != (noise_dev ? 2 * L : L))
             throw std::invalid_argument(noise_dev ? "an initial noise sample needs a UNet with 2 x latent input channels (marigold, run.py:59-78)"
                                                   : "without an initial noise sample the UNet takes the latent channels only (rgb_blending)");
-        const bool stage_ev = e->prof >= 1;
-        if (stage_ev) {
-            for (int i = 0; i < 4; ++i) if (!e->ev[i]) HIPCHK(hipEventCreate(&e->ev[i]));
-            HIPCHK(hipEventRecord(e->ev[0], e->st));
-        }
-        e->marks_used = 0;
+        begin_pass(e);
         const float t_before = e->timestep;
         Act lat = e->vae_encode(rgb_dev, is_u8, B, H, W);  // channels 0..L-1 = rgb latent; the UNet input tensor from here on
-        if (stage_ev) HIPCHK(hipEventRecord(e->ev[1], e->st));
+        stage(e, 1);
         const int off = noise_dev ? L : 0;
         float* sample = (float*)e->pool.alloc((size_t)lat.pixels() * L * sizeof(float));
-        e->mark("ddim_init");
-        if (e->contract) launch_c_ddim_init(noise_dev, lat.f, sample, B, lat.H, lat.W, L, lat.C, off, e->st);
-        else launch_ddim_init(noise_dev, lat.p, sample, B, lat.H, lat.W, L, lat.C, off, e->st);
-        Act x0 = e->contract ? e->new_act_f(B, lat.H, lat.W, 64) : e->new_act(B, lat.H, lat.W, 64);
+        e->ddim_init(noise_dev, lat, sample, L, off);
+        Act x0 = e->new_stored(B, lat.H, lat.W, 64);
         try {
             for (int i = 0; i < n_steps; ++i) {
                 const gp_ddim_step& s = steps[i];
                 if (s.timestep != e->timestep) e->set_timestep_on_stream(s.timestep);
                 Act v = e->unet(lat, nullptr, true);
                 const DdimCoef k{s.x0_sample, s.x0_model, s.eps_sample, s.eps_model, s.prev_x0, s.prev_eps, s.clip};
-                e->mark("ddim_step");
-                if (e->contract) launch_c_ddim_step(v.f, v.C, sample, lat.f, lat.C, off, i == n_steps - 1 ? x0.f : nullptr, x0.C, lat.pixels(), L, k, e->st);
-                else launch_ddim_step(v.p, v.C, sample, lat.p, lat.C, off, i == n_steps - 1 ? x0.p : nullptr, x0.C, lat.pixels(), L, k, e->st);
+                e->ddim_step(v, sample, lat, L, off, x0, i == n_steps - 1, k);
                 e->drop(v);
             }
         } catch (...) {  // a failed step must not leave the loop's timestep behind as the engine's (gp_set_timestep) one
@@ -1804,25 +1786,12 @@ gp_status gp_infer_steps(gp_engine* e, const void* rgb_dev, int is_u8, int B, in
         e->pool.release(sample);
         e->drop(lat);
         if (e->timestep != t_before) e->set_timestep_on_stream(t_before);
-        if (stage_ev) HIPCHK(hipEventRecord(e->ev[2], e->st));
+        stage(e, 2);
         const int mean3 = !(mode == GP_MODE_NORMAL || mode == GP_MODE_SEG);
-        Act dec = e->vae_decode(x0, 1.0f / e->cfg.vae_scaling_factor, out_dev, mean3, 0);
+        e->decode_to(x0, 1.0f / e->cfg.vae_scaling_factor, out_dev, mean3, 0);
         e->drop(x0);
-        if (dec.p || dec.f) {
-            e->decode_epilogue(dec, out_dev, mean3, 0);
-            e->drop(dec);
-        }
-        e->mark("END", 0.0, 0);
-        if (stage_ev) {
-            HIPCHK(hipEventRecord(e->ev[3], e->st));
-            HIPCHK(hipEventSynchronize(e->ev[3]));
-            HIPCHK(hipEventElapsedTime(&e->tm.ms_encode, e->ev[0], e->ev[1]));
-            HIPCHK(hipEventElapsedTime(&e->tm.ms_unet, e->ev[1], e->ev[2]));
-            HIPCHK(hipEventElapsedTime(&e->tm.ms_head, e->ev[2], e->ev[3]));
-            HIPCHK(hipEventElapsedTime(&e->tm.ms_total, e->ev[0], e->ev[3]));
-        }
-        e->collect_saturation();
-        HIPCHK(hipGetLastError());
+        end_pass(e);
+        finish_call(e);
     });
 }
 
@@ -1833,8 +1802,7 @@ gp_status gp_vae_encode(gp_engine* e, const void* rgb_dev, int is_u8, int B, int
         Act lat = e->vae_encode(rgb_dev, is_u8, B, H, W);
         e->to_nchw_f32(lat, e->cfg.vae_latent_channels, latent_out);
         e->drop(lat);
-        e->collect_saturation();
-        HIPCHK(hipGetLastError());
+        finish_call(e);
     });
 }
 
@@ -1856,8 +1824,7 @@ gp_status gp_unet(gp_engine* e, const float* latent_in, int B, int h, int w, flo
                 if (feats_out[i]) e->to_nchw_f32(feats[i], feats[i].C, feats_out[i]);
                 e->drop(feats[i]);
             }
-        e->collect_saturation();
-        HIPCHK(hipGetLastError());
+        finish_call(e);
     });
 }
 
@@ -1867,14 +1834,9 @@ gp_status gp_vae_decode(gp_engine* e, const float* pred_latent, int B, int h, in
         check_ready(e, stream);
         Act z = e->from_nchw_f32(pred_latent, B, e->cfg.vae_latent_channels, h, w, 64);
         // decode_pred (genpercept_pipeline.py:507-526): channel mean for 1-channel modes, no clip / shift
-        Act dec = e->vae_decode(z, 1.0f / e->cfg.vae_scaling_factor, out, mean3, 1);
+        e->decode_to(z, 1.0f / e->cfg.vae_scaling_factor, out, mean3, 1);
         e->drop(z);
-        if (dec.p || dec.f) {
-            e->decode_epilogue(dec, out, mean3, 1);
-            e->drop(dec);
-        }
-        e->collect_saturation();
-        HIPCHK(hipGetLastError());
+        finish_call(e);
     });
 }
 
@@ -1889,8 +1851,7 @@ gp_status gp_vae_mid_attention(gp_engine* e, int decoder, const float* x, int B,
         e->drop(a);
         e->to_nchw_f32(y, C, out);
         e->drop(y);
-        e->collect_saturation();
-        HIPCHK(hipGetLastError());
+        finish_call(e);
     });
 }
 
@@ -1905,8 +1866,7 @@ gp_status gp_dpt_head(gp_engine* e, const float* const* feats, int B, int h, int
         for (int i = 0; i < 4; ++i) f[i] = e->from_nchw_f32(feats[i], B, e->cfg.dpt_neck[i], hs[i], ws[i], e->cfg.dpt_neck[i]);
         e->dpt_head(f, out);
         for (int i = 0; i < 4; ++i) e->drop(f[i]);
-        e->collect_saturation();
-        HIPCHK(hipGetLastError());
+        finish_call(e);
     });
 }
 
