@@ -24,10 +24,8 @@ GP_DEV int attn_off128(int row, int slot) { return row * 128 + ((slot ^ ((row >>
 #endif
 // NKB: 32-key blocks per KV tile (2: 64 keys, 4: 128 keys -- one online-softmax update, one barrier and one DMA wait per 128 keys,
 // longer independent MFMA runs)
-// NST: depth of the K / V ring in LDS (16 KiB per stage at NKB = 2).  2 = one tile ahead, a full vmcnt(0) + barrier per tile; 3 = two tiles
-// ahead with COUNTED waits and one raw s_barrier per tile -- the DMA of tile t+2 is issued before tile t computes and is only waited for at
-// the top of tile t+2, so an L2 / MALL round trip no longer has to fit inside one tile's compute.
-template <int NKB, int NST>
+// The K / V tiles are double-buffered in LDS (16 KiB per stage at NKB = 2): one tile ahead, a full vmcnt(0) + barrier per tile.
+template <int NKB>
 __global__ __launch_bounds__(256, 2) void flash_attn64_kernel(const h16_t* __restrict__ Q, const h16_t* __restrict__ K,
                                                             const h16_t* __restrict__ Vt, h16_t* __restrict__ O, int T, int heads, int ldq,
                                                             int ldk, int Tpad, int ldo) {
@@ -189,22 +187,21 @@ __global__ __launch_bounds__(256, 2) void flash_attn64_kernel(const h16_t* __res
             }
     };
 
-    constexpr int LPS = NKB + 2 * NH;  // LDS-DMA instructions per wave and stage
+    // (the prologue as a one-trip loop and the slot counters with a wrap-around: for a plain stage(0, 0) / cur ^= 1 hipcc orders the address
+    // arithmetic ahead of the tile loop differently)
 #pragma unroll
-    for (int s0 = 0; s0 < NST - 1; ++s0)
+    for (int s0 = 0; s0 < 1; ++s0)
         if (s0 < nt) stage(s0, s0);
-    int nxt = NST - 1;
+    int nxt = 1;
     auto step = [&](int kt, auto maskc) __attribute__((always_inline)) {
-        // my DMAs of tile kt have landed (NST - 2 younger stages may stay in flight) ...
-        const int ahead = min(NST - 2, nt - 1 - kt);
-        if (ahead >= 1) wait_vm<LPS>(); else wait_vm<0>();
-        static_assert(NST == 2 || NST == 3, "ring depth");
-        // ... and after the barrier everybody's have, and everybody is done reading the slot of tile kt - 1, which tile kt + NST - 1 refills
+        // my DMAs of tile kt have landed, and after the barrier everybody's have, and everybody is done reading the slot of tile kt - 1, which
+        // tile kt + 1 refills
+        wait_vm<0>();
         __builtin_amdgcn_s_barrier();
-        if (kt + NST - 1 < nt) stage(nxt, kt + NST - 1);
+        if (kt + 1 < nt) stage(nxt, kt + 1);
         tile(kt, maskc);
-        cur = cur + 1 == NST ? 0 : cur + 1;
-        nxt = nxt + 1 == NST ? 0 : nxt + 1;
+        cur = cur + 1 == 2 ? 0 : cur + 1;
+        nxt = nxt + 1 == 2 ? 0 : nxt + 1;
     };
     // Only the last tile can reach past key T - 1.  It runs after the loop: with both tile variants inside the loop body the accumulators
     // lived in different registers on the two paths and every iteration paid 16 v_mov_b64 of copies at the merge.
@@ -237,13 +234,11 @@ void launch_flash_attn64(const h16_t* q, const h16_t* k, const h16_t* vt, h16_t*
     // packed fma / add forms (kept) and a deferred rescale (not kept, see tile()) did not change the time.
     // r2 notes (183-register kernel): forcing three waves, __launch_bounds__(256, 3), spilled 38 registers.
     // Measured alternatives, all slower at T = 9216 (610 us, kernel only): 128-key tiles -8 % (r1); a three-stage K / V ring with counted waits
-    // -2 % (stays as a switch, GENPERCEPT_FLASH_RING3: K / V latency is not what the kernel waits for); two 32-query blocks per wave so that each
+    // 0 to -2 % at T = 144 ... 9216 (K / V latency is not what the kernel waits for); two 32-query blocks per wave so that each
     // K / V^T fragment read feeds two MFMAs: 1100 us with 256 VGPRs + 42 spilled, 1050 us at one wave per SIMD; one online-softmax update per
     // 32 keys instead of 64 (165 VGPRs): 644 us.  r2 ablations of the shipped shape: no softmax arithmetic 494 us, no P.V MFMAs 587 us, neither
     // 442 us, additionally no K.Q^T MFMAs 249 us (the LDS fragment reads, DMA and loop alone), no waits / barriers 601 us.
-    const bool ring2 = !gp_sw().flash_ring3;
-    if (ring2) hipLaunchKernelGGL((flash_attn64_kernel<2, 2>), grid, dim3(256), 2 * 16384, s, q, k, vt, out, T, heads, ldq, ldk, Tpad, ldo);
-    else hipLaunchKernelGGL((flash_attn64_kernel<2, 3>), grid, dim3(256), 3 * 16384, s, q, k, vt, out, T, heads, ldq, ldk, Tpad, ldo);
+    hipLaunchKernelGGL(flash_attn64_kernel<2>, grid, dim3(256), 2 * 16384, s, q, k, vt, out, T, heads, ldq, ldk, Tpad, ldo);
 }
 
 // ---- flash_attn64 with SPLIT operands (contract precision, contract.hip): q = q_hi + q_lo, k, v, p likewise (bf16 pieces of fp32 values);
@@ -468,7 +463,7 @@ __global__ __launch_bounds__(256) void flash_attn512_kernel(const h16_t* __restr
                                                              const h16_t* __restrict__ Vt, h16_t* __restrict__ O,
                                                              float* __restrict__ part_o,
                                                              float* __restrict__ part_ml, int B, int T, int ldq, int ldk, int Tpad, int ldo,
-                                                             float scale, int dbg) {
+                                                             float scale) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -540,10 +535,10 @@ __global__ __launch_bounds__(256) void flash_attn512_kernel(const h16_t* __restr
             if (pc < 8) {
                 const int i = wave * 8 + pc;                    // LDS row i <- key kt * 32 + pi(i); one 1 KiB row per instruction
                 const int key = min(kt * 32 + pi23(i), T - 1);  // rows past T repeat the last one: their scores are masked (MASK)
-                if (!(dbg & 1)) blds16(k_rs, koff[pc & 7], (unsigned)key * (unsigned)(ldk * 2), sb + i * 1024);
+                blds16(k_rs, koff[pc & 7], (unsigned)key * (unsigned)(ldk * 2), sb + i * 1024);
             } else {
                 const int m = pc - 8;                           // 16 rows (channels) of 64 bytes per instruction
-                if (!(dbg & 2)) blds16(v_rs, v_lane_off, (unsigned)((128 * wave + 16 * m) * Tpad + kt * 32) * 2u, sb + 2 * F5_KBYTES + (wave * 8 + m) * 1024);
+                blds16(v_rs, v_lane_off, (unsigned)((128 * wave + 16 * m) * Tpad + kt * 32) * 2u, sb + 2 * F5_KBYTES + (wave * 8 + m) * 1024);
             }
         };
         auto stage = [&](int slot, int kt) __attribute__((always_inline)) {
@@ -758,9 +753,8 @@ void launch_flash_attn512(const h16_t* q, const h16_t* k, const h16_t* vt, h16_t
     const int rounds = nblocks / G, L = nblocks - rounds * G, S = L ? G / L : 0;
     float* part_o = ws;
     float* part_ml = ws ? ws + (long long)S * L * 128 * 512 : nullptr;
-    const int dbg = gp_sw().f5_dbg;  // timing ablations only: 1 no K DMA, 2 no V DMA
-    hipLaunchKernelGGL(flash_attn512_kernel, dim3(G), dim3(256), F5_LDS, s, q, k, vt, out, part_o, part_ml, B, T, ldq, ldk, Tpad,
-                       ldo, scale, dbg);
+    hipLaunchKernelGGL(flash_attn512_kernel, dim3(G), dim3(256), F5_LDS, s, q, k, vt, out, part_o, part_ml, B, T, ldq, ldk, Tpad, ldo,
+                       scale);
     if (L) hipLaunchKernelGGL(flash512_combine_kernel, dim3(L * 4), dim3(256), 0, s, part_o, part_ml, out, T, nqb, rounds * G, (L % B == 0) ? L / B : 0,
                               S, ldo, scale);
 }

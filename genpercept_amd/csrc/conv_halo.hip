@@ -601,25 +601,11 @@ __global__ __launch_bounds__(512) void conv3x3_halo3_kernel(const IGemmParams p)
         constexpr int TAP = decltype(tapc)::value, PAR = decltype(parc)::value, KK = decltype(kkc)::value;
         constexpr int KY = PH ? TAP / 2 : TAP / 3, KX = PH ? TAP % 2 : TAP % 3, SLOT = PH ? TAP : TAP % 3;
 #pragma unroll
-        for (int i = 0; i < FN; ++i) {
-            if (ABL & 8192) asm volatile("" : "+v"(f.w[i]));  // r4 diagnostic: no weight-fragment reads (registers keep whatever they hold: garbage results)
-            else f.w[i] = lds_frag(wb[KK], SLOT * B_STAGE + (i >> 1) * 4096 + (i & 1) * 512);
-            typedef const volatile __attribute__((address_space(3))) h16x8_t* lds_frag_vptr;
-            if (ABL & 32768) {  // r4 diagnostic: every fragment read issued TWICE (the copy is discarded): is LDS array time additive to the MFMA time?
-                const h16x8_t t = *(lds_frag_vptr)(wb[KK] + (unsigned)(SLOT * B_STAGE + (i >> 1) * 4096 + (i & 1) * 512));
-                asm volatile("" ::"v"(t));
-            }
-        }
+        for (int i = 0; i < FN; ++i) f.w[i] = lds_frag(wb[KK], SLOT * B_STAGE + (i >> 1) * 4096 + (i & 1) * 512);
 #pragma unroll
         for (int j = 0; j < FM; ++j) {
             const int hy = UPS ? ((j + KY - 1) >> 1) + 1 : j + KY;
-            if (ABL & 16384) asm volatile("" : "+v"(f.x[j]));  // ... no pixel-fragment reads
-            else f.x[j] = lds_frag(PH ? xs[KX][KK] : xb[KX][KK], PAR * A_BUF + hy * HW_ * 128);
-            typedef const volatile __attribute__((address_space(3))) h16x8_t* lds_frag_vptr;
-            if (ABL & 32768) {
-                const h16x8_t t = *(lds_frag_vptr)(xb[KX][KK] + (unsigned)(PAR * A_BUF + hy * HW_ * 128));
-                asm volatile("" ::"v"(t));
-            }
+            f.x[j] = lds_frag(PH ? xs[KX][KK] : xb[KX][KK], PAR * A_BUF + hy * HW_ * 128);
         }
     };
     auto mfma16 = [&](const Half& f) __attribute__((always_inline)) {
@@ -633,16 +619,6 @@ __global__ __launch_bounds__(512) void conv3x3_halo3_kernel(const IGemmParams p)
             for (int j = 0; j < FM; ++j) acc[i][j] = mfma_16x16x32(f.w[i], f.x[j], acc[i][j]);
     };
     auto interleave = [&]() __attribute__((always_inline)) {
-        if (ABL & 2048) {  // r4 experiment: the eight fragment reads under the FIRST eight MFMAs (the last one then has eight MFMAs of cover
-                           // before the step's lgkmcnt(0) + barrier instead of none)
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
-            return;
-        }
         if (FM == 3) {  // 12 MFMAs, 7 fragment reads (4 weight + 3 pixel)
 #pragma unroll
             for (int q = 0; q < 5; ++q) {
@@ -889,7 +865,6 @@ __global__ __launch_bounds__(512) void conv3x3_halo3_kernel(const IGemmParams p)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
 
-    if ((ABL & 4096) && second_half) __builtin_amdgcn_s_setprio(1);  // r4 experiment: static priority for the later-dispatched half (guide T5)
     // ---- main loop over (tile, chunk), nine unrolled taps each --------------------------------------------------------------------------
     int cc = 0;
     bool tile_end = cpt == 1;                                    // this chunk is the last of its tile
@@ -1098,15 +1073,8 @@ static void launch_halo3(const IGemmParams& p, int grid, int tr, hipStream_t s) 
     else if (fused == 1) launch_halo3_one<false, 1, 0>(p, grid, s);
     else if (abl == 2) launch_halo3_one<false, 0, 2>(p, grid, s);
     else if (abl == 24) launch_halo3_one<false, 0, 24>(p, grid, s);
-#ifdef GP_HALO_ABLATIONS  // the other r3 / r4 experiments (profiles/HISTORY.md): hipcc ... -DGP_HALO_ABLATIONS=1
-    else if (((p.dbg >> 24) & 3) == 1) launch_halo3_one<false, 0, 2048>(p, grid, s);   // r4 (IGemmParams::dbg bits 24-25): front-loaded fragment
-    else if (((p.dbg >> 24) & 3) == 2) launch_halo3_one<false, 0, 4096>(p, grid, s);   // reads / static wave priority / both: all neutral
-    else if (((p.dbg >> 24) & 3) == 3) launch_halo3_one<false, 0, 6144>(p, grid, s);   // (profiles/r04_halo3_schedule_ab.json)
-    else if (((p.dbg >> 26) & 3) == 1) launch_halo3_one<false, 0, 8192>(p, grid, s);    // r4 (bits 26-27): how much of the K loop is the LDS fragment
-    else if (((p.dbg >> 26) & 3) == 2) launch_halo3_one<false, 0, 16384>(p, grid, s);   // traffic -- no weight fragments / no pixel fragments / neither
-    else if (((p.dbg >> 26) & 3) == 3) launch_halo3_one<false, 0, 24576>(p, grid, s);   // (MFMAs, DMA, waits, barriers, epilogue unchanged; garbage results)
-    else if ((p.dbg >> 30) & 1) launch_halo3_one<false, 0, 32768>(p, grid, s);          // r4 (bit 30): every fragment read issued twice
-    else if ((p.dbg >> 31) & 1) launch_halo3_one<false, 0, 65536>(p, grid, s);          // r4 (bit 31): LDS-DMA as global_load_lds (r2 / r3) instead of MUBUF
+#ifdef GP_HALO_ABLATIONS  // the other profiling ablations (profiles/HISTORY.md): hipcc ... -DGP_HALO_ABLATIONS=1
+    else if ((p.dbg >> 31) & 1) launch_halo3_one<false, 0, 65536>(p, grid, s);   // (IGemmParams::dbg bit 31): LDS-DMA as global_load_lds instead of MUBUF
     else if (abl == 4) launch_halo3_one<false, 0, 4>(p, grid, s);
     else if (abl == 8) launch_halo3_one<false, 0, 8>(p, grid, s);
     else if (abl == 16) launch_halo3_one<false, 0, 16>(p, grid, s);

@@ -241,8 +241,6 @@ int conv_img_ksplit(const IGemmParams& p) {
     const int nc = p.Cin >> 5;
     if (S > nc / 2) S = nc / 2;           // at least two 32-channel chunks (six steps) per slice
     if (S > 16) S = 16;
-    const int s_env = gp_sw().conv_img_s;  // tuning switch
-    if (s_env > 0 && s_env <= nc / 2 && s_env <= 16) S = s_env;
     return S < 1 ? 1 : S;
 }
 

@@ -33,7 +33,7 @@ std::mutex& gp_attr_mutex() {
 
 static GpSwitches g_switches = [] {
     GpSwitches s{};
-    s.gn_fuse_max_slices = s.gn_fuse_below_px = s.vt_tile = s.xfold_lds = -1;
+    s.gn_fuse_max_slices = s.gn_fuse_below_px = s.vt_tile = -1;
     s.qkv_fuse_max_rows = 1 << 30;
     return s;
 }();
@@ -42,12 +42,9 @@ void gp_switches_reload() {
     auto flag = [](const char* n) { return getenv(n) != nullptr ? 1 : 0; };
     auto num = [](const char* n, int dflt) { const char* v = getenv(n); return v ? atoi(v) : dflt; };
     GpSwitches s{};
-    s.flash_ring3 = flag("GENPERCEPT_FLASH_RING3");
     s.no_flash512 = flag("GENPERCEPT_NO_FLASH512");
-    s.f5_dbg = num("GENPERCEPT_F5_DBG", 0);              // timing ablations only: 1 no K DMA, 2 no V DMA
     s.no_conv_few = flag("GENPERCEPT_NO_CONV_FEW");
     s.no_conv_img = flag("GENPERCEPT_NO_CONV_IMG");
-    s.conv_img_s = num("GENPERCEPT_CONV_IMG_S", 0);
     s.no_cross_fold = flag("GENPERCEPT_NO_CROSS_FOLD");
     s.no_gn_fusion = flag("GENPERCEPT_NO_GN_FUSION");
     s.gn_fuse_max_slices = num("GENPERCEPT_GN_FUSE_MAX_SLICES", -1);
@@ -63,13 +60,9 @@ void gp_switches_reload() {
     s.no_splitk = flag("GENPERCEPT_NO_SPLITK");
     s.no_halo = flag("GENPERCEPT_NO_HALO");              // generic implicit GEMM everywhere
     s.no_pgemm = flag("GENPERCEPT_NO_PGEMM");
-    s.gn_apply_old = flag("GENPERCEPT_GN_APPLY_OLD");
     s.no_up_phases = flag("GENPERCEPT_NO_UP_PHASES");      // A/B: the x2-upsample convs through the nine-tap upsample kernel instead of four phase convolutions (r5)
     s.gn_small_old = flag("GENPERCEPT_GN_SMALL_OLD");      // A/B: gn_small_kernel (three passes over L2) instead of gn_small_reg_kernel (r5)
-    s.xfold_lds = num("GENPERCEPT_XFOLD_LDS", -1);       // 0 = the r2 cross-attention fold kernel
-    s.no_fin_fuse = flag("GENPERCEPT_NO_FIN_FUSE");
     s.c_no_flash = flag("GENPERCEPT_C_NO_FLASH");         // A/B: contract precision's head_dim-64 attention unfused (logits in HBM) instead of flash_attn64_split_kernel
-    s.pgemm_ring3 = flag("GENPERCEPT_PGEMM_RING3");       // A/B: the 128-row persistent GEMM with the 3-deep ring of r2 / r3 (default since r4: 4-deep)
     // Engines on other host threads read g_switches on their launch paths: write it only when the environment really changed (tests / A/B
     // scripts, between calls), under a lock, so that concurrent engine creation with an unchanged environment never stores to it.
     static std::mutex mu;

@@ -65,9 +65,9 @@ struct IGemmParams {
 // the C-ABI calls when an engine is created / finalised and at the per-kernel test entry points -- never on the launch path: launchers and
 // the engine only read the cached struct (r3 had 27 getenv sites, several per conv launch, some cached per process and some not).
 struct GpSwitches {
-    int flash_ring3, no_flash512, f5_dbg, no_conv_few, no_conv_img, conv_img_s, no_cross_fold, no_gn_fusion, gn_fuse_max_slices,
-        gn_fuse_below_px, no_stats_fusion, vt_tile, no_gn_small, fp32_scores, no_qkv_fuse, qkv_fuse_max_rows, no_rgb_conv, igemm_dbg, no_splitk,
-        no_halo, no_pgemm, gn_apply_old, xfold_lds, no_fin_fuse, pgemm_ring3, gn_small_old, no_up_phases, c_no_flash;
+    int no_flash512, no_conv_few, no_conv_img, no_cross_fold, no_gn_fusion, gn_fuse_max_slices, gn_fuse_below_px, no_stats_fusion, vt_tile,
+        no_gn_small, fp32_scores, no_qkv_fuse, qkv_fuse_max_rows, no_rgb_conv, igemm_dbg, no_splitk, no_halo, no_pgemm, gn_small_old, no_up_phases,
+        c_no_flash;
 };
 const GpSwitches& gp_sw();
 void gp_switches_reload();

@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const h16_t* __restrict__
 
 // ---- pass 2: combine partials (Chan) and fold gamma/beta into per-(image, channel) scale/shift -----------------------------
 //   y = x * scale[b][c] + shift[b][c],  scale = rstd_g * gamma_c,  shift = beta_c - mean_g * scale
-// The pair is consumed either by gn_apply_kernel or, fused, by the conv kernel that reads the tensor (conv_halo.hip).
+// The pair is consumed either by gn_apply2_kernel or, fused, by the conv kernel that reads the tensor (conv_halo.hip).
 __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ ws, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, float* __restrict__ scale, float* __restrict__ shift,
                                                            int HW, int C, int G, int nchunk, float eps) {
@@ -147,44 +147,6 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
         const float sc = s_stat[2 * gg + 1] * gamma[c];
         scale[(long long)b * C + c] = sc;
         shift[(long long)b * C + c] = beta[c] - s_stat[2 * gg] * sc;
-    }
-}
-
-// ---- pass 3 (only when the consumer cannot fuse it): y = act(x * scale + shift) ----------------------------------------------
-__global__ __launch_bounds__(256) void gn_apply_kernel(const h16_t* __restrict__ x, h16_t* __restrict__ y, const float* __restrict__ scale,
-                                                        const float* __restrict__ shift, int HW, int C, int nchunk, int silu) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];  // [C] scale, [C] shift
-    float* s_scale = sm;
-    float* s_shift = sm + C;
-    const int b = blockIdx.y, ck = blockIdx.x, tid = threadIdx.x;
-    const int per = (HW + nchunk - 1) / nchunk;
-    for (int c = tid; c < C; c += 256) {
-        s_scale[c] = scale[(long long)b * C + c];
-        s_shift[c] = shift[(long long)b * C + c];
-    }
-    __syncthreads();
-    const int nvec = C >> 3;
-    const int p0 = ck * per, p1 = min(HW, p0 + per);
-    const long long base = (long long)b * HW * C;
-    const long long e0 = (long long)p0 * nvec, e1 = (long long)p1 * nvec;
-    for (long long e = e0 + tid; e < e1; e += 256) {
-        const int v = (int)(e % nvec);
-        const uint4 raw = *(const uint4*)(x + base + e * 8);
-        const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
-        float o[8];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int c = v * 8 + 2 * k;
-            o[2 * k] = h16_lo(w[k]) * s_scale[c] + s_shift[c];
-            o[2 * k + 1] = h16_hi(w[k]) * s_scale[c + 1] + s_shift[c + 1];
-        }
-        if (silu) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) o[k] = silu_f(o[k]);
-        }
-        uint4 r;
-        r.x = pack_h16x2(o[0], o[1]); r.y = pack_h16x2(o[2], o[3]); r.z = pack_h16x2(o[4], o[5]); r.w = pack_h16x2(o[6], o[7]);
-        *(uint4*)(y + base + e * 8) = r;
     }
 }
 
@@ -342,10 +304,11 @@ void launch_groupnorm_stats(const h16_t* x, const float* gamma, const float* bet
     hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(256), 0, s, (const float*)ws, gamma, beta, scale, shift, HW, C, G, nchunk, eps);
 }
 
-// r3: the same pass with a fixed 8-channel vector per thread.  gn_apply_kernel above spent its time on a 64-bit modulo and sixteen 4-byte LDS
-// reads per 16 bytes moved (2.6 TB/s on the 300 MB tensors of the VAE, 5.6 % of a pass); here a thread keeps scale / shift of ITS eight
-// channels in registers, a workgroup covers R = 256 / (C / 8) consecutive pixels per step (a contiguous 4 KiB of the NHWC tensor) and
-// four steps' loads are in flight before the first one is used.  C / 8 > 256 (C = 2560): the vectors are walked in blocks of 256.
+// ---- pass 3 (only when the consumer cannot fuse it): y = act(x * scale + shift) ----------------------------------------------
+// A fixed 8-channel vector per thread: a thread keeps scale / shift of ITS eight channels in registers (a per-element channel lookup in LDS
+// cost a 64-bit modulo and sixteen 4-byte LDS reads per 16 bytes moved), a workgroup covers R = 256 / (C / 8) consecutive pixels per step (a
+// contiguous 4 KiB of the NHWC tensor) and four steps' loads are in flight before the first one is used.  C / 8 > 256 (C = 2560): the vectors
+// are walked in blocks of 256.
 template <int SILU>
 __global__ __launch_bounds__(256) void gn_apply2_kernel(const h16_t* __restrict__ x, h16_t* __restrict__ y, const float* __restrict__ scale,
                                                          const float* __restrict__ shift, int HW, int C, int nchunk, int tpr, int R) {
@@ -398,12 +361,6 @@ __global__ __launch_bounds__(256) void gn_apply2_kernel(const h16_t* __restrict_
 }
 
 void launch_groupnorm_apply(const h16_t* x, h16_t* y, const float* scale, const float* shift, int B, int HW, int C, int silu, hipStream_t s) {
-    const bool old_kernel = gp_sw().gn_apply_old;  // A/B switch
-    if (old_kernel) {
-        const int nchunk = gn_nchunk(HW);
-        hipLaunchKernelGGL(gn_apply_kernel, dim3(nchunk, B), dim3(256), (size_t)2 * C * sizeof(float), s, x, y, scale, shift, HW, C, nchunk, silu);
-        return;
-    }
     const int nvec = C >> 3;
     const int tpr = nvec < 256 ? nvec : 256;   // threads per pixel row
     const int R = 256 / tpr;                   // pixel rows per workgroup step
@@ -752,11 +709,9 @@ bool cross_attn_fold_supported(int C, int heads) {
 template <int VPT, int R, int HEADS>
 static void launch_cross_fold_one(const h16_t* y, h16_t* y_out, h16_t* n3_out, const float* U, const float* u0, const float* G, const float* c0,
                                   const float* g3, const float* b3, int rows, int C, float eps, hipStream_t s) {
-    const int mode_env = gp_sw().xfold_lds;  // A/B switch: 0 = the r2 kernel
     const int blocks = (rows + 4 * R - 1) / (4 * R);
     const size_t tab = (size_t)HEADS * C * 4, vec = (size_t)3 * C * 4;
-    int mode = 2 * tab + vec <= 64 * 1024 ? 2 : (tab + vec <= 120 * 1024 ? 1 : 0);  // tables in LDS when >= 2 (mode 2) / 1 (mode 1) workgroups fit a CU
-    if (mode_env >= 0 && mode_env < mode) mode = mode_env;
+    const int mode = 2 * tab + vec <= 64 * 1024 ? 2 : (tab + vec <= 120 * 1024 ? 1 : 0);  // tables in LDS when >= 2 (mode 2) / 1 (mode 1) workgroups fit a CU
     if (mode == 0 || blocks < 64) {
         hipLaunchKernelGGL((cross_fold_kernel<VPT, R, HEADS, 0>), dim3(blocks), dim3(256), 0, s, y, y_out, n3_out, U, u0, G, c0, g3, b3, rows, C, eps);
         return;

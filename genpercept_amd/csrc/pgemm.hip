@@ -5,9 +5,9 @@
 // took 23.7 us, of which 10 us remained with neither K loop nor epilogue (launch of 1440 workgroups, address setup, the first HBM
 // round trip) and 5-8 us were an epilogue that nothing overlapped.  Here (same recipe as conv3x3_halo3_kernel):
 //   * one workgroup per CU walks the M tiles of ONE 128-column slice: bias and weight rows are per-workgroup constants;
-//   * the (tile, k) step stream never stops: a 3-deep LDS-DMA ring (A tile BM x 64 + W tile 128 x 64 per stage) runs three steps ahead
+//   * the (tile, k) step stream never stops: an NB-deep LDS-DMA ring (A tile BM x 64 + W tile 128 x 64 per stage) runs NB steps ahead
 //     ACROSS tile boundaries, so a tile's first operands arrive while the previous tile still computes;
-//   * ring slot = step % 3 is a compile-time constant (loop unrolled by three): every ds_read_b128 uses an immediate offset;
+//   * ring slot = step % NB is a compile-time constant (loop unrolled by a multiple of NB): every ds_read_b128 uses an immediate offset;
 //     fragments of step s+1 are read during step s's two MFMA batches (register sets dead in that batch);
 //   * per-WAVE epilogue, no workgroup barrier: fp32 staging through the LDS pieces the wave itself will refill next (its own DMA
 //     destinations of the slot just consumed), coalesced 16-byte stores, residual rows prefetched; stores drain under the next tile;
@@ -18,8 +18,12 @@
 
 constexpr int PG_BN = 128;
 
-template <int BM, int NB = 3>
+// NB: ring depth (stages in flight ahead of the compute): 3 for the 256-row tile, 4 (4 x 32 KiB) for the 128-row tile, whose launches are the
+// latency-bound ones -- M = 2304 / 9216 with one or two tiles per workgroup and 10-40 K-steps each, ~1.5 us per K-step against 0.2 us of MFMA work:
+// with a prefetch distance of three steps a stage has 1.5x as long to arrive.
+template <int BM>
 struct PGemmGeom {
+    static constexpr int NB = BM == 256 ? 3 : 4;
     static constexpr int WM = BM / 64, WN = 8 / WM;      // 8 waves: 4 x 2 (BM 256) or 2 x 4 (BM 128); wave tile 64 rows x TN columns
     static constexpr int TN = PG_BN / WN, FM = 4, FN = TN / 16, FP = FN / 2;
     static constexpr int A_IT = BM / 64, B_IT = 2, LPS = A_IT + B_IT;
@@ -29,14 +33,11 @@ struct PGemmGeom {
     static constexpr int LDS = BIAS_OFF + 512;
 };
 
-// NB: ring depth (stages in flight ahead of the compute).  3 everywhere in r2 / r3; r4: 4 for the 128-row tile (4 x 32 KiB), whose launches are the
-// latency-bound ones -- M = 2304 / 9216 with one or two tiles per workgroup and 10-40 K-steps each, ~1.5 us per K-step against 0.2 us of MFMA work:
-// with a prefetch distance of three steps a stage has 1.5x as long to arrive.
 // ABL: compile-time ablations for profiling (1: LDS-DMA as global_load_lds, the r2 / r3 form; 2: no MFMA, 4: no output stores, 8: no DMA)
-template <int BM, int ABL = 0, int NB = 3>
+template <int BM, int ABL = 0>
 __global__ __launch_bounds__(512) void pgemm_kernel(const IGemmParams p) {
-    using G = PGemmGeom<BM, NB>;
-    constexpr int WN = G::WN, TN = G::TN, FM = G::FM, FN = G::FN, FP = G::FP;
+    using G = PGemmGeom<BM>;
+    constexpr int NB = G::NB, WN = G::WN, TN = G::TN, FM = G::FM, FN = G::FN, FP = G::FP;
     constexpr int A_IT = G::A_IT, B_IT = G::B_IT, LPS = G::LPS, A_BYTES = G::A_BYTES, STAGE = G::STAGE;
     constexpr int SLW = TN / 8;          // 8-channel slots per staged row
     constexpr int RPI = 64 / SLW;        // rows one read-back instruction covers (8 or 16)
@@ -430,7 +431,7 @@ __global__ __launch_bounds__(512) void pgemm_kernel(const IGemmParams p) {
         }
     };
 
-    // ---- prologue: three stages in flight, fragments of step 0 in registers ----------------------------------------------------------
+    // ---- prologue: NB stages in flight, fragments of step 0 in registers ----------------------------------------------------------
     if (total > 0) stage(0);
     if (total > 1) stage(1);
     if (total > 2) stage(2);
@@ -538,17 +539,17 @@ int pgemm_bm(const IGemmParams& p) {
     return t256 >= 3 * groups ? 256 : 128;
 }
 
-template <int BM, int ABL, int NB = 3>
+template <int BM, int ABL>
 static void launch_pgemm_one(const IGemmParams& p, int ncu, hipStream_t s) {
-    using G = PGemmGeom<BM, NB>;
+    using G = PGemmGeom<BM>;
     static unsigned long long attr_mask = 0;
-    gp_once_per_device(&attr_mask, [&] { (void)hipFuncSetAttribute((const void*)pgemm_kernel<BM, ABL, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS); });
+    gp_once_per_device(&attr_mask, [&] { (void)hipFuncSetAttribute((const void*)pgemm_kernel<BM, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS); });
     const int ncols = p.N > p.n_store ? p.N : p.n_store;
     const int tiles_n = (ncols + PG_BN - 1) / PG_BN, tiles_m = (p.M + BM - 1) / BM;
     int groups = ncu / tiles_n;
     if (groups < 1) groups = 1;
     if (groups > tiles_m) groups = tiles_m;
-    hipLaunchKernelGGL((pgemm_kernel<BM, ABL, NB>), dim3(groups * tiles_n), dim3(512), G::LDS, s, p);
+    hipLaunchKernelGGL((pgemm_kernel<BM, ABL>), dim3(groups * tiles_n), dim3(512), G::LDS, s, p);
 }
 
 void launch_pgemm(const IGemmParams& p, hipStream_t s) {
@@ -567,14 +568,13 @@ void launch_pgemm(const IGemmParams& p, hipStream_t s) {
         else if (abl == 8) launch_pgemm_one<256, 8>(p, ncu, s);
         else launch_pgemm_one<256, 0>(p, ncu, s);
     } else {
-        if (abl == 1) launch_pgemm_one<128, 1, 4>(p, ncu, s);
+        if (abl == 1) launch_pgemm_one<128, 1>(p, ncu, s);
         else if (abl == 2) launch_pgemm_one<128, 2>(p, ncu, s);
         else if (abl == 4) launch_pgemm_one<128, 4>(p, ncu, s);
         else if (abl == 8) launch_pgemm_one<128, 8>(p, ncu, s);
         else if (abl == 10) launch_pgemm_one<128, 10>(p, ncu, s);
         else if (abl == 14) launch_pgemm_one<128, 14>(p, ncu, s);
-        else if (((p.dbg >> 23) & 1) || gp_sw().pgemm_ring3) launch_pgemm_one<128, 0>(p, ncu, s);   // A/B: the 3-deep ring of r2 / r3
-        else launch_pgemm_one<128, 0, 4>(p, ncu, s);
+        else launch_pgemm_one<128, 0>(p, ncu, s);
     }
 }
 

@@ -393,10 +393,11 @@ GEMM_CASES = [
     # fp32 output (the exact float32 value itself) and fp16 output in either library
     ("igemm_out_fp32", 1000, 320, 1280, 1, False, 0, "none", 1, {}, 1.0, 6, None),
     ("igemm_out_fp16", 1000, 320, 1280, 4, False, 0, "none", 2, {}, 1.0, 6, None),
-    # persistent GEMM: 128-row tiles (several per workgroup, ragged last tile), the 3-deep ring, 256-row tiles with a ragged tail
+    # persistent GEMM: 128-row tiles (4-deep ring; several tiles per workgroup, ragged last tile; 5, 40 and 10 K-steps per tile), 256-row tiles
+    # (3-deep ring) with a ragged tail
     ("pgemm128_ragged", 4801, 320, 320, 7, True, 0, "none", 0, {}, 1.0, 3, 128),
     ("pgemm128_k2560", 9216, 640, 2560, 7, True, 0, "none", 0, {}, 1.0, 3, 128),
-    ("pgemm128_ring3", 4801, 320, 640, 7, True, 0, "none", 0, {"GENPERCEPT_PGEMM_RING3": "1"}, 1.0, 3, 128),
+    ("pgemm128_k640", 4801, 320, 640, 7, True, 0, "none", 0, {}, 1.0, 3, 128),
     ("pgemm256_ragged", 200003, 128, 128, 7, True, 0, "none", 0, {}, 1.0, 3, 256),
     ("pgemm_auto_relu", 36864, 320, 320, 0, True, 0, "relu", 0, {}, 1.0, 3, None),
     ("pgemm_zero_fill", 9000, 320, 256, 0, True, 328, "none", 0, {}, 1.0, 3, None),

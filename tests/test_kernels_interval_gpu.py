@@ -136,9 +136,9 @@ GN_CASES = [
     # gn_stats_kernel<2> (C / 8 = 320 > 256) and gn_apply2_kernel walking the vectors in blocks of 256; HW = 900 > 819 keeps it off the one-launch path
     ("stats2_apply2_c2560", 1, 2560, 900, True, 1.0, {}),
     ("stats1_apply2_silu_hw70000", 1, 128, 70000, True, 1.0, {}),   # 256 chunks of 274 pixels
-    # gn_apply_kernel (GENPERCEPT_GN_APPLY_OLD)
-    ("stats1_apply_old_silu", 2, 320, 300, True, 1.0, {"GENPERCEPT_GN_APPLY_OLD": "1"}),
-    ("stats1_apply_old", 1, 64, 1030, False, 1.0, {"GENPERCEPT_GN_APPLY_OLD": "1"}),
+    # gn_apply2_kernel<1> with 40 threads per pixel row (C / 8 = 40: R = 6 rows per step, 16 idle threads); <0> with 8 (R = 32), HW no multiple of 4 R
+    ("stats1_apply2_silu_c320_hw300", 2, 320, 300, True, 1.0, {}),
+    ("stats1_apply2_c64_hw1030", 1, 64, 1030, False, 1.0, {}),
     # one launch: gn_small_reg_kernel<4> (items = 144 * 5 = 720 <= 1024), B > 1
     ("small_reg4_silu", 4, 1280, 144, True, 1.0, {}),
     ("small_reg4_hw1", 2, 512, 1, False, 1.0, {}),                  # items = 2
@@ -314,26 +314,26 @@ def test_layernorm_interval(case, metric_log):
 
 
 # ---- cross-attention against the two-token context, folded (cross_fold_kernel) ----------------------------------------------------------------
-# (rows, C, heads, GENPERCEPT_XFOLD_LDS or None) -- launch_cross_fold_r / launch_cross_fold_one (norm.hip): rows per wave R = 4 from 16384 rows
+# (rows, C, heads) -- launch_cross_fold_r / launch_cross_fold_one (norm.hip): rows per wave R = 4 from 16384 rows
 # (VPT * heads <= 20), 2 from 4096; at C = 1280: 3 for rows in [2048, 4096), 2 for [512, 2048).  Table mode: 2 (U and G in LDS) when 2 * heads * C * 4 +
-# 12 C <= 64 KiB, 1 (U only) when heads * C * 4 + 12 C <= 120 KiB, lowered by the switch; fewer than 64 workgroups (rows / 4 R) always run mode 0.
+# 12 C <= 64 KiB, 1 (U only) when heads * C * 4 + 12 C <= 120 KiB; fewer than 64 workgroups (rows / 4 R) always run mode 0.
 FOLD_CASES = [
-    (300, 64, 1, None),        # heads 1, R 1, mode 2
-    (5, 128, 2, None),         # heads 2, 2 workgroups: mode 0; ragged last workgroup
-    (1000, 256, 4, None),      # heads 4, mode 2
-    (1000, 320, 5, 0), (1000, 320, 5, 1), (1001, 320, 5, 2),   # heads 5: the three table modes
-    (300, 640, 10, None),      # heads 10 (VPT 2), mode 2 (58880 bytes)
-    (4100, 640, 10, 1),        # R 2, mode 1
-    (577, 1280, 20, None),     # heads 20 (VPT 3): R 2, 73 workgroups, mode 1 (117760 bytes)
-    (2050, 1280, 20, None),    # R 3, ragged
-    (2304, 1280, 20, 0),       # R 3, mode 0
-    (20000, 320, 5, None),     # R 4
+    (300, 64, 1),        # heads 1, R 1, mode 2
+    (5, 128, 2),         # heads 2, 2 workgroups: mode 0; ragged last workgroup
+    (1000, 256, 4),      # heads 4, mode 2
+    (1000, 320, 5), (1001, 320, 5),   # heads 5, mode 2 (22400 bytes); ragged last wave
+    (300, 640, 10),      # heads 10 (VPT 2), mode 2 (58880 bytes)
+    (4100, 640, 10),     # R 2, mode 2
+    (577, 1280, 20),     # heads 20 (VPT 3): R 2, 73 workgroups, mode 1 (117760 bytes)
+    (2050, 1280, 20),    # R 3, ragged
+    (2304, 1280, 20),    # R 3, mode 1
+    (20000, 320, 5),     # R 4
 ]
 
 
 def fold_inputs(case, dtype):
-    rows, c, heads, _ = case
-    g = torch.Generator().manual_seed(seed_of("fold", *case[:3]))
+    rows, c, heads = case
+    g = torch.Generator().manual_seed(seed_of("fold", *case))
     y = r16((torch.randn(rows, c, generator=g) * 1.5 + 0.3).double(), dtype)
     p = dict(wq=torch.randn(c, c, generator=g) / math.sqrt(c), wo=torch.randn(c, c, generator=g) / math.sqrt(c), bo=0.1 * torch.randn(c, generator=g),
              kc=torch.randn(2, c, generator=g), vc=torch.randn(2, c, generator=g), g2=1 + 0.1 * torch.randn(c, generator=g),
@@ -378,11 +378,9 @@ def fold_ref_bound(y, p, heads, eps=1e-5):
 
 
 @pytest.mark.parametrize("case", FOLD_CASES)
-def test_cross_attention_fold_interval(case, metric_log, monkeypatch):
+def test_cross_attention_fold_interval(case, metric_log):
     e = _eng()
-    rows, c, heads, lds = case
-    if lds is not None:
-        monkeypatch.setenv("GENPERCEPT_XFOLD_LDS", str(lds))
+    rows, c, heads = case
     d, dt = _dev(), e.act_dtype()
     y, p = fold_inputs(case, dt)
     y, p = y.to(d), {k: v.to(d) for k, v in p.items()}
@@ -437,14 +435,13 @@ def heads_merge(x):
     return x.transpose(1, 2).reshape(b, t, h * hd)
 
 
-# (B, T, heads, env): flash_attn64_kernel<2, 2>, or <2, 3> under GENPERCEPT_FLASH_RING3; 128 queries per workgroup, 64-key tiles, the last one masked
-FLASH64_CASES = [(1, 1, 1, {}), (2, 63, 5, {}), (1, 64, 1, {}), (2, 65, 1, {}), (1, 127, 5, {}), (1, 128, 20, {}), (1, 129, 1, {}), (2, 1200, 5, {}),
-                 (1, 2304, 20, {}), (1, 2304, 1, {}),
-                 (2, 65, 5, {"GENPERCEPT_FLASH_RING3": "1"}), (1, 128, 1, {"GENPERCEPT_FLASH_RING3": "1"}), (1, 1200, 20, {"GENPERCEPT_FLASH_RING3": "1"})]
+# (B, T, heads): flash_attn64_kernel<2>; 128 queries per workgroup, 64-key tiles, the last one masked
+FLASH64_CASES = [(1, 1, 1), (2, 63, 5), (1, 64, 1), (2, 65, 1), (1, 127, 5), (1, 128, 20), (1, 129, 1), (2, 1200, 5), (1, 2304, 20), (1, 2304, 1),
+                 (2, 65, 5), (1, 128, 1), (1, 1200, 20)]
 
 
 def flash64_inputs(case, dtype, heads=None):
-    b, t, h0, _ = case
+    b, t, h0 = case
     c = (heads or h0) * 64
     g = torch.Generator().manual_seed(seed_of("flash64", b, t, h0))
     qk = r16((torch.randn(b, t, 2 * c, generator=g) * 1.5).double(), dtype)
@@ -502,14 +499,12 @@ def _flash64_check(name, q, k, v, heads, log, failures, wrong_padded=False):
     gate(name, out, heads_merge(o), heads_merge(err), log, failures, wrong=wrong)
 
 
-@pytest.mark.parametrize("case", FLASH64_CASES, ids=[f"{c[0]}x{c[1]}x{c[2]}{'_ring3' if c[3] else ''}" for c in FLASH64_CASES])
-def test_flash_attention_interval(case, metric_log, monkeypatch):
+@pytest.mark.parametrize("case", FLASH64_CASES, ids=[f"{c[0]}x{c[1]}x{c[2]}" for c in FLASH64_CASES])
+def test_flash_attention_interval(case, metric_log):
     e = _eng()
-    for kname, val in case[3].items():
-        monkeypatch.setenv(kname, val)
     q, k, v = flash64_inputs(case, e.act_dtype())
     failures = []
-    _flash64_check(f"flash64{case[:3]}{'_ring3' if case[3] else ''}", q, k, v, case[2], metric_log, failures)  # measured: bf16 <= 0.68, fp16 <= 0.70
+    _flash64_check(f"flash64{case}", q, k, v, case[2], metric_log, failures)  # measured: bf16 <= 0.68, fp16 <= 0.70
     assert not failures, "\n".join(failures)
 
 
@@ -523,13 +518,10 @@ def test_flash_attention_negative_logits_interval(case, metric_log):
     assert not failures, "\n".join(failures)
 
 
-@pytest.mark.parametrize("ring3", [False, True])
-def test_flash_attention_spiky_interval(ring3, metric_log, monkeypatch):
+def test_flash_attention_spiky_interval(metric_log):
     e = _eng()
-    if ring3:
-        monkeypatch.setenv("GENPERCEPT_FLASH_RING3", "1")
     failures = []
-    _flash64_check(f"flash64_spiky{'_ring3' if ring3 else ''}", *spiky_inputs(e.act_dtype()), 1, metric_log, failures)  # measured: bf16 0.46, fp16 0.44 (either ring)
+    _flash64_check("flash64_spiky", *spiky_inputs(e.act_dtype()), 1, metric_log, failures)  # measured: bf16 0.46, fp16 0.44
     assert not failures, "\n".join(failures)
 
 

@@ -228,7 +228,7 @@ def test_layernorm_f32_within_half_gate_and_wrong_variants_outside(case, dt):
 @pytest.mark.parametrize("dt", DTYPES, ids=["bf16", "fp16"])
 @pytest.mark.parametrize("case", FOLD_CASES)
 def test_cross_fold_f32_within_half_gate_and_wrong_variants_outside(case, dt):
-    rows, c, heads, _ = case
+    rows, c, heads = case
     if rows > 2500:
         case = (2500,) + case[1:]   # reduced row count on the CPU (the inputs of the first rows differ from the GPU case's: same generator, other seed)
     y, p = fold_inputs(case, dt)
@@ -301,13 +301,13 @@ def _attention_checks(name, q, k, v, scale, dt, hd, padded_tile=0):
 
 
 @pytest.mark.parametrize("dt", DTYPES, ids=["bf16", "fp16"])
-@pytest.mark.parametrize("case", FLASH64_CASES, ids=[f"{c[0]}x{c[1]}x{c[2]}{'_ring3' if c[3] else ''}" for c in FLASH64_CASES])
+@pytest.mark.parametrize("case", FLASH64_CASES, ids=[f"{c[0]}x{c[1]}x{c[2]}" for c in FLASH64_CASES])
 def test_flash64_f32_within_half_gate_and_wrong_variants_outside(case, dt):
-    b, t, heads, _ = case
+    b, t, heads = case
     q, k, v = flash64_inputs(case, dt)
     hs = min(heads, 2) if t >= 1200 else heads   # reduced head count on the CPU for the long sequences (the first heads of the GPU case's tensors)
     q, k, v = (heads_split(z, heads)[:1, :hs] for z in (q, k, v))
-    _attention_checks(f"flash64{case[:3]}", q, k, v, 0.125, dt, 64)
+    _attention_checks(f"flash64{case}", q, k, v, 0.125, dt, 64)
 
 
 @pytest.mark.parametrize("dt", DTYPES, ids=["bf16", "fp16"])

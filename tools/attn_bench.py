@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel-only timing of flash_attn64 at the UNet's four levels and of flash_attn512 at the VAE's mid block (batch 4): HIP events around
 back-to-back launches.
-usage: python tools/attn_bench.py [--hd512-only]  (GENPERCEPT_FLASH_RING3=1 selects the three-stage K / V ring of flash_attn64: run twice for an A/B)"""
+usage: python tools/attn_bench.py [--hd512-only]"""
 import os
 import sys
 
@@ -59,7 +59,7 @@ def main():
             torch.cuda.synchronize()
             best = min(best, e0.elapsed_time(e1) / 20)
         fl = 4.0 * b * heads * t * t * 64
-        print(f"T={t:5d} heads={heads:2d}  {best * 1e3:8.1f} us  {fl / best / 1e9:7.1f} TFLOP/s  ring={'3' if os.environ.get('GENPERCEPT_FLASH_RING3') else '2'}", flush=True)
+        print(f"T={t:5d} heads={heads:2d}  {best * 1e3:8.1f} us  {fl / best / 1e9:7.1f} TFLOP/s", flush=True)
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 #!/bin/bash
 # builds tools/kbench_abl: kbench against a bf16 library whose conv_halo.hip carries the profiling ablations (-DGP_HALO_ABLATIONS=1: IGemmParams::dbg
-# bits 9-19 and 24-27); the product library under genpercept_amd/lib/ is not touched
+# bits 9-19 and 31); the product library under genpercept_amd/lib/ is not touched
 set -e
 cd "$(dirname "$0")/.."
 python -m genpercept_amd.build >/dev/null
