@@ -430,8 +430,17 @@ void launch_flash_attn64_split(const h16_t* qk_hi, const h16_t* qk_lo, const h16
 // ---- flash_attn512: the VAE mid-block attention (one head, head_dim 512; genpercept_pipeline.py:500-501,521-522) ----------------------
 // Same dataflow as flash_attn64 (S^T = K Q^T on v_mfma_f32_32x32x16, lane-local online softmax, the probabilities already in
 // B-operand order for O^T += V^T P^T), sized for d = 512:
-//   * one wave = 32 queries: Q^T stays in 128 VGPRs, O^T (512 x 32 fp32) in 256 accumulator registers -> one wave per SIMD, one
-//     256-thread workgroup (128 queries) per CU;
+//   * one wave = 32 queries: 24 of the 32 Q k-steps stay in 96 arch registers (the rest is parked in LDS), O^T (512 x 32 fp32) in the 256
+//     accumulator registers -> one wave per SIMD, one 256-thread workgroup (128 queries) per CU;
+//   * registers: the accumulator half of the file is O^T and nothing else, allocated by hand (f5_acc_*: block d = a[16 d .. 16 d + 15], named
+//     literally in asm statements); everything else -- Q, the two S^T chains (asm MFMAs with arch-register accumulators), two rings of F5_RD
+//     fragments, P -- fits the 256 arch registers: no scratch, no v_accvgpr copy that the kernel did not write itself
+//     (tests/test_flash512_resources_host.py);
+//   * per tile, one wave: 32 S^T MFMAs, each K fragment requested F5_RD MFMAs before its use, with the next tile's sixteen DMA pieces between
+//     them (unconditionally: on the last tile through an empty buffer resource); then the first F5_RD V^T fragments are requested, the
+//     softmax runs above them, and the 32 P.V MFMAs follow, each V^T fragment again F5_RD MFMAs ahead.  The waits in front of the MFMAs are
+//     counted (lgkmcnt(F5_RD - 1) in the steady state, 4 .. 0 for the last fragments of a phase); asm statements keep their order, the
+//     fragment reads between them are the compiler's and so are their waits;
 //   * 32-key tiles: K tile [32 keys][512 d] (1 KiB rows) + V^T tile [512 d][32 keys] (64-byte rows) = 64 KiB per stage, two stages;
 //     64 MFMAs (2048 matrix-pipe cycles) per wave and tile against 64 KiB of ds_read_b128 per wave (1024 LDS cycles per CU);
 //   * the K rows are staged in the order pi(i) = i with bits 2 and 3 swapped, so that the 8 keys a lane's accumulator registers
@@ -455,6 +464,59 @@ GP_DEV float other_half(float v) {
     const u32x2p_t r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
     return (threadIdx.x & 32) ? __uint_as_float(r[0]) : __uint_as_float(r[1]);   // r[0] = [lo, lo], r[1] = [hi, hi]
 }
+// The S^T MFMAs as asm statements with ARCH-register accumulators.  The builtin's result always lands in the accumulator half of the file
+// (a kernel that may use more than 256 registers gets the AGPR form of every MFMA), and that half is O^T: with the builtin two blocks of
+// O^T were copied out and back around every tile's score phase (64 v_accvgpr moves and 32 registers, which is what made the kernel spill).
+// asm statements keep their order; operand waits (lgkmcnt for the fragments) are still the compiler's, the wait states between the last
+// MFMA and the first VALU reader of the chain are not (f5_mfma_settle).
+#if GP_F16
+#define F5_MFMA "v_mfma_f32_32x32x16_f16"
+#else
+#define F5_MFMA "v_mfma_f32_32x32x16_bf16"
+#endif
+GP_DEV void f5_mfma_first(f32x16_t& c, h16x8_t a, h16x8_t b) { asm volatile(F5_MFMA " %0, %1, %2, 0" : "=&v"(c) : "v"(a), "v"(b)); }
+GP_DEV void f5_mfma_acc(f32x16_t& c, h16x8_t a, h16x8_t b) { asm volatile(F5_MFMA " %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b)); }
+GP_DEV void f5_mfma_settle(f32x16_t& c0, f32x16_t& c1) { asm volatile("s_nop 15\n\ts_nop 3" : "+v"(c0), "+v"(c1)); }  // 8-pass MFMA result -> VALU
+// O^T is allocated BY HAND: block d (channels 32 d .. 32 d + 31) is a[16 d .. 16 d + 15], named literally in asm statements, for the whole kernel.
+// Left to the compiler, the blocks got different registers in the hot loop, the cold rescale path and the epilogue, and all 256 were permuted
+// through the arch registers -- and the Q fragments through scratch -- between them.  The compiler must therefore never touch an accumulator
+// register itself: it has no reason to while the kernel does not spill (tests/test_flash512_resources_host.py checks both).
+#define F5_A10(t) "a" #t "0", "a" #t "1", "a" #t "2", "a" #t "3", "a" #t "4", "a" #t "5", "a" #t "6", "a" #t "7", "a" #t "8", "a" #t "9"
+#define F5_ALL_ACC                                                                                                                            \
+    F5_A10(), F5_A10(1), F5_A10(2), F5_A10(3), F5_A10(4), F5_A10(5), F5_A10(6), F5_A10(7), F5_A10(8), F5_A10(9), F5_A10(10), F5_A10(11),     \
+        F5_A10(12), F5_A10(13), F5_A10(14), F5_A10(15), F5_A10(16), F5_A10(17), F5_A10(18), F5_A10(19), F5_A10(20), F5_A10(21), F5_A10(22),  \
+        F5_A10(23), F5_A10(24), "a250", "a251", "a252", "a253", "a254", "a255"
+GP_DEV void f5_acc_zero() {
+    asm volatile(".set f5_i, 0\n\t.rept 256\n\tv_accvgpr_write_b32 a[f5_i], 0\n\t.set f5_i, f5_i + 1\n\t.endr" ::: F5_ALL_ACC);
+}
+// cold path: O^T *= alpha, one register at a time through one arch register (v_accvgpr_write -> MFMA C operand: the trailing wait states)
+GP_DEV void f5_acc_scale(float alpha) {
+    float t;
+    asm volatile(".set f5_i, 0\n\t.rept 256\n\tv_accvgpr_read_b32 %0, a[f5_i]\n\tv_mul_f32 %0, %1, %0\n\tv_accvgpr_write_b32 a[f5_i], %0\n\t"
+                 ".set f5_i, f5_i + 1\n\t.endr\n\ts_nop 7"
+                 : "=&v"(t) : "v"(alpha) : F5_ALL_ACC);
+}
+// O^T block d += a b (the P.V MFMA); d is a constant after unrolling
+#define F5_PV(d) case d: asm volatile(F5_MFMA " a[" #d "*16:" #d "*16+15], %0, %1, a[" #d "*16:" #d "*16+15]" ::"v"(a), "v"(b)); break;
+GP_DEV void f5_acc_mfma(int d, h16x8_t a, h16x8_t b) {
+    switch (d) { F5_PV(0) F5_PV(1) F5_PV(2) F5_PV(3) F5_PV(4) F5_PV(5) F5_PV(6) F5_PV(7) F5_PV(8) F5_PV(9) F5_PV(10) F5_PV(11) F5_PV(12) F5_PV(13) F5_PV(14) F5_PV(15) }
+}
+#undef F5_PV
+// block d out into arch registers (epilogue); f5_acc_settle first: the wait states between the last MFMA and the first read
+GP_DEV void f5_acc_settle() { asm volatile("s_nop 15\n\ts_nop 3"); }
+#define F5_RDL(d, r) "v_accvgpr_read_b32 %" #r ", a[" #d "*16+" #r "]\n\t"
+#define F5_GET(d)                                                                                                                              \
+    case d:                                                                                                                                    \
+        asm volatile(F5_RDL(d, 0) F5_RDL(d, 1) F5_RDL(d, 2) F5_RDL(d, 3) F5_RDL(d, 4) F5_RDL(d, 5) F5_RDL(d, 6) F5_RDL(d, 7) F5_RDL(d, 8)       \
+                         F5_RDL(d, 9) F5_RDL(d, 10) F5_RDL(d, 11) F5_RDL(d, 12) F5_RDL(d, 13) F5_RDL(d, 14) F5_RDL(d, 15)                       \
+                     : "=v"(t[0]), "=v"(t[1]), "=v"(t[2]), "=v"(t[3]), "=v"(t[4]), "=v"(t[5]), "=v"(t[6]), "=v"(t[7]), "=v"(t[8]), "=v"(t[9]),  \
+                       "=v"(t[10]), "=v"(t[11]), "=v"(t[12]), "=v"(t[13]), "=v"(t[14]), "=v"(t[15]));                                           \
+        break;
+GP_DEV void f5_acc_get(int d, float* t) {
+    switch (d) { F5_GET(0) F5_GET(1) F5_GET(2) F5_GET(3) F5_GET(4) F5_GET(5) F5_GET(6) F5_GET(7) F5_GET(8) F5_GET(9) F5_GET(10) F5_GET(11) F5_GET(12) F5_GET(13) F5_GET(14) F5_GET(15) }
+}
+#undef F5_GET
+#undef F5_RDL
 GP_DEV int k512_off(int row, int slot) { return row * 1024 + ((slot ^ (row & 15)) << 4); }
 GP_DEV int v512_off(int row, int slot) { return row * 64 + ((slot ^ ((row >> 2) & 3)) << 4); }
 GP_DEV int pi23(int i) { return (i & ~12) | ((i & 4) << 1) | ((i & 8) >> 1); }  // swap bits 2 and 3
@@ -474,9 +536,6 @@ __global__ __launch_bounds__(256) void flash_attn512_kernel(const h16_t* __restr
     const int sid = xcd_remap(blockIdx.x, G);           // consecutive sid = consecutive query blocks of one image on one XCD
     const unsigned smem_base = (unsigned)(unsigned long long)smem;
     const float sc = scale * 1.44269504088896340736f;
-    f32x16_t zero16;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
 
     const int items = rounds + ((L && sid / S < L) ? 1 : 0);
     for (int it = 0; it < items; ++it) {
@@ -510,10 +569,11 @@ __global__ __launch_bounds__(256) void flash_attn512_kernel(const h16_t* __restr
         {
             const int q = q0 + l31;
             const bool ok = q < T;
+            const h16_t* qrow = Qb + (long long)min(q, T - 1) * ldq + hh * 8;   // rows past T: a valid address, the values are replaced by zeros
 #pragma unroll
             for (int ks = 0; ks < 32; ++ks) {
-                h16x8_t v = h16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
-                if (ok) v = *(const h16x8_t*)(Qb + (long long)q * ldq + ks * 16 + hh * 8);
+                h16x8_t v = *(const h16x8_t*)(qrow + ks * 16);
+                if (!ok) v = h16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
                 if ((ks & 3) != 3) qf[3 * (ks >> 2) + (ks & 3)] = v;   // every fourth k-step is parked in LDS
                 else *(lds_frag_wptr)(q_lds + (ks >> 2) * 1024) = v;
             }
@@ -523,8 +583,12 @@ __global__ __launch_bounds__(256) void flash_attn512_kernel(const h16_t* __restr
         }
         // DMA sources: one buffer resource per operand (base of this image), a per-lane byte offset that is the same for every tile and a
         // uniform byte offset per instruction
-        const buf_rsrc_t k_rs = make_rsrc(Kb, (unsigned)((long long)T * ldk * 2));
-        const buf_rsrc_t v_rs = make_rsrc(Vb, (unsigned)(512ll * Tpad * 2));
+        // k_rs / v_rs are re-made per tile in s_phase: with the image's size when there is a next tile, EMPTY when there is none.  Every piece
+        // of an empty resource is out of range (no memory access; the slot it lands in is the one a next tile would have overwritten and is
+        // never read), so the sixteen pieces need no branch inside the unrolled S^T phase.
+        const unsigned k_bytes = (unsigned)((long long)T * ldk * 2), v_bytes = (unsigned)(512ll * Tpad * 2);
+        buf_rsrc_t k_rs = make_rsrc(Kb, k_bytes);
+        buf_rsrc_t v_rs = make_rsrc(Vb, v_bytes);
         unsigned koff[8];  // K: my LDS slot `lane` of row i = 8 wave + n holds logical slot lane ^ (i & 15)
 #pragma unroll
         for (int n = 0; n < 8; ++n) koff[n] = (unsigned)(lane ^ ((wave & 1) * 8 + n)) << 4;
@@ -546,9 +610,7 @@ __global__ __launch_bounds__(256) void flash_attn512_kernel(const h16_t* __restr
             for (int pc = 0; pc < 16; ++pc) stage_piece(slot, kt, pc);
         };
 
-        f32x16_t o_acc[16];
-#pragma unroll
-        for (int d = 0; d < 16; ++d) o_acc[d] = zero16;
+        f5_acc_zero();
         float m_run = -1e30f, l_run = 0.f, alpha = 1.f;
         // fragment addresses inside a slot: K slot (2 ks + hh) ^ (row & 15) = (hh ^ (row & 15)) ^ 2 (ks & 7), plus 256 bytes per 8 k-steps
         const unsigned ka0 = l31 * 1024 + ((hh ^ (l31 & 15)) << 4);
@@ -557,17 +619,22 @@ __global__ __launch_bounds__(256) void flash_attn512_kernel(const h16_t* __restr
         for (int j = 0; j < 2; ++j) va[j] = 2 * F5_KBYTES + l31 * 64 + (((2 * j + hh) ^ ((l31 >> 2) & 3)) << 4);
 
         // Fragments are read F5_RD MFMAs ahead of their use (counted lgkmcnt waits: the DMA is the MUBUF form, common.h); the next tile's
-        // sixteen DMA pieces are issued between the MFMAs of the S^T phase, one per two MFMAs.
+        // sixteen DMA pieces are issued between the MFMAs of the S^T phase, one per two MFMAs.  The P.V phase's first F5_RD fragments are
+        // requested at the end of s_phase (vfr, rd_v), before the softmax arithmetic; the cold path keeps them across the rescale.
         // The accumulators (256 registers: the whole AGPR half of the file) must only ever be MFMA operands in the hot loop, so the
         // online-softmax rescale is (a) lazy -- the reference maximum m_run only moves when some query's tile maximum exceeds it by more
         // than 8 in log2 units; until then probabilities may reach 2^8, exact in the quotient sum(p v) / sum(p) and harmless in fp32 /
         // 16-bit P -- and (b) done outside the hot loop: the loop breaks before the tile's P.V, the cold path rescales and finishes the tile.
-        h16x8_t pf[2];
+        h16x8_t pf[2], vfr[F5_RD];
+        unsigned sb = 0;
+        auto rd_v = [&](int st) __attribute__((always_inline)) { vfr[st % F5_RD] = lds_frag(sb + va[st >> 4], (st & 15) * 2048); };
         // ---- S^T = K Q^T over d = 512: 32 k-steps alternating between two accumulators (a single chain would wait for its own result)
         auto s_phase = [&](unsigned sb, int kt, bool do_stage, int slot_next, auto maskc) __attribute__((always_inline)) -> bool {
             constexpr bool MASK = decltype(maskc)::value != 0;
             f32x16_t s0, s1;  // (first MFMA of each chain takes the inline constant 0 as C: no 32 register writes per tile)
             h16x8_t fr[F5_RD], ql[2];
+            k_rs = make_rsrc(Kb, do_stage ? k_bytes : 0u);
+            v_rs = make_rsrc(Vb, do_stage ? v_bytes : 0u);
             auto rd = [&](int ks) __attribute__((always_inline)) {
                 fr[ks % F5_RD] = lds_frag(sb + (ka0 ^ ((ks & 7) << 5)), (ks >> 3) * 256);
                 if ((ks & 3) == 3) ql[(ks >> 2) & 1] = lds_frag(q_lds, (ks >> 2) * 1024);
@@ -577,11 +644,16 @@ __global__ __launch_bounds__(256) void flash_attn512_kernel(const h16_t* __restr
 #pragma unroll
             for (int ks = 0; ks < 32; ++ks) {
                 const h16x8_t qv = (ks & 3) != 3 ? qf[3 * (ks >> 2) + ((ks & 3) != 3 ? (ks & 3) : 0)] : ql[(ks >> 2) & 1];
-                if (ks & 1) s1 = mfma_32x32x16(fr[ks % F5_RD], qv, ks == 1 ? zero16 : s1);
-                else s0 = mfma_32x32x16(fr[ks % F5_RD], qv, ks == 0 ? zero16 : s0);
+                if (ks < 2) f5_mfma_first(ks ? s1 : s0, fr[ks % F5_RD], qv);
+                else f5_mfma_acc((ks & 1) ? s1 : s0, fr[ks % F5_RD], qv);
                 if (ks + F5_RD < 32) rd(ks + F5_RD);
-                if (do_stage && (ks & 1)) stage_piece(slot_next, kt + 1, ks >> 1);   // the next tile's 16 DMA pieces, one per two MFMAs
+                if (ks & 1) stage_piece(slot_next, kt + 1, ks >> 1);   // the next tile's 16 DMA pieces, one per two MFMAs
             }
+            // the first F5_RD V^T fragments of the P.V phase (their slot was certified by this tile's barrier) travel under the softmax
+#pragma unroll
+            for (int st = 0; st < F5_RD; ++st) rd_v(st);
+            f5_mfma_settle(s0, s1);
+            __builtin_amdgcn_sched_barrier(0);
             f32x16_t s_acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) s_acc[r] = s0[r] + s1[r];
@@ -621,15 +693,12 @@ __global__ __launch_bounds__(256) void flash_attn512_kernel(const h16_t* __restr
             return moved;
         };
         // ---- O^T += V^T P^T: two k-steps of 16 keys x 16 channel blocks of 32 (step = 16 j + block)
-        auto pv_phase = [&](unsigned sb) __attribute__((always_inline)) {
-            h16x8_t fr[F5_RD];
-            auto rd = [&](int st) __attribute__((always_inline)) { fr[st % F5_RD] = lds_frag(sb + va[st >> 4], (st & 15) * 2048); };
-#pragma unroll
-            for (int st = 0; st < F5_RD; ++st) rd(st);
+        auto pv_phase = [&](unsigned) __attribute__((always_inline)) {   // (vfr[0 .. F5_RD-1] were requested by s_phase)
+            asm volatile("s_nop 1");                     // pf (VALU) -> B operand of an asm MFMA: the compiler does not pad that
 #pragma unroll
             for (int st = 0; st < 32; ++st) {
-                o_acc[st & 15] = mfma_32x32x16(fr[st % F5_RD], pf[st >> 4], o_acc[st & 15]);
-                if (st + F5_RD < 32) rd(st + F5_RD);
+                f5_acc_mfma(st & 15, vfr[st % F5_RD], pf[st >> 4]);
+                if (st + F5_RD < 32) rd_v(st + F5_RD);
             }
         };
 
@@ -638,7 +707,6 @@ __global__ __launch_bounds__(256) void flash_attn512_kernel(const h16_t* __restr
         int kt = t0;
         for (;;) {
             bool pending = false;
-            unsigned sb = 0;
             for (; kt < t1; ++kt) {                       // hot loop
                 const int rel = (kt - t0) & 1;
                 sb = smem_base + rel * F5_KBYTES;
@@ -650,42 +718,46 @@ __global__ __launch_bounds__(256) void flash_attn512_kernel(const h16_t* __restr
                 pv_phase(sb);
             }
             if (!pending) break;
-#pragma unroll
-            for (int d = 0; d < 16; ++d) {                // one 16-register block at a time through the VGPRs (no reordering across blocks:
-#pragma unroll                                            // all 256 at once would spill the Q fragments)
-                for (int r = 0; r < 16; ++r) o_acc[d][r] *= alpha;
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            f5_acc_scale(alpha);
             pv_phase(sb);
             ++kt;
             // a wait the COMPILER sees (its own bookkeeping ignores the asm waits): whatever this cold path reloaded from scratch is
             // complete here, so that the hot loop's first MFMA is not made to wait, with vmcnt(0), behind the DMA it has just issued
             __builtin_amdgcn_s_waitcnt(0x0070);
         }
+        wait_vm<0>();                                     // the last tile's empty DMA pieces: nothing is in flight into the LDS past this item
         l_run += other_half(l_run);
         const int q = q0 + l31;
+        f5_acc_settle();
+        int l31_o = l31, hh_o = hh;
+        asm volatile("" : "+v"(l31_o), "+v"(hh_o));     // opaque: the output addresses are computed here, not carried through the tile loop
         if (whole) {
             // ---- normalise and store O[q][d] (this lane: q = l31, d = 32 blk + 8 (r >> 2) + 4 hh + (r & 3))
             const float inv = 1.f / l_run;
             if (q < T) {
-                h16_t* ob = O + ((long long)b * T + q) * ldo;
+                h16_t* ob = O + ((long long)b * T + q0) * ldo + (unsigned)(l31_o * ldo);   // uniform 64-bit row base + a 32-bit lane offset
 #pragma unroll
-                for (int d = 0; d < 16; ++d)
+                for (int d = 0; d < 16; ++d) {
+                    float o[16];
+                    f5_acc_get(d, o);
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        const uint2 pk = pack_h16x4(o_acc[d][4 * g] * inv, o_acc[d][4 * g + 1] * inv, o_acc[d][4 * g + 2] * inv, o_acc[d][4 * g + 3] * inv);
-                        *(uint2*)(ob + d * 32 + 8 * g + 4 * hh) = pk;
+                        const uint2 pk = pack_h16x4(o[4 * g] * inv, o[4 * g + 1] * inv, o[4 * g + 2] * inv, o[4 * g + 3] * inv);
+                        *(uint2*)(ob + d * 32 + 8 * g + 4 * hh_o) = pk;
                     }
+                }
             }
         } else {
             // ---- one part of a left-over block: unnormalised accumulators + (maximum, sum) per query
             const long long slot = (long long)(sid / S) * S + part;
-            float* po = part_o + (slot * 128 + wave * 32 + l31) * 512;
+            float* po = part_o + (slot * 128 + wave * 32 + l31_o) * 512;
 #pragma unroll
-            for (int d = 0; d < 16; ++d)
+            for (int d = 0; d < 16; ++d) {
+                float o[16];
+                f5_acc_get(d, o);
 #pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    *(float4*)(po + d * 32 + 8 * g + 4 * hh) = float4{o_acc[d][4 * g], o_acc[d][4 * g + 1], o_acc[d][4 * g + 2], o_acc[d][4 * g + 3]};
+                for (int g = 0; g < 4; ++g) *(float4*)(po + d * 32 + 8 * g + 4 * hh_o) = float4{o[4 * g], o[4 * g + 1], o[4 * g + 2], o[4 * g + 3]};
+            }
             if (hh == 0) {
                 float* pm = part_ml + (slot * 128 + wave * 32 + l31) * 2;
                 pm[0] = m_run;
