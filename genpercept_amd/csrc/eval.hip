@@ -1,0 +1,289 @@
+// Depth evaluation on the device (gp_eval_depth): the per-image protocol of eval.py:168-215 -- least-squares alignment
+// (src/util/alignment.py:29-94), clip to the dataset range, the ten metrics of src/util/metric.py:34-158 -- for predictions that are
+// already on the GPU.  The host restatement is genpercept_amd/eval_metrics.py (evaluate_depth); this file reproduces what that code computes
+// for float32 `pred` / `gt`:
+//   fit      np.linalg.lstsq works in float64 and returns float32: here float64 sums n, Sp, Sg, Spp, Spg over the fit mask, the 2 x 2 normal
+//            equations in float64, (s, t) rounded to float32;
+//   apply    aligned = pred * s + t in float32, two roundings, no FMA; disparity space: gt_disp = 1 / gt (float32, 0 where gt <= 0), fit mask
+//            valid & gt > 0 & pred > 0, disp clipped at 1e-3, aligned = 1 / disp in float32;
+//   clip     to [min_depth, max_depth], then to >= 1e-6, in float32;
+//   metrics  float64 from here on: masked means over valid_mask, terms evaluated at masked pixels only (the host's np.where discards the
+//            inf / nan of the others);
+//   max_res  the fit samples columns only, ix = min(floor(dst * float32(1 / scale)), W - 1) for dst < fit_cols, every row
+//            (eval_metrics._nearest_downscale); the metrics run at full resolution.
+// Two memory-bound passes (9 bytes per pixel each) and two one-workgroup-per-image finalisers, stream-ordered, no host synchronisation, no
+// atomics: every workgroup leaves one slab of float64 partial sums in the workspace and the finaliser adds the slabs in index order.  The
+// number of workgroups per image and the pixel -> thread assignment depend on H * W alone -- never on B, on the image's position in the
+// batch or on pointer alignment (which only selects 16-byte or scalar loads of the same four pixels) -- so an image's result is bitwise the
+// same alone and inside any batch.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/genpercept_hip.h"
+
+// The host's numpy code has no fused multiply-adds, so nothing below may be contracted into one.  The float32 recipe is written as plain
+// `*`, `+`, `/` under this pragma: the __fmul_rn / __fadd_rn wrappers are plain operators compiled under the header's own (contracting)
+// setting and fuse after inlining; float and double division are correctly rounded by default.
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int EV_THREADS = 256;
+constexpr int EV_WAVES = EV_THREADS / 64;
+constexpr long long EV_PIX_PER_WG = 4096;  // at least this many pixels per workgroup ...
+constexpr int EV_MAX_WG = 512;             // ... and at most this many workgroups (= slabs) per image
+constexpr int EV_NFIT = 5;                 // n, Sp, Sg, Spp, Spg
+constexpr int EV_NMET = 11;                // n_valid, abs_rel, sq_rel, sq, dlog^2, |dlog10|, inv^2, dlog, delta1..3 counts
+constexpr int EV_OUT = 14;                 // s, t, n_valid, n_fit, ten metrics
+
+int eval_blocks(long long hw) {
+    long long g = (hw + EV_PIX_PER_WG - 1) / EV_PIX_PER_WG;
+    return (int)(g < 1 ? 1 : (g > EV_MAX_WG ? EV_MAX_WG : g));
+}
+
+// v[0..N) of every thread -> their sums over the workgroup, in slab[0..N).  Fixed order: a 64-lane shuffle tree inside each wave (the
+// shuffle moves the two halves of a double), then the waves in index order through LDS.
+template <int N>
+__device__ __forceinline__ void block_reduce_store(double (&v)[N], double* __restrict__ slab) {
+    __shared__ double s_part[EV_WAVES][N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) s_part[wave][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        double a = s_part[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < EV_WAVES; ++w) a += s_part[w][threadIdx.x];
+        slab[threadIdx.x] = a;
+    }
+}
+
+// the slabs of one image, summed in index order by thread k < N (loads batched 16 deep: they are independent, the additions are not)
+template <int N>
+__device__ __forceinline__ double sum_slabs(const double* __restrict__ ws, int nblk, int k) {
+    double a = 0.0;
+    int j = 0;
+    for (; j + 16 <= nblk; j += 16) {
+        double v[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v[u] = ws[(long long)(j + u) * N + k];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) a += v[u];
+    }
+    for (; j < nblk; ++j) a += ws[(long long)j * N + k];
+    return a;
+}
+
+struct Quad { float p[4], g[4]; unsigned m; };  // four consecutive pixels; m: one mask byte per pixel (0 beyond the image)
+
+// pixels 4q .. 4q + 3 of one image: one 16-byte load each of pred and gt and one 4-byte load of the mask when the image's three base
+// addresses allow it (vec) and the quad is whole, scalar loads otherwise.  Same values, same order either way.
+__device__ __forceinline__ Quad load_quad(const float* __restrict__ pred, const float* __restrict__ gt, const unsigned char* __restrict__ mask, long long q,
+                                          long long hw, bool vec) {
+    Quad r;
+    const long long i0 = q * 4;
+    if (vec && i0 + 4 <= hw) {
+        const float4 p = *reinterpret_cast<const float4*>(pred + i0);
+        const float4 g = *reinterpret_cast<const float4*>(gt + i0);
+        r.m = *reinterpret_cast<const unsigned*>(mask + i0);
+        r.p[0] = p.x, r.p[1] = p.y, r.p[2] = p.z, r.p[3] = p.w;
+        r.g[0] = g.x, r.g[1] = g.y, r.g[2] = g.z, r.g[3] = g.w;
+    } else {
+        r.m = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool in = i0 + j < hw;
+            r.p[j] = in ? pred[i0 + j] : 0.f;
+            r.g[j] = in ? gt[i0 + j] : 0.f;
+            r.m |= in ? (unsigned)mask[i0 + j] << (8 * j) : 0u;
+        }
+    }
+    return r;
+}
+
+struct FitAcc {
+    unsigned n = 0;
+    double sp = 0.0, sg = 0.0, spp = 0.0, spg = 0.0;
+    __device__ __forceinline__ void add(float pf, float gf, bool valid, bool disparity) {
+        if (!valid) return;
+        if (disparity) {  // depth2disparity(gt) and the fit mask of eval.py:181-200
+            if (!(gf > 0.f) || !(pf > 0.f)) return;
+            gf = 1.0f / gf;
+        }
+        const double p = (double)pf, g = (double)gf;
+        n += 1;
+        sp += p;
+        sg += g;
+        spp += p * p;
+        spg += p * g;
+    }
+};
+
+// pass 1: the five sums of the normal equations over the fit mask.  grid (eval_blocks(H * W), B).  fit_cols > 0: column-subsampled fit.
+__global__ __launch_bounds__(EV_THREADS) void eval_fit_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                              const unsigned char* __restrict__ mask, int H, int W, int disparity, int fit_cols,
+                                                              float fit_inv_scale, double* __restrict__ ws) {
+    const long long hw = (long long)H * W;
+    const long long base = (long long)blockIdx.y * hw;
+    pred += base, gt += base, mask += base;
+    FitAcc acc;
+    const long long tid = (long long)blockIdx.x * EV_THREADS + threadIdx.x, stride = (long long)gridDim.x * EV_THREADS;
+    if (fit_cols > 0) {
+        const long long n = (long long)H * fit_cols;
+        const double inv = (double)fit_inv_scale;
+        for (long long k = tid; k < n; k += stride) {
+            const long long row = k / fit_cols;
+            const int dst = (int)(k - row * fit_cols);
+            long long ix = (long long)floor((double)dst * inv);
+            ix = ix < 0 ? 0 : (ix > W - 1 ? W - 1 : ix);
+            const long long i = row * W + ix;
+            acc.add(pred[i], gt[i], mask[i] != 0, disparity != 0);
+        }
+    } else {
+        const bool vec = (((uintptr_t)pred | (uintptr_t)gt) & 15) == 0 && ((uintptr_t)mask & 3) == 0;
+        const long long nq = (hw + 3) / 4;
+        for (long long q = tid; q < nq; q += stride) {
+            const Quad v = load_quad(pred, gt, mask, q, hw, vec);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc.add(v.p[j], v.g[j], ((v.m >> (8 * j)) & 0xffu) != 0, disparity != 0);
+        }
+    }
+    double v[EV_NFIT] = {(double)acc.n, acc.sp, acc.sg, acc.spp, acc.spg};
+    block_reduce_store<EV_NFIT>(v, ws + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * EV_NFIT);
+}
+
+// after pass 1: slabs in index order, 2 x 2 normal equations in float64, (s, t) rounded to float32 into out[b][0..1] (where pass 2 reads
+// them), n_fit into out[b][3].  Fewer than two fit pixels or a singular system: s = t = NaN.  nblk = 0 (no alignment): s = 1, t = 0.
+__global__ __launch_bounds__(64) void eval_fit_finalise_kernel(const double* __restrict__ ws, int nblk, double* __restrict__ out) {
+    __shared__ double s_sum[EV_NFIT];
+    const int b = blockIdx.x;
+    if (nblk == 0) {
+        if (threadIdx.x == 0) out[(long long)b * EV_OUT] = 1.0, out[(long long)b * EV_OUT + 1] = 0.0, out[(long long)b * EV_OUT + 3] = 0.0;
+        return;
+    }
+    if (threadIdx.x < EV_NFIT) s_sum[threadIdx.x] = sum_slabs<EV_NFIT>(ws + (long long)b * nblk * EV_NFIT, nblk, threadIdx.x);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double n = s_sum[0], sp = s_sum[1], sg = s_sum[2], spp = s_sum[3], spg = s_sum[4];
+        const double det = n * spp - sp * sp;
+        float s = __builtin_nanf(""), t = __builtin_nanf("");
+        if (n >= 2.0 && det > 0.0) {
+            s = (float)((n * spg - sp * sg) / det);
+            t = (float)((spp * sg - sp * spg) / det);
+        }
+        out[(long long)b * EV_OUT] = (double)s;
+        out[(long long)b * EV_OUT + 1] = (double)t;
+        out[(long long)b * EV_OUT + 3] = n;
+    }
+}
+
+struct MetAcc {
+    unsigned n = 0, d1 = 0, d2 = 0, d3 = 0;
+    double abs_rel = 0.0, sq_rel = 0.0, sq = 0.0, dlog2 = 0.0, dlog10 = 0.0, inv2 = 0.0, dlog = 0.0;
+    // alignment.py:57-76 / eval.py:181-215 on one pixel in float32, then the terms of metric.py in float64
+    __device__ __forceinline__ void add(float pf, float gf, bool valid, int alignment, float s, float t, float lo, float hi) {
+        if (!valid) return;
+        float al = pf;
+        if (alignment != 0) {
+            const float scaled = pf * s;  // two roundings
+            al = scaled + t;
+            if (alignment == 2) al = 1.0f / fmaxf(al, 1e-3f);  // clip the disparity at 1e-3, disparity2depth
+        }
+        al = fmaxf(fminf(fmaxf(al, lo), hi), 1e-6f);
+        const double a = (double)al, g = (double)gf;
+        const double diff = a - g, ad = fabs(diff);
+        const double dl = log(a) - log(g);
+        const double ia = 1.0 / a - 1.0 / g;
+        const double r = fmax(a / g, g / a);
+        n += 1;
+        abs_rel += ad / g;
+        sq_rel += ad * ad / g;
+        sq += diff * diff;
+        dlog2 += dl * dl;
+        dlog10 += fabs(log10(a) - log10(g));
+        inv2 += ia * ia;
+        dlog += dl;
+        d1 += r < 1.25 ? 1u : 0u;
+        d2 += r < 1.25 * 1.25 ? 1u : 0u;
+        d3 += r < 1.25 * 1.25 * 1.25 ? 1u : 0u;
+    }
+};
+
+// pass 2: the metric sums over valid_mask with the (s, t) the fit finaliser left in out[b][0..1]
+__global__ __launch_bounds__(EV_THREADS) void eval_metric_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                                 const unsigned char* __restrict__ mask, int H, int W, int alignment, float lo, float hi,
+                                                                 const double* __restrict__ out, double* __restrict__ ws) {
+    const long long hw = (long long)H * W;
+    const long long base = (long long)blockIdx.y * hw;
+    pred += base, gt += base, mask += base;
+    const float s = (float)out[(long long)blockIdx.y * EV_OUT], t = (float)out[(long long)blockIdx.y * EV_OUT + 1];
+    MetAcc acc;
+    const bool vec = (((uintptr_t)pred | (uintptr_t)gt) & 15) == 0 && ((uintptr_t)mask & 3) == 0;
+    const long long nq = (hw + 3) / 4;
+    for (long long q = (long long)blockIdx.x * EV_THREADS + threadIdx.x; q < nq; q += (long long)gridDim.x * EV_THREADS) {
+        const Quad v = load_quad(pred, gt, mask, q, hw, vec);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc.add(v.p[j], v.g[j], ((v.m >> (8 * j)) & 0xffu) != 0, alignment, s, t, lo, hi);
+    }
+    double v[EV_NMET] = {(double)acc.n, acc.abs_rel, acc.sq_rel, acc.sq, acc.dlog2, acc.dlog10, acc.inv2, acc.dlog,
+                         (double)acc.d1, (double)acc.d2, (double)acc.d3};
+    block_reduce_store<EV_NMET>(v, ws + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * EV_NMET);
+}
+
+// after pass 2: slabs in index order, then the ten values with the host's formulas, in eval_metrics.METRICS order
+__global__ __launch_bounds__(64) void eval_metric_finalise_kernel(const double* __restrict__ ws, int nblk, double* __restrict__ out) {
+    __shared__ double s_sum[EV_NMET];
+    const int b = blockIdx.x;
+    if (threadIdx.x < EV_NMET) s_sum[threadIdx.x] = sum_slabs<EV_NMET>(ws + (long long)b * nblk * EV_NMET, nblk, threadIdx.x);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double* o = out + (long long)b * EV_OUT;
+        const double n = s_sum[0];
+        o[2] = n;
+        o[4] = s_sum[1] / n;                                         // abs_relative_difference
+        o[5] = s_sum[2] / n;                                         // squared_relative_difference
+        o[6] = sqrt(s_sum[3] / n);                                   // rmse_linear
+        o[7] = sqrt(s_sum[4] / n);                                   // rmse_log
+        o[8] = s_sum[5] / n;                                         // log10
+        o[9] = s_sum[8] / n;                                         // delta1_acc
+        o[10] = s_sum[9] / n;                                        // delta2_acc
+        o[11] = s_sum[10] / n;                                       // delta3_acc
+        o[12] = sqrt(s_sum[6] / n);                                  // i_rmse
+        o[13] = sqrt(s_sum[4] / n - s_sum[7] * s_sum[7] / (n * n)) * 100.0;  // silog_rmse: sqrt(first - second) * 100
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+long long gp_eval_depth_workspace(int B, int H, int W) {
+    if (B < 1 || H < 1 || W < 1) return 0;
+    return (long long)B * eval_blocks((long long)H * W) * EV_NMET * (long long)sizeof(double);
+}
+
+gp_status gp_eval_depth(const float* pred, const float* gt, const unsigned char* mask, int B, int H, int W, int alignment, int fit_cols,
+                        float fit_inv_scale, float min_depth, float max_depth, double* out, void* workspace, long long workspace_bytes, void* stream) {
+    if (!pred || !gt || !mask || !out || !workspace) return GP_ERR_INVALID;
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) return GP_ERR_INVALID;
+    if (alignment < 0 || alignment > 2 || fit_cols < 0 || fit_cols > W || (fit_cols > 0 && !(fit_inv_scale > 0.f))) return GP_ERR_INVALID;
+    if (workspace_bytes < gp_eval_depth_workspace(B, H, W) || ((uintptr_t)workspace & 7) != 0 || ((uintptr_t)out & 7) != 0) return GP_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    double* ws = (double*)workspace;
+    const int nblk = eval_blocks((long long)H * W);
+    if (alignment != 0)
+        hipLaunchKernelGGL(eval_fit_kernel, dim3(nblk, B), dim3(EV_THREADS), 0, s, pred, gt, mask, H, W, alignment == 2 ? 1 : 0, fit_cols, fit_inv_scale, ws);
+    hipLaunchKernelGGL(eval_fit_finalise_kernel, dim3(B), dim3(64), 0, s, (const double*)ws, alignment != 0 ? nblk : 0, out);
+    hipLaunchKernelGGL(eval_metric_kernel, dim3(nblk, B), dim3(EV_THREADS), 0, s, pred, gt, mask, H, W, alignment, min_depth, max_depth, (const double*)out, ws);
+    hipLaunchKernelGGL(eval_metric_finalise_kernel, dim3(B), dim3(64), 0, s, (const double*)ws, nblk, out);
+    return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
+}
+
+}  // extern "C"

@@ -145,6 +145,8 @@ SYMBOLS = {
     "gp_preprocess": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp]),
     "gp_preprocess_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "gp_postprocess": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "gp_eval_depth_workspace": (_ll, [_i, _i, _i]),
+    "gp_eval_depth": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _ll, _vp]),
     "gp_mfma_peak_tflops": (C.c_double, [_i, _vp]),
     "gp_mfma_peak_tflops_shape": (C.c_double, [_i, _i, _vp]),
     "gp_mfma_lds_probe": (C.c_double, [_i, _i, _i, _i, _vp]),
@@ -830,6 +832,66 @@ def postprocess(pred: torch.Tensor, size, resample: str = "bilinear", cmap: Opti
     if st != GP_OK:
         raise RuntimeError(f"gp_postprocess failed ({st})")
     return out, col, q
+
+
+EVAL_ALIGNMENT = {None: 0, "": 0, "none": 0, "least_square": 1, "least_square_disparity": 2}  # eval.py:168-200
+
+
+def _eval_maps(x: torch.Tensor, name: str) -> torch.Tensor:
+    if x.dim() == 4 and x.shape[1] == 1:
+        x = x[:, 0]
+    elif x.dim() == 2:
+        x = x[None]
+    if x.dim() != 3:
+        raise ValueError(f"{name}: expected [B, H, W] (or [B, 1, H, W], [H, W]), got {tuple(x.shape)}")
+    return x
+
+
+def eval_depth_raw(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, alignment: Optional[str] = "least_square",
+                   alignment_max_res: Optional[int] = None, min_depth: float = 1e-3, max_depth: float = 10.0) -> torch.Tensor:
+    """gp_eval_depth on device tensors: float64 [B, 14] ON THE DEVICE = s, t, n_valid, n_fit, then the ten metrics in eval_metrics.METRICS
+    order.  Enqueued on the current stream, no synchronisation; the error checks of `eval_depth` are the caller's."""
+    import numpy as np
+    if alignment not in EVAL_ALIGNMENT:
+        raise NotImplementedError(alignment)
+    lib = load_library()
+    pred, gt, mask = _eval_maps(pred, "pred"), _eval_maps(gt, "gt"), _eval_maps(mask, "mask")
+    assert pred.is_cuda and gt.is_cuda and mask.is_cuda
+    if not (pred.shape == gt.shape == mask.shape):
+        raise ValueError(f"pred {tuple(pred.shape)}, gt {tuple(gt.shape)} and mask {tuple(mask.shape)} must have one shape")
+    pred, gt = pred.to(torch.float32).contiguous(), gt.to(torch.float32).contiguous()
+    mask = (mask.contiguous().view(torch.uint8) if mask.dtype == torch.bool else (mask != 0).view(torch.uint8)).contiguous()
+    b, h, w = (int(v) for v in pred.shape)
+    fit_cols, fit_inv = 0, 0.0
+    if alignment_max_res is not None and EVAL_ALIGNMENT[alignment]:  # alignment.py:43-55 as eval_metrics.align_depth_least_square restates it
+        scale = float(np.min(alignment_max_res / np.array([h, w])))
+        if scale < 1:
+            fit_cols, fit_inv = int(np.floor(w * scale)), float(np.float32(1.0 / scale))
+            if fit_cols < 1:
+                raise ValueError(f"alignment_max_res = {alignment_max_res} leaves no column of a {h} x {w} image to fit on")
+    out = torch.empty((b, 14), dtype=torch.float64, device=pred.device)
+    nbytes = int(lib.gp_eval_depth_workspace(b, h, w))
+    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=pred.device)
+    st = lib.gp_eval_depth(pred.data_ptr(), gt.data_ptr(), mask.data_ptr(), b, h, w, EVAL_ALIGNMENT[alignment], fit_cols, fit_inv, float(min_depth),
+                           float(max_depth), out.data_ptr(), ws.data_ptr(), nbytes, _stream_ptr(pred.device))
+    if st != GP_OK:
+        raise RuntimeError(f"gp_eval_depth failed ({st})")
+    return out
+
+
+def eval_depth(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, alignment: Optional[str] = "least_square",
+               alignment_max_res: Optional[int] = None, min_depth: float = 1e-3, max_depth: float = 10.0):
+    """eval_metrics.evaluate_depth (eval.py:168-215) for a batch of maps that are on the device: pred, gt fp32 [B, H, W], mask bool / uint8.
+    Returns (one metric dict per image, (s, t, n_valid)) with s, t, n_valid as numpy arrays [B] (s = 1, t = 0 without alignment).  Raises
+    ValueError when an image has fewer than 2 fit pixels or a singular system.  One device -> host copy of B x 14 doubles."""
+    from .eval_metrics import METRICS
+    raw = eval_depth_raw(pred, gt, mask, alignment, alignment_max_res, min_depth, max_depth).cpu().numpy()
+    if EVAL_ALIGNMENT[alignment]:
+        for i, row in enumerate(raw):
+            if row[3] < 2 or not (row[0] == row[0] and row[1] == row[1]):
+                raise ValueError(f"image {i}: least-squares alignment needs at least 2 fit pixels and a non-singular system (n_fit = {int(row[3])})")
+    names = list(METRICS.keys())
+    return [{k: float(row[4 + j]) for j, k in enumerate(names)} for row in raw], (raw[:, 0].copy(), raw[:, 1].copy(), raw[:, 2].astype("int64"))
 
 
 def mfma_peak_tflops(device: int = 0, precision: Optional[str] = None) -> float:

@@ -130,21 +130,72 @@ def valid_mask_of(depth: np.ndarray, min_depth: float, max_depth: float, eval_cr
     return m
 
 
+def _shard(n_items: int, rank: int, world: int) -> Tuple[int, int]:
+    if not 0 <= rank < world:
+        raise ValueError(f"rank {rank} outside world size {world}")
+    from .distributed import shard_range
+    return shard_range(n_items, rank, world)
+
+
+def _decode_ahead(items: Sequence, load: Callable, prefetch: int):
+    """(item, load(item)) in order, the next `prefetch` images decoded by a helper thread meanwhile (prefetch <= 0: inline)."""
+    if prefetch <= 0 or len(items) < 2:
+        for s in items:
+            yield s, load(s)
+        return
+    from collections import deque
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=1) as loader:
+        pending, it = deque(), iter(items)
+        for s in it:
+            pending.append((s, loader.submit(load, s)))
+            if len(pending) > prefetch:
+                break
+        while pending:
+            s, fut = pending.popleft()
+            img = fut.result()
+            nxt = next(it, None)
+            if nxt is not None:
+                pending.append((nxt, loader.submit(load, nxt)))
+            yield s, img
+
+
+def _size_groups(loaded: Iterable, batch_size: int):
+    """Consecutive (item, image) pairs whose images have one size, at most batch_size per group; order is kept."""
+    group: list = []
+    for s, img in loaded:
+        if group and (len(group) >= batch_size or img.size != group[0][1].size):
+            yield group
+            group = []
+        group.append((s, img))
+    if group:
+        yield group
+
+
+def _load_rgb(base_dir: str, rgb_rel: str, rgb_crop: Optional[Callable[[np.ndarray], np.ndarray]]) -> Image.Image:
+    img = Image.open(os.path.join(base_dir, rgb_rel)).convert("RGB")
+    if rgb_crop is not None:  # KITTI: the benchmark crop is applied to the RGB as well (kitti_dataset.py:70-74)
+        img = Image.fromarray(np.ascontiguousarray(np.moveaxis(rgb_crop(np.moveaxis(np.asarray(img), -1, 0)), 0, -1)))
+    return img
+
+
 def run_inference(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_dir: str, name_mode: FileNameMode, mode: str = "depth",
                   denoise_steps: int = 1, ensemble_size: int = 1, processing_res: int = 0, match_input_res: bool = True,
                   resample_method: str = "bilinear", fix_timesteps=None, prompt: str = "", rgb_crop: Optional[Callable[[np.ndarray], np.ndarray]] = None,
-                  prefetch: int = 2) -> List[str]:
+                  prefetch: int = 2, batch_size: int = 1, rank: int = 0, world: int = 1) -> List[str]:
     """infer.py:408-447.  Returns the paths written.  rgb_crop: e.g. kitti_benchmark_crop (applied to the [3, H, W] image).
     prefetch > 0: the next `prefetch` images are decoded (and cropped) by a helper thread while the engine works on the current one, and the .npy
-    files are written by another -- the role the DataLoader workers play in the reference's loop; order and results are those of prefetch = 0."""
+    files are written by another -- the role the DataLoader workers play in the reference's loop; order and results are those of prefetch = 0.
+    batch_size > 1: consecutive samples of one image size go through `pipe.infer_batch` together, up to batch_size per call (same file names,
+    same order).  world > 1: this call handles `shard_range(len(samples), rank, world)` of the filtered list, one process per GPU."""
     written = []
     samples = [s for s in samples if len(s) < 2 or s[1] != "None"]  # kitti_dataset.py:47: entries without ground truth are skipped
+    if world > 1:
+        lo, hi = _shard(len(samples), rank, world)
+        samples = samples[lo:hi]
 
     def load(rgb_rel):
-        img = Image.open(os.path.join(base_dir, rgb_rel)).convert("RGB")
-        if rgb_crop is not None:  # KITTI: the benchmark crop is applied to the RGB as well (kitti_dataset.py:70-74)
-            img = Image.fromarray(np.ascontiguousarray(np.moveaxis(rgb_crop(np.moveaxis(np.asarray(img), -1, 0)), 0, -1)))
-        return img
+        return _load_rgb(base_dir, rgb_rel, rgb_crop)
 
     def save(rgb_rel, pred_np):
         scene_dir = os.path.join(output_dir, os.path.dirname(rgb_rel))
@@ -158,6 +209,15 @@ def run_inference(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_
                     batch_size=0, color_map=None, show_progress_bar=False, resample_method=resample_method, mode=mode,
                     fix_timesteps=fix_timesteps, prompt=prompt)
 
+    if batch_size > 1:
+        for group in _size_groups(_decode_ahead(samples, lambda s: load(s[0]), prefetch), batch_size):
+            outs = pipe.infer_batch([img for _, img in group], mode, processing_res=processing_res, match_input_res=match_input_res,
+                                    resample_method=resample_method, color_map=None, fix_timesteps=fix_timesteps, prompt=prompt,
+                                    denoising_steps=denoise_steps, ensemble_size=ensemble_size)
+            assert len(outs) == len(group)
+            for (smp, _), out in zip(group, outs):
+                written.append(save(smp[0], out.pred_np))
+        return written
     if prefetch <= 0 or len(samples) < 2:
         for s in samples:
             written.append(save(s[0], infer(load(s[0])).pred_np))
@@ -180,6 +240,22 @@ def run_inference(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_
             saves.append(writer.submit(save, rgb_rel, infer(img).pred_np))
         written = [f.result() for f in saves]
     return written
+
+
+def _write_eval_files(output_dir: str, alignment: Optional[str], names: List[str], per_sample, result: Dict[str, float], prediction_dir: str,
+                      dataset: str) -> None:
+    """eval.py:217-244: `per_sample_metrics-<alignment>.csv` and `eval_metrics-<alignment>.txt`."""
+    cfg = DATASETS[dataset]
+    os.makedirs(output_dir, exist_ok=True)
+    tag = f"-{alignment}" if alignment else ""
+    with open(os.path.join(output_dir, f"per_sample_metrics{tag}.csv"), "w") as f:
+        f.write("filename," + ",".join(names) + "\n")
+        for nm, vals in per_sample:
+            f.write(nm + "," + ",".join(str(v) for v in vals) + "\n")
+    with open(os.path.join(output_dir, f"eval_metrics{tag}.txt"), "w") as f:
+        f.write(f"Evaluation metrics:\n    of predictions: {prediction_dir}\n    on dataset: {dataset}\n")
+        f.write(f"min_depth = {cfg['min_depth']}\nmax_depth = {cfg['max_depth']}\n")
+        f.write("  ".join(names) + "\n" + "  ".join(f"{result[k]:.6g}" for k in names) + "\n")
 
 
 def evaluate_predictions(prediction_dir: str, base_dir: str, samples: Sequence[Sequence[str]], dataset: str = "nyu",
@@ -209,14 +285,80 @@ def evaluate_predictions(prediction_dir: str, base_dir: str, samples: Sequence[S
         n += 1
     result = {k: (sums[k] / n if n else float("nan")) for k in names}
     if output_dir is not None:
-        os.makedirs(output_dir, exist_ok=True)
-        tag = f"-{alignment}" if alignment else ""
-        with open(os.path.join(output_dir, f"per_sample_metrics{tag}.csv"), "w") as f:
-            f.write("filename," + ",".join(names) + "\n")
-            for nm, vals in per_sample:
-                f.write(nm + "," + ",".join(str(v) for v in vals) + "\n")
-        with open(os.path.join(output_dir, f"eval_metrics{tag}.txt"), "w") as f:
-            f.write(f"Evaluation metrics:\n    of predictions: {prediction_dir}\n    on dataset: {dataset}\n")
-            f.write(f"min_depth = {cfg['min_depth']}\nmax_depth = {cfg['max_depth']}\n")
-            f.write("  ".join(names) + "\n" + "  ".join(f"{result[k]:.6g}" for k in names) + "\n")
+        _write_eval_files(output_dir, alignment, names, per_sample, result, prediction_dir, dataset)
+    return result
+
+
+def infer_and_evaluate(pipe, base_dir: str, samples: Sequence[Sequence[str]], dataset: str, output_dir: Optional[str] = None, batch_size: int = 4,
+                       rank: int = 0, world: int = 1, alignment: Optional[str] = "least_square", alignment_max_res: Optional[int] = None,
+                       save_predictions: bool = False, evaluator: Optional[Callable] = None, mode: str = "depth", denoise_steps: int = 1,
+                       ensemble_size: int = 1, processing_res: int = 0, match_input_res: bool = True, resample_method: str = "bilinear",
+                       fix_timesteps=None, prompt: str = "", prefetch: int = 2, prediction_dir: Optional[str] = None) -> Dict[str, float]:
+    """infer.py:408-447 and eval.py:143-244 in one loop, without the `.npy` round trip: batches of equal-sized images (grouping and sharding as
+    in `run_inference`) go through `pipe.predict_batch_device`, the maps stay on the device, and `evaluator` -- `engine.eval_depth` unless
+    given: (pred, gt, mask, alignment, alignment_max_res, min_depth, max_depth) -> (one metric dict per image, ...) -- aligns and scores them
+    there.  Ground truth and validity mask are decoded on the host exactly as `evaluate_predictions` does (read_gt_depth, dataset_valid_mask;
+    KITTI: benchmark crop of RGB and depth) and uploaded per batch.  save_predictions: the maps are also written as `run_inference` would,
+    under prediction_dir (default: output_dir).  With torch.distributed initialised the per-image rows of all ranks are combined (float64
+    sums and a count by all_reduce, rows by all_gather_object); rank 0 writes `eval_metrics-<alignment>.txt` and
+    `per_sample_metrics-<alignment>.csv` with rows in sample order; every rank returns the means over all samples."""
+    import torch
+    cfg = DATASETS[dataset]
+    names = list(em.METRICS.keys())
+    if evaluator is None:
+        from .engine import eval_depth as evaluator
+    if prediction_dir is None:
+        prediction_dir = output_dir
+    if save_predictions and prediction_dir is None:
+        raise ValueError("save_predictions needs prediction_dir or output_dir")
+    rgb_crop = kitti_benchmark_crop if cfg.get("kitti_bm_crop") else None
+    samples = [s for s in samples if len(s) < 2 or s[1] != "None"]
+    lo, hi = _shard(len(samples), rank, world) if world > 1 else (0, len(samples))
+    items = [(i, samples[i]) for i in range(lo, hi)]  # the index in the filtered list rides along: the rows of all ranks are ordered by it
+    rows = []  # (sample index, prediction name, metric values)
+    for group in _size_groups(_decode_ahead(items, lambda it: _load_rgb(base_dir, it[1][0], rgb_crop), prefetch), batch_size):
+        pred = pipe.predict_batch_device([img for _, img in group], mode, processing_res=processing_res, match_input_res=match_input_res,
+                                         resample_method=resample_method, fix_timesteps=fix_timesteps, prompt=prompt,
+                                         denoising_steps=denoise_steps, ensemble_size=ensemble_size)
+        if pred.dim() != 4 or pred.shape[0] != len(group) or pred.shape[1] != 1:
+            raise ValueError(f"depth evaluation needs one-channel maps [B, 1, H, W], got {tuple(pred.shape)} for mode {mode!r}")
+        gts, vms = [], []
+        for (_, smp), _ in group:
+            gt = read_gt_depth(os.path.join(base_dir, smp[1]), dataset)
+            if tuple(gt.shape) != tuple(pred.shape[-2:]):
+                raise ValueError(f"{smp[0]}: prediction {tuple(pred.shape[-2:])} and ground truth {tuple(gt.shape)} differ in size")
+            gts.append(gt)
+            vms.append(dataset_valid_mask(gt, dataset, os.path.join(base_dir, smp[2]) if cfg.get("mask_from_file") and len(smp) > 2 else None))
+        gt_t = torch.from_numpy(np.stack(gts)).to(pred.device, non_blocking=True)
+        vm_t = torch.from_numpy(np.stack(vms)).to(pred.device, non_blocking=True)
+        metrics = evaluator(pred[:, 0], gt_t, vm_t, alignment, alignment_max_res, cfg["min_depth"], cfg["max_depth"])[0]
+        pred_host = pred[:, 0].cpu().numpy() if save_predictions else None
+        for j, ((idx, smp), _) in enumerate(group):
+            pred_name = os.path.join(os.path.dirname(smp[0]), get_pred_name(os.path.basename(smp[0]), cfg["name_mode"], suffix=".npy"))
+            if save_predictions:
+                os.makedirs(os.path.dirname(os.path.join(prediction_dir, pred_name)), exist_ok=True)
+                np.save(os.path.join(prediction_dir, pred_name), pred_host[j])
+            rows.append((idx, pred_name, [float(metrics[j][k]) for k in names]))
+
+    acc = np.zeros(len(names) + 1, dtype=np.float64)  # metric sums of this rank, then its image count
+    for _, _, vals in rows:
+        acc[:-1] += vals
+        acc[-1] += 1
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
+        t = torch.from_numpy(acc).to(dev)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        acc = t.cpu().numpy()
+        parts: list = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, rows)
+        rows = [r for part in parts for r in part]
+        writer = dist.get_rank() == 0
+    else:
+        writer = True
+    rows.sort(key=lambda r: r[0])
+    n = int(acc[-1])
+    result = {k: (float(acc[j]) / n if n else float("nan")) for j, k in enumerate(names)}
+    if output_dir is not None and writer:
+        _write_eval_files(output_dir, alignment, names, [(nm, vals) for _, nm, vals in rows], result, prediction_dir, dataset)
     return result

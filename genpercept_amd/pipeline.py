@@ -485,15 +485,12 @@ class GenPerceptPipeline:
             return self._run_device(rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts)
         return self._run_host(rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts)
 
-    def _run_device(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None) -> List[GenPerceptOutput]:
-        """Pre / post processing on the GPU (gp_preprocess / gp_postprocess): the image goes up once, resize_max_res, the model, the
-        resize back to the input size, clip, colour map and the 8-bit image all run on the device; pred_np and the coloured bytes come down.
-        uint8 images (PIL input) stay uint8 up to the engine's prologue; float tensors (genpercept_trainer.py:1151-1165) are resized in fp32
-        without rounding and normalised to [-1, 1] by gp_preprocess_f32, with the reference's range assertion (genpercept_pipeline.py:247)."""
+    def _predict_device(self, rgb, processing_res, match_input_res, resample, fix_timesteps, prompt, opts, color_map=None, q_bits=0):
+        """The device half of __call__ up to the finished map: upload, gp_preprocess, the model, gp_postprocess to the output size (the input
+        size with match_input_res), clip.  Returns (pred fp32 [B,C,H,W] in [0, 1], coloured uint8 [B,H,W,3] or None, quantised or None), all on
+        the device."""
         from . import engine as ge
         input_size = rgb.shape
-        if color_map is not None:
-            assert self.mode in ["depth", "disparity"]
         x = rgb.to(self._device, non_blocking=True)
         size_in = tuple(int(v) for v in input_size[-2:])
         size_p = ge.resize_max_res_size(size_in[0], size_in[1], int(processing_res)) if processing_res > 0 else size_in
@@ -506,7 +503,41 @@ class GenPerceptPipeline:
         self._warn_if_saturated()
         size = tuple(int(v) for v in input_size[-2:]) if match_input_res else tuple(pred.shape[-2:])
         one_ch = pred.shape[1] == 1
-        pred_out, col, q8 = ge.postprocess(pred, size, resample, cmap=color_map if one_ch else None, q_bits=0 if color_map is not None else 8)
+        return ge.postprocess(pred, size, resample, cmap=color_map if one_ch else None, q_bits=q_bits)
+
+    @torch.no_grad()
+    def predict_batch_device(self, images: Union[Sequence[Image.Image], torch.Tensor], mode: str, processing_res: Optional[int] = None,
+                             match_input_res: bool = True, resample_method: str = "bilinear", fix_timesteps=None, prompt="",
+                             denoising_steps: Optional[int] = None, ensemble_size: int = 1, generator=None) -> torch.Tensor:
+        """`infer_batch` without the trip to the host: images of one common size (PIL images, or a uint8 / fp32 [B,3,H,W] tensor) -> the
+        finished maps as an fp32 [B,C,H,W] tensor ON THE DEVICE, resized to the input size (match_input_res) and clipped to [0, 1] -- the values
+        `infer_batch(...)[i].pred_np` holds.  For consumers that stay on the GPU (engine.eval_depth, infer_eval.infer_and_evaluate)."""
+        from .engine import RESAMPLE_CODE
+        self.mode = mode
+        if processing_res is None:
+            processing_res = self.default_processing_resolution
+        if not torch.is_tensor(images):
+            images = torch.stack([torch.from_numpy(np.asarray(im.convert("RGB")).copy()).permute(2, 0, 1) for im in images])
+        assert images.dim() == 4 and images.shape[1] == 3
+        resample = get_resample_method(resample_method)
+        if images.dtype not in (torch.uint8, torch.float32) or resample not in RESAMPLE_CODE:
+            raise ValueError(f"predict_batch_device needs uint8 or fp32 images and a resample method of {sorted(RESAMPLE_CODE)}; "
+                             f"got {images.dtype}, {resample!r}")
+        steps = self.default_denoising_steps if denoising_steps is None else int(denoising_steps)
+        if self.genpercept_pipeline:
+            assert steps == 1 and ensemble_size == 1
+        opts = dict(steps=steps, ensemble_size=int(ensemble_size), batch_size=max(1, int(ensemble_size)), generator=generator, ensemble_kwargs=None)
+        return self._predict_device(images, processing_res, match_input_res, resample, fix_timesteps, prompt, opts)[0]
+
+    def _run_device(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None) -> List[GenPerceptOutput]:
+        """Pre / post processing on the GPU (gp_preprocess / gp_postprocess): the image goes up once, resize_max_res, the model, the
+        resize back to the input size, clip, colour map and the 8-bit image all run on the device; pred_np and the coloured bytes come down.
+        uint8 images (PIL input) stay uint8 up to the engine's prologue; float tensors (genpercept_trainer.py:1151-1165) are resized in fp32
+        without rounding and normalised to [-1, 1] by gp_preprocess_f32, with the reference's range assertion (genpercept_pipeline.py:247)."""
+        if color_map is not None:
+            assert self.mode in ["depth", "disparity"]
+        pred_out, col, q8 = self._predict_device(rgb, processing_res, match_input_res, resample, fix_timesteps, prompt, opts, color_map,
+                                                 0 if color_map is not None else 8)
         pred_np = pred_out.cpu().numpy()
         col_np = col.cpu().numpy() if col is not None else None
         q8_np = q8.cpu().numpy() if q8 is not None else None

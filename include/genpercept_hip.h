@@ -15,6 +15,7 @@
  *   gp_set_timestep   scheduler.set_timesteps / fix_timesteps       genpercept_pipeline.py:403-408
  *   gp_infer_steps    single_infer for archs marigold / rgb_blending: the denoising loop with the DDIM update
  *                                                                   genpercept_pipeline.py:413-422,447-465; ddim.py:144-217; run.py:361-368
+ *   gp_eval_depth     eval.py's per-image alignment + metrics               eval.py:168-215; src/util/alignment.py:29-94; src/util/metric.py:34-158
  * The per-kernel entry points (gp_conv2d ... gp_bilinear) exist for the parity tests; they are the same launchers the
  * engine uses.
  *
@@ -181,6 +182,23 @@ gp_status gp_preprocess_f32(const float* rgb, int B, int C, int H0, int W0, floa
  * q_out = (pred_out * 65535).astype(uint16) (q_bits 16) or (pred_out * 255).astype(uint8) (q_bits 8), [B][C][Ho][Wo]. */
 gp_status gp_postprocess(const float* pred, int B, int C, int h, int w, float* pred_out, int Ho, int Wo, int resample, float* tmp,
                          const unsigned char* lut_dev, void* colored_out, void* q_out, int q_bits, void* stream);
+
+/* ---- depth evaluation on the device (DEVICE pointers; stateless like the pre / post entries; csrc/eval.hip) ----------------------
+ * The per-image protocol of eval.py:168-215 for predictions that are already on the GPU: least-squares alignment in depth or disparity space
+ * (src/util/alignment.py:29-94), clip to [min_depth, max_depth] and to >= 1e-6, the ten metrics of src/util/metric.py:34-158.
+ * pred, gt: fp32 [B][H][W]; mask: uint8 [B][H][W] (non-zero = valid).  alignment: 0 none, 1 least squares on depth, 2 least squares on
+ * disparity (gt_disp = 1 / gt where gt > 0; fit over valid & gt > 0 & pred > 0; aligned = 1 / max(s pred + t, 1e-3)).  fit_cols > 0: the fit
+ * (not the metrics) reads columns min(floor(dst * fit_inv_scale), W - 1), dst < fit_cols, of every row -- alignment.py:43-55 with
+ * fit_cols = floor(W * scale), fit_inv_scale = float32(1 / scale); 0: the fit reads every pixel.
+ * out: double [B][14] = s, t, n_valid, n_fit, then abs_relative_difference, squared_relative_difference, rmse_linear, rmse_log, log10,
+ * delta1_acc, delta2_acc, delta3_acc, i_rmse, silog_rmse.  s and t are float32 values (what np.linalg.lstsq returns for float32 data);
+ * both are NaN when an image has fewer than two fit pixels or a singular system; alignment 0 gives s = 1, t = 0, n_fit = 0.
+ * Sums are float64, reduced in a fixed order that depends on H * W alone: an image's 14 values are bitwise the same from call to call and
+ * for every batch it is part of.  workspace: DEVICE scratch of at least the workspace entry's byte count (8-byte aligned), free again once
+ * the stream has passed the call.  Four kernel launches on `stream` (three for alignment 0), no host synchronisation. */
+long long gp_eval_depth_workspace(int B, int H, int W);   /* bytes; 0 for B, H or W < 1 */
+gp_status gp_eval_depth(const float* pred, const float* gt, const unsigned char* mask, int B, int H, int W, int alignment, int fit_cols,
+                        float fit_inv_scale, float min_depth, float max_depth, double* out, void* workspace, long long workspace_bytes, void* stream);
 
 /* Sustained TFLOP/s of back-to-back v_mfma_f32_32x32x16 (this library's element type) on every CU of `device`: the chip's own MFMA
  * peak under load, reported by bench.py beside the nominal 2.5 PFLOP/s.  < 0 on error. */

@@ -1,0 +1,139 @@
+"""Time the device depth evaluation against the host evaluation, and the batched device loop on the tiny pipeline.
+
+  python tools/eval_bench.py --out profiles/<name>.json
+
+1. `engine.eval_depth` (gp_eval_depth: two passes of 9 bytes per pixel + two finalisers) at 1 x 4032 x 6048 (ETH3D) and 4 x 480 x 640 (NYU),
+   least-squares alignment: device events around `iters` back-to-back calls after a warm-up, against `eval_metrics.evaluate_depth` on the same
+   arrays on the host (wall clock; one run at ETH3D size, it takes seconds).  Also what the host loop pays before it can evaluate: the copy of
+   the prediction to the host.  The two sides' values are compared on the spot (they must agree to 1e-9).
+2. `infer_eval.infer_and_evaluate` images/s at batch_size 1 and 4 on the tiny synthetic-weight pipeline, 16 images of 480 x 640 in a temporary
+   ScanNet-style tree (a measurement of the loop's overheads -- decode, upload, launch count --, not of the full-size model).
+Needs a GPU; there is no CPU fall-back."""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def case(b, h, w, seed):
+    rng = np.random.default_rng(seed)
+    yy, xx = np.meshgrid(np.linspace(0, 1, h, dtype=np.float32), np.linspace(0, 1, w, dtype=np.float32), indexing="ij")
+    pred = np.stack([np.clip(0.5 + 0.35 * np.sin(3.1 * xx + i) * np.cos(2.3 * yy) + 0.05 * rng.standard_normal((h, w), dtype=np.float32), 0, 1)
+                     for i in range(b)]).astype(np.float32)
+    gt = (9.0 * pred ** 1.3 + 0.8 + 0.05 * rng.standard_normal(pred.shape, dtype=np.float32)).astype(np.float32)
+    mask = (gt > 1e-3) & (gt < 10.0) & (rng.random(pred.shape, dtype=np.float32) < 0.8)
+    return pred, gt, mask
+
+
+def bench_eval(b, h, w, iters, host_runs):
+    from genpercept_amd import engine as ge
+    from genpercept_amd import eval_metrics as em
+    d = torch.device("cuda", 0)
+    pred, gt, mask = case(b, h, w, 1)
+    tp, tg, tm = (torch.from_numpy(x).to(d) for x in (pred, gt, mask))
+    for _ in range(3):
+        ge.eval_depth_raw(tp, tg, tm, "least_square", None, 1e-3, 10.0)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        ge.eval_depth_raw(tp, tg, tm, "least_square", None, 1e-3, 10.0)
+    e1.record()
+    torch.cuda.synchronize()
+    dev_ms = e0.elapsed_time(e1) / iters
+    t0 = time.perf_counter()
+    metrics, _ = ge.eval_depth(tp, tg, tm, "least_square", None, 1e-3, 10.0)  # with the 14-double copy and the host synchronise
+    call_ms = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    for _ in range(5):
+        back = tp.cpu()
+    copy_ms = (time.perf_counter() - t0) * 1e3 / 5
+    assert back.shape == tp.shape
+    host_ms = []
+    for _ in range(host_runs):
+        t0 = time.perf_counter()
+        with np.errstate(all="ignore"):
+            ref = [em.evaluate_depth(pred[i], gt[i], mask[i], 1e-3, 10.0, alignment="least_square") for i in range(b)]
+        host_ms.append((time.perf_counter() - t0) * 1e3)
+    worst = max(abs(metrics[i][k] - ref[i][k]) / abs(ref[i][k]) for i in range(b) for k in ref[i])
+    assert worst <= 1e-9, worst
+    nbytes = 2 * 9 * b * h * w
+    return dict(shape=[b, h, w], device_ms_per_call=dev_ms, device_iters=iters, device_gb_per_s=nbytes / dev_ms / 1e6, bytes_per_call=nbytes,
+                device_call_with_sync_ms=call_ms, prediction_copy_to_host_ms=copy_ms, host_evaluate_depth_ms=min(host_ms), host_runs=host_runs,
+                host_over_device=min(host_ms) / dev_ms, worst_rel_device_vs_host=worst)
+
+
+def bench_loop(n_images, batch_sizes, repeats):
+    from PIL import Image
+    from genpercept_amd import GenPerceptPipeline
+    from genpercept_amd import infer_eval as ie
+    from oracle import sd21 as osd
+    uc, vc = osd.UNetCfg.tiny(), osd.VAECfg.tiny()
+    g = torch.Generator().manual_seed(0)
+    pipe = GenPerceptPipeline(unet=osd.synth_state_dict(osd.unet_manifest(uc), 1), vae=osd.synth_state_dict(osd.vae_manifest(vc), 2),
+                              scheduler=dict(beta_start=1.0, beta_end=1.0, prediction_type="v_prediction", clip_sample=False, steps_offset=1,
+                                             timestep_spacing="leading"),
+                              text_encoder=torch.randn(2, uc.cross_attention_dim, generator=g), tokenizer=None)
+    pipe.to("cuda")
+    out = {}
+    with tempfile.TemporaryDirectory() as base:
+        rng = np.random.RandomState(0)
+        samples = []
+        os.makedirs(os.path.join(base, "s", "color"))
+        os.makedirs(os.path.join(base, "s", "depth"))
+        for i in range(n_images):
+            Image.fromarray(rng.randint(0, 255, (480, 640, 3), dtype=np.uint8)).save(os.path.join(base, "s", "color", f"{i:06d}.png"))
+            Image.fromarray((1000 * (0.8 + 8 * rng.rand(480, 640))).astype(np.uint16)).save(os.path.join(base, "s", "depth", f"{i:06d}.png"))
+            samples.append([f"s/color/{i:06d}.png", f"s/depth/{i:06d}.png"])
+        means = {}
+        for bs in batch_sizes:
+            ie.infer_and_evaluate(pipe, base, samples[:bs], "scannet", batch_size=bs, processing_res=0)  # warm-up of this batch shape
+            best = float("inf")
+            for _ in range(repeats):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                means[bs] = ie.infer_and_evaluate(pipe, base, samples, "scannet", batch_size=bs, processing_res=0)
+                torch.cuda.synchronize()
+                best = min(best, time.perf_counter() - t0)
+            out[f"batch_size_{bs}_images_per_s"] = n_images / best
+        # the host loop it replaces: run_inference (.npy per image) + evaluate_predictions
+        with tempfile.TemporaryDirectory() as pred_dir:
+            ie.run_inference(pipe, base, samples[:1], pred_dir, ie.FileNameMode.id, processing_res=0)
+            t0 = time.perf_counter()
+            ie.run_inference(pipe, base, samples, pred_dir, ie.FileNameMode.id, processing_res=0)
+            ie.evaluate_predictions(pred_dir, base, samples, dataset="scannet")
+            out["host_loop_run_inference_plus_evaluate_predictions_images_per_s"] = n_images / (time.perf_counter() - t0)
+    out.update(n_images=n_images, image_size=[480, 640], pipeline="tiny synthetic weights, bf16, VAE-decoder head", repeats=repeats)
+    pipe._engine.close()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--skip-loop", action="store_true")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("eval_bench needs a GPU")
+    res = dict(device=torch.cuda.get_device_name(0), eval_depth=[bench_eval(1, 4032, 6048, a.iters, 1), bench_eval(4, 480, 640, a.iters, 3)])
+    if not a.skip_loop:
+        res["infer_and_evaluate"] = bench_loop(16, (1, 4), 3)
+    text = json.dumps(res, indent=1)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
