@@ -8,6 +8,7 @@
 //   already in B-operand order for O^T += V^T P^T -- no LDS round trip, no permutes.  The K rows are staged with bits 2 and 3 of
 //   their index swapped, which makes the 8 keys of a lane's k-step consecutive: the V^T A-operand is then one 16-byte read of the
 //   tile the projection GEMM produced transposed ([C][Tpad], zero-padded beyond T).
+// flash_attn64_split / flash_attn512_split: the same two over split operands (contract precision), see their own headers below.
 // cross_attn_small: cross-attention against the constant, tiny text context (L = 2 for GenPercept's empty prompt).
 // softmax_rows: row softmax for the GEMM-based single-head VAE attention (head_dim 512).
 #include <cstdlib>
@@ -427,6 +428,228 @@ void launch_flash_attn64_split(const h16_t* qk_hi, const h16_t* qk_lo, const h16
     hipLaunchKernelGGL(flash_attn64_split_kernel, grid, dim3(256), 2 * 32768, s, qk_hi, qk_lo, vt_hi, vt_lo, out, T, heads, ld, Tpad);
 }
 
+// ---- flash_attn512 with SPLIT operands (contract precision): the VAE mid-block attention (one head, head_dim 512) without logits in HBM.
+// The arithmetic of the unfused chain (engine.hip: attention_c), in another summation order:
+//   S = scale (q_hi k_hi + q_lo k_hi + q_hi k_lo) in fp32,  online fp32 softmax,  p = p_hi + p_lo split in registers,
+//   O += p_hi v_hi + p_lo v_hi + p_hi v_lo,  O / l at the end.
+// Doubling flash_attn512_kernel's operands does not fit (Q hi + lo of 32 queries alone are 256 registers), so the head dimension is cut
+// over the waves instead:
+//   * a 512-thread workgroup owns 64 queries; wave (qh, dq) = (wave >> 2, wave & 3) handles the 32 queries of half qh and the 128-wide d
+//     slice dq: Q hi / lo of the slice in 64 registers, the O^T slice (128 x 32 fp32) in 64 accumulators;
+//   * per 32-key tile a wave's 24 MFMAs (8 k-steps x 3 products, two chains) give the slice's PARTIAL S^T; the four partials of a query
+//     half meet in LDS (4 KiB per wave, lane-major) and every wave adds them in the same order (p0 + p1) + (p2 + p3): the four waves of a
+//     half hold bit-identical scores, so their lane-local softmax state (flash_attn64_split_kernel's) stays identical without any exchange;
+//   * then 24 P.V MFMAs on the slice (2 k-steps x 4 channel blocks x 3 products);
+//   * LDS: K hi | K lo tile [32 keys][512 d] and V^T hi | V^T lo tile [512 d][32 keys] (flash_attn512_kernel's row order pi23 and swizzles)
+//     of 32 KiB each + 32 KiB of partials = 160 KiB, one workgroup per CU, two waves per SIMD.  K and V^T alternate: the V^T tile travels
+//     (LDS-DMA) under the S^T MFMAs, the next K tile under the softmax and the P.V MFMAs; two barriers per tile;
+//   * one pass, one workgroup per (image, 64-query block): no workspace, no key split, no combine -- bitwise reproducible, and an image's
+//     result does not depend on the batch it is in.  K and V are re-read T / 64 times per image from L2 / MALL (xcd_remap keeps the
+//     workgroups of an XCD on neighbouring query blocks of one image, which walk the keys together).
+// Inputs: the planes launch_c_qkv_planes(heads = 1, hd = 512) writes -- QKhi / QKlo [B*T][1024] (q | k), Vthi / Vtlo [B][512][Tpad], Tpad =
+// round_up(T, 64), zero beyond T.  K rows past T - 1 repeat the last one and are masked by index.  Output: A-order split operand [B*T][1536].
+GP_DEV int pi23(int i) { return (i & ~12) | ((i & 4) << 1) | ((i & 8) >> 1); }  // swap bits 2 and 3
+constexpr int F5S_PLANE = 32 * 1024;                     // one plane (hi or lo) of a K tile or of a V^T tile
+constexpr int F5S_LDS = 4 * F5S_PLANE + 8 * 4096;        // K hi | K lo | V^T hi | V^T lo | eight S^T partials
+static_assert(F5S_LDS <= 160 * 1024, "flash_attn512_split: more LDS than a gfx950 CU has");
+__global__ __launch_bounds__(512) void flash_attn512_split_kernel(const h16_t* __restrict__ QKhi, const h16_t* __restrict__ QKlo,
+                                                                   const h16_t* __restrict__ Vthi, const h16_t* __restrict__ Vtlo,
+                                                                   h16_t* __restrict__ O, int T, int Tpad, float scale) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int qh = wave >> 2, dq = wave & 3;
+    const int l31 = lane & 31, hh = lane >> 5;
+    const int nqb = (T + 63) >> 6;
+    const int sid = xcd_remap(blockIdx.x, gridDim.x);
+    const int qb = sid % nqb, b = sid / nqb;
+    const int q = qb * 64 + qh * 32 + l31;
+    const long long row0 = (long long)b * T;
+    const unsigned smem_base = (unsigned)(unsigned long long)smem;  // integer-addressed LDS accesses (common.h)
+
+    // Q fragments of the slice (B operand of S^T = K Q^T): lane (q = l31, half hh) holds Q[q][128 dq + 16 ks + 8 hh .. +7]
+    h16x8_t qfh[8], qfl[8];
+    {
+        const bool ok = q < T;
+        const long long qo = (row0 + min(q, T - 1)) * 1024 + dq * 128 + hh * 8;   // rows past T: a valid address, the values are replaced by zeros
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+            qfh[ks] = *(const h16x8_t*)(QKhi + qo + ks * 16);
+            qfl[ks] = *(const h16x8_t*)(QKlo + qo + ks * 16);
+            if (!ok) qfh[ks] = qfl[ks] = h16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
+        }
+    }
+    // DMA sources: K rows of this image (columns 512 .. 1023 of the q | k planes) and its 512 V^T rows
+    const unsigned k_bytes = (unsigned)(((long long)T - 1) * 2048 + 1024), v_bytes = (unsigned)(1024ll * Tpad);
+    const buf_rsrc_t kh_rs = make_rsrc(QKhi + row0 * 1024 + 512, k_bytes), kl_rs = make_rsrc(QKlo + row0 * 1024 + 512, k_bytes);
+    const buf_rsrc_t vh_rs = make_rsrc(Vthi + (long long)b * 512 * Tpad, v_bytes), vl_rs = make_rsrc(Vtlo + (long long)b * 512 * Tpad, v_bytes);
+    // K: this wave stages LDS rows 4 wave .. 4 wave + 3 of both planes, one 1 KiB row per instruction; LDS row i <- key pi23(i) of the tile,
+    // physical slot `lane` of row i holds logical slot lane ^ (i & 15)
+    unsigned koff[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) koff[n] = (unsigned)(lane ^ ((4 * wave + n) & 15)) << 4;
+    auto stage_k = [&](int kt) __attribute__((always_inline)) {
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            const int i = 4 * wave + n;
+            const int key = min(kt * 32 + pi23(i), T - 1);   // rows past T repeat the last one: their scores are masked by index
+            const unsigned uo = (unsigned)key * 2048u;
+            blds16(kh_rs, koff[n], uo, smem + i * 1024);
+            blds16(kl_rs, koff[n], uo, smem + F5S_PLANE + i * 1024);
+        }
+    };
+    // V^T: this wave stages channels 64 wave .. 64 wave + 63 of both planes, 16 rows of 64 bytes per instruction (row 16 m + lane / 4,
+    // physical slot lane & 3 holds logical slot (lane & 3) ^ ((row >> 2) & 3)); kt * 32 + 32 <= Tpad always
+    const unsigned v_lane_off = ((unsigned)(lane >> 2) * Tpad + (((lane & 3) ^ ((lane >> 4) & 3)) << 3)) * 2;
+    auto stage_v = [&](int kt) __attribute__((always_inline)) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const unsigned uo = ((unsigned)(64 * wave + 16 * m) * (unsigned)Tpad + (unsigned)kt * 32u) * 2u;
+            blds16(vh_rs, v_lane_off, uo, smem + 2 * F5S_PLANE + (wave * 4 + m) * 1024);
+            blds16(vl_rs, v_lane_off, uo, smem + 3 * F5S_PLANE + (wave * 4 + m) * 1024);
+        }
+    };
+    // fragment addresses: K row l31, slot (2 (8 dq + ks) + hh) ^ (row & 15) = ((hh ^ (row & 15)) ^ 2 ks) + 16 dq;
+    // V^T row 128 dq + 32 blk + l31, slot (2 j + hh) ^ ((row >> 2) & 3)
+    const unsigned ka0 = smem_base + l31 * 1024 + dq * 256 + ((hh ^ (l31 & 15)) << 4);
+    unsigned va[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) va[j] = smem_base + 2 * F5S_PLANE + (dq * 128 + l31) * 64 + (((2 * j + hh) ^ ((l31 >> 2) & 3)) << 4);
+    const unsigned sp_w = smem_base + 4 * F5S_PLANE + wave * 4096 + lane * 16;       // this wave's partial
+    const unsigned sp_r = smem_base + 4 * F5S_PLANE + qh * 4 * 4096 + lane * 16;     // the four partials of this query half
+
+    f32x16_t o_acc[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o_acc[d][r] = 0.f;
+    f32x16_t zero16;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
+    float m_run = -1e30f, l_run = 0.f;
+    const float sc = scale * 1.44269504088896340736f;
+    const int nt = (T + 31) >> 5;
+
+    stage_k(0);
+    for (int kt = 0; kt < nt; ++kt) {
+        // the K tile has landed everywhere; everybody is done with the previous tile's V^T fragments and partials
+        wait_vm<0>();
+        __syncthreads();
+        stage_v(kt);
+        // ---- partial S^T = K Q^T over this wave's 128 channels: two chains of 12 MFMAs
+        f32x16_t s0 = zero16, s1 = zero16;
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+            const h16x8_t kfh = lds_frag(ka0 ^ (unsigned)(ks << 5), 0);
+            const h16x8_t kfl = lds_frag(ka0 ^ (unsigned)(ks << 5), F5S_PLANE);
+            f32x16_t& s = (ks & 1) ? s1 : s0;
+            s = mfma_32x32x16(kfl, qfh[ks], s);   // small terms first
+            s = mfma_32x32x16(kfh, qfl[ks], s);
+            s = mfma_32x32x16(kfh, qfh[ks], s);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            *(lds_f4_ptr)(sp_w + g * 1024) = f32x4_t{s0[4 * g] + s1[4 * g], s0[4 * g + 1] + s1[4 * g + 1], s0[4 * g + 2] + s1[4 * g + 2], s0[4 * g + 3] + s1[4 * g + 3]};
+        // the V^T tile and the partials are there; everybody is done with the K tile, which the next one overwrites
+        wait_vm<0>();
+        __syncthreads();
+        if (kt + 1 < nt) stage_k(kt + 1);
+        // ---- S^T: the four partials in one fixed order (the same bits in the four waves of a query half)
+        float sv[16];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4_t p0 = *(lds_f4_ptr)(sp_r + g * 1024), p1 = *(lds_f4_ptr)(sp_r + 4096 + g * 1024);
+            const f32x4_t p2 = *(lds_f4_ptr)(sp_r + 8192 + g * 1024), p3 = *(lds_f4_ptr)(sp_r + 12288 + g * 1024);
+            const f32x4_t t = (p0 + p1) + (p2 + p3);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sv[4 * g + e] = t[e];
+        }
+        // register r <-> LDS row (r & 3) + 4 hh + 8 (r >> 2) <-> key 32 kt + 8 hh + (r & 7) + 16 (r >> 3)
+        if (kt * 32 + 32 > T) {   // (uniform; the last tile only)
+            const int kbase = kt * 32 + 8 * hh;
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if (kbase + (r & 7) + 16 * (r >> 3) >= T) sv[r] = -1e30f;
+        }
+        // ---- online softmax, lane-local: this lane's 16 keys + the other half-wave's 16 of the same query
+        float mx = sv[0];
+#pragma unroll
+        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sv[r]);
+        mx = xor32_max(mx);
+        if (__builtin_amdgcn_ballot_w64(mx > m_run) != 0ull) {   // (uniform)
+            const float m_new = fmaxf(m_run, mx);
+            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * sc);
+            m_run = m_new;
+            l_run *= alpha;
+#pragma unroll
+            for (int d = 0; d < 4; ++d)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) o_acc[d][r] *= alpha;
+        }
+        const float nm = -m_run * sc;
+        float rs = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            sv[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(sv[r], sc, nm));
+            rs += sv[r];
+        }
+        l_run += rs;
+        // ---- O^T += V^T P^T on this wave's four channel blocks: k-steps j of 16 keys; this lane's P for its own query is the B operand
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            union { h16x8_t v; unsigned u[4]; } ph, pl;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float a = sv[8 * j + 2 * e], c = sv[8 * j + 2 * e + 1];
+                ph.u[e] = pack_h16x2_ns(a, c);
+                pl.u[e] = pack_h16x2_ns(a - h16_lo(ph.u[e]), c - h16_hi(ph.u[e]));
+            }
+            h16x8_t vfh[4], vfl[4];
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                vfh[d] = lds_frag(va[j], d * 2048);
+                vfl[d] = lds_frag(va[j], F5S_PLANE + d * 2048);
+            }
+#pragma unroll
+            for (int d = 0; d < 4; ++d) o_acc[d] = mfma_32x32x16(vfl[d], ph.v, o_acc[d]);
+#pragma unroll
+            for (int d = 0; d < 4; ++d) o_acc[d] = mfma_32x32x16(vfh[d], pl.v, o_acc[d]);
+#pragma unroll
+            for (int d = 0; d < 4; ++d) o_acc[d] = mfma_32x32x16(vfh[d], ph.v, o_acc[d]);
+        }
+    }
+    // ---- normalise and store (this lane: query q, channels 128 dq + 32 blk + 8 g + 4 hh + 0..3) as [hi | lo | hi] blocks of 512
+    l_run += __shfl_xor(l_run, 32);
+    const float inv = 1.f / l_run;
+    if (q < T) {
+        h16_t* ob = O + (row0 + q) * 1536 + dq * 128 + 4 * hh;
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float v0 = o_acc[d][4 * g] * inv, v1 = o_acc[d][4 * g + 1] * inv, v2 = o_acc[d][4 * g + 2] * inv, v3 = o_acc[d][4 * g + 3] * inv;
+                const unsigned h0 = pack_h16x2(v0, v1), h1 = pack_h16x2(v2, v3);
+                const unsigned l0 = pack_h16x2(v0 - h16_lo(h0), v1 - h16_hi(h0)), l1 = pack_h16x2(v2 - h16_lo(h1), v3 - h16_hi(h1));
+                const int c = d * 32 + 8 * g;
+                *(uint2*)(ob + c) = make_uint2(h0, h1);
+                *(uint2*)(ob + 512 + c) = make_uint2(l0, l1);
+                *(uint2*)(ob + 1024 + c) = make_uint2(h0, h1);
+            }
+    }
+}
+// T and Tpad are bounded by the 32-bit byte ranges of the per-image buffer resources (K rows: 2 KiB per token)
+bool flash_attn512_split_supported(int T) { return T >= 1 && T < (1 << 21); }
+void launch_flash_attn512_split(const h16_t* qk_hi, const h16_t* qk_lo, const h16_t* vt_hi, const h16_t* vt_lo, h16_t* out, int B, int T, int Tpad, float scale,
+                                hipStream_t s) {
+    static unsigned long long attr_mask = 0;
+    gp_once_per_device(&attr_mask, [&] {
+        (void)hipFuncSetAttribute((const void*)flash_attn512_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, F5S_LDS);
+    });
+    dim3 grid((unsigned)(((T + 63) / 64) * B));
+    hipLaunchKernelGGL(flash_attn512_split_kernel, grid, dim3(512), F5S_LDS, s, qk_hi, qk_lo, vt_hi, vt_lo, out, T, Tpad, scale);
+}
+
+
 // ---- flash_attn512: the VAE mid-block attention (one head, head_dim 512; genpercept_pipeline.py:500-501,521-522) ----------------------
 // Same dataflow as flash_attn64 (S^T = K Q^T on v_mfma_f32_32x32x16, lane-local online softmax, the probabilities already in
 // B-operand order for O^T += V^T P^T), sized for d = 512:
@@ -519,7 +742,6 @@ GP_DEV void f5_acc_get(int d, float* t) {
 #undef F5_RDL
 GP_DEV int k512_off(int row, int slot) { return row * 1024 + ((slot ^ (row & 15)) << 4); }
 GP_DEV int v512_off(int row, int slot) { return row * 64 + ((slot ^ ((row >> 2) & 3)) << 4); }
-GP_DEV int pi23(int i) { return (i & ~12) | ((i & 4) << 1) | ((i & 8) >> 1); }  // swap bits 2 and 3
 
 __global__ __launch_bounds__(256) void flash_attn512_kernel(const h16_t* __restrict__ Q, const h16_t* __restrict__ K,
                                                              const h16_t* __restrict__ Vt, h16_t* __restrict__ O,

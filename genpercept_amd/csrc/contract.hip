@@ -434,6 +434,20 @@ __global__ __launch_bounds__(256) void c_softmax_split_long_kernel(const float* 
     }
 }
 bool c_softmax_split_supported(int ld) { return (ld & 3) == 0; }
+// the attention core's way and its transient bytes (kernels.h); the plane sizes are the ones launch_c_qkv_planes writes
+int c_attention_plan(int B, int T, int heads, int hd, long long* workspace_bytes) {
+    const GpSwitches& sw = gp_sw();
+    const long long Tpad = ((long long)T + 63) / 64 * 64, Z = (long long)B * heads, C = (long long)heads * hd;
+    const long long unfused = 10 * Z * T * Tpad;                        // fp32 logits + split probabilities, both live across the softmax
+    const long long planes = 8 * (long long)B * T * C + 4 * Z * hd * Tpad;  // q | k hi + lo [B*T][2C], V^T hi + lo [Z][hd][Tpad]: 16-bit
+    int path = C_ATTN_UNFUSED;
+    if (hd == 64 && !sw.c_no_flash && (long long)T * 3 * C * 2 < 0x7fffffffll) path = C_ATTN_FLASH64;
+    else if (hd == 512 && heads == 1 && !GP_F16 && flash_attn512_split_supported(T) &&
+             (sw.c_flash512 > 0 || (sw.c_flash512 < 0 && unfused > C_FLASH512_ABOVE_BYTES)))
+        path = C_ATTN_FLASH512;
+    if (workspace_bytes) *workspace_bytes = path == C_ATTN_UNFUSED ? unfused : planes;
+    return path;
+}
 void launch_c_softmax_split(const float* in, h16_t* out, long long rows, int T, int ld, float scale, hipStream_t s) {
     if (ld <= 256 * 4 * CS_MAXV) hipLaunchKernelGGL(c_softmax_split_kernel, dim3((unsigned)rows), dim3(256), 0, s, in, out, T, ld, scale);
     else hipLaunchKernelGGL(c_softmax_split_long_kernel, dim3((unsigned)rows), dim3(256), 0, s, in, out, T, ld, scale);

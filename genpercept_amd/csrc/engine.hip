@@ -895,12 +895,32 @@ struct gp_engine {
     }
 
     // contract precision: softmax(scale q k^T) v per head with fp32 logits in HBM (head split -> batched logits GEMM -> row softmax -> batched
-    // P.V GEMM -> head merge; every product over split operands).  qkv: stored [B*T][3C] with q | k | v at columns 0 | C | 2C; returns the
-    // A-order operand [B*T][3C] the output projection reads.
+    // P.V GEMM -> head merge; every product over split operands), or fused where c_attention_plan (kernels.h) says so: flash_attn64_split for
+    // head_dim 64, flash_attn512_split for the VAE's one head of 512 above 8 GiB of logits + probabilities or by GENPERCEPT_C_FLASH512.
+    // qkv: stored [B*T][3C] with q | k | v at columns 0 | C | 2C; returns the A-order operand [B*T][3C] the output projection reads.
     Act attention_c(const Act& qkv, int heads, int hd, float scale) {
         const int B = qkv.B, T = qkv.H * qkv.W, Tpad = round_up(T, 64), Z = B * heads;
         if (hd % 64 || qkv.C != 3 * heads * hd) throw std::logic_error("attention_c: layout");
-        if (hd == 64 && !gp_sw().c_no_flash && (long long)T * qkv.C * 2 < 0x7fffffffll) {  // flash attention over split operands (attention.hip)
+        const int path = c_attention_plan(B, T, heads, hd, nullptr);
+        if (path == C_ATTN_FLASH512) {  // one head of 512 (the VAE), fused: no logits in HBM, 6 KiB of planes per token (attention.hip)
+            h16_t* qk_hi = (h16_t*)pool.alloc((size_t)B * T * 2 * hd * sizeof(h16_t));
+            h16_t* qk_lo = (h16_t*)pool.alloc((size_t)B * T * 2 * hd * sizeof(h16_t));
+            h16_t* vt_hi = (h16_t*)pool.alloc((size_t)B * hd * Tpad * sizeof(h16_t));
+            h16_t* vt_lo = (h16_t*)pool.alloc((size_t)B * hd * Tpad * sizeof(h16_t));
+            mark("c_qkv_planes T=" + std::to_string(T) + " heads=1", 0.0, 2);
+            launch_c_qkv_planes(qkv.f, qkv.C, qk_hi, qk_lo, vt_hi, vt_lo, B, T, Tpad, 1, hd, st);
+            Act a = new_operand(qkv.B, qkv.H, qkv.W, hd);
+            const double fl = 4.0 * Z * (double)T * T * hd;
+            tm.flops_attn += fl;
+            tm.n_attn++;
+            mark("flash_attn512_split T=" + std::to_string(T), fl);
+            prof_begin(1);
+            launch_flash_attn512_split(qk_hi, qk_lo, vt_hi, vt_lo, a.p, B, T, Tpad, scale, st);
+            prof_end();
+            pool.release(qk_hi); pool.release(qk_lo); pool.release(vt_hi); pool.release(vt_lo);
+            return a;
+        }
+        if (path == C_ATTN_FLASH64) {  // flash attention over split operands (attention.hip)
             if (scale != 0.125f) throw std::logic_error("attention_c: the split flash kernel computes softmax(q k^T / 8), scale must be 0.125");
             const int C = heads * hd;
             h16_t* qk_hi = (h16_t*)pool.alloc((size_t)B * T * 2 * C * sizeof(h16_t));
@@ -1617,6 +1637,13 @@ gp_status gp_reset_timings(gp_engine* e) {
 gp_status gp_halo_executed_flops(gp_engine* e, double* flops) {
     if (!e || !flops) return GP_ERR_INVALID;
     *flops = e->flops_halo_exec;
+    return GP_OK;
+}
+/* Bytes of device memory the activation pool holds (every buffer it ever allocated: the pool recycles, it never returns memory before
+ * gp_destroy), i.e. the high-water mark of the engine's transient memory.  Host bookkeeping only. */
+gp_status gp_pool_bytes(gp_engine* e, long long* bytes) {
+    if (!e || !bytes) return GP_ERR_INVALID;
+    *bytes = (long long)e->pool.total;
     return GP_OK;
 }
 gp_status gp_get_timings(gp_engine* e, gp_timings* out) {

@@ -33,7 +33,7 @@ std::mutex& gp_attr_mutex() {
 
 static GpSwitches g_switches = [] {
     GpSwitches s{};
-    s.gn_fuse_max_slices = s.gn_fuse_below_px = s.vt_tile = -1;
+    s.gn_fuse_max_slices = s.gn_fuse_below_px = s.vt_tile = s.c_flash512 = -1;
     s.qkv_fuse_max_rows = 1 << 30;
     return s;
 }();
@@ -63,6 +63,9 @@ void gp_switches_reload() {
     s.no_up_phases = flag("GENPERCEPT_NO_UP_PHASES");      // A/B: the x2-upsample convs through the nine-tap upsample kernel instead of four phase convolutions (r5)
     s.gn_small_old = flag("GENPERCEPT_GN_SMALL_OLD");      // A/B: gn_small_kernel (three passes over L2) instead of gn_small_reg_kernel (r5)
     s.c_no_flash = flag("GENPERCEPT_C_NO_FLASH");         // A/B: contract precision's head_dim-64 attention unfused (logits in HBM) instead of flash_attn64_split_kernel
+    // contract precision's head_dim-512 (VAE) attention: 1 = always flash_attn512_split_kernel, 0 = never, unset (-1) = only where the unfused
+    // path's logits + probabilities would exceed C_FLASH512_ABOVE_BYTES (kernels.h: c_attention_plan)
+    s.c_flash512 = num("GENPERCEPT_C_FLASH512", -1) < 0 ? -1 : (num("GENPERCEPT_C_FLASH512", -1) != 0 ? 1 : 0);
     // Engines on other host threads read g_switches on their launch paths: write it only when the environment really changed (tests / A/B
     // scripts, between calls), under a lock, so that concurrent engine creation with an unchanged environment never stores to it.
     static std::mutex mu;

@@ -297,6 +297,31 @@ gp_status gp_flash_attention_split(const float* qkv, int ld, void* out_split, in
     });
 }
 
+gp_status gp_flash_attention_hd512_split(const float* qkv, int ld, void* out_split, int B, int T, float scale, void* stream) {
+    if (!qkv || !out_split || B < 1 || T < 1 || ld < 1536 || (ld % 4) || !al16(qkv) || !al16(out_split) || GP_F16 || !flash_attn512_split_supported(T))
+        return GP_ERR_INVALID;  // (c_qk_planes_kernel reads float4 pairs: 16-byte aligned rows)
+    return kernel_entry([&]() -> gp_status {
+        const int Tpad = (T + 63) / 64 * 64;
+        const size_t n_qk = (size_t)B * T * 1024, n_vt = (size_t)B * 512 * Tpad;
+        h16_t* buf = nullptr;
+        HIPCHK(hipMalloc((void**)&buf, (2 * n_qk + 2 * n_vt) * sizeof(h16_t)));
+        h16_t *qk_hi = buf, *qk_lo = buf + n_qk, *vt_hi = buf + 2 * n_qk, *vt_lo = vt_hi + n_vt;
+        launch_c_qkv_planes(qkv, ld, qk_hi, qk_lo, vt_hi, vt_lo, B, T, Tpad, 1, 512, (hipStream_t)stream);
+        launch_flash_attn512_split(qk_hi, qk_lo, vt_hi, vt_lo, (h16_t*)out_split, B, T, Tpad, scale, (hipStream_t)stream);
+        const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+        (void)hipFree(buf);
+        if (e != hipSuccess) return GP_ERR_HIP;
+        return GP_OK;
+    });
+}
+
+gp_status gp_c_attention_plan(int B, int T, int heads, int hd, int* path, long long* workspace_bytes) {
+    if (B < 1 || T < 1 || heads < 1 || hd < 64 || (hd % 64) || !path || !workspace_bytes) return GP_ERR_INVALID;
+    gp_switches_reload();
+    *path = c_attention_plan(B, T, heads, hd, workspace_bytes);
+    return GP_OK;
+}
+
 // ---- contract-precision test entry points (bf16 library only): the launchers the engine's conv_c / linear_c / groupnorm use ---------------
 gp_status gp_c_split3(const float* x, int ldx, void* out, long long rows, int C, int b_order, int act, float scale, void* stream) {
     if (GP_F16 || !x || !out || rows < 1 || C < 8 || (C % 8) || ldx < C || (ldx % 4) || !al16(x) || !al16(out) || (b_order != 0 && b_order != 1) ||

@@ -67,7 +67,7 @@ struct IGemmParams {
 struct GpSwitches {
     int no_flash512, no_conv_few, no_conv_img, no_cross_fold, no_gn_fusion, gn_fuse_max_slices, gn_fuse_below_px, no_stats_fusion, vt_tile,
         no_gn_small, fp32_scores, no_qkv_fuse, qkv_fuse_max_rows, no_rgb_conv, igemm_dbg, no_splitk, no_halo, no_pgemm, gn_small_old, no_up_phases,
-        c_no_flash;
+        c_no_flash, c_flash512;
 };
 const GpSwitches& gp_sw();
 void gp_switches_reload();
@@ -236,6 +236,20 @@ void launch_c_qkv_planes(const float* qkv, int ld, h16_t* qk_hi, h16_t* qk_lo, h
 // attention.hip: flash attention (head_dim 64) over split operands; out = A-order split operand [B*T][3 * heads * 64]
 void launch_flash_attn64_split(const h16_t* qk_hi, const h16_t* qk_lo, const h16_t* vt_hi, const h16_t* vt_lo, h16_t* out, int B, int T, int heads, int ld,
                                int Tpad, hipStream_t s);
+// attention.hip: the VAE's one-head, head_dim-512 attention fused over split operands (planes of launch_c_qkv_planes(heads = 1, hd = 512));
+// out = A-order split operand [B*T][1536].  No workspace; T below flash_attn512_split_supported's bound (32-bit buffer ranges per image).
+bool flash_attn512_split_supported(int T);
+void launch_flash_attn512_split(const h16_t* qk_hi, const h16_t* qk_lo, const h16_t* vt_hi, const h16_t* vt_lo, h16_t* out, int B, int T, int Tpad, float scale,
+                                hipStream_t s);
+// Which way the contract precision's attention core goes for (B images, T tokens, heads x hd) and the transient workspace of that way in
+// bytes (pure host arithmetic over gp_sw(); engine.hip: attention_c follows it, gp_c_attention_plan exports it).
+//   0 unfused: fp32 logits S and split probabilities P in HBM, 10 * B * heads * T * Tpad bytes (4 + 6 per logit), Tpad = round_up(T, 64)
+//   1 flash_attn64_split (hd 64): hi / lo planes of q | k and of V^T
+//   2 flash_attn512_split (one head of 512): the same planes, 6 KiB per token
+// hd 512: GENPERCEPT_C_FLASH512=1 always 2, =0 never, unset 2 only when the unfused workspace would exceed C_FLASH512_ABOVE_BYTES.
+enum { C_ATTN_UNFUSED = 0, C_ATTN_FLASH64 = 1, C_ATTN_FLASH512 = 2 };
+constexpr long long C_FLASH512_ABOVE_BYTES = 8ll << 30;   // policy, not a measurement: above every shape the tests and the benchmark run unfused
+int c_attention_plan(int B, int T, int heads, int hd, long long* workspace_bytes);
 bool c_softmax_split_supported(int ld);
 void launch_c_softmax_split(const float* in, h16_t* out, long long rows, int T, int ld, float scale, hipStream_t s);
 void launch_c_heads_merge_split(const float* O, h16_t* out, int B, int T, int heads, int hd, hipStream_t s);

@@ -112,6 +112,7 @@ SYMBOLS = {
     "gp_reset_timings": (_i, [_vp]),
     "gp_halo_executed_flops": (_i, [_vp, C.POINTER(C.c_double)]),
     "gp_saturation_events": (_i, [_vp, C.POINTER(C.c_longlong), _i]),
+    "gp_pool_bytes": (_i, [_vp, C.POINTER(C.c_longlong)]),
     "gp_get_launch_log": (_i, [_vp, C.c_char_p, _i]),
     "gp_packed_rows": (_i, [_i]),
     "gp_last_igemm_path": (_i, [C.POINTER(_i)]),
@@ -132,6 +133,8 @@ SYMBOLS = {
     "gp_layernorm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "gp_flash_attention": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "gp_flash_attention_split": (_i, [_vp, _i, _vp, _i, _i, _i, _vp]),
+    "gp_flash_attention_hd512_split": (_i, [_vp, _i, _vp, _i, _i, _f, _vp]),
+    "gp_c_attention_plan": (_i, [_i, _i, _i, _i, C.POINTER(_i), C.POINTER(C.c_longlong)]),
     "gp_c_split3": (_i, [_vp, _i, _vp, _ll, _i, _i, _i, _f, _vp]),
     "gp_c_groupnorm_split": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
     "gp_pack_weight_split": (_i, [_vp, _i, _i, _i, _i, _i, _vp]),
@@ -398,6 +401,12 @@ class Engine:
         self._check(self.lib.gp_halo_executed_flops(self._h, C.byref(v)))
         return float(v.value)
 
+    def pool_bytes(self) -> int:
+        """Bytes of device memory the engine's activation pool holds (`gp_pool_bytes`): the high-water mark of its transient memory."""
+        n = C.c_longlong(0)
+        self._check(self.lib.gp_pool_bytes(self._h, C.byref(n)))
+        return int(n.value)
+
     def saturation_events(self, reset: bool = False) -> int:
         """fp16 library: (call, kernel file) pairs since the last reset in which a saturating fp32 -> fp16 conversion actually clipped
         (`gp_saturation_events`); 0 = nothing left the fp16 range.  Always 0 for the bf16 library.  Synchronises the engine's stream."""
@@ -655,6 +664,30 @@ def flash_attention_split(qkv: torch.Tensor, batch: int, tokens: int, heads: int
         raise RuntimeError(f"gp_flash_attention_split failed ({st})")
     assert torch.equal(out[:, :c], out[:, 2 * c:])  # [hi | lo | hi]
     return out[:, :c].float() + out[:, c:2 * c].float()
+
+
+def flash_attention_hd512_split(qkv: torch.Tensor, batch: int, tokens: int, scale: float, return_operand: bool = False):
+    """qkv fp32 [B*T, >= 1536] (q | k | v at columns 0 | 512 | 1024) -> softmax(scale q k^T) v of the one-head, head_dim-512 attention as fp32
+    [B*T, 512], reassembled (hi + lo) from the split operand gp_flash_attention_hd512_split writes (contract precision; bf16 library).
+    return_operand: also the bf16 operand [B*T, 1536] itself ([hi | lo | hi])."""
+    lib = load_library("bf16")
+    m, c3 = qkv.shape
+    assert m == batch * tokens and c3 >= 1536 and qkv.dtype == torch.float32
+    out = torch.empty((m, 1536), dtype=torch.bfloat16, device=qkv.device)
+    st = lib.gp_flash_attention_hd512_split(qkv.data_ptr(), qkv.stride(0), out.data_ptr(), batch, tokens, float(scale), _stream_ptr())
+    if st != GP_OK:
+        raise RuntimeError(f"gp_flash_attention_hd512_split failed ({st})")
+    val = out[:, :512].float() + out[:, 512:1024].float()
+    return (val, out) if return_operand else val
+
+
+def c_attention_plan(batch: int, tokens: int, heads: int, hd: int):
+    """(path, workspace bytes) of the contract precision's attention core for this shape under the current GENPERCEPT_* switches
+    (`gp_c_attention_plan`): 0 unfused, 1 flash_attn64_split, 2 flash_attn512_split.  Host arithmetic, no GPU."""
+    lib = load_library("bf16")
+    path, ws = C.c_int(-1), C.c_longlong(-1)
+    _c_check(lib.gp_c_attention_plan(batch, tokens, heads, hd, C.byref(path), C.byref(ws)), "gp_c_attention_plan")
+    return int(path.value), int(ws.value)
 
 
 # ---- contract precision (bf16 library): split operands are bf16 [rows][3 C], A order [hi | lo | hi], B order [hi | hi | lo] ----------------------

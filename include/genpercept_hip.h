@@ -100,7 +100,12 @@ gp_dtype gp_element_dtype(void);
  *                     every matrix product runs on the bf16 matrix cores with split operands (x = hi + lo, three MFMAs per product: hi.hi +
  *                     lo.hi + hi.lo, fp32 accumulation; csrc/contract.hip).  About 2^-16 relative per product: final maps within 1e-3 of the
  *                     fp32 path under both the mean-absolute and the relative-RMS reading, at roughly a quarter of the native throughput.
- *                     bf16 library only (GP_ERR_INVALID in the fp16 library). */
+ *                     bf16 library only (GP_ERR_INVALID in the fp16 library).
+ *                     Memory of the VAE mid-block attention (one head of 512, T = h * w tokens per image) in this precision: the unfused path
+ *                     keeps fp32 logits and split probabilities in device memory, 10 * B * T * Tpad bytes (Tpad = T rounded up to 64: 3.4 GB
+ *                     for batch 4 at 768 x 768, 10.7 GB at 1024 x 1024), the fused one (flash_attn512_split_kernel) 6 KiB per token and
+ *                     nothing quadratic in T.  Selection (gp_c_attention_plan): GENPERCEPT_C_FLASH512=1 always fused, =0 never, unset
+ *                     fused only where the unfused workspace would exceed 8 GiB.  The two differ by summation order only. */
 typedef enum { GP_PREC_NATIVE = 0, GP_PREC_CONTRACT = 1 } gp_precision;
 gp_status gp_set_precision(gp_engine* e, gp_precision prec);
 gp_precision gp_get_precision(const gp_engine* e);
@@ -157,6 +162,9 @@ gp_status gp_get_timings(gp_engine* e, gp_timings* out);
  * range) always reports 0.  Synchronises the engine's stream.  The Python pipeline logs a warning when a call raised events. */
 gp_status gp_saturation_events(gp_engine* e, long long* events, int reset);
 gp_status gp_reset_timings(gp_engine* e);
+/* Bytes of device memory the engine's activation pool holds: everything it ever allocated (it recycles buffers and returns memory only in
+ * gp_destroy), i.e. the high-water mark of the transient memory of the calls so far. */
+gp_status gp_pool_bytes(gp_engine* e, long long* bytes);
 /* executed (not algorithmic) MFMA flops of the halo-conv launches since gp_reset_timings: equals gp_timings.flops_halo except for launches that do
  * less arithmetic than their algorithmic count (the x2-upsample convs as four 2x2-tap phase convolutions: 4/9) */
 gp_status gp_halo_executed_flops(gp_engine* e, double* flops);
@@ -280,6 +288,16 @@ gp_status gp_flash_attention(const void* q, const void* k, const void* vt, void*
  * out_split: DEVICE 16-bit [B*T][3C] = the A-order split operand [hi | lo | hi] of softmax(q k^T / 8) v that the output projection reads (value = hi + lo).
  * ld % 4 == 0 and 16-byte aligned qkv / out_split (GP_ERR_INVALID otherwise).  bf16 library only.  Synchronises the stream (test entry point). */
 gp_status gp_flash_attention_split(const float* qkv, int ld, void* out_split, int B, int T, int heads, void* stream);
+/* The same for the VAE mid-block attention (one head, head_dim 512; attention.hip: flash_attn512_split_kernel): qkv DEVICE fp32 [B*T][ld] with
+ * q | k | v at columns 0 | 512 | 1024, out_split 16-bit [B*T][1536] = [hi | lo | hi] of softmax(scale q k^T) v; scores and probabilities stay
+ * on the CU, no workspace beyond the operand planes (6 KiB per token).  Any B >= 1, T >= 1 (T < 2^21); ld >= 1536, ld % 4 == 0, 16-byte aligned
+ * qkv / out_split (GP_ERR_INVALID otherwise, before anything is launched).  bf16 library only.  Synchronises the stream (test entry point). */
+gp_status gp_flash_attention_hd512_split(const float* qkv, int ld, void* out_split, int B, int T, float scale, void* stream);
+/* Which way the contract precision's attention core goes for B images of T tokens, heads x hd, with the GENPERCEPT_* switches as the
+ * environment has them now, and the transient workspace of that way in bytes.  path: 0 unfused (logits + probabilities in device memory,
+ * 10 * B * heads * T * Tpad bytes), 1 flash_attn64_split (hd 64), 2 flash_attn512_split (one head of 512; see gp_set_precision); for 1 and 2
+ * the workspace is the hi / lo operand planes, 8 * B * T * heads * hd + 4 * B * heads * hd * Tpad bytes.  Host arithmetic only. */
+gp_status gp_c_attention_plan(int B, int T, int heads, int hd, int* path, long long* workspace_bytes);
 /* ---- contract-precision test entry points (bf16 library only; GP_ERR_INVALID from the fp16 library) -------------------------------------------
  * The launchers the engine's contract path uses (csrc/contract.hip), with every argument checked on the host first: fp32 rows with ld % 4 == 0,
  * 16-byte aligned pointers.  A "split" operand is 16-bit [rows][3 C]: A order [hi | lo | hi], B order [hi | hi | lo], hi = bf16(x), lo = bf16(x - hi).
