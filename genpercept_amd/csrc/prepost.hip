@@ -15,6 +15,7 @@
 // All HBM-bound, one thread per output element.
 #include "common.h"
 #include "kernels.h"
+#include "resize_index.h"
 
 namespace {
 
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(256) void resize_nearest_exact_kernel(const T* __re
         const long long r = idx / Wo;
         const int oy = (int)(r % Ho);
         const long long pl = r / Ho;
-        const int iy = min((int)floorf(((float)oy + 0.5f) * sy), Hi - 1), ix = min((int)floorf(((float)ox + 0.5f) * sx), Wi - 1);
+        const int iy = nearest_exact_src(oy, sy, Hi), ix = nearest_exact_src(ox, sx, Wi);
         T v = in[(pl * Hi + iy) * Wi + ix];
         if constexpr (CLIP01 && sizeof(T) == 4) v = fminf(fmaxf(v, 0.f), 1.f);
         out[idx] = v;

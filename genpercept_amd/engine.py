@@ -150,6 +150,9 @@ SYMBOLS = {
     "gp_postprocess": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "gp_eval_depth_workspace": (_ll, [_i, _i, _i]),
     "gp_eval_depth": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _ll, _vp]),
+    "gp_ensemble_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "gp_ensemble_workspace": (_ll, [_i, _i, _i, _i]),
+    "gp_ensemble_reduce": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
     "gp_mfma_peak_tflops": (C.c_double, [_i, _vp]),
     "gp_mfma_peak_tflops_shape": (C.c_double, [_i, _i, _vp]),
     "gp_mfma_lds_probe": (C.c_double, [_i, _i, _i, _i, _vp]),
@@ -925,6 +928,56 @@ def eval_depth(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, alignme
                 raise ValueError(f"image {i}: least-squares alignment needs at least 2 fit pixels and a non-singular system (n_fit = {int(row[3])})")
     names = list(METRICS.keys())
     return [{k: float(row[4 + j]) for j, k in enumerate(names)} for row in raw], (raw[:, 0].copy(), raw[:, 1].copy(), raw[:, 2].astype("int64"))
+
+
+ENSEMBLE_REDUCTION = {"median": 0, "mean": 1}
+
+
+def ensemble_gather(depth: torch.Tensor, h: int, w: int, out: Optional[torch.Tensor] = None):
+    """gp_ensemble_gather on the members depth fp32 [B, E, H, W] ON THE DEVICE: (small [B, E, h, w], minmax [B, E, 2]) = the nearest-exact
+    reduction `image_util.resize_max_res(depth, max_res, "nearest-exact")` for (h, w) = `image_util.resize_max_res_size(H, W, max_res)` and each
+    reduced member's (min, max).  `out`: an fp32 device buffer of B * E * (h * w + 2) elements to carve both results from (so that one copy
+    brings them to the host).  Enqueued on the current stream, no synchronisation."""
+    assert depth.is_cuda and depth.dim() == 4
+    depth = depth.to(torch.float32).contiguous()
+    b, e, hh, ww = (int(v) for v in depth.shape)
+    n = b * e * int(h) * int(w)
+    if out is None:
+        out = torch.empty((n + b * e * 2,), dtype=torch.float32, device=depth.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n + b * e * 2
+    small, minmax = out[:n].view(b, e, int(h), int(w)), out[n:].view(b, e, 2)
+    st = load_library().gp_ensemble_gather(depth.data_ptr(), b, e, hh, ww, int(h), int(w), small.data_ptr(), minmax.data_ptr(), _stream_ptr(depth.device))
+    if st != GP_OK:
+        raise RuntimeError(f"gp_ensemble_gather failed ({st})")
+    return small, minmax
+
+
+def ensemble_reduce(depth: torch.Tensor, scale=None, shift=None, reduction: str = "median", output_uncertainty: bool = False):
+    """gp_ensemble_reduce on the members depth fp32 [B, E, H, W] ON THE DEVICE: per pixel a_e = depth_e * scale_e + shift_e (fp32, no FMA),
+    the median (torch.median: lower middle) or mean over the members, per-image rescale to [0, 1] -> (pred [B, H, W], uncertainty [B, H, W] or
+    None).  scale, shift: [B, E] (any tensor / array; cast to fp32); scale None = ones (no alignment), shift None = scale-only (d_min = 0).
+    Enqueued on the current stream, no synchronisation."""
+    assert depth.is_cuda and depth.dim() == 4
+    if reduction not in ENSEMBLE_REDUCTION:
+        raise ValueError(f"Unrecognized reduction method: {reduction}.")
+    depth = depth.to(torch.float32).contiguous()
+    b, e, h, w = (int(v) for v in depth.shape)
+    host = [torch.ones((b, e), dtype=torch.float32) if scale is None else torch.as_tensor(scale).to(torch.float32).reshape(b, e)]
+    if shift is not None:
+        host.append(torch.as_tensor(shift).to(torch.float32).reshape(b, e))
+    if len({t.device for t in host}) > 1:
+        host = [t.to(depth.device) for t in host]
+    par = torch.stack(host).to(depth.device).contiguous()  # one upload when both come from the host
+    lib = load_library()
+    pred = torch.empty((b, h, w), dtype=torch.float32, device=depth.device)
+    unc = torch.empty((b, h, w), dtype=torch.float32, device=depth.device) if output_uncertainty else None
+    nbytes = int(lib.gp_ensemble_workspace(b, e, h, w))
+    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=depth.device)
+    st = lib.gp_ensemble_reduce(depth.data_ptr(), par[0].data_ptr(), par[1].data_ptr() if shift is not None else None, b, e, h, w,
+                                ENSEMBLE_REDUCTION[reduction], pred.data_ptr(), _ptr(unc), ws.data_ptr(), nbytes, _stream_ptr(depth.device))
+    if st != GP_OK:
+        raise RuntimeError(f"gp_ensemble_reduce failed ({st})")
+    return pred, unc
 
 
 def mfma_peak_tflops(device: int = 0, precision: Optional[str] = None) -> float:

@@ -450,15 +450,15 @@ class GenPerceptPipeline:
         gen = o.get("generator")
         if e == 1:
             return self.single_infer(x, steps, gen, False, fix_timesteps, prompt)
-        from .ensemble import ensemble_depth
+        from .ensemble import ensemble_depth_batch
         bs = max(1, o.get("batch_size", 1))
-        outs = []
+        members = []
         for i in range(x.shape[0]):
             dup = x[i:i + 1].expand(e, -1, -1, -1)
-            preds = torch.cat([self.single_infer(dup[j:j + bs], steps, gen, False, fix_timesteps, prompt) for j in range(0, e, bs)], dim=0)
-            pred, _ = ensemble_depth(preds, scale_invariant=True, shift_invariant=True, max_res=50, **(o.get("ensemble_kwargs") or {}))
-            outs.append(pred)
-        return torch.cat(outs, dim=0)
+            members.append(torch.cat([self.single_infer(dup[j:j + bs], steps, gen, False, fix_timesteps, prompt) for j in range(0, e, bs)], dim=0))
+        # the members of all images at once: on the device one gather, one copy to the host, one reduce for the batch (ensemble.py)
+        pred, _ = ensemble_depth_batch(torch.stack(members), scale_invariant=True, shift_invariant=True, max_res=50, **(o.get("ensemble_kwargs") or {}))
+        return pred
 
     def infer_batch(self, images: Union[Sequence[Image.Image], torch.Tensor], mode: str, processing_res: Optional[int] = None,
                     match_input_res: bool = True, resample_method: str = "bilinear", color_map: Optional[str] = "Spectral", fix_timesteps=None,

@@ -16,6 +16,9 @@
  *   gp_infer_steps    single_infer for archs marigold / rgb_blending: the denoising loop with the DDIM update
  *                                                                   genpercept_pipeline.py:413-422,447-465; ddim.py:144-217; run.py:361-368
  *   gp_eval_depth     eval.py's per-image alignment + metrics               eval.py:168-215; src/util/alignment.py:29-94; src/util/metric.py:34-158
+ *   gp_ensemble_gather, gp_ensemble_reduce
+ *                     ensemble_depth's tensor half (the BFGS fit stays on the host)   genpercept/util/ensemble.py:43-205;
+ *                                                                   genpercept_pipeline.py:289-298
  * The per-kernel entry points (gp_conv2d ... gp_bilinear) exist for the parity tests; they are the same launchers the
  * engine uses.
  *
@@ -207,6 +210,25 @@ gp_status gp_postprocess(const float* pred, int B, int C, int h, int w, float* p
 long long gp_eval_depth_workspace(int B, int H, int W);   /* bytes; 0 for B, H or W < 1 */
 gp_status gp_eval_depth(const float* pred, const float* gt, const unsigned char* mask, int B, int H, int W, int alignment, int fit_cols,
                         float fit_inv_scale, float min_depth, float max_depth, double* out, void* workspace, long long workspace_bytes, void* stream);
+
+/* ---- test-time ensembling on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation, no atomics; csrc/ensemble.hip) ----
+ * The tensor half of ensemble_depth (genpercept/util/ensemble.py:43-205, called at genpercept_pipeline.py:289-298) for the E members of each of
+ * B images; the optimiser that finds the per-member (scale, shift) runs on the host between the two entries, on what the gather produced.
+ * gather: small [B][E][h][w] = the nearest-exact reduction of depth [B][E][H][W] (image_util.resize_max_res with (h, w) from the size rule of
+ *   gp_resize_max_res_size; the source index of the nearest-exact resize of gp_preprocess; h == H and w == W: a copy), minmax [B][E][2] = each
+ *   reduced member's (min, max).  One launch.
+ * reduce, per pixel in float32 without fused multiply-adds: a_e = depth_e * scale_e + shift_e (shift == NULL: scale-only, a_e = depth_e * scale_e);
+ *   reduction 0: pred = the element of rank (E - 1) / 2 of the sorted members (torch.median: the lower middle for even E), uncertainty = the
+ *   same rank of |a_e - pred|; reduction 1: pred = (sum in member order) / E, uncertainty = the unbiased standard deviation (two passes, divisor
+ *   E - 1; NaN for E = 1).  Then per image d_max = max(pred), d_min = min(pred) (0 when shift == NULL), rng = max(d_max - d_min, 1e-6),
+ *   pred = (pred - d_min) / rng, uncertainty = uncertainty / rng.  pred, uncertainty: [B][H][W]; uncertainty may be NULL.  1 <= E <= 64,
+ *   1 <= B <= 65535, H * W <= 0x7fffffff.  An image's result is bitwise the same alone and inside any batch.  An image with a NaN or an
+ *   infinite member has an unspecified result.  workspace: DEVICE scratch of at least the workspace entry's byte count (8-byte aligned), free
+ *   again once the stream has passed the call.  Three launches.  Arguments are validated before any HIP call (GP_ERR_INVALID). */
+gp_status gp_ensemble_gather(const float* depth, int B, int E, int H, int W, int h, int w, float* small, float* minmax, void* stream);
+long long gp_ensemble_workspace(int B, int E, int H, int W);   /* bytes; 0 for B, E, H or W < 1; proportional to B */
+gp_status gp_ensemble_reduce(const float* depth, const float* scale, const float* shift, int B, int E, int H, int W, int reduction, float* pred,
+                             float* uncertainty, void* workspace, long long workspace_bytes, void* stream);
 
 /* Sustained TFLOP/s of back-to-back v_mfma_f32_32x32x16 (this library's element type) on every CU of `device`: the chip's own MFMA
  * peak under load, reported by bench.py beside the nominal 2.5 PFLOP/s.  < 0 on error. */
