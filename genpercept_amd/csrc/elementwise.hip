@@ -54,9 +54,12 @@ void launch_concat(const h16_t* a, int Ca, const h16_t* b, int Cb, h16_t* out, l
     hipLaunchKernelGGL(concat_kernel, dim3(grid_for(pixels * ((Ca + Cb) / 8))), dim3(256), 0, s, a, Ca, b, Cb, out, pixels);
 }
 
-// The same concat, also leaving the GroupNorm statistics of the tensor it writes: per (bm consecutive pixels, channel) {sum, sum of
-// squares} in the layout of the conv epilogues (mode 0 of gn_finalize_tiles_kernel), so the resnet that consumes the concatenation
-// skips its statistics read pass.  A thread owns one 8-channel slot for the bm pixels of its tile: no cross-thread reduction.
+// The same concat, also leaving the GroupNorm statistics of the tensor it writes: per (bm consecutive pixels, channel) {sum, CENTRED second
+// moment M2 = sum (x - tile mean)^2} in the tiling of the conv epilogues' mode 0 (mode 4 = CONCAT_STATS_MODE of gn_finalize_tiles_kernel), so the
+// resnet that consumes the concatenation skips its statistics read pass.  A thread owns one 8-channel slot for the bm pixels of its tile: no
+// cross-thread reduction.  The sums run over d = x - x0, x0 the tile's first pixel: sum = bm x0 + sum d, M2 = sum d^2 - (sum d)^2 / bm, whose
+// cancellation is relative to the spread INSIDE the tile, not to the channel's mean (raw {sum, sum x^2} partials lose (mean / std)^2 2^-24 of
+// the variance; DESIGN.md, parity status, has the gate ratios of both forms from tests/test_kernels_glue_gpu.py).
 __global__ __launch_bounds__(256) void concat_stats_kernel(const h16_t* __restrict__ a, int Ca, const h16_t* __restrict__ b, int Cb,
                                                             h16_t* __restrict__ out, int bm, float* __restrict__ part) {
     const int va = Ca >> 3, vt = (Ca + Cb) >> 3, C = Ca + Cb;
@@ -67,20 +70,25 @@ __global__ __launch_bounds__(256) void concat_stats_kernel(const h16_t* __restri
     const h16_t* src = from_a ? a + p0 * Ca + v * 8 : b + p0 * Cb + (v - va) * 8;
     const int ld = from_a ? Ca : Cb;
     h16_t* dst = out + p0 * C + v * 8;
-    float s[8], q[8];
+    float x0[8], s[8], q[8];
+    {
+        const uint4 x = *(const uint4*)src;
+        const float f[8] = {h16_lo(x.x), h16_hi(x.x), h16_lo(x.y), h16_hi(x.y), h16_lo(x.z), h16_hi(x.z), h16_lo(x.w), h16_hi(x.w)};
 #pragma unroll
-    for (int e = 0; e < 8; ++e) s[e] = q[e] = 0.f;
+        for (int e = 0; e < 8; ++e) { x0[e] = f[e]; s[e] = q[e] = 0.f; }
+    }
 #pragma unroll 8
     for (int r = 0; r < bm; ++r) {  // (eight 16-byte loads in flight per thread: r3's four left the pass at half the HBM rate)
         const uint4 x = *(const uint4*)(src + (long long)r * ld);
         *(uint4*)(dst + (long long)r * C) = x;
         const float f[8] = {h16_lo(x.x), h16_hi(x.x), h16_lo(x.y), h16_hi(x.y), h16_lo(x.z), h16_hi(x.z), h16_lo(x.w), h16_hi(x.w)};
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { s[e] += f[e]; q[e] += f[e] * f[e]; }
+        for (int e = 0; e < 8; ++e) { const float d = f[e] - x0[e]; s[e] += d; q[e] += d * d; }
     }
     float* po = part + ((long long)blockIdx.x * C + v * 8) * 2;
+    const float n = (float)bm, inv_n = 1.f / n;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { po[2 * e] = s[e]; po[2 * e + 1] = q[e]; }
+    for (int e = 0; e < 8; ++e) { po[2 * e] = n * x0[e] + s[e]; po[2 * e + 1] = fmaxf(q[e] - s[e] * s[e] * inv_n, 0.f); }
 }
 // pixels per statistics tile: the largest divisor of an image's pixel count among {64, 48, 32, 16} that still gives the launch ~2 workgroups
 // per CU (r3 always took the largest: the UNet's 24x24 maps then ran on 72 workgroups and the pass was latency-bound, 34 us for 24 MB)
@@ -365,7 +373,7 @@ void launch_minmax_norm(float* x, int B, long long n, float* ws, hipStream_t s) 
 // v_mfma_f32_16x16x32_bf16 per 16 pixels x 16 channels, the image is read as uint8 and the layer is bound by its 2 B/element output.
 //   workgroup: 4 waves, 16x16 output pixels x 128 channels; halo 18x18x3 normalised to bf16 in LDS ([pixel][4]); k = 3 * tap + c.
 //   r4: PERSISTENT -- grid = (B x J, channel slices): a workgroup walks the tiles jw, jw + J, ... of one image with its weights, bias and
-//   fragments loaded once, and leaves ONE statistics row (+ its pixel count: the "mode 2" layout of the persistent convs) instead of one per
+//   fragments loaded once, and leaves ONE statistics row (+ its pixel count: the layout of the persistent convs' "mode 2") instead of one per
 //   16x16 tile: at 768x768 that is 128 rows per image for the finalize kernel instead of 2304 (its first launch cost 40 us, and the one-tile
 //   workgroups spent as long on weights / bias / launch as on their 16 MFMA k-steps).
 __global__ __launch_bounds__(256) void rgb_conv_in_kernel(const void* __restrict__ rgb, int is_u8, const h16_t* __restrict__ w27,
@@ -453,12 +461,16 @@ __global__ __launch_bounds__(256) void rgb_conv_in_kernel(const void* __restrict
                     *(uint4*)(o + 32 * ip) = pk;
                     const float r[8] = {h16_lo(pk.x), h16_hi(pk.x), h16_lo(pk.y), h16_hi(pk.y), h16_lo(pk.z), h16_hi(pk.z), h16_lo(pk.w), h16_hi(pk.w)};
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) { st_s[ip][e] += r[e]; st_q[ip][e] += r[e] * r[e]; }
+                    for (int e = 0; e < 8; ++e) { const float dv = r[e] - bv[ip][e]; st_s[ip][e] += dv; st_q[ip][e] += dv * dv; }  // (about the bias: below)
                 }
             }
         }
     }
-    if (stats) {  // per (workgroup, channel) sums of the stored values: 16 pixel lanes -> lane a == 0, 4 waves -> LDS -> one thread per channel
+    // per (workgroup, channel) {sum, CENTRED second moment} of the stored values ("mode 3" of gn_finalize_tiles_kernel).  Every lane sums d = x - bias[c]
+    // and d^2 -- one pivot per channel, so lanes, waves and tiles simply add -- and the row leaves sum = n bias + sum d, M2 = sum d^2 - (sum d)^2 / n:
+    // a channel offset the bias carries no longer cancels against the variance (raw {sum, sum x^2} rows read 1.1 of the scale gate at mean / std = 8 in
+    // the fp16 library, tests/test_kernels_glue_gpu.py).  16 pixel lanes -> lane a == 0, 4 waves -> LDS -> one thread per channel
+    if (stats) {
 #pragma unroll
         for (int ip = 0; ip < 4; ++ip)
 #pragma unroll
@@ -479,8 +491,9 @@ __global__ __launch_bounds__(256) void rgb_conv_in_kernel(const void* __restrict
 #pragma unroll
             for (int w = 0; w < 4; ++w) { ss += s_red[(w * 128 + tid) * 2]; qq += s_red[(w * 128 + tid) * 2 + 1]; }
             float* so = stats + (row * Cout + n0 + tid) * 2;
-            so[0] = ss;
-            so[1] = qq;
+            const float n = (float)run_px, pv = bias ? bias[n0 + tid] : 0.f;
+            so[0] = n * pv + ss;
+            so[1] = fmaxf(qq - ss * (ss / n), 0.f);
         }
         if (tid == 0 && blockIdx.y == 0) stats[(long long)B * J * Cout * 2 + row] = (float)run_px;
     }
@@ -508,7 +521,7 @@ int rgb_conv_in_rows(int B, int H, int W) {
     if (J > tiles_sp) J = tiles_sp;
     return J < 1 ? 1 : J;
 }
-// Cout % 32 == 0; w27 = launch_pack_k27 output; stats (optional): [B * J][Cout][2] sums + [B * J] pixel counts, J = rgb_conv_in_rows() ("mode 2")
+// Cout % 32 == 0; w27 = launch_pack_k27 output; stats (optional): [B * J][Cout][2] {sum, centred M2} + [B * J] pixel counts, J = rgb_conv_in_rows() ("mode 3")
 void launch_rgb_conv_in(const void* rgb, int is_u8, const h16_t* w27, const float* bias, h16_t* out, float* stats, int B, int H, int W, int Cout,
                         hipStream_t s) {
     const int J = rgb_conv_in_rows(B, H, W);

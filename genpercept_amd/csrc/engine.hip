@@ -1110,9 +1110,9 @@ struct gp_engine {
             // u8 image -> conv_in output in one kernel (K = 27), statistics for the first resnet's norm1 included
             h = new_act(B, Hh, Ww, win.cout);
             if (fuse_stats) {
-                const int rows = rgb_conv_in_rows(B, Hh, Ww);  // persistent conv_in: one row per workgroup + its pixel count ("mode 2")
+                const int rows = rgb_conv_in_rows(B, Hh, Ww);  // persistent conv_in: one row per workgroup + its pixel count (mode 2's layout, centred: "mode 3")
                 h.st = (float*)pool.alloc((size_t)B * rows * (2 * win.cout + 1) * sizeof(float));
-                h.st_mode = 2;
+                h.st_mode = RGB_CONV_IN_STATS_MODE;
                 h.st_bm = rows;
             }
             tm.flops_igemm += 2.0 * (double)h.pixels() * win.cout * 27.0;
@@ -1172,7 +1172,7 @@ struct gp_engine {
             launch_c_concat(h.f, h.C, skip.f, skip.C, cat.f, h.pixels(), st);
         } else if (cbm) {  // the copy also leaves the statistics the resnet's first GroupNorm needs
             cat.st = (float*)pool.alloc((size_t)(h.pixels() / cbm) * cat.C * 2 * sizeof(float));
-            cat.st_mode = 0;
+            cat.st_mode = CONCAT_STATS_MODE;
             cat.st_bm = cbm;
             launch_concat_stats(h.p, h.C, skip.p, skip.C, cat.p, h.pixels(), cbm, cat.st, st);
         } else {

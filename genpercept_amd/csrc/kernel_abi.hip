@@ -496,4 +496,192 @@ gp_status gp_bilinear(const void* in, void* out, int B, int Hi, int Wi, int Ho, 
     return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
 }
 
+// ---- the elementwise / layout kernels between the matrix products (elementwise.hip), and with contract != 0 their fp32 twins (contract.hip, bf16
+// library only).  Everything a kernel would fault on is refused here, before any HIP call. ------------------------------------------------------
+#define GP_LAUNCHED() (hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP)
+static bool al8(const void* p) { return ((uintptr_t)p & 7) == 0; }
+
+gp_status gp_rgb_prologue(const void* rgb, int is_u8, void* out, int B, int H, int W, int Cpad, int contract, void* stream) {
+    if (!rgb || !out || B < 1 || H < 1 || W < 1 || !al16(out) || (!is_u8 && ((uintptr_t)rgb & 3))) return GP_ERR_INVALID;
+    if (contract) {
+        if (GP_F16 || Cpad != 64) return GP_ERR_INVALID;  // (c_rgb_split_kernel writes 64 logical channels: 192 elements per pixel)
+        launch_c_rgb_split(rgb, is_u8, (h16_t*)out, B, H, W, (hipStream_t)stream);
+    } else {
+        if (Cpad < 8 || (Cpad % 8)) return GP_ERR_INVALID;
+        launch_rgb_prologue(rgb, is_u8, (h16_t*)out, B, H, W, Cpad, (hipStream_t)stream);
+    }
+    return GP_LAUNCHED();
+}
+
+gp_status gp_concat(const void* a, int Ca, const void* b, int Cb, void* out, long long pixels, int contract, void* stream) {
+    const int v = contract ? 4 : 8;
+    if ((contract && GP_F16) || !a || !b || !out || pixels < 1 || Ca < v || Cb < v || (Ca % v) || (Cb % v) || !al16(a) || !al16(b) || !al16(out))
+        return GP_ERR_INVALID;
+    if (contract) launch_c_concat((const float*)a, Ca, (const float*)b, Cb, (float*)out, pixels, (hipStream_t)stream);
+    else launch_concat((const h16_t*)a, Ca, (const h16_t*)b, Cb, (h16_t*)out, pixels, (hipStream_t)stream);
+    return GP_LAUNCHED();
+}
+
+int gp_concat_stats_bm(long long hw, long long pixels, int channels) { return (hw < 1 || pixels < 1 || channels < 8) ? 0 : concat_stats_bm(hw, pixels, channels); }
+
+gp_status gp_concat_stats(const void* a, int Ca, const void* b, int Cb, void* out, int B, int HW, int bm, int* bm_used, const float* gamma, const float* beta,
+                          int groups, float eps, float* scale_out, float* shift_out, void* stream) {
+    if (!a || !b || !out || B < 1 || HW < 1 || Ca < 8 || Cb < 8 || (Ca % 8) || (Cb % 8) || !al16(a) || !al16(b) || !al16(out) || bm < 0) return GP_ERR_INVALID;
+    const int C = Ca + Cb;
+    if (gamma && (!beta || !scale_out || !shift_out || groups < 1 || (C % groups))) return GP_ERR_INVALID;
+    const long long pixels = (long long)B * HW;
+    if (!bm) bm = concat_stats_bm(HW, pixels, C);
+    if (bm < 1 || (HW % bm)) return GP_ERR_INVALID;  // (a statistics tile never spans two images)
+    if (bm_used) *bm_used = bm;
+    return kernel_entry([&]() -> gp_status {
+        float* part = scratch_floats(1, (size_t)(pixels / bm) * C * 2);
+        launch_concat_stats((const h16_t*)a, Ca, (const h16_t*)b, Cb, (h16_t*)out, pixels, bm, part, (hipStream_t)stream);
+        if (gamma)  // the engine's consumer (gp_engine::gn_scale_shift with the Act::st_mode gp_engine::concat sets)
+            launch_groupnorm_from_partials(part, CONCAT_STATS_MODE, bm, B, HW, 1, C, groups, eps, gamma, beta, scale_out, shift_out, (hipStream_t)stream);
+        return GP_OK;
+    });
+}
+
+gp_status gp_rgb_conv_in_stats(const void* rgb, int is_u8, const void* w_packed, const float* bias, void* out, int B, int H, int W, int Cout, const float* gamma,
+                               const float* beta, int groups, float eps, float* scale_out, float* shift_out, void* stream) {
+    if (!rgb || !w_packed || !out || B < 1 || H < 1 || W < 1 || Cout < 32 || (Cout % 32) || !gamma || !beta || !scale_out || !shift_out || groups < 1 ||
+        (Cout % groups) || !al16(w_packed) || !al16(out) || (!is_u8 && ((uintptr_t)rgb & 3)))
+        return GP_ERR_INVALID;
+    return kernel_entry([&]() -> gp_status {
+        const int J = rgb_conv_in_rows(B, H, W);
+        float* st = scratch_floats(1, (size_t)B * J * (2 * Cout + 1));
+        h16_t* w27 = nullptr;
+        HIPCHK(hipMalloc((void**)&w27, (size_t)Cout * 32 * sizeof(h16_t)));
+        launch_pack_k27((const h16_t*)w_packed, 9 * 64, Cout, w27, (hipStream_t)stream);
+        launch_rgb_conv_in(rgb, is_u8, w27, bias, (h16_t*)out, st, B, H, W, Cout, (hipStream_t)stream);
+        launch_groupnorm_from_partials(st, RGB_CONV_IN_STATS_MODE, J, B, H, W, Cout, groups, eps, gamma, beta, scale_out, shift_out, (hipStream_t)stream);
+        const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+        (void)hipFree(w27);
+        return e == hipSuccess ? GP_OK : GP_ERR_HIP;
+    });
+}
+
+gp_status gp_nchw_to_nhwc(const float* in, void* out, int B, int C, int H, int W, int Cpad, int contract, void* stream) {
+    if ((contract && GP_F16) || !in || !out || B < 1 || C < 1 || H < 1 || W < 1 || Cpad < C) return GP_ERR_INVALID;
+    if (contract) launch_c_nchw_to_nhwc(in, (float*)out, B, C, H, W, Cpad, (hipStream_t)stream);
+    else launch_nchw_f32_to_nhwc(in, (h16_t*)out, B, C, H, W, Cpad, (hipStream_t)stream);
+    return GP_LAUNCHED();
+}
+
+gp_status gp_nhwc_to_nchw(const void* in, float* out, int B, int C, int H, int W, int ld, int contract, void* stream) {
+    if ((contract && GP_F16) || !in || !out || B < 1 || C < 1 || H < 1 || W < 1 || ld < C) return GP_ERR_INVALID;
+    if (contract) launch_c_nhwc_to_nchw((const float*)in, out, B, C, H, W, ld, (hipStream_t)stream);
+    else launch_nhwc_to_nchw_f32((const h16_t*)in, out, B, C, H, W, ld, (hipStream_t)stream);
+    return GP_LAUNCHED();
+}
+
+gp_status gp_ddim_init(const float* noise_nchw, void* lat, float* sample, int B, int H, int W, int L, int ld, int off, int contract, void* stream) {
+    if ((contract && GP_F16) || !lat || !sample || B < 1 || H < 1 || W < 1 || L < 1 || off < 0 || (long long)off + L > ld) return GP_ERR_INVALID;
+    if (contract) launch_c_ddim_init(noise_nchw, (float*)lat, sample, B, H, W, L, ld, off, (hipStream_t)stream);
+    else launch_ddim_init(noise_nchw, (h16_t*)lat, sample, B, H, W, L, ld, off, (hipStream_t)stream);
+    return GP_LAUNCHED();
+}
+
+gp_status gp_ddim_update(const void* model, int ldm, float* sample, void* uin, int ldu, int off, void* x0_out, int ldx, long long pixels, int L,
+                         const float* coef7_host, int contract, void* stream) {
+    if ((contract && GP_F16) || !model || !sample || !uin || !coef7_host || pixels < 1 || L < 1 || ldm < L || off < 0 || (long long)off + L > ldu ||
+        (x0_out && ldx < L))
+        return GP_ERR_INVALID;
+    const DdimCoef k{coef7_host[0], coef7_host[1], coef7_host[2], coef7_host[3], coef7_host[4], coef7_host[5], coef7_host[6]};
+    if (contract) launch_c_ddim_step((const float*)model, ldm, sample, (float*)uin, ldu, off, (float*)x0_out, ldx, pixels, L, k, (hipStream_t)stream);
+    else launch_ddim_step((const h16_t*)model, ldm, sample, (h16_t*)uin, ldu, off, (h16_t*)x0_out, ldx, pixels, L, k, (hipStream_t)stream);
+    return GP_LAUNCHED();
+}
+
+gp_status gp_decode_epilogue(const void* in, float* out, int B, int H, int W, int ld, int mean3, int raw, int contract, void* stream) {
+    if ((contract && GP_F16) || !in || !out || B < 1 || H < 1 || W < 1 || ld < 3) return GP_ERR_INVALID;
+    if (contract) {
+        launch_c_decode_epilogue((const float*)in, out, B, H, W, ld, mean3, raw, (hipStream_t)stream);
+    } else {
+        if ((ld % 4) || !al8(in)) return GP_ERR_INVALID;  // (decode_epilogue_kernel reads a pixel's three channels as one uint2)
+        launch_decode_epilogue((const h16_t*)in, out, B, H, W, ld, mean3, raw, (hipStream_t)stream);
+    }
+    return GP_LAUNCHED();
+}
+
+gp_status gp_scale_pad(const void* in, void* out, long long pixels, int C, int ldi, int ldo, float scale, void* stream) {
+    if (!in || !out || pixels < 1 || C < 1 || ldi < C || ldo < C) return GP_ERR_INVALID;
+    launch_scale_pad((const h16_t*)in, (h16_t*)out, pixels, C, ldi, ldo, scale, (hipStream_t)stream);
+    return GP_LAUNCHED();
+}
+
+gp_status gp_pointwise_small(const void* in, void* out, const float* w, const float* bias, long long pixels, int Cin, int Cout, int ldi, int ldo, float in_scale,
+                             int contract, void* stream) {
+    if ((contract && GP_F16) || !in || !out || !w || pixels < 1 || Cin < 1 || Cin > 8 || Cout < 1 || Cout > 8 || ldi < Cin || ldo < Cout) return GP_ERR_INVALID;
+    if (contract) launch_c_pointwise_small((const float*)in, (float*)out, w, bias, pixels, Cin, Cout, ldi, ldo, in_scale, (hipStream_t)stream);
+    else launch_pointwise_small((const h16_t*)in, (h16_t*)out, w, bias, pixels, Cin, Cout, ldi, ldo, in_scale, (hipStream_t)stream);
+    return GP_LAUNCHED();
+}
+
+gp_status gp_relu(const void* in, void* out, long long n, void* stream) {
+    if (!in || !out || n < 8 || (n % 8) || !al16(in) || !al16(out)) return GP_ERR_INVALID;
+    launch_relu((const h16_t*)in, (h16_t*)out, n, (hipStream_t)stream);
+    return GP_LAUNCHED();
+}
+
+gp_status gp_add(const void* a, const void* b, void* out, long long n, int contract, void* stream) {
+    const int v = contract ? 4 : 8;
+    if ((contract && GP_F16) || !a || !b || !out || n < v || (n % v) || !al16(a) || !al16(b) || !al16(out)) return GP_ERR_INVALID;
+    if (contract) launch_c_add((const float*)a, (const float*)b, (float*)out, n, (hipStream_t)stream);
+    else launch_add((const h16_t*)a, (const h16_t*)b, (h16_t*)out, n, (hipStream_t)stream);
+    return GP_LAUNCHED();
+}
+
+gp_status gp_dpt_final(const void* in, const float* w, float bias, float* out, int B, int HW, int Cin, int contract, void* stream) {
+    const int v = contract ? 4 : 8;
+    if ((contract && GP_F16) || !in || !w || !out || B < 1 || HW < 1 || Cin < v || (Cin % v) || !al16(in)) return GP_ERR_INVALID;
+    if (contract) launch_c_dpt_final((const float*)in, w, bias, out, B, HW, Cin, (hipStream_t)stream);
+    else launch_dpt_final((const h16_t*)in, w, bias, out, B, HW, Cin, (hipStream_t)stream);
+    return GP_LAUNCHED();
+}
+
+gp_status gp_minmax_norm(float* x, int B, long long n, void* stream) {
+    if (!x || B < 1 || B > 65535 || n < 1) return GP_ERR_INVALID;
+    return kernel_entry([&]() -> gp_status {
+        launch_minmax_norm(x, B, n, scratch_floats(1, (size_t)B * 64 * 2), (hipStream_t)stream);  // (64 partial {min, max} per image)
+        return GP_OK;
+    });
+}
+
+// ---- contract-only glue (contract.hip) -----------------------------------------------------------------------------------------------------------
+gp_status gp_c_heads_split(const float* qkv, int ld, void* Qs, void* Ks, void* Vts, int B, int T, int Tpad, int heads, int hd, void* stream) {
+    if (GP_F16 || !qkv || !Qs || !Ks || !Vts || B < 1 || T < 1 || heads < 1 || hd < 64 || (hd % 64) || (Tpad % 64) || Tpad < T || (long long)B * heads > 65535 ||
+        ld < 3 * heads * hd || (ld % 4) || !al16(qkv) || !al16(Qs) || !al16(Ks) || !al16(Vts))
+        return GP_ERR_INVALID;
+    launch_c_heads_split(qkv, ld, (h16_t*)Qs, (h16_t*)Ks, (h16_t*)Vts, B, T, Tpad, heads, hd, (hipStream_t)stream);
+    return GP_LAUNCHED();
+}
+
+gp_status gp_c_heads_merge_split(const float* O, void* out, int B, int T, int heads, int hd, void* stream) {
+    if (GP_F16 || !O || !out || B < 1 || T < 1 || heads < 1 || hd < 8 || (hd % 8) || !al16(O) || !al16(out)) return GP_ERR_INVALID;
+    launch_c_heads_merge_split(O, (h16_t*)out, B, T, heads, hd, (hipStream_t)stream);
+    return GP_LAUNCHED();
+}
+
+gp_status gp_c_cross_fold(const float* y, float* y_out, void* n3_out, const float* U, const float* u0, const float* G, const float* c0, const float* g3,
+                          const float* b3, int rows, int C, int heads, float eps, void* stream) {
+    if (GP_F16 || !y || !y_out || !U || !u0 || !G || !c0 || rows < 1 || C < 8 || !c_cross_fold_supported(C) || heads < 1 || (n3_out && (!g3 || !b3)) ||
+        !al16(y) || !al16(y_out) || !al16(n3_out) || !al16(U) || !al16(G) || !al16(c0) || !al16(g3) || !al16(b3))
+        return GP_ERR_INVALID;
+    launch_c_cross_fold(y, y_out, (h16_t*)n3_out, U, u0, G, c0, g3, b3, rows, C, heads, eps, (hipStream_t)stream);
+    return GP_LAUNCHED();
+}
+
+gp_status gp_c_cross_attention(const float* q, const float* kc, const float* vc, void* out, int rows, int C, int L, void* stream) {
+    if (GP_F16 || !q || !kc || !vc || !out || rows < 1 || C < 64 || (C % 64) || L < 1 || !al16(q) || !al16(out)) return GP_ERR_INVALID;
+    launch_c_cross_attn_small(q, kc, vc, (h16_t*)out, rows, C, L, (hipStream_t)stream);
+    return GP_LAUNCHED();
+}
+
+gp_status gp_c_bilinear(const float* in, float* out, int B, int Hi, int Wi, int Ho, int Wo, int C, int align_corners, void* stream) {
+    if (GP_F16 || !in || !out || B < 1 || Hi < 1 || Wi < 1 || Ho < 1 || Wo < 1 || C < 4 || (C % 4) || !al16(in) || !al16(out)) return GP_ERR_INVALID;
+    launch_c_bilinear(in, out, B, Hi, Wi, Ho, Wo, C, align_corners, (hipStream_t)stream);
+    return GP_LAUNCHED();
+}
+
 }  // extern "C"

@@ -122,7 +122,8 @@ int igemm_last_path(int* pgemm_rows);  // igemm_path of this host thread's last 
 // mode 2 = *bm rows per image, each with its own pixel count appended after the [rows][N][2] sums; returns the number of rows (callers
 // allocate rows * (2 N + 1) floats), or 0 when that kernel path cannot produce stats_out (direct epilogue, GEGLU, fp32 output, ...).
 int igemm_tile_info(const IGemmParams& p, int tile_hint, int* mode, int* bm);
-// scale/shift from per-tile channel partials written by a conv epilogue (instead of launch_groupnorm_stats)
+// scale/shift from per-tile channel partials written by a conv epilogue (instead of launch_groupnorm_stats); modes 3 / 4 = the layouts of modes
+// 2 / 0 with {sum, CENTRED second moment about the tile's mean} partials (launch_c_gn_stats / launch_concat_stats)
 void launch_groupnorm_from_partials(const float* partials, int mode, int bm, int B, int H, int W, int C, int G, float eps, const float* gamma,
                                     const float* beta, float* scale, float* shift, hipStream_t s);
 
@@ -177,13 +178,15 @@ void launch_softmax_rows_f16(const void* in_f16, h16_t* out, int rows, int T, in
 // Elementwise / layout kernels
 void launch_rgb_prologue(const void* rgb, int is_u8, h16_t* out, int B, int H, int W, int Cpad, hipStream_t s);  // NCHW -> NHWC, x/255*2-1
 // fused RGB prologue + VAE-encoder conv_in (3 -> Cout, Cout % 32 == 0) + GroupNorm partial statistics (16x16 tiles) of the output
-int rgb_conv_in_rows(int B, int H, int W);  // statistics rows per image launch_rgb_conv_in writes (mode 2: sums + pixel counts)
+int rgb_conv_in_rows(int B, int H, int W);  // statistics rows per image launch_rgb_conv_in writes (RGB_CONV_IN_STATS_MODE: {sum, centred M2} + pixel counts)
+enum { RGB_CONV_IN_STATS_MODE = 3 };
 void launch_pack_k27(const h16_t* wt, int ldw, int Cout, h16_t* w27, hipStream_t s);  // [rows][9][64] conv layout -> compact [Cout][32]
 void launch_rgb_conv_in(const void* rgb, int is_u8, const h16_t* w27, const float* bias, h16_t* out, float* stats, int B, int H, int W, int Cout,
                         hipStream_t s);
 void launch_concat(const h16_t* a, int Ca, const h16_t* b, int Cb, h16_t* out, long long pixels, hipStream_t s);
 int concat_stats_bm(long long hw, long long pixels, int channels);  // pixels per statistics tile launch_concat_stats can use for an image of hw pixels (0: none)
 void launch_concat_stats(const h16_t* a, int Ca, const h16_t* b, int Cb, h16_t* out, long long pixels, int bm, float* part, hipStream_t s);
+enum { CONCAT_STATS_MODE = 4 };  // what launch_groupnorm_from_partials takes for launch_concat_stats' partials: mode 0's tiling, {sum, centred M2}
 struct DdimCoef { float x0_sample, x0_model, eps_sample, eps_model, prev_x0, prev_eps, clip; };
 void launch_ddim_init(const float* noise_nchw, h16_t* lat, float* sample, int B, int H, int W, int L, int ld, int off, hipStream_t s);
 void launch_ddim_step(const h16_t* model, int ldm, float* sample, h16_t* uin, int ldu, int off, h16_t* x0_out, int ldx, long long pixels, int L,

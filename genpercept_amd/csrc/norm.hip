@@ -386,7 +386,8 @@ void launch_groupnorm(const h16_t* x, h16_t* y, const float* gamma, const float*
 // One workgroup per (group, image): 256 threads walk the group's (tile, channel) partials in a fixed order; tile pixel counts
 // come from the tiling (mode 0: bm consecutive rows; mode 1: 16x16 tiles clipped at the image edge; mode 2: bm rows per image with their
 // counts stored after the partials); Chan-combined variance.  Partials are {sum, sum of squares} in modes 0-2; mode 3 has mode 2's layout
-// with {sum, CENTRED second moment} partials (contract.hip: c_gn_stats_kernel), free of the qk - sk * mk cancellation.
+// with {sum, CENTRED second moment} partials (contract.hip: c_gn_stats_kernel), free of the qk - sk * mk cancellation; mode 4 is the same
+// for mode 0's layout (elementwise.hip: concat_stats_kernel).
 __global__ __launch_bounds__(256) void gn_finalize_tiles_kernel(const float* __restrict__ part, int mode, int bm, int H, int W, int C, int G,
                                                                  float eps, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                  float* __restrict__ scale, float* __restrict__ shift) {
@@ -395,8 +396,8 @@ __global__ __launch_bounds__(256) void gn_finalize_tiles_kernel(const float* __r
     const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int cpg = C / G;
     const int tiles_x = (W + 15) >> 4, tiles_y = (H + 15) >> 4;
-    const bool centred = mode == 3;
-    if (centred) mode = 2;
+    const bool centred = mode == 3 || mode == 4;
+    if (centred) mode = mode == 3 ? 2 : 0;
     const int ntile = mode == 2 ? bm : mode ? tiles_x * tiles_y : (H * W) / bm;
     const float* pb = part + (long long)b * ntile * C * 2;
     const float* cnt = part + (long long)gridDim.y * ntile * C * 2 + (long long)b * ntile;  // mode 2: pixel count of every row

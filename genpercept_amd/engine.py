@@ -160,6 +160,27 @@ SYMBOLS = {
     "gp_softmax_rows": (_i, [_vp, _vp, _i, _i, _i, _f, _vp]),
     "gp_softmax_rows_f16": (_i, [_vp, _vp, _i, _i, _i, _f, _vp]),
     "gp_bilinear": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "gp_rgb_prologue": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
+    "gp_concat": (_i, [_vp, _i, _vp, _i, _vp, _ll, _i, _vp]),
+    "gp_concat_stats_bm": (_i, [_ll, _ll, _i]),
+    "gp_concat_stats": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, C.POINTER(_i), _vp, _vp, _i, _f, _vp, _vp, _vp]),
+    "gp_rgb_conv_in_stats": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _vp]),
+    "gp_nchw_to_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "gp_nhwc_to_nchw": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "gp_ddim_init": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "gp_ddim_update": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _i, _ll, _i, C.POINTER(_f), _i, _vp]),
+    "gp_decode_epilogue": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "gp_scale_pad": (_i, [_vp, _vp, _ll, _i, _i, _i, _f, _vp]),
+    "gp_pointwise_small": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _f, _i, _vp]),
+    "gp_relu": (_i, [_vp, _vp, _ll, _vp]),
+    "gp_add": (_i, [_vp, _vp, _vp, _ll, _i, _vp]),
+    "gp_dpt_final": (_i, [_vp, _vp, _f, _vp, _i, _i, _i, _i, _vp]),
+    "gp_minmax_norm": (_i, [_vp, _i, _ll, _vp]),
+    "gp_c_heads_split": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "gp_c_heads_merge_split": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "gp_c_cross_fold": (_i, [_vp] * 9 + [_i, _i, _i, _f, _vp]),
+    "gp_c_cross_attention": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "gp_c_bilinear": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
 }
 
 
@@ -1029,4 +1050,170 @@ def bilinear(x_nhwc: torch.Tensor, out_hw, align_corners: bool) -> torch.Tensor:
     st = lib.gp_bilinear(x_nhwc.data_ptr(), out.data_ptr(), b, h, w, out_hw[0], out_hw[1], c, int(align_corners), _stream_ptr())
     if st != GP_OK:
         raise RuntimeError(f"gp_bilinear failed ({st})")
+    return out
+
+
+# ---- the elementwise / layout kernels (tests/test_kernels_glue_*.py).  Thin: the caller owns every buffer, so that a test can prefill a
+# destination and see what a kernel leaves alone.  contract=True runs the fp32 twin of the contract precision (bf16 library). -------------------
+DDIM_COEF = ("x0_sample", "x0_model", "eps_sample", "eps_model", "prev_x0", "prev_eps", "clip")
+
+
+def _glue(name: str, contract: bool = False):
+    lib = load_library("bf16" if contract else None)
+    fn = getattr(lib, name)
+
+    def call(*args):
+        st = fn(*args)
+        if st != GP_OK:
+            raise RuntimeError(f"{name} failed ({st})")
+    return call
+
+
+def rgb_prologue(rgb: torch.Tensor, out: torch.Tensor, cpad: int, contract: bool = False):
+    b, _, h, w = rgb.shape
+    _glue("gp_rgb_prologue", contract)(rgb.data_ptr(), int(rgb.dtype == torch.uint8), out.data_ptr(), b, h, w, cpad, int(contract), _stream_ptr(rgb.device))
+    return out
+
+
+def concat(a: torch.Tensor, b: torch.Tensor, contract: bool = False) -> torch.Tensor:
+    """a [pixels, Ca], b [pixels, Cb] contiguous -> [pixels, Ca + Cb]"""
+    out = torch.empty((a.shape[0], a.shape[1] + b.shape[1]), dtype=a.dtype, device=a.device)
+    _glue("gp_concat", contract)(a.data_ptr(), a.shape[1], b.data_ptr(), b.shape[1], out.data_ptr(), a.shape[0], int(contract), _stream_ptr(a.device))
+    return out
+
+
+def concat_stats_bm(hw: int, pixels: int, channels: int) -> int:
+    return int(load_library().gp_concat_stats_bm(hw, pixels, channels))
+
+
+def concat_stats(a: torch.Tensor, b: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, eps: float, bm: int = 0):
+    """a [B, HW, Ca], b [B, HW, Cb] -> (out [B, HW, Ca + Cb], scale [B, C], shift [B, C], bm used)"""
+    bsz, hw, ca = a.shape
+    c = ca + b.shape[2]
+    out = torch.empty((bsz, hw, c), dtype=a.dtype, device=a.device)
+    sc = torch.empty((bsz, c), dtype=torch.float32, device=a.device)
+    sh = torch.empty_like(sc)
+    used = C.c_int(0)
+    _glue("gp_concat_stats")(a.data_ptr(), ca, b.data_ptr(), b.shape[2], out.data_ptr(), bsz, hw, bm, C.byref(used), gamma.data_ptr(), beta.data_ptr(), groups,
+                             float(eps), sc.data_ptr(), sh.data_ptr(), _stream_ptr(a.device))
+    return out, sc, sh, int(used.value)
+
+
+def rgb_conv_in_stats(rgb: torch.Tensor, w_packed: torch.Tensor, bias, cout: int, gamma: torch.Tensor, beta: torch.Tensor, groups: int, eps: float):
+    b, _, h, w = rgb.shape
+    rgb = rgb.contiguous()
+    out = torch.empty((b, h, w, cout), dtype=act_dtype(), device=rgb.device)
+    sc = torch.empty((b, cout), dtype=torch.float32, device=rgb.device)
+    sh = torch.empty_like(sc)
+    _glue("gp_rgb_conv_in_stats")(rgb.data_ptr(), int(rgb.dtype == torch.uint8), w_packed.data_ptr(), _ptr(bias), out.data_ptr(), b, h, w, cout, gamma.data_ptr(),
+                                  beta.data_ptr(), groups, float(eps), sc.data_ptr(), sh.data_ptr(), _stream_ptr(rgb.device))
+    return out, sc, sh
+
+
+def nchw_to_nhwc(x: torch.Tensor, out: torch.Tensor, cpad: int, contract: bool = False):
+    b, c, h, w = x.shape
+    _glue("gp_nchw_to_nhwc", contract)(x.data_ptr(), out.data_ptr(), b, c, h, w, cpad, int(contract), _stream_ptr(x.device))
+    return out
+
+
+def nhwc_to_nchw(x: torch.Tensor, b: int, c: int, h: int, w: int, ld: int, contract: bool = False) -> torch.Tensor:
+    out = torch.empty((b, c, h, w), dtype=torch.float32, device=x.device)
+    _glue("gp_nhwc_to_nchw", contract)(x.data_ptr(), out.data_ptr(), b, c, h, w, ld, int(contract), _stream_ptr(x.device))
+    return out
+
+
+def ddim_init(noise: Optional[torch.Tensor], lat: torch.Tensor, sample: torch.Tensor, b: int, h: int, w: int, L: int, ld: int, off: int, contract: bool = False):
+    _glue("gp_ddim_init", contract)(_ptr(noise), lat.data_ptr(), sample.data_ptr(), b, h, w, L, ld, off, int(contract), _stream_ptr(lat.device))
+
+
+def ddim_update(model: torch.Tensor, ldm: int, sample: torch.Tensor, uin: torch.Tensor, ldu: int, off: int, x0_out: Optional[torch.Tensor], ldx: int, pixels: int,
+                L: int, coef: dict, contract: bool = False):
+    k = (C.c_float * 7)(*[float(coef[n]) for n in DDIM_COEF])
+    _glue("gp_ddim_update", contract)(model.data_ptr(), ldm, sample.data_ptr(), uin.data_ptr(), ldu, off, _ptr(x0_out), ldx, pixels, L, k, int(contract),
+                                      _stream_ptr(model.device))
+
+
+def decode_epilogue(x: torch.Tensor, b: int, h: int, w: int, ld: int, mean3: bool, raw: bool, out: torch.Tensor, contract: bool = False):
+    _glue("gp_decode_epilogue", contract)(x.data_ptr(), out.data_ptr(), b, h, w, ld, int(mean3), int(raw), int(contract), _stream_ptr(x.device))
+    return out
+
+
+def scale_pad(x: torch.Tensor, out: torch.Tensor, pixels: int, c: int, ldi: int, ldo: int, scale: float):
+    _glue("gp_scale_pad")(x.data_ptr(), out.data_ptr(), pixels, c, ldi, ldo, float(scale), _stream_ptr(x.device))
+    return out
+
+
+def pointwise_small(x: torch.Tensor, out: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], pixels: int, ldi: int, ldo: int, in_scale: float,
+                    contract: bool = False):
+    cout, cin = w.shape
+    _glue("gp_pointwise_small", contract)(x.data_ptr(), out.data_ptr(), w.data_ptr(), _ptr(bias), pixels, cin, cout, ldi, ldo, float(in_scale), int(contract),
+                                          _stream_ptr(x.device))
+    return out
+
+
+def relu(x: torch.Tensor) -> torch.Tensor:
+    out = torch.empty_like(x)
+    _glue("gp_relu")(x.data_ptr(), out.data_ptr(), x.numel(), _stream_ptr(x.device))
+    return out
+
+
+def add(a: torch.Tensor, b: torch.Tensor, contract: bool = False) -> torch.Tensor:
+    out = torch.empty_like(a)
+    _glue("gp_add", contract)(a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), int(contract), _stream_ptr(a.device))
+    return out
+
+
+def dpt_final(x: torch.Tensor, w: torch.Tensor, bias: float, contract: bool = False) -> torch.Tensor:
+    """x [B, HW, Cin] -> fp32 [B, HW]"""
+    b, hw, cin = x.shape
+    out = torch.empty((b, hw), dtype=torch.float32, device=x.device)
+    _glue("gp_dpt_final", contract)(x.data_ptr(), w.data_ptr(), float(bias), out.data_ptr(), b, hw, cin, int(contract), _stream_ptr(x.device))
+    return out
+
+
+def minmax_norm(x: torch.Tensor) -> torch.Tensor:
+    """x fp32 [B, n] -> per-image (x - min) / (max - min) (a copy; the kernel works in place)"""
+    y = x.clone()
+    _glue("gp_minmax_norm")(y.data_ptr(), y.shape[0], y.shape[1], _stream_ptr(x.device))
+    return y
+
+
+def c_heads_split(qkv: torch.Tensor, batch: int, tokens: int, heads: int, hd: int, vts: torch.Tensor):
+    """qkv fp32 [B*T, ld]; vts = the caller's (prefilled) [B*heads, hd, 3 Tpad] -> (Qs, Ks [B*heads, T, 3 hd], vts)"""
+    qs = torch.empty((batch * heads, tokens, 3 * hd), dtype=torch.bfloat16, device=qkv.device)
+    ks = torch.empty_like(qs)
+    _glue("gp_c_heads_split", True)(qkv.data_ptr(), qkv.stride(0), qs.data_ptr(), ks.data_ptr(), vts.data_ptr(), batch, tokens, vts.shape[2] // 3, heads, hd,
+                                    _stream_ptr(qkv.device))
+    return qs, ks, vts
+
+
+def c_heads_merge_split(o: torch.Tensor, batch: int, heads: int) -> torch.Tensor:
+    """O fp32 [B*heads, T, hd] -> A-order split [B*T, 3 heads hd]"""
+    _, t, hd = o.shape
+    out = torch.empty((batch * t, 3 * heads * hd), dtype=torch.bfloat16, device=o.device)
+    _glue("gp_c_heads_merge_split", True)(o.data_ptr(), out.data_ptr(), batch, t, heads, hd, _stream_ptr(o.device))
+    return out
+
+
+def c_cross_fold(y: torch.Tensor, U: torch.Tensor, u0: torch.Tensor, G: torch.Tensor, c0: torch.Tensor, g3: torch.Tensor, b3: torch.Tensor, want_n3: bool = True,
+                 eps: float = 1e-5):
+    rows, c = y.shape
+    y_out = torch.empty_like(y)
+    n3 = torch.empty((rows, 3 * c), dtype=torch.bfloat16, device=y.device) if want_n3 else None
+    _glue("gp_c_cross_fold", True)(y.data_ptr(), y_out.data_ptr(), _ptr(n3), U.data_ptr(), u0.data_ptr(), G.data_ptr(), c0.data_ptr(), g3.data_ptr(), b3.data_ptr(),
+                                   rows, c, U.shape[0], float(eps), _stream_ptr(y.device))
+    return y_out, n3
+
+
+def c_cross_attention(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor) -> torch.Tensor:
+    rows, c = q.shape
+    out = torch.empty((rows, 3 * c), dtype=torch.bfloat16, device=q.device)
+    _glue("gp_c_cross_attention", True)(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(), rows, c, kc.shape[0], _stream_ptr(q.device))
+    return out
+
+
+def c_bilinear(x_nhwc: torch.Tensor, out_hw, align_corners: bool) -> torch.Tensor:
+    b, h, w, c = x_nhwc.shape
+    out = torch.empty((b, out_hw[0], out_hw[1], c), dtype=torch.float32, device=x_nhwc.device)
+    _glue("gp_c_bilinear", True)(x_nhwc.data_ptr(), out.data_ptr(), b, h, w, out_hw[0], out_hw[1], c, int(align_corners), _stream_ptr(x_nhwc.device))
     return out

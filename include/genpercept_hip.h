@@ -362,6 +362,60 @@ gp_status gp_softmax_rows(const float* in, void* out, int rows, int T, int ld, f
 gp_status gp_softmax_rows_f16(const void* in_f16, void* out, int rows, int T, int ld, float scale, void* stream);
 gp_status gp_bilinear(const void* in, void* out, int B, int Hi, int Wi, int Ho, int Wo, int C, int align_corners, void* stream);
 
+/* ---- test entry points of the elementwise / layout kernels between the matrix products (csrc/elementwise.hip) and, with contract != 0, of their
+ * fp32 twins of the contract precision (csrc/contract.hip; bf16 library only, GP_ERR_INVALID from the fp16 library).  Stateless, on the
+ * caller's stream, DEVICE pointers; "16-bit" = this library's element type.  Whatever a kernel would fault on is refused with GP_ERR_INVALID
+ * before any HIP call: null pointers, pointers that are not 16-byte aligned where the kernel moves 16-byte vectors, channel counts that are
+ * no multiple of the vector (8 elements, fp32 twins 4), strides smaller than what is read or written.
+ * gp_rgb_prologue: rgb [B][3][H][W] (uint8, or float in [-1, 1]) -> 16-bit NHWC [B*H*W][Cpad], x / 255 * 2 - 1 in fp32 in that order, channels
+ *   3 .. Cpad-1 zero (Cpad % 8 == 0); contract: the A-order split operand [B*H*W][192] of 64 logical channels (Cpad must be 64).
+ * gp_concat: out[p] = [a[p][0..Ca) | b[p][0..Cb)] (the UNet's [hidden, skip]).
+ * gp_concat_stats: the same copy (16-bit only) that also leaves per-(bm pixels, channel) GroupNorm partials; bm = 0 takes gp_concat_stats_bm's
+ *   choice, *bm_used (optional) reports it, HW % bm == 0 is required.  With gamma non-null the partials are finalised to scale / shift [B][C] as
+ *   gp_conv2d_stats does.  gp_concat_stats_bm: host arithmetic, 0 = no tile size divides hw.
+ * gp_rgb_conv_in_stats: gp_rgb_conv_in with the statistics rows its persistent workgroups leave, finalised to scale / shift [B][Cout].
+ * gp_nchw_to_nhwc: fp32 NCHW -> NHWC [B*H*W][Cpad] (16-bit, or fp32 with contract), channels >= C zero.  gp_nhwc_to_nchw: NHWC rows of stride ld -> fp32 NCHW.
+ * gp_ddim_init / gp_ddim_update: the state kernels of the multi-step archs.  init: sample [B*H*W][L] fp32 = noise (NCHW) and lat[p][off .. off+L) =
+ *   its copy in the tensor's type, or with noise null sample = lat[p][0..L) widened; off + L <= ld.  update: one scheduler step in the affine form
+ *   of gp_ddim_step, coef7_host = HOST {x0_sample, x0_model, eps_sample, eps_model, prev_x0, prev_eps, clip}; model rows of stride ldm, the new
+ *   sample also into uin[p][off .. off+L) (stride ldu, off + L <= ldu) and x0 into x0_out[p][0..L) (optional, stride ldx).
+ * gp_decode_epilogue: NHWC (3 real channels, stride ld; 16-bit: ld % 4 == 0 and an 8-byte aligned tensor) -> fp32 NCHW [B][mean3 ? 1 : 3][H][W],
+ *   channel mean, then unless raw clip(-1, 1), + 1, * 0.5.
+ * gp_scale_pad: out[p][0..ldo) = {in[p][0..C) * scale, 0 ...}.  gp_pointwise_small: out[p][0..ldo) = {W (in[p][0..Cin) * in_scale) + bias, 0 ...},
+ *   W [Cout][Cin] fp32, 1 <= Cin, Cout <= 8, bias optional.  gp_relu, gp_add: n elements, n % 8 == 0 (fp32 gp_add: % 4).
+ * gp_dpt_final: out[p] = sum_c w[c] in[p][c] + bias, fp32 out.  gp_minmax_norm: x[b][0..n) <- (x - min_b) / (max_b - min_b) in place, per image. */
+gp_status gp_rgb_prologue(const void* rgb, int is_u8, void* out, int B, int H, int W, int Cpad, int contract, void* stream);
+gp_status gp_concat(const void* a, int Ca, const void* b, int Cb, void* out, long long pixels, int contract, void* stream);
+int gp_concat_stats_bm(long long hw, long long pixels, int channels);
+gp_status gp_concat_stats(const void* a, int Ca, const void* b, int Cb, void* out, int B, int HW, int bm, int* bm_used, const float* gamma, const float* beta,
+                          int groups, float eps, float* scale_out, float* shift_out, void* stream);
+gp_status gp_rgb_conv_in_stats(const void* rgb, int is_u8, const void* w_packed, const float* bias, void* out, int B, int H, int W, int Cout, const float* gamma,
+                               const float* beta, int groups, float eps, float* scale_out, float* shift_out, void* stream);
+gp_status gp_nchw_to_nhwc(const float* in, void* out, int B, int C, int H, int W, int Cpad, int contract, void* stream);
+gp_status gp_nhwc_to_nchw(const void* in, float* out, int B, int C, int H, int W, int ld, int contract, void* stream);
+gp_status gp_ddim_init(const float* noise_nchw, void* lat, float* sample, int B, int H, int W, int L, int ld, int off, int contract, void* stream);
+gp_status gp_ddim_update(const void* model, int ldm, float* sample, void* uin, int ldu, int off, void* x0_out, int ldx, long long pixels, int L,
+                         const float* coef7_host, int contract, void* stream);
+gp_status gp_decode_epilogue(const void* in, float* out, int B, int H, int W, int ld, int mean3, int raw, int contract, void* stream);
+gp_status gp_scale_pad(const void* in, void* out, long long pixels, int C, int ldi, int ldo, float scale, void* stream);
+gp_status gp_pointwise_small(const void* in, void* out, const float* w, const float* bias, long long pixels, int Cin, int Cout, int ldi, int ldo, float in_scale,
+                             int contract, void* stream);
+gp_status gp_relu(const void* in, void* out, long long n, void* stream);
+gp_status gp_add(const void* a, const void* b, void* out, long long n, int contract, void* stream);
+gp_status gp_dpt_final(const void* in, const float* w, float bias, float* out, int B, int HW, int Cin, int contract, void* stream);
+gp_status gp_minmax_norm(float* x, int B, long long n, void* stream);
+/* contract precision only (bf16 library).  gp_c_heads_split: qkv fp32 [B*T][ld] (q | k | v at columns 0 | C | 2C, C = heads * hd) -> Qs [B*heads][T][3 hd]
+ * A order, Ks the same in B order, Vts [B*heads][hd][3 Tpad] B order, V TRANSPOSED, zero in [T, Tpad); hd % 64 == 0, Tpad % 64 == 0, Tpad >= T.
+ * gp_c_heads_merge_split: O fp32 [B*heads][T][hd] -> A-order split [B*T][3 heads hd].  gp_c_cross_fold: gp_cross_attention_fold on fp32 rows (C % 8 == 0,
+ * C <= 2048), n3_out the A-order split of LayerNorm(y_out).  gp_c_cross_attention: gp_cross_attention on fp32 q, A-order split out.  gp_c_bilinear:
+ * gp_bilinear on fp32 NHWC (C % 4 == 0). */
+gp_status gp_c_heads_split(const float* qkv, int ld, void* Qs, void* Ks, void* Vts, int B, int T, int Tpad, int heads, int hd, void* stream);
+gp_status gp_c_heads_merge_split(const float* O, void* out, int B, int T, int heads, int hd, void* stream);
+gp_status gp_c_cross_fold(const float* y, float* y_out, void* n3_out, const float* U, const float* u0, const float* G, const float* c0, const float* g3,
+                          const float* b3, int rows, int C, int heads, float eps, void* stream);
+gp_status gp_c_cross_attention(const float* q, const float* kc, const float* vc, void* out, int rows, int C, int L, void* stream);
+gp_status gp_c_bilinear(const float* in, float* out, int B, int Hi, int Wi, int Ho, int Wo, int C, int align_corners, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

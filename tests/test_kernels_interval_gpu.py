@@ -24,8 +24,8 @@ stays within HALF of every gate and that the nearest wrong variants fall outside
 
 Out of scope: the outputs of gp_conv2d_gn and gp_decoder_tail (the normalised operand is rounded to 16 bits before an MFMA; a rounding flip
 there moves the output by ulp16 * |w|, which no per-element interval expresses -- their statistics come from the launch_groupnorm_stats
-tested here), gp_bilinear, pre / post processing, the unfused VAE attention chain, and the elementwise kernels without an entry point of
-their own (concat_stats, the DDIM step: they need new C-ABI entries first).
+tested here), gp_bilinear, pre / post processing and the unfused VAE attention chain.  The elementwise and layout kernels (concat and its
+statistics, the DDIM state kernels, the prologue / epilogue and layout kernels) are in tests/test_kernels_glue_gpu.py.
 """
 import math
 import zlib
