@@ -7,6 +7,12 @@
 // new_stored / new_product_input allocate the form the precision uses, conv / linear pick `.p` or `.f` of their input, residual and in-place target,
 // and each kernel pair (X / c_X) is chosen in one small op.  Only attention_c, the split-operand attention, has no 16-bit twin.
 //
+// Lifetime: every activation and scratch buffer is a Pool::Buf (pool.h), a move-only owner that hands its buffer back to the pool when it ends; an
+// `Act` owns its tensor and its statistics partials, and whatever only reads one takes `const Act&`.  The pool recycles a buffer as soon as it is
+// back, so WHERE an owner ends relative to the allocations around it sets the pool's high-water mark: the schedules end an owner early with
+// reset() or a nested block, and write `h = f(h)` for a layer that replaces its input (f(h) is evaluated first, then the old h released).
+// A stage that throws returns its buffers by unwinding; every entry point ends with nothing outstanding (finish_call checks it).
+//
 // Control flow mirrors (never copies) the reference: genpercept/genpercept_pipeline.py:399-526 (single_infer,
 // encode_rgb, decode_pred), genpercept/models/custom_unet.py:109-119,146-170,273,305-415 (UNet forward, skip order,
 // upsample_size, multi_level_feats), genpercept/models/dpt_head.py:213-335,443-582 (DPT neck/head); module internals
@@ -30,6 +36,7 @@
 #include "../../include/genpercept_hip.h"
 #include "host_pack.h"
 #include "igemm_problem.h"
+#include "pool.h"
 
 namespace {
 
@@ -41,53 +48,30 @@ struct HostTensor {
     int64_t numel() const { int64_t n = 1; for (auto s : shape) n *= s; return n; }
 };
 
-struct Pool {
-    std::multimap<size_t, void*> free_;
-    std::unordered_map<void*, size_t> size_;
-    std::unordered_map<void*, int> live_;  // buffers handed out and not yet returned (an aborted call returns them all: release_live)
-    size_t total = 0;
-    void* alloc(size_t bytes) {
-        bytes = (bytes + 255) & ~(size_t)255;
-        auto it = free_.lower_bound(bytes);
-        void* p = nullptr;
-        if (it != free_.end() && it->first <= bytes * 2 + (1u << 20)) {
-            p = it->second;
-            free_.erase(it);
-        } else {
-            HIPCHK(hipMalloc(&p, bytes));
-            size_[p] = bytes;
-            total += bytes;
-        }
-        live_[p] = 1;
-        return p;
-    }
-    void release(void* p) {
-        if (!p) return;
-        if (!live_.erase(p)) return;  // not outstanding (already returned by release_live)
-        free_.insert({size_.at(p), p});
-    }
-    void release_live() {
-        for (auto& kv : live_) free_.insert({size_.at(kv.first), kv.first});
-        live_.clear();
-    }
-    void destroy() {
-        for (auto& kv : size_) hipFree(kv.first);
-        size_.clear();
-        free_.clear();
-        live_.clear();
-    }
-};
+// the pool's device allocator (pool.h takes it as two function pointers)
+void* device_alloc(size_t bytes) {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, bytes));
+    return p;
+}
+void device_free(void* p) { (void)hipFree(p); }
 
+// An activation: move-only owner of its tensor and of the statistics partials that go with it; both go back to the pool when it ends or at reset().
 struct Act {
-    h16_t* p = nullptr;
-    // contract precision (contract.hip): a STORED tensor is fp32 (`f`, C channels per pixel); a matrix-product operand is a split tensor (`p`, with
-    // C = 3 x the logical width: [hi | lo | hi] blocks).  Exactly one of p / f is set.
-    float* f = nullptr;
+    Pool::Buf mem;      // the tensor: 16-bit (p) or fp32 (f)
+    bool fp32 = false;
     int B = 0, H = 0, W = 0, C = 0;  // C = allocated channels (row stride)
-    // GroupNorm partial statistics written by the producing conv's epilogue ([pixel tile][C][2] fp32; owned with p)
-    float* st = nullptr;
+    // GroupNorm partial statistics written by the producing conv's epilogue ([pixel tile][C][2] fp32)
+    Pool::Buf stats;
     int st_mode = 0, st_bm = 0;
+    // contract precision (contract.hip): a STORED tensor is fp32 (`f`, C channels per pixel); a matrix-product operand is a split tensor (`p`, with
+    // C = 3 x the logical width: [hi | lo | hi] blocks).  Exactly one of p / f is set; neither in an empty Act.
+    h16_t* p() const { return fp32 ? nullptr : mem.get<h16_t>(); }
+    float* f() const { return fp32 ? mem.get<float>() : nullptr; }
+    void* data() const { return mem.get<void>(); }
+    float* st() const { return stats.get<float>(); }
     long long pixels() const { return (long long)B * H * W; }
+    void reset() { mem.reset(); stats.reset(); }
 };
 
 struct NormW {
@@ -143,10 +127,10 @@ struct gp_engine {
     std::unordered_map<std::string, HostTensor> host;
     bool finalized = false;
     hipStream_t st = nullptr;
-    Pool pool;
+    Pool pool{device_alloc, device_free};
     std::vector<void*> weights_dev;  // everything hipMalloc'ed for weights
     h16_t* zero = nullptr;
-    float* gn_ws = nullptr;
+    Pool::Buf gn_ws;  // GroupNorm workspace, kept across calls (declared after the pool: it goes back before the pool frees its buffers)
     size_t gn_ws_floats = 0;
     hipStream_t last_stream = nullptr;  // the pool recycles buffers in stream order: a change of stream is fenced (check_ready)
     bool stream_seen = false;
@@ -595,22 +579,15 @@ struct gp_engine {
     Act new_act(int B, int H, int W, int C) {
         Act a;
         a.B = B; a.H = H; a.W = W; a.C = C;
-        a.p = (h16_t*)pool.alloc((size_t)B * H * W * C * sizeof(h16_t));
+        a.mem = pool.alloc((size_t)B * H * W * C * sizeof(h16_t));
         return a;
-    }
-    void drop(Act& a) {
-        pool.release(a.p);
-        pool.release(a.f);
-        if (a.st) pool.release(a.st);
-        a.p = nullptr;
-        a.f = nullptr;
-        a.st = nullptr;
     }
     // ---- contract precision: stored tensors (fp32) and split operands -----------------------------------------------------------------
     Act new_act_f(int B, int H, int W, int C) {
         Act a;
         a.B = B; a.H = H; a.W = W; a.C = C;
-        a.f = (float*)pool.alloc((size_t)B * H * W * C * sizeof(float));
+        a.fp32 = true;
+        a.mem = pool.alloc((size_t)B * H * W * C * sizeof(float));
         return a;
     }
     Act new_operand(int B, int H, int W, int C_logical) { return new_act(B, H, W, 3 * C_logical); }
@@ -625,13 +602,12 @@ struct gp_engine {
         if (contract) return new_operand(B, H, W, C);
         return new_act(B, H, W, C);
     }
-    static void* data(const Act& a) { return a.f ? (void*)a.f : (void*)a.p; }
     // A-order split of a stored tensor (optionally through ReLU): the operand form a conv / linear layer reads
     Act split_operand(const Act& x, int act = GP_ACT_NONE) {
-        if (!x.f) throw std::logic_error("split_operand: not a stored fp32 tensor");
+        if (!x.f()) throw std::logic_error("split_operand: not a stored fp32 tensor");
         Act y = new_operand(x.B, x.H, x.W, x.C);
         mark("split3 " + dims(x));
-        launch_c_split3(x.f, x.C, y.p, x.pixels(), x.C, 0, act, 1.0f, st);
+        launch_c_split3(x.f(), x.C, y.p(), x.pixels(), x.C, 0, act, 1.0f, st);
         return y;
     }
     // ask the kernel that is about to write `y` to leave per-tile channel statistics behind (next GroupNorm skips its read pass)
@@ -642,10 +618,10 @@ struct gp_engine {
         int mode = 0, bm = 0;
         const int nt = igemm_tile_info(p, 0, &mode, &bm);
         if (nt <= 0) return;
-        y.st = (float*)pool.alloc((size_t)nt * (p.N * 2 + 1) * sizeof(float));
+        y.stats = pool.alloc((size_t)nt * (p.N * 2 + 1) * sizeof(float));
         y.st_mode = mode;
         y.st_bm = bm;
-        p.stats_out = y.st;
+        p.stats_out = y.st();
     }
     // profiling level 3: one event before every launch; a launch's cost is the time to the next mark (kernel + the gap behind it)
     struct Mark { hipEvent_t ev; std::string name; double flops; };
@@ -700,66 +676,75 @@ struct gp_engine {
             tm.n_launches++;
         }
         IGemmParams q = p;
-        void* ws = nullptr;
+        Pool::Buf ws;
         const int S = halo ? 1 : igemm_ksplit(q, hint);
         if (S > 1) {  // split-K partial sums: from this engine's pool (stream-ordered reuse), never process-global
             q.splitk_ws_floats = (long long)S * q.M * q.n_store;
             ws = pool.alloc((size_t)q.splitk_ws_floats * sizeof(float));
-            q.splitk_ws = (float*)ws;
+            q.splitk_ws = ws.get<float>();
         }
         prof_begin(halo ? 2 : 0);
         launch_igemm(q, hint, st);
         prof_end();
-        if (ws) pool.release(ws);
     }
 
     struct ConvOpt : ConvForm {
         const Act* residual = nullptr;  // added to the output; conv fills ConvForm::res (16-bit) or the fp32 residual (contract precision) from it
         bool want_stats = false;        // the output feeds a GroupNorm
     };
-    static Nhwc nhwc(const Act& a) { return {a.p, a.B, a.H, a.W, a.C}; }
+    static Nhwc nhwc(const Act& a) { return {a.p(), a.B, a.H, a.W, a.C}; }
     ConvForm conv_form(const ConvOpt& o) const {
         ConvForm f = o;
-        if (o.residual && !contract) f.res = o.residual->p;
+        if (o.residual && !contract) f.res = o.residual->p();
         return f;
     }
-    // Contract precision, in both ops: the product reads a split operand (a stored input is split on entry and the temporary dropped after the
-    // launch), writes fp32 rows and adds an fp32 residual (igemm_contract).
+    // Contract precision, in all three ops: the product reads a split operand (a stored input is split on entry into `xs`, which ends with the
+    // op, after the launch), writes fp32 rows and adds an fp32 residual (igemm_contract).
     // in_scale / in_shift / in_silu: GroupNorm(+SiLU) applied to the staged input inside the halo conv kernel (16-bit only, see conv_gn)
     Act conv(const Act& x0, const PackedW& w, const ConvOpt& o, const float* in_scale = nullptr, const float* in_shift = nullptr, bool in_silu = false) {
-        const bool split = contract && !x0.p;
-        Act x = split ? split_operand(x0) : x0;
+        Act xs;
+        if (contract && !x0.p()) xs = split_operand(x0);
+        const Act& x = xs.data() ? xs : x0;
         IGemmParams p = igemm_conv(nhwc(x), w, conv_form(o), nullptr, zero);
-        if (contract) igemm_contract(p, o.residual ? o.residual->f : nullptr);
+        if (contract) igemm_contract(p, o.residual ? o.residual->f() : nullptr);
         Act y = new_stored(x.B, p.Ho, p.Wo, p.n_store);
-        p.out = data(y);
+        p.out = y.data();
         if (!contract) {
             p.in_scale = in_scale; p.in_shift = in_shift; p.in_silu = in_silu ? 1 : 0;
             if (in_scale && !conv_uses_halo(p, 0)) throw std::logic_error("fused GroupNorm input needs the halo conv kernel");
         }
         if (o.want_stats) attach_stats(y, p);
         run_igemm(p);
-        if (split) drop(x);
         return y;
     }
-    // y[M][N] = x[M][K] W^T (+bias) (+res), N = w.cout (GEGLU halves it); inplace: write into that tensor (it may be `res`) instead of a new one
-    Act linear(const Act& x0, const PackedW& w, const Act* res = nullptr, int act = GP_ACT_NONE, const Act* inplace = nullptr, bool want_stats = false) {
-        const bool split = contract && !x0.p;
-        Act x = split ? split_operand(x0) : x0;
-        IGemmParams p = igemm_linear(nhwc(x), w, res && !contract ? res->p : nullptr, act, nullptr, zero);
-        if (contract) igemm_contract(p, res ? res->f : nullptr);
-        Act y = inplace ? *inplace : new_stored(x.B, x.H, x.W, p.n_store);
-        p.out = data(y);
-        if (want_stats && !inplace) attach_stats(y, p);
+    // y[M][N] = x[M][K] W^T (+bias) (+res), N = w.cout (GEGLU halves it)
+    Act linear(const Act& x0, const PackedW& w, const Act* res = nullptr, int act = GP_ACT_NONE, bool want_stats = false) {
+        Act xs;
+        if (contract && !x0.p()) xs = split_operand(x0);
+        const Act& x = xs.data() ? xs : x0;
+        IGemmParams p = igemm_linear(nhwc(x), w, res && !contract ? res->p() : nullptr, act, nullptr, zero);
+        if (contract) igemm_contract(p, res ? res->f() : nullptr);
+        Act y = new_stored(x.B, x.H, x.W, p.n_store);
+        p.out = y.data();
+        if (want_stats) attach_stats(y, p);
         run_igemm(p);
-        if (split) drop(x);
         return y;
+    }
+    // y += x W^T (+bias), in place: y is the residual and the output
+    void linear_add_into(const Act& x0, const PackedW& w, const Act& y) {
+        Act xs;
+        if (contract && !x0.p()) xs = split_operand(x0);
+        const Act& x = xs.data() ? xs : x0;
+        IGemmParams p = igemm_linear(nhwc(x), w, contract ? nullptr : y.p(), GP_ACT_NONE, nullptr, zero);
+        if (contract) igemm_contract(p, y.f());
+        p.out = y.data();
+        run_igemm(p);
     }
     // V^T[b][c][t] = sum_k Wv[c][k] x[b][t][k] (+ bias[c]); zero-filled up to Tpad
-    h16_t* v_transposed(const Act& x, const PackedW& wv, int T, int Tpad) {
+    Pool::Buf v_transposed(const Act& x, const PackedW& wv, int T, int Tpad) {
         const int C = wv.cout;
-        h16_t* vt = (h16_t*)pool.alloc((size_t)x.B * C * Tpad * sizeof(h16_t));
-        const IGemmParams p = igemm_bgemm({wv.w, wv.cin_pad, 0}, {x.p, x.C, (long long)T * x.C}, {vt, Tpad, (long long)C * Tpad}, C, T, wv.cin_pad, T, Tpad, x.B,
+        Pool::Buf vt = pool.alloc((size_t)x.B * C * Tpad * sizeof(h16_t));
+        const IGemmParams p = igemm_bgemm({wv.w, wv.cin_pad, 0}, {x.p(), x.C, (long long)T * x.C}, {vt.get<h16_t>(), Tpad, (long long)C * Tpad}, C, T, wv.cin_pad, T, Tpad, x.B,
                                           wv.bias, GP_BIAS_ROW, 0, zero);
         // rows = channels (320 ... 1280), columns = tokens: 64x64 tiles when there are few tokens or the channel count is not a multiple of 128
         // (320 rows leave a 128-row tile half empty), 128x64 tiles otherwise -- measured per shape with GENPERCEPT_VT_TILE (igemm.hip: tile_hint),
@@ -775,35 +760,34 @@ struct gp_engine {
         groupnorm_ws_layout(x.B, x.H * x.W, x.C, cfg.norm_groups, ws, &scale, &shift);
         if (contract) {  // statistics pass over the fp32 tensor: centred per-row partials, Chan-combined by the tile finaliser ("mode 3")
             const int R = c_gn_stat_rows(x.H * x.W, x.C, nullptr);
-            float* part = (float*)pool.alloc((size_t)x.B * R * (2 * x.C + 1) * sizeof(float));
+            Pool::Buf part = pool.alloc((size_t)x.B * R * (2 * x.C + 1) * sizeof(float));
             mark("c_gn_stats+finalize " + dims(x), 0.0, 2);
-            launch_c_groupnorm_scale_shift(x.f, part, x.B, x.H, x.W, x.C, cfg.norm_groups, eps, n.g, n.b, scale, shift, st);
-            pool.release(part);
+            launch_c_groupnorm_scale_shift(x.f(), part.get<float>(), x.B, x.H, x.W, x.C, cfg.norm_groups, eps, n.g, n.b, scale, shift, st);
             return;
         }
-        if (x.st) {
+        if (x.st()) {
             mark("gn_finalize_tiles " + dims(x));
-            launch_groupnorm_from_partials(x.st, x.st_mode, x.st_bm, x.B, x.H, x.W, x.C, cfg.norm_groups, eps, n.g, n.b, scale, shift, st);
+            launch_groupnorm_from_partials(x.st(), x.st_mode, x.st_bm, x.B, x.H, x.W, x.C, cfg.norm_groups, eps, n.g, n.b, scale, shift, st);
         } else {
             mark("gn_stats+finalize " + dims(x), 0.0, 2);
-            launch_groupnorm_stats(x.p, n.g, n.b, x.B, x.H * x.W, x.C, cfg.norm_groups, eps, ws, scale, shift, st);
+            launch_groupnorm_stats(x.p(), n.g, n.b, x.B, x.H * x.W, x.C, cfg.norm_groups, eps, ws, scale, shift, st);
         }
     }
     // one-launch GroupNorm for small maps whose producer left no statistics behind (split-K convs of the 12x12 level, ...)
-    bool gn_small(const Act& x) const { return !contract && !x.st && groupnorm_small_applicable(x.B, x.H * x.W, x.C, cfg.norm_groups) && !gp_sw().no_gn_small; }
+    bool gn_small(const Act& x) const { return !contract && !x.st() && groupnorm_small_applicable(x.B, x.H * x.W, x.C, cfg.norm_groups) && !gp_sw().no_gn_small; }
     Act groupnorm_small(const Act& x, const NormW& n, float eps, bool silu) {
         if (x.C != n.C) throw std::logic_error("groupnorm: channel mismatch");
         Act y = new_act(x.B, x.H, x.W, x.C);
         mark("gn_small " + dims(x));
-        launch_groupnorm_small(x.p, y.p, n.g, n.b, x.B, x.H * x.W, x.C, cfg.norm_groups, eps, silu ? 1 : 0, st);
+        launch_groupnorm_small(x.p(), y.p(), n.g, n.b, x.B, x.H * x.W, x.C, cfg.norm_groups, eps, silu ? 1 : 0, st);
         return y;
     }
     // x * scale + shift (+ SiLU); the normalised tensor only ever feeds a matrix product (contract precision: written as its split operand)
     Act gn_apply(const Act& x, const float* scale, const float* shift, bool silu) {
         Act y = new_product_input(x.B, x.H, x.W, x.C);
         mark((contract ? "c_gn_apply_split " : "gn_apply ") + dims(x));
-        if (contract) launch_c_gn_apply_split(x.f, y.p, scale, shift, x.B, x.H * x.W, x.C, silu ? 1 : 0, st);
-        else launch_groupnorm_apply(x.p, y.p, scale, shift, x.B, x.H * x.W, x.C, silu ? 1 : 0, st);
+        if (contract) launch_c_gn_apply_split(x.f(), y.p(), scale, shift, x.B, x.H * x.W, x.C, silu ? 1 : 0, st);
+        else launch_groupnorm_apply(x.p(), y.p(), scale, shift, x.B, x.H * x.W, x.C, silu ? 1 : 0, st);
         return y;
     }
     Act groupnorm(const Act& x, const NormW& n, float eps, bool silu) {
@@ -815,12 +799,11 @@ struct gp_engine {
     float* gn_workspace(const Act& x) {  // partial statistics + per-(image, channel) scale / shift
         const size_t need = groupnorm_ws_layout(x.B, x.H * x.W, x.C, cfg.norm_groups);
         if (need > gn_ws_floats) {
-            if (gn_ws) { pool.live_[gn_ws] = 1; pool.release(gn_ws); }
-            gn_ws = (float*)pool.alloc(need * 4 * 2);
-            pool.live_.erase(gn_ws);  // kept across calls: not part of a call's outstanding set
+            gn_ws.reset();
+            gn_ws = pool.alloc_persistent(need * 4 * 2);
             gn_ws_floats = need * 2;
         }
-        return gn_ws;
+        return gn_ws.get<float>();
     }
     // conv(act(GroupNorm(x))): statistics pass, then the normalisation is applied either inside the conv kernel on the staged
     // input halo (conv_halo.hip) or, when that kernel does not take the layer, by the separate apply pass.
@@ -829,9 +812,7 @@ struct gp_engine {
         // conv would fuse the apply: keep the statistics path for that
         if (contract || (gn_small(x) && !conv_uses_halo(igemm_conv(nhwc(x), w, conv_form(o), nullptr, zero), 0))) {
             Act y = groupnorm(x, n, eps, silu);
-            Act out = conv(y, w, o);
-            drop(y);
-            return out;
+            return conv(y, w, o);
         }
         float *scale, *shift;
         gn_scale_shift(x, n, eps, scale, shift);
@@ -845,15 +826,13 @@ struct gp_engine {
         const bool fuse_here = slices <= gn_fuse_max_slices || x.H * x.W < gn_fuse_always_below_px;
         if (fuse_gn && fuse_here && conv_uses_halo(p, 0)) return conv(x, w, o, scale, shift, silu);
         Act y = gn_apply(x, scale, shift, silu);
-        Act out = conv(y, w, o);
-        drop(y);
-        return out;
+        return conv(y, w, o);
     }
     Act layernorm(const Act& x, const NormW& n) {
         Act y = new_product_input(x.B, x.H, x.W, x.C);
         mark((contract ? "c_layernorm_split " : "layernorm ") + dims(x));
-        if (contract) launch_c_layernorm_split(x.f, y.p, n.g, n.b, (int)x.pixels(), x.C, 1e-5f, st);
-        else launch_layernorm(x.p, y.p, n.g, n.b, (int)x.pixels(), x.C, 1e-5f, st);
+        if (contract) launch_c_layernorm_split(x.f(), y.p(), n.g, n.b, (int)x.pixels(), x.C, 1e-5f, st);
+        else launch_layernorm(x.p(), y.p(), n.g, n.b, (int)x.pixels(), x.C, 1e-5f, st);
         return y;
     }
 
@@ -862,36 +841,32 @@ struct gp_engine {
         ConvOpt o1;
         o1.want_stats = true;
         Act h = conv_gn(x, r.n1, eps, true, r.c1, o1);
-        Act sc = x;
+        Act sc;  // the shortcut's output where there is one; else x itself is the residual
         if (r.has_sc) sc = linear(x, r.sc);
         ConvOpt o;
-        o.residual = &sc;
+        o.residual = r.has_sc ? &sc : &x;
         o.want_stats = true;
-        Act y = conv_gn(h, r.n2, eps, true, r.c2, o);
-        drop(h);
-        if (r.has_sc) drop(sc);
-        return y;
+        return conv_gn(h, r.n2, eps, true, r.c2, o);
     }
 
     // GEMM -> scores in HBM -> row softmax -> GEMM (head dims other than 512, and the A/B switch GENPERCEPT_NO_FLASH512)
-    void vae_attention_unfused(const Act& qk, const h16_t* vt, Act& o, int B, int T, int Tpad, int C) {
+    void vae_attention_unfused(const Act& qk, const h16_t* vt, const Act& o, int B, int T, int Tpad, int C) {
         // logits as fp16 (11 significant bits: finer than the bf16 probabilities they turn into) halve the score traffic, the largest HBM
         // item of this path.  They are the SCALED logits (1/sqrt(C) is folded into the query projection, build_vae_attn) and the fp16
         // conversion saturates at +-65504 (epilogue.h), so an outlier row degrades to a one-hot softmax instead of inf - inf = NaN.
         // GENPERCEPT_FP32_SCORES=1 keeps fp32 (A/B)
         const bool f32_scores = gp_sw().fp32_scores;
         const bool half_scores = !f32_scores && softmax_rows_f16_supported(Tpad);
-        float* S = (float*)pool.alloc((size_t)B * T * Tpad * (half_scores ? 2 : 4));
-        run_igemm(igemm_bgemm({qk.p, 2 * C, (long long)T * 2 * C}, {qk.p + C, 2 * C, (long long)T * 2 * C}, {S, Tpad, (long long)T * Tpad}, T, T, C, T, T, B,
-                              nullptr, GP_BIAS_NONE, half_scores ? 2 : 1, zero));
-        h16_t* P = (h16_t*)pool.alloc((size_t)B * T * Tpad * sizeof(h16_t));
+        Pool::Buf S = pool.alloc((size_t)B * T * Tpad * (half_scores ? 2 : 4));
+        run_igemm(igemm_bgemm({qk.p(), 2 * C, (long long)T * 2 * C}, {qk.p() + C, 2 * C, (long long)T * 2 * C}, {S.get<float>(), Tpad, (long long)T * Tpad}, T, T, C,
+                              T, T, B, nullptr, GP_BIAS_NONE, half_scores ? 2 : 1, zero));
+        Pool::Buf P = pool.alloc((size_t)B * T * Tpad * sizeof(h16_t));
         mark("softmax_rows T=" + std::to_string(T));
-        if (half_scores) launch_softmax_rows_f16(S, P, B * T, T, Tpad, 1.0f, st);
-        else launch_softmax_rows(S, P, B * T, T, Tpad, 1.0f, st);
-        pool.release(S);
-        run_igemm(igemm_bgemm({P, Tpad, (long long)T * Tpad}, {vt, Tpad, (long long)C * Tpad}, {o.p, C, (long long)T * C}, T, C, Tpad, C, C, B, nullptr,
-                              GP_BIAS_NONE, 0, zero));
-        pool.release(P);
+        if (half_scores) launch_softmax_rows_f16(S.get<float>(), P.get<h16_t>(), B * T, T, Tpad, 1.0f, st);
+        else launch_softmax_rows(S.get<float>(), P.get<h16_t>(), B * T, T, Tpad, 1.0f, st);
+        S.reset();
+        run_igemm(igemm_bgemm({P.get<h16_t>(), Tpad, (long long)T * Tpad}, {vt, Tpad, (long long)C * Tpad}, {o.p(), C, (long long)T * C}, T, C, Tpad, C, C, B,
+                              nullptr, GP_BIAS_NONE, 0, zero));
     }
 
     // contract precision: softmax(scale q k^T) v per head with fp32 logits in HBM (head split -> batched logits GEMM -> row softmax -> batched
@@ -902,127 +877,102 @@ struct gp_engine {
         const int B = qkv.B, T = qkv.H * qkv.W, Tpad = round_up(T, 64), Z = B * heads;
         if (hd % 64 || qkv.C != 3 * heads * hd) throw std::logic_error("attention_c: layout");
         const int path = c_attention_plan(B, T, heads, hd, nullptr);
-        if (path == C_ATTN_FLASH512) {  // one head of 512 (the VAE), fused: no logits in HBM, 6 KiB of planes per token (attention.hip)
-            h16_t* qk_hi = (h16_t*)pool.alloc((size_t)B * T * 2 * hd * sizeof(h16_t));
-            h16_t* qk_lo = (h16_t*)pool.alloc((size_t)B * T * 2 * hd * sizeof(h16_t));
-            h16_t* vt_hi = (h16_t*)pool.alloc((size_t)B * hd * Tpad * sizeof(h16_t));
-            h16_t* vt_lo = (h16_t*)pool.alloc((size_t)B * hd * Tpad * sizeof(h16_t));
-            mark("c_qkv_planes T=" + std::to_string(T) + " heads=1", 0.0, 2);
-            launch_c_qkv_planes(qkv.f, qkv.C, qk_hi, qk_lo, vt_hi, vt_lo, B, T, Tpad, 1, hd, st);
-            Act a = new_operand(qkv.B, qkv.H, qkv.W, hd);
-            const double fl = 4.0 * Z * (double)T * T * hd;
-            tm.flops_attn += fl;
-            tm.n_attn++;
-            mark("flash_attn512_split T=" + std::to_string(T), fl);
-            prof_begin(1);
-            launch_flash_attn512_split(qk_hi, qk_lo, vt_hi, vt_lo, a.p, B, T, Tpad, scale, st);
-            prof_end();
-            pool.release(qk_hi); pool.release(qk_lo); pool.release(vt_hi); pool.release(vt_lo);
-            return a;
-        }
-        if (path == C_ATTN_FLASH64) {  // flash attention over split operands (attention.hip)
-            if (scale != 0.125f) throw std::logic_error("attention_c: the split flash kernel computes softmax(q k^T / 8), scale must be 0.125");
+        if (path == C_ATTN_FLASH512 || path == C_ATTN_FLASH64) {
+            // fused over hi / lo planes of q | k and of V^T, no logits in HBM (attention.hip): flash_attn512_split for one head of 512 (the VAE,
+            // 6 KiB of planes per token), flash_attn64_split for heads of 64
+            const bool f512 = path == C_ATTN_FLASH512;
+            if (!f512 && scale != 0.125f) throw std::logic_error("attention_c: the split flash kernel computes softmax(q k^T / 8), scale must be 0.125");
             const int C = heads * hd;
-            h16_t* qk_hi = (h16_t*)pool.alloc((size_t)B * T * 2 * C * sizeof(h16_t));
-            h16_t* qk_lo = (h16_t*)pool.alloc((size_t)B * T * 2 * C * sizeof(h16_t));
-            h16_t* vt_hi = (h16_t*)pool.alloc((size_t)Z * hd * Tpad * sizeof(h16_t));
-            h16_t* vt_lo = (h16_t*)pool.alloc((size_t)Z * hd * Tpad * sizeof(h16_t));
+            Pool::Buf qk_hi = pool.alloc((size_t)B * T * 2 * C * sizeof(h16_t));
+            Pool::Buf qk_lo = pool.alloc((size_t)B * T * 2 * C * sizeof(h16_t));
+            Pool::Buf vt_hi = pool.alloc((size_t)Z * hd * Tpad * sizeof(h16_t));
+            Pool::Buf vt_lo = pool.alloc((size_t)Z * hd * Tpad * sizeof(h16_t));
             mark("c_qkv_planes T=" + std::to_string(T) + " heads=" + std::to_string(heads), 0.0, 2);
-            launch_c_qkv_planes(qkv.f, qkv.C, qk_hi, qk_lo, vt_hi, vt_lo, B, T, Tpad, heads, hd, st);
+            launch_c_qkv_planes(qkv.f(), qkv.C, qk_hi.get<h16_t>(), qk_lo.get<h16_t>(), vt_hi.get<h16_t>(), vt_lo.get<h16_t>(), B, T, Tpad, heads, hd, st);
             Act a = new_operand(qkv.B, qkv.H, qkv.W, C);
             const double fl = 4.0 * Z * (double)T * T * hd;
             tm.flops_attn += fl;
             tm.n_attn++;
-            mark("flash_attn64_split T=" + std::to_string(T) + " heads=" + std::to_string(heads), fl);
+            mark(f512 ? "flash_attn512_split T=" + std::to_string(T) : "flash_attn64_split T=" + std::to_string(T) + " heads=" + std::to_string(heads), fl);
             prof_begin(1);
-            launch_flash_attn64_split(qk_hi, qk_lo, vt_hi, vt_lo, a.p, B, T, heads, 2 * C, Tpad, st);
+            if (f512) launch_flash_attn512_split(qk_hi.get<h16_t>(), qk_lo.get<h16_t>(), vt_hi.get<h16_t>(), vt_lo.get<h16_t>(), a.p(), B, T, Tpad, scale, st);
+            else launch_flash_attn64_split(qk_hi.get<h16_t>(), qk_lo.get<h16_t>(), vt_hi.get<h16_t>(), vt_lo.get<h16_t>(), a.p(), B, T, heads, 2 * C, Tpad, st);
             prof_end();
-            pool.release(qk_hi); pool.release(qk_lo); pool.release(vt_hi); pool.release(vt_lo);
             return a;
         }
         if (!c_softmax_split_supported(Tpad)) throw std::logic_error("attention_c: Tpad");
-        h16_t* Qs = (h16_t*)pool.alloc((size_t)Z * T * 3 * hd * sizeof(h16_t));
-        h16_t* Ks = (h16_t*)pool.alloc((size_t)Z * T * 3 * hd * sizeof(h16_t));
-        h16_t* Vts = (h16_t*)pool.alloc((size_t)Z * hd * 3 * Tpad * sizeof(h16_t));
+        Pool::Buf Qs = pool.alloc((size_t)Z * T * 3 * hd * sizeof(h16_t));
+        Pool::Buf Ks = pool.alloc((size_t)Z * T * 3 * hd * sizeof(h16_t));
+        Pool::Buf Vts = pool.alloc((size_t)Z * hd * 3 * Tpad * sizeof(h16_t));
         mark("c_heads_split T=" + std::to_string(T) + " heads=" + std::to_string(heads), 0.0, 2);
-        launch_c_heads_split(qkv.f, qkv.C, Qs, Ks, Vts, B, T, Tpad, heads, hd, st);
-        float* S = (float*)pool.alloc((size_t)Z * T * Tpad * sizeof(float));
-        run_igemm(igemm_bgemm({Qs, 3 * hd, (long long)T * 3 * hd}, {Ks, 3 * hd, (long long)T * 3 * hd}, {S, Tpad, (long long)T * Tpad}, T, T, 3 * hd, T, T, Z,
-                              nullptr, GP_BIAS_NONE, 1, zero));
-        pool.release(Qs);
-        pool.release(Ks);
-        h16_t* P = (h16_t*)pool.alloc((size_t)Z * T * 3 * Tpad * sizeof(h16_t));
+        launch_c_heads_split(qkv.f(), qkv.C, Qs.get<h16_t>(), Ks.get<h16_t>(), Vts.get<h16_t>(), B, T, Tpad, heads, hd, st);
+        Pool::Buf S = pool.alloc((size_t)Z * T * Tpad * sizeof(float));
+        run_igemm(igemm_bgemm({Qs.get<h16_t>(), 3 * hd, (long long)T * 3 * hd}, {Ks.get<h16_t>(), 3 * hd, (long long)T * 3 * hd}, {S.get<float>(), Tpad, (long long)T * Tpad},
+                              T, T, 3 * hd, T, T, Z, nullptr, GP_BIAS_NONE, 1, zero));
+        Qs.reset();
+        Ks.reset();
+        Pool::Buf P = pool.alloc((size_t)Z * T * 3 * Tpad * sizeof(h16_t));
         mark("c_softmax_split T=" + std::to_string(T));
-        launch_c_softmax_split(S, P, (long long)Z * T, T, Tpad, scale, st);
-        pool.release(S);
-        float* O = (float*)pool.alloc((size_t)Z * T * hd * sizeof(float));
-        run_igemm(igemm_bgemm({P, 3 * Tpad, (long long)T * 3 * Tpad}, {Vts, 3 * Tpad, (long long)hd * 3 * Tpad}, {O, hd, (long long)T * hd}, T, hd, 3 * Tpad, hd,
-                              hd, Z, nullptr, GP_BIAS_NONE, 1, zero));
-        pool.release(P);
-        pool.release(Vts);
+        launch_c_softmax_split(S.get<float>(), P.get<h16_t>(), (long long)Z * T, T, Tpad, scale, st);
+        S.reset();
+        Pool::Buf O = pool.alloc((size_t)Z * T * hd * sizeof(float));
+        run_igemm(igemm_bgemm({P.get<h16_t>(), 3 * Tpad, (long long)T * 3 * Tpad}, {Vts.get<h16_t>(), 3 * Tpad, (long long)hd * 3 * Tpad}, {O.get<float>(), hd, (long long)T * hd},
+                              T, hd, 3 * Tpad, hd, hd, Z, nullptr, GP_BIAS_NONE, 1, zero));
+        P.reset();
+        Vts.reset();
         Act a = new_operand(qkv.B, qkv.H, qkv.W, heads * hd);
         mark("c_heads_merge_split " + dims(a));
-        launch_c_heads_merge_split(O, a.p, B, T, heads, hd, st);
-        pool.release(O);
+        launch_c_heads_merge_split(O.get<float>(), a.p(), B, T, heads, hd, st);
         tm.flops_attn += 4.0 * Z * (double)T * T * hd;
         tm.n_attn++;
         return a;
     }
-    // VAE self-attention, head_dim 512 = C, one head: the GroupNorm output (released here, as soon as q, k and v are enqueued) -> the input of to_out
-    Act vae_self_attention(Act& n, const VaeAttnW& a) {
+    // VAE self-attention, head_dim 512 = C, one head: the GroupNorm output (consumed: released here, as soon as q, k and v are enqueued) -> the input of to_out
+    Act vae_self_attention(Act n, const VaeAttnW& a) {
         if (contract) {  // stacked q | k | v, stored, then the split attention
             Act qkv = linear(n, a.qkv);
-            drop(n);
-            Act o = attention_c(qkv, 1, a.C, 1.0f / std::sqrt((float)a.C));
-            drop(qkv);
-            return o;
+            n.reset();
+            return attention_c(qkv, 1, a.C, 1.0f / std::sqrt((float)a.C));
         }
         const int T = n.H * n.W, C = a.C, Tpad = round_up(T, 64), B = n.B;
         Act qk = linear(n, a.qk);  // [B*T][2C]
-        h16_t* vt = v_transposed(n, a.v, T, Tpad);
-        drop(n);
+        Pool::Buf vt = v_transposed(n, a.v, T, Tpad);
+        n.reset();
         Act o = new_act(qk.B, qk.H, qk.W, C);
         if (flash_attn512_supported(C)) {
             // fused: scores and probabilities never leave the CU (attention.hip: flash_attn512_kernel).  The softmax scale 1/sqrt(C) is
             // folded into the query projection (build_vae_attn), logits exist in fp32 registers only.
             const long long wsf = flash_attn512_workspace_floats(B, T, ncu);
-            float* ws = wsf ? (float*)pool.alloc((size_t)wsf * sizeof(float)) : nullptr;
+            Pool::Buf ws;
+            if (wsf) ws = pool.alloc((size_t)wsf * sizeof(float));
             const double fl = 4.0 * B * (double)T * T * C;
             tm.flops_attn += fl;
             tm.n_attn++;
             mark("flash_attn512 T=" + std::to_string(T), fl);
             prof_begin(1);
-            launch_flash_attn512(qk.p, qk.p + C, vt, o.p, ws, B, T, 2 * C, 2 * C, Tpad, C, 1.0f, ncu, st);
+            launch_flash_attn512(qk.p(), qk.p() + C, vt.get<h16_t>(), o.p(), ws.get<float>(), B, T, 2 * C, 2 * C, Tpad, C, 1.0f, ncu, st);
             prof_end();
-            if (ws) pool.release(ws);
         } else {
-            vae_attention_unfused(qk, vt, o, B, T, Tpad, C);
+            vae_attention_unfused(qk, vt.get<h16_t>(), o, B, T, Tpad, C);
         }
-        drop(qk);
-        pool.release(vt);
         return o;
     }
     Act vae_attention(const Act& x, const std::string& name) {
         const VaeAttnW& a = vattn.at(name);
-        Act n = groupnorm(x, a.gn, cfg.vae_norm_eps, false);
-        Act o = vae_self_attention(n, a);
-        Act y = linear(o, a.o, &x, GP_ACT_NONE, nullptr, true);
-        drop(o);
-        return y;
+        Act o = vae_self_attention(groupnorm(x, a.gn, cfg.vae_norm_eps, false), a);
+        return linear(o, a.o, &x, GP_ACT_NONE, true);
     }
 
-    // UNet self-attention, head_dim 64: the LayerNorm output (released here, as soon as q, k and v are enqueued) -> the input of to_out
-    Act self_attention64(Act& l1, const TfW& t) {
+    // UNet self-attention, head_dim 64: the LayerNorm output (consumed: released here, as soon as q, k and v are enqueued) -> the input of to_out
+    Act self_attention64(Act l1, const TfW& t) {
         if (contract) {  // stacked q | k | v, stored, then the split attention
             Act qkv = linear(l1, t.qkv);
-            drop(l1);
-            Act a = attention_c(qkv, t.heads, 64, 0.125f);
-            drop(qkv);
-            return a;
+            l1.reset();
+            return attention_c(qkv, t.heads, 64, 0.125f);
         }
         const int B = l1.B, T = l1.H * l1.W, C = t.C, Tpad = round_up(T, 64);
         Act qk;
-        h16_t* vt = nullptr;
+        Pool::Buf vt;
         {   // q | k | V^T in ONE launch when the persistent GEMM takes it (T % 16 == 0 ...), else the q | k GEMM + the transposed V GEMM
             const bool no_fuse = gp_sw().no_qkv_fuse;  // A/B switch
             IGemmParams p = igemm_qkv(nhwc(l1), t.qkv.w, t.qkv.cin_pad, t.qkv.n_rows, t.qkv.cin_pad, C, Tpad, nullptr,
@@ -1034,8 +984,8 @@ struct gp_engine {
             const int fuse_max_rows = gp_sw().qkv_fuse_max_rows;
             if (!no_fuse && p.M <= fuse_max_rows && !t.qkv.bias && l1.C == t.qkv.cin_pad && igemm_uses_pgemm(p, 0)) {
                 qk = new_act(l1.B, l1.H, l1.W, 2 * C);
-                vt = (h16_t*)pool.alloc((size_t)B * C * Tpad * sizeof(h16_t));
-                p.out = qk.p; p.vt_out = vt;
+                vt = pool.alloc((size_t)B * C * Tpad * sizeof(h16_t));
+                p.out = qk.p(); p.vt_out = vt.get<h16_t>();
                 igemm_qkv_clear_pad(p, st);
                 run_igemm(p);
             } else {
@@ -1043,17 +993,15 @@ struct gp_engine {
                 vt = v_transposed(l1, t.v, T, Tpad);
             }
         }
-        drop(l1);
+        l1.reset();
         Act a = new_act(qk.B, qk.H, qk.W, C);
         const double fl = 4.0 * B * t.heads * (double)T * T * 64;
         tm.flops_attn += fl;
         tm.n_attn++;
         mark("flash_attn64 T=" + std::to_string(T) + " heads=" + std::to_string(t.heads), fl);
         prof_begin(1);
-        launch_flash_attn64(qk.p, qk.p + C, vt, a.p, B, T, t.heads, 2 * C, 2 * C, Tpad, C, st);
+        launch_flash_attn64(qk.p(), qk.p() + C, vt.get<h16_t>(), a.p(), B, T, t.heads, 2 * C, 2 * C, Tpad, C, st);
         prof_end();
-        drop(qk);
-        pool.release(vt);
         return a;
     }
     // cross-attention against the folded constant context: y += to_out(attn2(LN2(y))) in place; returns LN3(y), the feed-forward's input
@@ -1063,42 +1011,33 @@ struct gp_engine {
         if (t.fU && (!contract || c_cross_fold_supported(C))) {
             Act l3 = new_product_input(y.B, y.H, y.W, C);
             mark((contract ? "c_cross_fold " : "cross_attn_fold ") + dims(y));
-            if (contract) launch_c_cross_fold(y.f, y.f, l3.p, t.fU, t.fu0, t.fG, t.fc0, t.ln3.g, t.ln3.b, M, C, t.heads, 1e-5f, st);
-            else launch_cross_attn_fold(y.p, y.p, l3.p, t.fU, t.fu0, t.fG, t.fc0, t.ln3.g, t.ln3.b, M, C, t.heads, 1e-5f, st);
+            if (contract) launch_c_cross_fold(y.f(), y.f(), l3.p(), t.fU, t.fu0, t.fG, t.fc0, t.ln3.g, t.ln3.b, M, C, t.heads, 1e-5f, st);
+            else launch_cross_attn_fold(y.p(), y.p(), l3.p(), t.fU, t.fu0, t.fG, t.fc0, t.ln3.g, t.ln3.b, M, C, t.heads, 1e-5f, st);
             return l3;
         }
-        Act l2 = layernorm(y, t.ln2);
-        Act q2 = linear(l2, t.q2);
-        drop(l2);
+        Act q2 = linear(layernorm(y, t.ln2), t.q2);  // (the LayerNorm output ends with this statement)
         Act a2 = new_product_input(y.B, y.H, y.W, C);
         mark((contract ? "c_cross_attn_small " : "cross_attn_small ") + dims(q2));
-        if (contract) launch_c_cross_attn_small(q2.f, t.kc, t.vc, a2.p, M, C, ctx_L, st);
-        else launch_cross_attn_small(q2.p, t.kc, t.vc, a2.p, M, C, ctx_L, st);
-        drop(q2);
-        linear(a2, t.o2, &y, GP_ACT_NONE, &y);
-        drop(a2);
+        if (contract) launch_c_cross_attn_small(q2.f(), t.kc, t.vc, a2.p(), M, C, ctx_L, st);
+        else launch_cross_attn_small(q2.p(), t.kc, t.vc, a2.p(), M, C, ctx_L, st);
+        q2.reset();
+        linear_add_into(a2, t.o2, y);
+        a2.reset();
         return layernorm(y, t.ln3);
     }
     // BasicTransformerBlock inside Transformer2DModel (custom_unet.py call sites :305-327,341-352)
     Act transformer(const Act& x, const std::string& name) {
         const TfW& t = tfs.at(name);
         if (!t.kc) throw std::logic_error("gp_set_context has not been called");
-        Act n = groupnorm(x, t.gn, 1e-6f, false);
-        Act y = linear(n, t.proj_in);
-        drop(n);
-        Act l1 = layernorm(y, t.ln1);
-        Act a = self_attention64(l1, t);
-        linear(a, t.o1, &y, GP_ACT_NONE, &y);  // y += to_out(attn), in place
-        drop(a);
-        Act l3 = cross_attention(y, t);
+        Act y = linear(groupnorm(x, t.gn, 1e-6f, false), t.proj_in);
+        Act a = self_attention64(layernorm(y, t.ln1), t);
+        linear_add_into(a, t.o1, y);  // y += to_out(attn), in place
+        a.reset();
         // GEGLU feed-forward
-        Act ff = linear(l3, t.ff1, nullptr, GP_ACT_GEGLU);
-        drop(l3);
-        linear(ff, t.ff2, &y, GP_ACT_NONE, &y);
-        drop(ff);
-        Act out = linear(y, t.proj_out, &x, GP_ACT_NONE, nullptr, true);
-        drop(y);
-        return out;
+        Act ff = linear(cross_attention(y, t), t.ff1, nullptr, GP_ACT_GEGLU);
+        linear_add_into(ff, t.ff2, y);
+        ff.reset();
+        return linear(y, t.proj_out, &x, GP_ACT_NONE, true);
     }
 
     // ---- stages ---------------------------------------------------------------------------------------------------
@@ -1111,7 +1050,7 @@ struct gp_engine {
             h = new_act(B, Hh, Ww, win.cout);
             if (fuse_stats) {
                 const int rows = rgb_conv_in_rows(B, Hh, Ww);  // persistent conv_in: one row per workgroup + its pixel count (mode 2's layout, centred: "mode 3")
-                h.st = (float*)pool.alloc((size_t)B * rows * (2 * win.cout + 1) * sizeof(float));
+                h.stats = pool.alloc((size_t)B * rows * (2 * win.cout + 1) * sizeof(float));
                 h.st_mode = RGB_CONV_IN_STATS_MODE;
                 h.st_bm = rows;
             }
@@ -1123,44 +1062,37 @@ struct gp_engine {
                 weights_dev.push_back(conv_in_w27);
                 launch_pack_k27(win.w, 9 * win.cin_pad, win.cout, conv_in_w27, st);
             }
-            launch_rgb_conv_in(rgb, is_u8, conv_in_w27, win.bias, h.p, h.st, B, Hh, Ww, win.cout, st);
+            launch_rgb_conv_in(rgb, is_u8, conv_in_w27, win.bias, h.p(), h.st(), B, Hh, Ww, win.cout, st);
             prof_end();
         } else {
             Act x = new_product_input(B, Hh, Ww, 64);
             mark(contract ? "c_rgb_split" : "rgb_prologue");
             // (contract precision: x / 255 * 2 - 1 is not a bf16 number: the image itself enters as a split operand)
-            if (contract) launch_c_rgb_split(rgb, is_u8, x.p, B, Hh, Ww, st);
-            else launch_rgb_prologue(rgb, is_u8, x.p, B, Hh, Ww, 64, st);
+            if (contract) launch_c_rgb_split(rgb, is_u8, x.p(), B, Hh, Ww, st);
+            else launch_rgb_prologue(rgb, is_u8, x.p(), B, Hh, Ww, 64, st);
             ConvOpt oin;
             oin.want_stats = true;
             h = conv(x, win, oin);
-            drop(x);
         }
         for (int i = 0; i < 4; ++i) {
             for (int j = 0; j < cfg.vae_layers_per_block; ++j) {
-                Act y = resnet(h, "vae.encoder.down_blocks." + std::to_string(i) + ".resnets." + std::to_string(j), cfg.vae_norm_eps);
-                drop(h);
-                h = y;
+                h = resnet(h, "vae.encoder.down_blocks." + std::to_string(i) + ".resnets." + std::to_string(j), cfg.vae_norm_eps);
             }
             if (i != 3) {
                 ConvOpt o;  // pad (0,1,0,1) then stride-2 conv without padding (Appendix B.6)
                 o.stride = 2; o.pad_t = 0; o.pad_l = 0; o.want_stats = true;
                 o.Ho = (h.H + 1 - 3) / 2 + 1; o.Wo = (h.W + 1 - 3) / 2 + 1;
-                Act y = conv(h, convs.at("vae.encoder.down_blocks." + std::to_string(i) + ".downsamplers.0.conv"), o);
-                drop(h);
-                h = y;
+                h = conv(h, convs.at("vae.encoder.down_blocks." + std::to_string(i) + ".downsamplers.0.conv"), o);
             }
         }
-        Act y = resnet(h, "vae.encoder.mid_block.resnets.0", cfg.vae_norm_eps); drop(h); h = y;
-        y = vae_attention(h, "vae.encoder.mid_block.attentions.0"); drop(h); h = y;
-        y = resnet(h, "vae.encoder.mid_block.resnets.1", cfg.vae_norm_eps); drop(h); h = y;
+        h = resnet(h, "vae.encoder.mid_block.resnets.0", cfg.vae_norm_eps);
+        h = vae_attention(h, "vae.encoder.mid_block.attentions.0");
+        h = resnet(h, "vae.encoder.mid_block.resnets.1", cfg.vae_norm_eps);
         Act n = groupnorm(h, norms.at("vae.encoder.conv_norm_out"), cfg.vae_norm_eps, true);
-        drop(h);
+        h.reset();
         ConvOpt o;
         o.n_store = 64;
-        Act lat = conv(n, convs.at("vae.encoder.conv_out_folded"), o);
-        drop(n);
-        return lat;
+        return conv(n, convs.at("vae.encoder.conv_out_folded"), o);
     }
 
     // [h | skip] along the channels
@@ -1169,101 +1101,81 @@ struct gp_engine {
         const int cbm = (fuse_stats && !contract) ? concat_stats_bm((long long)h.H * h.W, h.pixels(), h.C + skip.C) : 0;
         mark("concat " + dims(cat));
         if (contract) {
-            launch_c_concat(h.f, h.C, skip.f, skip.C, cat.f, h.pixels(), st);
+            launch_c_concat(h.f(), h.C, skip.f(), skip.C, cat.f(), h.pixels(), st);
         } else if (cbm) {  // the copy also leaves the statistics the resnet's first GroupNorm needs
-            cat.st = (float*)pool.alloc((size_t)(h.pixels() / cbm) * cat.C * 2 * sizeof(float));
+            cat.stats = pool.alloc((size_t)(h.pixels() / cbm) * cat.C * 2 * sizeof(float));
             cat.st_mode = CONCAT_STATS_MODE;
             cat.st_bm = cbm;
-            launch_concat_stats(h.p, h.C, skip.p, skip.C, cat.p, h.pixels(), cbm, cat.st, st);
+            launch_concat_stats(h.p(), h.C, skip.p(), skip.C, cat.p(), h.pixels(), cbm, cat.st(), st);
         } else {
-            launch_concat(h.p, h.C, skip.p, skip.C, cat.p, h.pixels(), st);
+            launch_concat(h.p(), h.C, skip.p(), skip.C, cat.p(), h.pixels(), st);
         }
         return cat;
     }
-    // latent NHWC (64 allocated channels) -> sample NHWC (64 allocated, unet_out_channels real) and/or the 4 up-block features
+    // latent NHWC (64 allocated channels) -> sample NHWC (64 allocated, unet_out_channels real; empty unless wanted) and/or the 4 up-block features
     Act unet(const Act& latent, Act* feats /* [4] or null */, bool want_sample) {
-        std::vector<Act> skips;
+        std::vector<Act> skips;  // owns every down-path output; the running tensor of the down path is skips.back()
         const int nup = 3;
         const bool fwd_size = (latent.H % (1 << nup)) != 0 || (latent.W % (1 << nup)) != 0;
         ConvOpt oin;
         oin.want_stats = true;
-        Act x = conv(latent, convs.at("unet.conv_in"), oin);
-        skips.push_back(x);
-        Act cur = x;  // `cur` aliases the top of the skip stack until replaced
+        skips.push_back(conv(latent, convs.at("unet.conv_in"), oin));
         for (int i = 0; i < 4; ++i) {
             const std::string bp = "unet.down_blocks." + std::to_string(i);
             for (int j = 0; j < cfg.unet_layers_per_block; ++j) {
-                Act y = resnet(cur, bp + ".resnets." + std::to_string(j), cfg.unet_norm_eps);
-                if (cfg.unet_down_attn[i]) {
-                    Act z = transformer(y, bp + ".attentions." + std::to_string(j));
-                    drop(y);
-                    y = z;
-                }
-                skips.push_back(y);
-                cur = y;
+                Act y = resnet(skips.back(), bp + ".resnets." + std::to_string(j), cfg.unet_norm_eps);
+                if (cfg.unet_down_attn[i]) y = transformer(y, bp + ".attentions." + std::to_string(j));
+                skips.push_back(std::move(y));
             }
             if (i != 3) {
+                const Act& cur = skips.back();
                 ConvOpt o;
                 o.stride = 2; o.want_stats = true;
                 o.Ho = (cur.H + 2 - 3) / 2 + 1; o.Wo = (cur.W + 2 - 3) / 2 + 1;
                 Act y = conv(cur, convs.at(bp + ".downsamplers.0.conv"), o);
-                skips.push_back(y);
-                cur = y;
+                skips.push_back(std::move(y));
             }
         }
-        // mid (cur is also skips.back(): do not drop it)
-        Act m = resnet(cur, "unet.mid_block.resnets.0", cfg.unet_norm_eps);
-        Act m2 = transformer(m, "unet.mid_block.attentions.0");
-        drop(m);
-        m = resnet(m2, "unet.mid_block.resnets.1", cfg.unet_norm_eps);
-        drop(m2);
-        Act h = m;
-        bool h_is_feat = false;  // h is one of the caller's feature maps (multi_level_feats): the caller drops it, not this function
+        // mid
+        Act own = resnet(skips.back(), "unet.mid_block.resnets.0", cfg.unet_norm_eps);
+        own = transformer(own, "unet.mid_block.attentions.0");
+        own = resnet(own, "unet.mid_block.resnets.1", cfg.unet_norm_eps);
+        // up: the running tensor h is `own`, or the caller's feats[i] once an up block's output was moved there (multi_level_feats).  The caller
+        // keeps a feature map's tensor; only its statistics partials go back here, where an owned h goes back whole.
+        Act* h = &own;
         for (int i = 0; i < 4; ++i) {
             const std::string bp = "unet.up_blocks." + std::to_string(i);
             const bool attn = cfg.unet_down_attn[3 - i];
             const int nres = cfg.unet_layers_per_block + 1;
             for (int j = 0; j < nres; ++j) {
-                Act skip = skips.back();
+                Act cat = concat(*h, skips.back());
+                h->stats.reset();
+                own.reset();  // (already empty when h is a feature map)
+                h = &own;
                 skips.pop_back();
-                Act cat = concat(h, skip);
-                if (!h_is_feat) drop(h);
-                else if (h.st) pool.release(h.st);
-                h_is_feat = false;
-                drop(skip);
-                Act y = resnet(cat, bp + ".resnets." + std::to_string(j), cfg.unet_norm_eps);
-                drop(cat);
-                if (attn) {
-                    Act z = transformer(y, bp + ".attentions." + std::to_string(j));
-                    drop(y);
-                    y = z;
-                }
-                h = y;
+                own = resnet(cat, bp + ".resnets." + std::to_string(j), cfg.unet_norm_eps);
+                cat.reset();
+                if (attn) own = transformer(own, bp + ".attentions." + std::to_string(j));
             }
             if (i != 3) {
                 ConvOpt o;
                 if (fwd_size) { o.ups_h = skips.back().H; o.ups_w = skips.back().W; }
-                else { o.ups_h = h.H * 2; o.ups_w = h.W * 2; }
-                Act y = conv(h, convs.at(bp + ".upsamplers.0.conv"), o);
-                drop(h);
-                h = y;
+                else { o.ups_h = own.H * 2; o.ups_w = own.W * 2; }
+                own = conv(own, convs.at(bp + ".upsamplers.0.conv"), o);
             }
             if (feats) {  // custom_unet.py:365,400: the output of every up block; retained, not copied (the buffer outlives its use here)
-                feats[i] = h;
-                feats[i].st = nullptr;  // (its statistics partials stay with h and are released below / by the next concat)
-                h_is_feat = true;
+                feats[i] = std::move(own);
+                h = &feats[i];
             }
         }
         Act out;
         if (want_sample && cfg.unet_has_out) {
-            Act n = groupnorm(h, norms.at("unet.conv_norm_out"), cfg.unet_norm_eps, true);
+            Act n = groupnorm(*h, norms.at("unet.conv_norm_out"), cfg.unet_norm_eps, true);
             ConvOpt o;
             o.n_store = 64;
             out = conv(n, convs.at("unet.conv_out"), o);
-            drop(n);
         }
-        if (!h_is_feat) drop(h);
-        else if (h.st) { pool.release(h.st); }
+        h->stats.reset();
         return out;
     }
 
@@ -1272,34 +1184,28 @@ struct gp_engine {
         const int L = cfg.vae_latent_channels;
         Act z = new_stored(z_in.B, z_in.H, z_in.W, 64);
         mark("post_quant_conv");
-        if (contract) launch_c_pointwise_small(z_in.f, z.f, pq_w_dev, pq_b_dev, z_in.pixels(), L, L, z_in.C, 64, in_scale, st);
-        else launch_pointwise_small(z_in.p, z.p, pq_w_dev, pq_b_dev, z_in.pixels(), L, L, z_in.C, 64, in_scale, st);
+        if (contract) launch_c_pointwise_small(z_in.f(), z.f(), pq_w_dev, pq_b_dev, z_in.pixels(), L, L, z_in.C, 64, in_scale, st);
+        else launch_pointwise_small(z_in.p(), z.p(), pq_w_dev, pq_b_dev, z_in.pixels(), L, L, z_in.C, 64, in_scale, st);
         return z;
     }
     // z_in: NHWC with 64 allocated channels holding the UNet output v (in_scale = -1/scaling) or a pred latent (1/scaling)
     // out_dev != nullptr: the caller wants the fp32 NCHW result of decode_pred (+ clip / shift unless raw); when the fused tail kernel takes
     // the last three layers (conv_few.hip) it is written directly and the returned Act is empty, else decode_to runs decode_epilogue
     Act vae_decode(const Act& z_in, float in_scale, float* out_dev = nullptr, int mean3 = 0, int raw = 0) {
-        Act z = post_quant(z_in, in_scale);
         ConvOpt oin;
         oin.want_stats = true;
-        Act h = conv(z, convs.at("vae.decoder.conv_in"), oin);
-        drop(z);
-        Act y = resnet(h, "vae.decoder.mid_block.resnets.0", cfg.vae_norm_eps); drop(h); h = y;
-        y = vae_attention(h, "vae.decoder.mid_block.attentions.0"); drop(h); h = y;
-        y = resnet(h, "vae.decoder.mid_block.resnets.1", cfg.vae_norm_eps); drop(h); h = y;
+        Act h = conv(post_quant(z_in, in_scale), convs.at("vae.decoder.conv_in"), oin);
+        h = resnet(h, "vae.decoder.mid_block.resnets.0", cfg.vae_norm_eps);
+        h = vae_attention(h, "vae.decoder.mid_block.attentions.0");
+        h = resnet(h, "vae.decoder.mid_block.resnets.1", cfg.vae_norm_eps);
         for (int i = 0; i < 4; ++i) {
             for (int j = 0; j < cfg.vae_layers_per_block + 1; ++j) {
-                y = resnet(h, "vae.decoder.up_blocks." + std::to_string(i) + ".resnets." + std::to_string(j), cfg.vae_norm_eps);
-                drop(h);
-                h = y;
+                h = resnet(h, "vae.decoder.up_blocks." + std::to_string(i) + ".resnets." + std::to_string(j), cfg.vae_norm_eps);
             }
             if (i != 3) {
                 ConvOpt o;
                 o.ups_h = h.H * 2; o.ups_w = h.W * 2; o.want_stats = true;
-                y = conv(h, convs.at("vae.decoder.up_blocks." + std::to_string(i) + ".upsamplers.0.conv"), o);
-                drop(h);
-                h = y;
+                h = conv(h, convs.at("vae.decoder.up_blocks." + std::to_string(i) + ".upsamplers.0.conv"), o);
             }
         }
         const PackedW& wout = convs.at("vae.decoder.conv_out");
@@ -1311,151 +1217,125 @@ struct gp_engine {
             tm.n_igemm++;
             mark("conv_few gn+silu+conv3x3+decode " + dims(h), fl);
             prof_begin(0);
-            launch_conv_few(h.p, wout.w, wout.bias, scale, shift, zero, out_dev, h.B, h.H, h.W, 1, mean3, raw, ncu, st);
+            launch_conv_few(h.p(), wout.w, wout.bias, scale, shift, zero, out_dev, h.B, h.H, h.W, 1, mean3, raw, ncu, st);
             prof_end();
-            drop(h);
             return Act{};
         }
         Act n = groupnorm(h, norms.at("vae.decoder.conv_norm_out"), cfg.vae_norm_eps, true);
-        drop(h);
+        h.reset();
         ConvOpt o;
         o.n_store = 4;  // 3 real channels + one zero: 8-byte pixels for the epilogue
-        Act out = conv(n, wout, o);
-        drop(n);
-        return out;
+        return conv(n, wout, o);
     }
 
     // decoder output NHWC (3 real channels) -> the caller's fp32 NCHW map: channel mean, clip / shift unless raw (genpercept_pipeline.py:523-525,469-472)
     void decode_epilogue(const Act& dec, float* out, int mean3, int raw) {
         mark("decode_epilogue");
-        if (dec.f) launch_c_decode_epilogue(dec.f, out, dec.B, dec.H, dec.W, dec.C, mean3, raw, st);
-        else launch_decode_epilogue(dec.p, out, dec.B, dec.H, dec.W, dec.C, mean3, raw, st);
+        if (dec.f()) launch_c_decode_epilogue(dec.f(), out, dec.B, dec.H, dec.W, dec.C, mean3, raw, st);
+        else launch_decode_epilogue(dec.p(), out, dec.B, dec.H, dec.W, dec.C, mean3, raw, st);
     }
     // the decode tail of an entry point: latent -> the caller's map (the fused tail kernel of vae_decode wrote `out` itself when no tensor comes back)
     void decode_to(const Act& z, float in_scale, float* out, int mean3, int raw) {
         Act dec = vae_decode(z, in_scale, out, mean3, raw);
-        if (dec.p || dec.f) {
-            decode_epilogue(dec, out, mean3, raw);
-            drop(dec);
-        }
+        if (dec.data()) decode_epilogue(dec, out, mean3, raw);
     }
 
     Act bilinear(const Act& x, int Ho, int Wo, int align_corners) {
         Act y = new_stored(x.B, Ho, Wo, x.C);
         mark("bilinear " + dims(y));
-        if (contract) launch_c_bilinear(x.f, y.f, x.B, x.H, x.W, Ho, Wo, x.C, align_corners, st);
-        else launch_bilinear(x.p, y.p, x.B, x.H, x.W, Ho, Wo, x.C, align_corners, st);
+        if (contract) launch_c_bilinear(x.f(), y.f(), x.B, x.H, x.W, Ho, Wo, x.C, align_corners, st);
+        else launch_bilinear(x.p(), y.p(), x.B, x.H, x.W, Ho, Wo, x.C, align_corners, st);
         return y;
     }
     Act relu_input(const Act& x) {  // ReLU(x) as the input of a matrix product
         if (contract) return split_operand(x, GP_ACT_RELU);
         Act r = new_act(x.B, x.H, x.W, x.C);
         mark("relu " + dims(x));
-        launch_relu(x.p, r.p, x.pixels() * x.C, st);
+        launch_relu(x.p(), r.p(), x.pixels() * x.C, st);
         return r;
     }
     Act add(const Act& a, const Act& b) {
         Act y = new_stored(a.B, a.H, a.W, a.C);
         mark("add " + dims(a));
-        if (contract) launch_c_add(a.f, b.f, y.f, a.pixels() * a.C, st);
-        else launch_add(a.p, b.p, y.p, a.pixels() * a.C, st);
+        if (contract) launch_c_add(a.f(), b.f(), y.f(), a.pixels() * a.C, st);
+        else launch_add(a.p(), b.p(), y.p(), a.pixels() * a.C, st);
         return y;
     }
     void dpt_final(const Act& z, float* out_dev) {  // head.head.4 (1x1 to one channel), fp32 [B][H * W]
         mark("dpt_final " + dims(z));
-        if (contract) launch_c_dpt_final(z.f, dpt_w_dev, dpt_b, out_dev, z.B, z.H * z.W, z.C, st);
-        else launch_dpt_final(z.p, dpt_w_dev, dpt_b, out_dev, z.B, z.H * z.W, z.C, st);
+        if (contract) launch_c_dpt_final(z.f(), dpt_w_dev, dpt_b, out_dev, z.B, z.H * z.W, z.C, st);
+        else launch_dpt_final(z.p(), dpt_w_dev, dpt_b, out_dev, z.B, z.H * z.W, z.C, st);
     }
     Act rcu(const Act& x, const std::string& p) {  // pre-activation residual unit (dpt_head.py:256-271)
-        Act r = relu_input(x);
         ConvOpt o1;
         o1.act = GP_ACT_RELU;
-        Act h = conv(r, convs.at(p + ".convolution1"), o1);
-        drop(r);
+        Act h = conv(relu_input(x), convs.at(p + ".convolution1"), o1);
         ConvOpt o2;
         o2.residual = &x;
-        Act y = conv(h, convs.at(p + ".convolution2"), o2);
-        drop(h);
-        return y;
+        return conv(h, convs.at(p + ".convolution2"), o2);
     }
     // feats: reversed multi_level_feats [c0@h, c1@h, c2@h/2, c3@h/4] -> fp32 [B][8h*8w] written to out_dev
-    void dpt_head(const Act* feats, float* out_dev) {
+    void dpt_head(const Act* const feats[4], float* out_dev) {
         ConvOpt ou;
-        ou.ups_h = feats[0].H * 2; ou.ups_w = feats[0].W * 2;
-        Act f0 = conv(feats[0], convs.at("dpt.feature_upsample_0.conv"), ou);
+        ou.ups_h = feats[0]->H * 2; ou.ups_w = feats[0]->W * 2;
         Act nk[4];
-        nk[0] = conv(f0, convs.at("dpt.neck.convs.0"), ConvOpt{});
-        drop(f0);
-        for (int i = 1; i < 4; ++i) nk[i] = conv(feats[i], convs.at("dpt.neck.convs." + std::to_string(i)), ConvOpt{});
+        nk[0] = conv(conv(*feats[0], convs.at("dpt.feature_upsample_0.conv"), ou), convs.at("dpt.neck.convs.0"), ConvOpt{});
+        for (int i = 1; i < 4; ++i) nk[i] = conv(*feats[i], convs.at("dpt.neck.convs." + std::to_string(i)), ConvOpt{});
         Act fused;
         for (int i = 0; i < 4; ++i) {
             const std::string lp = "dpt.neck.fusion_stage.layers." + std::to_string(i);
-            Act& hsrc = nk[3 - i];
-            Act x;
-            if (i == 0) {
-                x = hsrc;
-            } else {
-                Act r = hsrc;
-                if (r.H != fused.H || r.W != fused.W) {
-                    Act rr = bilinear(r, fused.H, fused.W, 0);
-                    drop(r);
-                    r = rr;
-                }
-                Act rc = rcu(r, lp + ".residual_layer1");
-                drop(r);
+            Act x = std::move(nk[3 - i]);
+            if (i != 0) {
+                if (x.H != fused.H || x.W != fused.W) x = bilinear(x, fused.H, fused.W, 0);
+                Act rc = rcu(x, lp + ".residual_layer1");
+                x.reset();
                 x = add(fused, rc);
-                drop(rc);
-                drop(fused);
+                fused.reset();
             }
             Act x2 = rcu(x, lp + ".residual_layer2");
-            drop(x);
+            x.reset();
             // dpt_head.py:303-309 interpolates (bilinear x2, align_corners) and THEN applies the 1x1 projection.  The two commute -- the projection mixes
             // channels per pixel, the interpolation mixes pixels per channel with weights that sum to one, so the bias passes through as well --
             // and the projection on the SOURCE map is a quarter of the GEMM and of its HBM traffic (r5)
             Act pr = linear(x2, convs.at(lp + ".projection"));
-            drop(x2);
+            x2.reset();
             fused = bilinear(pr, pr.H * 2, pr.W * 2, 1);
-            drop(pr);
         }
         ConvOpt op;
         op.act = GP_ACT_RELU;
-        Act x = conv(fused, convs.at("dpt.head.projection"), op);
-        drop(fused);
-        Act y = conv(x, convs.at("dpt.head.head.0"), ConvOpt{});
-        drop(x);
-        Act up = bilinear(y, y.H * 2, y.W * 2, 1);
-        drop(y);
+        Act h = conv(fused, convs.at("dpt.head.projection"), op);
+        fused.reset();
+        h = conv(h, convs.at("dpt.head.head.0"), ConvOpt{});
+        h = bilinear(h, h.H * 2, h.W * 2, 1);
         ConvOpt o32;
         o32.act = GP_ACT_RELU;
-        Act z = conv(up, convs.at("dpt.head.head.2"), o32);
-        drop(up);
-        dpt_final(z, out_dev);
-        drop(z);
+        h = conv(h, convs.at("dpt.head.head.2"), o32);
+        dpt_final(h, out_dev);
     }
 
     Act from_nchw_f32(const float* src, int B, int C, int Hh, int Ww, int Cpad) {
         Act a = new_stored(B, Hh, Ww, Cpad);
         mark("nchw_f32_to_nhwc");
-        if (contract) launch_c_nchw_to_nhwc(src, a.f, B, C, Hh, Ww, Cpad, st);
-        else launch_nchw_f32_to_nhwc(src, a.p, B, C, Hh, Ww, Cpad, st);
+        if (contract) launch_c_nchw_to_nhwc(src, a.f(), B, C, Hh, Ww, Cpad, st);
+        else launch_nchw_f32_to_nhwc(src, a.p(), B, C, Hh, Ww, Cpad, st);
         return a;
     }
     void to_nchw_f32(const Act& a, int C, float* dst) {
         mark("nhwc_to_nchw_f32");
-        if (a.f) launch_c_nhwc_to_nchw(a.f, dst, a.B, C, a.H, a.W, a.C, st);
-        else launch_nhwc_to_nchw_f32(a.p, dst, a.B, C, a.H, a.W, a.C, st);
+        if (a.f()) launch_c_nhwc_to_nchw(a.f(), dst, a.B, C, a.H, a.W, a.C, st);
+        else launch_nhwc_to_nchw_f32(a.p(), dst, a.B, C, a.H, a.W, a.C, st);
     }
 
     // multi-step archs: the fp32 denoising state `sample` and the UNet input `lat` (channels [off, off + L) hold the sample)
     void ddim_init(const float* noise_dev, const Act& lat, float* sample, int L, int off) {
         mark("ddim_init");
-        if (contract) launch_c_ddim_init(noise_dev, lat.f, sample, lat.B, lat.H, lat.W, L, lat.C, off, st);
-        else launch_ddim_init(noise_dev, lat.p, sample, lat.B, lat.H, lat.W, L, lat.C, off, st);
+        if (contract) launch_c_ddim_init(noise_dev, lat.f(), sample, lat.B, lat.H, lat.W, L, lat.C, off, st);
+        else launch_ddim_init(noise_dev, lat.p(), sample, lat.B, lat.H, lat.W, L, lat.C, off, st);
     }
     void ddim_step(const Act& v, float* sample, const Act& lat, int L, int off, const Act& x0, bool last /* pred_x0 goes to x0 */, const DdimCoef& k) {
         mark("ddim_step");
-        if (contract) launch_c_ddim_step(v.f, v.C, sample, lat.f, lat.C, off, last ? x0.f : nullptr, x0.C, lat.pixels(), L, k, st);
-        else launch_ddim_step(v.p, v.C, sample, lat.p, lat.C, off, last ? x0.p : nullptr, x0.C, lat.pixels(), L, k, st);
+        if (contract) launch_c_ddim_step(v.f(), v.C, sample, lat.f(), lat.C, off, last ? x0.f() : nullptr, x0.C, lat.pixels(), L, k, st);
+        else launch_ddim_step(v.p(), v.C, sample, lat.p(), lat.C, off, last ? x0.p() : nullptr, x0.C, lat.pixels(), L, k, st);
     }
 
     void collect_profile() {
@@ -1493,12 +1373,6 @@ static gp_status guard(gp_engine* e, F&& f) {
     } catch (const std::exception& ex) {
         if (e) e->err = ex.what();
         st = GP_ERR_HIP;
-    }
-    // a stage that threw abandoned its activations: wait for whatever it had enqueued, then hand every outstanding buffer back to the pool
-    if (e && !e->pool.live_.empty()) {
-        (void)hipSetDevice(e->cfg.device);
-        (void)hipDeviceSynchronize();
-        e->pool.release_live();
     }
     return st;
 }
@@ -1560,11 +1434,10 @@ void gp_destroy(gp_engine* e) {
     hipDeviceSynchronize();
     for (void* p : e->weights_dev) hipFree(p);
     if (e->sat_dev) hipFree(e->sat_dev);
-    e->pool.destroy();
     for (auto& pr : e->ev_pool) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
     for (auto& m : e->marks) hipEventDestroy(m.ev);
     for (int i = 0; i < 4; ++i) if (e->ev[i]) hipEventDestroy(e->ev[i]);
-    delete e;
+    delete e;  // (the pool frees its buffers)
 }
 
 const char* gp_last_error(const gp_engine* e) { return e ? e->err.c_str() : "null engine"; }
@@ -1704,6 +1577,8 @@ int gp_get_launch_log(gp_engine* e, char* buf, int cap) {
     return (int)out.size() + 1;
 }
 
+}  // extern "C"
+
 static void check_ready(gp_engine* e, void* stream) {
     if (!e->finalized) throw std::logic_error("engine not finalized");
     HIPCHK(hipSetDevice(e->cfg.device));
@@ -1735,52 +1610,68 @@ static void end_pass(gp_engine* e) {
     HIPCHK(hipEventElapsedTime(&e->tm.ms_head, e->ev[2], e->ev[3]));
     HIPCHK(hipEventElapsedTime(&e->tm.ms_total, e->ev[0], e->ev[3]));
 }
-// the last thing every entry point that enqueues work does
+// the last thing every entry point that enqueues work does: every activation and scratch buffer of the call has gone back to the pool by now
 static void finish_call(gp_engine* e) {
     e->collect_saturation();
     HIPCHK(hipGetLastError());
+    if (e->pool.outstanding != 0) throw std::logic_error("pool buffers outstanding at the end of a call: " + std::to_string(e->pool.outstanding));
 }
+// An entry point that enqueues work on `stream`: f() runs between check_ready and finish_call.  A stage that throws has, by unwinding, already
+// handed its buffers back to the pool while kernels that use them may still be queued: the failed call waits for the device before it returns,
+// so the next call's kernels cannot meet them.
+template <typename F>
+static gp_status guard_call(gp_engine* e, void* stream, F&& f) {
+    bool entered = false;
+    const gp_status s = guard(e, [&] {
+        check_ready(e, stream);
+        entered = true;
+        f();
+        finish_call(e);
+    });
+    if (s != GP_OK && entered) {
+        (void)hipSetDevice(e->cfg.device);
+        (void)hipDeviceSynchronize();
+    }
+    return s;
+}
+
+extern "C" {
 
 gp_status gp_infer(gp_engine* e, const void* rgb_dev, int is_u8, int B, int H, int W, gp_mode mode, float* out_dev, void* stream) {
     if (!e || !rgb_dev || !out_dev) return GP_ERR_INVALID;
-    return guard(e, [&] {
-        check_ready(e, stream);
+    return guard_call(e, stream, [&] {
         if (B < 1 || H < 8 || W < 8) throw std::invalid_argument("need B >= 1 and H, W >= 8");
         begin_pass(e);
         Act lat = e->vae_encode(rgb_dev, is_u8, B, H, W);
         stage(e, 1);
         if (!e->cfg.dpt_enabled) {
             Act v = e->unet(lat, nullptr, true);
-            e->drop(lat);
+            lat.reset();
             stage(e, 2);
             // scheduler step with beta == 1: pred_x0 = -v (F5); decode_pred divides by the scaling factor
             const int mean3 = !(mode == GP_MODE_NORMAL || mode == GP_MODE_SEG);
             e->decode_to(v, -1.0f / e->cfg.vae_scaling_factor, out_dev, mean3, 0);
-            e->drop(v);
         } else {
             Act feats[4];
             e->unet(lat, feats, false);
-            e->drop(lat);
+            lat.reset();
             stage(e, 2);
-            Act rev[4] = {feats[3], feats[2], feats[1], feats[0]};
-            const long long out_px = (long long)gp_dpt_out_size(rev[0].H) * gp_dpt_out_size(rev[0].W);
+            const Act* rev[4] = {&feats[3], &feats[2], &feats[1], &feats[0]};
+            const long long out_px = (long long)gp_dpt_out_size(rev[0]->H) * gp_dpt_out_size(rev[0]->W);
             e->dpt_head(rev, out_dev);
-            for (int i = 0; i < 4; ++i) e->drop(feats[i]);
+            for (Act& f : feats) f.reset();
             e->mark("minmax_norm", 0.0, 2);
-            float* mm_ws = (float*)e->pool.alloc((size_t)B * 64 * 2 * sizeof(float));  // [B][64 partials][min, max]
-            launch_minmax_norm(out_dev, B, out_px, mm_ws, e->st);
-            e->pool.release(mm_ws);
+            Pool::Buf mm_ws = e->pool.alloc((size_t)B * 64 * 2 * sizeof(float));  // [B][64 partials][min, max]
+            launch_minmax_norm(out_dev, B, out_px, mm_ws.get<float>(), e->st);
         }
         end_pass(e);
-        finish_call(e);
     });
 }
 
 gp_status gp_infer_steps(gp_engine* e, const void* rgb_dev, int is_u8, int B, int H, int W, gp_mode mode, const gp_ddim_step* steps,
                          int n_steps, const float* noise_dev, float* out_dev, void* stream) {
     if (!e || !rgb_dev || !out_dev || !steps) return GP_ERR_INVALID;
-    return guard(e, [&] {
-        check_ready(e, stream);
+    return guard_call(e, stream, [&] {
         if (B < 1 || H < 8 || W < 8 || n_steps < 1) throw std::invalid_argument("need B >= 1, H, W >= 8 and at least one step");
         if (e->cfg.dpt_enabled || !e->cfg.unet_has_out) throw std::invalid_argument("the multi-step archs use the VAE-decoder head");
         const int L = e->cfg.vae_latent_channels;
@@ -1792,8 +1683,8 @@ gp_status gp_infer_steps(gp_engine* e, const void* rgb_dev, int is_u8, int B, in
         Act lat = e->vae_encode(rgb_dev, is_u8, B, H, W);  // channels 0..L-1 = rgb latent; the UNet input tensor from here on
         stage(e, 1);
         const int off = noise_dev ? L : 0;
-        float* sample = (float*)e->pool.alloc((size_t)lat.pixels() * L * sizeof(float));
-        e->ddim_init(noise_dev, lat, sample, L, off);
+        Pool::Buf sample = e->pool.alloc((size_t)lat.pixels() * L * sizeof(float));
+        e->ddim_init(noise_dev, lat, sample.get<float>(), L, off);
         Act x0 = e->new_stored(B, lat.H, lat.W, 64);
         try {
             for (int i = 0; i < n_steps; ++i) {
@@ -1801,8 +1692,7 @@ gp_status gp_infer_steps(gp_engine* e, const void* rgb_dev, int is_u8, int B, in
                 if (s.timestep != e->timestep) e->set_timestep_on_stream(s.timestep);
                 Act v = e->unet(lat, nullptr, true);
                 const DdimCoef k{s.x0_sample, s.x0_model, s.eps_sample, s.eps_model, s.prev_x0, s.prev_eps, s.clip};
-                e->ddim_step(v, sample, lat, L, off, x0, i == n_steps - 1, k);
-                e->drop(v);
+                e->ddim_step(v, sample.get<float>(), lat, L, off, x0, i == n_steps - 1, k);
             }
         } catch (...) {  // a failed step must not leave the loop's timestep behind as the engine's (gp_set_timestep) one
             if (e->timestep != t_before) {
@@ -1810,90 +1700,73 @@ gp_status gp_infer_steps(gp_engine* e, const void* rgb_dev, int is_u8, int B, in
             }
             throw;
         }
-        e->pool.release(sample);
-        e->drop(lat);
+        sample.reset();
+        lat.reset();
         if (e->timestep != t_before) e->set_timestep_on_stream(t_before);
         stage(e, 2);
         const int mean3 = !(mode == GP_MODE_NORMAL || mode == GP_MODE_SEG);
         e->decode_to(x0, 1.0f / e->cfg.vae_scaling_factor, out_dev, mean3, 0);
-        e->drop(x0);
+        x0.reset();
         end_pass(e);
-        finish_call(e);
     });
 }
 
 gp_status gp_vae_encode(gp_engine* e, const void* rgb_dev, int is_u8, int B, int H, int W, float* latent_out, void* stream) {
     if (!e || !rgb_dev || !latent_out) return GP_ERR_INVALID;
-    return guard(e, [&] {
-        check_ready(e, stream);
+    return guard_call(e, stream, [&] {
         Act lat = e->vae_encode(rgb_dev, is_u8, B, H, W);
         e->to_nchw_f32(lat, e->cfg.vae_latent_channels, latent_out);
-        e->drop(lat);
-        finish_call(e);
     });
 }
 
 gp_status gp_unet(gp_engine* e, const float* latent_in, int B, int h, int w, float* sample_out, float* const* feats_out, void* stream) {
     if (!e || !latent_in) return GP_ERR_INVALID;
-    return guard(e, [&] {
-        check_ready(e, stream);
+    return guard_call(e, stream, [&] {
         Act lat = e->from_nchw_f32(latent_in, B, e->cfg.unet_in_channels, h, w, 64);
         Act feats[4];
         Act v = e->unet(lat, feats_out ? feats : nullptr, sample_out != nullptr);
-        e->drop(lat);
+        lat.reset();
         if (sample_out) {
-            if (!v.p && !v.f) throw std::logic_error("this UNet has no conv_out (DPT variant)");
+            if (!v.data()) throw std::logic_error("this UNet has no conv_out (DPT variant)");
             e->to_nchw_f32(v, e->cfg.unet_out_channels, sample_out);
         }
-        if (v.p || v.f) e->drop(v);
         if (feats_out)
-            for (int i = 0; i < 4; ++i) {
+            for (int i = 0; i < 4; ++i)
                 if (feats_out[i]) e->to_nchw_f32(feats[i], feats[i].C, feats_out[i]);
-                e->drop(feats[i]);
-            }
-        finish_call(e);
     });
 }
 
 gp_status gp_vae_decode(gp_engine* e, const float* pred_latent, int B, int h, int w, int mean3, float* out, void* stream) {
     if (!e || !pred_latent || !out) return GP_ERR_INVALID;
-    return guard(e, [&] {
-        check_ready(e, stream);
+    return guard_call(e, stream, [&] {
         Act z = e->from_nchw_f32(pred_latent, B, e->cfg.vae_latent_channels, h, w, 64);
         // decode_pred (genpercept_pipeline.py:507-526): channel mean for 1-channel modes, no clip / shift
         e->decode_to(z, 1.0f / e->cfg.vae_scaling_factor, out, mean3, 1);
-        e->drop(z);
-        finish_call(e);
     });
 }
 
 gp_status gp_vae_mid_attention(gp_engine* e, int decoder, const float* x, int B, int h, int w, float* out, void* stream) {
     if (!e || !x || !out) return GP_ERR_INVALID;
-    return guard(e, [&] {
-        check_ready(e, stream);
+    return guard_call(e, stream, [&] {
         const std::string name = decoder ? "vae.decoder.mid_block.attentions.0" : "vae.encoder.mid_block.attentions.0";
         const int C = e->vattn.at(name).C;
         Act a = e->from_nchw_f32(x, B, C, h, w, C);
         Act y = e->vae_attention(a, name);
-        e->drop(a);
+        a.reset();
         e->to_nchw_f32(y, C, out);
-        e->drop(y);
-        finish_call(e);
     });
 }
 
 gp_status gp_dpt_head(gp_engine* e, const float* const* feats, int B, int h, int w, float* out, void* stream) {
     if (!e || !feats || !out) return GP_ERR_INVALID;
-    return guard(e, [&] {
-        check_ready(e, stream);
+    return guard_call(e, stream, [&] {
         if (!e->dpt_w_dev) throw std::logic_error("DPT head weights were not loaded");
         const int h2 = (h - 1) / 2 + 1, w2 = (w - 1) / 2 + 1;  // UNet stride-2 pad-1 downsamples
         const int hs[4] = {h, h, h2, (h2 - 1) / 2 + 1}, ws[4] = {w, w, w2, (w2 - 1) / 2 + 1};
         Act f[4];
         for (int i = 0; i < 4; ++i) f[i] = e->from_nchw_f32(feats[i], B, e->cfg.dpt_neck[i], hs[i], ws[i], e->cfg.dpt_neck[i]);
-        e->dpt_head(f, out);
-        for (int i = 0; i < 4; ++i) e->drop(f[i]);
-        finish_call(e);
+        const Act* fp[4] = {&f[0], &f[1], &f[2], &f[3]};
+        e->dpt_head(fp, out);
     });
 }
 
