@@ -260,6 +260,272 @@ __global__ __launch_bounds__(64) void eval_metric_finalise_kernel(const double* 
     }
 }
 
+// ---- surface normals (gp_eval_normal) ------------------------------------------------------------------------------------------------------
+// The per-image quantity of eval_metrics.normal_angular_error -- the reference's angular_loss (genpercept/losses/geometry_losses.py:550-590)
+// in float64, operation by operation -- for maps that are on the GPU, plus the exact median of the device's own angles:
+//   angle    p, g = double(x) (decoded: double(x) * 2 - 1, eval_metrics.decode_normals); num = (p0 g0 + p1 g1) + p2 g2; |x| = sqrt((x0 x0 + x1 x1)
+//            + x2 x2); den = max(|p|, 1e-8) max(|g|, 1e-8); ang = acos(min(max(num / den, -1 + 1e-4), 1 - 1e-4)); deg = ang * (180 / pi).
+//            Products, sums, division and sqrt are correctly rounded on both sides, so acos sees the host's argument bit for bit.
+//   sums     n, sum ang, sum deg, sum deg^2 and the three counts over the valid pixels, slabs as above.
+//   median   the angle pass stores each angle's bit pattern (positive doubles order like their patterns; invalid pixels: all ones, never
+//            counted) and a radix select walks the key from the top: six digits (five of 11 bits, one of 9), per digit one histogram pass
+//            (integer LDS atomics, one slab of counts per workgroup) and one pick kernel per image that adds the slabs, finds the bucket of
+//            rank (n - 1) / 2 and of rank n / 2 and extends their prefixes.  The two prefixes may diverge at any digit; from then on each has
+//            its own histogram.  Integer sums do not depend on their order, so the result is bitwise reproducible and batch-independent.
+// 14 launches for every B; nothing is read back.
+constexpr int EN_NSUM = 7;        // n, sum ang, sum deg, sum deg^2, counts < 11.25, < 22.5, < 30
+constexpr int EN_OUT = 8;         // n_valid, mean_rad, mean_deg, median_deg, rmse_deg, within_11.25, within_22.5, within_30
+constexpr int EN_BINS = 2048;     // 11-bit digits
+constexpr int EN_PASSES = 6;      // 5 x 11 + 9 = 64 key bits
+constexpr int EN_STATE = 4;       // per image: prefix of rank (n-1)/2, prefix of rank n/2, the two remaining ranks (low | high 32 bits), active
+constexpr int EN_PICK_THREADS = 1024;
+constexpr int EN_PICK_GROUPS = EN_PICK_THREADS / 256;
+constexpr unsigned long long EN_INVALID_KEY = ~0ull;
+
+__host__ __device__ constexpr int en_shift(int pass) { return pass < 5 ? 53 - 11 * pass : 0; }
+__host__ __device__ constexpr int en_width(int pass) { return pass < 5 ? 11 : 9; }
+
+struct NormalWs {  // carving of the workspace: every part a multiple of 8 bytes and proportional to B
+    long long keys, slabs, hist, state, total;  // byte offsets
+};
+NormalWs normal_ws(long long B, long long hw) {
+    const long long nblk = eval_blocks(hw);
+    NormalWs w;
+    w.keys = 0;
+    w.slabs = w.keys + B * hw * 8;
+    w.hist = w.slabs + B * nblk * EN_NSUM * 8;
+    w.state = w.hist + B * nblk * 2 * EN_BINS * 4;
+    w.total = w.state + B * EN_STATE * 8;
+    return w;
+}
+
+// four consecutive values of one channel plane (0 beyond the image): one 16-byte load when the plane's base allows it and the quad is whole
+__device__ __forceinline__ void load_plane_quad(const float* __restrict__ plane, long long i0, long long hw, float (&v)[4]) {
+    if (((uintptr_t)plane & 15) == 0 && i0 + 4 <= hw) {
+        const float4 x = *reinterpret_cast<const float4*>(plane + i0);
+        v[0] = x.x, v[1] = x.y, v[2] = x.z, v[3] = x.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = i0 + j < hw ? plane[i0 + j] : 0.f;
+    }
+}
+
+// angle pass: grid (eval_blocks(H * W), B).  keys: [B][H * W] bit patterns; angles_out: optional [B][H * W] radians, NaN where invalid.
+__global__ __launch_bounds__(EV_THREADS) void normal_angle_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                                  const unsigned char* __restrict__ mask, long long hw, int decode,
+                                                                  unsigned long long* __restrict__ keys, double* __restrict__ angles_out,
+                                                                  double* __restrict__ ws) {
+    const long long b = blockIdx.y;
+    pred += b * 3 * hw, gt += b * 3 * hw, keys += b * hw;
+    if (mask) mask += b * hw;
+    if (angles_out) angles_out += b * hw;
+    const bool mvec = mask && ((uintptr_t)mask & 3) == 0;
+    const bool dp = (decode & 1) != 0, dg = (decode & 2) != 0;
+    const double lo = -1.0 + 1e-4, hi = 1.0 - 1e-4, to_deg = 180.0 / 3.141592653589793;
+    unsigned n = 0, c11 = 0, c22 = 0, c30 = 0;
+    double sa = 0.0, sd = 0.0, sdd = 0.0;
+    const long long nq = (hw + 3) / 4;
+    for (long long q = (long long)blockIdx.x * EV_THREADS + threadIdx.x; q < nq; q += (long long)gridDim.x * EV_THREADS) {
+        const long long i0 = q * 4;
+        float pf[3][4], gf[3][4];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            load_plane_quad(pred + c * hw, i0, hw, pf[c]);
+            load_plane_quad(gt + c * hw, i0, hw, gf[c]);
+        }
+        unsigned m = 0;
+        if (mask) {
+            if (mvec && i0 + 4 <= hw) {
+                m = *reinterpret_cast<const unsigned*>(mask + i0);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) m |= i0 + j < hw ? (unsigned)mask[i0 + j] << (8 * j) : 0u;
+            }
+        } else {  // base_dataset.py:416-418: (normal != 0).any(dim=0) on the stored ground truth
+#pragma unroll
+            for (int j = 0; j < 4; ++j) m |= (i0 + j < hw && (gf[0][j] != 0.f || gf[1][j] != 0.f || gf[2][j] != 0.f)) ? 1u << (8 * j) : 0u;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (i0 + j >= hw) break;
+            const bool valid = ((m >> (8 * j)) & 0xffu) != 0;
+            double ang = __builtin_nan("");
+            if (valid) {
+                double p[3], g[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    p[c] = (double)pf[c][j], g[c] = (double)gf[c][j];
+                    if (dp) p[c] = p[c] * 2.0 - 1.0;
+                    if (dg) g[c] = g[c] * 2.0 - 1.0;
+                }
+                const double num = (p[0] * g[0] + p[1] * g[1]) + p[2] * g[2];
+                const double np_ = sqrt((p[0] * p[0] + p[1] * p[1]) + p[2] * p[2]);
+                const double ng_ = sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
+                const double den = fmax(np_, 1e-8) * fmax(ng_, 1e-8);
+                ang = acos(fmin(fmax(num / den, lo), hi));
+                const double deg = ang * to_deg;
+                n += 1;
+                sa += ang;
+                sd += deg;
+                sdd += deg * deg;
+                c11 += deg < 11.25 ? 1u : 0u;
+                c22 += deg < 22.5 ? 1u : 0u;
+                c30 += deg < 30.0 ? 1u : 0u;
+            }
+            keys[i0 + j] = valid ? (unsigned long long)__double_as_longlong(ang) : EN_INVALID_KEY;
+            if (angles_out) angles_out[i0 + j] = ang;
+        }
+    }
+    double v[EN_NSUM] = {(double)n, sa, sd, sdd, (double)c11, (double)c22, (double)c30};
+    block_reduce_store<EN_NSUM>(v, ws + (b * gridDim.x + blockIdx.x) * EN_NSUM);
+}
+
+// after the angle pass: slabs in index order, the seven values that need no order statistic, and the state the selection starts from.
+// n = 0: seven NaN and an inactive state -- the selection kernels then do nothing for this image.
+__global__ __launch_bounds__(64) void normal_finalise_kernel(const double* __restrict__ ws, int nblk, double* __restrict__ out,
+                                                             unsigned long long* __restrict__ state) {
+    __shared__ double s_sum[EN_NSUM];
+    const int b = blockIdx.x;
+    if (threadIdx.x < EN_NSUM) s_sum[threadIdx.x] = sum_slabs<EN_NSUM>(ws + (long long)b * nblk * EN_NSUM, nblk, threadIdx.x);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double* o = out + (long long)b * EN_OUT;
+        unsigned long long* st = state + (long long)b * EN_STATE;
+        const double n = s_sum[0];
+        o[0] = n;
+        st[0] = 0, st[1] = 0;
+        if (n > 0.0) {
+            o[1] = s_sum[1] / n;
+            o[2] = s_sum[2] / n;
+            o[3] = __builtin_nan("");  // the last pick kernel writes the median
+            o[4] = sqrt(s_sum[3] / n);
+            o[5] = s_sum[4] / n;
+            o[6] = s_sum[5] / n;
+            o[7] = s_sum[6] / n;
+            const unsigned long long cnt = (unsigned long long)n;
+            st[2] = ((cnt - 1) / 2) | ((cnt / 2) << 32);
+            st[3] = 1;
+        } else {
+            for (int k = 1; k < EN_OUT; ++k) o[k] = __builtin_nan("");
+            st[2] = 0, st[3] = 0;
+        }
+    }
+}
+
+// one digit of the selection: per workgroup the counts of the digit among the keys that carry the prefix of rank (n-1)/2 (histogram 0) and,
+// once the prefixes differ, of rank n/2 (histogram 1).  grid (eval_blocks(H * W), B); slabs: [B][nblk][2][EN_BINS].
+__global__ __launch_bounds__(EV_THREADS) void normal_hist_kernel(const unsigned long long* __restrict__ keys, long long hw, int pass,
+                                                                 const unsigned long long* __restrict__ state, unsigned* __restrict__ hist) {
+    __shared__ unsigned s_h[2][EN_BINS];
+    const long long b = blockIdx.y;
+    const unsigned long long* st = state + b * EN_STATE;
+    if (st[3] == 0) return;  // no valid pixel: no rank
+    const unsigned long long p0 = st[0], p1 = st[1];
+    const bool two = p0 != p1;
+    for (int k = threadIdx.x; k < 2 * EN_BINS; k += EV_THREADS) (&s_h[0][0])[k] = 0;
+    __syncthreads();
+    keys += b * hw;
+    const int shift = en_shift(pass), width = en_width(pass);
+    const unsigned dmask = (1u << width) - 1u;
+    const long long stride = (long long)gridDim.x * EV_THREADS;
+    for (long long i = (long long)blockIdx.x * EV_THREADS + threadIdx.x; i < hw; i += 4 * stride) {
+        unsigned long long k[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) k[u] = i + u * stride < hw ? keys[i + u * stride] : EN_INVALID_KEY;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (k[u] == EN_INVALID_KEY) continue;
+            const unsigned long long top = pass == 0 ? 0ull : k[u] >> (shift + width);
+            const unsigned d = (unsigned)(k[u] >> shift) & dmask;
+            if (top == p0) atomicAdd(&s_h[0][d], 1u);
+            if (two && top == p1) atomicAdd(&s_h[1][d], 1u);
+        }
+    }
+    __syncthreads();
+    unsigned* slab = hist + (b * gridDim.x + blockIdx.x) * (2 * EN_BINS);
+    const int nwrite = two ? 2 * EN_BINS : EN_BINS;
+    for (int k = threadIdx.x; k < nwrite; k += EV_THREADS) slab[k] = (&s_h[0][0])[k];
+}
+
+// after a histogram pass, one workgroup per image: add the slabs (thread t of each of the four groups owns bins 8t .. 8t + 7 of every fourth
+// slab), find for each rank the bucket that holds it, extend the prefix and make the rank relative to the bucket.  The last digit completes the
+// two keys: median = (lo * (180 / pi) + hi * (180 / pi)) / 2, np.median's rule for the degrees.
+__global__ __launch_bounds__(EN_PICK_THREADS) void normal_pick_kernel(const unsigned* __restrict__ hist, int nblk, int pass,
+                                                                      unsigned long long* __restrict__ state, double* __restrict__ out) {
+    __shared__ unsigned s_cnt[EN_PICK_GROUPS][EN_BINS];
+    __shared__ unsigned s_bin[2], s_rank[2];
+    const long long b = blockIdx.x;
+    unsigned long long* st = state + b * EN_STATE;
+    if (st[3] == 0) return;
+    const unsigned long long p[2] = {st[0], st[1]};
+    const unsigned rank[2] = {(unsigned)(st[2] & 0xffffffffull), (unsigned)(st[2] >> 32)};
+    const bool two = p[0] != p[1];
+    const int t = threadIdx.x & 255, grp = threadIdx.x >> 8;
+    const int width = en_width(pass), nbins = 1 << width;
+    if (threadIdx.x < 2) s_bin[threadIdx.x] = 0, s_rank[threadIdx.x] = 0;
+    for (int h = 0; h < (two ? 2 : 1); ++h) {
+        unsigned c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll 8  // (independent loads, integer sums)
+        for (int j = grp; j < nblk; j += EN_PICK_GROUPS) {
+            const uint2* s = reinterpret_cast<const uint2*>(hist + ((b * nblk + j) * 2 + h) * EN_BINS + 8 * t);  // (the workspace is 8-byte aligned)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint2 a = s[k];
+                c[2 * k] += a.x, c[2 * k + 1] += a.y;
+            }
+        }
+        __syncthreads();  // (second histogram: the scan below has finished with s_cnt)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s_cnt[grp][8 * t + k] = c[k];
+        __syncthreads();
+        for (int k = threadIdx.x; k < EN_BINS; k += EN_PICK_THREADS) {
+            unsigned a = s_cnt[0][k];
+#pragma unroll
+            for (int g = 1; g < EN_PICK_GROUPS; ++g) a += s_cnt[g][k];
+            s_cnt[0][k] = a;
+        }
+        __syncthreads();
+        if (threadIdx.x < 64) {  // wave 0: lane l owns bins [l * per, (l + 1) * per), an inclusive scan of the lane totals, then a walk
+            const int per = nbins / 64, lane = threadIdx.x;
+            unsigned mine = 0;
+            for (int k = 0; k < per; ++k) mine += s_cnt[0][lane * per + k];
+            unsigned incl = mine;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const unsigned o = __shfl_up(incl, off, 64);
+                if (lane >= off) incl += o;
+            }
+            const unsigned excl = incl - mine;
+            for (int r = 0; r < 2; ++r) {
+                if (two ? r != h : false) continue;
+                const unsigned want = rank[r];
+                if (want >= excl && want < incl) {
+                    unsigned before = excl;
+                    int k = 0;
+                    for (; k < per - 1; ++k) {
+                        const unsigned cb = s_cnt[0][lane * per + k];
+                        if (want < before + cb) break;
+                        before += cb;
+                    }
+                    s_bin[r] = (unsigned)(lane * per + k);
+                    s_rank[r] = want - before;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long k0 = (p[0] << width) | s_bin[0], k1 = (p[1] << width) | s_bin[1];
+        st[0] = k0, st[1] = k1;
+        st[2] = (unsigned long long)s_rank[0] | ((unsigned long long)s_rank[1] << 32);
+        if (pass == EN_PASSES - 1) {
+            const double to_deg = 180.0 / 3.141592653589793;
+            const double lo = __longlong_as_double((long long)k0) * to_deg, hi = __longlong_as_double((long long)k1) * to_deg;
+            out[b * EN_OUT + 3] = (lo + hi) / 2.0;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -283,6 +549,37 @@ gp_status gp_eval_depth(const float* pred, const float* gt, const unsigned char*
     hipLaunchKernelGGL(eval_fit_finalise_kernel, dim3(B), dim3(64), 0, s, (const double*)ws, alignment != 0 ? nblk : 0, out);
     hipLaunchKernelGGL(eval_metric_kernel, dim3(nblk, B), dim3(EV_THREADS), 0, s, pred, gt, mask, H, W, alignment, min_depth, max_depth, (const double*)out, ws);
     hipLaunchKernelGGL(eval_metric_finalise_kernel, dim3(B), dim3(64), 0, s, (const double*)ws, nblk, out);
+    return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
+}
+
+long long gp_eval_normal_workspace(int B, int H, int W) {
+    if (B < 1 || H < 1 || W < 1) return 0;
+    return normal_ws(B, (long long)H * W).total;
+}
+
+gp_status gp_eval_normal(const float* pred, const float* gt, const unsigned char* mask, int B, int H, int W, int decode, double* out,
+                         double* angles_out, void* workspace, long long workspace_bytes, void* stream) {
+    if (!pred || !gt || !out || !workspace) return GP_ERR_INVALID;
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) return GP_ERR_INVALID;
+    if (decode < 0 || decode > 3 || (!mask && (decode & 2) != 0)) return GP_ERR_INVALID;
+    if ((((uintptr_t)workspace | (uintptr_t)out | (uintptr_t)angles_out) & 7) != 0) return GP_ERR_INVALID;
+    const long long hw = (long long)H * W;
+    const NormalWs w = normal_ws(B, hw);
+    if (workspace_bytes < w.total) return GP_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)workspace;
+    unsigned long long* keys = (unsigned long long*)(base + w.keys);
+    double* slabs = (double*)(base + w.slabs);
+    unsigned* hist = (unsigned*)(base + w.hist);
+    unsigned long long* state = (unsigned long long*)(base + w.state);
+    const int nblk = eval_blocks(hw);
+    hipLaunchKernelGGL(normal_angle_kernel, dim3(nblk, B), dim3(EV_THREADS), 0, s, pred, gt, mask, hw, decode, keys, angles_out, slabs);
+    hipLaunchKernelGGL(normal_finalise_kernel, dim3(B), dim3(64), 0, s, (const double*)slabs, nblk, out, state);
+    for (int pass = 0; pass < EN_PASSES; ++pass) {
+        hipLaunchKernelGGL(normal_hist_kernel, dim3(nblk, B), dim3(EV_THREADS), 0, s, (const unsigned long long*)keys, hw, pass,
+                           (const unsigned long long*)state, hist);
+        hipLaunchKernelGGL(normal_pick_kernel, dim3(B), dim3(EN_PICK_THREADS), 0, s, (const unsigned*)hist, nblk, pass, state, out);
+    }
     return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
 }
 

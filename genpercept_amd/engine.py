@@ -150,6 +150,8 @@ SYMBOLS = {
     "gp_postprocess": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "gp_eval_depth_workspace": (_ll, [_i, _i, _i]),
     "gp_eval_depth": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _ll, _vp]),
+    "gp_eval_normal_workspace": (_ll, [_i, _i, _i]),
+    "gp_eval_normal": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
     "gp_ensemble_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gp_ensemble_workspace": (_ll, [_i, _i, _i, _i]),
     "gp_ensemble_reduce": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
@@ -949,6 +951,60 @@ def eval_depth(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, alignme
                 raise ValueError(f"image {i}: least-squares alignment needs at least 2 fit pixels and a non-singular system (n_fit = {int(row[3])})")
     names = list(METRICS.keys())
     return [{k: float(row[4 + j]) for j, k in enumerate(names)} for row in raw], (raw[:, 0].copy(), raw[:, 1].copy(), raw[:, 2].astype("int64"))
+
+
+NORMAL_METRICS = ("mean_rad", "mean_deg", "median_deg", "rmse_deg", "within_11.25", "within_22.5", "within_30")  # normal_angular_error's keys
+
+
+def _normal_maps(x: torch.Tensor, name: str) -> torch.Tensor:
+    if x.dim() == 3:
+        x = x[None]
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"{name}: expected [B, 3, H, W] (or [3, H, W]), got {tuple(x.shape)}")
+    return x
+
+
+def eval_normal_raw(pred: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.Tensor] = None, pred_encoded: bool = True, gt_encoded: bool = False,
+                    want_angles: bool = False):
+    """gp_eval_normal on device tensors: float64 [B, 8] ON THE DEVICE = n_valid, then the seven values of eval_metrics.normal_angular_error in
+    its order (NaN for an image without a valid pixel); with want_angles also the float64 [B, H, W] angles in radians (NaN where invalid).
+    pred, gt: [B, 3, H, W] or [3, H, W]; *_encoded: the map is the pipeline's [0, 1] encoding (decode_normals); mask: [B, H, W], [B, 1, H, W] or
+    [H, W], bool or integer, None = "any stored gt channel != 0" (not with gt_encoded).  Enqueued on the current stream, no synchronisation."""
+    lib = load_library()
+    pred, gt = _normal_maps(pred, "pred"), _normal_maps(gt, "gt")
+    assert pred.is_cuda and gt.is_cuda
+    if pred.shape != gt.shape:
+        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have one shape")
+    if mask is None and gt_encoded:
+        raise ValueError("the derived validity rule (gt != 0) needs the signed ground truth: pass a mask with gt_encoded")
+    pred, gt = pred.to(torch.float32).contiguous(), gt.to(torch.float32).contiguous()
+    b, _, h, w = (int(v) for v in pred.shape)
+    if mask is not None:
+        mask = _eval_maps(mask, "mask")
+        assert mask.is_cuda
+        if tuple(mask.shape) != (b, h, w):
+            raise ValueError(f"mask {tuple(mask.shape)} does not match the maps {(b, h, w)}")
+        mask = (mask.contiguous().view(torch.uint8) if mask.dtype == torch.bool else (mask != 0).view(torch.uint8)).contiguous()
+    out = torch.empty((b, 8), dtype=torch.float64, device=pred.device)
+    angles = torch.empty((b, h, w), dtype=torch.float64, device=pred.device) if want_angles else None
+    nbytes = int(lib.gp_eval_normal_workspace(b, h, w))
+    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=pred.device)
+    st = lib.gp_eval_normal(pred.data_ptr(), gt.data_ptr(), _ptr(mask), b, h, w, int(bool(pred_encoded)) | int(bool(gt_encoded)) << 1, out.data_ptr(),
+                            _ptr(angles), ws.data_ptr(), nbytes, _stream_ptr(pred.device))
+    if st != GP_OK:
+        raise RuntimeError(f"gp_eval_normal failed ({st})")
+    return (out, angles) if want_angles else out
+
+
+def eval_normal(pred: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.Tensor] = None, pred_encoded: bool = True, gt_encoded: bool = False):
+    """eval_metrics.normal_angular_error for a batch of maps that are on the device (arguments as `eval_normal_raw`).  Returns (one dict per
+    image with normal_angular_error's seven names, n_valid as an int64 numpy array [B]).  Raises ValueError naming the image when it has no
+    valid pixel.  One device -> host copy of B x 8 doubles."""
+    raw = eval_normal_raw(pred, gt, mask, pred_encoded, gt_encoded).cpu().numpy()
+    for i, row in enumerate(raw):
+        if row[0] == 0:
+            raise ValueError(f"image {i}: no valid pixel to evaluate normals on (n_valid = 0)")
+    return [{k: float(row[1 + j]) for j, k in enumerate(NORMAL_METRICS)} for row in raw], raw[:, 0].astype("int64")
 
 
 ENSEMBLE_REDUCTION = {"median": 0, "mean": 1}

@@ -242,20 +242,32 @@ def run_inference(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_
     return written
 
 
-def _write_eval_files(output_dir: str, alignment: Optional[str], names: List[str], per_sample, result: Dict[str, float], prediction_dir: str,
-                      dataset: str) -> None:
-    """eval.py:217-244: `per_sample_metrics-<alignment>.csv` and `eval_metrics-<alignment>.txt`."""
-    cfg = DATASETS[dataset]
+def _write_metric_files(output_dir: str, tag: str, names: List[str], per_sample, result: Dict[str, float], header: str) -> None:
+    """`per_sample_metrics<tag>.csv` (one row per prediction file) and `eval_metrics<tag>.txt` (header, metric names, means)."""
     os.makedirs(output_dir, exist_ok=True)
-    tag = f"-{alignment}" if alignment else ""
     with open(os.path.join(output_dir, f"per_sample_metrics{tag}.csv"), "w") as f:
         f.write("filename," + ",".join(names) + "\n")
         for nm, vals in per_sample:
             f.write(nm + "," + ",".join(str(v) for v in vals) + "\n")
     with open(os.path.join(output_dir, f"eval_metrics{tag}.txt"), "w") as f:
-        f.write(f"Evaluation metrics:\n    of predictions: {prediction_dir}\n    on dataset: {dataset}\n")
-        f.write(f"min_depth = {cfg['min_depth']}\nmax_depth = {cfg['max_depth']}\n")
+        f.write(header)
         f.write("  ".join(names) + "\n" + "  ".join(f"{result[k]:.6g}" for k in names) + "\n")
+
+
+def _write_eval_files(output_dir: str, alignment: Optional[str], names: List[str], per_sample, result: Dict[str, float], prediction_dir: str,
+                      dataset: str) -> None:
+    """eval.py:217-244: `per_sample_metrics-<alignment>.csv` and `eval_metrics-<alignment>.txt`."""
+    cfg = DATASETS[dataset]
+    header = f"Evaluation metrics:\n    of predictions: {prediction_dir}\n    on dataset: {dataset}\n"
+    header += f"min_depth = {cfg['min_depth']}\nmax_depth = {cfg['max_depth']}\n"
+    _write_metric_files(output_dir, f"-{alignment}" if alignment else "", names, per_sample, result, header)
+
+
+def _write_normal_eval_files(output_dir: str, names: List[str], per_sample, result: Dict[str, float], prediction_dir: Optional[str],
+                             gt_column: int) -> None:
+    """`per_sample_metrics-normal.csv` and `eval_metrics-normal.txt`, laid out like the depth files."""
+    header = f"Evaluation metrics:\n    of predictions: {prediction_dir}\n    on normals: column {gt_column} of the filename list\n"
+    _write_metric_files(output_dir, "-normal", names, per_sample, result, header)
 
 
 def evaluate_predictions(prediction_dir: str, base_dir: str, samples: Sequence[Sequence[str]], dataset: str = "nyu",
@@ -289,6 +301,116 @@ def evaluate_predictions(prediction_dir: str, base_dir: str, samples: Sequence[S
     return result
 
 
+# ---- surface normals: ground truth and the `.npy` route ---------------------------------------------------------------------------------
+NORMAL_METRICS = ["mean_rad", "mean_deg", "median_deg", "rmse_deg", "within_11.25", "within_22.5", "within_30"]  # normal_angular_error's keys, in order
+
+
+def read_gt_normal(path: str) -> np.ndarray:
+    """Ground-truth normals as float32 [3, H, W]: a `.npy` of signed, linear, not necessarily unit vectors stored [H, W, 3] or [3, H, W] -- the
+    raster the reference's _load_normal_data yields for column 3 of a filename-list line (src/dataset/base_dataset.py:362-363).  Other
+    formats: pass a `read_gt` callable to the evaluation functions."""
+    if os.path.splitext(path)[1].lower() != ".npy":
+        raise ValueError(f"{path}: normal ground truth is read from .npy files only (pass read_gt= for other formats)")
+    n = np.load(path)
+    if n.ndim != 3 or 3 not in (n.shape[0], n.shape[-1]):
+        raise ValueError(f"{path}: expected [H, W, 3] or [3, H, W], got {n.shape}")
+    if n.shape[-1] == 3:  # [H, W, 3] (a [3, H, 3] array is read as three rows of it: the raster's own layout wins)
+        n = np.moveaxis(n, -1, 0)
+    return np.ascontiguousarray(n, dtype=np.float32)
+
+
+def normal_valid_mask(gt: np.ndarray) -> np.ndarray:
+    """base_dataset.py:416-418: a pixel is valid where any of the three ground-truth channels is non-zero.  gt [3, H, W] -> bool [H, W]."""
+    return (np.asarray(gt) != 0).any(axis=0)
+
+
+def _normal_path(s: Sequence[str], gt_column: int) -> Optional[str]:
+    return s[gt_column] if len(s) > gt_column and s[gt_column] != "None" else None
+
+
+def _normal_pred_name(rgb_rel: str, name_mode: FileNameMode) -> str:
+    return os.path.join(os.path.dirname(rgb_rel), get_pred_name(os.path.basename(rgb_rel), name_mode, suffix=".npy"))
+
+
+def evaluate_normal_predictions(prediction_dir: str, base_dir: str, samples: Sequence[Sequence[str]], name_mode: FileNameMode, gt_column: int = 3,
+                                output_dir: Optional[str] = None, read_gt: Optional[Callable[[str], np.ndarray]] = None) -> Dict[str, float]:
+    """The `.npy` route for what `run_inference(mode="normal")` writes ([H, W, 3] in [0, 1]): per image decode_normals ->
+    normal_angular_error over normal_valid_mask(gt), then the mean of the per-image values (eval.py's reduction).  Samples without a normal
+    path (column gt_column absent or "None") or without a prediction file are skipped.  Optionally writes `eval_metrics-normal.txt` and
+    `per_sample_metrics-normal.csv`."""
+    names = list(NORMAL_METRICS)
+    sums = {k: 0.0 for k in names}
+    per_sample = []
+    n = 0
+    for s in samples:
+        rel = _normal_path(s, gt_column)
+        if rel is None:
+            continue
+        pred_name = _normal_pred_name(s[0], name_mode)
+        pred_path = os.path.join(prediction_dir, pred_name)
+        if not os.path.exists(pred_path):
+            continue
+        gt = (read_gt or read_gt_normal)(os.path.join(base_dir, rel))
+        pred = em.decode_normals(np.load(pred_path))
+        if tuple(pred.shape) != tuple(gt.shape):
+            raise ValueError(f"{s[0]}: prediction {tuple(pred.shape)} and ground truth {tuple(gt.shape)} differ in size")
+        m = em.normal_angular_error(pred, gt, normal_valid_mask(gt))
+        for k in names:
+            sums[k] += m[k]
+        per_sample.append((pred_name, [m[k] for k in names]))
+        n += 1
+    result = {k: (sums[k] / n if n else float("nan")) for k in names}
+    if output_dir is not None:
+        _write_normal_eval_files(output_dir, names, per_sample, result, prediction_dir, gt_column)
+    return result
+
+
+# ---- the loops where predictions never leave the GPU ------------------------------------------------------------------------------------
+def _evaluation_loop(samples: Sequence[Sequence[str]], keep: Callable, load: Callable, score_group: Callable, names: List[str], batch_size: int,
+                     rank: int, world: int, prefetch: int):
+    """The skeleton `infer_and_evaluate` and `infer_and_evaluate_normals` share.  `samples` filtered by `keep`, then sharded
+    (`shard_range`), the index in the filtered list riding along; images decoded ahead by `load(sample)` and grouped by size, at most batch_size
+    per group; `score_group([((index, sample), image), ...])` -> one list of metric values (in `names` order) per image.  With
+    torch.distributed initialised the rows of all ranks are combined: float64 sums and a count by all_reduce, rows by all_gather_object.
+    Returns (rows [(index, sample, values)] in sample order, means over all samples, whether this rank writes the files)."""
+    import torch
+    samples = [s for s in samples if keep(s)]
+    lo, hi = _shard(len(samples), rank, world) if world > 1 else (0, len(samples))
+    items = [(i, samples[i]) for i in range(lo, hi)]  # the index in the filtered list rides along: the rows of all ranks are ordered by it
+    rows = []  # (sample index, sample, metric values)
+    for group in _size_groups(_decode_ahead(items, lambda it: load(it[1]), prefetch), batch_size):
+        values = score_group(group)
+        assert len(values) == len(group)
+        for ((idx, smp), _), vals in zip(group, values):
+            rows.append((idx, list(smp), [float(v) for v in vals]))
+
+    acc = np.zeros(len(names) + 1, dtype=np.float64)  # metric sums of this rank, then its image count
+    for _, _, vals in rows:
+        acc[:-1] += vals
+        acc[-1] += 1
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
+        t = torch.from_numpy(acc).to(dev)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        acc = t.cpu().numpy()
+        parts: list = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, rows)
+        rows = [r for part in parts for r in part]
+        writer = dist.get_rank() == 0
+    else:
+        writer = True
+    rows.sort(key=lambda r: r[0])
+    n = int(acc[-1])
+    result = {k: (float(acc[j]) / n if n else float("nan")) for j, k in enumerate(names)}
+    return rows, result, writer
+
+
+def _save_prediction(prediction_dir: str, pred_name: str, pred_np: np.ndarray) -> None:
+    os.makedirs(os.path.dirname(os.path.join(prediction_dir, pred_name)), exist_ok=True)
+    np.save(os.path.join(prediction_dir, pred_name), pred_np)
+
+
 def infer_and_evaluate(pipe, base_dir: str, samples: Sequence[Sequence[str]], dataset: str, output_dir: Optional[str] = None, batch_size: int = 4,
                        rank: int = 0, world: int = 1, alignment: Optional[str] = "least_square", alignment_max_res: Optional[int] = None,
                        save_predictions: bool = False, evaluator: Optional[Callable] = None, mode: str = "depth", denoise_steps: int = 1,
@@ -312,11 +434,11 @@ def infer_and_evaluate(pipe, base_dir: str, samples: Sequence[Sequence[str]], da
     if save_predictions and prediction_dir is None:
         raise ValueError("save_predictions needs prediction_dir or output_dir")
     rgb_crop = kitti_benchmark_crop if cfg.get("kitti_bm_crop") else None
-    samples = [s for s in samples if len(s) < 2 or s[1] != "None"]
-    lo, hi = _shard(len(samples), rank, world) if world > 1 else (0, len(samples))
-    items = [(i, samples[i]) for i in range(lo, hi)]  # the index in the filtered list rides along: the rows of all ranks are ordered by it
-    rows = []  # (sample index, prediction name, metric values)
-    for group in _size_groups(_decode_ahead(items, lambda it: _load_rgb(base_dir, it[1][0], rgb_crop), prefetch), batch_size):
+
+    def pred_name_of(smp):
+        return os.path.join(os.path.dirname(smp[0]), get_pred_name(os.path.basename(smp[0]), cfg["name_mode"], suffix=".npy"))
+
+    def score_group(group):
         pred = pipe.predict_batch_device([img for _, img in group], mode, processing_res=processing_res, match_input_res=match_input_res,
                                          resample_method=resample_method, fix_timesteps=fix_timesteps, prompt=prompt,
                                          denoising_steps=denoise_steps, ensemble_size=ensemble_size)
@@ -332,33 +454,64 @@ def infer_and_evaluate(pipe, base_dir: str, samples: Sequence[Sequence[str]], da
         gt_t = torch.from_numpy(np.stack(gts)).to(pred.device, non_blocking=True)
         vm_t = torch.from_numpy(np.stack(vms)).to(pred.device, non_blocking=True)
         metrics = evaluator(pred[:, 0], gt_t, vm_t, alignment, alignment_max_res, cfg["min_depth"], cfg["max_depth"])[0]
-        pred_host = pred[:, 0].cpu().numpy() if save_predictions else None
-        for j, ((idx, smp), _) in enumerate(group):
-            pred_name = os.path.join(os.path.dirname(smp[0]), get_pred_name(os.path.basename(smp[0]), cfg["name_mode"], suffix=".npy"))
-            if save_predictions:
-                os.makedirs(os.path.dirname(os.path.join(prediction_dir, pred_name)), exist_ok=True)
-                np.save(os.path.join(prediction_dir, pred_name), pred_host[j])
-            rows.append((idx, pred_name, [float(metrics[j][k]) for k in names]))
+        if save_predictions:
+            pred_host = pred[:, 0].cpu().numpy()
+            for j, ((_, smp), _) in enumerate(group):
+                _save_prediction(prediction_dir, pred_name_of(smp), pred_host[j])
+        return [[metrics[j][k] for k in names] for j in range(len(group))]
 
-    acc = np.zeros(len(names) + 1, dtype=np.float64)  # metric sums of this rank, then its image count
-    for _, _, vals in rows:
-        acc[:-1] += vals
-        acc[-1] += 1
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
-        t = torch.from_numpy(acc).to(dev)
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
-        acc = t.cpu().numpy()
-        parts: list = [None] * dist.get_world_size()
-        dist.all_gather_object(parts, rows)
-        rows = [r for part in parts for r in part]
-        writer = dist.get_rank() == 0
-    else:
-        writer = True
-    rows.sort(key=lambda r: r[0])
-    n = int(acc[-1])
-    result = {k: (float(acc[j]) / n if n else float("nan")) for j, k in enumerate(names)}
+    rows, result, writer = _evaluation_loop(samples, lambda s: len(s) < 2 or s[1] != "None", lambda smp: _load_rgb(base_dir, smp[0], rgb_crop),
+                                            score_group, names, batch_size, rank, world, prefetch)
     if output_dir is not None and writer:
-        _write_eval_files(output_dir, alignment, names, [(nm, vals) for _, nm, vals in rows], result, prediction_dir, dataset)
+        _write_eval_files(output_dir, alignment, names, [(pred_name_of(smp), vals) for _, smp, vals in rows], result, prediction_dir, dataset)
+    return result
+
+
+def infer_and_evaluate_normals(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_dir: Optional[str] = None,
+                               name_mode: FileNameMode = FileNameMode.id, gt_column: int = 3, batch_size: int = 4, rank: int = 0, world: int = 1,
+                               save_predictions: bool = False, prediction_dir: Optional[str] = None, evaluator: Optional[Callable] = None,
+                               read_gt: Optional[Callable[[str], np.ndarray]] = None, denoise_steps: int = 1, ensemble_size: int = 1,
+                               processing_res: int = 0, match_input_res: bool = True, resample_method: str = "bilinear", fix_timesteps=None,
+                               prompt: str = "", prefetch: int = 2) -> Dict[str, float]:
+    """`infer_and_evaluate` for surface normals: batches go through `pipe.predict_batch_device(mode="normal")`, the [B, 3, H, W] maps (the
+    [0, 1] encoding) stay on the device, and `evaluator` -- `engine.eval_normal` unless given: (pred, gt, mask, pred_encoded, gt_encoded) ->
+    (one dict per image with NORMAL_METRICS, ...) -- scores them there against the signed ground truth of column gt_column (read_gt_normal
+    or `read_gt`), decoded on the host and uploaded per batch, with mask None: the derived rule of normal_valid_mask.  What it computes per
+    image is `evaluate_normal_predictions`' quantity; sharding, the torch.distributed combination, the rank-0 files (`eval_metrics-normal.txt`,
+    `per_sample_metrics-normal.csv`) and the return value on every rank are `infer_and_evaluate`'s.  save_predictions: the maps are also
+    written as `run_inference(mode="normal")` would, [H, W, 3] `.npy` under prediction_dir (default: output_dir)."""
+    import torch
+    names = list(NORMAL_METRICS)
+    if evaluator is None:
+        from .engine import eval_normal as evaluator
+    if prediction_dir is None:
+        prediction_dir = output_dir
+    if save_predictions and prediction_dir is None:
+        raise ValueError("save_predictions needs prediction_dir or output_dir")
+
+    def score_group(group):
+        pred = pipe.predict_batch_device([img for _, img in group], "normal", processing_res=processing_res, match_input_res=match_input_res,
+                                         resample_method=resample_method, fix_timesteps=fix_timesteps, prompt=prompt,
+                                         denoising_steps=denoise_steps, ensemble_size=ensemble_size)
+        if pred.dim() != 4 or pred.shape[0] != len(group) or pred.shape[1] != 3:
+            raise ValueError(f"normal evaluation needs three-channel maps [B, 3, H, W], got {tuple(pred.shape)}")
+        gts = []
+        for (_, smp), _ in group:
+            gt = (read_gt or read_gt_normal)(os.path.join(base_dir, _normal_path(smp, gt_column)))
+            if tuple(gt.shape) != tuple(pred.shape[-3:]):
+                raise ValueError(f"{smp[0]}: prediction {tuple(pred.shape[-3:])} and ground truth {tuple(gt.shape)} differ in size")
+            gts.append(np.asarray(gt, dtype=np.float32))
+        gt_t = torch.from_numpy(np.stack(gts)).to(pred.device, non_blocking=True)
+        metrics = evaluator(pred, gt_t, None, True, False)[0]
+        if save_predictions:
+            pred_host = pred.cpu().numpy()
+            for j, ((_, smp), _) in enumerate(group):
+                _save_prediction(prediction_dir, _normal_pred_name(smp[0], name_mode), np.transpose(pred_host[j], (1, 2, 0)))
+        return [[metrics[j][k] for k in names] for j in range(len(group))]
+
+    rows, result, writer = _evaluation_loop(samples, lambda s: _normal_path(s, gt_column) is not None, lambda smp: _load_rgb(base_dir, smp[0], None),
+                                            score_group, names, batch_size, rank, world, prefetch)
+    if output_dir is not None and writer:
+        _write_normal_eval_files(output_dir, names, [(_normal_pred_name(smp[0], name_mode), vals) for _, smp, vals in rows], result, prediction_dir,
+                                 gt_column)
     return result

@@ -16,6 +16,8 @@
  *   gp_infer_steps    single_infer for archs marigold / rgb_blending: the denoising loop with the DDIM update
  *                                                                   genpercept_pipeline.py:413-422,447-465; ddim.py:144-217; run.py:361-368
  *   gp_eval_depth     eval.py's per-image alignment + metrics               eval.py:168-215; src/util/alignment.py:29-94; src/util/metric.py:34-158
+ *   gp_eval_normal    the angular error of angular_loss per image + summary statistics   genpercept/losses/geometry_losses.py:550-590;
+ *                       ground-truth column and validity rule                 src/dataset/base_dataset.py:362-363,416-418
  *   gp_ensemble_gather, gp_ensemble_reduce
  *                     ensemble_depth's tensor half (the BFGS fit stays on the host)   genpercept/util/ensemble.py:43-205;
  *                                                                   genpercept_pipeline.py:289-298
@@ -210,6 +212,29 @@ gp_status gp_postprocess(const float* pred, int B, int C, int h, int w, float* p
 long long gp_eval_depth_workspace(int B, int H, int W);   /* bytes; 0 for B, H or W < 1 */
 gp_status gp_eval_depth(const float* pred, const float* gt, const unsigned char* mask, int B, int H, int W, int alignment, int fit_cols,
                         float fit_inv_scale, float min_depth, float max_depth, double* out, void* workspace, long long workspace_bytes, void* stream);
+
+/* ---- surface-normal evaluation on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation; csrc/eval.hip) ----
+ * Per image the angle of the reference's angular_loss (genpercept/losses/geometry_losses.py:550-590) between prediction and ground truth at
+ * every valid pixel, in float64 and operation by operation what eval_metrics.normal_angular_error computes, and its summary statistics; the
+ * ground truth is column 3 of a filename-list line (src/dataset/base_dataset.py:362-363), valid where any channel is non-zero (:416-418);
+ * the per-image-then-mean reduction is eval.py's and stays with the caller.
+ * pred, gt: fp32 [B][3][H][W].  decode: bit 0 = pred is the pipeline's [0, 1] encoding, bit 1 = gt is; decoding is n = double(x) * 2 - 1.
+ * mask: uint8 [B][H][W], non-zero = valid, or NULL: valid = any of the three stored gt channels != 0 (NULL with decode bit 1 is refused).
+ * num = (p0 g0 + p1 g1) + p2 g2, |x| = sqrt((x0 x0 + x1 x1) + x2 x2), ang = acos(min(max(num / (max(|p|, 1e-8) max(|g|, 1e-8)), -1 + 1e-4),
+ * 1 - 1e-4)), deg = ang * (180 / pi), no FMA: the argument of acos is bitwise the host's, only acos itself may differ in its last bits.
+ * out: double [B][8] = n_valid, mean_rad, mean_deg, median_deg, rmse_deg, within_11.25, within_22.5, within_30 (the last seven NaN when
+ * n_valid = 0).  median_deg is the EXACT order statistic of the device's own angles, (lo + hi) / 2 of ranks (n - 1) / 2 and n / 2 in degrees
+ * (np.median): a radix select over the angles' bit patterns, six digits from the top, integer histograms in LDS, one slab per workgroup.
+ * angles_out: optional double [B][H][W], the per-pixel angle in radians, NaN at invalid pixels.
+ * Sums are float64 in a fixed order that depends on H * W alone, histogram counts are integers: an image's eight values are bitwise the
+ * same from call to call and for every batch it is part of.  workspace: DEVICE scratch of at least the workspace entry's byte count
+ * (8-byte aligned; 8 bytes per pixel for the keys plus the slabs), free again once the stream has passed the call.  Fourteen kernel launches
+ * on `stream` for every B (angle pass, finaliser, 6 x (histogram, pick)), no global atomics, nothing read back.
+ * GP_ERR_INVALID before any HIP call: null pred / gt / out / workspace, B, H or W < 1, B > 65535, H * W > 2^31 - 1, decode outside 0..3,
+ * out / angles_out / workspace not 8-byte aligned, workspace_bytes too small. */
+long long gp_eval_normal_workspace(int B, int H, int W);      /* bytes; 0 for B, H or W < 1; proportional to B; multiple of 8 */
+gp_status gp_eval_normal(const float* pred, const float* gt, const unsigned char* mask, int B, int H, int W, int decode,
+                         double* out, double* angles_out, void* workspace, long long workspace_bytes, void* stream);
 
 /* ---- test-time ensembling on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation, no atomics; csrc/ensemble.hip) ----
  * The tensor half of ensemble_depth (genpercept/util/ensemble.py:43-205, called at genpercept_pipeline.py:289-298) for the E members of each of

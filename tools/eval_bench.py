@@ -1,4 +1,4 @@
-"""Time the device depth evaluation against the host evaluation, and the batched device loop on the tiny pipeline.
+"""Time the device depth (or, with --normals, surface-normal) evaluation against the host evaluation, and the batched device loop on the tiny pipeline.
 
   python tools/eval_bench.py --out profiles/<name>.json
 
@@ -8,6 +8,12 @@
    the prediction to the host.  The two sides' values are compared on the spot (they must agree to 1e-9).
 2. `infer_eval.infer_and_evaluate` images/s at batch_size 1 and 4 on the tiny synthetic-weight pipeline, 16 images of 480 x 640 in a temporary
    ScanNet-style tree (a measurement of the loop's overheads -- decode, upload, launch count --, not of the full-size model).
+
+  python tools/eval_bench.py --normals --out profiles/<name>.json
+
+3. `--normals` (instead of 1 and 2): `engine.eval_normal` (gp_eval_normal: the angle pass, 24 bytes + the mask byte in and an 8-byte key out per
+   pixel, then six selection passes of 8 bytes per pixel, plus the small finaliser / pick kernels) at 4 x 480 x 640 and 1 x 4032 x 6048 with the
+   derived validity rule, against `eval_metrics.normal_angular_error` on the same arrays on the host, timed and compared the same way.
 Needs a GPU; there is no CPU fall-back."""
 import argparse
 import json
@@ -71,6 +77,51 @@ def bench_eval(b, h, w, iters, host_runs):
                 host_over_device=min(host_ms) / dev_ms, worst_rel_device_vs_host=worst)
 
 
+def normal_case(b, h, w, seed):
+    """gt: Gaussian directions (float32, a twentieth of the pixels all-zero); pred: gt plus Gaussian noise, in the pipeline's [0, 1] encoding."""
+    rng = np.random.default_rng(seed)
+    gt = rng.standard_normal((b, 3, h, w), dtype=np.float32)
+    pred = gt + 0.35 * rng.standard_normal((b, 3, h, w), dtype=np.float32)
+    pred /= np.maximum(np.sqrt((pred * pred).sum(axis=1, keepdims=True)), 1e-6)
+    enc = ((pred + 1.0) * 0.5).astype(np.float32)
+    gt *= rng.random((b, 1, h, w), dtype=np.float32) >= 0.05
+    return enc, gt
+
+
+def bench_eval_normal(b, h, w, iters, host_runs):
+    from genpercept_amd import engine as ge
+    from genpercept_amd import eval_metrics as em
+    d = torch.device("cuda", 0)
+    enc, gt = normal_case(b, h, w, 2)
+    tp, tg = (torch.from_numpy(x).to(d) for x in (enc, gt))
+    for _ in range(3):
+        ge.eval_normal_raw(tp, tg)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        ge.eval_normal_raw(tp, tg)
+    e1.record()
+    torch.cuda.synchronize()
+    dev_ms = e0.elapsed_time(e1) / iters
+    t0 = time.perf_counter()
+    metrics, n_valid = ge.eval_normal(tp, tg)  # with the 8-double copy and the host synchronise
+    call_ms = (time.perf_counter() - t0) * 1e3
+    host_ms = []
+    for _ in range(host_runs):
+        t0 = time.perf_counter()
+        ref = [em.normal_angular_error(enc[i].astype(np.float64) * 2.0 - 1.0, gt[i], (gt[i] != 0).any(axis=0)) for i in range(b)]
+        host_ms.append((time.perf_counter() - t0) * 1e3)
+    worst = max(abs(metrics[i][k] - ref[i][k]) / abs(ref[i][k]) for i in range(b) for k in ref[i])
+    assert worst <= 1e-9, worst
+    angle_bytes, select_bytes = (24 + 8) * b * h * w, 6 * 8 * b * h * w  # mask None: no mask byte
+    nbytes = angle_bytes + select_bytes
+    return dict(shape=[b, h, w], n_valid=[int(v) for v in n_valid], device_ms_per_call=dev_ms, device_iters=iters, launches_per_call=14,
+                bytes_per_call=nbytes, angle_pass_bytes=angle_bytes, selection_bytes=select_bytes, device_gb_per_s=nbytes / dev_ms / 1e6,
+                device_call_with_sync_ms=call_ms, host_normal_angular_error_ms=min(host_ms), host_runs=host_runs,
+                host_over_device=min(host_ms) / dev_ms, worst_rel_device_vs_host=worst)
+
+
 def bench_loop(n_images, batch_sizes, repeats):
     from PIL import Image
     from genpercept_amd import GenPerceptPipeline
@@ -121,11 +172,16 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--skip-loop", action="store_true")
+    ap.add_argument("--normals", action="store_true", help="time engine.eval_normal against normal_angular_error instead")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU")
-    res = dict(device=torch.cuda.get_device_name(0), eval_depth=[bench_eval(1, 4032, 6048, a.iters, 1), bench_eval(4, 480, 640, a.iters, 3)])
-    if not a.skip_loop:
+    if a.normals:
+        res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box",
+                   eval_normal=[bench_eval_normal(4, 480, 640, a.iters, 3), bench_eval_normal(1, 4032, 6048, a.iters, 1)])
+    else:
+        res = dict(device=torch.cuda.get_device_name(0), eval_depth=[bench_eval(1, 4032, 6048, a.iters, 1), bench_eval(4, 480, 640, a.iters, 3)])
+    if not a.skip_loop and not a.normals:
         res["infer_and_evaluate"] = bench_loop(16, (1, 4), 3)
     text = json.dumps(res, indent=1)
     print(text)
