@@ -8,8 +8,10 @@
 //     [hi | lo | hi] ("A order"), the B operand (weights, keys, values) as [hi | hi | lo] ("B order"), so the kernels' inner loops, rings
 //     and swizzles are untouched and the accumulator never leaves fp32.
 //
-// This file holds the kernels that sit BETWEEN the matrix products in that mode: fp32 in, fp32 or split-bf16 out.  They are written for
-// exactness and simplicity (all HBM-bound, one read and one write of their tensor), not for the last 10 %.
+// This file holds the kernels that sit BETWEEN the matrix products in that mode and exist in no other: fp32 in, split-bf16 (or statistics) out.
+// They are written for exactness and simplicity (all HBM-bound, one read and one write of their tensor), not for the last 10 %.  The layout and
+// pointwise kernels with fp32 in AND out (concat, add, bilinear, the layout changes, ddim, decode epilogue, ...) are the float instantiations of
+// elementwise.hip's templates.
 // Reference call sites: genpercept_pipeline.py:399-526 (single_infer / encode_rgb / decode_pred), custom_unet.py:305-415, dpt_head.py:213-335.
 #include "common.h"
 #include "kernels.h"
@@ -241,21 +243,6 @@ __global__ __launch_bounds__(256) void c_layernorm_split_kernel(const float* __r
 }
 void launch_c_layernorm_split(const float* x, h16_t* out, const float* gamma, const float* beta, int rows, int C, float eps, hipStream_t s) {
     hipLaunchKernelGGL(c_layernorm_split_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, out, gamma, beta, rows, C, eps);
-}
-
-// ---- channel concat of two fp32 NHWC tensors ([hidden, skip], custom_unet.py:341-352) ---------------------------------------------------
-__global__ __launch_bounds__(256) void c_concat_kernel(const float* __restrict__ a, int Ca, const float* __restrict__ b, int Cb, float* __restrict__ out,
-                                                        long long pixels) {
-    const int va = Ca >> 2, vb = Cb >> 2, vt = va + vb;
-    const long long n = pixels * vt;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const long long p = i / vt;
-        const int v = (int)(i - p * vt);
-        *(float4*)(out + i * 4) = v < va ? *(const float4*)(a + p * Ca + v * 4) : *(const float4*)(b + p * Cb + (v - va) * 4);
-    }
-}
-void launch_c_concat(const float* a, int Ca, const float* b, int Cb, float* out, long long pixels, hipStream_t s) {
-    hipLaunchKernelGGL(c_concat_kernel, dim3(cgrid(pixels * ((Ca + Cb) / 4))), dim3(256), 0, s, a, Ca, b, Cb, out, pixels);
 }
 
 // ---- attention, unfused: head split -> batched logits GEMM (fp32) -> row softmax -> batched P.V GEMM -> head merge --------------------------
@@ -623,162 +610,4 @@ void launch_c_cross_attn_small(const float* q, const float* kc, const float* vc,
     const int heads = C / 64;
     const long long nrh = (long long)rows * heads;
     hipLaunchKernelGGL(c_cross_attn_small_kernel, dim3((unsigned)((nrh + 255) / 256)), dim3(256), 0, s, q, kc, vc, out, nrh, C, heads, L);
-}
-
-// ---- small layout / pointwise kernels (fp32 twins of elementwise.hip) --------------------------------------------------------------------
-// post_quant_conv (Cin, Cout <= 8) on the first Cin channels: out = W (in * in_scale) + bias, zero padded to ldo channels
-__global__ __launch_bounds__(256) void c_pointwise_small_kernel(const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ w,
-                                                                 const float* __restrict__ bias, long long pixels, int Cin, int Cout, int ldi, int ldo,
-                                                                 float in_scale) {
-    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (long long)gridDim.x * 256) {
-        float x[8], y[8];
-        for (int c = 0; c < Cin; ++c) x[c] = in[p * ldi + c] * in_scale;
-        for (int o = 0; o < Cout; ++o) {
-            float a = bias ? bias[o] : 0.f;
-            for (int c = 0; c < Cin; ++c) a += w[o * Cin + c] * x[c];
-            y[o] = a;
-        }
-        for (int o = 0; o < ldo; ++o) out[p * ldo + o] = o < Cout ? y[o] : 0.f;
-    }
-}
-void launch_c_pointwise_small(const float* in, float* out, const float* w, const float* bias, long long pixels, int Cin, int Cout, int ldi, int ldo,
-                              float in_scale, hipStream_t s) {
-    hipLaunchKernelGGL(c_pointwise_small_kernel, dim3(cgrid(pixels)), dim3(256), 0, s, in, out, w, bias, pixels, Cin, Cout, ldi, ldo, in_scale);
-}
-// decoder output NHWC fp32 (3 real channels, row stride ld) -> fp32 NCHW: optional channel mean, then (unless raw) clip / shift
-__global__ __launch_bounds__(256) void c_decode_epilogue_kernel(const float* __restrict__ in, float* __restrict__ out, int B, long long HW, int ld,
-                                                                 int mean3, int raw) {
-    const long long n = (long long)B * HW;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const float c[3] = {in[i * ld], in[i * ld + 1], in[i * ld + 2]};
-        const long long b = i / HW, p = i - b * HW;
-        if (mean3) {
-            float v = (c[0] + c[1] + c[2]) / 3.0f;
-            if (!raw) v = (fminf(fmaxf(v, -1.f), 1.f) + 1.f) * 0.5f;
-            out[b * HW + p] = v;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                float v = c[k];
-                if (!raw) v = (fminf(fmaxf(v, -1.f), 1.f) + 1.f) * 0.5f;
-                out[(b * 3 + k) * HW + p] = v;
-            }
-        }
-    }
-}
-void launch_c_decode_epilogue(const float* in, float* out, int B, int H, int W, int ld, int mean3, int raw, hipStream_t s) {
-    hipLaunchKernelGGL(c_decode_epilogue_kernel, dim3(cgrid((long long)B * H * W)), dim3(256), 0, s, in, out, B, (long long)H * W, ld, mean3, raw);
-}
-__global__ __launch_bounds__(256) void c_nchw_to_nhwc_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int C, long long HW, int Cpad) {
-    const long long n = (long long)B * HW * Cpad;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const int c = (int)(i % Cpad);
-        const long long bp = i / Cpad, b = bp / HW, p = bp - b * HW;
-        out[i] = c < C ? in[(b * C + c) * HW + p] : 0.f;
-    }
-}
-void launch_c_nchw_to_nhwc(const float* in, float* out, int B, int C, int H, int W, int Cpad, hipStream_t s) {
-    hipLaunchKernelGGL(c_nchw_to_nhwc_kernel, dim3(cgrid((long long)B * H * W * Cpad)), dim3(256), 0, s, in, out, B, C, (long long)H * W, Cpad);
-}
-__global__ __launch_bounds__(256) void c_nhwc_to_nchw_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int C, long long HW, int ld) {
-    const long long n = (long long)B * C * HW;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const long long p = i % HW, bc = i / HW;
-        const int c = (int)(bc % C);
-        const long long b = bc / C;
-        out[i] = in[(b * HW + p) * ld + c];
-    }
-}
-void launch_c_nhwc_to_nchw(const float* in, float* out, int B, int C, int H, int W, int ld, hipStream_t s) {
-    hipLaunchKernelGGL(c_nhwc_to_nchw_kernel, dim3(cgrid((long long)B * C * H * W)), dim3(256), 0, s, in, out, B, C, (long long)H * W, ld);
-}
-__global__ __launch_bounds__(256) void c_add_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, long long nvec) {
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long long)gridDim.x * 256) {
-        const float4 x = *(const float4*)(a + i * 4), y = *(const float4*)(b + i * 4);
-        *(float4*)(out + i * 4) = make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w);
-    }
-}
-void launch_c_add(const float* a, const float* b, float* out, long long n, hipStream_t s) {
-    hipLaunchKernelGGL(c_add_kernel, dim3(cgrid(n / 4)), dim3(256), 0, s, a, b, out, n / 4);
-}
-// bilinear resize of fp32 NHWC, PyTorch semantics (elementwise.hip: bilinear_kernel)
-__global__ __launch_bounds__(256) void c_bilinear_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int Hi, int Wi, int Ho, int Wo, int C,
-                                                          int align) {
-    const int nvec = C >> 2;
-    const long long n = (long long)B * Ho * Wo * nvec;
-    const float sy = align ? (Ho > 1 ? (float)(Hi - 1) / (float)(Ho - 1) : 0.f) : (float)Hi / (float)Ho;
-    const float sx = align ? (Wo > 1 ? (float)(Wi - 1) / (float)(Wo - 1) : 0.f) : (float)Wi / (float)Wo;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const int v = (int)(i % nvec);
-        long long t = i / nvec;
-        const int ox = (int)(t % Wo); t /= Wo;
-        const int oy = (int)(t % Ho);
-        const long long b = t / Ho;
-        const float fy = align ? oy * sy : fmaxf((oy + 0.5f) * sy - 0.5f, 0.f);
-        const float fx = align ? ox * sx : fmaxf((ox + 0.5f) * sx - 0.5f, 0.f);
-        const int y0 = min((int)fy, Hi - 1), x0 = min((int)fx, Wi - 1);
-        const int y1 = min(y0 + 1, Hi - 1), x1 = min(x0 + 1, Wi - 1);
-        const float ly = fy - (float)y0, lx = fx - (float)x0;
-        const float* base = in + b * Hi * Wi * C + v * 4;
-        const float4 a = *(const float4*)(base + ((long long)y0 * Wi + x0) * C), bq = *(const float4*)(base + ((long long)y0 * Wi + x1) * C);
-        const float4 c = *(const float4*)(base + ((long long)y1 * Wi + x0) * C), d = *(const float4*)(base + ((long long)y1 * Wi + x1) * C);
-        const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
-        *(float4*)(out + i * 4) = make_float4(w00 * a.x + w01 * bq.x + w10 * c.x + w11 * d.x, w00 * a.y + w01 * bq.y + w10 * c.y + w11 * d.y,
-                                              w00 * a.z + w01 * bq.z + w10 * c.z + w11 * d.z, w00 * a.w + w01 * bq.w + w10 * c.w + w11 * d.w);
-    }
-}
-void launch_c_bilinear(const float* in, float* out, int B, int Hi, int Wi, int Ho, int Wo, int C, int align_corners, hipStream_t s) {
-    hipLaunchKernelGGL(c_bilinear_kernel, dim3(cgrid((long long)B * Ho * Wo * (C / 4))), dim3(256), 0, s, in, out, B, Hi, Wi, Ho, Wo, C, align_corners);
-}
-// DPT head tail: out[p] = sum_c w[c] in[p][c] + bias (dpt_head.py head.4, 1x1 conv 32 -> 1)
-__global__ __launch_bounds__(256) void c_dpt_final_kernel(const float* __restrict__ in, const float* __restrict__ w, float bias, float* __restrict__ out,
-                                                           long long n, int Cin) {
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        float a = bias;
-        for (int v = 0; v < Cin; v += 4) {
-            const float4 x = *(const float4*)(in + i * Cin + v);
-            a += x.x * w[v] + x.y * w[v + 1] + x.z * w[v + 2] + x.w * w[v + 3];
-        }
-        out[i] = a;
-    }
-}
-void launch_c_dpt_final(const float* in, const float* w, float bias, float* out, int B, int HW, int Cin, hipStream_t s) {
-    const long long n = (long long)B * HW;
-    hipLaunchKernelGGL(c_dpt_final_kernel, dim3(cgrid(n)), dim3(256), 0, s, in, w, bias, out, n, Cin);
-}
-
-// ---- multi-step archs (elementwise.hip: ddim_init_kernel / ddim_step_kernel) with the UNet input tensor in fp32 -------------------------------
-__global__ __launch_bounds__(256) void c_ddim_init_kernel(const float* __restrict__ noise, float* __restrict__ lat, float* __restrict__ sample, int B,
-                                                           long long HW, int L, int ld, int off) {
-    const long long n = (long long)B * HW * L;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const int c = (int)(i % L);
-        const long long bp = i / L, b = bp / HW, p = bp - b * HW;
-        const float s = noise ? noise[(b * L + c) * HW + p] : lat[bp * ld + c];
-        sample[i] = s;
-        if (noise) lat[bp * ld + off + c] = s;
-    }
-}
-void launch_c_ddim_init(const float* noise_nchw, float* lat, float* sample, int B, int H, int W, int L, int ld, int off, hipStream_t s) {
-    hipLaunchKernelGGL(c_ddim_init_kernel, dim3(cgrid((long long)B * H * W * L)), dim3(256), 0, s, noise_nchw, lat, sample, B, (long long)H * W, L, ld, off);
-}
-__global__ __launch_bounds__(256) void c_ddim_step_kernel(const float* __restrict__ model, int ldm, float* __restrict__ sample, float* __restrict__ uin,
-                                                           int ldu, int off, float* __restrict__ x0_out, int ldx, long long pixels, int L, DdimCoef k) {
-    const long long n = pixels * L;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const int c = (int)(i % L);
-        const long long px = i / L;
-        const float m = model[px * ldm + c], s = sample[i];
-        float x0 = k.x0_sample * s + k.x0_model * m;
-        if (k.clip > 0.f) x0 = fminf(fmaxf(x0, -k.clip), k.clip);
-        const float eps = k.eps_sample * s + k.eps_model * m;
-        const float prev = k.prev_x0 * x0 + k.prev_eps * eps;
-        sample[i] = prev;
-        uin[px * ldu + off + c] = prev;
-        if (x0_out) x0_out[px * ldx + c] = x0;
-    }
-}
-void launch_c_ddim_step(const float* model, int ldm, float* sample, float* uin, int ldu, int off, float* x0_out, int ldx, long long pixels, int L,
-                        const DdimCoef& k, hipStream_t s) {
-    hipLaunchKernelGGL(c_ddim_step_kernel, dim3(cgrid(pixels * L)), dim3(256), 0, s, model, ldm, sample, uin, ldu, off, x0_out, ldx, pixels, L, k);
 }

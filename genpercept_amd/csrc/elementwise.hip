@@ -1,11 +1,51 @@
 // Layout / elementwise kernels (K9-K12 of SURVEY.md §2.3).  All HBM-bound; vectorised to 16 B per lane where the
-// layout allows, grid-stride loops capped at 2048 workgroups.
+// layout allows, grid-stride loops of 256 threads capped at Elem<T>::GRID_CAP workgroups (4096 on 16-bit tensors, 8192 on fp32 ones).
+//
+// The kernels that also sit between the matrix products of the contract precision (fp32 storage: contract.hip) are templates over the element
+// type T of the tensor, h16_t or float, instantiated for both; Elem<T> below is everything the two forms differ in.  Two things in it fix
+// output bits and must stay: set2 takes the two elements of one packed 16-bit word per loop iteration (in the fp16 library that loop shape keeps
+// bilinear's blend uncontracted, no mixed-precision FMA), and dot_add sums in each type's own association.
 #include "common.h"
 #include "kernels.h"
 
-static inline unsigned grid_for(long long n, int per_block = 256) {
-    long long g = (n + per_block - 1) / per_block;
-    if (g > 4096) g = 4096;
+template <typename T>
+struct Elem;
+template <>
+struct Elem<h16_t> {  // the library's 16-bit element (bf16, or fp16 with its saturating conversion)
+    static constexpr int N = 8, LOG_N = 3, GRID_CAP = 4096;  // N: elements per 16-byte vector
+    GP_DEV static float get(h16_t x) { return h16_to_f(x); }
+    GP_DEV static h16_t put(float v) { return f_to_h16(v); }
+    typedef uint4 Vec;  // 16 bytes of a tensor; at: element k as a float; set2: elements k (even) and k + 1 from two floats
+    GP_DEV static float at(const uint4& v, int k) { return (k & 1) ? h16_hi(((const unsigned*)&v)[k >> 1]) : h16_lo(((const unsigned*)&v)[k >> 1]); }
+    GP_DEV static void set2(uint4& v, int k, float lo, float hi) { ((unsigned*)&v)[k >> 1] = pack_h16x2(lo, hi); }
+    GP_DEV static void load3(const h16_t* p, float (&c)[3]) {  // a pixel's three real channels: one 8-byte read (rows are padded to 4 channels)
+        const uint2 x = *(const uint2*)p;
+        c[0] = h16_lo(x.x); c[1] = h16_hi(x.x); c[2] = h16_lo(x.y);
+    }
+    // a + <one 16-byte vector, its N weights>, the two elements of a packed word summed first
+    GP_DEV static float dot_add(float a, const uint4& x, const float* w) {
+#pragma unroll
+        for (int k = 0; k < 8; k += 2) a += at(x, k) * w[k] + at(x, k + 1) * w[k + 1];
+        return a;
+    }
+};
+template <>
+struct Elem<float> {  // contract precision: activations stored in fp32
+    static constexpr int N = 4, LOG_N = 2, GRID_CAP = 8192;
+    GP_DEV static float get(float x) { return x; }
+    GP_DEV static float put(float v) { return v; }
+    typedef float4 Vec;
+    GP_DEV static float at(const float4& v, int k) { return ((const float*)&v)[k]; }
+    GP_DEV static void set2(float4& v, int k, float lo, float hi) { ((float*)&v)[k] = lo; ((float*)&v)[k + 1] = hi; }
+    GP_DEV static void load3(const float* p, float (&c)[3]) { c[0] = p[0]; c[1] = p[1]; c[2] = p[2]; }
+    // the same with the four products summed first (NOT the 16-bit form's association: each keeps the bits it has always produced)
+    GP_DEV static float dot_add(float a, const float4& x, const float* w) { return a + (x.x * w[0] + x.y * w[1] + x.z * w[2] + x.w * w[3]); }
+};
+static_assert(Elem<h16_t>::N == 1 << Elem<h16_t>::LOG_N && Elem<float>::N == 1 << Elem<float>::LOG_N, "N = 2^LOG_N");
+
+static inline unsigned grid_for(long long n, int cap = Elem<h16_t>::GRID_CAP) {
+    long long g = (n + 255) / 256;
+    if (g > cap) g = cap;
     if (g < 1) g = 1;
     return (unsigned)g;
 }
@@ -38,21 +78,26 @@ void launch_rgb_prologue(const void* rgb, int is_u8, h16_t* out, int B, int H, i
     hipLaunchKernelGGL(rgb_prologue_kernel, dim3(grid_for(n)), dim3(256), 0, s, rgb, is_u8, out, B, (long long)H * W, Cpad);
 }
 
-// channel concat of two NHWC tensors (UNet skip connections: [hidden, skip])
-__global__ __launch_bounds__(256) void concat_kernel(const h16_t* __restrict__ a, int Ca, const h16_t* __restrict__ b, int Cb,
-                                                      h16_t* __restrict__ out, long long pixels) {
-    const int va = Ca >> 3, vb = Cb >> 3, vt = va + vb;
+// channel concat of two NHWC tensors (UNet skip connections: [hidden, skip], custom_unet.py:341-352): a copy of 16-byte vectors, va and vb
+// of them per pixel, whatever the element type
+__global__ __launch_bounds__(256) void concat_kernel(const uint4* __restrict__ a, int va, const uint4* __restrict__ b, int vb,
+                                                      uint4* __restrict__ out, long long pixels) {
+    const int vt = va + vb;
     const long long n = pixels * vt;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const long long p = i / vt;
         const int v = (int)(i - p * vt);
-        const uint4 x = v < va ? *(const uint4*)(a + p * Ca + v * 8) : *(const uint4*)(b + p * Cb + (v - va) * 8);
-        *(uint4*)(out + i * 8) = x;
+        out[i] = v < va ? a[p * va + v] : b[p * vb + (v - va)];
     }
 }
-void launch_concat(const h16_t* a, int Ca, const h16_t* b, int Cb, h16_t* out, long long pixels, hipStream_t s) {
-    hipLaunchKernelGGL(concat_kernel, dim3(grid_for(pixels * ((Ca + Cb) / 8))), dim3(256), 0, s, a, Ca, b, Cb, out, pixels);
+template <typename T>
+void launch_concat(const T* a, int Ca, const T* b, int Cb, T* out, long long pixels, hipStream_t s) {
+    constexpr int N = Elem<T>::N;
+    hipLaunchKernelGGL(concat_kernel, dim3(grid_for(pixels * ((Ca + Cb) / N), Elem<T>::GRID_CAP)), dim3(256), 0, s, (const uint4*)a, Ca / N,
+                       (const uint4*)b, Cb / N, (uint4*)out, pixels);
 }
+template void launch_concat(const h16_t*, int, const h16_t*, int, h16_t*, long long, hipStream_t);
+template void launch_concat(const float*, int, const float*, int, float*, long long, hipStream_t);
 
 // The same concat, also leaving the GroupNorm statistics of the tensor it writes: per (bm consecutive pixels, channel) {sum, CENTRED second
 // moment M2 = sum (x - tile mean)^2} in the tiling of the conv epilogues' mode 0 (mode 4 = CONCAT_STATS_MODE of gn_finalize_tiles_kernel), so the
@@ -106,87 +151,104 @@ void launch_concat_stats(const h16_t* a, int Ca, const h16_t* b, int Cb, h16_t* 
     hipLaunchKernelGGL(concat_stats_kernel, dim3((unsigned)(pixels / bm), ((Ca + Cb) / 8 + 255) / 256), dim3(256), 0, s, a, Ca, b, Cb, out, bm, part);
 }
 
-// fp32 NCHW -> bf16 NHWC with zero-padded channels (stage-level entry points: latents / features handed in by the host)
-__global__ __launch_bounds__(256) void nchw_f32_to_nhwc_kernel(const float* __restrict__ in, h16_t* __restrict__ out, int B, int C,
-                                                                long long HW, int Cpad) {
+// fp32 NCHW -> NHWC with zero-padded channels (stage-level entry points: latents / features handed in by the host)
+template <typename T>
+__global__ __launch_bounds__(256) void nchw_f32_to_nhwc_kernel(const float* __restrict__ in, T* __restrict__ out, int B, int C, long long HW,
+                                                                int Cpad) {
     const long long n = (long long)B * HW * Cpad;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const int c = (int)(i % Cpad);
         const long long bp = i / Cpad, b = bp / HW, p = bp - b * HW;
-        out[i] = c < C ? f_to_h16(in[(b * C + c) * HW + p]) : (h16_t)0;
+        out[i] = c < C ? Elem<T>::put(in[(b * C + c) * HW + p]) : (T)0;
     }
 }
-void launch_nchw_f32_to_nhwc(const float* in, h16_t* out, int B, int C, int H, int W, int Cpad, hipStream_t s) {
-    hipLaunchKernelGGL(nchw_f32_to_nhwc_kernel, dim3(grid_for((long long)B * H * W * Cpad)), dim3(256), 0, s, in, out, B, C,
+template <typename T>
+void launch_nchw_f32_to_nhwc(const float* in, T* out, int B, int C, int H, int W, int Cpad, hipStream_t s) {
+    hipLaunchKernelGGL(nchw_f32_to_nhwc_kernel<T>, dim3(grid_for((long long)B * H * W * Cpad, Elem<T>::GRID_CAP)), dim3(256), 0, s, in, out, B, C,
                        (long long)H * W, Cpad);
 }
+template void launch_nchw_f32_to_nhwc(const float*, h16_t*, int, int, int, int, int, hipStream_t);
+template void launch_nchw_f32_to_nhwc(const float*, float*, int, int, int, int, int, hipStream_t);
 
 // ---- multi-step archs (marigold / rgb_blending; genpercept_pipeline.py:413-422,447-465) ---------------------------------------------
 // The denoising state lives in fp32, pixel-major [B*h*w][L]; the UNet reads its 16-bit copy from channels [off, off+L) of the latent
 // tensor the encoder wrote (marigold: [rgb_latent, pred_latent] in channels 0..2L-1, "this order is important" :452; rgb_blending:
 // the state replaces the rgb latent in channels 0..L-1).
-__global__ __launch_bounds__(256) void ddim_init_kernel(const float* __restrict__ noise, h16_t* __restrict__ lat, float* __restrict__ sample,
-                                                         int B, long long HW, int L, int ld, int off) {
+template <typename T>
+__global__ __launch_bounds__(256) void ddim_init_kernel(const float* __restrict__ noise, T* __restrict__ lat, float* __restrict__ sample, int B,
+                                                         long long HW, int L, int ld, int off) {
     const long long n = (long long)B * HW * L;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const int c = (int)(i % L);
         const long long bp = i / L, b = bp / HW, p = bp - b * HW;
-        const float s = noise ? noise[(b * L + c) * HW + p] : h16_to_f(lat[bp * ld + c]);
+        const float s = noise ? noise[(b * L + c) * HW + p] : Elem<T>::get(lat[bp * ld + c]);
         sample[i] = s;
-        if (noise) lat[bp * ld + off + c] = f_to_h16(s);
+        if (noise) lat[bp * ld + off + c] = Elem<T>::put(s);
     }
 }
-void launch_ddim_init(const float* noise_nchw, h16_t* lat, float* sample, int B, int H, int W, int L, int ld, int off, hipStream_t s) {
-    hipLaunchKernelGGL(ddim_init_kernel, dim3(grid_for((long long)B * H * W * L)), dim3(256), 0, s, noise_nchw, lat, sample, B,
+template <typename T>
+void launch_ddim_init(const float* noise_nchw, T* lat, float* sample, int B, int H, int W, int L, int ld, int off, hipStream_t s) {
+    hipLaunchKernelGGL(ddim_init_kernel<T>, dim3(grid_for((long long)B * H * W * L, Elem<T>::GRID_CAP)), dim3(256), 0, s, noise_nchw, lat, sample, B,
                        (long long)H * W, L, ld, off);
 }
+template void launch_ddim_init(const float*, h16_t*, float*, int, int, int, int, int, int, hipStream_t);
+template void launch_ddim_init(const float*, float*, float*, int, int, int, int, int, int, hipStream_t);
 // One scheduler step in its affine form (genpercept_amd/scheduler.py: step_coefficients):
 //   x0 = clip(x0_sample * s + x0_model * m), eps = eps_sample * s + eps_model * m, s' = prev_x0 * x0 + prev_eps * eps.
-__global__ __launch_bounds__(256) void ddim_step_kernel(const h16_t* __restrict__ model, int ldm, float* __restrict__ sample,
-                                                         h16_t* __restrict__ uin, int ldu, int off, h16_t* __restrict__ x0_out, int ldx,
-                                                         long long pixels, int L, DdimCoef k) {
+template <typename T>
+__global__ __launch_bounds__(256) void ddim_step_kernel(const T* __restrict__ model, int ldm, float* __restrict__ sample, T* __restrict__ uin,
+                                                         int ldu, int off, T* __restrict__ x0_out, int ldx, long long pixels, int L, DdimCoef k) {
     const long long n = pixels * L;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const int c = (int)(i % L);
         const long long px = i / L;
-        const float m = h16_to_f(model[px * ldm + c]), s = sample[i];
+        const float m = Elem<T>::get(model[px * ldm + c]), s = sample[i];
         float x0 = k.x0_sample * s + k.x0_model * m;
         if (k.clip > 0.f) x0 = fminf(fmaxf(x0, -k.clip), k.clip);
         const float eps = k.eps_sample * s + k.eps_model * m;
         const float prev = k.prev_x0 * x0 + k.prev_eps * eps;
         sample[i] = prev;
-        uin[px * ldu + off + c] = f_to_h16(prev);
-        if (x0_out) x0_out[px * ldx + c] = f_to_h16(x0);
+        uin[px * ldu + off + c] = Elem<T>::put(prev);
+        if (x0_out) x0_out[px * ldx + c] = Elem<T>::put(x0);
     }
 }
-void launch_ddim_step(const h16_t* model, int ldm, float* sample, h16_t* uin, int ldu, int off, h16_t* x0_out, int ldx, long long pixels, int L,
-                      const DdimCoef& k, hipStream_t s) {
-    hipLaunchKernelGGL(ddim_step_kernel, dim3(grid_for(pixels * L)), dim3(256), 0, s, model, ldm, sample, uin, ldu, off, x0_out, ldx, pixels, L, k);
+template <typename T>
+void launch_ddim_step(const T* model, int ldm, float* sample, T* uin, int ldu, int off, T* x0_out, int ldx, long long pixels, int L, const DdimCoef& k,
+                      hipStream_t s) {
+    hipLaunchKernelGGL(ddim_step_kernel<T>, dim3(grid_for(pixels * L, Elem<T>::GRID_CAP)), dim3(256), 0, s, model, ldm, sample, uin, ldu, off, x0_out,
+                       ldx, pixels, L, k);
 }
+template void launch_ddim_step(const h16_t*, int, float*, h16_t*, int, int, h16_t*, int, long long, int, const DdimCoef&, hipStream_t);
+template void launch_ddim_step(const float*, int, float*, float*, int, int, float*, int, long long, int, const DdimCoef&, hipStream_t);
 
-// bf16 NHWC (row stride ld) -> fp32 NCHW
-__global__ __launch_bounds__(256) void nhwc_to_nchw_f32_kernel(const h16_t* __restrict__ in, float* __restrict__ out, int B, int C,
-                                                                long long HW, int ld) {
+// NHWC (row stride ld) -> fp32 NCHW
+template <typename T>
+__global__ __launch_bounds__(256) void nhwc_to_nchw_f32_kernel(const T* __restrict__ in, float* __restrict__ out, int B, int C, long long HW, int ld) {
     const long long n = (long long)B * C * HW;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const long long p = i % HW, bc = i / HW;
         const int c = (int)(bc % C);
         const long long b = bc / C;
-        out[i] = h16_to_f(in[(b * HW + p) * ld + c]);
+        out[i] = Elem<T>::get(in[(b * HW + p) * ld + c]);
     }
 }
-void launch_nhwc_to_nchw_f32(const h16_t* in, float* out, int B, int C, int H, int W, int ld, hipStream_t s) {
-    hipLaunchKernelGGL(nhwc_to_nchw_f32_kernel, dim3(grid_for((long long)B * C * H * W)), dim3(256), 0, s, in, out, B, C, (long long)H * W, ld);
+template <typename T>
+void launch_nhwc_to_nchw_f32(const T* in, float* out, int B, int C, int H, int W, int ld, hipStream_t s) {
+    hipLaunchKernelGGL(nhwc_to_nchw_f32_kernel<T>, dim3(grid_for((long long)B * C * H * W, Elem<T>::GRID_CAP)), dim3(256), 0, s, in, out, B, C,
+                       (long long)H * W, ld);
 }
+template void launch_nhwc_to_nchw_f32(const h16_t*, float*, int, int, int, int, int, hipStream_t);
+template void launch_nhwc_to_nchw_f32(const float*, float*, int, int, int, int, int, hipStream_t);
 
 // decoder output NHWC (3 real channels, row stride ld) -> fp32 NCHW [B][1|3][H][W]:
 // optional mean over the 3 channels, then (unless raw) clip(-1,1), (x+1)/2   (genpercept_pipeline.py:523-525,470-472)
-__global__ __launch_bounds__(256) void decode_epilogue_kernel(const h16_t* __restrict__ in, float* __restrict__ out, int B, long long HW,
-                                                               int ld, int mean3, int raw) {
+template <typename T>
+__global__ __launch_bounds__(256) void decode_epilogue_kernel(const T* __restrict__ in, float* __restrict__ out, int B, long long HW, int ld,
+                                                               int mean3, int raw) {
     const long long n = (long long)B * HW;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const uint2 rw = *(const uint2*)(in + i * ld);
-        float c[3] = {h16_lo(rw.x), h16_hi(rw.x), h16_lo(rw.y)};
+        float c[3];
+        Elem<T>::load3(in + i * ld, c);
         const long long b = i / HW, p = i - b * HW;
         if (mean3) {
             float v = (c[0] + c[1] + c[2]) / 3.0f;
@@ -202,9 +264,13 @@ __global__ __launch_bounds__(256) void decode_epilogue_kernel(const h16_t* __res
         }
     }
 }
-void launch_decode_epilogue(const h16_t* in, float* out, int B, int H, int W, int ld, int mean3, int raw, hipStream_t s) {
-    hipLaunchKernelGGL(decode_epilogue_kernel, dim3(grid_for((long long)B * H * W)), dim3(256), 0, s, in, out, B, (long long)H * W, ld, mean3, raw);
+template <typename T>
+void launch_decode_epilogue(const T* in, float* out, int B, int H, int W, int ld, int mean3, int raw, hipStream_t s) {
+    hipLaunchKernelGGL(decode_epilogue_kernel<T>, dim3(grid_for((long long)B * H * W, Elem<T>::GRID_CAP)), dim3(256), 0, s, in, out, B,
+                       (long long)H * W, ld, mean3, raw);
 }
+template void launch_decode_epilogue(const h16_t*, float*, int, int, int, int, int, int, hipStream_t);
+template void launch_decode_epilogue(const float*, float*, int, int, int, int, int, int, hipStream_t);
 
 // out[p][0..ldo) = {in[p][0..C) * scale, 0...}
 __global__ __launch_bounds__(256) void scale_pad_kernel(const h16_t* __restrict__ in, h16_t* __restrict__ out, long long pixels, int C,
@@ -222,24 +288,29 @@ void launch_scale_pad(const h16_t* in, h16_t* out, long long pixels, int C, int 
 
 // tiny 1x1 conv (Cin, Cout <= 8) on the first Cin channels of a padded NHWC tensor: out = W (in * in_scale) + bias, zero padded
 // to ldo channels.  Used for post_quant_conv (4->4) with in_scale = -1/0.18215 (pred_x0 = -v, then /scaling_factor).
-__global__ __launch_bounds__(256) void pointwise_small_kernel(const h16_t* __restrict__ in, h16_t* __restrict__ out, const float* __restrict__ w,
+template <typename T>
+__global__ __launch_bounds__(256) void pointwise_small_kernel(const T* __restrict__ in, T* __restrict__ out, const float* __restrict__ w,
                                                                const float* __restrict__ bias, long long pixels, int Cin, int Cout, int ldi,
                                                                int ldo, float in_scale) {
     for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (long long)gridDim.x * 256) {
         float x[8], y[8];
-        for (int c = 0; c < Cin; ++c) x[c] = h16_to_f(in[p * ldi + c]) * in_scale;
+        for (int c = 0; c < Cin; ++c) x[c] = Elem<T>::get(in[p * ldi + c]) * in_scale;
         for (int o = 0; o < Cout; ++o) {
             float a = bias ? bias[o] : 0.f;
             for (int c = 0; c < Cin; ++c) a += w[o * Cin + c] * x[c];
             y[o] = a;
         }
-        for (int o = 0; o < ldo; ++o) out[p * ldo + o] = o < Cout ? f_to_h16(y[o]) : (h16_t)0;
+        for (int o = 0; o < ldo; ++o) out[p * ldo + o] = o < Cout ? Elem<T>::put(y[o]) : (T)0;
     }
 }
-void launch_pointwise_small(const h16_t* in, h16_t* out, const float* w, const float* bias, long long pixels, int Cin, int Cout, int ldi,
-                            int ldo, float in_scale, hipStream_t s) {
-    hipLaunchKernelGGL(pointwise_small_kernel, dim3(grid_for(pixels)), dim3(256), 0, s, in, out, w, bias, pixels, Cin, Cout, ldi, ldo, in_scale);
+template <typename T>
+void launch_pointwise_small(const T* in, T* out, const float* w, const float* bias, long long pixels, int Cin, int Cout, int ldi, int ldo,
+                            float in_scale, hipStream_t s) {
+    hipLaunchKernelGGL(pointwise_small_kernel<T>, dim3(grid_for(pixels, Elem<T>::GRID_CAP)), dim3(256), 0, s, in, out, w, bias, pixels, Cin, Cout, ldi,
+                       ldo, in_scale);
 }
+template void launch_pointwise_small(const h16_t*, h16_t*, const float*, const float*, long long, int, int, int, int, float, hipStream_t);
+template void launch_pointwise_small(const float*, float*, const float*, const float*, long long, int, int, int, int, float, hipStream_t);
 
 __global__ __launch_bounds__(256) void relu_kernel(const h16_t* __restrict__ in, h16_t* __restrict__ out, long long nvec) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long long)gridDim.x * 256) {
@@ -257,26 +328,33 @@ void launch_relu(const h16_t* in, h16_t* out, long long n, hipStream_t s) {
     hipLaunchKernelGGL(relu_kernel, dim3(grid_for(n / 8)), dim3(256), 0, s, in, out, n / 8);
 }
 
-__global__ __launch_bounds__(256) void add_kernel(const h16_t* __restrict__ a, const h16_t* __restrict__ b, h16_t* __restrict__ out,
-                                                   long long nvec) {
+template <typename T>
+__global__ __launch_bounds__(256) void add_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, long long nvec) {
+    using E = Elem<T>;
+    typedef typename E::Vec Vec;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long long)gridDim.x * 256) {
-        const uint4 x = *(const uint4*)(a + i * 8), y = *(const uint4*)(b + i * 8);
-        const unsigned xw[4] = {x.x, x.y, x.z, x.w}, yw[4] = {y.x, y.y, y.z, y.w};
-        uint4 r;
-        unsigned* rw = (unsigned*)&r;
+        const Vec x = ((const Vec*)a)[i], y = ((const Vec*)b)[i];
+        Vec r;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) rw[k] = pack_h16x2(h16_lo(xw[k]) + h16_lo(yw[k]), h16_hi(xw[k]) + h16_hi(yw[k]));
-        *(uint4*)(out + i * 8) = r;
+        for (int k = 0; k < E::N; k += 2) E::set2(r, k, E::at(x, k) + E::at(y, k), E::at(x, k + 1) + E::at(y, k + 1));
+        ((Vec*)out)[i] = r;
     }
 }
-void launch_add(const h16_t* a, const h16_t* b, h16_t* out, long long n, hipStream_t s) {
-    hipLaunchKernelGGL(add_kernel, dim3(grid_for(n / 8)), dim3(256), 0, s, a, b, out, n / 8);
+template <typename T>
+void launch_add(const T* a, const T* b, T* out, long long n, hipStream_t s) {
+    const long long nvec = n / Elem<T>::N;
+    hipLaunchKernelGGL(add_kernel<T>, dim3(grid_for(nvec, Elem<T>::GRID_CAP)), dim3(256), 0, s, a, b, out, nvec);
 }
+template void launch_add(const h16_t*, const h16_t*, h16_t*, long long, hipStream_t);
+template void launch_add(const float*, const float*, float*, long long, hipStream_t);
 
-// bilinear resize of NHWC bf16, PyTorch semantics (align_corners True: src = dst*(in-1)/(out-1); False: (dst+.5)*in/out-.5, clamped at 0)
-__global__ __launch_bounds__(256) void bilinear_kernel(const h16_t* __restrict__ in, h16_t* __restrict__ out, int B, int Hi, int Wi, int Ho,
-                                                        int Wo, int C, int align) {
-    const int nvec = C >> 3;
+// bilinear resize of an NHWC tensor, PyTorch semantics (align_corners True: src = dst*(in-1)/(out-1); False: (dst+.5)*in/out-.5, clamped at 0)
+template <typename T>
+__global__ __launch_bounds__(256) void bilinear_kernel(const T* __restrict__ in, T* __restrict__ out, int B, int Hi, int Wi, int Ho, int Wo, int C,
+                                                        int align) {
+    using E = Elem<T>;
+    typedef typename E::Vec Vec;
+    const int nvec = C >> E::LOG_N;
     const long long n = (long long)B * Ho * Wo * nvec;
     const float sy = align ? (Ho > 1 ? (float)(Hi - 1) / (float)(Ho - 1) : 0.f) : (float)Hi / (float)Ho;
     const float sx = align ? (Wo > 1 ? (float)(Wi - 1) / (float)(Wo - 1) : 0.f) : (float)Wi / (float)Wo;
@@ -291,45 +369,45 @@ __global__ __launch_bounds__(256) void bilinear_kernel(const h16_t* __restrict__
         const int y0 = min((int)fy, Hi - 1), x0 = min((int)fx, Wi - 1);
         const int y1 = min(y0 + 1, Hi - 1), x1 = min(x0 + 1, Wi - 1);
         const float ly = fy - (float)y0, lx = fx - (float)x0;
-        const h16_t* base = in + b * Hi * Wi * C + v * 8;
-        const uint4 a = *(const uint4*)(base + ((long long)y0 * Wi + x0) * C), bq = *(const uint4*)(base + ((long long)y0 * Wi + x1) * C);
-        const uint4 c = *(const uint4*)(base + ((long long)y1 * Wi + x0) * C), d = *(const uint4*)(base + ((long long)y1 * Wi + x1) * C);
-        const unsigned aw[4] = {a.x, a.y, a.z, a.w}, bw[4] = {bq.x, bq.y, bq.z, bq.w}, cw[4] = {c.x, c.y, c.z, c.w}, dw[4] = {d.x, d.y, d.z, d.w};
+        const T* base = in + b * Hi * Wi * C + v * E::N;
+        const Vec a = *(const Vec*)(base + ((long long)y0 * Wi + x0) * C), bq = *(const Vec*)(base + ((long long)y0 * Wi + x1) * C);
+        const Vec c = *(const Vec*)(base + ((long long)y1 * Wi + x0) * C), d = *(const Vec*)(base + ((long long)y1 * Wi + x1) * C);
         const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
-        uint4 r;
-        unsigned* rw = (unsigned*)&r;
+        Vec r;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float lo = w00 * h16_lo(aw[k]) + w01 * h16_lo(bw[k]) + w10 * h16_lo(cw[k]) + w11 * h16_lo(dw[k]);
-            const float hi = w00 * h16_hi(aw[k]) + w01 * h16_hi(bw[k]) + w10 * h16_hi(cw[k]) + w11 * h16_hi(dw[k]);
-            rw[k] = pack_h16x2(lo, hi);
+        for (int k = 0; k < E::N; k += 2) {  // (one packed word per iteration: the fp16 library's blend stays uncontracted this way)
+            const float lo = w00 * E::at(a, k) + w01 * E::at(bq, k) + w10 * E::at(c, k) + w11 * E::at(d, k);
+            const float hi = w00 * E::at(a, k + 1) + w01 * E::at(bq, k + 1) + w10 * E::at(c, k + 1) + w11 * E::at(d, k + 1);
+            E::set2(r, k, lo, hi);
         }
-        *(uint4*)(out + i * 8) = r;
+        ((Vec*)out)[i] = r;
     }
 }
-void launch_bilinear(const h16_t* in, h16_t* out, int B, int Hi, int Wi, int Ho, int Wo, int C, int align_corners, hipStream_t s) {
-    hipLaunchKernelGGL(bilinear_kernel, dim3(grid_for((long long)B * Ho * Wo * (C / 8))), dim3(256), 0, s, in, out, B, Hi, Wi, Ho, Wo, C,
-                       align_corners);
+template <typename T>
+void launch_bilinear(const T* in, T* out, int B, int Hi, int Wi, int Ho, int Wo, int C, int align_corners, hipStream_t s) {
+    hipLaunchKernelGGL(bilinear_kernel<T>, dim3(grid_for((long long)B * Ho * Wo * (C / Elem<T>::N), Elem<T>::GRID_CAP)), dim3(256), 0, s, in, out, B,
+                       Hi, Wi, Ho, Wo, C, align_corners);
 }
+template void launch_bilinear(const h16_t*, h16_t*, int, int, int, int, int, int, int, hipStream_t);
+template void launch_bilinear(const float*, float*, int, int, int, int, int, int, int, hipStream_t);
 
-// DPT head tail: out[b][p] = sum_c w[c] * in[p][c] + bias  (input already ReLU'd by the producing conv), fp32 out
-__global__ __launch_bounds__(256) void dpt_final_kernel(const h16_t* __restrict__ in, const float* __restrict__ w, float bias,
-                                                         float* __restrict__ out, long long n, int Cin) {
+// DPT head tail: out[b][p] = sum_c w[c] * in[p][c] + bias  (dpt_head.py head.4, 1x1 conv 32 -> 1; input already ReLU'd by the producing conv)
+template <typename T>
+__global__ __launch_bounds__(256) void dpt_final_kernel(const T* __restrict__ in, const float* __restrict__ w, float bias, float* __restrict__ out,
+                                                         long long n, int Cin) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         float a = bias;
-        for (int v = 0; v < Cin; v += 8) {
-            const uint4 x = *(const uint4*)(in + i * Cin + v);
-            const unsigned xw[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) a += h16_lo(xw[k]) * w[v + 2 * k] + h16_hi(xw[k]) * w[v + 2 * k + 1];
-        }
+        for (int v = 0; v < Cin; v += Elem<T>::N) a = Elem<T>::dot_add(a, *(const typename Elem<T>::Vec*)(in + i * Cin + v), w + v);
         out[i] = a;
     }
 }
-void launch_dpt_final(const h16_t* in, const float* w, float bias, float* out, int B, int HW, int Cin, hipStream_t s) {
+template <typename T>
+void launch_dpt_final(const T* in, const float* w, float bias, float* out, int B, int HW, int Cin, hipStream_t s) {
     const long long n = (long long)B * HW;
-    hipLaunchKernelGGL(dpt_final_kernel, dim3(grid_for(n)), dim3(256), 0, s, in, w, bias, out, n, Cin);
+    hipLaunchKernelGGL(dpt_final_kernel<T>, dim3(grid_for(n, Elem<T>::GRID_CAP)), dim3(256), 0, s, in, w, bias, out, n, Cin);
 }
+template void launch_dpt_final(const h16_t*, const float*, float, float*, int, int, int, hipStream_t);
+template void launch_dpt_final(const float*, const float*, float, float*, int, int, int, hipStream_t);
 
 // per-image min-max normalisation (genpercept_pipeline.py:482, per image: SURVEY.md F10).  Two passes, deterministic.
 __global__ __launch_bounds__(256) void minmax_partial_kernel(const float* __restrict__ x, long long n, float* __restrict__ ws) {

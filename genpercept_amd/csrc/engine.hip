@@ -5,7 +5,7 @@
 //
 // Both precisions run ONE set of layer ops and schedules.  An `Act` is either a 16-bit tensor / split operand (`p`) or a stored fp32 tensor (`f`);
 // new_stored / new_product_input allocate the form the precision uses, conv / linear pick `.p` or `.f` of their input, residual and in-place target,
-// and each kernel pair (X / c_X) is chosen in one small op.  Only attention_c, the split-operand attention, has no 16-bit twin.
+// and each glue kernel's 16-bit or fp32 form is chosen in one small op.  Only attention_c, the split-operand attention, has no 16-bit twin.
 //
 // Lifetime: every activation and scratch buffer is a Pool::Buf (pool.h), a move-only owner that hands its buffer back to the pool when it ends; an
 // `Act` owns its tensor and its statistics partials, and whatever only reads one takes `const Act&`.  The pool recycles a buffer as soon as it is
@@ -1101,7 +1101,7 @@ struct gp_engine {
         const int cbm = (fuse_stats && !contract) ? concat_stats_bm((long long)h.H * h.W, h.pixels(), h.C + skip.C) : 0;
         mark("concat " + dims(cat));
         if (contract) {
-            launch_c_concat(h.f(), h.C, skip.f(), skip.C, cat.f(), h.pixels(), st);
+            launch_concat(h.f(), h.C, skip.f(), skip.C, cat.f(), h.pixels(), st);
         } else if (cbm) {  // the copy also leaves the statistics the resnet's first GroupNorm needs
             cat.stats = pool.alloc((size_t)(h.pixels() / cbm) * cat.C * 2 * sizeof(float));
             cat.st_mode = CONCAT_STATS_MODE;
@@ -1184,7 +1184,7 @@ struct gp_engine {
         const int L = cfg.vae_latent_channels;
         Act z = new_stored(z_in.B, z_in.H, z_in.W, 64);
         mark("post_quant_conv");
-        if (contract) launch_c_pointwise_small(z_in.f(), z.f(), pq_w_dev, pq_b_dev, z_in.pixels(), L, L, z_in.C, 64, in_scale, st);
+        if (contract) launch_pointwise_small(z_in.f(), z.f(), pq_w_dev, pq_b_dev, z_in.pixels(), L, L, z_in.C, 64, in_scale, st);
         else launch_pointwise_small(z_in.p(), z.p(), pq_w_dev, pq_b_dev, z_in.pixels(), L, L, z_in.C, 64, in_scale, st);
         return z;
     }
@@ -1231,7 +1231,7 @@ struct gp_engine {
     // decoder output NHWC (3 real channels) -> the caller's fp32 NCHW map: channel mean, clip / shift unless raw (genpercept_pipeline.py:523-525,469-472)
     void decode_epilogue(const Act& dec, float* out, int mean3, int raw) {
         mark("decode_epilogue");
-        if (dec.f()) launch_c_decode_epilogue(dec.f(), out, dec.B, dec.H, dec.W, dec.C, mean3, raw, st);
+        if (dec.f()) launch_decode_epilogue(dec.f(), out, dec.B, dec.H, dec.W, dec.C, mean3, raw, st);
         else launch_decode_epilogue(dec.p(), out, dec.B, dec.H, dec.W, dec.C, mean3, raw, st);
     }
     // the decode tail of an entry point: latent -> the caller's map (the fused tail kernel of vae_decode wrote `out` itself when no tensor comes back)
@@ -1243,7 +1243,7 @@ struct gp_engine {
     Act bilinear(const Act& x, int Ho, int Wo, int align_corners) {
         Act y = new_stored(x.B, Ho, Wo, x.C);
         mark("bilinear " + dims(y));
-        if (contract) launch_c_bilinear(x.f(), y.f(), x.B, x.H, x.W, Ho, Wo, x.C, align_corners, st);
+        if (contract) launch_bilinear(x.f(), y.f(), x.B, x.H, x.W, Ho, Wo, x.C, align_corners, st);
         else launch_bilinear(x.p(), y.p(), x.B, x.H, x.W, Ho, Wo, x.C, align_corners, st);
         return y;
     }
@@ -1257,13 +1257,13 @@ struct gp_engine {
     Act add(const Act& a, const Act& b) {
         Act y = new_stored(a.B, a.H, a.W, a.C);
         mark("add " + dims(a));
-        if (contract) launch_c_add(a.f(), b.f(), y.f(), a.pixels() * a.C, st);
+        if (contract) launch_add(a.f(), b.f(), y.f(), a.pixels() * a.C, st);
         else launch_add(a.p(), b.p(), y.p(), a.pixels() * a.C, st);
         return y;
     }
     void dpt_final(const Act& z, float* out_dev) {  // head.head.4 (1x1 to one channel), fp32 [B][H * W]
         mark("dpt_final " + dims(z));
-        if (contract) launch_c_dpt_final(z.f(), dpt_w_dev, dpt_b, out_dev, z.B, z.H * z.W, z.C, st);
+        if (contract) launch_dpt_final(z.f(), dpt_w_dev, dpt_b, out_dev, z.B, z.H * z.W, z.C, st);
         else launch_dpt_final(z.p(), dpt_w_dev, dpt_b, out_dev, z.B, z.H * z.W, z.C, st);
     }
     Act rcu(const Act& x, const std::string& p) {  // pre-activation residual unit (dpt_head.py:256-271)
@@ -1316,25 +1316,25 @@ struct gp_engine {
     Act from_nchw_f32(const float* src, int B, int C, int Hh, int Ww, int Cpad) {
         Act a = new_stored(B, Hh, Ww, Cpad);
         mark("nchw_f32_to_nhwc");
-        if (contract) launch_c_nchw_to_nhwc(src, a.f(), B, C, Hh, Ww, Cpad, st);
+        if (contract) launch_nchw_f32_to_nhwc(src, a.f(), B, C, Hh, Ww, Cpad, st);
         else launch_nchw_f32_to_nhwc(src, a.p(), B, C, Hh, Ww, Cpad, st);
         return a;
     }
     void to_nchw_f32(const Act& a, int C, float* dst) {
         mark("nhwc_to_nchw_f32");
-        if (a.f()) launch_c_nhwc_to_nchw(a.f(), dst, a.B, C, a.H, a.W, a.C, st);
+        if (a.f()) launch_nhwc_to_nchw_f32(a.f(), dst, a.B, C, a.H, a.W, a.C, st);
         else launch_nhwc_to_nchw_f32(a.p(), dst, a.B, C, a.H, a.W, a.C, st);
     }
 
     // multi-step archs: the fp32 denoising state `sample` and the UNet input `lat` (channels [off, off + L) hold the sample)
     void ddim_init(const float* noise_dev, const Act& lat, float* sample, int L, int off) {
         mark("ddim_init");
-        if (contract) launch_c_ddim_init(noise_dev, lat.f(), sample, lat.B, lat.H, lat.W, L, lat.C, off, st);
+        if (contract) launch_ddim_init(noise_dev, lat.f(), sample, lat.B, lat.H, lat.W, L, lat.C, off, st);
         else launch_ddim_init(noise_dev, lat.p(), sample, lat.B, lat.H, lat.W, L, lat.C, off, st);
     }
     void ddim_step(const Act& v, float* sample, const Act& lat, int L, int off, const Act& x0, bool last /* pred_x0 goes to x0 */, const DdimCoef& k) {
         mark("ddim_step");
-        if (contract) launch_c_ddim_step(v.f(), v.C, sample, lat.f(), lat.C, off, last ? x0.f() : nullptr, x0.C, lat.pixels(), L, k, st);
+        if (contract) launch_ddim_step(v.f(), v.C, sample, lat.f(), lat.C, off, last ? x0.f() : nullptr, x0.C, lat.pixels(), L, k, st);
         else launch_ddim_step(v.p(), v.C, sample, lat.p(), lat.C, off, last ? x0.p() : nullptr, x0.C, lat.pixels(), L, k, st);
     }
 

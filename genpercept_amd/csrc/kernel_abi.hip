@@ -496,8 +496,8 @@ gp_status gp_bilinear(const void* in, void* out, int B, int Hi, int Wi, int Ho, 
     return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
 }
 
-// ---- the elementwise / layout kernels between the matrix products (elementwise.hip), and with contract != 0 their fp32 twins (contract.hip, bf16
-// library only).  Everything a kernel would fault on is refused here, before any HIP call. ------------------------------------------------------
+// ---- the elementwise / layout kernels between the matrix products (elementwise.hip), and with contract != 0 their fp32 forms (the same templates
+// over float; contract.hip for the split outputs; bf16 library only).  Everything a kernel would fault on is refused here, before any HIP call. -----
 #define GP_LAUNCHED() (hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP)
 static bool al8(const void* p) { return ((uintptr_t)p & 7) == 0; }
 
@@ -517,7 +517,7 @@ gp_status gp_concat(const void* a, int Ca, const void* b, int Cb, void* out, lon
     const int v = contract ? 4 : 8;
     if ((contract && GP_F16) || !a || !b || !out || pixels < 1 || Ca < v || Cb < v || (Ca % v) || (Cb % v) || !al16(a) || !al16(b) || !al16(out))
         return GP_ERR_INVALID;
-    if (contract) launch_c_concat((const float*)a, Ca, (const float*)b, Cb, (float*)out, pixels, (hipStream_t)stream);
+    if (contract) launch_concat((const float*)a, Ca, (const float*)b, Cb, (float*)out, pixels, (hipStream_t)stream);
     else launch_concat((const h16_t*)a, Ca, (const h16_t*)b, Cb, (h16_t*)out, pixels, (hipStream_t)stream);
     return GP_LAUNCHED();
 }
@@ -563,21 +563,21 @@ gp_status gp_rgb_conv_in_stats(const void* rgb, int is_u8, const void* w_packed,
 
 gp_status gp_nchw_to_nhwc(const float* in, void* out, int B, int C, int H, int W, int Cpad, int contract, void* stream) {
     if ((contract && GP_F16) || !in || !out || B < 1 || C < 1 || H < 1 || W < 1 || Cpad < C) return GP_ERR_INVALID;
-    if (contract) launch_c_nchw_to_nhwc(in, (float*)out, B, C, H, W, Cpad, (hipStream_t)stream);
+    if (contract) launch_nchw_f32_to_nhwc(in, (float*)out, B, C, H, W, Cpad, (hipStream_t)stream);
     else launch_nchw_f32_to_nhwc(in, (h16_t*)out, B, C, H, W, Cpad, (hipStream_t)stream);
     return GP_LAUNCHED();
 }
 
 gp_status gp_nhwc_to_nchw(const void* in, float* out, int B, int C, int H, int W, int ld, int contract, void* stream) {
     if ((contract && GP_F16) || !in || !out || B < 1 || C < 1 || H < 1 || W < 1 || ld < C) return GP_ERR_INVALID;
-    if (contract) launch_c_nhwc_to_nchw((const float*)in, out, B, C, H, W, ld, (hipStream_t)stream);
+    if (contract) launch_nhwc_to_nchw_f32((const float*)in, out, B, C, H, W, ld, (hipStream_t)stream);
     else launch_nhwc_to_nchw_f32((const h16_t*)in, out, B, C, H, W, ld, (hipStream_t)stream);
     return GP_LAUNCHED();
 }
 
 gp_status gp_ddim_init(const float* noise_nchw, void* lat, float* sample, int B, int H, int W, int L, int ld, int off, int contract, void* stream) {
     if ((contract && GP_F16) || !lat || !sample || B < 1 || H < 1 || W < 1 || L < 1 || off < 0 || (long long)off + L > ld) return GP_ERR_INVALID;
-    if (contract) launch_c_ddim_init(noise_nchw, (float*)lat, sample, B, H, W, L, ld, off, (hipStream_t)stream);
+    if (contract) launch_ddim_init(noise_nchw, (float*)lat, sample, B, H, W, L, ld, off, (hipStream_t)stream);
     else launch_ddim_init(noise_nchw, (h16_t*)lat, sample, B, H, W, L, ld, off, (hipStream_t)stream);
     return GP_LAUNCHED();
 }
@@ -588,7 +588,7 @@ gp_status gp_ddim_update(const void* model, int ldm, float* sample, void* uin, i
         (x0_out && ldx < L))
         return GP_ERR_INVALID;
     const DdimCoef k{coef7_host[0], coef7_host[1], coef7_host[2], coef7_host[3], coef7_host[4], coef7_host[5], coef7_host[6]};
-    if (contract) launch_c_ddim_step((const float*)model, ldm, sample, (float*)uin, ldu, off, (float*)x0_out, ldx, pixels, L, k, (hipStream_t)stream);
+    if (contract) launch_ddim_step((const float*)model, ldm, sample, (float*)uin, ldu, off, (float*)x0_out, ldx, pixels, L, k, (hipStream_t)stream);
     else launch_ddim_step((const h16_t*)model, ldm, sample, (h16_t*)uin, ldu, off, (h16_t*)x0_out, ldx, pixels, L, k, (hipStream_t)stream);
     return GP_LAUNCHED();
 }
@@ -596,7 +596,7 @@ gp_status gp_ddim_update(const void* model, int ldm, float* sample, void* uin, i
 gp_status gp_decode_epilogue(const void* in, float* out, int B, int H, int W, int ld, int mean3, int raw, int contract, void* stream) {
     if ((contract && GP_F16) || !in || !out || B < 1 || H < 1 || W < 1 || ld < 3) return GP_ERR_INVALID;
     if (contract) {
-        launch_c_decode_epilogue((const float*)in, out, B, H, W, ld, mean3, raw, (hipStream_t)stream);
+        launch_decode_epilogue((const float*)in, out, B, H, W, ld, mean3, raw, (hipStream_t)stream);
     } else {
         if ((ld % 4) || !al8(in)) return GP_ERR_INVALID;  // (decode_epilogue_kernel reads a pixel's three channels as one uint2)
         launch_decode_epilogue((const h16_t*)in, out, B, H, W, ld, mean3, raw, (hipStream_t)stream);
@@ -613,7 +613,7 @@ gp_status gp_scale_pad(const void* in, void* out, long long pixels, int C, int l
 gp_status gp_pointwise_small(const void* in, void* out, const float* w, const float* bias, long long pixels, int Cin, int Cout, int ldi, int ldo, float in_scale,
                              int contract, void* stream) {
     if ((contract && GP_F16) || !in || !out || !w || pixels < 1 || Cin < 1 || Cin > 8 || Cout < 1 || Cout > 8 || ldi < Cin || ldo < Cout) return GP_ERR_INVALID;
-    if (contract) launch_c_pointwise_small((const float*)in, (float*)out, w, bias, pixels, Cin, Cout, ldi, ldo, in_scale, (hipStream_t)stream);
+    if (contract) launch_pointwise_small((const float*)in, (float*)out, w, bias, pixels, Cin, Cout, ldi, ldo, in_scale, (hipStream_t)stream);
     else launch_pointwise_small((const h16_t*)in, (h16_t*)out, w, bias, pixels, Cin, Cout, ldi, ldo, in_scale, (hipStream_t)stream);
     return GP_LAUNCHED();
 }
@@ -627,7 +627,7 @@ gp_status gp_relu(const void* in, void* out, long long n, void* stream) {
 gp_status gp_add(const void* a, const void* b, void* out, long long n, int contract, void* stream) {
     const int v = contract ? 4 : 8;
     if ((contract && GP_F16) || !a || !b || !out || n < v || (n % v) || !al16(a) || !al16(b) || !al16(out)) return GP_ERR_INVALID;
-    if (contract) launch_c_add((const float*)a, (const float*)b, (float*)out, n, (hipStream_t)stream);
+    if (contract) launch_add((const float*)a, (const float*)b, (float*)out, n, (hipStream_t)stream);
     else launch_add((const h16_t*)a, (const h16_t*)b, (h16_t*)out, n, (hipStream_t)stream);
     return GP_LAUNCHED();
 }
@@ -635,7 +635,7 @@ gp_status gp_add(const void* a, const void* b, void* out, long long n, int contr
 gp_status gp_dpt_final(const void* in, const float* w, float bias, float* out, int B, int HW, int Cin, int contract, void* stream) {
     const int v = contract ? 4 : 8;
     if ((contract && GP_F16) || !in || !w || !out || B < 1 || HW < 1 || Cin < v || (Cin % v) || !al16(in)) return GP_ERR_INVALID;
-    if (contract) launch_c_dpt_final((const float*)in, w, bias, out, B, HW, Cin, (hipStream_t)stream);
+    if (contract) launch_dpt_final((const float*)in, w, bias, out, B, HW, Cin, (hipStream_t)stream);
     else launch_dpt_final((const h16_t*)in, w, bias, out, B, HW, Cin, (hipStream_t)stream);
     return GP_LAUNCHED();
 }
@@ -680,7 +680,7 @@ gp_status gp_c_cross_attention(const float* q, const float* kc, const float* vc,
 
 gp_status gp_c_bilinear(const float* in, float* out, int B, int Hi, int Wi, int Ho, int Wo, int C, int align_corners, void* stream) {
     if (GP_F16 || !in || !out || B < 1 || Hi < 1 || Wi < 1 || Ho < 1 || Wo < 1 || C < 4 || (C % 4) || !al16(in) || !al16(out)) return GP_ERR_INVALID;
-    launch_c_bilinear(in, out, B, Hi, Wi, Ho, Wo, C, align_corners, (hipStream_t)stream);
+    launch_bilinear(in, out, B, Hi, Wi, Ho, Wo, C, align_corners, (hipStream_t)stream);
     return GP_LAUNCHED();
 }
 

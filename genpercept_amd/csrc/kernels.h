@@ -175,7 +175,8 @@ void launch_softmax_rows(const float* in, h16_t* out, int rows, int T, int ld, f
 bool softmax_rows_f16_supported(int ld);
 void launch_softmax_rows_f16(const void* in_f16, h16_t* out, int rows, int T, int ld, float scale, hipStream_t s);  // fp16 logits
 
-// Elementwise / layout kernels
+// Elementwise / layout kernels.  The launchers declared as templates take T = h16_t (the library's 16-bit element) or float (the fp32 tensors
+// of the contract precision); elementwise.hip instantiates both.
 void launch_rgb_prologue(const void* rgb, int is_u8, h16_t* out, int B, int H, int W, int Cpad, hipStream_t s);  // NCHW -> NHWC, x/255*2-1
 // fused RGB prologue + VAE-encoder conv_in (3 -> Cout, Cout % 32 == 0) + GroupNorm partial statistics (16x16 tiles) of the output
 int rgb_conv_in_rows(int B, int H, int W);  // statistics rows per image launch_rgb_conv_in writes (RGB_CONV_IN_STATS_MODE: {sum, centred M2} + pixel counts)
@@ -183,24 +184,34 @@ enum { RGB_CONV_IN_STATS_MODE = 3 };
 void launch_pack_k27(const h16_t* wt, int ldw, int Cout, h16_t* w27, hipStream_t s);  // [rows][9][64] conv layout -> compact [Cout][32]
 void launch_rgb_conv_in(const void* rgb, int is_u8, const h16_t* w27, const float* bias, h16_t* out, float* stats, int B, int H, int W, int Cout,
                         hipStream_t s);
-void launch_concat(const h16_t* a, int Ca, const h16_t* b, int Cb, h16_t* out, long long pixels, hipStream_t s);
+template <typename T>
+void launch_concat(const T* a, int Ca, const T* b, int Cb, T* out, long long pixels, hipStream_t s);
 int concat_stats_bm(long long hw, long long pixels, int channels);  // pixels per statistics tile launch_concat_stats can use for an image of hw pixels (0: none)
 void launch_concat_stats(const h16_t* a, int Ca, const h16_t* b, int Cb, h16_t* out, long long pixels, int bm, float* part, hipStream_t s);
 enum { CONCAT_STATS_MODE = 4 };  // what launch_groupnorm_from_partials takes for launch_concat_stats' partials: mode 0's tiling, {sum, centred M2}
 struct DdimCoef { float x0_sample, x0_model, eps_sample, eps_model, prev_x0, prev_eps, clip; };
-void launch_ddim_init(const float* noise_nchw, h16_t* lat, float* sample, int B, int H, int W, int L, int ld, int off, hipStream_t s);
-void launch_ddim_step(const h16_t* model, int ldm, float* sample, h16_t* uin, int ldu, int off, h16_t* x0_out, int ldx, long long pixels, int L,
-                      const DdimCoef& k, hipStream_t s);
-void launch_nchw_f32_to_nhwc(const float* in, h16_t* out, int B, int C, int H, int W, int Cpad, hipStream_t s);
-void launch_nhwc_to_nchw_f32(const h16_t* in, float* out, int B, int C, int H, int W, int ld, hipStream_t s);
-void launch_decode_epilogue(const h16_t* in, float* out, int B, int H, int W, int ld, int mean3, int raw, hipStream_t s);  // mean, clip, (x+1)/2
+template <typename T>
+void launch_ddim_init(const float* noise_nchw, T* lat, float* sample, int B, int H, int W, int L, int ld, int off, hipStream_t s);
+template <typename T>
+void launch_ddim_step(const T* model, int ldm, float* sample, T* uin, int ldu, int off, T* x0_out, int ldx, long long pixels, int L, const DdimCoef& k,
+                      hipStream_t s);
+template <typename T>
+void launch_nchw_f32_to_nhwc(const float* in, T* out, int B, int C, int H, int W, int Cpad, hipStream_t s);
+template <typename T>
+void launch_nhwc_to_nchw_f32(const T* in, float* out, int B, int C, int H, int W, int ld, hipStream_t s);
+template <typename T>
+void launch_decode_epilogue(const T* in, float* out, int B, int H, int W, int ld, int mean3, int raw, hipStream_t s);  // mean, clip, (x+1)/2
 void launch_scale_pad(const h16_t* in, h16_t* out, long long pixels, int C, int ldi, int ldo, float scale, hipStream_t s);
-void launch_pointwise_small(const h16_t* in, h16_t* out, const float* w, const float* bias, long long pixels, int Cin, int Cout, int ldi,
-                            int ldo, float in_scale, hipStream_t s);  // 1x1 conv for Cin, Cout <= 8 (post_quant_conv)
+template <typename T>
+void launch_pointwise_small(const T* in, T* out, const float* w, const float* bias, long long pixels, int Cin, int Cout, int ldi, int ldo,
+                            float in_scale, hipStream_t s);  // 1x1 conv for Cin, Cout <= 8 (post_quant_conv)
 void launch_relu(const h16_t* in, h16_t* out, long long n, hipStream_t s);
-void launch_add(const h16_t* a, const h16_t* b, h16_t* out, long long n, hipStream_t s);
-void launch_bilinear(const h16_t* in, h16_t* out, int B, int Hi, int Wi, int Ho, int Wo, int C, int align_corners, hipStream_t s);
-void launch_dpt_final(const h16_t* in, const float* w, float bias, float* out, int B, int HW, int Cin, hipStream_t s);  // ReLU'd 32ch -> 1
+template <typename T>
+void launch_add(const T* a, const T* b, T* out, long long n, hipStream_t s);
+template <typename T>
+void launch_bilinear(const T* in, T* out, int B, int Hi, int Wi, int Ho, int Wo, int C, int align_corners, hipStream_t s);
+template <typename T>
+void launch_dpt_final(const T* in, const float* w, float bias, float* out, int B, int HW, int Cin, hipStream_t s);  // ReLU'd 32ch -> 1
 void launch_minmax_norm(float* x, int B, long long n, float* ws, hipStream_t s);  // per-image (x-min)/(max-min)
 
 // conv_img.hip: 3x3 stride-1 convs whose maps tile into 576-pixel units (24x24, 12x12 x 4): whole-image tiles, K split over workgroups,
@@ -232,7 +243,6 @@ void launch_c_groupnorm_scale_shift(const float* x, float* part, int B, int H, i
                                     float* scale, float* shift, hipStream_t s);
 void launch_c_gn_apply_split(const float* x, h16_t* out, const float* scale, const float* shift, int B, int HW, int C, int silu, hipStream_t s);
 void launch_c_layernorm_split(const float* x, h16_t* out, const float* gamma, const float* beta, int rows, int C, float eps, hipStream_t s);
-void launch_c_concat(const float* a, int Ca, const float* b, int Cb, float* out, long long pixels, hipStream_t s);
 void launch_c_heads_split(const float* qkv, int ld, h16_t* Qs, h16_t* Ks, h16_t* Vts, int B, int T, int Tpad, int heads, int hd, hipStream_t s);
 void launch_c_qkv_planes(const float* qkv, int ld, h16_t* qk_hi, h16_t* qk_lo, h16_t* vt_hi, h16_t* vt_lo, int B, int T, int Tpad, int heads, int hd,
                          hipStream_t s);
@@ -260,17 +270,6 @@ bool c_cross_fold_supported(int C);
 void launch_c_cross_fold(const float* y, float* y_out, h16_t* n3_out, const float* U, const float* u0, const float* G, const float* c0, const float* g3,
                          const float* b3, int rows, int C, int heads, float eps, hipStream_t s);
 void launch_c_cross_attn_small(const float* q, const float* kc, const float* vc, h16_t* out, int rows, int C, int L, hipStream_t s);
-void launch_c_pointwise_small(const float* in, float* out, const float* w, const float* bias, long long pixels, int Cin, int Cout, int ldi, int ldo,
-                              float in_scale, hipStream_t s);
-void launch_c_decode_epilogue(const float* in, float* out, int B, int H, int W, int ld, int mean3, int raw, hipStream_t s);
-void launch_c_nchw_to_nhwc(const float* in, float* out, int B, int C, int H, int W, int Cpad, hipStream_t s);
-void launch_c_nhwc_to_nchw(const float* in, float* out, int B, int C, int H, int W, int ld, hipStream_t s);
-void launch_c_add(const float* a, const float* b, float* out, long long n, hipStream_t s);
-void launch_c_bilinear(const float* in, float* out, int B, int Hi, int Wi, int Ho, int Wo, int C, int align_corners, hipStream_t s);
-void launch_c_dpt_final(const float* in, const float* w, float bias, float* out, int B, int HW, int Cin, hipStream_t s);
-void launch_c_ddim_init(const float* noise_nchw, float* lat, float* sample, int B, int H, int W, int L, int ld, int off, hipStream_t s);
-void launch_c_ddim_step(const float* model, int ldm, float* sample, float* uin, int ldu, int off, float* x0_out, int ldx, long long pixels, int L,
-                        const DdimCoef& k, hipStream_t s);
 
 // microbench.hip: sustained TFLOP/s of back-to-back v_mfma_f32_32x32x16 on this chip (register operands, all CUs), or < 0 on error
 double mfma_peak_tflops(int ms_target, hipStream_t s, int shape = 0);

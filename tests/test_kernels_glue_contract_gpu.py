@@ -1,10 +1,11 @@
-"""Float64 and bit-exact tests of the contract precision's glue kernels (csrc/contract.hip, bf16 library) through their stateless test entries.
+"""Float64 and bit-exact tests of the contract precision's glue kernels (bf16 library) through their stateless test entries.
 
-The fp32 twins of the elementwise kernels (c_rgb_split, c_concat, c_nchw_to_nhwc, c_nhwc_to_nchw, c_ddim_init, c_ddim_step, c_decode_epilogue,
-c_pointwise_small, c_add, c_dpt_final) run the checks of tests/test_kernels_glue_gpu.py with fp32 storage: the same references and bounds,
-|out - y64| <= E in place of the 16-bit interval, one case per kernel that wraps cgrid's 8192 * 256 items.  The kernels that exist in this
-precision only are tested here: c_heads_split and c_heads_merge_split (bit-exact RNE hi / lo in the right order and position, as
-test_split_is_round_to_nearest_even_in_both_orders), c_cross_fold, c_cross_attn_small and c_bilinear (float64 bounds).  A split operand
+c_rgb_split (csrc/contract.hip) and the float instantiations of csrc/elementwise.hip's templates (concat, nchw_f32_to_nhwc, nhwc_to_nchw_f32,
+ddim_init, ddim_step, decode_epilogue, pointwise_small, add, dpt_final) run the checks of tests/test_kernels_glue_gpu.py with fp32 storage:
+the same references and bounds, |out - y64| <= E in place of the 16-bit interval, one case per kernel that wraps the fp32 grid cap's
+8192 * 256 items.  Tested here: the kernels that exist in this precision only, c_heads_split and c_heads_merge_split (bit-exact RNE hi / lo
+in the right order and position, as test_split_is_round_to_nearest_even_in_both_orders), c_cross_fold and c_cross_attn_small, and the float
+form of bilinear through its own entry gp_c_bilinear (float64 bounds).  A split operand
 x = hi + lo carries 2^-17 |x| (tests/test_contract_kernels_gpu.py)."""
 import pytest
 import torch
@@ -28,7 +29,7 @@ def e():
     return engine
 
 
-# ---- the fp32 twins ------------------------------------------------------------------------------------------------------------------------
+# ---- the fp32 forms ------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("u8", [True, False], ids=["u8", "f32"])
 @pytest.mark.parametrize("case", glue.RGB_CASES)
 def test_c_rgb_split_exact(case, u8, metric_log):

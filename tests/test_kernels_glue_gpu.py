@@ -1,7 +1,8 @@
 """Float64 and bit-exact tests of the 16-bit elementwise / layout kernels between the matrix products (csrc/elementwise.hip), both libraries,
 through the stateless gp_* test entries: rgb_prologue, concat, concat_stats (+ gn_finalize_tiles mode 4), the statistics rows of rgb_conv_in
 (mode 3), nchw <-> nhwc, ddim_init, ddim_step, decode_epilogue, scale_pad, pointwise_small, relu, add, dpt_final, minmax_norm.  The fp32
-twins of the contract precision run the same checks from tests/test_kernels_glue_contract_gpu.py (the run_* functions below take `contract`).
+forms of the contract precision (the same templates instantiated for float) run the same checks from tests/test_kernels_glue_contract_gpu.py
+(the run_* functions below take `contract`).
 
 References are float64 on the values the kernel reads; nothing of a kernel's tiling is emulated.
   * Pure data movement and single roundings are bit-exact: zero mismatches (check_exact).
@@ -162,7 +163,7 @@ def test_rgb_prologue_exact(case, u8, metric_log):
     run_rgb_prologue(case, u8, False, metric_log)  # measured: 0 mismatches, both libraries
 
 
-# ---- concat / c_concat ---------------------------------------------------------------------------------------------------------------------
+# ---- concat (16-bit / fp32) ----------------------------------------------------------------------------------------------------------------
 # (Ca, Cb, pixels): the UNet's widths; the last case wraps the loop (pixels * (Ca + Cb) / vector > one pass)
 CONCAT_CASES = [(8, 8, 1), (8, 8, 3 * 37), (320, 640, 3 * 37), (1280, 1280, 37), (320, 640, None)]
 
@@ -569,7 +570,7 @@ def test_scale_pad_interval(case, metric_log):
     assert not failures, "\n".join(failures)
 
 
-ADD_CASES = [8, 3 * 37 * 8, WRAP * 8 + 64]   # elements (vectors of 8; the contract twin: of 4)
+ADD_CASES = [8, 3 * 37 * 8, WRAP * 8 + 64]   # elements (vectors of 8; the contract form: of 4)
 
 
 def run_add(n, contract, log):
