@@ -152,6 +152,8 @@ SYMBOLS = {
     "gp_eval_depth": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _ll, _vp]),
     "gp_eval_normal_workspace": (_ll, [_i, _i, _i]),
     "gp_eval_normal": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
+    "gp_eval_mask_workspace": (_ll, [_i, _i, _i]),
+    "gp_eval_mask": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
     "gp_ensemble_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gp_ensemble_workspace": (_ll, [_i, _i, _i, _i]),
     "gp_ensemble_reduce": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
@@ -1005,6 +1007,72 @@ def eval_normal(pred: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.Tenso
         if row[0] == 0:
             raise ValueError(f"image {i}: no valid pixel to evaluate normals on (n_valid = 0)")
     return [{k: float(row[1 + j]) for j, k in enumerate(NORMAL_METRICS)} for row in raw], raw[:, 0].astype("int64")
+
+
+MASK_METRICS = ["mae", "mse", "sad", "max_f", "mean_f", "adp_f", "iou"]  # gp_eval_mask's out[2 .. 8]; eval_metrics.mask_metrics_from_counts' keys
+MASK_OUT = 10      # n, n_fg, the seven metrics, t_max
+MASK_COUNTS = 516  # n, sum_q, sad, sse, hist_bg[256], hist_fg[256]
+
+
+def _eval_mask_launch(pred: torch.Tensor, gt: torch.Tensor, region: Optional[torch.Tensor], want_counts: bool):
+    """The checks and the call of `eval_mask_raw`.  Returns (buf, out, counts): out float64 [B, 10] and counts int64 [B, 516] (or None) are
+    views of the one int64 device buffer `buf`, so that one copy brings both to the host."""
+    lib = load_library()
+    pred, gt = _eval_maps(pred, "pred"), _eval_maps(gt, "gt")
+    assert pred.is_cuda and gt.is_cuda
+    if gt.dtype != torch.uint8:
+        raise ValueError(f"gt: the ground truth is an 8-bit mask / alpha map (uint8), got {gt.dtype}")
+    if pred.shape != gt.shape:
+        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have one shape")
+    is_u8 = pred.dtype == torch.uint8
+    if not is_u8 and not pred.dtype.is_floating_point:
+        raise ValueError(f"pred: a float map in [0, 1] or its uint8 quantisation, got {pred.dtype}")
+    pred, gt = (pred if is_u8 else pred.to(torch.float32)).contiguous(), gt.contiguous()
+    b, h, w = (int(v) for v in pred.shape)
+    if region is not None:
+        region = _eval_maps(region, "region")
+        assert region.is_cuda
+        if tuple(region.shape) != (b, h, w):
+            raise ValueError(f"region {tuple(region.shape)} does not match the maps {(b, h, w)}")
+        region = (region.contiguous().view(torch.uint8) if region.dtype in (torch.bool, torch.uint8) else (region != 0).view(torch.uint8)).contiguous()
+    buf = torch.empty((b * (MASK_OUT + (MASK_COUNTS if want_counts else 0)),), dtype=torch.int64, device=pred.device)
+    out = buf[:b * MASK_OUT].view(torch.float64).view(b, MASK_OUT)
+    counts = buf[b * MASK_OUT:].view(b, MASK_COUNTS) if want_counts else None
+    nbytes = int(lib.gp_eval_mask_workspace(b, h, w))
+    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=pred.device)
+    st = lib.gp_eval_mask(pred.data_ptr(), int(is_u8), gt.data_ptr(), _ptr(region), b, h, w, out.data_ptr(), _ptr(counts), ws.data_ptr(), nbytes,
+                          _stream_ptr(pred.device))
+    if st != GP_OK:
+        raise RuntimeError(f"gp_eval_mask failed ({st})")
+    return buf, out, counts
+
+
+def eval_mask_raw(pred: torch.Tensor, gt: torch.Tensor, region: Optional[torch.Tensor] = None, want_counts: bool = False):
+    """gp_eval_mask on device tensors: float64 [B, 10] ON THE DEVICE = n, n_fg, then MASK_METRICS, then t_max (NaN after n_fg for an image whose
+    region is empty); with want_counts also the int64 [B, 516] counts n, sum_q, sad, sse, hist_bg[256], hist_fg[256] (eval_metrics.mask_counts).
+    pred: [B, H, W], [B, 1, H, W] or [H, W], a float map in [0, 1] (quantised to 8 bits by the kernel as run.py:449-455 does) or uint8 (the
+    bytes `postprocess(..., q_bits=8)` returns); gt: uint8, same shape; region: bool or integer, non-zero = scored, None = every pixel.
+    Enqueued on the current stream, no synchronisation."""
+    _, out, counts = _eval_mask_launch(pred, gt, region, want_counts)
+    return (out, counts) if want_counts else out
+
+
+def eval_mask(pred: torch.Tensor, gt: torch.Tensor, region: Optional[torch.Tensor] = None):
+    """eval_metrics.mask_metrics for a batch of maps that are on the device (arguments as `eval_mask_raw`).  Returns one dict per image:
+    MASK_METRICS, "n", "n_fg", "t_max" and "counts" (int64 numpy [516]).  Raises ValueError naming the image when its region is empty.  One
+    device -> host copy of B x (10 + 516) words."""
+    buf, out, _ = _eval_mask_launch(pred, gt, region, True)
+    b = out.shape[0]
+    host = buf.cpu().numpy()
+    raw, counts = host[:b * MASK_OUT].view("float64").reshape(b, MASK_OUT), host[b * MASK_OUT:].reshape(b, MASK_COUNTS)
+    res = []
+    for i, row in enumerate(raw):
+        if row[0] == 0:
+            raise ValueError(f"image {i}: no pixel to evaluate the mask on (n = 0)")
+        d = {k: float(row[2 + j]) for j, k in enumerate(MASK_METRICS)}
+        d.update(n=int(row[0]), n_fg=int(row[1]), t_max=int(row[9]), counts=counts[i].copy())
+        res.append(d)
+    return res
 
 
 ENSEMBLE_REDUCTION = {"median": 0, "mean": 1}

@@ -164,3 +164,96 @@ def normal_angular_error(pred: np.ndarray, gt: np.ndarray, valid_mask: Optional[
 def decode_normals(pred_np: np.ndarray) -> np.ndarray:
     """GenPerceptOutput.pred_np of mode='normal' is [H, W, 3] in [0, 1] = (n + 1) / 2 (genpercept_pipeline.py:469-472): back to [3, H, W] in [-1, 1]."""
     return np.moveaxis(np.asarray(pred_np, dtype=np.float64) * 2.0 - 1.0, -1, -3)
+
+
+# ---- dis / matting ------------------------------------------------------------------------------------------------------------------------
+# The reference has no metric for its dis and matting checkpoints (genpercept_trainer.py:1169 is a TODO).  The definitions below are this
+# project's, stated once in include/genpercept_hip.h (gp_eval_mask): everything is computed on the 8-BIT prediction -- the byte run.py:449-455
+# saves -- against an 8-bit ground truth, so every per-pixel quantity is an integer, the reductions are exact, and each value is one fixed
+# sequence of float64 operations on integer counts.  The device entry runs the same sequence and is bit-equal.
+MASK_METRICS = ["mae", "mse", "sad", "max_f", "mean_f", "adp_f", "iou"]
+MASK_COUNTS = 4 + 2 * 256  # n, sum_q, sad, sse, hist_bg[256], hist_fg[256]
+
+
+def quantize_mask(pred: np.ndarray) -> np.ndarray:
+    """(clip(pred, 0, 1) * 255).astype(uint8) with the product in float32 and NaN -> 0 (run.py:449-455); uint8 input is returned as it is."""
+    pred = np.asarray(pred)
+    if pred.dtype == np.uint8:
+        return pred
+    if not np.issubdtype(pred.dtype, np.floating):
+        raise ValueError(f"a float map in [0, 1] or its uint8 quantisation, got {pred.dtype}")
+    x = pred.astype(np.float32)
+    x = np.clip(np.where(np.isnan(x), np.float32(0.0), x), np.float32(0.0), np.float32(1.0))
+    return (x * np.float32(255.0)).astype(np.uint8)
+
+
+def mask_counts(q: np.ndarray, g: np.ndarray, region: Optional[np.ndarray] = None) -> np.ndarray:
+    """The integer counts of one image, int64 [516] = n, sum q, sum |q - g|, sum (q - g)^2, hist_bg[256] (counts of q where g <= 128),
+    hist_fg[256] (where g > 128), over the pixels with region != 0 (None: all).  q, g: uint8 arrays of one shape."""
+    q, g = np.asarray(q), np.asarray(g)
+    if q.dtype != np.uint8 or g.dtype != np.uint8 or q.shape != g.shape:
+        raise ValueError(f"q and g must be uint8 arrays of one shape, got {q.dtype} {q.shape} and {g.dtype} {g.shape}")
+    q, g = q.reshape(-1), g.reshape(-1)
+    if region is not None:
+        sel = np.asarray(region).reshape(-1) != 0
+        if sel.shape != q.shape:
+            raise ValueError("region does not match the maps")
+        q, g = q[sel], g[sel]
+    qi, gi = q.astype(np.int64), g.astype(np.int64)
+    d = np.abs(qi - gi)
+    fg = g > 128
+    out = np.empty(MASK_COUNTS, dtype=np.int64)
+    out[0], out[1], out[2], out[3] = q.size, qi.sum(), d.sum(), (d * d).sum()
+    out[4:260] = np.bincount(q[~fg], minlength=256)
+    out[260:516] = np.bincount(q[fg], minlength=256)
+    return out
+
+
+def mask_curves_from_counts(counts) -> Tuple[list, list, list]:
+    """(precision, recall, F) for the 256 thresholds "q >= t", Python floats: TP_t = sum_{v >= t} hist_fg[v], P_t = TP_t + sum_{v >= t}
+    hist_bg[v], prec = TP_t / max(P_t, 1), rec = TP_t / max(n_fg, 1), F_t = (1.3 * prec * rec) / (0.3 * prec + rec), 0.0 when the
+    denominator is 0 (beta^2 = 0.3)."""
+    c = [int(v) for v in np.asarray(counts).reshape(-1)]
+    if len(c) != MASK_COUNTS:
+        raise ValueError(f"expected {MASK_COUNTS} counts, got {len(c)}")
+    hist_bg, hist_fg = c[4:260], c[260:516]
+    n_fg = sum(hist_fg)
+    prec, rec, f = [0.0] * 256, [0.0] * 256, [0.0] * 256
+    tp = bgp = 0
+    for t in range(255, -1, -1):
+        tp += hist_fg[t]
+        bgp += hist_bg[t]
+        p, r = tp / max(tp + bgp, 1), tp / max(n_fg, 1)
+        den = 0.3 * p + r
+        prec[t], rec[t], f[t] = p, r, ((1.3 * p * r) / den if den != 0.0 else 0.0)
+    return prec, rec, f
+
+
+def mask_metrics_from_counts(counts) -> Dict[str, float]:
+    """The values of gp_eval_mask's `out` from the counts, in its order: n, n_fg, mae, mse, sad, max_f, mean_f, adp_f, iou, t_max (n and n_fg
+    ints; n = 0: NaN for the other eight).  Plain float64 *, /, + in the order the header prescribes; the 256-term sum runs left to right."""
+    c = [int(v) for v in np.asarray(counts).reshape(-1)]
+    if len(c) != MASK_COUNTS:
+        raise ValueError(f"expected {MASK_COUNTS} counts, got {len(c)}")
+    n, sum_q, sad, sse = c[:4]
+    hist_bg, hist_fg = c[4:260], c[260:516]
+    n_fg = sum(hist_fg)
+    if n == 0:
+        nan = float("nan")
+        return dict(n=0, n_fg=0, mae=nan, mse=nan, sad=nan, max_f=nan, mean_f=nan, adp_f=nan, iou=nan, t_max=nan)
+    _, _, f = mask_curves_from_counts(c)
+    total, best, t_max = f[0], f[0], 0
+    for t in range(1, 256):
+        total = total + f[t]
+        if f[t] > best:
+            best, t_max = f[t], t
+    t_a = (min(2 * sum_q, 255 * n) + n - 1) // n  # the smallest integer with t_a * n >= min(2 * sum_q, 255 * n)
+    tp = sum(hist_fg[128:])
+    union = tp + sum(hist_bg[128:]) + n_fg - tp
+    return dict(n=n, n_fg=n_fg, mae=sad / (255.0 * n), mse=sse / (65025.0 * n), sad=sad / 255000.0, max_f=best, mean_f=total / 256.0,
+                adp_f=f[t_a], iou=(tp / union if union != 0 else 0.0), t_max=float(t_max))
+
+
+def mask_metrics(pred: np.ndarray, gt: np.ndarray, region: Optional[np.ndarray] = None) -> Dict[str, float]:
+    """One image: pred a float map in [0, 1] (quantised by `quantize_mask`) or uint8, gt uint8, region optional (non-zero = scored)."""
+    return mask_metrics_from_counts(mask_counts(quantize_mask(pred), gt, region))

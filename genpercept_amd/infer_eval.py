@@ -7,7 +7,9 @@ Mirrors, for RGB + depth datasets listed in the reference's `data_split/*/filena
                                depth range, ten metrics (eval_metrics.py), mean over images, `eval_metrics-<alignment>.txt` + per-sample csv;
   * src/dataset/nyu_dataset.py:39-58, base_dataset.py:399-413 -- NYUv2 decoding (png / 1000), validity (min < d < max) and Eigen crop.
 Pinned to the reference by tests/golden/infer_eval_ref.npz (naming modes; disparity-space alignment and max_resolution fits come from
-the reference's alignment.py).  Nothing here touches the GPU except through the pipeline object handed in.
+the reference's alignment.py).  The loops for surface normals and for dis / matting masks follow the same pattern; the reference has no
+evaluation script for either, their metrics are defined in eval_metrics.py.  Nothing here touches the GPU except through the pipeline
+object handed in.
 """
 from __future__ import annotations
 
@@ -366,6 +368,18 @@ def evaluate_normal_predictions(prediction_dir: str, base_dir: str, samples: Seq
 
 
 # ---- the loops where predictions never leave the GPU ------------------------------------------------------------------------------------
+def _all_reduce_sum(acc: np.ndarray) -> np.ndarray:
+    """The float64 vector summed over the ranks of an initialised torch.distributed (on the device for nccl); unchanged for one process."""
+    import torch
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return acc
+    dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
+    t = torch.from_numpy(np.ascontiguousarray(acc, dtype=np.float64)).to(dev)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t.cpu().numpy()
+
+
 def _evaluation_loop(samples: Sequence[Sequence[str]], keep: Callable, load: Callable, score_group: Callable, names: List[str], batch_size: int,
                      rank: int, world: int, prefetch: int):
     """The skeleton `infer_and_evaluate` and `infer_and_evaluate_normals` share.  `samples` filtered by `keep`, then sharded
@@ -373,7 +387,6 @@ def _evaluation_loop(samples: Sequence[Sequence[str]], keep: Callable, load: Cal
     per group; `score_group([((index, sample), image), ...])` -> one list of metric values (in `names` order) per image.  With
     torch.distributed initialised the rows of all ranks are combined: float64 sums and a count by all_reduce, rows by all_gather_object.
     Returns (rows [(index, sample, values)] in sample order, means over all samples, whether this rank writes the files)."""
-    import torch
     samples = [s for s in samples if keep(s)]
     lo, hi = _shard(len(samples), rank, world) if world > 1 else (0, len(samples))
     items = [(i, samples[i]) for i in range(lo, hi)]  # the index in the filtered list rides along: the rows of all ranks are ordered by it
@@ -390,10 +403,7 @@ def _evaluation_loop(samples: Sequence[Sequence[str]], keep: Callable, load: Cal
         acc[-1] += 1
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
-        t = torch.from_numpy(acc).to(dev)
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
-        acc = t.cpu().numpy()
+        acc = _all_reduce_sum(acc)
         parts: list = [None] * dist.get_world_size()
         dist.all_gather_object(parts, rows)
         rows = [r for part in parts for r in part]
@@ -514,4 +524,171 @@ def infer_and_evaluate_normals(pipe, base_dir: str, samples: Sequence[Sequence[s
     if output_dir is not None and writer:
         _write_normal_eval_files(output_dir, names, [(_normal_pred_name(smp[0], name_mode), vals) for _, smp, vals in rows], result, prediction_dir,
                                  gt_column)
+    return result
+
+
+# ---- dis / matting: 8-bit masks and alpha maps ------------------------------------------------------------------------------------------------
+MASK_METRICS = list(em.MASK_METRICS)  # per-image values, in order; the dataset-level "max_f_dataset" comes on top
+
+
+def read_gt_mask(path: str) -> np.ndarray:
+    """An 8-bit mask / alpha map as uint8 [H, W].  A three-channel file whose channels are equal gives channel 0 (the rule of the reference's
+    _read_depth_file, src/dataset/base_dataset.py:399-408); an alpha channel on top is ignored.  Other formats: pass a `read_gt` callable."""
+    a = np.asarray(Image.open(path))
+    if a.ndim == 3 and a.shape[2] in (3, 4):
+        if not (np.all(a[:, :, 0] == a[:, :, 1]) and np.all(a[:, :, 0] == a[:, :, 2])):
+            raise ValueError(f"{path}: the three channels differ; a mask is one channel")
+        a = a[:, :, 0]
+    if a.ndim != 2 or a.dtype != np.uint8:
+        raise ValueError(f"{path}: expected an 8-bit single-channel image, got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def _read_mask_prediction(path: str) -> np.ndarray:
+    """What `run_inference(mode="dis" | "matting")` writes (`.npy`, float [H, W] in [0, 1]) or the 8-bit `.png` of the same map."""
+    if os.path.splitext(path)[1].lower() == ".npy":
+        p = np.load(path).squeeze()
+        if p.ndim != 2:
+            raise ValueError(f"{path}: expected a single-channel map, got {p.shape}")
+        return p
+    return read_gt_mask(path)
+
+
+def _mask_pred_name(rgb_rel: str, name_mode: FileNameMode, suffix: str = ".npy") -> str:
+    return os.path.join(os.path.dirname(rgb_rel), get_pred_name(os.path.basename(rgb_rel), name_mode, suffix=suffix))
+
+
+def _mask_region(region_of: Optional[Callable], smp: Sequence[str], gt: np.ndarray) -> Optional[np.ndarray]:
+    if region_of is None:
+        return None
+    r = np.asarray(region_of(smp, gt)) != 0
+    if r.shape != gt.shape:
+        raise ValueError(f"{smp[0]}: region {r.shape} and ground truth {gt.shape} differ in size")
+    return r
+
+
+def _max_f_of_mean_curves(curve_sums: np.ndarray, n: int) -> float:
+    """The usual dis protocol: max_t F_t of the DATASET-MEAN precision and recall curves.  curve_sums: float64 [512] = the per-image precision
+    curves summed, then the recall curves; n images."""
+    if n == 0:
+        return float("nan")
+    best = 0.0
+    for t in range(256):
+        p, r = float(curve_sums[t]) / n, float(curve_sums[256 + t]) / n
+        den = 0.3 * p + r
+        best = max(best, (1.3 * p * r) / den if den != 0.0 else 0.0)
+    return best
+
+
+def _sum_curves(counts_in_order) -> np.ndarray:
+    acc = np.zeros(512, dtype=np.float64)
+    for c in counts_in_order:
+        prec, rec, _ = em.mask_curves_from_counts(c)
+        acc[:256] += prec
+        acc[256:] += rec
+    return acc
+
+
+def _write_mask_eval_files(output_dir: str, names: List[str], per_sample, result: Dict[str, float], prediction_dir: Optional[str]) -> None:
+    """`per_sample_metrics-mask.csv` and `eval_metrics-mask.txt`, laid out like the depth files; the dataset-level value sits in the header."""
+    header = f"Evaluation metrics:\n    of predictions: {prediction_dir}\n    on 8-bit masks: column 1 of the filename list\n"
+    header += f"max_f_dataset = {result['max_f_dataset']:.6g}\n"
+    _write_metric_files(output_dir, "-mask", names, per_sample, result, header)
+
+
+def evaluate_mask_predictions(prediction_dir: str, base_dir: str, samples: Sequence[Sequence[str]], name_mode: FileNameMode,
+                              output_dir: Optional[str] = None, pred_suffix: str = ".npy", region_of: Optional[Callable] = None,
+                              read_gt: Optional[Callable[[str], np.ndarray]] = None) -> Dict[str, float]:
+    """The file route for what `run_inference(mode="dis" | "matting")` writes (`.npy`) or for 8-bit `.png` maps (pred_suffix): per image
+    eval_metrics.mask_metrics against the 8-bit ground truth of column 1 (read_gt_mask or `read_gt`), over `region_of(sample, gt)` (a bool
+    array, e.g. a trimap's unknown region; None: every pixel).  Returns the means of the per-image MASK_METRICS and "max_f_dataset", the
+    maximum F of the dataset-mean precision / recall curves.  Samples without ground truth ("None") or without a prediction file are
+    skipped.  Optionally writes `eval_metrics-mask.txt` and `per_sample_metrics-mask.csv`."""
+    names = list(MASK_METRICS)
+    sums = {k: 0.0 for k in names}
+    per_sample, counts = [], []
+    for s in samples:
+        if len(s) < 2 or s[1] == "None":
+            continue
+        pred_name = _mask_pred_name(s[0], name_mode, pred_suffix)
+        pred_path = os.path.join(prediction_dir, pred_name)
+        if not os.path.exists(pred_path):
+            continue
+        gt = (read_gt or read_gt_mask)(os.path.join(base_dir, s[1]))
+        pred = _read_mask_prediction(pred_path)
+        if tuple(pred.shape) != tuple(gt.shape):
+            raise ValueError(f"{s[0]}: prediction {tuple(pred.shape)} and ground truth {tuple(gt.shape)} differ in size")
+        c = em.mask_counts(em.quantize_mask(pred), gt, _mask_region(region_of, s, gt))
+        if c[0] == 0:
+            raise ValueError(f"{s[0]}: no pixel to evaluate the mask on (n = 0)")
+        m = em.mask_metrics_from_counts(c)
+        for k in names:
+            sums[k] += m[k]
+        per_sample.append((pred_name, [m[k] for k in names]))
+        counts.append(c)
+    n = len(per_sample)
+    result = {k: (sums[k] / n if n else float("nan")) for k in names}
+    result["max_f_dataset"] = _max_f_of_mean_curves(_sum_curves(counts), n)
+    if output_dir is not None:
+        _write_mask_eval_files(output_dir, names, per_sample, result, prediction_dir)
+    return result
+
+
+def infer_and_evaluate_masks(pipe, base_dir: str, samples: Sequence[Sequence[str]], mode: str, output_dir: Optional[str] = None,
+                             name_mode: FileNameMode = FileNameMode.id, batch_size: int = 4, rank: int = 0, world: int = 1,
+                             save_predictions: bool = False, prediction_dir: Optional[str] = None, evaluator: Optional[Callable] = None,
+                             read_gt: Optional[Callable[[str], np.ndarray]] = None, region_of: Optional[Callable] = None, denoise_steps: int = 1,
+                             ensemble_size: int = 1, processing_res: int = 0, match_input_res: bool = True, resample_method: str = "bilinear",
+                             fix_timesteps=None, prompt: str = "", prefetch: int = 2) -> Dict[str, float]:
+    """`infer_and_evaluate` for mode "dis" or "matting": batches go through `pipe.predict_batch_device(mode=mode)`, the float [B, 1, H, W] maps
+    stay on the device, and `evaluator` -- `engine.eval_mask` unless given: (pred, gt, region) -> one dict per image with MASK_METRICS and
+    "counts" -- quantises and scores them there against the 8-bit ground truth of column 1 (and `region_of(sample, gt)`, if given), decoded on
+    the host and uploaded per batch.  What it computes per image is `evaluate_mask_predictions`' quantity, bit for bit; sharding, the
+    torch.distributed combination, the rank-0 files (`eval_metrics-mask.txt`, `per_sample_metrics-mask.csv`) and the return value on every
+    rank are `infer_and_evaluate`'s, with one more float64 all_reduce for the precision / recall curves behind "max_f_dataset".
+    save_predictions: the maps are also written as `run_inference` would, float32 [H, W] `.npy` under prediction_dir (default: output_dir)."""
+    import torch
+    if mode not in ("dis", "matting"):
+        raise ValueError(f"mask evaluation is for mode 'dis' or 'matting', got {mode!r}")
+    names = list(MASK_METRICS)
+    if evaluator is None:
+        from .engine import eval_mask as evaluator
+    if prediction_dir is None:
+        prediction_dir = output_dir
+    if save_predictions and prediction_dir is None:
+        raise ValueError("save_predictions needs prediction_dir or output_dir")
+    counts = []  # (sample index, counts) of this rank's images
+
+    def score_group(group):
+        pred = pipe.predict_batch_device([img for _, img in group], mode, processing_res=processing_res, match_input_res=match_input_res,
+                                         resample_method=resample_method, fix_timesteps=fix_timesteps, prompt=prompt,
+                                         denoising_steps=denoise_steps, ensemble_size=ensemble_size)
+        if pred.dim() != 4 or pred.shape[0] != len(group) or pred.shape[1] != 1:
+            raise ValueError(f"mask evaluation needs one-channel maps [B, 1, H, W], got {tuple(pred.shape)} for mode {mode!r}")
+        gts, regions = [], []
+        for (_, smp), _ in group:
+            gt = (read_gt or read_gt_mask)(os.path.join(base_dir, smp[1]))
+            if tuple(gt.shape) != tuple(pred.shape[-2:]):
+                raise ValueError(f"{smp[0]}: prediction {tuple(pred.shape[-2:])} and ground truth {tuple(gt.shape)} differ in size")
+            gts.append(gt)
+            regions.append(_mask_region(region_of, smp, gt))
+        gt_t = torch.from_numpy(np.stack(gts)).to(pred.device, non_blocking=True)
+        region_t = torch.from_numpy(np.stack(regions)).to(pred.device, non_blocking=True) if region_of is not None else None
+        metrics = evaluator(pred[:, 0], gt_t, region_t)
+        assert len(metrics) == len(group)
+        for ((idx, _), _), m in zip(group, metrics):
+            counts.append((idx, np.asarray(m["counts"])))
+        if save_predictions:
+            pred_host = pred[:, 0].cpu().numpy()
+            for j, ((_, smp), _) in enumerate(group):
+                _save_prediction(prediction_dir, _mask_pred_name(smp[0], name_mode), pred_host[j])
+        return [[metrics[j][k] for k in names] for j in range(len(group))]
+
+    rows, result, writer = _evaluation_loop(samples, lambda s: len(s) > 1 and s[1] != "None", lambda smp: _load_rgb(base_dir, smp[0], None),
+                                            score_group, names, batch_size, rank, world, prefetch)
+    counts.sort(key=lambda c: c[0])
+    curve_sums = _all_reduce_sum(_sum_curves([c for _, c in counts]))
+    result["max_f_dataset"] = _max_f_of_mean_curves(curve_sums, len(rows))
+    if output_dir is not None and writer:
+        _write_mask_eval_files(output_dir, names, [(_mask_pred_name(smp[0], name_mode), vals) for _, smp, vals in rows], result, prediction_dir)
     return result

@@ -18,6 +18,7 @@
  *   gp_eval_depth     eval.py's per-image alignment + metrics               eval.py:168-215; src/util/alignment.py:29-94; src/util/metric.py:34-158
  *   gp_eval_normal    the angular error of angular_loss per image + summary statistics   genpercept/losses/geometry_losses.py:550-590;
  *                       ground-truth column and validity rule                 src/dataset/base_dataset.py:362-363,416-418
+ *   gp_eval_mask      (no reference code: genpercept_trainer.py:1169 is a TODO) dis / matting metrics on the saved 8-bit map   run.py:449-455
  *   gp_ensemble_gather, gp_ensemble_reduce
  *                     ensemble_depth's tensor half (the BFGS fit stays on the host)   genpercept/util/ensemble.py:43-205;
  *                                                                   genpercept_pipeline.py:289-298
@@ -235,6 +236,36 @@ gp_status gp_eval_depth(const float* pred, const float* gt, const unsigned char*
 long long gp_eval_normal_workspace(int B, int H, int W);      /* bytes; 0 for B, H or W < 1; proportional to B; multiple of 8 */
 gp_status gp_eval_normal(const float* pred, const float* gt, const unsigned char* mask, int B, int H, int W, int decode,
                          double* out, double* angles_out, void* workspace, long long workspace_bytes, void* stream);
+
+/* ---- dis / matting evaluation on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation; csrc/eval.hip) ----
+ * Scores the single-channel [0, 1] maps of mode dis and matting against an 8-bit ground truth (mask or alpha).  The reference has no metric for
+ * them (genpercept_trainer.py:1169 is a TODO), so the definitions are this project's; eval_metrics.mask_counts / mask_metrics_from_counts are
+ * the same definitions on the host.  Everything is computed on the 8-BIT prediction q = (unsigned char)(clamp(x, 0, 1) * 255.0f): the product
+ * in fp32, truncated, NaN -> 0 -- on pipeline outputs the byte run.py:449-455 saves and gp_postprocess writes with q_bits = 8.
+ * pred: fp32 [B][H][W] (pred_is_u8 = 0; quantised here) or uint8 [B][H][W] (pred_is_u8 = 1; q as it is).  gt: uint8 [B][H][W].
+ * region: uint8 [B][H][W], non-zero = scored, or NULL = every pixel (e.g. a trimap's unknown region for matting).
+ * Per image over the region R, unsigned 64-bit counts: n = |R|, sum_q = sum q, sad = sum |q - g|, sse = sum (q - g)^2, hist_bg[256] = counts of
+ * q over the pixels with g <= 128, hist_fg[256] = counts of q over the pixels with g > 128, n_fg = sum hist_fg.  Integers: exact, order-free.
+ * The values are float64, each one fixed sequence of correctly rounded *, /, + on those integers (no FMA):
+ *   mae = sad / (255.0 * n);  mse = sse / (65025.0 * n);  sad = sad / 255000.0 (the matting "SAD", in thousands of pixels);
+ *   for t = 0..255, prediction positive where q >= t: TP_t = sum_{v >= t} hist_fg[v], P_t = TP_t + sum_{v >= t} hist_bg[v],
+ *     prec = TP_t / max(P_t, 1), rec = TP_t / max(n_fg, 1), F_t = ((1.3 * prec) * rec) / (0.3 * prec + rec), 0.0 when that denominator is 0
+ *     (beta^2 = 0.3);
+ *   max_f = max_t F_t, t_max the smallest t that attains it;  mean_f = (F_0 + F_1 + ... + F_255) / 256.0, summed left to right;
+ *   adp_f = F_{t_a}, t_a the smallest integer with t_a * n >= min(2 * sum_q, 255 * n) (threshold = min(2 * mean, 1), in integers);
+ *   iou at t = 128: TP / (P + n_fg - TP), 0.0 when that denominator is 0.
+ * out: double [B][10] = n, n_fg, mae, mse, sad, max_f, mean_f, adp_f, iou, t_max; n = 0 gives n = n_fg = 0 and NaN for the other eight.
+ * counts_out: optional unsigned 64-bit [B][516] = n, sum_q, sad, sse, hist_bg[256], hist_fg[256].
+ * An image's values are bitwise the same from call to call, for every batch it is part of and for every pointer alignment.  workspace:
+ * DEVICE scratch of at least the workspace entry's byte count (8-byte aligned; one slab of 4 + 512 counts per workgroup), free again once the
+ * stream has passed the call.  Two kernel launches on `stream` for every B (count pass of 5 bytes per pixel, 6 with a region, 2 or 3 for
+ * uint8 predictions; one finalising workgroup per image), no global atomics, no float sums, nothing read back.
+ * GP_ERR_INVALID before any HIP call: null pred / gt / out / workspace, B, H or W < 1, B > 65535, H * W > 2^31 - 1, pred_is_u8 outside 0..1,
+ * out / counts_out / workspace not 8-byte aligned, workspace_bytes too small. */
+long long gp_eval_mask_workspace(int B, int H, int W);        /* bytes; 0 for B, H or W < 1; proportional to B; multiple of 8 */
+gp_status gp_eval_mask(const void* pred, int pred_is_u8, const unsigned char* gt, const unsigned char* region, int B, int H, int W,
+                       double* out /* [B][10] */, unsigned long long* counts_out /* [B][516] or NULL */, void* workspace,
+                       long long workspace_bytes, void* stream);
 
 /* ---- test-time ensembling on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation, no atomics; csrc/ensemble.hip) ----
  * The tensor half of ensemble_depth (genpercept/util/ensemble.py:43-205, called at genpercept_pipeline.py:289-298) for the E members of each of

@@ -1,4 +1,4 @@
-"""Time the device depth (or, with --normals, surface-normal) evaluation against the host evaluation, and the batched device loop on the tiny pipeline.
+"""Time the device depth (or, with --normals, surface-normal; with --masks, dis / matting) evaluation against the host evaluation, and the batched device loop on the tiny pipeline.
 
   python tools/eval_bench.py --out profiles/<name>.json
 
@@ -14,6 +14,13 @@
 3. `--normals` (instead of 1 and 2): `engine.eval_normal` (gp_eval_normal: the angle pass, 24 bytes + the mask byte in and an 8-byte key out per
    pixel, then six selection passes of 8 bytes per pixel, plus the small finaliser / pick kernels) at 4 x 480 x 640 and 1 x 4032 x 6048 with the
    derived validity rule, against `eval_metrics.normal_angular_error` on the same arrays on the host, timed and compared the same way.
+
+  python tools/eval_bench.py --masks --out profiles/<name>.json
+
+4. `--masks` (instead of 1 and 2): the `gp_eval_mask` entry behind `engine.eval_mask` (one count pass of 5 bytes per pixel -- the float map and the 8-bit ground
+   truth --, 6 with a region, and one finalising workgroup per image) at 4 x 1024 x 1024 and 1 x 4032 x 6048, on a 0 / 255 mask and on
+   uniform-random values, against `eval_metrics.mask_metrics` on the same arrays on the host (wall clock), and against the time the bytes
+   alone cost at the device-to-device copy bandwidth measured in the same process.  The two sides' values are compared on the spot (bit-equal).
 Needs a GPU; there is no CPU fall-back."""
 import argparse
 import json
@@ -122,6 +129,83 @@ def bench_eval_normal(b, h, w, iters, host_runs):
                 host_over_device=min(host_ms) / dev_ms, worst_rel_device_vs_host=worst)
 
 
+def mask_case(b, h, w, seed, kind):
+    """kind "mask": prediction exactly 0.0 / 1.0 and ground truth 0 / 255, a noisy copy of one another; "uniform": random floats and bytes."""
+    rng = np.random.default_rng(seed)
+    if kind == "uniform":
+        return rng.random((b, h, w), dtype=np.float32), rng.integers(0, 256, (b, h, w), dtype=np.uint8)
+    yy, xx = np.meshgrid(np.linspace(0, 1, h, dtype=np.float32), np.linspace(0, 1, w, dtype=np.float32), indexing="ij")
+    obj = np.stack([(xx - 0.5) ** 2 + (yy - 0.5) ** 2 < (0.15 + 0.05 * i) ** 2 for i in range(b)])
+    flip = rng.random((b, h, w), dtype=np.float32) < 0.03
+    return (obj ^ flip).astype(np.float32), (obj * 255).astype(np.uint8)
+
+
+def copy_bandwidth(d, nbytes=1 << 28, iters=20):
+    """Device-to-device copy of nbytes: GB/s of traffic (read + write), device events over `iters` copies after a warm-up."""
+    src, dst = torch.empty(nbytes, dtype=torch.uint8, device=d).random_(0, 256), torch.empty(nbytes, dtype=torch.uint8, device=d)
+    for _ in range(3):
+        dst.copy_(src)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        dst.copy_(src)
+    e1.record()
+    torch.cuda.synchronize()
+    return 2 * nbytes / (e0.elapsed_time(e1) / iters) / 1e6
+
+
+def time_eval_mask(tp, tg, iters):
+    """ms per gp_eval_mask call: the C entry itself on preallocated buffers (the two launches, none of the binding's tensor bookkeeping)."""
+    from genpercept_amd import engine as ge
+    lib = ge.load_library()
+    b, h, w = (int(v) for v in tp.shape)
+    nbytes = int(lib.gp_eval_mask_workspace(b, h, w))
+    ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=tp.device)
+    out = torch.empty((b, 10), dtype=torch.float64, device=tp.device)
+    stream = int(torch.cuda.current_stream(tp.device).cuda_stream)
+
+    def call():
+        st = lib.gp_eval_mask(tp.data_ptr(), int(tp.dtype == torch.uint8), tg.data_ptr(), None, b, h, w, out.data_ptr(), None, ws.data_ptr(), nbytes, stream)
+        assert st == ge.GP_OK, st
+
+    for _ in range(3):
+        call()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        call()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def bench_eval_mask(b, h, w, kind, iters, host_runs, copy_gb_per_s):
+    from genpercept_amd import engine as ge
+    from genpercept_amd import eval_metrics as em
+    d = torch.device("cuda", 0)
+    pred, gt = mask_case(b, h, w, 3, kind)
+    tp, tg = (torch.from_numpy(x).to(d) for x in (pred, gt))
+    dev_ms = time_eval_mask(tp, tg, iters)
+    t0 = time.perf_counter()
+    metrics = ge.eval_mask(tp, tg)  # with the copy of the 10 values and 516 counts per image and the host synchronise
+    call_ms = (time.perf_counter() - t0) * 1e3
+    host_ms = []
+    for _ in range(host_runs):
+        t0 = time.perf_counter()
+        ref = [em.mask_metrics(pred[i], gt[i]) for i in range(b)]
+        host_ms.append((time.perf_counter() - t0) * 1e3)
+    for i in range(b):
+        assert all(metrics[i][k] == ref[i][k] for k in em.MASK_METRICS) and metrics[i]["n"] == ref[i]["n"], (i, metrics[i], ref[i])
+    nbytes = 5 * b * h * w
+    floor_ms = nbytes / copy_gb_per_s / 1e6
+    return dict(shape=[b, h, w], input=kind, device_ms_per_call=dev_ms, device_iters=iters, launches_per_call=2, bytes_per_call=nbytes,
+                device_gb_per_s=nbytes / dev_ms / 1e6, copy_gb_per_s=copy_gb_per_s, bytes_alone_ms=floor_ms, device_over_bytes_alone=dev_ms / floor_ms,
+                device_call_with_sync_ms=call_ms, host_mask_metrics_ms=min(host_ms), host_runs=host_runs, host_over_device=min(host_ms) / dev_ms,
+                device_equals_host=True)
+
+
 def bench_loop(n_images, batch_sizes, repeats):
     from PIL import Image
     from genpercept_amd import GenPerceptPipeline
@@ -173,15 +257,21 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--skip-loop", action="store_true")
     ap.add_argument("--normals", action="store_true", help="time engine.eval_normal against normal_angular_error instead")
+    ap.add_argument("--masks", action="store_true", help="time gp_eval_mask against mask_metrics instead")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU")
-    if a.normals:
+    if a.masks:
+        bw = copy_bandwidth(torch.device("cuda", 0))
+        res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box",
+                   eval_mask=[bench_eval_mask(b, h, w, kind, a.iters, runs, bw) for (b, h, w, runs) in ((4, 1024, 1024, 3), (1, 4032, 6048, 1))
+                              for kind in ("mask", "uniform")])
+    elif a.normals:
         res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box",
                    eval_normal=[bench_eval_normal(4, 480, 640, a.iters, 3), bench_eval_normal(1, 4032, 6048, a.iters, 1)])
     else:
         res = dict(device=torch.cuda.get_device_name(0), eval_depth=[bench_eval(1, 4032, 6048, a.iters, 1), bench_eval(4, 480, 640, a.iters, 3)])
-    if not a.skip_loop and not a.normals:
+    if not a.skip_loop and not a.normals and not a.masks:
         res["infer_and_evaluate"] = bench_loop(16, (1, 4), 3)
     text = json.dumps(res, indent=1)
     print(text)
