@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "../../include/genpercept_hip.h"
+#include "eval_common.h"  // EV_THREADS, eval_blocks, block_reduce_store, sum_slabs, quantise8
 
 // The host's numpy code has no fused multiply-adds, so nothing below may be contracted into one.  The float32 recipe is written as plain
 // `*`, `+`, `/` under this pragma: the __fmul_rn / __fadd_rn wrappers are plain operators compiled under the header's own (contracting)
@@ -28,58 +29,9 @@
 
 namespace {
 
-constexpr int EV_THREADS = 256;
-constexpr int EV_WAVES = EV_THREADS / 64;
-constexpr long long EV_PIX_PER_WG = 4096;  // at least this many pixels per workgroup ...
-constexpr int EV_MAX_WG = 512;             // ... and at most this many workgroups (= slabs) per image
 constexpr int EV_NFIT = 5;                 // n, Sp, Sg, Spp, Spg
 constexpr int EV_NMET = 11;                // n_valid, abs_rel, sq_rel, sq, dlog^2, |dlog10|, inv^2, dlog, delta1..3 counts
 constexpr int EV_OUT = 14;                 // s, t, n_valid, n_fit, ten metrics
-
-int eval_blocks(long long hw) {
-    long long g = (hw + EV_PIX_PER_WG - 1) / EV_PIX_PER_WG;
-    return (int)(g < 1 ? 1 : (g > EV_MAX_WG ? EV_MAX_WG : g));
-}
-
-// v[0..N) of every thread -> their sums over the workgroup, in slab[0..N).  Fixed order: a 64-lane shuffle tree inside each wave (the
-// shuffle moves the two halves of a double), then the waves in index order through LDS.
-template <int N>
-__device__ __forceinline__ void block_reduce_store(double (&v)[N], double* __restrict__ slab) {
-    __shared__ double s_part[EV_WAVES][N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) s_part[wave][k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < N) {
-        double a = s_part[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < EV_WAVES; ++w) a += s_part[w][threadIdx.x];
-        slab[threadIdx.x] = a;
-    }
-}
-
-// the slabs of one image, summed in index order by thread k < N (loads batched 16 deep: they are independent, the additions are not)
-template <int N>
-__device__ __forceinline__ double sum_slabs(const double* __restrict__ ws, int nblk, int k) {
-    double a = 0.0;
-    int j = 0;
-    for (; j + 16 <= nblk; j += 16) {
-        double v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = ws[(long long)(j + u) * N + k];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) a += v[u];
-    }
-    for (; j < nblk; ++j) a += ws[(long long)j * N + k];
-    return a;
-}
 
 struct Quad { float p[4], g[4]; unsigned m; };  // four consecutive pixels; m: one mask byte per pixel (0 beyond the image)
 
@@ -579,12 +531,6 @@ struct MaskAcc {
         q4 = ad4 = sq4 = 0;
     }
 };
-
-// run.py:449-455 on one value: clip to [0, 1] (NaN -> 0), * 255 in fp32, truncate
-__device__ __forceinline__ unsigned quantise8(float x) {
-    const float c = x > 0.f ? (x < 1.f ? x : 1.f) : 0.f;
-    return (unsigned)(unsigned char)(c * 255.0f);
-}
 
 // grid (eval_blocks(H * W), B).  pred: float (quantised here) or, U8, bytes.  Pixels [head, head + 4 nq) of an image go as quads -- one 16-byte
 // load of pred (4 bytes for U8), 4 bytes of gt and of region per lane --, the up to three before and after them one by one; head is the

@@ -154,6 +154,8 @@ SYMBOLS = {
     "gp_eval_normal": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
     "gp_eval_mask_workspace": (_ll, [_i, _i, _i]),
     "gp_eval_mask": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
+    "gp_eval_structure_workspace": (_ll, [_i, _i, _i]),
+    "gp_eval_structure": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _ll, _vp]),
     "gp_ensemble_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gp_ensemble_workspace": (_ll, [_i, _i, _i, _i]),
     "gp_ensemble_reduce": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
@@ -1073,6 +1075,54 @@ def eval_mask(pred: torch.Tensor, gt: torch.Tensor, region: Optional[torch.Tenso
         d.update(n=int(row[0]), n_fg=int(row[1]), t_max=int(row[9]), counts=counts[i].copy())
         res.append(d)
     return res
+
+
+STRUCTURE_METRICS = ["s_alpha", "max_e", "mean_e", "adp_e", "wf"]  # gp_eval_structure's out[2], [5 .. 8]; eval_metrics.STRUCTURE_METRICS
+STRUCTURE_OUT_NAMES = ["n", "n_fg", "s_alpha", "s_object", "s_region", "max_e", "mean_e", "adp_e", "wf", "wf_precision", "wf_recall", "wf_sum_fg",
+                       "wf_sum_bg", "cx", "cy"]
+STRUCTURE_OUT = 15       # the names above
+STRUCTURE_COUNTS = 537   # n_fg, sum_fg x, sum_fg y, cx, cy, 4 x (N, a, a2, b, c), hist_bg[256], hist_fg[256]
+
+
+def eval_structure_raw(pred: torch.Tensor, gt: torch.Tensor, want_counts: bool = False, want_edt: bool = False):
+    """gp_eval_structure on device tensors: float64 [B, 15] ON THE DEVICE = STRUCTURE_OUT_NAMES (S-measure, E-measure and weighted F of a dis
+    prediction; definitions in include/genpercept_hip.h); with want_counts also the int64 [B, 537] counts (eval_metrics.structure_counts),
+    with want_edt also the int64 [B, H, W] distance-transform keys (eval_metrics.edt_keys, the same bits), in that order.  pred: [B, H, W],
+    [B, 1, H, W] or [H, W], a float map in [0, 1] (quantised to 8 bits by the kernel) or uint8; gt: uint8, same shape; H, W <= 32767.
+    Enqueued on the current stream, no synchronisation."""
+    lib = load_library()
+    pred, gt = _eval_maps(pred, "pred"), _eval_maps(gt, "gt")
+    assert pred.is_cuda and gt.is_cuda
+    if gt.dtype != torch.uint8:
+        raise ValueError(f"gt: the ground truth is an 8-bit mask (uint8), got {gt.dtype}")
+    if pred.shape != gt.shape:
+        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have one shape")
+    is_u8 = pred.dtype == torch.uint8
+    if not is_u8 and not pred.dtype.is_floating_point:
+        raise ValueError(f"pred: a float map in [0, 1] or its uint8 quantisation, got {pred.dtype}")
+    pred, gt = (pred if is_u8 else pred.to(torch.float32)).contiguous(), gt.contiguous()
+    b, h, w = (int(v) for v in pred.shape)
+    if h > 32767 or w > 32767:
+        raise ValueError(f"structure scores take maps of at most 32767 x 32767, got {h} x {w}")
+    out = torch.empty((b, STRUCTURE_OUT), dtype=torch.float64, device=pred.device)
+    counts = torch.empty((b, STRUCTURE_COUNTS), dtype=torch.int64, device=pred.device) if want_counts else None
+    edt = torch.empty((b, h, w), dtype=torch.int64, device=pred.device) if want_edt else None
+    nbytes = int(lib.gp_eval_structure_workspace(b, h, w))
+    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=pred.device)
+    st = lib.gp_eval_structure(pred.data_ptr(), int(is_u8), gt.data_ptr(), b, h, w, out.data_ptr(), _ptr(counts), _ptr(edt), ws.data_ptr(), nbytes,
+                               _stream_ptr(pred.device))
+    if st != GP_OK:
+        raise RuntimeError(f"gp_eval_structure failed ({st})")
+    res = (out,) + ((counts,) if want_counts else ()) + ((edt,) if want_edt else ())
+    return res if len(res) > 1 else out
+
+
+def eval_structure(pred: torch.Tensor, gt: torch.Tensor):
+    """eval_metrics.structure_metrics for a batch of maps that are on the device (arguments as `eval_structure_raw`).  Returns one dict per
+    image with STRUCTURE_OUT_NAMES (n, n_fg, cx, cy as ints).  One device -> host copy of B x 15 doubles."""
+    raw = eval_structure_raw(pred, gt).cpu().numpy()
+    ints = ("n", "n_fg", "cx", "cy")
+    return [{k: (int(row[j]) if k in ints else float(row[j])) for j, k in enumerate(STRUCTURE_OUT_NAMES)} for row in raw]
 
 
 ENSEMBLE_REDUCTION = {"median": 0, "mean": 1}

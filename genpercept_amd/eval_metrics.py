@@ -7,6 +7,7 @@ Per-image masked means, then a mean over images — exactly the reference's redu
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -257,3 +258,220 @@ def mask_metrics_from_counts(counts) -> Dict[str, float]:
 def mask_metrics(pred: np.ndarray, gt: np.ndarray, region: Optional[np.ndarray] = None) -> Dict[str, float]:
     """One image: pred a float map in [0, 1] (quantised by `quantize_mask`) or uint8, gt uint8, region optional (non-zero = scored)."""
     return mask_metrics_from_counts(mask_counts(quantize_mask(pred), gt, region))
+
+
+# ---- dis structure scores: S-measure, E-measure, weighted F -------------------------------------------------------------------------------
+# The other three columns of the DIS5K table.  Definitions: include/genpercept_hip.h (gp_eval_structure); the functions below restate them.
+# S and E are fixed sequences of float64 operations on integer counts (bit-equal to the device); the weighted F shares keys, Et, E, EA and
+# the minimum with the device bit for bit and differs in exp's last bits and in the order of the two float64 sums.
+STRUCTURE_METRICS = ["s_alpha", "max_e", "mean_e", "adp_e", "wf"]
+STRUCTURE_COUNTS = 5 + 20 + 2 * 256  # n_fg, sum_fg x, sum_fg y, cx, cy, 4 x (N, a, a2, b, c), hist_bg[256], hist_fg[256]
+EDT_NO_KEY = np.uint64(0xFFFFFFFFFFFFFFFF)  # every key of an image without foreground
+# the normalised 7 x 7 Gaussian, sigma = 5 (the same literals as csrc/eval_structure.hip ES_K)
+WF_K_HEX = """
+    0x1.1075d7f1e0af6p-6, 0x1.2d1d7fa535fb0p-6, 0x1.3fbc331b753f8p-6, 0x1.4631b947fa56fp-6, 0x1.3fbc331b753f8p-6, 0x1.2d1d7fa535fb0p-6, 0x1.1075d7f1e0af6p-6,
+    0x1.2d1d7fa535fb0p-6, 0x1.4cc8a6b9e9761p-6, 0x1.615cabadc2e2fp-6, 0x1.688018ee505f7p-6, 0x1.615cabadc2e2fp-6, 0x1.4cc8a6b9e9761p-6, 0x1.2d1d7fa535fb0p-6,
+    0x1.3fbc331b753f8p-6, 0x1.615cabadc2e2fp-6, 0x1.77367232eb477p-6, 0x1.7ecadfe6d5847p-6, 0x1.77367232eb477p-6, 0x1.615cabadc2e2fp-6, 0x1.3fbc331b753f8p-6,
+    0x1.4631b947fa56fp-6, 0x1.688018ee505f7p-6, 0x1.7ecadfe6d5847p-6, 0x1.8686809d3875ep-6, 0x1.7ecadfe6d5847p-6, 0x1.688018ee505f7p-6, 0x1.4631b947fa56fp-6,
+    0x1.3fbc331b753f8p-6, 0x1.615cabadc2e2fp-6, 0x1.77367232eb477p-6, 0x1.7ecadfe6d5847p-6, 0x1.77367232eb477p-6, 0x1.615cabadc2e2fp-6, 0x1.3fbc331b753f8p-6,
+    0x1.2d1d7fa535fb0p-6, 0x1.4cc8a6b9e9761p-6, 0x1.615cabadc2e2fp-6, 0x1.688018ee505f7p-6, 0x1.615cabadc2e2fp-6, 0x1.4cc8a6b9e9761p-6, 0x1.2d1d7fa535fb0p-6,
+    0x1.1075d7f1e0af6p-6, 0x1.2d1d7fa535fb0p-6, 0x1.3fbc331b753f8p-6, 0x1.4631b947fa56fp-6, 0x1.3fbc331b753f8p-6, 0x1.2d1d7fa535fb0p-6, 0x1.1075d7f1e0af6p-6"""
+WF_K = np.array([float.fromhex(v) for v in WF_K_HEX.replace("\n", " ").split(",")], dtype=np.float64).reshape(7, 7)
+WF_C = float.fromhex("-0x1.1be9bff2e94bfp-3")  # log(0.5) / 5
+
+
+def _check_q_g(q, g):
+    q, g = np.asarray(q), np.asarray(g)
+    if q.dtype != np.uint8 or g.dtype != np.uint8 or q.shape != g.shape or q.ndim != 2:
+        raise ValueError(f"q and g must be uint8 [H, W] arrays of one shape, got {q.dtype} {q.shape} and {g.dtype} {g.shape}")
+    if q.shape[0] < 1 or q.shape[1] < 1 or q.shape[0] > 32767 or q.shape[1] > 32767 or q.size > 0x7FFFFFFF:
+        raise ValueError(f"1 <= H, W <= 32767 and H * W <= 2^31 - 1, got {q.shape}")
+    return q, g
+
+
+def structure_counts(q: np.ndarray, g: np.ndarray) -> np.ndarray:
+    """The integer counts of one image behind S and E, int64 [537] = n_fg, sum_fg x, sum_fg y, cx, cy, then for the blocks LT, RT, LB, RB the
+    centroid cuts (N, a = sum q, a2 = sum q^2, b = sum G, c = sum q G), then hist_bg[256], hist_fg[256].  q, g: uint8 [H, W]; G = g > 128."""
+    q, g = _check_q_g(q, g)
+    h, w = q.shape
+    fg = g > 128
+    out = np.zeros(STRUCTURE_COUNTS, dtype=np.int64)
+    ys, xs = np.nonzero(fg)
+    n_fg = int(ys.size)
+    sx, sy = int(xs.sum()), int(ys.sum())
+    cx = (2 * sx + n_fg) // (2 * n_fg) if n_fg else 0
+    cy = (2 * sy + n_fg) // (2 * n_fg) if n_fg else 0
+    out[:5] = n_fg, sx, sy, cx, cy
+    qi, gi = q.astype(np.int64), fg.astype(np.int64)
+    for k, (rows, cols) in enumerate(((slice(0, cy + 1), slice(0, cx + 1)), (slice(0, cy + 1), slice(cx + 1, w)),
+                                      (slice(cy + 1, h), slice(0, cx + 1)), (slice(cy + 1, h), slice(cx + 1, w)))):
+        qq, gg = qi[rows, cols], gi[rows, cols]
+        out[5 + 5 * k:10 + 5 * k] = qq.size, qq.sum(), (qq * qq).sum(), gg.sum(), (qq * gg).sum()
+    out[25:281] = np.bincount(q[~fg], minlength=256)
+    out[281:537] = np.bincount(q[fg], minlength=256)
+    return out
+
+
+def _e_term(p: float, g: float, mp: float, mg: float) -> float:
+    ap, ag = p - mp, g - mg
+    phi = ((2.0 * ap) * ag) / (ap * ap + ag * ag)
+    return ((phi + 1.0) * (phi + 1.0)) / 4.0
+
+
+def e_curve_from_counts(counts) -> list:
+    """E_t for the 256 thresholds "q >= t" from the two class histograms (Python floats)."""
+    c = [int(v) for v in np.asarray(counts).reshape(-1)]
+    if len(c) != STRUCTURE_COUNTS:
+        raise ValueError(f"expected {STRUCTURE_COUNTS} counts, got {len(c)}")
+    hist_bg, hist_fg = c[25:281], c[281:537]
+    n_fg = sum(hist_fg)
+    n = n_fg + sum(hist_bg)
+    dm1 = float(max(n - 1, 1))
+    e = [0.0] * 256
+    tp = bp = 0
+    for t in range(255, -1, -1):
+        tp += hist_fg[t]
+        bp += hist_bg[t]
+        p = tp + bp
+        if n_fg == 0:
+            e[t] = float(n - p) / dm1
+        elif n_fg == n:
+            e[t] = float(p) / dm1
+        else:
+            mp, mg = p / n, n_fg / n
+            s = float(tp) * _e_term(1.0, 1.0, mp, mg)
+            s = s + float(bp) * _e_term(1.0, 0.0, mp, mg)
+            s = s + float(n_fg - tp) * _e_term(0.0, 1.0, mp, mg)
+            s = s + float(n - n_fg - bp) * _e_term(0.0, 0.0, mp, mg)
+            e[t] = s / dm1
+    return e
+
+
+def _s_object(N: int, a: int, a2: int) -> float:
+    xb, m2 = a / (255.0 * N), a2 / (65025.0 * N)
+    d = m2 - xb * xb
+    if d < 0.0:
+        d = 0.0
+    var = 0.0 if N == 1 else (d * N) / (N - 1)
+    return (2.0 * xb) / ((xb * xb + 1.0) + math.sqrt(var))
+
+
+def _s_block(N: int, a: int, a2: int, b: int, c: int) -> float:
+    xb, yb = a / (255.0 * N), b / N
+    sxx = syy = sxy = 0.0
+    if N > 1:
+        sxx = (a2 / 65025.0 - (xb * xb) * N) / (N - 1)
+        syy = (b - (yb * yb) * N) / (N - 1)
+        sxy = (c / 255.0 - (xb * yb) * N) / (N - 1)
+    A, Bq = ((4.0 * xb) * yb) * sxy, (xb * xb + yb * yb) * (sxx + syy)
+    if A != 0.0 and Bq != 0.0:
+        return A / Bq
+    return 1.0 if A == 0.0 and Bq == 0.0 else 0.0
+
+
+def structure_from_counts(counts) -> Dict[str, float]:
+    """S and E from `structure_counts`: n, n_fg, s_alpha, s_object, s_region, max_e, mean_e, adp_e, cx, cy -- gp_eval_structure's values of
+    the same names, bit for bit (s_object = s_region = NaN in the degenerate S branches)."""
+    c = [int(v) for v in np.asarray(counts).reshape(-1)]
+    e = e_curve_from_counts(c)
+    hist_bg, hist_fg = c[25:281], c[281:537]
+    n_fg = sum(hist_fg)
+    n = n_fg + sum(hist_bg)
+    total, best = e[0], e[0]
+    for t in range(1, 256):
+        total = total + e[t]
+        if e[t] > best:
+            best = e[t]
+    sum_q = sum(v * (hist_bg[v] + hist_fg[v]) for v in range(256))
+    t_a = (min(2 * sum_q, 255 * n) + n - 1) // n
+    nan = float("nan")
+    if n_fg == 0:
+        s, so, sr = 1.0 - sum_q / (255.0 * n), nan, nan
+    elif n_fg == n:
+        s, so, sr = sum_q / (255.0 * n), nan, nan
+    else:
+        u = n_fg / n
+        a_fg, a2_fg = sum(v * hist_fg[v] for v in range(256)), sum(v * v * hist_fg[v] for v in range(256))
+        a_bg, a2_bg = sum((255 - v) * hist_bg[v] for v in range(256)), sum((255 - v) * (255 - v) * hist_bg[v] for v in range(256))
+        so = u * _s_object(n_fg, a_fg, a2_fg) + (1.0 - u) * _s_object(n - n_fg, a_bg, a2_bg)
+        sr = 0.0
+        for k in range(4):
+            N, a, a2, b, cc = c[5 + 5 * k:10 + 5 * k]
+            if N != 0:
+                sr = sr + (N / n) * _s_block(N, a, a2, b, cc)
+        s = 0.5 * so + 0.5 * sr
+        if s < 0.0:
+            s = 0.0
+    return dict(n=n, n_fg=n_fg, s_alpha=s, s_object=so, s_region=sr, max_e=best, mean_e=total / 256.0, adp_e=e[t_a], cx=c[3], cy=c[4])
+
+
+def edt_keys(G: np.ndarray) -> np.ndarray:
+    """The exact Euclidean distance transform with nearest-foreground indices of a boolean [H, W] array, as uint64 keys (d2 << 32 | idx): d2 the
+    squared distance to the nearest True pixel, idx = y' * W + x' its row-major index, the smallest index among the equidistant ones (a True
+    pixel: (0, itself)).  No True pixel: every key EDT_NO_KEY.  Two passes: per column the nearest True pixel above-or-at and below-or-at
+    gives each (row, column) its better candidate key; per row, pixel x minimises key(x') + ((x - x')^2 << 32), one offset at a time, until
+    the offset's square passes every pixel's best d2."""
+    G = np.asarray(G).astype(bool)
+    if G.ndim != 2 or G.shape[0] > 32767 or G.shape[1] > 32767:
+        raise ValueError(f"a boolean [H, W] array with H, W <= 32767, got {G.shape}")
+    h, w = G.shape
+    if not G.any():
+        return np.full((h, w), EDT_NO_KEY, dtype=np.uint64)
+    far = np.uint64((0x7FFFFFFF << 32) | 0xFFFFFFFF)
+    ys, xs = np.arange(h, dtype=np.int64)[:, None], np.arange(w, dtype=np.int64)[None, :]
+    up = np.maximum.accumulate(np.where(G, ys, -1), axis=0)                  # the nearest True row at or above, -1: none
+    dn = np.minimum.accumulate(np.where(G, ys, h)[::-1], axis=0)[::-1]       # at or below, h: none
+    ku = np.where(up >= 0, (((ys - up) ** 2) << 32) | (np.maximum(up, 0) * w + xs), 0).astype(np.uint64)
+    ku[up < 0] = far
+    kd = np.where(dn < h, (((dn - ys) ** 2) << 32) | (np.minimum(dn, h - 1) * w + xs), 0).astype(np.uint64)
+    kd[dn >= h] = far
+    col = np.minimum(ku, kd)
+    best = col.copy()
+    shift = np.uint64(32)
+    for r in range(1, w):
+        if r * r > int(best.max() >> shift):
+            break
+        add = np.uint64((r * r) << 32)
+        np.minimum(best[:, r:], col[:, :-r] + add, out=best[:, r:])          # the candidate r columns to the left
+        np.minimum(best[:, :-r], col[:, r:] + add, out=best[:, :-r])         # ... to the right
+    return best
+
+
+def weighted_f(q: np.ndarray, g: np.ndarray, keys: Optional[np.ndarray] = None) -> Dict[str, float]:
+    """The weighted F-measure (beta^2 = 1) of the 8-bit prediction q against G = g > 128: wf, wf_precision, wf_recall, wf_sum_fg, wf_sum_bg as
+    gp_eval_structure defines them (`keys`: edt_keys(G), computed here unless given)."""
+    q, g = _check_q_g(q, g)
+    h, w = q.shape
+    fg = g > 128
+    n_fg = int(fg.sum())
+    if n_fg == 0:
+        return dict(wf=0.0, wf_precision=0.0, wf_recall=0.0, wf_sum_fg=0.0, wf_sum_bg=0.0)
+    if keys is None:
+        keys = edt_keys(fg)
+    idx = (keys & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    d2 = (keys >> np.uint64(32)).astype(np.float64)
+    et = (255 - q.reshape(-1)[idx].astype(np.int64)).astype(np.float64) / 255.0
+    e = np.where(fg, et, q.astype(np.float64) / 255.0)
+    pad = np.zeros((h + 6, w + 6), dtype=np.float64)   # a tap outside the image adds K * 0.0 = +0.0: the same bits as skipping it
+    pad[3:h + 3, 3:w + 3] = et
+    ea = np.zeros((h, w), dtype=np.float64)
+    for i in range(7):
+        for j in range(7):
+            ea = ea + WF_K[i, j] * pad[i:i + h, j:j + w]
+    ew = np.where(fg, np.minimum(ea, e), e * (2.0 - np.exp(WF_C * np.sqrt(d2))))
+    s_fg, s_bg = float(ew[fg].sum()), float(ew[~fg].sum())
+    tpw = n_fg - s_fg
+    rec = 1.0 - s_fg / n_fg
+    den = tpw + s_bg
+    prec = tpw / den if den != 0.0 else 0.0
+    wf = ((2.0 * rec) * prec) / (rec + prec) if rec + prec != 0.0 else 0.0
+    return dict(wf=wf, wf_precision=prec, wf_recall=rec, wf_sum_fg=s_fg, wf_sum_bg=s_bg)
+
+
+def structure_metrics(pred: np.ndarray, gt: np.ndarray) -> Dict[str, float]:
+    """One image: pred a float map in [0, 1] (quantised by `quantize_mask`) or uint8, gt uint8, both [H, W].  STRUCTURE_METRICS and the other
+    values of `structure_from_counts` and `weighted_f`."""
+    q = quantize_mask(pred)
+    m = structure_from_counts(structure_counts(q, gt))
+    m.update(weighted_f(q, gt))
+    return m

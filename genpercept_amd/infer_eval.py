@@ -529,6 +529,7 @@ def infer_and_evaluate_normals(pipe, base_dir: str, samples: Sequence[Sequence[s
 
 # ---- dis / matting: 8-bit masks and alpha maps ------------------------------------------------------------------------------------------------
 MASK_METRICS = list(em.MASK_METRICS)  # per-image values, in order; the dataset-level "max_f_dataset" comes on top
+STRUCTURE_METRICS = list(em.STRUCTURE_METRICS)  # with structure=True: appended to the per-image columns, the means and the files
 
 
 def read_gt_mask(path: str) -> np.ndarray:
@@ -598,13 +599,16 @@ def _write_mask_eval_files(output_dir: str, names: List[str], per_sample, result
 
 def evaluate_mask_predictions(prediction_dir: str, base_dir: str, samples: Sequence[Sequence[str]], name_mode: FileNameMode,
                               output_dir: Optional[str] = None, pred_suffix: str = ".npy", region_of: Optional[Callable] = None,
-                              read_gt: Optional[Callable[[str], np.ndarray]] = None) -> Dict[str, float]:
+                              read_gt: Optional[Callable[[str], np.ndarray]] = None, structure: bool = False) -> Dict[str, float]:
     """The file route for what `run_inference(mode="dis" | "matting")` writes (`.npy`) or for 8-bit `.png` maps (pred_suffix): per image
     eval_metrics.mask_metrics against the 8-bit ground truth of column 1 (read_gt_mask or `read_gt`), over `region_of(sample, gt)` (a bool
     array, e.g. a trimap's unknown region; None: every pixel).  Returns the means of the per-image MASK_METRICS and "max_f_dataset", the
     maximum F of the dataset-mean precision / recall curves.  Samples without ground truth ("None") or without a prediction file are
-    skipped.  Optionally writes `eval_metrics-mask.txt` and `per_sample_metrics-mask.csv`."""
-    names = list(MASK_METRICS)
+    skipped.  Optionally writes `eval_metrics-mask.txt` and `per_sample_metrics-mask.csv`.  structure: the dis structure scores
+    (eval_metrics.structure_metrics: STRUCTURE_METRICS, whole-image quantities, so not together with region_of) as five more columns."""
+    if structure and region_of is not None:
+        raise ValueError("structure scores are whole-image quantities: structure=True does not go with region_of")
+    names = list(MASK_METRICS) + (list(STRUCTURE_METRICS) if structure else [])
     sums = {k: 0.0 for k in names}
     per_sample, counts = [], []
     for s in samples:
@@ -622,6 +626,8 @@ def evaluate_mask_predictions(prediction_dir: str, base_dir: str, samples: Seque
         if c[0] == 0:
             raise ValueError(f"{s[0]}: no pixel to evaluate the mask on (n = 0)")
         m = em.mask_metrics_from_counts(c)
+        if structure:
+            m.update(em.structure_metrics(pred, gt))
         for k in names:
             sums[k] += m[k]
         per_sample.append((pred_name, [m[k] for k in names]))
@@ -639,20 +645,27 @@ def infer_and_evaluate_masks(pipe, base_dir: str, samples: Sequence[Sequence[str
                              save_predictions: bool = False, prediction_dir: Optional[str] = None, evaluator: Optional[Callable] = None,
                              read_gt: Optional[Callable[[str], np.ndarray]] = None, region_of: Optional[Callable] = None, denoise_steps: int = 1,
                              ensemble_size: int = 1, processing_res: int = 0, match_input_res: bool = True, resample_method: str = "bilinear",
-                             fix_timesteps=None, prompt: str = "", prefetch: int = 2) -> Dict[str, float]:
+                             fix_timesteps=None, prompt: str = "", prefetch: int = 2, structure: bool = False,
+                             structure_evaluator: Optional[Callable] = None) -> Dict[str, float]:
     """`infer_and_evaluate` for mode "dis" or "matting": batches go through `pipe.predict_batch_device(mode=mode)`, the float [B, 1, H, W] maps
     stay on the device, and `evaluator` -- `engine.eval_mask` unless given: (pred, gt, region) -> one dict per image with MASK_METRICS and
     "counts" -- quantises and scores them there against the 8-bit ground truth of column 1 (and `region_of(sample, gt)`, if given), decoded on
     the host and uploaded per batch.  What it computes per image is `evaluate_mask_predictions`' quantity, bit for bit; sharding, the
     torch.distributed combination, the rank-0 files (`eval_metrics-mask.txt`, `per_sample_metrics-mask.csv`) and the return value on every
     rank are `infer_and_evaluate`'s, with one more float64 all_reduce for the precision / recall curves behind "max_f_dataset".
-    save_predictions: the maps are also written as `run_inference` would, float32 [H, W] `.npy` under prediction_dir (default: output_dir)."""
+    save_predictions: the maps are also written as `run_inference` would, float32 [H, W] `.npy` under prediction_dir (default: output_dir).
+    structure: the dis structure scores as five more per-image columns (STRUCTURE_METRICS), from a second device call on the same uploaded
+    batch -- `structure_evaluator`, `engine.eval_structure` unless given: (pred, gt) -> one dict per image; not together with region_of."""
     import torch
     if mode not in ("dis", "matting"):
         raise ValueError(f"mask evaluation is for mode 'dis' or 'matting', got {mode!r}")
-    names = list(MASK_METRICS)
+    if structure and region_of is not None:
+        raise ValueError("structure scores are whole-image quantities: structure=True does not go with region_of")
+    names = list(MASK_METRICS) + (list(STRUCTURE_METRICS) if structure else [])
     if evaluator is None:
         from .engine import eval_mask as evaluator
+    if structure and structure_evaluator is None:
+        from .engine import eval_structure as structure_evaluator
     if prediction_dir is None:
         prediction_dir = output_dir
     if save_predictions and prediction_dir is None:
@@ -676,6 +689,10 @@ def infer_and_evaluate_masks(pipe, base_dir: str, samples: Sequence[Sequence[str
         region_t = torch.from_numpy(np.stack(regions)).to(pred.device, non_blocking=True) if region_of is not None else None
         metrics = evaluator(pred[:, 0], gt_t, region_t)
         assert len(metrics) == len(group)
+        if structure:
+            more = structure_evaluator(pred[:, 0], gt_t)
+            assert len(more) == len(group)
+            metrics = [dict(m, **{k: s[k] for k in STRUCTURE_METRICS}) for m, s in zip(metrics, more)]
         for ((idx, _), _), m in zip(group, metrics):
             counts.append((idx, np.asarray(m["counts"])))
         if save_predictions:

@@ -267,6 +267,53 @@ gp_status gp_eval_mask(const void* pred, int pred_is_u8, const unsigned char* gt
                        double* out /* [B][10] */, unsigned long long* counts_out /* [B][516] or NULL */, void* workspace,
                        long long workspace_bytes, void* stream);
 
+/* ---- dis structure scores on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation; csrc/eval_structure.hip) ----
+ * The other three columns of the DIS5K table beside max F and MAE: S-measure (Fan 2017, alpha = 0.5), E-measure (Fan 2018) and the weighted
+ * F-measure (Margolin 2014, beta^2 = 1 as published).  The reference has no metric for dis (genpercept_trainer.py:1169 is a TODO), so the
+ * definitions are this project's; they follow the published evaluation code wherever integers allow, and eval_metrics.structure_counts /
+ * structure_from_counts / edt_keys / weighted_f are the same definitions on the host.  Deviations from the toolboxes: their `eps` terms are
+ * dropped wherever the branch structure already keeps the denominator non-zero (the E-measure's alignment and its n - 1, the S-measure's
+ * object and block quotients, the weighted F's precision and final quotient), the centroid is rounded in integers, and the weighted F works on
+ * the 8-bit prediction like everything else.
+ * pred, pred_is_u8, gt as for gp_eval_mask: everything is computed on the 8-bit prediction q; G = g > 128; no region (whole-image scores).
+ * p = q / 255.0, n = H * W, n_fg = |G|.  All float64 arithmetic is a fixed sequence of correctly rounded + - * / sqrt, no FMA.
+ * E-measure, from hist_bg / hist_fg alone.  Threshold t (positive where q >= t): class counts TP, FP, FN, TN, P_t = TP + FP, mp = P_t / n,
+ *   mg = n_fg / n.  0 < n_fg < n: per class ap = p - mp, ag = g - mg with p, g in {0, 1}, phi = ((2 * ap) * ag) / (ap * ap + ag * ag),
+ *   e = ((phi + 1) * (phi + 1)) / 4, E_t = (TP * e(TP) + FP * e(FP) + FN * e(FN) + TN * e(TN)) / max(n - 1, 1), summed in that order.
+ *   n_fg == 0: E_t = (n - P_t) / max(n - 1, 1);  n_fg == n: E_t = P_t / max(n - 1, 1).
+ *   max_e = max_t E_t;  mean_e = (E_0 + ... + E_255) / 256.0, left to right;  adp_e = E_{t_a} with gp_eval_mask's t_a.
+ * S-measure.  n_fg == 0: S = 1 - sum q / (255.0 * n);  n_fg == n: S = sum q / (255.0 * n);  otherwise S = max(0.5 * S_o + 0.5 * S_r, 0).
+ *   S_o = u * O(fg) + (1 - u) * O(bg), u = n_fg / n.  A class of N pixels with a = sum v, a2 = sum v^2 (v = q on the foreground, 255 - q on
+ *   the background): xb = a / (255.0 * N), m2 = a2 / (65025.0 * N), var = (max(m2 - xb * xb, 0) * N) / (N - 1) (0 for N == 1),
+ *   O = (2 * xb) / ((xb * xb + 1) + sqrt(var)).
+ *   S_r: cx = (2 * sum_fg x + n_fg) div (2 * n_fg), cy likewise (0-based, halves up).  Blocks rows [0, cy] / (cy, H) x columns [0, cx] /
+ *   (cx, W) in the order LT, RT, LB, RB, weight N_k / n.  Per block from N, a = sum q, a2 = sum q^2, b = sum G, c = sum q G:
+ *   xb = a / (255.0 * N), yb = b / N, sxx = (a2 / 65025.0 - (xb * xb) * N) / (N - 1), syy = (b - (yb * yb) * N) / (N - 1),
+ *   sxy = (c / 255.0 - (xb * yb) * N) / (N - 1) (all 0 for N == 1), A = ((4 * xb) * yb) * sxy, Bq = (xb * xb + yb * yb) * (sxx + syy),
+ *   Q = A / Bq when both are non-zero, 1 when both are 0, else 0.  S_r = sum w_k * Q_k in block order; a block with N == 0 adds nothing.
+ * Weighted F.  key(pixel) = min over foreground pixels of (d2 << 32 | idx): d2 the squared Euclidean distance, idx = y' * W + x'; among
+ *   equidistant foreground pixels the smallest row-major index wins; a foreground pixel's key is (0, itself); an image without foreground
+ *   has every key = 2^64 - 1.  Et = double(255 - q[idx]) / 255.0;  E = Et on the foreground, q / 255.0 on the background;  EA = the 49-tap
+ *   sum K[i][j] * Et(y + i - 3, x + j - 3) in row-major tap order, taps outside the image skipped, K the normalised 7 x 7 Gaussian with
+ *   sigma = 5 as a table of hex-float literals (eval_structure.hip ES_K == eval_metrics.WF_K);  Ew = min(EA, E) on the foreground,
+ *   E * (2 - exp(c * sqrt(double(d2)))) on the background, c = log(0.5) / 5 as a literal.  S_fg = sum_fg Ew, S_bg = sum_bg Ew: float64 sums
+ *   per 32 x 8 tile, tiles added in an order that depends on H and W alone.  TPw = n_fg - S_fg, R = 1 - S_fg / n_fg,
+ *   P = TPw / (TPw + S_bg) (0 when that is 0), wf = ((2 * R) * P) / (R + P) (0 when R + P == 0);  n_fg == 0: wf = P = R = S_fg = S_bg = 0.
+ *   Only exp may differ from the host in its last bits.
+ * out: double [B][15] = n, n_fg, s_alpha, s_object, s_region, max_e, mean_e, adp_e, wf, wf_precision, wf_recall, wf_sum_fg, wf_sum_bg, cx, cy
+ *   (s_object = s_region = NaN in the degenerate S branches; cx = cy = 0 without foreground).
+ * counts_out: optional unsigned 64-bit [B][537] = n_fg, sum_fg x, sum_fg y, cx, cy, 4 x (N, a, a2, b, c), hist_bg[256], hist_fg[256].
+ * edt_out: optional unsigned 64-bit [B][H][W], the keys.
+ * An image's values are bitwise the same from call to call and for every batch it is part of.  workspace: DEVICE scratch of at least the
+ * workspace entry's byte count (8-byte aligned; about 13 bytes per pixel), free again once the stream has passed the call.  Seven kernel
+ * launches on `stream` for every B, no global atomics, nothing read back.
+ * GP_ERR_INVALID before any HIP call: null pred / gt / out / workspace, B, H or W < 1, B > 65535, H or W > 32767 (d2 < 2^31),
+ * H * W > 2^31 - 1, pred_is_u8 outside 0..1, out / counts_out / edt_out / workspace not 8-byte aligned, workspace_bytes too small. */
+long long gp_eval_structure_workspace(int B, int H, int W);   /* bytes; 0 for B, H or W < 1; proportional to B; multiple of 8 */
+gp_status gp_eval_structure(const void* pred, int pred_is_u8, const unsigned char* gt, int B, int H, int W, double* out /* [B][15] */,
+                            unsigned long long* counts_out /* [B][537] or NULL */, unsigned long long* edt_out /* [B][H][W] keys or NULL */,
+                            void* workspace, long long workspace_bytes, void* stream);
+
 /* ---- test-time ensembling on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation, no atomics; csrc/ensemble.hip) ----
  * The tensor half of ensemble_depth (genpercept/util/ensemble.py:43-205, called at genpercept_pipeline.py:289-298) for the E members of each of
  * B images; the optimiser that finds the per-member (scale, shift) runs on the host between the two entries, on what the gather produced.

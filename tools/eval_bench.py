@@ -1,4 +1,4 @@
-"""Time the device depth (or, with --normals, surface-normal; with --masks, dis / matting) evaluation against the host evaluation, and the batched device loop on the tiny pipeline.
+"""Time the device depth (or, with --normals, surface-normal; with --masks, dis / matting; with --structure, dis structure-score) evaluation against the host evaluation, and the batched device loop on the tiny pipeline.
 
   python tools/eval_bench.py --out profiles/<name>.json
 
@@ -21,6 +21,14 @@
    truth --, 6 with a region, and one finalising workgroup per image) at 4 x 1024 x 1024 and 1 x 4032 x 6048, on a 0 / 255 mask and on
    uniform-random values, against `eval_metrics.mask_metrics` on the same arrays on the host (wall clock), and against the time the bytes
    alone cost at the device-to-device copy bandwidth measured in the same process.  The two sides' values are compared on the spot (bit-equal).
+
+  python tools/eval_bench.py --structure --out profiles/<name>.json
+
+5. `--structure` (instead of 1 and 2): the `gp_eval_structure` entry behind `engine.eval_structure` (S-measure, E-measure, weighted F: seven
+   launches, the exact distance transform among them) at 4 x 1024 x 1024 and 1 x 2048 x 2048, on a mask-like input (a disc, 3 % of the
+   prediction flipped) and on a single far object (a small square in one corner: the row search of the distance transform spans the image),
+   against `eval_metrics.structure_metrics` on the same arrays on the host (wall clock, one run: it takes seconds).  The exact scores are
+   compared on the spot (bit-equal), wf to 1e-8.  `--no-host` skips the host route (for a kernel trace of the device calls alone).
 Needs a GPU; there is no CPU fall-back."""
 import argparse
 import json
@@ -206,6 +214,69 @@ def bench_eval_mask(b, h, w, kind, iters, host_runs, copy_gb_per_s):
                 device_equals_host=True)
 
 
+def structure_case(b, h, w, seed, kind):
+    """kind "mask": mask_case's disc; "far": one 16 x 16 object in the bottom-right corner, found by the prediction up to 3 % flips."""
+    if kind == "mask":
+        return mask_case(b, h, w, seed, "mask")
+    rng = np.random.default_rng(seed)
+    obj = np.zeros((b, h, w), dtype=bool)
+    obj[:, h - 24:h - 8, w - 24:w - 8] = True
+    flip = rng.random((b, h, w), dtype=np.float32) < 0.03
+    return (obj ^ flip).astype(np.float32), (obj * 255).astype(np.uint8)
+
+
+def time_eval_structure(tp, tg, iters):
+    """ms per gp_eval_structure call: the C entry itself on preallocated buffers (the seven launches, none of the binding's bookkeeping)."""
+    from genpercept_amd import engine as ge
+    lib = ge.load_library()
+    b, h, w = (int(v) for v in tp.shape)
+    nbytes = int(lib.gp_eval_structure_workspace(b, h, w))
+    ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=tp.device)
+    out = torch.empty((b, 15), dtype=torch.float64, device=tp.device)
+    stream = int(torch.cuda.current_stream(tp.device).cuda_stream)
+
+    def call():
+        st = lib.gp_eval_structure(tp.data_ptr(), int(tp.dtype == torch.uint8), tg.data_ptr(), b, h, w, out.data_ptr(), None, None, ws.data_ptr(), nbytes,
+                                   stream)
+        assert st == ge.GP_OK, st
+
+    for _ in range(3):
+        call()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        call()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def bench_eval_structure(b, h, w, kind, iters, host):
+    from genpercept_amd import engine as ge
+    from genpercept_amd import eval_metrics as em
+    d = torch.device("cuda", 0)
+    pred, gt = structure_case(b, h, w, 5, kind)
+    tp, tg = (torch.from_numpy(x).to(d) for x in (pred, gt))
+    dev_ms = time_eval_structure(tp, tg, iters)
+    t0 = time.perf_counter()
+    metrics = ge.eval_structure(tp, tg)  # with the copy of the 15 values per image and the host synchronise
+    call_ms = (time.perf_counter() - t0) * 1e3
+    res = dict(shape=[b, h, w], input=kind, device_ms_per_call=dev_ms, device_iters=iters, launches_per_call=7, device_call_with_sync_ms=call_ms,
+               workspace_bytes=int(ge.load_library().gp_eval_structure_workspace(b, h, w)), scores_image_0={k: metrics[0][k] for k in em.STRUCTURE_METRICS})
+    if host:
+        t0 = time.perf_counter()
+        ref = [em.structure_metrics(pred[i], gt[i]) for i in range(b)]
+        host_ms = (time.perf_counter() - t0) * 1e3
+        worst = 0.0
+        for i in range(b):
+            assert all(metrics[i][k] == ref[i][k] for k in ("s_alpha", "max_e", "mean_e", "adp_e", "n_fg", "cx", "cy")), (i, metrics[i], ref[i])
+            worst = max(worst, abs(metrics[i]["wf"] - ref[i]["wf"]) / ref[i]["wf"])
+        assert worst <= 1e-8, worst
+        res.update(host_structure_metrics_ms=host_ms, host_runs=1, host_over_device=host_ms / dev_ms, s_and_e_equal_host=True, wf_worst_rel_device_vs_host=worst)
+    return res
+
+
 def bench_loop(n_images, batch_sizes, repeats):
     from PIL import Image
     from genpercept_amd import GenPerceptPipeline
@@ -258,10 +329,16 @@ def main():
     ap.add_argument("--skip-loop", action="store_true")
     ap.add_argument("--normals", action="store_true", help="time engine.eval_normal against normal_angular_error instead")
     ap.add_argument("--masks", action="store_true", help="time gp_eval_mask against mask_metrics instead")
+    ap.add_argument("--structure", action="store_true", help="time gp_eval_structure against structure_metrics instead")
+    ap.add_argument("--no-host", action="store_true", help="with --structure: the device calls alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU")
-    if a.masks:
+    if a.structure:
+        res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box",
+                   eval_structure=[bench_eval_structure(b, h, w, kind, a.iters, not a.no_host) for (b, h, w) in ((4, 1024, 1024), (1, 2048, 2048))
+                                   for kind in ("mask", "far")])
+    elif a.masks:
         bw = copy_bandwidth(torch.device("cuda", 0))
         res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box",
                    eval_mask=[bench_eval_mask(b, h, w, kind, a.iters, runs, bw) for (b, h, w, runs) in ((4, 1024, 1024, 3), (1, 4032, 6048, 1))
@@ -271,7 +348,7 @@ def main():
                    eval_normal=[bench_eval_normal(4, 480, 640, a.iters, 3), bench_eval_normal(1, 4032, 6048, a.iters, 1)])
     else:
         res = dict(device=torch.cuda.get_device_name(0), eval_depth=[bench_eval(1, 4032, 6048, a.iters, 1), bench_eval(4, 480, 640, a.iters, 3)])
-    if not a.skip_loop and not a.normals and not a.masks:
+    if not a.skip_loop and not a.normals and not a.masks and not a.structure:
         res["infer_and_evaluate"] = bench_loop(16, (1, 4), 3)
     text = json.dumps(res, indent=1)
     print(text)
