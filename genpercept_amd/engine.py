@@ -156,6 +156,8 @@ SYMBOLS = {
     "gp_eval_mask": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
     "gp_eval_structure_workspace": (_ll, [_i, _i, _i]),
     "gp_eval_structure": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _ll, _vp]),
+    "gp_eval_matting_workspace": (_ll, [_i, _i, _i]),
+    "gp_eval_matting": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _ll, _vp]),
     "gp_ensemble_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gp_ensemble_workspace": (_ll, [_i, _i, _i, _i]),
     "gp_ensemble_reduce": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
@@ -1123,6 +1125,63 @@ def eval_structure(pred: torch.Tensor, gt: torch.Tensor):
     raw = eval_structure_raw(pred, gt).cpu().numpy()
     ints = ("n", "n_fg", "cx", "cy")
     return [{k: (int(row[j]) if k in ints else float(row[j])) for j, k in enumerate(STRUCTURE_OUT_NAMES)} for row in raw]
+
+
+MATTING_METRICS = ["grad", "conn"]  # gp_eval_matting's out[1], [2]; eval_metrics.MATTING_METRICS
+MATTING_OUT_NAMES = ["n", "grad", "conn", "grad_sum"]
+MATTING_OUT = 4       # the names above
+MATTING_COUNTS = 13   # n, conn_num, the counts of the levels 0..10 over the whole image
+
+
+def eval_matting_raw(pred: torch.Tensor, gt: torch.Tensor, region: Optional[torch.Tensor] = None, want_counts: bool = False,
+                     want_levels: bool = False, want_grad_map: bool = False):
+    """gp_eval_matting on device tensors: float64 [B, 4] ON THE DEVICE = MATTING_OUT_NAMES (gradient and connectivity error of a matting
+    prediction; definitions in include/genpercept_hip.h; NaN after n for an image whose region is empty); with want_counts also the int64
+    [B, 13] counts (eval_metrics.conn_error's "counts"), with want_levels the uint8 [B, H, W] levels (eval_metrics.conn_levels), with
+    want_grad_map the float64 [B, H, W] error map (eval_metrics.grad_error_map, the same bits), in that order.  pred: [B, H, W], [B, 1, H, W]
+    or [H, W], a float map in [0, 1] (quantised to 8 bits by the kernel) or uint8; gt: uint8, same shape; region: bool or integer, non-zero =
+    scored, None = every pixel (it restricts only the sums).  Enqueued on the current stream, no synchronisation."""
+    lib = load_library()
+    pred, gt = _eval_maps(pred, "pred"), _eval_maps(gt, "gt")
+    assert pred.is_cuda and gt.is_cuda
+    if gt.dtype != torch.uint8:
+        raise ValueError(f"gt: the ground truth is an 8-bit alpha map (uint8), got {gt.dtype}")
+    if pred.shape != gt.shape:
+        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have one shape")
+    is_u8 = pred.dtype == torch.uint8
+    if not is_u8 and not pred.dtype.is_floating_point:
+        raise ValueError(f"pred: a float map in [0, 1] or its uint8 quantisation, got {pred.dtype}")
+    pred, gt = (pred if is_u8 else pred.to(torch.float32)).contiguous(), gt.contiguous()
+    b, h, w = (int(v) for v in pred.shape)
+    if region is not None:
+        region = _eval_maps(region, "region")
+        assert region.is_cuda
+        if tuple(region.shape) != (b, h, w):
+            raise ValueError(f"region {tuple(region.shape)} does not match the maps {(b, h, w)}")
+        region = (region.contiguous().view(torch.uint8) if region.dtype in (torch.bool, torch.uint8) else (region != 0).view(torch.uint8)).contiguous()
+    out = torch.empty((b, MATTING_OUT), dtype=torch.float64, device=pred.device)
+    counts = torch.empty((b, MATTING_COUNTS), dtype=torch.int64, device=pred.device) if want_counts else None
+    levels = torch.empty((b, h, w), dtype=torch.uint8, device=pred.device) if want_levels else None
+    grad_map = torch.empty((b, h, w), dtype=torch.float64, device=pred.device) if want_grad_map else None
+    nbytes = int(lib.gp_eval_matting_workspace(b, h, w))
+    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=pred.device)
+    st = lib.gp_eval_matting(pred.data_ptr(), int(is_u8), gt.data_ptr(), _ptr(region), b, h, w, out.data_ptr(), _ptr(counts), _ptr(levels),
+                             _ptr(grad_map), ws.data_ptr(), nbytes, _stream_ptr(pred.device))
+    if st != GP_OK:
+        raise RuntimeError(f"gp_eval_matting failed ({st})")
+    res = (out,) + ((counts,) if want_counts else ()) + ((levels,) if want_levels else ()) + ((grad_map,) if want_grad_map else ())
+    return res if len(res) > 1 else out
+
+
+def eval_matting(pred: torch.Tensor, gt: torch.Tensor, region: Optional[torch.Tensor] = None):
+    """eval_metrics.matting_metrics for a batch of maps that are on the device (arguments as `eval_matting_raw`).  Returns one dict per image
+    with MATTING_OUT_NAMES (n as an int).  Raises ValueError naming the image when its region is empty.  One device -> host copy of B x 4
+    doubles."""
+    raw = eval_matting_raw(pred, gt, region).cpu().numpy()
+    for i, row in enumerate(raw):
+        if row[0] == 0:
+            raise ValueError(f"image {i}: no pixel to evaluate the alpha map on (n = 0)")
+    return [{k: (int(row[j]) if k == "n" else float(row[j])) for j, k in enumerate(MATTING_OUT_NAMES)} for row in raw]
 
 
 ENSEMBLE_REDUCTION = {"median": 0, "mean": 1}

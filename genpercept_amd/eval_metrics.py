@@ -475,3 +475,139 @@ def structure_metrics(pred: np.ndarray, gt: np.ndarray) -> Dict[str, float]:
     m = structure_from_counts(structure_counts(q, gt))
     m.update(weighted_f(q, gt))
     return m
+
+
+# ---- matting: gradient and connectivity errors ----------------------------------------------------------------------------------------------
+# The other two columns of the matting table beside SAD and MSE (Rhemann et al. 2009).  Definitions: include/genpercept_hip.h (gp_eval_matting);
+# the functions below restate them.  Conn is integers up to one division (bit-equal to the device); the gradient error map is one prescribed
+# sequence of float64 + - * / sqrt per pixel (bit-equal) and its sum differs from the device's in the order of the additions.
+MATTING_METRICS = ["grad", "conn"]
+MATTING_COUNTS = 2 + 11  # n, conn_num, the counts of the levels 0..10 over the whole image
+CONN_T = [26, 51, 77, 102, 128, 153, 179, 204, 230, 255]  # T_k = ceil(255 k / 10), k = 1..10
+# the 9-tap Gaussian (sigma = 1.4) and its derivative, each divided by its L2 norm (the same literals as csrc/eval_matting.hip MT_G, MT_D)
+GRAD_G_HEX = """0x1.5f2161173037cp-7, 0x1.05c2b72947cf6p-4, 0x1.d49edcea5016bp-3, 0x1.f7af85f5976d7p-2, 0x1.4506d2f73739dp-1, 0x1.f7af85f5976d7p-2,
+    0x1.d49edcea5016bp-3, 0x1.05c2b72947cf6p-4, 0x1.5f2161173037cp-7"""
+GRAD_D_HEX = """0x1.62b49a56df053p-5, 0x1.8ca37e89855ffp-3, 0x1.d9645351e6fcbp-2, 0x1.fcd0621654797p-2, 0x0.0p+0, -0x1.fcd0621654797p-2,
+    -0x1.d9645351e6fcbp-2, -0x1.8ca37e89855ffp-3, -0x1.62b49a56df053p-5"""
+GRAD_G = np.array([float.fromhex(v) for v in GRAD_G_HEX.replace("\n", " ").split(",")], dtype=np.float64)
+GRAD_D = np.array([float.fromhex(v) for v in GRAD_D_HEX.replace("\n", " ").split(",")], dtype=np.float64)
+
+
+def _components_min_index(mask: np.ndarray) -> np.ndarray:
+    """int64 [H * W]: for every pixel of the boolean [H, W] mask the smallest row-major index of its 4-connected component (a pixel outside
+    the mask: itself).  A union-find over the pixel indices in array form: every round hooks the larger of an edge's two roots to the
+    smaller (np.minimum.at), then flattens by pointer jumping; an edge whose ends share a root leaves the list.  Each round at least halves
+    the number of trees that still have a neighbour, so the number of rounds is logarithmic in the longest component."""
+    h, w = mask.shape
+    idx = np.arange(h * w, dtype=np.int64).reshape(h, w)
+    a = np.concatenate([idx[:, :-1][mask[:, :-1] & mask[:, 1:]], idx[:-1][mask[:-1] & mask[1:]]])
+    b = np.concatenate([idx[:, 1:][mask[:, :-1] & mask[:, 1:]], idx[1:][mask[:-1] & mask[1:]]])
+    p = idx.reshape(-1).copy()
+    while a.size:
+        pa, pb = p[a], p[b]
+        sel = pa != pb
+        a, b, pa, pb = a[sel], b[sel], pa[sel], pb[sel]
+        if not a.size:
+            break
+        np.minimum.at(p, np.maximum(pa, pb), np.minimum(pa, pb))
+        while True:
+            pp = p[p]
+            if np.array_equal(pp, p):
+                break
+            p = pp
+    return p
+
+
+def _largest_component(mask: np.ndarray) -> np.ndarray:
+    """The largest 4-connected component of a boolean [H, W] mask as a boolean array; among components of equal size the one that holds the
+    smallest row-major index; an empty mask gives an empty one."""
+    if not mask.any():
+        return np.zeros_like(mask)
+    root = _components_min_index(mask).reshape(mask.shape)
+    sizes = np.bincount(root[mask], minlength=mask.size)
+    return mask & (root == int(np.argmax(sizes)))  # argmax: the first, so the smallest root, among equal sizes
+
+
+def conn_levels(q: np.ndarray, g: np.ndarray) -> np.ndarray:
+    """uint8 [H, W], 0..10: level(x) = (the smallest k in 1..10 with x outside Omega_k) - 1, 10 if x is in all ten; Omega_k the largest
+    4-connected component of { min(q, g) >= T_k } (ties: the component with the smallest row-major index)."""
+    q, g = _check_q_g(q, g)
+    m = np.minimum(q, g)
+    level = np.full(q.shape, 10, dtype=np.uint8)
+    for k in range(10, 0, -1):
+        level[~_largest_component(m >= CONN_T[k - 1])] = k - 1
+    return level
+
+
+def _conn_terms(q: np.ndarray, g: np.ndarray, level: np.ndarray) -> np.ndarray:
+    """int64 [H, W]: |dg' - dq'| per pixel, d = 10 v - 255 level kept when >= 383 (the published 0.15 on this scale), else 0."""
+    base = 255 * level.astype(np.int64)
+    dg, dq = 10 * g.astype(np.int64) - base, 10 * q.astype(np.int64) - base
+    return np.abs(np.where(dg >= 383, dg, 0) - np.where(dq >= 383, dq, 0))
+
+
+def _region_of(region, shape) -> Optional[np.ndarray]:
+    if region is None:
+        return None
+    sel = np.asarray(region) != 0
+    if sel.shape != tuple(shape):
+        raise ValueError("region does not match the maps")
+    return sel
+
+
+def conn_error(q: np.ndarray, g: np.ndarray, region: Optional[np.ndarray] = None) -> Dict[str, object]:
+    """conn = conn_num / 2550000.0 (NaN for an empty region), conn_num = sum over the region of the per-pixel terms (int), n = |region|,
+    level_counts int64 [11] over the WHOLE image, counts int64 [13] = n, conn_num, level_counts (gp_eval_matting's counts_out)."""
+    q, g = _check_q_g(q, g)
+    sel = _region_of(region, q.shape)
+    level = conn_levels(q, g)
+    term = _conn_terms(q, g, level)
+    n = int(q.size if sel is None else sel.sum())
+    num = int(term.sum() if sel is None else term[sel].sum())
+    lc = np.bincount(level.reshape(-1), minlength=11).astype(np.int64)
+    return dict(conn=(num / 2550000.0 if n else float("nan")), conn_num=num, n=n, level_counts=lc,
+                counts=np.concatenate([np.array([n, num], dtype=np.int64), lc]))
+
+
+def _grad_amp(x: np.ndarray) -> np.ndarray:
+    """The gradient magnitude of one 8-bit map: mat2gray in integers, the two separable filters (rows first, taps in index order, replicate
+    border, plain float64 products and sums starting from 0.0), sqrt(gx * gx + gy * gy)."""
+    h, w = x.shape
+    lo, hi = int(x.min()), int(x.max())
+    xn = (x.astype(np.int64) - lo).astype(np.float64) / float(hi - lo) if hi > lo else np.zeros((h, w), dtype=np.float64)
+    px = xn[:, np.clip(np.arange(-4, w + 4), 0, w - 1)]
+    row_d, row_g = np.zeros((h, w), dtype=np.float64), np.zeros((h, w), dtype=np.float64)
+    for j in range(9):
+        row_d = row_d + GRAD_D[j] * px[:, j:j + w]
+        row_g = row_g + GRAD_G[j] * px[:, j:j + w]
+    rows = np.clip(np.arange(-4, h + 4), 0, h - 1)
+    pd, pg = row_d[rows], row_g[rows]
+    gx, gy = np.zeros((h, w), dtype=np.float64), np.zeros((h, w), dtype=np.float64)
+    for i in range(9):
+        gx = gx + GRAD_G[i] * pd[i:i + h]
+        gy = gy + GRAD_D[i] * pg[i:i + h]
+    return np.sqrt(gx * gx + gy * gy)
+
+
+def grad_error_map(q: np.ndarray, g: np.ndarray) -> np.ndarray:
+    """float64 [H, W]: err = (amp_q - amp_g)^2 per pixel (gp_eval_matting's grad_map_out, the same bits)."""
+    q, g = _check_q_g(q, g)
+    d = _grad_amp(q) - _grad_amp(g)
+    return d * d
+
+
+def grad_error(q: np.ndarray, g: np.ndarray, region: Optional[np.ndarray] = None) -> Dict[str, float]:
+    """grad = grad_sum / 1000.0, grad_sum = the sum of the error map over the region (NaN for an empty region), n = |region|."""
+    q, g = _check_q_g(q, g)
+    sel = _region_of(region, q.shape)
+    err = grad_error_map(q, g)
+    n = int(q.size if sel is None else sel.sum())
+    s = float(err.sum() if sel is None else err[sel].sum()) if n else float("nan")
+    return dict(grad=s / 1000.0, grad_sum=s, n=n)
+
+
+def matting_metrics(pred: np.ndarray, gt: np.ndarray, region: Optional[np.ndarray] = None) -> Dict[str, float]:
+    """One image: pred a float map in [0, 1] (quantised by `quantize_mask`) or uint8, gt uint8, both [H, W]; region optional (non-zero =
+    scored; the filters and the labelling always see the whole image).  MATTING_METRICS."""
+    q = quantize_mask(pred)
+    return dict(grad=grad_error(q, gt, region)["grad"], conn=conn_error(q, gt, region)["conn"])

@@ -530,6 +530,7 @@ def infer_and_evaluate_normals(pipe, base_dir: str, samples: Sequence[Sequence[s
 # ---- dis / matting: 8-bit masks and alpha maps ------------------------------------------------------------------------------------------------
 MASK_METRICS = list(em.MASK_METRICS)  # per-image values, in order; the dataset-level "max_f_dataset" comes on top
 STRUCTURE_METRICS = list(em.STRUCTURE_METRICS)  # with structure=True: appended to the per-image columns, the means and the files
+MATTING_METRICS = list(em.MATTING_METRICS)  # with matting=True: appended after them
 
 
 def read_gt_mask(path: str) -> np.ndarray:
@@ -599,16 +600,19 @@ def _write_mask_eval_files(output_dir: str, names: List[str], per_sample, result
 
 def evaluate_mask_predictions(prediction_dir: str, base_dir: str, samples: Sequence[Sequence[str]], name_mode: FileNameMode,
                               output_dir: Optional[str] = None, pred_suffix: str = ".npy", region_of: Optional[Callable] = None,
-                              read_gt: Optional[Callable[[str], np.ndarray]] = None, structure: bool = False) -> Dict[str, float]:
+                              read_gt: Optional[Callable[[str], np.ndarray]] = None, structure: bool = False,
+                              matting: bool = False) -> Dict[str, float]:
     """The file route for what `run_inference(mode="dis" | "matting")` writes (`.npy`) or for 8-bit `.png` maps (pred_suffix): per image
     eval_metrics.mask_metrics against the 8-bit ground truth of column 1 (read_gt_mask or `read_gt`), over `region_of(sample, gt)` (a bool
     array, e.g. a trimap's unknown region; None: every pixel).  Returns the means of the per-image MASK_METRICS and "max_f_dataset", the
     maximum F of the dataset-mean precision / recall curves.  Samples without ground truth ("None") or without a prediction file are
     skipped.  Optionally writes `eval_metrics-mask.txt` and `per_sample_metrics-mask.csv`.  structure: the dis structure scores
-    (eval_metrics.structure_metrics: STRUCTURE_METRICS, whole-image quantities, so not together with region_of) as five more columns."""
+    (eval_metrics.structure_metrics: STRUCTURE_METRICS, whole-image quantities, so not together with region_of) as five more columns.
+    matting: the gradient and connectivity errors (eval_metrics.matting_metrics: MATTING_METRICS, summed over the same region) as two more
+    columns, after the structure columns if both are asked for."""
     if structure and region_of is not None:
         raise ValueError("structure scores are whole-image quantities: structure=True does not go with region_of")
-    names = list(MASK_METRICS) + (list(STRUCTURE_METRICS) if structure else [])
+    names = list(MASK_METRICS) + (list(STRUCTURE_METRICS) if structure else []) + (list(MATTING_METRICS) if matting else [])
     sums = {k: 0.0 for k in names}
     per_sample, counts = [], []
     for s in samples:
@@ -622,12 +626,15 @@ def evaluate_mask_predictions(prediction_dir: str, base_dir: str, samples: Seque
         pred = _read_mask_prediction(pred_path)
         if tuple(pred.shape) != tuple(gt.shape):
             raise ValueError(f"{s[0]}: prediction {tuple(pred.shape)} and ground truth {tuple(gt.shape)} differ in size")
-        c = em.mask_counts(em.quantize_mask(pred), gt, _mask_region(region_of, s, gt))
+        region = _mask_region(region_of, s, gt)
+        c = em.mask_counts(em.quantize_mask(pred), gt, region)
         if c[0] == 0:
             raise ValueError(f"{s[0]}: no pixel to evaluate the mask on (n = 0)")
         m = em.mask_metrics_from_counts(c)
         if structure:
             m.update(em.structure_metrics(pred, gt))
+        if matting:
+            m.update(em.matting_metrics(pred, gt, region))
         for k in names:
             sums[k] += m[k]
         per_sample.append((pred_name, [m[k] for k in names]))
@@ -646,7 +653,8 @@ def infer_and_evaluate_masks(pipe, base_dir: str, samples: Sequence[Sequence[str
                              read_gt: Optional[Callable[[str], np.ndarray]] = None, region_of: Optional[Callable] = None, denoise_steps: int = 1,
                              ensemble_size: int = 1, processing_res: int = 0, match_input_res: bool = True, resample_method: str = "bilinear",
                              fix_timesteps=None, prompt: str = "", prefetch: int = 2, structure: bool = False,
-                             structure_evaluator: Optional[Callable] = None) -> Dict[str, float]:
+                             structure_evaluator: Optional[Callable] = None, matting: bool = False,
+                             matting_evaluator: Optional[Callable] = None) -> Dict[str, float]:
     """`infer_and_evaluate` for mode "dis" or "matting": batches go through `pipe.predict_batch_device(mode=mode)`, the float [B, 1, H, W] maps
     stay on the device, and `evaluator` -- `engine.eval_mask` unless given: (pred, gt, region) -> one dict per image with MASK_METRICS and
     "counts" -- quantises and scores them there against the 8-bit ground truth of column 1 (and `region_of(sample, gt)`, if given), decoded on
@@ -655,17 +663,22 @@ def infer_and_evaluate_masks(pipe, base_dir: str, samples: Sequence[Sequence[str
     rank are `infer_and_evaluate`'s, with one more float64 all_reduce for the precision / recall curves behind "max_f_dataset".
     save_predictions: the maps are also written as `run_inference` would, float32 [H, W] `.npy` under prediction_dir (default: output_dir).
     structure: the dis structure scores as five more per-image columns (STRUCTURE_METRICS), from a second device call on the same uploaded
-    batch -- `structure_evaluator`, `engine.eval_structure` unless given: (pred, gt) -> one dict per image; not together with region_of."""
+    batch -- `structure_evaluator`, `engine.eval_structure` unless given: (pred, gt) -> one dict per image; not together with region_of.
+    matting: the gradient and connectivity errors as two more per-image columns (MATTING_METRICS, after the structure columns), from a further
+    device call on the same uploaded batch and region -- `matting_evaluator`, `engine.eval_matting` unless given: (pred, gt, region) -> one
+    dict per image."""
     import torch
     if mode not in ("dis", "matting"):
         raise ValueError(f"mask evaluation is for mode 'dis' or 'matting', got {mode!r}")
     if structure and region_of is not None:
         raise ValueError("structure scores are whole-image quantities: structure=True does not go with region_of")
-    names = list(MASK_METRICS) + (list(STRUCTURE_METRICS) if structure else [])
+    names = list(MASK_METRICS) + (list(STRUCTURE_METRICS) if structure else []) + (list(MATTING_METRICS) if matting else [])
     if evaluator is None:
         from .engine import eval_mask as evaluator
     if structure and structure_evaluator is None:
         from .engine import eval_structure as structure_evaluator
+    if matting and matting_evaluator is None:
+        from .engine import eval_matting as matting_evaluator
     if prediction_dir is None:
         prediction_dir = output_dir
     if save_predictions and prediction_dir is None:
@@ -693,6 +706,10 @@ def infer_and_evaluate_masks(pipe, base_dir: str, samples: Sequence[Sequence[str
             more = structure_evaluator(pred[:, 0], gt_t)
             assert len(more) == len(group)
             metrics = [dict(m, **{k: s[k] for k in STRUCTURE_METRICS}) for m, s in zip(metrics, more)]
+        if matting:
+            more = matting_evaluator(pred[:, 0], gt_t, region_t)
+            assert len(more) == len(group)
+            metrics = [dict(m, **{k: s[k] for k in MATTING_METRICS}) for m, s in zip(metrics, more)]
         for ((idx, _), _), m in zip(group, metrics):
             counts.append((idx, np.asarray(m["counts"])))
         if save_predictions:

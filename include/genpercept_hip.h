@@ -314,6 +314,44 @@ gp_status gp_eval_structure(const void* pred, int pred_is_u8, const unsigned cha
                             unsigned long long* counts_out /* [B][537] or NULL */, unsigned long long* edt_out /* [B][H][W] keys or NULL */,
                             void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- matting gradient and connectivity errors on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation; csrc/eval_matting.hip) ----
+ * The other two columns of the matting table beside SAD and MSE: Grad and Conn (Rhemann et al. 2009, as used by Deep Image Matting).  The
+ * reference has no metric for matting (genpercept_trainer.py:1169 is a TODO), so the definitions are this project's; they follow the published
+ * Matlab and Python evaluation code wherever integers allow, and eval_metrics.conn_levels / conn_error / grad_error_map / grad_error are the
+ * same definitions on the host.  Deviation from the toolboxes: their Conn compares q / 255 >= k / 10 in floating point, which depends on how
+ * k / 10 was produced (byte 153 against 0.6); here the thresholds are integers.
+ * pred, pred_is_u8, gt, region as for gp_eval_mask: everything is computed on the 8-bit prediction q against the 8-bit alpha g.  The filters
+ * and the labelling run over the whole image; region (non-zero = scored, e.g. a trimap's unknown band; NULL = every pixel) restricts only the
+ * final sums.  n = |R|.
+ * Conn.  T_k = ceil(255 k / 10), k = 1..10: 26, 51, 77, 102, 128, 153, 179, 204, 230, 255.  m = min(q, g), I_k = { m >= T_k } (nested).
+ *   Omega_k = the largest 4-connected component of I_k; among components of equal size the one that holds the smallest row-major pixel index;
+ *   empty when I_k is.  level(x) = (the smallest k in 1..10 with x outside Omega_k) - 1, 10 if x is in all ten.
+ *   dg = 10 g - 255 level, dq = 10 q - 255 level; dg' = dg if dg >= 383 else 0, dq' likewise (the published >= 0.15 is >= 382.5 on this scale).
+ *   conn_num = sum_R |dg' - dq'| (unsigned 64-bit; exact, order-free);  conn = conn_num / 2550000.0 (in thousands), one float64 division.
+ * Grad.  Per map x (q, then g): xn = (x - min x) / double(max x - min x), min and max over the whole image; a constant map gives all zeros.
+ *   G[9], D[9]: the Gaussian with sigma = 1.4 and its derivative at the taps -4..4 (D[0] > 0, D[4] = 0), each divided by its own L2 norm, as
+ *   tables of hex-float literals (eval_matting.hip MT_G, MT_D == eval_metrics.GRAD_G, GRAD_D).
+ *   gx(y, x) = sum_i G[i] * (sum_j D[j] * xn(clamp(y + i - 4), clamp(x + j - 4))), gy with the tables exchanged: the inner (row) sum first,
+ *   every sum from 0.0 with the taps in index order 0..8, coordinates clamped to the image, float64, no FMA.
+ *   amp = sqrt(gx * gx + gy * gy);  err = (amp_q - amp_g) * (amp_q - amp_g);  grad_sum = sum_R err: float64 sums per 32 x 8 tile, tiles added
+ *   in an order that depends on H and W alone (the rule of the weighted F);  grad = grad_sum / 1000.0.
+ * out: double [B][4] = n, grad, conn, grad_sum; n = 0 gives n = 0 and NaN for the other three.
+ * counts_out: optional unsigned 64-bit [B][13] = n, conn_num, then the counts of the levels 0..10 over the WHOLE image (not the region).
+ * level_out: optional uint8 [B][H][W], the levels.  grad_map_out: optional double [B][H][W], err (every pixel, whatever the region).
+ * The labelling is one union-find over the row-major pixel indices (the root of a component is its smallest index), grown from k = 10 down
+ * to 1.  Unlike the other evaluation entries this one USES global atomics, integers only: atomicMin on the 32-bit labels, atomicAdd on the
+ * component sizes and the final counts, a 64-bit atomicMax for (size, ~root).  Integer min, add and max are order-free, so an image's values
+ * are still bitwise the same from call to call and for every batch it is part of; no float is ever added atomically.  workspace: DEVICE
+ * scratch of at least the workspace entry's byte count (8-byte aligned; about 47 bytes per pixel), free again once the stream has passed the
+ * call.  26 kernel launches on `stream` for every B, nothing read back.
+ * GP_ERR_INVALID before any HIP call: null pred / gt / out / workspace, B, H or W < 1, B > 65535, H * W > 2^31 - 1, pred_is_u8 outside 0..1,
+ * a float pred not 4-byte aligned, out / counts_out / grad_map_out / workspace not 8-byte aligned, workspace_bytes too small. */
+long long gp_eval_matting_workspace(int B, int H, int W);     /* bytes; 0 for B, H or W < 1; proportional to B; multiple of 8 */
+gp_status gp_eval_matting(const void* pred, int pred_is_u8, const unsigned char* gt, const unsigned char* region, int B, int H, int W,
+                          double* out /* [B][4] */, unsigned long long* counts_out /* [B][13] or NULL */,
+                          unsigned char* level_out /* [B][H][W] or NULL */, double* grad_map_out /* [B][H][W] err or NULL */, void* workspace,
+                          long long workspace_bytes, void* stream);
+
 /* ---- test-time ensembling on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation, no atomics; csrc/ensemble.hip) ----
  * The tensor half of ensemble_depth (genpercept/util/ensemble.py:43-205, called at genpercept_pipeline.py:289-298) for the E members of each of
  * B images; the optimiser that finds the per-member (scale, shift) runs on the host between the two entries, on what the gather produced.

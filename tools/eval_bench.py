@@ -1,4 +1,4 @@
-"""Time the device depth (or, with --normals, surface-normal; with --masks, dis / matting; with --structure, dis structure-score) evaluation against the host evaluation, and the batched device loop on the tiny pipeline.
+"""Time the device depth (or, with --normals, surface-normal; with --masks, dis / matting; with --structure, dis structure-score; with --matting, matting Grad / Conn) evaluation against the host evaluation, and the batched device loop on the tiny pipeline.
 
   python tools/eval_bench.py --out profiles/<name>.json
 
@@ -29,6 +29,14 @@
    prediction flipped) and on a single far object (a small square in one corner: the row search of the distance transform spans the image),
    against `eval_metrics.structure_metrics` on the same arrays on the host (wall clock, one run: it takes seconds).  The exact scores are
    compared on the spot (bit-equal), wf to 1e-8.  `--no-host` skips the host route (for a kernel trace of the device calls alone).
+
+  python tools/eval_bench.py --matting --out profiles/<name>.json
+
+6. `--matting` (instead of 1 and 2): the `gp_eval_matting` entry behind `engine.eval_matting` (gradient and connectivity error: 26 launches,
+   the ten-stage union-find labelling among them) at 4 x 480 x 640 and 1 x 2048 x 2048 on an alpha-like input (a disc with a soft edge and
+   thin strands, the prediction = the alpha plus noise in the soft band and a few detached blobs), against `eval_metrics.matting_metrics` on
+   the same arrays on the host (wall clock, one run).  conn is compared on the spot (bit-equal), grad to 1e-9.  `--no-host` skips the host
+   route (for a kernel trace of the device calls alone).
 Needs a GPU; there is no CPU fall-back."""
 import argparse
 import json
@@ -277,6 +285,78 @@ def bench_eval_structure(b, h, w, kind, iters, host):
     return res
 
 
+def matting_case(b, h, w, seed):
+    """(pred float32 in [0, 1], alpha uint8): a disc whose edge fades over 6 % of the image, crossed by thin strands; the prediction adds noise
+    where the alpha is soft, loses a third of the strands and gains a few detached blobs."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.meshgrid(np.linspace(-1, 1, h, dtype=np.float32), np.linspace(-1, 1, w, dtype=np.float32), indexing="ij")
+    preds, gts = [], []
+    for i in range(b):
+        r = np.sqrt((xx - 0.1 * i) ** 2 + yy ** 2)
+        alpha = np.clip((0.6 - r) / 0.12 + 0.5, 0, 1)
+        strands = (np.abs(np.sin(40 * np.arctan2(yy, xx - 0.1 * i))) > 0.97) & (r > 0.55) & (r < 0.8)
+        alpha = np.maximum(alpha, strands * 0.7).astype(np.float32)
+        soft = (alpha > 0) & (alpha < 1)
+        pred = alpha + soft * 0.15 * rng.standard_normal((h, w), dtype=np.float32)
+        pred[strands & (rng.random((h, w), dtype=np.float32) < 0.33)] = 0
+        pred[(rng.random((h, w), dtype=np.float32) < 2e-4) & (r > 0.85)] = 0.9
+        preds.append(np.clip(pred, 0, 1))
+        gts.append((alpha * 255).astype(np.uint8))
+    return np.stack(preds).astype(np.float32), np.stack(gts)
+
+
+def time_eval_matting(tp, tg, iters):
+    """ms per gp_eval_matting call: the C entry itself on preallocated buffers (the 26 launches, none of the binding's bookkeeping)."""
+    from genpercept_amd import engine as ge
+    lib = ge.load_library()
+    b, h, w = (int(v) for v in tp.shape)
+    nbytes = int(lib.gp_eval_matting_workspace(b, h, w))
+    ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=tp.device)
+    out = torch.empty((b, 4), dtype=torch.float64, device=tp.device)
+    stream = int(torch.cuda.current_stream(tp.device).cuda_stream)
+
+    def call():
+        st = lib.gp_eval_matting(tp.data_ptr(), int(tp.dtype == torch.uint8), tg.data_ptr(), None, b, h, w, out.data_ptr(), None, None, None,
+                                 ws.data_ptr(), nbytes, stream)
+        assert st == ge.GP_OK, st
+
+    for _ in range(3):
+        call()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        call()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def bench_eval_matting(b, h, w, iters, host):
+    from genpercept_amd import engine as ge
+    from genpercept_amd import eval_metrics as em
+    d = torch.device("cuda", 0)
+    pred, gt = matting_case(b, h, w, 5)
+    tp, tg = (torch.from_numpy(x).to(d) for x in (pred, gt))
+    dev_ms = time_eval_matting(tp, tg, iters)
+    t0 = time.perf_counter()
+    metrics = ge.eval_matting(tp, tg)  # with the copy of the 4 values per image and the host synchronise
+    call_ms = (time.perf_counter() - t0) * 1e3
+    res = dict(shape=[b, h, w], input="alpha", device_ms_per_call=dev_ms, device_iters=iters, launches_per_call=26, device_call_with_sync_ms=call_ms,
+               workspace_bytes=int(ge.load_library().gp_eval_matting_workspace(b, h, w)), scores_image_0={k: metrics[0][k] for k in em.MATTING_METRICS})
+    if host:
+        t0 = time.perf_counter()
+        ref = [em.matting_metrics(pred[i], gt[i]) for i in range(b)]
+        host_ms = (time.perf_counter() - t0) * 1e3
+        worst = 0.0
+        for i in range(b):
+            assert metrics[i]["conn"] == ref[i]["conn"], (i, metrics[i], ref[i])
+            worst = max(worst, abs(metrics[i]["grad"] - ref[i]["grad"]) / ref[i]["grad"])
+        assert worst <= 1e-9, worst
+        res.update(host_matting_metrics_ms=host_ms, host_runs=1, host_over_device=host_ms / dev_ms, conn_equals_host=True, grad_worst_rel_device_vs_host=worst)
+    return res
+
+
 def bench_loop(n_images, batch_sizes, repeats):
     from PIL import Image
     from genpercept_amd import GenPerceptPipeline
@@ -330,11 +410,15 @@ def main():
     ap.add_argument("--normals", action="store_true", help="time engine.eval_normal against normal_angular_error instead")
     ap.add_argument("--masks", action="store_true", help="time gp_eval_mask against mask_metrics instead")
     ap.add_argument("--structure", action="store_true", help="time gp_eval_structure against structure_metrics instead")
-    ap.add_argument("--no-host", action="store_true", help="with --structure: the device calls alone")
+    ap.add_argument("--matting", action="store_true", help="time gp_eval_matting against matting_metrics instead")
+    ap.add_argument("--no-host", action="store_true", help="with --structure or --matting: the device calls alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU")
-    if a.structure:
+    if a.matting:
+        res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box",
+                   eval_matting=[bench_eval_matting(b, h, w, a.iters, not a.no_host) for (b, h, w) in ((4, 480, 640), (1, 2048, 2048))])
+    elif a.structure:
         res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box",
                    eval_structure=[bench_eval_structure(b, h, w, kind, a.iters, not a.no_host) for (b, h, w) in ((4, 1024, 1024), (1, 2048, 2048))
                                    for kind in ("mask", "far")])
@@ -348,7 +432,7 @@ def main():
                    eval_normal=[bench_eval_normal(4, 480, 640, a.iters, 3), bench_eval_normal(1, 4032, 6048, a.iters, 1)])
     else:
         res = dict(device=torch.cuda.get_device_name(0), eval_depth=[bench_eval(1, 4032, 6048, a.iters, 1), bench_eval(4, 480, 640, a.iters, 3)])
-    if not a.skip_loop and not a.normals and not a.masks and not a.structure:
+    if not a.skip_loop and not a.normals and not a.masks and not a.structure and not a.matting:
         res["infer_and_evaluate"] = bench_loop(16, (1, 4), 3)
     text = json.dumps(res, indent=1)
     print(text)
