@@ -158,6 +158,9 @@ SYMBOLS = {
     "gp_eval_structure": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _ll, _vp]),
     "gp_eval_matting_workspace": (_ll, [_i, _i, _i]),
     "gp_eval_matting": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _ll, _vp]),
+    "gp_seg_decode": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "gp_eval_seg_workspace": (_ll, [_i, _i, _i, _i]),
+    "gp_eval_seg": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _ll, _vp]),
     "gp_ensemble_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gp_ensemble_workspace": (_ll, [_i, _i, _i, _i]),
     "gp_ensemble_reduce": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
@@ -1182,6 +1185,129 @@ def eval_matting(pred: torch.Tensor, gt: torch.Tensor, region: Optional[torch.Te
         if row[0] == 0:
             raise ValueError(f"image {i}: no pixel to evaluate the alpha map on (n = 0)")
     return [{k: (int(row[j]) if k == "n" else float(row[j])) for j, k in enumerate(MATTING_OUT_NAMES)} for row in raw]
+
+
+SEG_METRICS = ["pixel_acc", "mean_acc", "miou", "fwiou", "colour_rmse"]  # gp_eval_seg's out[2 .. 6]; eval_metrics.SEG_METRICS
+SEG_OUT = 8        # n, n_void, the five metrics, n_classes; iou[K] follows
+SEG_NSUM = 3       # n, n_void, sum_d in front of the K x K matrix of counts_out
+SEG_MAX_K = 192
+
+
+def _seg_pred(pred: torch.Tensor):
+    """pred [B, 3, H, W] or [3, H, W], float or uint8 -> (contiguous fp32 / uint8 [B, 3, H, W], is_u8)"""
+    if not torch.is_tensor(pred) or pred.dim() not in (3, 4) or pred.shape[-3] != 3:
+        raise ValueError(f"pred: expected [B, 3, H, W] or [3, H, W], got {tuple(pred.shape) if torch.is_tensor(pred) else type(pred)}")
+    is_u8 = pred.dtype == torch.uint8
+    if not is_u8 and not pred.dtype.is_floating_point:
+        raise ValueError(f"pred: a float colour map in [0, 1] or its uint8 quantisation, got {pred.dtype}")
+    if pred.dim() == 3:
+        pred = pred[None]
+    if min(pred.shape) < 1:
+        raise ValueError(f"pred: empty map {tuple(pred.shape)}")
+    return (pred if is_u8 else pred.to(torch.float32)).contiguous(), is_u8
+
+
+def _seg_palette(palette, device) -> torch.Tensor:
+    pal = palette if torch.is_tensor(palette) else torch.from_numpy(np.array(palette))  # (a copy: the array may be read-only)
+    if pal.dtype != torch.uint8 or pal.dim() != 2 or pal.shape[1] != 3 or not 1 <= pal.shape[0] <= SEG_MAX_K:
+        raise ValueError(f"palette: uint8 [K, 3] with 1 <= K <= {SEG_MAX_K}, got {pal.dtype} {tuple(pal.shape)}")
+    return pal.to(device).contiguous()
+
+
+def seg_decode(pred: torch.Tensor, palette, want_dist: bool = False):
+    """gp_seg_decode on a device tensor: the classes of a seg colour map, uint8 [B, H, W] ON THE DEVICE -- per pixel the smallest index of the
+    nearest palette colour (squared distance in integers on the 8-bit colour; eval_metrics.palette_labels, the same bits); with want_dist also
+    the int32 [B, H, W] minimum distances.  pred: [B, 3, H, W] or [3, H, W], a float map in [0, 1] (quantised to 8 bits per channel by the
+    kernel as run.py:449-455 does) or uint8 (the bytes `postprocess(..., q_bits=8)` returns); palette: uint8 [K, 3], tensor or array, K <= 192.
+    Enqueued on the current stream, no synchronisation."""
+    pred, is_u8 = _seg_pred(pred)
+    pal = _seg_palette(palette, pred.device)
+    assert pred.is_cuda
+    b, _, h, w = (int(v) for v in pred.shape)
+    labels = torch.empty((b, h, w), dtype=torch.uint8, device=pred.device)
+    dist = torch.empty((b, h, w), dtype=torch.int32, device=pred.device) if want_dist else None
+    st = load_library().gp_seg_decode(pred.data_ptr(), int(is_u8), pal.data_ptr(), int(pal.shape[0]), b, h, w, labels.data_ptr(), _ptr(dist),
+                                      _stream_ptr(pred.device))
+    if st != GP_OK:
+        raise RuntimeError(f"gp_seg_decode failed ({st})")
+    return (labels, dist) if want_dist else labels
+
+
+def _eval_seg_launch(pred, gt, palette, region, gt_tol, want_counts: bool, want_labels: bool):
+    """The checks and the call of `eval_seg_raw`.  Returns (buf, out, counts, labels): out float64 [B, 8 + K] and counts int64 [B, 3 + K * K]
+    (or None) are views of the one int64 device buffer `buf`, so that one copy brings both to the host."""
+    pred_dim = pred.dim() if torch.is_tensor(pred) else 0
+    pred, is_u8 = _seg_pred(pred)
+    b, _, h, w = (int(v) for v in pred.shape)
+    if not torch.is_tensor(gt) or gt.dtype != torch.uint8:
+        raise ValueError(f"gt: a uint8 colour image [B, H, W, 3] or label map [B, H, W], got {gt.dtype if torch.is_tensor(gt) else type(gt)}")
+    batch = (b,) if pred_dim == 4 else ()
+    if gt.dim() == pred_dim and gt.shape[-1] == 3:
+        labels_gt, want = False, batch + (h, w, 3)
+    elif gt.dim() == pred_dim - 1:
+        labels_gt, want = True, batch + (h, w)
+    else:
+        raise ValueError(f"gt {tuple(gt.shape)}: neither a colour image (last dimension 3, {pred_dim} dimensions) nor a label map ({pred_dim - 1})")
+    if tuple(gt.shape) != want:
+        raise ValueError(f"gt {tuple(gt.shape)} does not match pred {tuple(pred.shape)}: expected {want}")
+    gt = gt.reshape((b, h, w) if labels_gt else (b, h, w, 3)).contiguous()
+    pal = _seg_palette(palette, pred.device)
+    k = int(pal.shape[0])
+    gt_tol = int(gt_tol)
+    if gt_tol < 0:
+        raise ValueError(f"gt_tol: a squared distance >= 0, got {gt_tol}")
+    if region is not None:
+        region = _eval_maps(region, "region")
+        if tuple(region.shape) != (b, h, w):
+            raise ValueError(f"region {tuple(region.shape)} does not match the maps {(b, h, w)}")
+        region = (region.contiguous().view(torch.uint8) if region.dtype in (torch.bool, torch.uint8) else (region != 0).view(torch.uint8)).contiguous()
+    assert pred.is_cuda and gt.is_cuda and (region is None or region.is_cuda)
+    lib = load_library()
+    n_out, n_cnt = SEG_OUT + k, SEG_NSUM + k * k
+    buf = torch.empty((b * (n_out + (n_cnt if want_counts else 0)),), dtype=torch.int64, device=pred.device)
+    out = buf[:b * n_out].view(torch.float64).view(b, n_out)
+    counts = buf[b * n_out:].view(b, n_cnt) if want_counts else None
+    labels = torch.empty((b, h, w), dtype=torch.uint8, device=pred.device) if want_labels else None
+    nbytes = int(lib.gp_eval_seg_workspace(b, h, w, k))
+    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=pred.device)
+    st = lib.gp_eval_seg(pred.data_ptr(), int(is_u8), gt.data_ptr(), int(labels_gt), gt_tol, _ptr(region), pal.data_ptr(), k, b, h, w, out.data_ptr(),
+                         _ptr(counts), _ptr(labels), ws.data_ptr(), nbytes, _stream_ptr(pred.device))
+    if st != GP_OK:
+        raise RuntimeError(f"gp_eval_seg failed ({st})")
+    return buf, out, counts, labels
+
+
+def eval_seg_raw(pred: torch.Tensor, gt: torch.Tensor, palette, region: Optional[torch.Tensor] = None, gt_tol: int = 0, want_counts: bool = False,
+                 want_labels: bool = False):
+    """gp_eval_seg on device tensors: float64 [B, 8 + K] ON THE DEVICE = n, n_void, then SEG_METRICS, n_classes and the K per-class IoUs (NaN
+    after n_void for an image without a scored pixel; definitions in include/genpercept_hip.h); with want_counts also the int64
+    [B, 3 + K * K] counts n, n_void, sum_d, conf[g][c] (eval_metrics.seg_counts), with want_labels the uint8 [B, H, W] classes of the prediction
+    (`seg_decode`), in that order.  pred, palette as for `seg_decode`.  gt: uint8, the colour image [B, H, W, 3] (last dimension 3, as many
+    dimensions as pred: decoded by the same rule, a pixel farther than the squared distance gt_tol from every palette colour is void) or the
+    label map [B, H, W] (one dimension fewer: values >= K are void).  region: bool or integer [B, H, W], non-zero = scored, None = every pixel.
+    Enqueued on the current stream, no synchronisation."""
+    _, out, counts, labels = _eval_seg_launch(pred, gt, palette, region, gt_tol, want_counts, want_labels)
+    res = (out,) + ((counts,) if want_counts else ()) + ((labels,) if want_labels else ())
+    return res if len(res) > 1 else out
+
+
+def eval_seg(pred: torch.Tensor, gt: torch.Tensor, palette, region: Optional[torch.Tensor] = None, gt_tol: int = 0):
+    """eval_metrics.seg_metrics for a batch of maps that are on the device (arguments as `eval_seg_raw`).  Returns one dict per image:
+    SEG_METRICS, "n", "n_void", "n_classes", "iou" (float64 numpy [K]) and "conf" (int64 numpy [K, K], row = ground truth).  Raises ValueError
+    naming the image when it has no scored pixel.  One device -> host copy of B x (8 + K + 3 + K * K) words."""
+    buf, out, counts, _ = _eval_seg_launch(pred, gt, palette, region, gt_tol, True, False)
+    b, n_out, n_cnt = out.shape[0], out.shape[1], counts.shape[1]
+    k = n_out - SEG_OUT
+    host = buf.cpu().numpy()
+    raw, cnt = host[:b * n_out].view("float64").reshape(b, n_out), host[b * n_out:].reshape(b, n_cnt)
+    res = []
+    for i, row in enumerate(raw):
+        if row[0] == 0:
+            raise ValueError(f"image {i}: no pixel to evaluate the segmentation on (n = 0)")
+        d = {name: float(row[2 + j]) for j, name in enumerate(SEG_METRICS)}
+        d.update(n=int(row[0]), n_void=int(row[1]), n_classes=int(row[7]), iou=row[SEG_OUT:].copy(), conf=cnt[i, SEG_NSUM:].reshape(k, k).copy())
+        res.append(d)
+    return res
 
 
 ENSEMBLE_REDUCTION = {"median": 0, "mean": 1}

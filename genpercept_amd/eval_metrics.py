@@ -611,3 +611,131 @@ def matting_metrics(pred: np.ndarray, gt: np.ndarray, region: Optional[np.ndarra
     scored; the filters and the labelling always see the whole image).  MATTING_METRICS."""
     q = quantize_mask(pred)
     return dict(grad=grad_error(q, gt, region)["grad"], conn=conn_error(q, gt, region)["conn"])
+
+
+# ---- seg: palette decode and confusion-matrix scores -----------------------------------------------------------------------------------------
+# Mode seg is colour regression against an RGB label image (src/dataset/base_dataset.py:333-346,366); the reference has neither a palette nor a
+# decode nor a metric for it.  The definitions below are this project's, stated once in include/genpercept_hip.h (gp_seg_decode, gp_eval_seg):
+# the user supplies the palette, everything is computed on the 8-BIT prediction (run.py:449-455, per channel), the decode and the counts are
+# integers, and each value is one fixed sequence of float64 operations on the counts.  The device entry runs the same sequence and is bit-equal.
+SEG_METRICS = ["pixel_acc", "mean_acc", "miou", "fwiou", "colour_rmse"]
+SEG_MAX_K = 192
+SEG_VOID = 255  # seg_gt_labels' label of a void pixel (any value >= K is void)
+
+
+def _check_palette(palette) -> np.ndarray:
+    pal = np.asarray(palette)
+    if pal.dtype != np.uint8 or pal.ndim != 2 or pal.shape[1] != 3 or not 1 <= pal.shape[0] <= SEG_MAX_K:
+        raise ValueError(f"palette: uint8 [K, 3] with 1 <= K <= {SEG_MAX_K}, got {pal.dtype} {pal.shape}")
+    return pal
+
+
+def quantize_seg(pred: np.ndarray) -> np.ndarray:
+    """The 8-bit colour image uint8 [H, W, 3] of a seg prediction: `quantize_mask` per channel of a float map stored [H, W, 3] (what
+    `run_inference(mode="seg")` writes) or [3, H, W] (a slice of `predict_batch_device`); uint8 input is only brought to [H, W, 3].  An
+    [3, H, 3] array is read as [H, W, 3] with H = 3: the file's own layout wins."""
+    pred = np.asarray(pred)
+    if pred.ndim != 3 or 3 not in (pred.shape[0], pred.shape[-1]):
+        raise ValueError(f"expected [H, W, 3] or [3, H, W], got {pred.shape}")
+    if pred.shape[-1] != 3:
+        pred = np.moveaxis(pred, 0, -1)
+    return np.ascontiguousarray(quantize_mask(pred))
+
+
+def palette_labels(rgb_u8: np.ndarray, palette) -> Tuple[np.ndarray, np.ndarray]:
+    """(labels uint8 [...], d int32 [...]) of a uint8 colour array [..., 3]: d_k = (r - pr_k)^2 + (g - pg_k)^2 + (b - pb_k)^2 in integers, the
+    label is the smallest k attaining the minimum, d that minimum.  Pixels go in chunks of 65536, so that K = 192 on a megapixel stays in memory."""
+    pal = _check_palette(palette).astype(np.int32)
+    rgb = np.asarray(rgb_u8)
+    if rgb.dtype != np.uint8 or rgb.ndim < 1 or rgb.shape[-1] != 3:
+        raise ValueError(f"expected a uint8 colour array [..., 3], got {rgb.dtype} {rgb.shape}")
+    flat = rgb.reshape(-1, 3)
+    labels, dist = np.empty(flat.shape[0], dtype=np.uint8), np.empty(flat.shape[0], dtype=np.int32)
+    for lo in range(0, flat.shape[0], 65536):
+        px = flat[lo:lo + 65536].astype(np.int32)
+        d = np.zeros((px.shape[0], pal.shape[0]), dtype=np.int32)
+        for c in range(3):
+            diff = px[:, c:c + 1] - pal[None, :, c]
+            d += diff * diff
+        k = d.argmin(axis=1)  # the first index of the minimum
+        labels[lo:lo + 65536] = k
+        dist[lo:lo + 65536] = d[np.arange(px.shape[0]), k]
+    return labels.reshape(rgb.shape[:-1]), dist.reshape(rgb.shape[:-1])
+
+
+def seg_gt_labels(gt: np.ndarray, palette, gt_tol: int = 0) -> np.ndarray:
+    """The ground-truth label map uint8 [H, W], void = 255.  gt: a uint8 colour image [H, W, 3] (decoded by `palette_labels`; a pixel whose
+    minimum squared distance exceeds gt_tol is void) or a uint8 label map [H, W] (values >= K are void; gt_tol is ignored)."""
+    pal = _check_palette(palette)
+    gt = np.asarray(gt)
+    if int(gt_tol) < 0:
+        raise ValueError(f"gt_tol: a squared distance >= 0, got {gt_tol}")
+    if gt.dtype != np.uint8 or gt.ndim not in (2, 3) or (gt.ndim == 3 and gt.shape[-1] != 3):
+        raise ValueError(f"gt: a uint8 colour image [H, W, 3] or label map [H, W], got {gt.dtype} {gt.shape}")
+    if gt.ndim == 2:
+        return np.where(gt >= pal.shape[0], np.uint8(SEG_VOID), gt).astype(np.uint8)
+    labels, d = palette_labels(gt, pal)
+    return np.where(d > int(gt_tol), np.uint8(SEG_VOID), labels).astype(np.uint8)
+
+
+def seg_counts(q: np.ndarray, gt_labels: np.ndarray, palette, region: Optional[np.ndarray] = None) -> np.ndarray:
+    """The integer counts of one image, int64 [3 + K * K] = n (scored: in the region and not void), n_void (in the region but void), sum_d (the
+    prediction's minimum distances summed over the scored pixels), conf[g][c] row-major (row = ground-truth class, column = predicted class).
+    q: the uint8 colour image [H, W, 3] of the prediction (`quantize_seg`); gt_labels: uint8 [H, W], values >= K void (`seg_gt_labels`)."""
+    pal = _check_palette(palette)
+    K = pal.shape[0]
+    q, g = np.asarray(q), np.asarray(gt_labels)
+    if q.dtype != np.uint8 or g.dtype != np.uint8 or q.ndim != 3 or q.shape[-1] != 3 or q.shape[:2] != g.shape:
+        raise ValueError(f"q must be uint8 [H, W, 3] and gt_labels uint8 [H, W], got {q.dtype} {q.shape} and {g.dtype} {g.shape}")
+    c, d = palette_labels(q, pal)
+    sel = np.ones(g.shape, dtype=bool) if region is None else np.asarray(region) != 0
+    if sel.shape != g.shape:
+        raise ValueError("region does not match the maps")
+    void = g >= K
+    scored = sel & ~void
+    out = np.empty(3 + K * K, dtype=np.int64)
+    out[0], out[1], out[2] = scored.sum(), (sel & void).sum(), d[scored].astype(np.int64).sum()
+    out[3:] = np.bincount(g[scored].astype(np.int64) * K + c[scored].astype(np.int64), minlength=K * K)
+    return out
+
+
+def seg_metrics_from_counts(counts, K: int) -> dict:
+    """The values of gp_eval_seg's `out` from the counts: n, n_void (ints), SEG_METRICS, n_classes, iou (a list of K floats, NaN where the
+    class is in neither map).  Plain float64 + * / sqrt in the order the header prescribes, classes in increasing index; n = 0: NaN for
+    everything but the two counts."""
+    c = [int(v) for v in np.asarray(counts).reshape(-1)]
+    if len(c) != 3 + K * K:
+        raise ValueError(f"expected {3 + K * K} counts for K = {K}, got {len(c)}")
+    n, n_void, sum_d = c[:3]
+    nan = float("nan")
+    if n == 0:
+        return dict(n=0, n_void=n_void, pixel_acc=nan, mean_acc=nan, miou=nan, fwiou=nan, colour_rmse=nan, n_classes=nan, iou=[nan] * K)
+    conf = c[3:]
+    sum_tp = n_rows = n_classes = 0
+    acc = iou_sum = fw = 0.0
+    iou = [nan] * K
+    for i in range(K):
+        row, col, tp = sum(conf[i * K:(i + 1) * K]), sum(conf[i::K]), conf[i * K + i]
+        union = row + col - tp
+        sum_tp += tp
+        if union > 0:
+            iou[i] = float(tp) / float(union)
+        if row > 0:
+            acc = acc + float(tp) / float(row)
+            fw = fw + float(row) * iou[i]
+            n_rows += 1
+        if union > 0:
+            iou_sum = iou_sum + iou[i]
+            n_classes += 1
+    return dict(n=n, n_void=n_void, pixel_acc=float(sum_tp) / float(n), mean_acc=acc / float(n_rows), miou=iou_sum / float(n_classes),
+                fwiou=fw / float(n), colour_rmse=math.sqrt(float(sum_d) / (3.0 * float(n))) / 255.0, n_classes=n_classes, iou=iou)
+
+
+def seg_metrics(pred: np.ndarray, gt: np.ndarray, palette, region: Optional[np.ndarray] = None, gt_tol: int = 0) -> dict:
+    """One image: pred a float colour map in [0, 1], [H, W, 3] or [3, H, W] (quantised by `quantize_seg`), or uint8; gt a uint8 colour image
+    [H, W, 3] or label map [H, W]; palette uint8 [K, 3]; region optional (non-zero = scored).  `seg_metrics_from_counts` plus "conf" (int64
+    [K, K])."""
+    pal = _check_palette(palette)
+    K = pal.shape[0]
+    c = seg_counts(quantize_seg(pred), seg_gt_labels(gt, pal, gt_tol), pal, region)
+    return dict(seg_metrics_from_counts(c, K), conf=c[3:].reshape(K, K).copy())

@@ -726,3 +726,211 @@ def infer_and_evaluate_masks(pipe, base_dir: str, samples: Sequence[Sequence[str
     if output_dir is not None and writer:
         _write_mask_eval_files(output_dir, names, [(_mask_pred_name(smp[0], name_mode), vals) for _, smp, vals in rows], result, prediction_dir)
     return result
+
+
+# ---- seg: colour maps against a user-supplied palette -----------------------------------------------------------------------------------------
+SEG_METRICS = list(em.SEG_METRICS)  # per-image values, in order; "miou_dataset", "pixel_acc_dataset" and "iou_dataset" come on top
+
+
+def read_palette(path: str) -> Tuple[np.ndarray, List[str]]:
+    """(palette uint8 [K, 3], names) from a text file -- one `r g b [name]` per line, `#` starts a comment, a class without a name is called by
+    its index -- or from a `.npy` of shape [K, 3] (integers in 0..255; names = the indices)."""
+    if os.path.splitext(path)[1].lower() == ".npy":
+        a = np.load(path)
+        if a.ndim != 2 or a.shape[1] != 3 or not np.issubdtype(a.dtype, np.integer) or a.min() < 0 or a.max() > 255:
+            raise ValueError(f"{path}: expected integers in 0..255 of shape [K, 3], got {a.dtype} {a.shape}")
+        rows, names = [tuple(int(v) for v in r) for r in a], [str(k) for k in range(a.shape[0])]
+    else:
+        rows, names = [], []
+        with open(path, "r") as f:
+            for no, line in enumerate(f, 1):
+                parts = line.split("#", 1)[0].split()
+                if not parts:
+                    continue
+                try:
+                    rgb = tuple(int(v) for v in parts[:3])
+                except ValueError:
+                    rgb = ()
+                if len(rgb) != 3 or min(rgb) < 0 or max(rgb) > 255:
+                    raise ValueError(f"{path}:{no}: expected `r g b [name]` with 0 <= r, g, b <= 255, got {line.strip()!r}")
+                rows.append(rgb)
+                names.append(" ".join(parts[3:]) or str(len(names)))
+    if not 1 <= len(rows) <= em.SEG_MAX_K:
+        raise ValueError(f"{path}: a palette has 1 to {em.SEG_MAX_K} colours, got {len(rows)}")
+    return np.array(rows, dtype=np.uint8).reshape(-1, 3), names
+
+
+def read_gt_seg(path: str) -> np.ndarray:
+    """Seg ground truth as the reference's column 6 stores it (src/dataset/base_dataset.py:333-346,366): an RGB or palettised image gives the
+    colour form uint8 [H, W, 3] (an alpha channel is dropped), a single-channel 8-bit image the label map uint8 [H, W].  Other formats: pass
+    a `read_gt` callable."""
+    img = Image.open(path)
+    if img.mode in ("P", "RGB", "RGBA"):
+        return np.ascontiguousarray(np.asarray(img.convert("RGB")))
+    if img.mode == "L":
+        return np.ascontiguousarray(np.asarray(img))
+    raise ValueError(f"{path}: expected an RGB, palettised or 8-bit single-channel image, got mode {img.mode}")
+
+
+def _read_seg_prediction(path: str) -> np.ndarray:
+    """What `run_inference(mode="seg")` writes (`.npy`, float [H, W, 3] in [0, 1]) or the 8-bit RGB `.png` of the same map."""
+    if os.path.splitext(path)[1].lower() == ".npy":
+        p = np.load(path)
+        if p.ndim != 3 or p.shape[-1] != 3:
+            raise ValueError(f"{path}: expected a colour map [H, W, 3], got {p.shape}")
+        return p
+    a = np.asarray(Image.open(path))
+    if a.ndim != 3 or a.shape[2] not in (3, 4) or a.dtype != np.uint8:
+        raise ValueError(f"{path}: expected an 8-bit RGB image, got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a[:, :, :3])
+
+
+def _palette_and_names(palette) -> Tuple[np.ndarray, List[str]]:
+    """palette: uint8 [K, 3], or the (palette, names) pair `read_palette` returns"""
+    names = None
+    if isinstance(palette, (tuple, list)) and len(palette) == 2 and isinstance(palette[1], (tuple, list)) and all(isinstance(n, str) for n in palette[1]):
+        palette, names = palette
+    pal = em._check_palette(np.asarray(palette))
+    names = [str(k) for k in range(pal.shape[0])] if names is None else list(names)
+    if len(names) != pal.shape[0]:
+        raise ValueError(f"{len(names)} names for {pal.shape[0]} palette colours")
+    return np.ascontiguousarray(pal), names
+
+
+def _seg_path(s: Sequence[str], gt_column: int) -> Optional[str]:
+    return s[gt_column] if len(s) > gt_column and s[gt_column] != "None" else None
+
+
+def _seg_region(region_of: Optional[Callable], smp: Sequence[str], gt: np.ndarray) -> Optional[np.ndarray]:
+    if region_of is None:
+        return None
+    r = np.asarray(region_of(smp, gt)) != 0
+    if r.shape != gt.shape[:2]:
+        raise ValueError(f"{smp[0]}: region {r.shape} and ground truth {gt.shape[:2]} differ in size")
+    return r
+
+
+def _seg_dataset_values(result: Dict, conf_sum: np.ndarray, K: int) -> None:
+    """The usual protocol: scores of the SUMMED confusion matrix of all images (float64 [K * K], exact below 2^53) into `result`."""
+    conf = [int(v) for v in conf_sum]
+    m = em.seg_metrics_from_counts([sum(conf), 0, 0] + conf, K)
+    result["miou_dataset"], result["pixel_acc_dataset"], result["iou_dataset"] = m["miou"], m["pixel_acc"], list(m["iou"])
+
+
+def _write_seg_eval_files(output_dir: str, names: List[str], per_sample, result: Dict, prediction_dir: Optional[str], gt_column: int,
+                          class_names: List[str]) -> None:
+    """`per_sample_metrics-seg.csv` and `eval_metrics-seg.txt`, laid out like the depth files; the dataset-level values and the per-class IoU
+    (one `name = value` line per palette colour) sit in the header."""
+    header = f"Evaluation metrics:\n    of predictions: {prediction_dir}\n    on seg labels: column {gt_column} of the filename list\n"
+    header += f"miou_dataset = {result['miou_dataset']:.6g}\npixel_acc_dataset = {result['pixel_acc_dataset']:.6g}\n"
+    header += "iou_dataset of the classes " + ", ".join(class_names) + ":\n"
+    header += "".join(f"    {nm} = {v:.6g}\n" for nm, v in zip(class_names, result["iou_dataset"]))
+    _write_metric_files(output_dir, "-seg", names, per_sample, result, header)
+
+
+def evaluate_seg_predictions(prediction_dir: str, base_dir: str, samples: Sequence[Sequence[str]], name_mode: FileNameMode, palette,
+                             output_dir: Optional[str] = None, pred_suffix: str = ".npy", gt_column: int = 6, gt_tol: int = 0,
+                             region_of: Optional[Callable] = None, read_gt: Optional[Callable[[str], np.ndarray]] = None) -> Dict:
+    """The file route for what `run_inference(mode="seg")` writes (`.npy`, float [H, W, 3]) or for 8-bit RGB `.png` maps (pred_suffix): per image
+    eval_metrics.seg_metrics against the ground truth of column gt_column (read_gt_seg or `read_gt`: a colour image or a label map), with
+    `palette` (uint8 [K, 3], or the pair `read_palette` returns) and gt_tol, over `region_of(sample, gt)` (a bool array; None: every pixel).
+    Returns the means of the per-image SEG_METRICS and, from the summed confusion matrix of all images, "miou_dataset", "pixel_acc_dataset"
+    and "iou_dataset" (a list of K).  Samples without ground truth (column absent or "None") or without a prediction file are skipped.
+    Optionally writes `eval_metrics-seg.txt` and `per_sample_metrics-seg.csv`."""
+    pal, class_names = _palette_and_names(palette)
+    K = pal.shape[0]
+    names = list(SEG_METRICS)
+    sums = {k: 0.0 for k in names}
+    per_sample = []
+    conf_sum = np.zeros(K * K, dtype=np.float64)
+    for s in samples:
+        rel = _seg_path(s, gt_column)
+        if rel is None:
+            continue
+        pred_name = _mask_pred_name(s[0], name_mode, pred_suffix)
+        pred_path = os.path.join(prediction_dir, pred_name)
+        if not os.path.exists(pred_path):
+            continue
+        gt = (read_gt or read_gt_seg)(os.path.join(base_dir, rel))
+        pred = _read_seg_prediction(pred_path)
+        if tuple(pred.shape[:2]) != tuple(gt.shape[:2]):
+            raise ValueError(f"{s[0]}: prediction {tuple(pred.shape[:2])} and ground truth {tuple(gt.shape[:2])} differ in size")
+        m = em.seg_metrics(pred, gt, pal, _seg_region(region_of, s, gt), gt_tol)
+        if m["n"] == 0:
+            raise ValueError(f"{s[0]}: no pixel to evaluate the segmentation on (n = 0)")
+        for k in names:
+            sums[k] += m[k]
+        per_sample.append((pred_name, [m[k] for k in names]))
+        conf_sum += m["conf"].reshape(-1)
+    n = len(per_sample)
+    result = {k: (sums[k] / n if n else float("nan")) for k in names}
+    _seg_dataset_values(result, conf_sum, K)
+    if output_dir is not None:
+        _write_seg_eval_files(output_dir, names, per_sample, result, prediction_dir, gt_column, class_names)
+    return result
+
+
+def infer_and_evaluate_seg(pipe, base_dir: str, samples: Sequence[Sequence[str]], palette, output_dir: Optional[str] = None,
+                           name_mode: FileNameMode = FileNameMode.id, batch_size: int = 4, rank: int = 0, world: int = 1,
+                           save_predictions: bool = False, prediction_dir: Optional[str] = None, evaluator: Optional[Callable] = None,
+                           read_gt: Optional[Callable[[str], np.ndarray]] = None, region_of: Optional[Callable] = None, denoise_steps: int = 1,
+                           ensemble_size: int = 1, processing_res: int = 0, match_input_res: bool = True, resample_method: str = "bilinear",
+                           fix_timesteps=None, prompt: str = "", prefetch: int = 2, gt_column: int = 6, gt_tol: int = 0) -> Dict:
+    """`infer_and_evaluate` for mode "seg": batches go through `pipe.predict_batch_device(mode="seg")`, the float [B, 3, H, W] colour maps stay
+    on the device, and `evaluator` -- `engine.eval_seg` unless given: (pred, gt, palette, region, gt_tol) -> one dict per image with SEG_METRICS
+    and "conf" -- quantises, decodes and scores them there against the ground truth of column gt_column (read_gt_seg or `read_gt`; and
+    `region_of(sample, gt)`, if given), decoded on the host and uploaded per batch (a batch that mixes colour images and label maps goes up as
+    label maps).  What it computes per image is `evaluate_seg_predictions`' quantity, bit for bit; sharding, the torch.distributed
+    combination, the rank-0 files (`eval_metrics-seg.txt`, `per_sample_metrics-seg.csv`) and the return value on every rank are
+    `infer_and_evaluate`'s, with one more float64 all_reduce for the K x K confusion matrix behind the dataset-level values.
+    save_predictions: the maps are also written as `run_inference(mode="seg")` would, float32 [H, W, 3] `.npy` under prediction_dir (default:
+    output_dir)."""
+    import torch
+    pal, class_names = _palette_and_names(palette)
+    K = pal.shape[0]
+    names = list(SEG_METRICS)
+    if evaluator is None:
+        from .engine import eval_seg as evaluator
+    if prediction_dir is None:
+        prediction_dir = output_dir
+    if save_predictions and prediction_dir is None:
+        raise ValueError("save_predictions needs prediction_dir or output_dir")
+    conf_sum = np.zeros(K * K, dtype=np.float64)  # this rank's images
+    pal_dev: dict = {}  # the palette goes up once per device
+
+    def score_group(group):
+        pred = pipe.predict_batch_device([img for _, img in group], "seg", processing_res=processing_res, match_input_res=match_input_res,
+                                         resample_method=resample_method, fix_timesteps=fix_timesteps, prompt=prompt,
+                                         denoising_steps=denoise_steps, ensemble_size=ensemble_size)
+        if pred.dim() != 4 or pred.shape[0] != len(group) or pred.shape[1] != 3:
+            raise ValueError(f"seg evaluation needs three-channel maps [B, 3, H, W], got {tuple(pred.shape)}")
+        gts, regions = [], []
+        for (_, smp), _ in group:
+            gt = np.asarray((read_gt or read_gt_seg)(os.path.join(base_dir, _seg_path(smp, gt_column))))
+            if tuple(gt.shape[:2]) != tuple(pred.shape[-2:]):
+                raise ValueError(f"{smp[0]}: prediction {tuple(pred.shape[-2:])} and ground truth {tuple(gt.shape[:2])} differ in size")
+            gts.append(gt)
+            regions.append(_seg_region(region_of, smp, gt))
+        if len({g.ndim for g in gts}) > 1:
+            gts = [em.seg_gt_labels(g, pal, gt_tol) for g in gts]
+        if pred.device not in pal_dev:
+            pal_dev[pred.device] = torch.from_numpy(pal).to(pred.device)
+        gt_t = torch.from_numpy(np.stack(gts)).to(pred.device, non_blocking=True)
+        region_t = torch.from_numpy(np.stack(regions)).to(pred.device, non_blocking=True) if region_of is not None else None
+        metrics = evaluator(pred, gt_t, pal_dev[pred.device], region_t, gt_tol)
+        assert len(metrics) == len(group)
+        for m in metrics:
+            conf_sum[:] += np.asarray(m["conf"]).reshape(-1)
+        if save_predictions:
+            pred_host = pred.cpu().numpy()
+            for j, ((_, smp), _) in enumerate(group):
+                _save_prediction(prediction_dir, _mask_pred_name(smp[0], name_mode), np.transpose(pred_host[j], (1, 2, 0)))
+        return [[metrics[j][k] for k in names] for j in range(len(group))]
+
+    rows, result, writer = _evaluation_loop(samples, lambda s: _seg_path(s, gt_column) is not None, lambda smp: _load_rgb(base_dir, smp[0], None),
+                                            score_group, names, batch_size, rank, world, prefetch)
+    _seg_dataset_values(result, _all_reduce_sum(conf_sum), K)
+    if output_dir is not None and writer:
+        _write_seg_eval_files(output_dir, names, [(_mask_pred_name(smp[0], name_mode), vals) for _, smp, vals in rows], result, prediction_dir,
+                              gt_column, class_names)
+    return result

@@ -19,6 +19,9 @@
  *   gp_eval_normal    the angular error of angular_loss per image + summary statistics   genpercept/losses/geometry_losses.py:550-590;
  *                       ground-truth column and validity rule                 src/dataset/base_dataset.py:362-363,416-418
  *   gp_eval_mask      (no reference code: genpercept_trainer.py:1169 is a TODO) dis / matting metrics on the saved 8-bit map   run.py:449-455
+ *   gp_seg_decode, gp_eval_seg
+ *                     (no reference code: the trainer's evaluation branch is a TODO) palette decode and confusion-matrix scores of the seg
+ *                       colour output against the RGB label image of column 6   src/dataset/base_dataset.py:333-346,366; run.py:449-455
  *   gp_ensemble_gather, gp_ensemble_reduce
  *                     ensemble_depth's tensor half (the BFGS fit stays on the host)   genpercept/util/ensemble.py:43-205;
  *                                                                   genpercept_pipeline.py:289-298
@@ -351,6 +354,54 @@ gp_status gp_eval_matting(const void* pred, int pred_is_u8, const unsigned char*
                           double* out /* [B][4] */, unsigned long long* counts_out /* [B][13] or NULL */,
                           unsigned char* level_out /* [B][H][W] or NULL */, double* grad_map_out /* [B][H][W] err or NULL */, void* workspace,
                           long long workspace_bytes, void* stream);
+
+/* ---- seg evaluation on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation; csrc/eval_seg.hip) ----
+ * Mode seg is colour regression: the reference trains it against an RGB label image, column 6 of the filename list
+ * (src/dataset/base_dataset.py:333-346,366), and ships neither a palette nor a decode nor a metric (the trainer's evaluation branch is a TODO).
+ * So the definitions are this project's and the USER supplies the palette; eval_metrics.palette_labels / seg_gt_labels / seg_counts /
+ * seg_metrics_from_counts are the same definitions on the host.
+ * palette: uint8 [K][3] (r, g, b), 1 <= K <= 192 (the count kernel keeps K * K 32-bit counters in LDS: 147456 of a CU's 163840 bytes at K = 192);
+ *   duplicate colours are allowed; any alignment.
+ * Quantised prediction: everything is computed on the 8-BIT prediction, quantise8 per channel = (unsigned char)(clamp(x, 0, 1) * 255.0f), the
+ *   product in fp32, truncated, NaN -> 0 -- the byte run.py:449-455 saves and gp_postprocess writes with q_bits = 8.  A uint8 prediction is
+ *   taken as it is.  pred: fp32 (pred_is_u8 = 0) or uint8 (pred_is_u8 = 1), [B][3][H][W] planar, planes at any offset (H * W need not be a
+ *   multiple of 4).
+ * Decode: for a pixel colour (r, g, b), d_k = (r - pr_k)^2 + (g - pg_k)^2 + (b - pb_k)^2 in integers; the class is the SMALLEST k attaining
+ *   the minimum, d is that minimum.  Exact and order-free: host and device agree bit for bit, ties included.
+ * Ground truth, one of two forms.  gt_is_labels = 0: a colour image, uint8 [B][H][W][3], interleaved as the image file decodes (3 bytes per
+ *   pixel at any alignment), decoded by the same rule; a pixel whose minimum distance exceeds gt_tol is void (gt_tol: int >= 0, a squared
+ *   distance; 0 = exact palette colour).  gt_is_labels = 1: a label map, uint8 [B][H][W]; values >= K are void (255: the usual ignore label);
+ *   gt_tol is ignored.
+ * region: uint8 [B][H][W], non-zero = scored, or NULL = every pixel, as in gp_eval_mask.
+ * Per image, unsigned 64-bit counts: n = scored pixels (in the region and not void), n_void = pixels in the region but void, sum_d = the sum
+ *   of the prediction's d over the scored pixels, conf[g][c] = scored pixels of ground-truth class g (row) predicted as class c (column).
+ * The values are float64, each one fixed sequence of correctly rounded + * / sqrt on those integers (no FMA), classes in increasing index:
+ *   row_i = sum_j conf[i][j], col_i = sum_j conf[j][i], tp_i = conf[i][i], union_i = row_i + col_i - tp_i, all in integers;
+ *   pixel_acc = (sum_i tp_i) / n;  mean_acc = the mean of tp_i / row_i over the classes with row_i > 0;
+ *   iou_i = tp_i / union_i where union_i > 0, NaN otherwise;  miou = the mean of the defined iou_i;
+ *   fwiou = (sum_{row_i > 0} (double)row_i * iou_i) / n;  colour_rmse = sqrt(sum_d / (3.0 * n)) / 255.0 (how far the colour output sits from
+ *   the palette);  n_classes = the number of classes with union_i > 0.
+ * out: double [B][8 + K] = n, n_void, pixel_acc, mean_acc, miou, fwiou, colour_rmse, n_classes, iou[K]; n = 0 gives the two counts and NaN
+ *   for everything else.
+ * counts_out: optional unsigned 64-bit [B][3 + K * K] = n, n_void, sum_d, conf row-major.  labels_out: optional uint8 [B][H][W], the
+ *   prediction's classes (every pixel, whatever the region).
+ * gp_seg_decode is the decode alone: labels_out uint8 [B][H][W], dist_out optional int32 [B][H][W] = the minimum d.  One kernel launch.
+ * gp_eval_seg: THREE kernel launches on `stream` for every B: the per-image matrices (in counts_out, or in the workspace when it is NULL) are
+ * zeroed, one count pass (K x K 32-bit counters per workgroup in LDS, filled by LDS integer atomics; the non-zero entries added to the image's
+ * matrix by 64-bit integer atomicAdd), one finalising workgroup per image.  Integer global atomics only, exact and order-free as in
+ * gp_eval_matting; no float is ever added atomically, nothing is read back.  An image's counts_out, out and labels are bitwise the same from
+ * call to call, for every batch it is part of and for every pointer alignment.  workspace: DEVICE scratch of at least the workspace entry's
+ * byte count (8-byte aligned; one matrix per image), free again once the stream has passed the call.
+ * GP_ERR_INVALID before any HIP call: null pred / gt / palette / out / workspace (gp_seg_decode: null pred / palette / labels_out), B, H or
+ * W < 1, B > 65535, H * W > 2^31 - 1, K < 1 or K > 192, gt_tol < 0, pred_is_u8 or gt_is_labels outside 0..1, a float pred (or dist_out) not
+ * 4-byte aligned, out / counts_out / workspace not 8-byte aligned, workspace_bytes too small. */
+gp_status gp_seg_decode(const void* pred, int pred_is_u8, const unsigned char* palette /* [K][3] */, int K, int B, int H, int W,
+                        unsigned char* labels_out /* [B][H][W] */, int* dist_out /* [B][H][W] or NULL */, void* stream);
+long long gp_eval_seg_workspace(int B, int H, int W, int K);  /* bytes; 0 for B, H or W < 1 or K outside 1..192; proportional to B; multiple of 8 */
+gp_status gp_eval_seg(const void* pred, int pred_is_u8, const unsigned char* gt, int gt_is_labels, int gt_tol, const unsigned char* region,
+                      const unsigned char* palette /* [K][3] */, int K, int B, int H, int W, double* out /* [B][8 + K] */,
+                      unsigned long long* counts_out /* [B][3 + K * K] or NULL */, unsigned char* labels_out /* [B][H][W] or NULL */,
+                      void* workspace, long long workspace_bytes, void* stream);
 
 /* ---- test-time ensembling on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation, no atomics; csrc/ensemble.hip) ----
  * The tensor half of ensemble_depth (genpercept/util/ensemble.py:43-205, called at genpercept_pipeline.py:289-298) for the E members of each of

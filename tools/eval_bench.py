@@ -1,4 +1,4 @@
-"""Time the device depth (or, with --normals, surface-normal; with --masks, dis / matting; with --structure, dis structure-score; with --matting, matting Grad / Conn) evaluation against the host evaluation, and the batched device loop on the tiny pipeline.
+"""Time the device depth (or, with --normals, surface-normal; with --masks, dis / matting; with --structure, dis structure-score; with --matting, matting Grad / Conn; with --seg, seg palette decode + confusion matrix) evaluation against the host evaluation, and the batched device loop on the tiny pipeline.
 
   python tools/eval_bench.py --out profiles/<name>.json
 
@@ -37,6 +37,15 @@
    thin strands, the prediction = the alpha plus noise in the soft band and a few detached blobs), against `eval_metrics.matting_metrics` on
    the same arrays on the host (wall clock, one run).  conn is compared on the spot (bit-equal), grad to 1e-9.  `--no-host` skips the host
    route (for a kernel trace of the device calls alone).
+
+  python tools/eval_bench.py --seg --out profiles/<name>.json
+
+7. `--seg` (instead of 1 and 2): the `gp_eval_seg` entry behind `engine.eval_seg` (palette decode of prediction and colour ground truth, the
+   K x K confusion matrix in LDS, three launches) at 4 x 480 x 640 with K = 19 and K = 150 and at 1 x 2048 x 2048 with K = 150, on a seg-like
+   input (blocks of palette colours, +-3 / 255 of colour noise, 5 % of the pixels flipped, 4 % of the ground truth off the palette): device
+   events around `iters` back-to-back calls after a warm-up, for the C entry on preallocated buffers and for `engine.eval_seg` itself (which
+   allocates, copies the result down and synchronises), against `eval_metrics.seg_metrics` on the same arrays on the host (wall clock, one
+   run).  The two sides' values are compared on the spot (bit-equal).  The result carries the shader clock sampled meanwhile and the build id.
 Needs a GPU; there is no CPU fall-back."""
 import argparse
 import json
@@ -357,6 +366,67 @@ def bench_eval_matting(b, h, w, iters, host):
     return res
 
 
+def seg_case(b, h, w, K, seed):
+    """pred float32 [b, 3, h, w], colour ground truth uint8 [b, h, w, 3], palette uint8 [K, 3]"""
+    rng = np.random.RandomState(seed)
+    pal = rng.randint(0, 256, (K, 3)).astype(np.uint8)
+    lab = rng.randint(0, K, (b, h // 16 + 1, w // 16 + 1)).repeat(16, 1).repeat(16, 2)[:, :h, :w]
+    seen = np.where(rng.rand(b, h, w) < 0.05, rng.randint(0, K, (b, h, w)), lab)
+    col = np.clip(pal[seen].astype(np.int16) + rng.randint(-3, 4, (b, h, w, 3)), 0, 255).astype(np.float32)
+    pred = np.ascontiguousarray(np.moveaxis((col + np.float32(0.2)) / np.float32(255.0), -1, 1))
+    gt = pal[lab]
+    off = rng.rand(b, h, w) < 0.04
+    gt[off] = rng.randint(0, 256, (int(off.sum()), 3)).astype(np.uint8)
+    return pred, np.ascontiguousarray(gt), pal
+
+
+def time_events(call, iters):
+    for _ in range(3):
+        call()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        call()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def bench_eval_seg(b, h, w, K, iters, host):
+    from genpercept_amd import engine as ge
+    from genpercept_amd import eval_metrics as em
+    d = torch.device("cuda", 0)
+    lib = ge.load_library()
+    pred, gt, pal = seg_case(b, h, w, K, 11)
+    tp, tg, tpal = (torch.from_numpy(x).to(d) for x in (pred, gt, pal))
+    nbytes = int(lib.gp_eval_seg_workspace(b, h, w, K))
+    ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=d)
+    out = torch.empty((b, 8 + K), dtype=torch.float64, device=d)
+    stream = int(torch.cuda.current_stream(d).cuda_stream)
+
+    def entry():
+        st = lib.gp_eval_seg(tp.data_ptr(), 0, tg.data_ptr(), 0, 0, None, tpal.data_ptr(), K, b, h, w, out.data_ptr(), None, None, ws.data_ptr(), nbytes, stream)
+        assert st == ge.GP_OK, st
+
+    entry_ms = time_events(entry, iters)
+    call_ms = time_events(lambda: ge.eval_seg(tp, tg, tpal), iters)
+    decode_ms = time_events(lambda: ge.seg_decode(tp, tpal), iters)
+    metrics = ge.eval_seg(tp, tg, tpal)
+    res = dict(shape=[b, h, w], K=K, input="seg-like, colour ground truth", gp_eval_seg_ms_per_call=entry_ms, engine_eval_seg_ms_per_call=call_ms,
+               engine_seg_decode_ms_per_call=decode_ms, device_iters=iters, launches_per_call=3, workspace_bytes=nbytes,
+               scores_image_0={k: metrics[0][k] for k in em.SEG_METRICS})
+    if host:
+        t0 = time.perf_counter()
+        ref = [em.seg_metrics(pred[i], gt[i], pal) for i in range(b)]
+        host_ms = (time.perf_counter() - t0) * 1e3
+        for i in range(b):
+            assert all(metrics[i][k] == ref[i][k] for k in em.SEG_METRICS) and np.array_equal(metrics[i]["conf"], ref[i]["conf"]), (i, metrics[i], ref[i])
+            assert np.array_equal(metrics[i]["iou"], np.array(ref[i]["iou"]), equal_nan=True)
+        res.update(host_seg_metrics_ms=host_ms, host_runs=1, host_over_engine_call=host_ms / call_ms, values_equal_host=True)
+    return res
+
+
 def bench_loop(n_images, batch_sizes, repeats):
     from PIL import Image
     from genpercept_amd import GenPerceptPipeline
@@ -411,11 +481,18 @@ def main():
     ap.add_argument("--masks", action="store_true", help="time gp_eval_mask against mask_metrics instead")
     ap.add_argument("--structure", action="store_true", help="time gp_eval_structure against structure_metrics instead")
     ap.add_argument("--matting", action="store_true", help="time gp_eval_matting against matting_metrics instead")
-    ap.add_argument("--no-host", action="store_true", help="with --structure or --matting: the device calls alone")
+    ap.add_argument("--seg", action="store_true", help="time gp_eval_seg against seg_metrics instead")
+    ap.add_argument("--no-host", action="store_true", help="with --structure, --matting or --seg: the device calls alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU")
-    if a.matting:
+    if a.seg:
+        import bench
+        with bench.ClockPowerSampler("cuda:0") as clock:
+            rows = [bench_eval_seg(b, h, w, K, a.iters, not a.no_host) for (b, h, w, K) in ((4, 480, 640, 19), (4, 480, 640, 150), (1, 2048, 2048, 150))]
+        res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box", build_id=bench.source_build_id(), clock=clock.summary(),
+                   eval_seg=rows)
+    elif a.matting:
         res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box",
                    eval_matting=[bench_eval_matting(b, h, w, a.iters, not a.no_host) for (b, h, w) in ((4, 480, 640), (1, 2048, 2048))])
     elif a.structure:
@@ -432,7 +509,7 @@ def main():
                    eval_normal=[bench_eval_normal(4, 480, 640, a.iters, 3), bench_eval_normal(1, 4032, 6048, a.iters, 1)])
     else:
         res = dict(device=torch.cuda.get_device_name(0), eval_depth=[bench_eval(1, 4032, 6048, a.iters, 1), bench_eval(4, 480, 640, a.iters, 3)])
-    if not a.skip_loop and not a.normals and not a.masks and not a.structure and not a.matting:
+    if not a.skip_loop and not a.normals and not a.masks and not a.structure and not a.matting and not a.seg:
         res["infer_and_evaluate"] = bench_loop(16, (1, 4), 3)
     text = json.dumps(res, indent=1)
     print(text)
