@@ -48,6 +48,7 @@ def precision_of(dtype) -> str:
     raise ValueError(f"unsupported dtype {dtype}")
 
 GP_OK = 0
+GP_ERR_INVALID = 1
 MODES = {"depth": 0, "normal": 1, "seg": 2, "matting": 3, "dis": 4, "disparity": 5}
 ONE_CHANNEL_MODES = ("depth", "matting", "dis", "disparity")  # genpercept_pipeline.py:523
 ACT = {"none": 0, "silu": 1, "relu": 2, "geglu": 3}
@@ -161,6 +162,8 @@ SYMBOLS = {
     "gp_seg_decode": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gp_eval_seg_workspace": (_ll, [_i, _i, _i, _i]),
     "gp_eval_seg": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _ll, _vp]),
+    "gp_mask_band_workspace": (_ll, [_i, _i, _i]),
+    "gp_mask_band": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp]),
     "gp_ensemble_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gp_ensemble_workspace": (_ll, [_i, _i, _i, _i]),
     "gp_ensemble_reduce": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
@@ -1185,6 +1188,83 @@ def eval_matting(pred: torch.Tensor, gt: torch.Tensor, region: Optional[torch.Te
         if row[0] == 0:
             raise ValueError(f"image {i}: no pixel to evaluate the alpha map on (n = 0)")
     return [{k: (int(row[j]) if k == "n" else float(row[j])) for j, k in enumerate(MATTING_OUT_NAMES)} for row in raw]
+
+
+TRIMAP_METRICS = ["mae_t", "mse_t", "sad_t", "sad_fg", "sad_bg"]  # eval_metrics.TRIMAP_METRICS
+BOUNDARY_METRICS = ["biou"]  # eval_metrics.BOUNDARY_METRICS
+BAND_PLANES = ["band", "fg", "bg", "inner", "trimap"]  # gp_mask_band's output planes, in argument order
+BAND_METRIC = {"euclidean": 0, "chebyshev": 1, 0: 0, 1: 1}
+
+
+def mask_band(a: torch.Tensor, lo: int, hi: int, reach: int, metric="euclidean", border: bool = False, want: Sequence[str] = ("band",)):
+    """gp_mask_band on a device tensor: a [B, H, W], [B, 1, H, W] or [H, W], a float map in [0, 1] (quantised to 8 bits by the kernel) or
+    uint8.  A = {a > lo}, Bc = {a < hi} (-1 <= lo < hi <= 256).  Returns a dict of the uint8 [B, H, W] planes named in `want` (BAND_PLANES):
+    band (within reach of A and of Bc), fg (out of Bc's reach), bg (out of A's reach), inner (in A, within Bc's reach), each 0 / 255, trimap
+    (0 / 128 / 255).  metric "euclidean": reach is a squared radius (<= 2^24); "chebyshev": a radius (<= 4096).  border: the outside of the
+    image counts as Bc.  Definitions in include/genpercept_hip.h; eval_metrics.mask_band gives the same bits.  Enqueued on the current
+    stream, no synchronisation."""
+    lib = load_library()
+    a = _eval_maps(a, "a")
+    assert a.is_cuda
+    if metric not in BAND_METRIC:
+        raise ValueError(f"metric is 'euclidean' or 'chebyshev', got {metric!r}")
+    want = list(want)
+    if not want or any(k not in BAND_PLANES for k in want) or len(set(want)) != len(want):
+        raise ValueError(f"want names one or more of {BAND_PLANES}, got {want}")
+    is_u8 = a.dtype == torch.uint8
+    if not is_u8 and not a.dtype.is_floating_point:
+        raise ValueError(f"a: a float map in [0, 1] or its uint8 quantisation, got {a.dtype}")
+    a = (a if is_u8 else a.to(torch.float32)).contiguous()
+    b, h, w = (int(v) for v in a.shape)
+    planes = torch.empty((len(want), b, h, w), dtype=torch.uint8, device=a.device)
+    outs = [_ptr(planes[want.index(k)]) if k in want else None for k in BAND_PLANES]
+    nbytes = int(lib.gp_mask_band_workspace(b, h, w))
+    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=a.device)
+    st = lib.gp_mask_band(a.data_ptr(), int(is_u8), b, h, w, int(lo), int(hi), BAND_METRIC[metric], int(reach), int(bool(border)), *outs,
+                          ws.data_ptr(), nbytes, _stream_ptr(a.device))
+    if st == GP_ERR_INVALID:
+        raise ValueError(f"gp_mask_band: invalid arguments (lo = {lo}, hi = {hi}, reach = {reach}, metric = {metric!r}, maps {(b, h, w)})")
+    if st != GP_OK:
+        raise RuntimeError(f"gp_mask_band failed ({st})")
+    return {k: planes[j] for j, k in enumerate(want)}
+
+
+def eval_trimap(pred: torch.Tensor, gt: torch.Tensor, radius: float, metric="euclidean"):
+    """eval_metrics.trimap_metrics for a batch of maps that are on the device (pred, gt as `eval_mask_raw`): one gp_mask_band on the ground
+    truth (lo = 0, hi = 255, nothing outside the image) gives the transition region and the two sides, three gp_eval_mask calls score the
+    prediction over them.  Returns one dict per image: TRIMAP_METRICS, "n_t", "n_fg_side", "n_bg_side".  Raises ValueError naming the image
+    when its transition region is empty.  One device -> host copy of 3 x B x 516 words."""
+    from .eval_metrics import band_reach, trimap_from_counts
+    gt = _eval_maps(gt, "gt")
+    planes = mask_band(gt, 0, 255, band_reach(radius, metric), metric, False, want=("band", "fg", "bg"))
+    counts = torch.stack([_eval_mask_launch(pred, gt, planes[k], True)[2] for k in ("band", "fg", "bg")]).cpu().numpy()
+    res = []
+    for i in range(counts.shape[1]):
+        if counts[0, i, 0] == 0:
+            raise ValueError(f"image {i}: no pixel in the transition region (n = 0)")
+        res.append(trimap_from_counts(counts[0, i], counts[1, i], counts[2, i]))
+    return res
+
+
+def eval_boundary_iou(pred: torch.Tensor, gt: torch.Tensor, ratio: float = 0.02):
+    """eval_metrics.boundary_iou for a batch of maps that are on the device (pred, gt as `eval_mask_raw`): the inner bands of G = gt > 128 and
+    of P = q >= 128 (Chebyshev, d = boundary_reach(H, W, ratio), the outside of the image counts as the other side) from two gp_mask_band
+    calls, their IoU from gp_eval_mask.  Returns one dict per image: "biou", "d", "n_gt_band", "n_pred_band".  One device -> host copy of
+    B x (10 + 516) words."""
+    from .eval_metrics import boundary_reach
+    pred, gt = _eval_maps(pred, "pred"), _eval_maps(gt, "gt")
+    if gt.dtype != torch.uint8:
+        raise ValueError(f"gt: the ground truth is an 8-bit mask (uint8), got {gt.dtype}")
+    if pred.shape != gt.shape:
+        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have one shape")
+    b, h, w = (int(v) for v in gt.shape)
+    d = boundary_reach(h, w, ratio)
+    g_d = mask_band(gt, 128, 129, d, "chebyshev", True, want=("inner",))["inner"]
+    p_d = mask_band(pred, 127, 128, d, "chebyshev", True, want=("inner",))["inner"]
+    buf, _, _ = _eval_mask_launch(p_d, g_d, None, True)
+    host = buf.cpu().numpy()
+    raw, counts = host[:b * MASK_OUT].view("float64").reshape(b, MASK_OUT), host[b * MASK_OUT:].reshape(b, MASK_COUNTS)
+    return [dict(biou=float(raw[i, 8]), d=d, n_gt_band=int(raw[i, 1]), n_pred_band=int(counts[i, 1]) // 255) for i in range(b)]
 
 
 SEG_METRICS = ["pixel_acc", "mean_acc", "miou", "fwiou", "colour_rmse"]  # gp_eval_seg's out[2 .. 6]; eval_metrics.SEG_METRICS

@@ -613,6 +613,132 @@ def matting_metrics(pred: np.ndarray, gt: np.ndarray, region: Optional[np.ndarra
     return dict(grad=grad_error(q, gt, region)["grad"], conn=conn_error(q, gt, region)["conn"])
 
 
+# ---- trimap and boundary bands: the matting transition-region scores, Boundary IoU ----------------------------------------------------------
+# "Within reach of a set and within reach of its complement", exactly.  Definitions: include/genpercept_hip.h (gp_mask_band); the functions
+# below restate them with numpy alone (capped column distances and one pass per horizontal offset for the disc -- equal to thresholding
+# edt_keys' high word --, two 1-D running-window passes for the square) and
+# are bit-equal to the device planes.
+TRIMAP_METRICS = ["mae_t", "mse_t", "sad_t", "sad_fg", "sad_bg"]
+BOUNDARY_METRICS = ["biou"]
+BAND_PLANES = ["band", "fg", "bg", "inner", "trimap"]
+BAND_METRIC = {"euclidean": 0, "chebyshev": 1, 0: 0, 1: 1}
+BAND_MAX_REACH = (1 << 24, 4096)  # per metric: a squared radius, a radius
+
+
+def band_reach(radius: float, metric) -> int:
+    """gp_mask_band's integer `reach` of a real radius: floor(radius^2) for the Euclidean disc, floor(radius) for the Chebyshev square."""
+    if metric not in BAND_METRIC:
+        raise ValueError(f"metric is 'euclidean' (0) or 'chebyshev' (1), got {metric!r}")
+    if not radius >= 0:
+        raise ValueError(f"a radius is >= 0, got {radius}")
+    return int(math.floor(radius * radius)) if BAND_METRIC[metric] == 0 else int(math.floor(radius))
+
+
+def boundary_reach(h: int, w: int, ratio: float = 0.02) -> int:
+    """Boundary IoU's band width in pixels: `ratio` of the image diagonal, rounded, at least 1."""
+    return max(1, int(round(ratio * math.sqrt(h * h + w * w))))
+
+
+def _check_band_args(lo: int, hi: int, reach: int, metric, border) -> Tuple[int, int, int, int, int]:
+    if metric not in BAND_METRIC:
+        raise ValueError(f"metric is 'euclidean' (0) or 'chebyshev' (1), got {metric!r}")
+    m = BAND_METRIC[metric]
+    lo, hi, reach = int(lo), int(hi), int(reach)
+    if not -1 <= lo < hi <= 256:
+        raise ValueError(f"-1 <= lo < hi <= 256, got lo = {lo}, hi = {hi}")
+    if not 0 <= reach <= BAND_MAX_REACH[m]:
+        raise ValueError(f"0 <= reach <= {BAND_MAX_REACH[m]} for metric {m}, got {reach}")
+    return lo, hi, reach, m, int(bool(border))
+
+
+def _window_any(s: np.ndarray, d: int, axis: int) -> np.ndarray:
+    """Whether any element of the boolean array within d positions along `axis` is set (a running window over a cumulative sum)."""
+    n = s.shape[axis]
+    c = np.concatenate([np.zeros_like(s.take([0], axis=axis), dtype=np.int64), np.cumsum(s, axis=axis, dtype=np.int64)], axis=axis)
+    i = np.arange(n)
+    return c.take(np.minimum(i + d, n - 1) + 1, axis=axis) - c.take(np.maximum(i - d, 0), axis=axis) > 0
+
+
+def _within_reach(s: np.ndarray, reach: int, metric: int) -> np.ndarray:
+    """Pixels whose distance to the nearest set pixel of the boolean [H, W] array is <= reach (none when the array is empty).  Chebyshev: two
+    1-D running windows.  Euclidean: what `(edt_keys(s) >> 32) <= reach` gives, without the full transform (whose row search runs until the
+    FARTHEST pixel is settled, a minute on a 2048 x 2048 alpha): the vertical distance to the column's nearest set pixel, capped just above
+    the radius, then one pass per horizontal offset up to the radius."""
+    if metric == 1:
+        return _window_any(_window_any(s, reach, 0), reach, 1)
+    h, w = s.shape
+    rv = math.isqrt(reach)
+    ys = np.arange(h, dtype=np.int64)[:, None]
+    up = np.maximum.accumulate(np.where(s, ys, -(h + rv + 1)), axis=0)             # the nearest set row at or above (far away: none)
+    dn = np.minimum.accumulate(np.where(s, ys, 2 * h + rv + 1)[::-1], axis=0)[::-1]  # ... at or below
+    dv = np.minimum(np.minimum(ys - up, dn - ys), rv + 1)
+    d2 = dv * dv
+    hit = d2 <= reach
+    for dx in range(1, min(rv, w - 1) + 1):
+        c = d2 <= reach - dx * dx
+        hit[:, dx:] |= c[:, :-dx]
+        hit[:, :-dx] |= c[:, dx:]
+    return hit
+
+
+def mask_band(a: np.ndarray, lo: int, hi: int, reach: int, metric="euclidean", border=False) -> Dict[str, np.ndarray]:
+    """gp_mask_band on the host for one map: a float [H, W] in [0, 1] (quantised by `quantize_mask`) or uint8.  A = {a > lo}, Bc = {a < hi};
+    returns the uint8 planes BAND_PLANES: band (within reach of both), fg (out of Bc's reach), bg (out of A's reach), inner (in A and within
+    Bc's reach), each 0 / 255, and trimap (0 / 128 / 255 for bg / band / fg).  metric "euclidean" (0): reach is a squared radius; "chebyshev"
+    (1): a radius.  border: the outside of the image counts as Bc."""
+    lo, hi, reach, m, border = _check_band_args(lo, hi, reach, metric, border)
+    q = quantize_mask(a)
+    if q.ndim != 2 or q.shape[0] < 1 or q.shape[1] < 1:
+        raise ValueError(f"one [H, W] map, got {q.shape}")
+    h, w = q.shape
+    in_a = q.astype(np.int64) > lo
+    near_a = _within_reach(in_a, reach, m)
+    near_b = _within_reach(q.astype(np.int64) < hi, reach, m)
+    if border:
+        ys, xs = np.arange(h, dtype=np.int64)[:, None], np.arange(w, dtype=np.int64)[None, :]
+        e = np.minimum(np.minimum(ys + 1, h - ys), np.minimum(xs + 1, w - xs))
+        near_b = near_b | ((e * e if m == 0 else e) <= reach)
+    u8 = lambda sel: np.where(sel, 255, 0).astype(np.uint8)
+    band = near_a & near_b
+    return dict(band=u8(band), fg=u8(~near_b), bg=u8(~near_a), inner=u8(in_a & near_b),
+                trimap=np.where(band, 128, np.where(near_a, 255, 0)).astype(np.uint8))
+
+
+def trimap_from_counts(c_t, c_fg, c_bg) -> Dict[str, float]:
+    """TRIMAP_METRICS and the three region sizes from gp_eval_mask's counts over the transition region, the foreground side and the background
+    side: mae_t = sad / (255.0 n_t), mse_t = sse / (65025.0 n_t) (NaN for an empty transition region), sad_* = sad / 255000.0 (0.0 for an
+    empty region)."""
+    (n_t, _, sad_t, sse_t), (n_f, _, sad_f, _), (n_b, _, sad_b, _) = ([int(v) for v in np.asarray(c).reshape(-1)[:4]] for c in (c_t, c_fg, c_bg))
+    nan = float("nan")
+    return dict(mae_t=sad_t / (255.0 * n_t) if n_t else nan, mse_t=sse_t / (65025.0 * n_t) if n_t else nan, sad_t=sad_t / 255000.0,
+                sad_fg=sad_f / 255000.0, sad_bg=sad_b / 255000.0, n_t=n_t, n_fg_side=n_f, n_bg_side=n_b)
+
+
+def trimap_metrics(pred: np.ndarray, gt: np.ndarray, radius: float, metric="euclidean") -> Dict[str, float]:
+    """The trimap-free matting protocol for one image: the trimap comes from the ground-truth alpha (dilate(gt != 0) - erode(gt == 255) with a
+    disc or square of `radius`, nothing outside the image), SAD / MSE / MAD over the transition region and SAD over the two sides.  pred a
+    float map in [0, 1] or uint8, gt uint8.  Raises ValueError when the transition region is empty."""
+    planes = mask_band(gt, 0, 255, band_reach(radius, metric), metric, False)
+    q = quantize_mask(pred)
+    m = trimap_from_counts(*(mask_counts(q, gt, planes[k]) for k in ("band", "fg", "bg")))
+    if m["n_t"] == 0:
+        raise ValueError("no pixel in the transition region (n = 0)")
+    return m
+
+
+def boundary_iou(pred: np.ndarray, gt: np.ndarray, ratio: float = 0.02) -> Dict[str, float]:
+    """Boundary IoU (Cheng et al. 2021) of one image: d = boundary_reach(H, W, ratio); G_d, P_d the pixels of G = gt > 128 and of
+    P = q >= 128 within Chebyshev distance d of the other side, the outside of the image included; biou = |G_d & P_d| / |G_d | P_d|, 0.0 when
+    both are empty.  Also d and the two band sizes."""
+    q = quantize_mask(pred)
+    h, w = q.shape
+    d = boundary_reach(h, w, ratio)
+    g_d = mask_band(gt, 128, 129, d, 1, True)["inner"]
+    p_d = mask_band(q, 127, 128, d, 1, True)["inner"]
+    c = mask_counts(p_d, g_d)
+    return dict(biou=mask_metrics_from_counts(c)["iou"], d=d, n_gt_band=int(c[260:516].sum()), n_pred_band=int(c[1]) // 255)
+
+
 # ---- seg: palette decode and confusion-matrix scores -----------------------------------------------------------------------------------------
 # Mode seg is colour regression against an RGB label image (src/dataset/base_dataset.py:333-346,366); the reference has neither a palette nor a
 # decode nor a metric for it.  The definitions below are this project's, stated once in include/genpercept_hip.h (gp_seg_decode, gp_eval_seg):

@@ -531,6 +531,8 @@ def infer_and_evaluate_normals(pipe, base_dir: str, samples: Sequence[Sequence[s
 MASK_METRICS = list(em.MASK_METRICS)  # per-image values, in order; the dataset-level "max_f_dataset" comes on top
 STRUCTURE_METRICS = list(em.STRUCTURE_METRICS)  # with structure=True: appended to the per-image columns, the means and the files
 MATTING_METRICS = list(em.MATTING_METRICS)  # with matting=True: appended after them
+TRIMAP_METRICS = list(em.TRIMAP_METRICS)  # with trimap_radius: the transition-region and side scores of the trimap-free matting protocol, after them
+BOUNDARY_METRICS = list(em.BOUNDARY_METRICS)  # with boundary_iou=True: Boundary IoU, last
 
 
 def read_gt_mask(path: str) -> np.ndarray:
@@ -591,9 +593,29 @@ def _sum_curves(counts_in_order) -> np.ndarray:
     return acc
 
 
-def _write_mask_eval_files(output_dir: str, names: List[str], per_sample, result: Dict[str, float], prediction_dir: Optional[str]) -> None:
+def _band_options(trimap_radius, trimap_metric, boundary_iou: bool, boundary_ratio: float, region_of) -> Tuple[List[str], str]:
+    """The extra column names (trimap, then boundary) and the header line of the band options; checks them."""
+    names, note = [], ""
+    if trimap_radius is None and not boundary_iou:
+        return names, note
+    if region_of is not None:
+        raise ValueError("trimap_radius / boundary_iou derive their regions from the ground truth: they do not go with region_of")
+    if trimap_radius is not None:
+        em.band_reach(trimap_radius, trimap_metric)  # (raises on a bad radius or metric)
+        names += list(TRIMAP_METRICS)
+        note += f"    trimap from the ground truth: radius {trimap_radius:g}, metric {trimap_metric}\n"
+    if boundary_iou:
+        if not boundary_ratio > 0:
+            raise ValueError(f"boundary_ratio is > 0, got {boundary_ratio}")
+        names += list(BOUNDARY_METRICS)
+        note += f"    boundary IoU: band of {boundary_ratio:g} of the image diagonal\n"
+    return names, note
+
+
+def _write_mask_eval_files(output_dir: str, names: List[str], per_sample, result: Dict[str, float], prediction_dir: Optional[str],
+                           note: str = "") -> None:
     """`per_sample_metrics-mask.csv` and `eval_metrics-mask.txt`, laid out like the depth files; the dataset-level value sits in the header."""
-    header = f"Evaluation metrics:\n    of predictions: {prediction_dir}\n    on 8-bit masks: column 1 of the filename list\n"
+    header = f"Evaluation metrics:\n    of predictions: {prediction_dir}\n    on 8-bit masks: column 1 of the filename list\n{note}"
     header += f"max_f_dataset = {result['max_f_dataset']:.6g}\n"
     _write_metric_files(output_dir, "-mask", names, per_sample, result, header)
 
@@ -601,7 +623,8 @@ def _write_mask_eval_files(output_dir: str, names: List[str], per_sample, result
 def evaluate_mask_predictions(prediction_dir: str, base_dir: str, samples: Sequence[Sequence[str]], name_mode: FileNameMode,
                               output_dir: Optional[str] = None, pred_suffix: str = ".npy", region_of: Optional[Callable] = None,
                               read_gt: Optional[Callable[[str], np.ndarray]] = None, structure: bool = False,
-                              matting: bool = False) -> Dict[str, float]:
+                              matting: bool = False, trimap_radius: Optional[float] = None, trimap_metric: str = "euclidean",
+                              boundary_iou: bool = False, boundary_ratio: float = 0.02) -> Dict[str, float]:
     """The file route for what `run_inference(mode="dis" | "matting")` writes (`.npy`) or for 8-bit `.png` maps (pred_suffix): per image
     eval_metrics.mask_metrics against the 8-bit ground truth of column 1 (read_gt_mask or `read_gt`), over `region_of(sample, gt)` (a bool
     array, e.g. a trimap's unknown region; None: every pixel).  Returns the means of the per-image MASK_METRICS and "max_f_dataset", the
@@ -609,10 +632,14 @@ def evaluate_mask_predictions(prediction_dir: str, base_dir: str, samples: Seque
     skipped.  Optionally writes `eval_metrics-mask.txt` and `per_sample_metrics-mask.csv`.  structure: the dis structure scores
     (eval_metrics.structure_metrics: STRUCTURE_METRICS, whole-image quantities, so not together with region_of) as five more columns.
     matting: the gradient and connectivity errors (eval_metrics.matting_metrics: MATTING_METRICS, summed over the same region) as two more
-    columns, after the structure columns if both are asked for."""
+    columns, after the structure columns if both are asked for.  trimap_radius: the trimap-free matting protocol (eval_metrics.trimap_metrics:
+    TRIMAP_METRICS over the transition region and the two sides of the trimap that the ground-truth alpha gives with a disc -- trimap_metric
+    "euclidean" -- or a square -- "chebyshev" -- of that radius) as five more columns.  boundary_iou: Boundary IoU (eval_metrics.boundary_iou
+    with boundary_ratio of the diagonal) as one more column, last.  Neither goes with region_of; a header line states radius, metric, ratio."""
     if structure and region_of is not None:
         raise ValueError("structure scores are whole-image quantities: structure=True does not go with region_of")
-    names = list(MASK_METRICS) + (list(STRUCTURE_METRICS) if structure else []) + (list(MATTING_METRICS) if matting else [])
+    band_names, note = _band_options(trimap_radius, trimap_metric, boundary_iou, boundary_ratio, region_of)
+    names = list(MASK_METRICS) + (list(STRUCTURE_METRICS) if structure else []) + (list(MATTING_METRICS) if matting else []) + band_names
     sums = {k: 0.0 for k in names}
     per_sample, counts = [], []
     for s in samples:
@@ -635,6 +662,13 @@ def evaluate_mask_predictions(prediction_dir: str, base_dir: str, samples: Seque
             m.update(em.structure_metrics(pred, gt))
         if matting:
             m.update(em.matting_metrics(pred, gt, region))
+        if trimap_radius is not None:
+            try:
+                m.update(em.trimap_metrics(pred, gt, trimap_radius, trimap_metric))
+            except ValueError as e:
+                raise ValueError(f"{s[0]}: {e}") from None
+        if boundary_iou:
+            m.update(em.boundary_iou(pred, gt, boundary_ratio))
         for k in names:
             sums[k] += m[k]
         per_sample.append((pred_name, [m[k] for k in names]))
@@ -643,7 +677,7 @@ def evaluate_mask_predictions(prediction_dir: str, base_dir: str, samples: Seque
     result = {k: (sums[k] / n if n else float("nan")) for k in names}
     result["max_f_dataset"] = _max_f_of_mean_curves(_sum_curves(counts), n)
     if output_dir is not None:
-        _write_mask_eval_files(output_dir, names, per_sample, result, prediction_dir)
+        _write_mask_eval_files(output_dir, names, per_sample, result, prediction_dir, note)
     return result
 
 
@@ -654,7 +688,9 @@ def infer_and_evaluate_masks(pipe, base_dir: str, samples: Sequence[Sequence[str
                              ensemble_size: int = 1, processing_res: int = 0, match_input_res: bool = True, resample_method: str = "bilinear",
                              fix_timesteps=None, prompt: str = "", prefetch: int = 2, structure: bool = False,
                              structure_evaluator: Optional[Callable] = None, matting: bool = False,
-                             matting_evaluator: Optional[Callable] = None) -> Dict[str, float]:
+                             matting_evaluator: Optional[Callable] = None, trimap_radius: Optional[float] = None,
+                             trimap_metric: str = "euclidean", trimap_evaluator: Optional[Callable] = None, boundary_iou: bool = False,
+                             boundary_ratio: float = 0.02, boundary_evaluator: Optional[Callable] = None) -> Dict[str, float]:
     """`infer_and_evaluate` for mode "dis" or "matting": batches go through `pipe.predict_batch_device(mode=mode)`, the float [B, 1, H, W] maps
     stay on the device, and `evaluator` -- `engine.eval_mask` unless given: (pred, gt, region) -> one dict per image with MASK_METRICS and
     "counts" -- quantises and scores them there against the 8-bit ground truth of column 1 (and `region_of(sample, gt)`, if given), decoded on
@@ -666,19 +702,27 @@ def infer_and_evaluate_masks(pipe, base_dir: str, samples: Sequence[Sequence[str
     batch -- `structure_evaluator`, `engine.eval_structure` unless given: (pred, gt) -> one dict per image; not together with region_of.
     matting: the gradient and connectivity errors as two more per-image columns (MATTING_METRICS, after the structure columns), from a further
     device call on the same uploaded batch and region -- `matting_evaluator`, `engine.eval_matting` unless given: (pred, gt, region) -> one
-    dict per image."""
+    dict per image.  trimap_radius: the trimap-free matting protocol as five more columns (TRIMAP_METRICS), the trimap made on the device from
+    the uploaded ground truth -- `trimap_evaluator`, `engine.eval_trimap` unless given: (pred, gt, radius, metric) -> one dict per image.
+    boundary_iou: Boundary IoU as one more column (BOUNDARY_METRICS, last) -- `boundary_evaluator`, `engine.eval_boundary_iou` unless given:
+    (pred, gt, ratio) -> one dict per image.  Neither goes with region_of; a header line of the text file states radius, metric and ratio."""
     import torch
     if mode not in ("dis", "matting"):
         raise ValueError(f"mask evaluation is for mode 'dis' or 'matting', got {mode!r}")
     if structure and region_of is not None:
         raise ValueError("structure scores are whole-image quantities: structure=True does not go with region_of")
-    names = list(MASK_METRICS) + (list(STRUCTURE_METRICS) if structure else []) + (list(MATTING_METRICS) if matting else [])
+    band_names, note = _band_options(trimap_radius, trimap_metric, boundary_iou, boundary_ratio, region_of)
+    names = list(MASK_METRICS) + (list(STRUCTURE_METRICS) if structure else []) + (list(MATTING_METRICS) if matting else []) + band_names
     if evaluator is None:
         from .engine import eval_mask as evaluator
     if structure and structure_evaluator is None:
         from .engine import eval_structure as structure_evaluator
     if matting and matting_evaluator is None:
         from .engine import eval_matting as matting_evaluator
+    if trimap_radius is not None and trimap_evaluator is None:
+        from .engine import eval_trimap as trimap_evaluator
+    if boundary_iou and boundary_evaluator is None:
+        from .engine import eval_boundary_iou as boundary_evaluator
     if prediction_dir is None:
         prediction_dir = output_dir
     if save_predictions and prediction_dir is None:
@@ -710,6 +754,17 @@ def infer_and_evaluate_masks(pipe, base_dir: str, samples: Sequence[Sequence[str
             more = matting_evaluator(pred[:, 0], gt_t, region_t)
             assert len(more) == len(group)
             metrics = [dict(m, **{k: s[k] for k in MATTING_METRICS}) for m, s in zip(metrics, more)]
+        if trimap_radius is not None:
+            try:
+                more = trimap_evaluator(pred[:, 0], gt_t, trimap_radius, trimap_metric)
+            except ValueError as e:
+                raise ValueError(f"{', '.join(smp[0] for (_, smp), _ in group)}: {e}") from None
+            assert len(more) == len(group)
+            metrics = [dict(m, **{k: s[k] for k in TRIMAP_METRICS}) for m, s in zip(metrics, more)]
+        if boundary_iou:
+            more = boundary_evaluator(pred[:, 0], gt_t, boundary_ratio)
+            assert len(more) == len(group)
+            metrics = [dict(m, **{k: s[k] for k in BOUNDARY_METRICS}) for m, s in zip(metrics, more)]
         for ((idx, _), _), m in zip(group, metrics):
             counts.append((idx, np.asarray(m["counts"])))
         if save_predictions:
@@ -724,7 +779,8 @@ def infer_and_evaluate_masks(pipe, base_dir: str, samples: Sequence[Sequence[str
     curve_sums = _all_reduce_sum(_sum_curves([c for _, c in counts]))
     result["max_f_dataset"] = _max_f_of_mean_curves(curve_sums, len(rows))
     if output_dir is not None and writer:
-        _write_mask_eval_files(output_dir, names, [(_mask_pred_name(smp[0], name_mode), vals) for _, smp, vals in rows], result, prediction_dir)
+        _write_mask_eval_files(output_dir, names, [(_mask_pred_name(smp[0], name_mode), vals) for _, smp, vals in rows], result, prediction_dir,
+                               note)
     return result
 
 

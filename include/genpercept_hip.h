@@ -22,6 +22,8 @@
  *   gp_seg_decode, gp_eval_seg
  *                     (no reference code: the trainer's evaluation branch is a TODO) palette decode and confusion-matrix scores of the seg
  *                       colour output against the RGB label image of column 6   src/dataset/base_dataset.py:333-346,366; run.py:449-455
+ *   gp_mask_band      (no reference code) the trimap of a ground-truth alpha (dilate(alpha != 0) - erode(alpha == 255)) and the inner boundary
+ *                       band of Boundary IoU, as region planes for gp_eval_mask
  *   gp_ensemble_gather, gp_ensemble_reduce
  *                     ensemble_depth's tensor half (the BFGS fit stays on the host)   genpercept/util/ensemble.py:43-205;
  *                                                                   genpercept_pipeline.py:289-298
@@ -402,6 +404,40 @@ gp_status gp_eval_seg(const void* pred, int pred_is_u8, const unsigned char* gt,
                       const unsigned char* palette /* [K][3] */, int K, int B, int H, int W, double* out /* [B][8 + K] */,
                       unsigned long long* counts_out /* [B][3 + K * K] or NULL */, unsigned char* labels_out /* [B][H][W] or NULL */,
                       void* workspace, long long workspace_bytes, void* stream);
+
+/* ---- trimap and boundary bands on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation; csrc/mask_band.hip) ----
+ * "Which pixels lie within reach of a set and within reach of its complement", exactly: the transition region of the trimap-free matting protocol
+ * (P3M / AIM tables: trimap = dilate(alpha != 0) - erode(alpha == 255)) and the inner boundary band of Boundary IoU (Cheng et al. 2021), as 0 / 255
+ * planes that gp_eval_mask / gp_eval_matting take as `region` or as maps.  eval_metrics.mask_band is the same definition on the host.
+ * a: uint8 [B][H][W] (a_is_u8 = 1) or fp32 [B][H][W] (a_is_u8 = 0), quantised first by gp_eval_mask's rule,
+ *   q = (unsigned char)(clamp(x, 0, 1) * 255.0f), NaN -> 0.
+ * Thresholds -1 <= lo < hi <= 256:  A = { a > lo },  Bc = { a < hi };  every pixel is in A or in Bc.  The matting trimap is lo = 0, hi = 255; a
+ *   binary ground truth g > 128 is lo = 128, hi = 129; a binarised prediction q >= 128 is lo = 127, hi = 128.
+ * d(p, S), over the pixels of S INSIDE the image: metric 0 the squared Euclidean distance min (dy^2 + dx^2), metric 1 the Chebyshev distance
+ *   min max(|dy|, |dx|); +inf when S is empty.
+ * border = 1: the outside of the image counts as Bc, so d(p, Bc) is additionally at most the distance to the nearest outside pixel: with
+ *   e = min(y + 1, x + 1, H - y, W - x), e^2 for metric 0 and e for metric 1.  border = 0: nothing lies outside (cv2's default for dilate and
+ *   erode alike).
+ * reach: an integer.  Metric 0: the squared radius R^2 (the disc dy^2 + dx^2 <= R^2; for a real radius pass floor(radius^2)); metric 1: the radius d.
+ * Per pixel:  band = d(p, A) <= reach and d(p, Bc) <= reach;  fg side = d(p, Bc) > reach (implies a >= hi);  bg side = d(p, A) > reach (implies
+ *   a <= lo);  inner = p in A and d(p, Bc) <= reach.  band, fg and bg partition the image.  Planes are 0 / 255; trimap is 0 / 128 / 255 for
+ *   bg / band / fg.
+ * band(metric 1, border 0) is cv2 dilate - erode with a MORPH_RECT kernel of size 2 d + 1, exactly; inner(metric 1, border 1) is Boundary IoU's
+ *   "pad with 0, erode d times with 3 x 3, subtract".  cv2's MORPH_ELLIPSE is NOT the disc of metric 0, so numbers differ slightly from tables
+ *   that were produced with an elliptical kernel.
+ * band_out, fg_out, bg_out, inner_out, trimap_out: uint8 [B][H][W] each, or NULL; at least one is given.
+ * Integers only, no atomics, nothing read back; two kernel launches on `stream` for every B (a column pass that leaves one 32-bit word per
+ * pixel in the workspace, a row pass).  Every pixel -> thread assignment depends on H, W and reach alone: an image's planes are bitwise the
+ * same from call to call and for every batch it is part of.  workspace: DEVICE scratch of at least the workspace entry's byte count (8-byte
+ * aligned; 4 bytes per pixel), free again once the stream has passed the call.
+ * GP_ERR_INVALID before any HIP call: null a / workspace, all five outputs null, B, H or W < 1, B > 65535, H * W > 2^31 - 1, a_is_u8, metric or
+ * border outside 0..1, lo < -1, hi > 256 or lo >= hi, reach < 0, reach > 2^24 (metric 0) or reach > 4096 (metric 1), a float `a` not 4-byte
+ * aligned, workspace not 8-byte aligned, workspace_bytes too small. */
+long long gp_mask_band_workspace(int B, int H, int W);        /* bytes; 0 for B, H or W < 1; proportional to B; multiple of 8 */
+gp_status gp_mask_band(const void* a, int a_is_u8, int B, int H, int W, int lo, int hi, int metric, int reach, int border,
+                       unsigned char* band_out, unsigned char* fg_out, unsigned char* bg_out, unsigned char* inner_out,
+                       unsigned char* trimap_out /* each [B][H][W] or NULL, at least one non-NULL */, void* workspace,
+                       long long workspace_bytes, void* stream);
 
 /* ---- test-time ensembling on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation, no atomics; csrc/ensemble.hip) ----
  * The tensor half of ensemble_depth (genpercept/util/ensemble.py:43-205, called at genpercept_pipeline.py:289-298) for the E members of each of

@@ -1,4 +1,4 @@
-"""Time the device depth (or, with --normals, surface-normal; with --masks, dis / matting; with --structure, dis structure-score; with --matting, matting Grad / Conn; with --seg, seg palette decode + confusion matrix) evaluation against the host evaluation, and the batched device loop on the tiny pipeline.
+"""Time the device depth (or, with --normals, surface-normal; with --masks, dis / matting; with --structure, dis structure-score; with --matting, matting Grad / Conn; with --seg, seg palette decode + confusion matrix; with --band, trimap / boundary bands) evaluation against the host evaluation, and the batched device loop on the tiny pipeline.
 
   python tools/eval_bench.py --out profiles/<name>.json
 
@@ -46,6 +46,15 @@
    events around `iters` back-to-back calls after a warm-up, for the C entry on preallocated buffers and for `engine.eval_seg` itself (which
    allocates, copies the result down and synchronises), against `eval_metrics.seg_metrics` on the same arrays on the host (wall clock, one
    run).  The two sides' values are compared on the spot (bit-equal).  The result carries the shader clock sampled meanwhile and the build id.
+
+  python tools/eval_bench.py --band --out profiles/<name>.json
+
+8. `--band` (instead of 1 and 2): the `gp_mask_band` entry behind `engine.mask_band` (a column pass and a row pass) and the two evaluators
+   composed from it, `engine.eval_trimap` (radius 25, Euclidean) and `engine.eval_boundary_iou` (the 2 % Chebyshev band), at 4 x 480 x 640 and
+   1 x 2048 x 2048 on the alpha-like input of `--matting`: device events around `iters` back-to-back calls after a warm-up, against
+   `eval_metrics.mask_band` / `trimap_metrics` / `boundary_iou` on the same arrays on the host (wall clock, one run).  Planes and values are
+   compared on the spot (bit-equal).  The band call's bytes -- the 1 + planes per pixel it has to move, and the 18 + planes it does move with
+   its scratch word -- are set against the device-to-device copy bandwidth measured in the same process.  `--no-host` skips the host route.
 Needs a GPU; there is no CPU fall-back."""
 import argparse
 import json
@@ -427,6 +436,62 @@ def bench_eval_seg(b, h, w, K, iters, host):
     return res
 
 
+def bench_band(b, h, w, iters, host, copy_gb_per_s):
+    from genpercept_amd import engine as ge
+    from genpercept_amd import eval_metrics as em
+    d = torch.device("cuda", 0)
+    lib = ge.load_library()
+    pred, gt = matting_case(b, h, w, 5)
+    tp, tg = (torch.from_numpy(x).to(d) for x in (pred, gt))
+    nbytes = int(lib.gp_mask_band_workspace(b, h, w))
+    ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=d)
+    planes = torch.empty((3, b, h, w), dtype=torch.uint8, device=d)
+    stream = int(torch.cuda.current_stream(d).cuda_stream)
+    d_b = em.boundary_reach(h, w, 0.02)
+    settings = [dict(name="trimap of the alpha: disc of radius 25", src=tg, lo=0, hi=255, metric=0, reach=625, border=0, want=("band", "fg", "bg")),
+                dict(name=f"inner band of the mask: square of radius {d_b} (2 % of the diagonal), border", src=tg, lo=128, hi=129, metric=1, reach=d_b,
+                     border=1, want=("inner",))]
+    rows = []
+    for st in settings:
+        outs = [planes[st["want"].index(k)].data_ptr() if k in st["want"] else None for k in ge.BAND_PLANES]
+
+        def entry():
+            rc = lib.gp_mask_band(st["src"].data_ptr(), 1, b, h, w, st["lo"], st["hi"], st["metric"], st["reach"], st["border"], *outs, ws.data_ptr(), nbytes,
+                                  stream)
+            assert rc == ge.GP_OK, rc
+
+        entry_ms = time_events(entry, iters)
+        metric = ("euclidean", "chebyshev")[st["metric"]]
+        call_ms = time_events(lambda: ge.mask_band(st["src"], st["lo"], st["hi"], st["reach"], metric, bool(st["border"]), want=st["want"]), iters)
+        got = {k: v.cpu().numpy() for k, v in ge.mask_band(st["src"], st["lo"], st["hi"], st["reach"], metric, bool(st["border"]), want=st["want"]).items()}
+        must, moved = (1 + len(st["want"])) * b * h * w, (18 + len(st["want"])) * b * h * w
+        row = dict(setting=st["name"], metric=metric, reach=st["reach"], planes=list(st["want"]), gp_mask_band_ms_per_call=entry_ms,
+                   engine_mask_band_ms_per_call=call_ms, launches_per_call=2, workspace_bytes=nbytes, bytes_needed=must, bytes_moved=moved,
+                   needed_gb_per_s=must / entry_ms / 1e6, moved_gb_per_s=moved / entry_ms / 1e6, copy_gb_per_s=copy_gb_per_s,
+                   needed_bytes_alone_ms=must / copy_gb_per_s / 1e6, band_fraction_image_0=float((got[st["want"][0]][0] == 255).mean()))
+        if host:
+            t0 = time.perf_counter()
+            ref = [em.mask_band(gt[i], st["lo"], st["hi"], st["reach"], st["metric"], st["border"]) for i in range(b)]
+            host_ms = (time.perf_counter() - t0) * 1e3
+            assert all(np.array_equal(got[k][i], ref[i][k]) for k in st["want"] for i in range(b))
+            row.update(host_mask_band_ms=host_ms, host_runs=1, host_over_engine_call=host_ms / call_ms, planes_equal_host=True)
+        rows.append(row)
+    res = dict(shape=[b, h, w], input="alpha", device_iters=iters, mask_band=rows)
+    for name, dev, ref_of in (("eval_trimap", lambda: ge.eval_trimap(tp, tg, 25, "euclidean"), lambda i: em.trimap_metrics(pred[i], gt[i], 25, "euclidean")),
+                              ("eval_boundary_iou", lambda: ge.eval_boundary_iou(tp, tg, 0.02), lambda i: em.boundary_iou(pred[i], gt[i], 0.02))):
+        ms = time_events(dev, iters)
+        metrics = dev()
+        row = dict(engine_ms_per_call=ms, values_image_0=metrics[0])
+        if host:
+            t0 = time.perf_counter()
+            ref = [ref_of(i) for i in range(b)]
+            host_ms = (time.perf_counter() - t0) * 1e3
+            assert metrics == ref, (name, metrics, ref)
+            row.update(host_ms=host_ms, host_runs=1, host_over_engine_call=host_ms / ms, values_equal_host=True)
+        res[name] = row
+    return res
+
+
 def bench_loop(n_images, batch_sizes, repeats):
     from PIL import Image
     from genpercept_amd import GenPerceptPipeline
@@ -482,11 +547,19 @@ def main():
     ap.add_argument("--structure", action="store_true", help="time gp_eval_structure against structure_metrics instead")
     ap.add_argument("--matting", action="store_true", help="time gp_eval_matting against matting_metrics instead")
     ap.add_argument("--seg", action="store_true", help="time gp_eval_seg against seg_metrics instead")
-    ap.add_argument("--no-host", action="store_true", help="with --structure, --matting or --seg: the device calls alone")
+    ap.add_argument("--band", action="store_true", help="time gp_mask_band, eval_trimap and eval_boundary_iou against their host routes instead")
+    ap.add_argument("--no-host", action="store_true", help="with --structure, --matting, --seg or --band: the device calls alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU")
-    if a.seg:
+    if a.band:
+        import bench
+        bw = copy_bandwidth(torch.device("cuda", 0))
+        with bench.ClockPowerSampler("cuda:0") as clock:
+            rows = [bench_band(b, h, w, a.iters, not a.no_host, bw) for (b, h, w) in ((4, 480, 640), (1, 2048, 2048))]
+        res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box", build_id=bench.source_build_id(), clock=clock.summary(),
+                   copy_gb_per_s=bw, band=rows)
+    elif a.seg:
         import bench
         with bench.ClockPowerSampler("cuda:0") as clock:
             rows = [bench_eval_seg(b, h, w, K, a.iters, not a.no_host) for (b, h, w, K) in ((4, 480, 640, 19), (4, 480, 640, 150), (1, 2048, 2048, 150))]
@@ -509,7 +582,7 @@ def main():
                    eval_normal=[bench_eval_normal(4, 480, 640, a.iters, 3), bench_eval_normal(1, 4032, 6048, a.iters, 1)])
     else:
         res = dict(device=torch.cuda.get_device_name(0), eval_depth=[bench_eval(1, 4032, 6048, a.iters, 1), bench_eval(4, 480, 640, a.iters, 3)])
-    if not a.skip_loop and not a.normals and not a.masks and not a.structure and not a.matting and not a.seg:
+    if not a.skip_loop and not a.normals and not a.masks and not a.structure and not a.matting and not a.seg and not a.band:
         res["infer_and_evaluate"] = bench_loop(16, (1, 4), 3)
     text = json.dumps(res, indent=1)
     print(text)
