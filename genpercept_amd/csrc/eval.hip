@@ -20,7 +20,7 @@
 #include <stdint.h>
 
 #include "../../include/genpercept_hip.h"
-#include "eval_common.h"  // EV_THREADS, eval_blocks, block_reduce_store, sum_slabs, quantise8
+#include "eval_common.h"
 
 // The host's numpy code has no fused multiply-adds, so nothing below may be contracted into one.  The float32 recipe is written as plain
 // `*`, `+`, `/` under this pragma: the __fmul_rn / __fadd_rn wrappers are plain operators compiled under the header's own (contracting)
@@ -492,39 +492,25 @@ __global__ __launch_bounds__(EN_PICK_THREADS) void normal_pick_kernel(const unsi
 //            is one fixed sequence of correctly rounded float64 *, /, + on the integers (this file contracts nothing), so the host's float64
 //            restatement is bit-equal.
 // Two launches for every B; nothing is read back.
-constexpr int EM_BINS = 256;
+constexpr int EM_BINS = EV_BINS;
 constexpr int EM_NSUM = 4;                        // n, sum_q, sad, sse
 constexpr int EM_COUNTS = EM_NSUM + 2 * EM_BINS;  // a row of counts_out: the four sums, hist_bg, hist_fg
 constexpr int EM_OUT = 10;                        // n, n_fg, mae, mse, sad, max_f, mean_f, adp_f, iou, t_max
 constexpr int EM_UNROLL = 2;                      // quads in flight per lane (4: the ballot masks of an iteration no longer fit the SGPRs)
-constexpr int EM_FIN_THREADS = 1024;              // the finaliser: EM_FIN_LANES threads cover one slab's bins, four each;
-constexpr int EM_FIN_LANES = 2 * EM_BINS / 4;     // EM_FIN_GROUPS slabs at a time
-constexpr int EM_FIN_GROUPS = EM_FIN_THREADS / EM_FIN_LANES;
 // a slab: the four sums as 64-bit, the 512 bins as 32-bit (an image has fewer than 2^31 pixels)
-constexpr long long EM_SLAB_BYTES = EM_NSUM * 8 + 2 * EM_BINS * 4;
+constexpr long long EM_SLAB_BYTES = class_slab_bytes(EM_NSUM);
 
 struct MaskAcc {
-    unsigned n = 0, q4 = 0, ad4 = 0, sq4 = 0;        // per lane; q4, ad4, sq4: the sums of at most four pixels, flushed into the 64-bit ones
-    unsigned long long sum_q = 0, sad = 0, sse = 0;  // per lane
-    unsigned sat[4] = {0, 0, 0, 0};                  // per WAVE (uniform): q == 0 & bg, q == 0 & fg, q == 255 & bg, q == 255 & fg
-    // one pixel; every lane of the wave calls this together (`in`: the pixel exists and is inside the region); hist: this wave's [2][EM_BINS]
-    __device__ __forceinline__ void add(unsigned q, unsigned g, bool in, unsigned* hist) {
-        const bool fg = g > 128u;
+    unsigned n = 0, q4 = 0, ad4 = 0, sq4 = 0;  // per lane; q4, ad4, sq4: the sums of at most four pixels, flushed into the 64-bit ones
+    u64 sum_q = 0, sad = 0, sse = 0;           // per lane
+    // one pixel; every lane of the wave calls this together (`in`: the pixel exists and is inside the region)
+    __device__ __forceinline__ void add(unsigned q, unsigned g, bool in, ClassHist& hist) {
         const unsigned d = in ? max(q, g) - min(q, g) : 0u;
         n += in ? 1u : 0u;
         q4 += in ? q : 0u;
         ad4 += d;
         sq4 += d * d;
-#ifndef GP_MASK_PLAIN_ATOMICS
-        const bool lo = in && q == 0u, hi = in && q == 255u;
-        sat[0] += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(lo && !fg));
-        sat[1] += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(lo && fg));
-        sat[2] += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(hi && !fg));
-        sat[3] += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(hi && fg));
-        if (in && !lo && !hi) atomicAdd(&hist[(fg ? EM_BINS : 0) + q], 1u);
-#else  // the A/B form of DESIGN section 5: every pixel through the atomics
-        if (in) atomicAdd(&hist[(fg ? EM_BINS : 0) + q], 1u);
-#endif
+        hist.add(q, g > 128u, in);
     }
     __device__ __forceinline__ void flush() {
         sum_q += q4, sad += ad4, sse += sq4;
@@ -539,39 +525,31 @@ struct MaskAcc {
 template <bool U8>
 __global__ __launch_bounds__(EV_THREADS) void mask_count_kernel(const void* __restrict__ pred_v, const unsigned char* __restrict__ gt,
                                                                 const unsigned char* __restrict__ region, long long hw, char* __restrict__ ws) {
-    __shared__ unsigned s_h[EV_WAVES][2 * EM_BINS];
-    __shared__ unsigned long long s_part[EV_WAVES][EM_NSUM];
     const long long b = blockIdx.y;
-    const float* predf = U8 ? nullptr : (const float*)pred_v + b * hw;
-    const unsigned char* predb = U8 ? (const unsigned char*)pred_v + b * hw : nullptr;
+    const Pred8<U8> pred(pred_v, b * hw);
     gt += b * hw;
     if (region) region += b * hw;
-    for (int k = threadIdx.x; k < EV_WAVES * 2 * EM_BINS; k += EV_THREADS) (&s_h[0][0])[k] = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned* hist = s_h[wave];
+    ClassHist hist;
 
-    long long head = (long long)((4 - ((uintptr_t)gt & 3)) & 3);
-    const bool vec = head <= hw && (U8 ? ((uintptr_t)(predb + head) & 3) == 0 : ((uintptr_t)(predf + head) & 15) == 0) &&
-                     (!region || ((uintptr_t)(region + head) & 3) == 0);
-    if (!vec) head = hw;
-    const long long nq = (hw - head) / 4, tail0 = head + 4 * nq, ns = head + (hw - tail0);
+    const long long head = (long long)((4 - ((uintptr_t)gt & 3)) & 3);
+    const bool vec = head <= hw && pred.quad_aligned(head) && (!region || ((uintptr_t)(region + head) & 3) == 0);
+    const QuadSplit sp(hw, vec ? head : hw);
     const long long stride = (long long)gridDim.x * EV_THREADS;
     MaskAcc acc;
     // (both loops have workgroup-uniform bounds: the ballots inside add() see whole waves)
-    for (long long q0 = (long long)blockIdx.x * EV_THREADS; q0 < nq; q0 += EM_UNROLL * stride) {
+    for (long long q0 = (long long)blockIdx.x * EV_THREADS; q0 < sp.nq; q0 += EM_UNROLL * stride) {
         float4 pf[EM_UNROLL];
         unsigned pb[EM_UNROLL], g4[EM_UNROLL], r4[EM_UNROLL];
         bool act[EM_UNROLL];
 #pragma unroll
         for (int u = 0; u < EM_UNROLL; ++u) {
             const long long q = q0 + u * stride + threadIdx.x;
-            act[u] = q < nq;
+            act[u] = q < sp.nq;
             pf[u] = make_float4(0.f, 0.f, 0.f, 0.f), pb[u] = 0, g4[u] = 0, r4[u] = 0x01010101u;
             if (act[u]) {
-                const long long i0 = head + 4 * q;
-                if (U8) pb[u] = *reinterpret_cast<const unsigned*>(predb + i0);
-                else pf[u] = *reinterpret_cast<const float4*>(predf + i0);
+                const long long i0 = sp.quad(q);
+                if (U8) pb[u] = *reinterpret_cast<const unsigned*>(pred.u + i0);
+                else pf[u] = *reinterpret_cast<const float4*>(pred.f + i0);
                 g4[u] = *reinterpret_cast<const unsigned*>(gt + i0);
                 if (region) r4[u] = *reinterpret_cast<const unsigned*>(region + i0);
             }
@@ -587,118 +565,43 @@ __global__ __launch_bounds__(EV_THREADS) void mask_count_kernel(const void* __re
             acc.flush();
         }
     }
-    for (long long k0 = (long long)blockIdx.x * EV_THREADS; k0 < ns; k0 += stride) {
+    for (long long k0 = (long long)blockIdx.x * EV_THREADS; k0 < sp.ns; k0 += stride) {
         const long long k = k0 + threadIdx.x;
-        const bool act = k < ns;
+        const bool act = k < sp.ns;
         unsigned q = 0, g = 0;
         bool in = false;
         if (act) {
-            const long long i = k < head ? k : tail0 + (k - head);
-            q = U8 ? (unsigned)predb[i] : quantise8(predf[i]);
+            const long long i = sp.scalar(k);
+            q = pred[i];
             g = gt[i];
             in = region ? region[i] != 0 : true;
         }
         acc.add(q, g, in, hist);
         acc.flush();
     }
-#ifndef GP_MASK_PLAIN_ATOMICS
-    if (lane == 0) {
-        atomicAdd(&hist[0], acc.sat[0]);
-        atomicAdd(&hist[EM_BINS], acc.sat[1]);
-        atomicAdd(&hist[EM_BINS - 1], acc.sat[2]);
-        atomicAdd(&hist[2 * EM_BINS - 1], acc.sat[3]);
-    }
-#endif
-    unsigned long long v[EM_NSUM] = {acc.n, acc.sum_q, acc.sad, acc.sse};
-#pragma unroll
-    for (int k = 0; k < EM_NSUM; ++k) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < EM_NSUM; ++k) s_part[wave][k] = v[k];
-    }
-    __syncthreads();
+    hist.flush();
+    u64 v[EM_NSUM] = {acc.n, acc.sum_q, acc.sad, acc.sse};
+    const u64 a = block_sum(v);  // (its barrier: every wave's histogram is complete)
     char* slab = ws + (b * gridDim.x + blockIdx.x) * EM_SLAB_BYTES;
-    if (threadIdx.x < EM_NSUM) {
-        unsigned long long a = s_part[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < EV_WAVES; ++w) a += s_part[w][threadIdx.x];
-        reinterpret_cast<unsigned long long*>(slab)[threadIdx.x] = a;
-    }
-    unsigned* slab_h = reinterpret_cast<unsigned*>(slab + EM_NSUM * 8);
-    for (int k = threadIdx.x; k < 2 * EM_BINS; k += EV_THREADS) {
-        unsigned a = s_h[0][k];
-#pragma unroll
-        for (int w = 1; w < EV_WAVES; ++w) a += s_h[w][k];
-        slab_h[k] = a;
-    }
+    if (threadIdx.x < EM_NSUM) reinterpret_cast<u64*>(slab)[threadIdx.x] = a;
+    hist.store(reinterpret_cast<unsigned*>(slab + EM_NSUM * 8));
 }
 
-// one workgroup per image.  Adding the slabs is the long part (512 slabs of 2 KB for a 24-megapixel image, pulled by one CU), so it runs with
-// 1024 threads and batched loads: 128 threads cover the 512 bins of a slab, four bins each, eight slabs at a time, eight such loads in flight
-// per thread; wave 0 adds the four sums.  Then thread i < 512 owns bin i, and thread t < 256 threshold t.
-__global__ __launch_bounds__(EM_FIN_THREADS) void mask_finalise_kernel(const char* __restrict__ ws, int nblk, double* __restrict__ out,
-                                                                       unsigned long long* __restrict__ counts_out) {
-    __shared__ unsigned long long s_cnt[EM_FIN_GROUPS][2 * EM_BINS], s_sum[EM_NSUM];
+// one workgroup per image: sum_class_slabs, then thread i < 512 owns bin i, and thread t < 256 threshold t.
+__global__ __launch_bounds__(EV_FIN_THREADS) void mask_finalise_kernel(const char* __restrict__ ws, int nblk, double* __restrict__ out,
+                                                                       u64* __restrict__ counts_out) {
+    __shared__ u64 s_cnt[EV_FIN_GROUPS][2 * EM_BINS], s_sum[EM_NSUM];
     __shared__ double s_f[EM_BINS];
-    unsigned long long* s_bg = s_cnt[0];
-    unsigned long long* s_fg = s_cnt[0] + EM_BINS;
+    u64* s_bg = s_cnt[0];
+    u64* s_fg = s_cnt[0] + EM_BINS;
     const long long b = blockIdx.x;
     const int t = threadIdx.x & (EM_BINS - 1);
     const bool first = threadIdx.x < EM_BINS, owner = threadIdx.x < 2 * EM_BINS;
-    const char* base = ws + b * nblk * EM_SLAB_BYTES;
-    {
-        const int l = threadIdx.x % EM_FIN_LANES, grp = threadIdx.x / EM_FIN_LANES;
-        const char* mine = base + EM_NSUM * 8 + 16 * l;  // bins 4 l .. 4 l + 3 of a slab (8-byte aligned, like the workspace)
-        unsigned long long c[4] = {0, 0, 0, 0};
-        int j = grp;
-        for (; j + 7 * EM_FIN_GROUPS < nblk; j += 8 * EM_FIN_GROUPS) {
-            uint2 lo[8], hi[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const uint2* h = reinterpret_cast<const uint2*>(mine + (long long)(j + u * EM_FIN_GROUPS) * EM_SLAB_BYTES);
-                lo[u] = h[0], hi[u] = h[1];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) c[0] += lo[u].x, c[1] += lo[u].y, c[2] += hi[u].x, c[3] += hi[u].y;
-        }
-        for (; j < nblk; j += EM_FIN_GROUPS) {
-            const uint2* h = reinterpret_cast<const uint2*>(mine + (long long)j * EM_SLAB_BYTES);
-            const uint2 lo = h[0], hi = h[1];
-            c[0] += lo.x, c[1] += lo.y, c[2] += hi.x, c[3] += hi.y;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s_cnt[grp][4 * l + k] = c[k];
-    }
-    if (threadIdx.x < 64) {
-        unsigned long long a[EM_NSUM] = {0, 0, 0, 0};
-        for (int j = threadIdx.x; j < nblk; j += 64) {
-            const unsigned long long* sl = reinterpret_cast<const unsigned long long*>(base + (long long)j * EM_SLAB_BYTES);
-#pragma unroll
-            for (int k = 0; k < EM_NSUM; ++k) a[k] += sl[k];
-        }
-#pragma unroll
-        for (int k = 0; k < EM_NSUM; ++k) {
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) a[k] += __shfl_down(a[k], off, 64);
-        }
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int k = 0; k < EM_NSUM; ++k) {
-                s_sum[k] = a[k];
-                if (counts_out) counts_out[b * EM_COUNTS + k] = a[k];
-            }
-        }
-    }
-    __syncthreads();
+    const u64 bin = sum_class_slabs<EM_NSUM>(ws + b * nblk * EM_SLAB_BYTES, nblk, s_cnt, s_sum);
+    if (counts_out && threadIdx.x < EM_NSUM) counts_out[b * EM_COUNTS + threadIdx.x] = s_sum[threadIdx.x];
     if (owner) {  // bin threadIdx.x of [hist_bg | hist_fg]
-        unsigned long long a = s_cnt[0][threadIdx.x];
-#pragma unroll
-        for (int g = 1; g < EM_FIN_GROUPS; ++g) a += s_cnt[g][threadIdx.x];
-        if (counts_out) counts_out[b * EM_COUNTS + EM_NSUM + threadIdx.x] = a;
-        s_cnt[0][threadIdx.x] = a;  // (its own column)
+        if (counts_out) counts_out[b * EM_COUNTS + EM_NSUM + threadIdx.x] = bin;
+        s_cnt[0][threadIdx.x] = bin;  // (its own column)
     }
     __syncthreads();
     for (int off = 1; off < EM_BINS; off <<= 1) {  // inclusive suffix sums inside each histogram: s_x[t] = sum_{v >= t} hist_x[v]
@@ -758,9 +661,9 @@ long long gp_eval_depth_workspace(int B, int H, int W) {
 gp_status gp_eval_depth(const float* pred, const float* gt, const unsigned char* mask, int B, int H, int W, int alignment, int fit_cols,
                         float fit_inv_scale, float min_depth, float max_depth, double* out, void* workspace, long long workspace_bytes, void* stream) {
     if (!pred || !gt || !mask || !out || !workspace) return GP_ERR_INVALID;
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) return GP_ERR_INVALID;
+    if (!eval_dims_ok(B, H, W)) return GP_ERR_INVALID;
     if (alignment < 0 || alignment > 2 || fit_cols < 0 || fit_cols > W || (fit_cols > 0 && !(fit_inv_scale > 0.f))) return GP_ERR_INVALID;
-    if (workspace_bytes < gp_eval_depth_workspace(B, H, W) || ((uintptr_t)workspace & 7) != 0 || ((uintptr_t)out & 7) != 0) return GP_ERR_INVALID;
+    if (workspace_bytes < gp_eval_depth_workspace(B, H, W) || !eval_aligned8(workspace, out)) return GP_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     double* ws = (double*)workspace;
     const int nblk = eval_blocks((long long)H * W);
@@ -780,9 +683,9 @@ long long gp_eval_normal_workspace(int B, int H, int W) {
 gp_status gp_eval_normal(const float* pred, const float* gt, const unsigned char* mask, int B, int H, int W, int decode, double* out,
                          double* angles_out, void* workspace, long long workspace_bytes, void* stream) {
     if (!pred || !gt || !out || !workspace) return GP_ERR_INVALID;
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) return GP_ERR_INVALID;
+    if (!eval_dims_ok(B, H, W)) return GP_ERR_INVALID;
     if (decode < 0 || decode > 3 || (!mask && (decode & 2) != 0)) return GP_ERR_INVALID;
-    if ((((uintptr_t)workspace | (uintptr_t)out | (uintptr_t)angles_out) & 7) != 0) return GP_ERR_INVALID;
+    if (!eval_aligned8(workspace, out, angles_out)) return GP_ERR_INVALID;
     const long long hw = (long long)H * W;
     const NormalWs w = normal_ws(B, hw);
     if (workspace_bytes < w.total) return GP_ERR_INVALID;
@@ -811,17 +714,16 @@ long long gp_eval_mask_workspace(int B, int H, int W) {
 gp_status gp_eval_mask(const void* pred, int pred_is_u8, const unsigned char* gt, const unsigned char* region, int B, int H, int W, double* out,
                        unsigned long long* counts_out, void* workspace, long long workspace_bytes, void* stream) {
     if (!pred || !gt || !out || !workspace) return GP_ERR_INVALID;
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) return GP_ERR_INVALID;
-    if (pred_is_u8 < 0 || pred_is_u8 > 1 || (!pred_is_u8 && ((uintptr_t)pred & 3) != 0)) return GP_ERR_INVALID;
-    if ((((uintptr_t)workspace | (uintptr_t)out | (uintptr_t)counts_out) & 7) != 0) return GP_ERR_INVALID;
+    if (!eval_dims_ok(B, H, W)) return GP_ERR_INVALID;
+    if (!eval_pred_ok(pred, pred_is_u8) || !eval_aligned8(workspace, out, counts_out)) return GP_ERR_INVALID;
     if (workspace_bytes < gp_eval_mask_workspace(B, H, W)) return GP_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const long long hw = (long long)H * W;
     const int nblk = eval_blocks(hw);
     char* ws = (char*)workspace;
-    if (pred_is_u8) hipLaunchKernelGGL(mask_count_kernel<true>, dim3(nblk, B), dim3(EV_THREADS), 0, s, pred, gt, region, hw, ws);
-    else hipLaunchKernelGGL(mask_count_kernel<false>, dim3(nblk, B), dim3(EV_THREADS), 0, s, pred, gt, region, hw, ws);
-    hipLaunchKernelGGL(mask_finalise_kernel, dim3(B), dim3(EM_FIN_THREADS), 0, s, (const char*)ws, nblk, out, counts_out);
+    const auto count = pred_is_u8 ? mask_count_kernel<true> : mask_count_kernel<false>;
+    hipLaunchKernelGGL(count, dim3(nblk, B), dim3(EV_THREADS), 0, s, pred, gt, region, hw, ws);
+    hipLaunchKernelGGL(mask_finalise_kernel, dim3(B), dim3(EV_FIN_THREADS), 0, s, (const char*)ws, nblk, out, counts_out);
     return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
 }
 

@@ -32,8 +32,6 @@
 
 namespace {
 
-typedef unsigned long long u64;
-
 constexpr int MT_OUT = 4;                            // n, grad, conn, grad_sum
 constexpr int MT_LEVELS = 10;
 constexpr int MT_COUNTS = 2 + MT_LEVELS + 1;         // counts_out: n, conn_num, the counts of the levels 0..10
@@ -89,8 +87,7 @@ __global__ __launch_bounds__(EV_THREADS) void mt_prep_kernel(const void* __restr
                                                              unsigned* __restrict__ range, u64* __restrict__ info) {
     __shared__ unsigned s_r[EV_WAVES][4];
     const long long b = blockIdx.y;
-    const float* predf = U8 ? nullptr : (const float*)pred_v + b * hw;
-    const unsigned char* predb = U8 ? (const unsigned char*)pred_v + b * hw : nullptr;
+    const Pred8<U8> pred(pred_v, b * hw);
     gt += b * hw, qbuf += b * hwp, mbuf += b * hwp, level += b * hwp, parent += b * hwp;
     if (blockIdx.x == 0 && threadIdx.x < MT_INFO) info[b * MT_INFO + threadIdx.x] = 0;
     unsigned r[4] = {255u, 0u, 255u, 0u};  // min q, max q, min g, max g
@@ -102,7 +99,7 @@ __global__ __launch_bounds__(EV_THREADS) void mt_prep_kernel(const void* __restr
         const bool in = i < hw;
         unsigned m = 0;
         if (in) {
-            const unsigned q = U8 ? (unsigned)predb[i] : quantise8(predf[i]);
+            const unsigned q = pred[i];
             const unsigned g = gt[i];
             m = q < g ? q : g;
             qbuf[i] = (unsigned char)q;
@@ -328,8 +325,7 @@ __global__ __launch_bounds__(EV_THREADS) void mt_conn_kernel(const unsigned char
 #pragma unroll
         for (int l = 0; l <= MT_LEVELS; ++l) cnt[l] += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(lev == l));
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) n += __shfl_down(n, off, 64), num += __shfl_down(num, off, 64);
+    n = wave_sum(n), num = wave_sum(num);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) {
         s_part[wave][0] = n, s_part[wave][1] = num;
@@ -460,9 +456,8 @@ gp_status gp_eval_matting(const void* pred, int pred_is_u8, const unsigned char*
                           unsigned long long* counts_out, unsigned char* level_out, double* grad_map_out, void* workspace, long long workspace_bytes,
                           void* stream) {
     if (!pred || !gt || !out || !workspace) return GP_ERR_INVALID;
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) return GP_ERR_INVALID;
-    if (pred_is_u8 < 0 || pred_is_u8 > 1 || (!pred_is_u8 && ((uintptr_t)pred & 3) != 0)) return GP_ERR_INVALID;
-    if ((((uintptr_t)workspace | (uintptr_t)out | (uintptr_t)counts_out | (uintptr_t)grad_map_out) & 7) != 0) return GP_ERR_INVALID;
+    if (!eval_dims_ok(B, H, W) || !eval_pred_ok(pred, pred_is_u8)) return GP_ERR_INVALID;
+    if (!eval_aligned8(workspace, out, counts_out, grad_map_out)) return GP_ERR_INVALID;
     const MatWs w = mat_ws(B, H, W);
     if (workspace_bytes < w.total) return GP_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
@@ -479,8 +474,8 @@ gp_status gp_eval_matting(const void* pred, int pred_is_u8, const unsigned char*
     unsigned* root = (unsigned*)(base + w.root);
     double4* rows = (double4*)(base + w.rows);
     const dim3 pix((unsigned)((hw + EV_THREADS - 1) / EV_THREADS), B), cnt((unsigned)((hw + MT_CNT_THREADS - 1) / MT_CNT_THREADS), B);
-    if (pred_is_u8) hipLaunchKernelGGL(mt_prep_kernel<true>, dim3(w.nblk, B), dim3(EV_THREADS), 0, s, pred, gt, (unsigned)W, hw, w.hwp, qbuf, mbuf, level, parent, range, info);
-    else hipLaunchKernelGGL(mt_prep_kernel<false>, dim3(w.nblk, B), dim3(EV_THREADS), 0, s, pred, gt, (unsigned)W, hw, w.hwp, qbuf, mbuf, level, parent, range, info);
+    const auto prep = pred_is_u8 ? mt_prep_kernel<true> : mt_prep_kernel<false>;
+    hipLaunchKernelGGL(prep, dim3(w.nblk, B), dim3(EV_THREADS), 0, s, pred, gt, (unsigned)W, hw, w.hwp, qbuf, mbuf, level, parent, range, info);
     hipLaunchKernelGGL(mt_range_kernel, dim3(B), dim3(64), 0, s, (const unsigned*)range, w.nblk, info);
     for (int k = MT_LEVELS; k >= 1; --k) {
         hipLaunchKernelGGL(mt_union_kernel, pix, dim3(EV_THREADS), 0, s, (const unsigned char*)mbuf, parent, size, (const unsigned*)root, level,

@@ -30,8 +30,6 @@
 
 namespace {
 
-typedef unsigned long long u64;
-
 constexpr int SG_MAX_K = 192;   // K * K * 4 bytes of LDS counters: 147456 of the CU's 163840
 constexpr int SG_NSUM = 3;      // n, n_void, sum_d in front of the matrix
 constexpr int SG_OUT = 8;       // n, n_void, pixel_acc, mean_acc, miou, fwiou, colour_rmse, n_classes in front of iou[K]
@@ -79,28 +77,22 @@ __device__ __forceinline__ void seg_st4(unsigned char* p, bool aligned, unsigned
 // The prediction of one image: three planes hw apart, floats (quantised here) or bytes.
 template <bool U8>
 struct SegPred {
-    const float* f;
-    const unsigned char* u;
+    Pred8<U8> p;  // plane c, pixel i: element c * hw + i
     long long hw;
-    bool al[3];  // plane c is vector-aligned at pixel `head` (16 bytes for floats, 4 for bytes)
-    __device__ __forceinline__ SegPred(const void* pred, long long b, long long hw_, long long head) : hw(hw_) {
-        f = U8 ? nullptr : (const float*)pred + b * 3 * hw_;
-        u = U8 ? (const unsigned char*)pred + b * 3 * hw_ : nullptr;
+    bool al[3];   // plane c is vector-aligned at pixel `head`
+    __device__ __forceinline__ SegPred(const void* pred, long long b, long long hw_, long long head) : p(pred, b * 3 * hw_), hw(hw_) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) al[c] = U8 ? ((uintptr_t)(u + c * hw_ + head) & 3) == 0 : ((uintptr_t)(f + c * hw_ + head) & 15) == 0;
+        for (int c = 0; c < 3; ++c) al[c] = p.quad_aligned(c * hw_ + head);
     }
     // pixel i as a packed colour
-    __device__ __forceinline__ unsigned one(long long i) const {
-        if (U8) return (unsigned)u[i] | (unsigned)u[hw + i] << 8 | (unsigned)u[2 * hw + i] << 16;
-        return quantise8(f[i]) | quantise8(f[hw + i]) << 8 | quantise8(f[2 * hw + i]) << 16;
-    }
+    __device__ __forceinline__ unsigned one(long long i) const { return p[i] | p[hw + i] << 8 | p[2 * hw + i] << 16; }
     // the four quantised bytes of plane c at pixels i0 .. i0 + 3
     __device__ __forceinline__ unsigned plane4(int c, long long i0) const {
-        if (U8) return seg_ld4(u + c * hw + i0, al[c]);
-        const float* p = f + c * hw + i0;
+        if (U8) return seg_ld4(p.u + c * hw + i0, al[c]);
+        const float* f = p.f + c * hw + i0;
         float4 v;
-        if (al[c]) v = *reinterpret_cast<const float4*>(p);
-        else v = make_float4(p[0], p[1], p[2], p[3]);
+        if (al[c]) v = *reinterpret_cast<const float4*>(f);
+        else v = make_float4(f[0], f[1], f[2], f[3]);
         return quantise8(v.x) | quantise8(v.y) << 8 | quantise8(v.z) << 16 | quantise8(v.w) << 24;
     }
     // pixels i0 .. i0 + 3 as packed colours
@@ -122,14 +114,12 @@ __global__ __launch_bounds__(EV_THREADS) void seg_decode_kernel(const void* __re
     __syncthreads();
     labels_out += b * hw;
     if (dist_out) dist_out += b * hw;
-    long long head = (long long)((4 - ((uintptr_t)labels_out & 3)) & 3);
-    if (head > hw) head = hw;
-    const SegPred<U8> pred(pred_v, b, hw, head);
-    const bool d_al = dist_out && ((uintptr_t)(dist_out + head) & 15) == 0;
-    const long long nq = (hw - head) / 4, tail0 = head + 4 * nq, ns = head + (hw - tail0);
+    const QuadSplit sp(hw, (long long)((4 - ((uintptr_t)labels_out & 3)) & 3));
+    const SegPred<U8> pred(pred_v, b, hw, sp.head);
+    const bool d_al = dist_out && ((uintptr_t)(dist_out + sp.head) & 15) == 0;
     const long long stride = (long long)gridDim.x * EV_THREADS;
-    for (long long q = (long long)blockIdx.x * EV_THREADS + threadIdx.x; q < nq; q += stride) {
-        const long long i0 = head + 4 * q;
+    for (long long q = (long long)blockIdx.x * EV_THREADS + threadIdx.x; q < sp.nq; q += stride) {
+        const long long i0 = sp.quad(q);
         unsigned rgb[4], cls[4];
         int dist[4];
         pred.quad(i0, rgb);
@@ -140,8 +130,8 @@ __global__ __launch_bounds__(EV_THREADS) void seg_decode_kernel(const void* __re
             else dist_out[i0] = dist[0], dist_out[i0 + 1] = dist[1], dist_out[i0 + 2] = dist[2], dist_out[i0 + 3] = dist[3];
         }
     }
-    for (long long k = (long long)blockIdx.x * EV_THREADS + threadIdx.x; k < ns; k += stride) {
-        const long long i = k < head ? k : tail0 + (k - head);
+    for (long long k = (long long)blockIdx.x * EV_THREADS + threadIdx.x; k < sp.ns; k += stride) {
+        const long long i = sp.scalar(k);
         const unsigned rgb[1] = {pred.one(i)};
         unsigned cls[1];
         int dist[1];
@@ -180,7 +170,6 @@ __global__ __launch_bounds__(EV_THREADS) void seg_count_kernel(const void* __res
                                                                long long hw, u64* __restrict__ mat, unsigned char* __restrict__ labels_out) {
     extern __shared__ unsigned s_conf[];
     __shared__ unsigned s_pal[SG_MAX_K];
-    __shared__ u64 s_part[EV_WAVES][SG_NSUM];
     const long long b = blockIdx.y;
     const int kk = K * K;
     for (int k = threadIdx.x; k < kk; k += EV_THREADS) s_conf[k] = 0;
@@ -191,15 +180,13 @@ __global__ __launch_bounds__(EV_THREADS) void seg_count_kernel(const void* __res
     if (labels_out) labels_out += b * hw;
     mat += b * (SG_NSUM + (long long)kk);
     // head: pixel `head` of the ground truth sits on a 4-byte boundary (3 * head = -address mod 4 for the interleaved form)
-    long long head = LABELS ? (long long)((4 - ((uintptr_t)gt & 3)) & 3) : (long long)((uintptr_t)gt & 3);
-    if (head > hw) head = hw;
-    const SegPred<U8> pred(pred_v, b, hw, head);
-    const bool r_al = region && ((uintptr_t)(region + head) & 3) == 0, l_al = labels_out && ((uintptr_t)(labels_out + head) & 3) == 0;
-    const long long nq = (hw - head) / 4, tail0 = head + 4 * nq, ns = head + (hw - tail0);
+    const QuadSplit sp(hw, LABELS ? (long long)((4 - ((uintptr_t)gt & 3)) & 3) : (long long)((uintptr_t)gt & 3));
+    const SegPred<U8> pred(pred_v, b, hw, sp.head);
+    const bool r_al = region && ((uintptr_t)(region + sp.head) & 3) == 0, l_al = labels_out && ((uintptr_t)(labels_out + sp.head) & 3) == 0;
     const long long stride = (long long)gridDim.x * EV_THREADS;
     SegAcc acc;
-    for (long long q = (long long)blockIdx.x * EV_THREADS + threadIdx.x; q < nq; q += stride) {
-        const long long i0 = head + 4 * q;
+    for (long long q = (long long)blockIdx.x * EV_THREADS + threadIdx.x; q < sp.nq; q += stride) {
+        const long long i0 = sp.quad(q);
         unsigned rgb[4], cls[4], gcl[4];
         int dist[4];
         pred.quad(i0, rgb);
@@ -223,8 +210,8 @@ __global__ __launch_bounds__(EV_THREADS) void seg_count_kernel(const void* __res
         for (int j = 0; j < 4; ++j) acc.add(cls[j], dist[j], gcl[j], ((r4 >> (8 * j)) & 0xffu) != 0, (unsigned)K, s_conf);
         if (labels_out) seg_st4(labels_out + i0, l_al, cls[0] | cls[1] << 8 | cls[2] << 16 | cls[3] << 24);
     }
-    for (long long k = (long long)blockIdx.x * EV_THREADS + threadIdx.x; k < ns; k += stride) {
-        const long long i = k < head ? k : tail0 + (k - head);
+    for (long long k = (long long)blockIdx.x * EV_THREADS + threadIdx.x; k < sp.ns; k += stride) {
+        const long long i = sp.scalar(k);
         unsigned c, g;
         int d;
         if (LABELS) {
@@ -244,23 +231,8 @@ __global__ __launch_bounds__(EV_THREADS) void seg_count_kernel(const void* __res
         if (labels_out) labels_out[i] = (unsigned char)c;
     }
     u64 v[SG_NSUM] = {acc.n, acc.n_void, acc.sum_d};
-#pragma unroll
-    for (int k = 0; k < SG_NSUM; ++k) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < SG_NSUM; ++k) s_part[wave][k] = v[k];
-    }
-    __syncthreads();  // (also: every LDS atomic of the workgroup has landed)
-    if (threadIdx.x < SG_NSUM) {
-        u64 a = s_part[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < EV_WAVES; ++w) a += s_part[w][threadIdx.x];
-        if (a != 0) atomicAdd(mat + threadIdx.x, a);
-    }
+    const u64 a = block_sum(v);  // (its barrier also: every LDS atomic of the workgroup has landed)
+    if (threadIdx.x < SG_NSUM && a != 0) atomicAdd(mat + threadIdx.x, a);
     for (int k = threadIdx.x; k < kk; k += EV_THREADS) {
         const unsigned a = s_conf[k];
         if (a != 0) atomicAdd(mat + SG_NSUM + k, (u64)a);
@@ -343,13 +315,13 @@ extern "C" {
 gp_status gp_seg_decode(const void* pred, int pred_is_u8, const unsigned char* palette, int K, int B, int H, int W, unsigned char* labels_out,
                         int* dist_out, void* stream) {
     if (!pred || !palette || !labels_out) return GP_ERR_INVALID;
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL || K < 1 || K > SG_MAX_K) return GP_ERR_INVALID;
-    if (pred_is_u8 < 0 || pred_is_u8 > 1 || (!pred_is_u8 && ((uintptr_t)pred & 3) != 0) || ((uintptr_t)dist_out & 3) != 0) return GP_ERR_INVALID;
+    if (!eval_dims_ok(B, H, W) || K < 1 || K > SG_MAX_K) return GP_ERR_INVALID;
+    if (!eval_pred_ok(pred, pred_is_u8) || ((uintptr_t)dist_out & 3) != 0) return GP_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const long long hw = (long long)H * W;
     const dim3 grid(eval_blocks(hw), B);
-    if (pred_is_u8) hipLaunchKernelGGL(seg_decode_kernel<true>, grid, dim3(EV_THREADS), 0, s, pred, palette, K, hw, labels_out, dist_out);
-    else hipLaunchKernelGGL(seg_decode_kernel<false>, grid, dim3(EV_THREADS), 0, s, pred, palette, K, hw, labels_out, dist_out);
+    const auto decode = pred_is_u8 ? seg_decode_kernel<true> : seg_decode_kernel<false>;
+    hipLaunchKernelGGL(decode, grid, dim3(EV_THREADS), 0, s, pred, palette, K, hw, labels_out, dist_out);
     return hipGetLastError() == hipSuccess ? GP_OK : GP_ERR_HIP;
 }
 
@@ -362,10 +334,9 @@ gp_status gp_eval_seg(const void* pred, int pred_is_u8, const unsigned char* gt,
                       const unsigned char* palette, int K, int B, int H, int W, double* out, unsigned long long* counts_out,
                       unsigned char* labels_out, void* workspace, long long workspace_bytes, void* stream) {
     if (!pred || !gt || !palette || !out || !workspace) return GP_ERR_INVALID;
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL || K < 1 || K > SG_MAX_K) return GP_ERR_INVALID;
-    if (pred_is_u8 < 0 || pred_is_u8 > 1 || gt_is_labels < 0 || gt_is_labels > 1 || gt_tol < 0) return GP_ERR_INVALID;
-    if (!pred_is_u8 && ((uintptr_t)pred & 3) != 0) return GP_ERR_INVALID;
-    if ((((uintptr_t)workspace | (uintptr_t)out | (uintptr_t)counts_out) & 7) != 0) return GP_ERR_INVALID;
+    if (!eval_dims_ok(B, H, W) || K < 1 || K > SG_MAX_K) return GP_ERR_INVALID;
+    if (!eval_pred_ok(pred, pred_is_u8) || gt_is_labels < 0 || gt_is_labels > 1 || gt_tol < 0) return GP_ERR_INVALID;
+    if (!eval_aligned8(workspace, out, counts_out)) return GP_ERR_INVALID;
     if (workspace_bytes < gp_eval_seg_workspace(B, H, W, K)) return GP_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const long long hw = (long long)H * W, words = (long long)B * seg_words(K);

@@ -26,20 +26,17 @@
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int ES_BINS = 256;
+constexpr int ES_BINS = EV_BINS;
 constexpr int ES_OUT = 15;                          // n, n_fg, s_alpha, s_object, s_region, max_e, mean_e, adp_e, wf, wf_precision, wf_recall, sums, cx, cy
 constexpr int ES_HEAD = 5;                          // counts_out: n_fg, sum x, sum y, cx, cy ...
 constexpr int ES_NQUAD = 16;                        // ... 4 x (a, a2, b, c) in the slabs, 4 x (N, a, a2, b, c) in counts_out ...
 constexpr int ES_COUNTS = ES_HEAD + 20 + 2 * ES_BINS;  // ... hist_bg, hist_fg
 constexpr int ES_NSUM = 3;                          // n_fg, sum x, sum y
-constexpr long long ES_CSLAB = ES_NSUM * 8 + 2 * ES_BINS * 4;  // a count slab: three 64-bit sums, 512 32-bit bins
+constexpr long long ES_CSLAB = class_slab_bytes(ES_NSUM);  // a count slab: three 64-bit sums, 512 32-bit bins
 constexpr int ES_INFO = 8;                          // 64-bit words per image: n_fg, sum x, sum y, cx, cy, 3 spare
 constexpr int ES_TW = 32, ES_TH = 8, ES_AP = 3;     // the weighting tile and its apron
 constexpr int ES_COL_THREADS = 64;
 constexpr int ES_COL_BATCH = 16;                    // rows of a column scan whose loads are in flight together
-constexpr int ES_CEN_THREADS = 1024;                // the centroid finaliser
 constexpr int ES_ROW_GROUP = 4;                     // offsets of the row search examined together
 constexpr int ES_ROW_LDS = 8192;                    // columns of a row whose candidate keys are staged in LDS (64 KiB)
 constexpr unsigned ES_NONE16 = 0xffffu;
@@ -88,18 +85,11 @@ template <bool U8>
 __global__ __launch_bounds__(EV_THREADS) void st_count_kernel(const void* __restrict__ pred_v, const unsigned char* __restrict__ gt, unsigned W,
                                                               long long hw, long long hwp, char* __restrict__ cslab,
                                                               unsigned char* __restrict__ qbuf) {
-    __shared__ unsigned s_h[EV_WAVES][2 * ES_BINS];
-    __shared__ u64 s_part[EV_WAVES][ES_NSUM];
     const long long b = blockIdx.y;
-    const float* predf = U8 ? nullptr : (const float*)pred_v + b * hw;
-    const unsigned char* predb = U8 ? (const unsigned char*)pred_v + b * hw : nullptr;
+    const Pred8<U8> pred(pred_v, b * hw);
     gt += b * hw, qbuf += b * hwp;
-    for (int k = threadIdx.x; k < EV_WAVES * 2 * ES_BINS; k += EV_THREADS) (&s_h[0][0])[k] = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned* hist = s_h[wave];
+    ClassHist hist;
     u64 v[ES_NSUM] = {0, 0, 0};
-    unsigned sat[4] = {0, 0, 0, 0};  // per wave (uniform): q == 0 & bg, q == 0 & fg, q == 255 & bg, q == 255 & fg
     const long long stride = (long long)gridDim.x * EV_THREADS;
     // (workgroup-uniform bounds: the ballots see whole waves)
     for (long long i0 = (long long)blockIdx.x * EV_THREADS; i0 < hw; i0 += stride) {
@@ -107,7 +97,7 @@ __global__ __launch_bounds__(EV_THREADS) void st_count_kernel(const void* __rest
         const bool in = i < hw;
         unsigned q = 0, g = 0;
         if (in) {
-            q = U8 ? (unsigned)predb[i] : quantise8(predf[i]);
+            q = pred[i];
             g = gt[i];
             qbuf[i] = (unsigned char)q;
         }
@@ -116,90 +106,22 @@ __global__ __launch_bounds__(EV_THREADS) void st_count_kernel(const void* __rest
             const unsigned y = (unsigned)i / W;
             v[0] += 1, v[1] += (unsigned)i - y * W, v[2] += y;
         }
-        const bool lo = in && q == 0u, hi = in && q == 255u;
-        sat[0] += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(lo && !fg));
-        sat[1] += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(lo && fg));
-        sat[2] += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(hi && !fg));
-        sat[3] += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(hi && fg));
-        if (in && !lo && !hi) atomicAdd(&hist[(fg ? ES_BINS : 0) + q], 1u);
+        hist.add(q, fg, in);
     }
-    if (lane == 0) {
-        atomicAdd(&hist[0], sat[0]);
-        atomicAdd(&hist[ES_BINS], sat[1]);
-        atomicAdd(&hist[ES_BINS - 1], sat[2]);
-        atomicAdd(&hist[2 * ES_BINS - 1], sat[3]);
-    }
-#pragma unroll
-    for (int k = 0; k < ES_NSUM; ++k) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < ES_NSUM; ++k) s_part[wave][k] = v[k];
-    }
-    __syncthreads();
+    hist.flush();
+    const u64 a = block_sum(v);  // (its barrier: every wave's histogram is complete)
     char* slab = cslab + (b * gridDim.x + blockIdx.x) * ES_CSLAB;
-    if (threadIdx.x < ES_NSUM) {
-        u64 a = s_part[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < EV_WAVES; ++w) a += s_part[w][threadIdx.x];
-        reinterpret_cast<u64*>(slab)[threadIdx.x] = a;
-    }
-    unsigned* slab_h = reinterpret_cast<unsigned*>(slab + ES_NSUM * 8);
-    for (int k = threadIdx.x; k < 2 * ES_BINS; k += EV_THREADS) {
-        unsigned a = s_h[0][k];
-#pragma unroll
-        for (int w = 1; w < EV_WAVES; ++w) a += s_h[w][k];
-        slab_h[k] = a;
-    }
+    if (threadIdx.x < ES_NSUM) reinterpret_cast<u64*>(slab)[threadIdx.x] = a;
+    hist.store(reinterpret_cast<unsigned*>(slab + ES_NSUM * 8));
 }
 
-// one workgroup per image: the slabs added, the centroid (halves rounded up; 0, 0 without foreground)
-// (adding the slabs is the long part, as in mask_finalise_kernel: 1024 threads, thread (g, l) adds bins 2 l, 2 l + 1 of slabs g, g + 4, ...,
-// eight loads in flight; the waves of group 3 add the three sums)
-__global__ __launch_bounds__(ES_CEN_THREADS) void st_centroid_kernel(const char* __restrict__ cslab, int nblk, u64* __restrict__ hist,
+// one workgroup per image: the slabs added (sum_class_slabs), the centroid (halves rounded up; 0, 0 without foreground)
+__global__ __launch_bounds__(EV_FIN_THREADS) void st_centroid_kernel(const char* __restrict__ cslab, int nblk, u64* __restrict__ hist,
                                                                      u64* __restrict__ info) {
-    __shared__ u64 s_cnt[ES_CEN_THREADS / ES_BINS][2 * ES_BINS], s_sum[ES_NSUM];
+    __shared__ u64 s_cnt[EV_FIN_GROUPS][2 * ES_BINS], s_sum[ES_NSUM];
     const long long b = blockIdx.x;
-    const char* base = cslab + b * nblk * ES_CSLAB;
-    {
-        const int l = threadIdx.x % ES_BINS, grp = threadIdx.x / ES_BINS;
-        const char* mine = base + ES_NSUM * 8 + 8 * l;
-        u64 c0 = 0, c1 = 0;
-        int j = grp;
-        for (; j + 7 * 4 < nblk; j += 8 * 4) {
-            uint2 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const uint2*>(mine + (long long)(j + 4 * u) * ES_CSLAB);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) c0 += v[u].x, c1 += v[u].y;
-        }
-        for (; j < nblk; j += 4) {
-            const uint2 v = *reinterpret_cast<const uint2*>(mine + (long long)j * ES_CSLAB);
-            c0 += v.x, c1 += v.y;
-        }
-        s_cnt[grp][2 * l] = c0, s_cnt[grp][2 * l + 1] = c1;
-    }
-    if (threadIdx.x >= ES_CEN_THREADS - 64) {
-        const int lane = threadIdx.x & 63;
-        u64 a[ES_NSUM] = {0, 0, 0};
-        for (int j = lane; j < nblk; j += 64) {
-#pragma unroll
-            for (int k = 0; k < ES_NSUM; ++k) a[k] += reinterpret_cast<const u64*>(base + (long long)j * ES_CSLAB)[k];
-        }
-#pragma unroll
-        for (int k = 0; k < ES_NSUM; ++k) {
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) a[k] += __shfl_down(a[k], off, 64);
-        }
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < ES_NSUM; ++k) s_sum[k] = a[k];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 * ES_BINS) hist[b * 2 * ES_BINS + threadIdx.x] = s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] + s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
+    const u64 bin = sum_class_slabs<ES_NSUM>(cslab + b * nblk * ES_CSLAB, nblk, s_cnt, s_sum);
+    if (threadIdx.x < 2 * ES_BINS) hist[b * 2 * ES_BINS + threadIdx.x] = bin;
     if (threadIdx.x == 0) {
         const u64 n_fg = s_sum[0], sx = s_sum[1], sy = s_sum[2];
         u64* o = info + b * ES_INFO;
@@ -215,7 +137,6 @@ __global__ __launch_bounds__(ES_CEN_THREADS) void st_centroid_kernel(const char*
 __global__ __launch_bounds__(EV_THREADS) void st_quad_kernel(const unsigned char* __restrict__ qbuf, const unsigned char* __restrict__ gt,
                                                              const u64* __restrict__ info, unsigned W, long long hw, long long hwp,
                                                              u64* __restrict__ qslab) {
-    __shared__ u64 s_part[EV_WAVES][ES_NQUAD];
     const long long b = blockIdx.y;
     qbuf += b * hwp, gt += b * hw;
     const unsigned cx = (unsigned)info[b * ES_INFO + 3], cy = (unsigned)info[b * ES_INFO + 4];
@@ -233,23 +154,8 @@ __global__ __launch_bounds__(EV_THREADS) void st_quad_kernel(const unsigned char
             acc[4 * k + 0] += m * q, acc[4 * k + 1] += m * q * q, acc[4 * k + 2] += m * fg, acc[4 * k + 3] += m * fg * q;
         }
     }
-#pragma unroll
-    for (int k = 0; k < ES_NQUAD; ++k) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) acc[k] += __shfl_down(acc[k], off, 64);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < ES_NQUAD; ++k) s_part[wave][k] = acc[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < ES_NQUAD) {
-        u64 a = s_part[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < EV_WAVES; ++w) a += s_part[w][threadIdx.x];
-        qslab[(b * gridDim.x + blockIdx.x) * ES_NQUAD + threadIdx.x] = a;
-    }
+    const u64 a = block_sum(acc);
+    if (threadIdx.x < ES_NQUAD) qslab[(b * gridDim.x + blockIdx.x) * ES_NQUAD + threadIdx.x] = a;
 }
 
 // ---- exact Euclidean distance transform -----------------------------------------------------------------------------------------------------
@@ -543,9 +449,8 @@ long long gp_eval_structure_workspace(int B, int H, int W) {
 gp_status gp_eval_structure(const void* pred, int pred_is_u8, const unsigned char* gt, int B, int H, int W, double* out,
                             unsigned long long* counts_out, unsigned long long* edt_out, void* workspace, long long workspace_bytes, void* stream) {
     if (!pred || !gt || !out || !workspace) return GP_ERR_INVALID;
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || H > 32767 || W > 32767 || (long long)H * W > 0x7fffffffLL) return GP_ERR_INVALID;
-    if (pred_is_u8 < 0 || pred_is_u8 > 1 || (!pred_is_u8 && ((uintptr_t)pred & 3) != 0)) return GP_ERR_INVALID;
-    if ((((uintptr_t)workspace | (uintptr_t)out | (uintptr_t)counts_out | (uintptr_t)edt_out) & 7) != 0) return GP_ERR_INVALID;
+    if (!eval_dims_ok(B, H, W) || H > 32767 || W > 32767) return GP_ERR_INVALID;
+    if (!eval_pred_ok(pred, pred_is_u8) || !eval_aligned8(workspace, out, counts_out, edt_out)) return GP_ERR_INVALID;
     const StructWs w = struct_ws(B, H, W);
     if (workspace_bytes < w.total) return GP_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
@@ -559,9 +464,9 @@ gp_status gp_eval_structure(const void* pred, int pred_is_u8, const unsigned cha
     unsigned* dudd = (unsigned*)(base + w.dudd);
     u64* keys = edt_out ? edt_out : (u64*)(base + w.keys);
     unsigned char* qbuf = (unsigned char*)(base + w.qbuf);
-    if (pred_is_u8) hipLaunchKernelGGL(st_count_kernel<true>, dim3(w.nblk, B), dim3(EV_THREADS), 0, s, pred, gt, (unsigned)W, hw, w.hwp, cslab, qbuf);
-    else hipLaunchKernelGGL(st_count_kernel<false>, dim3(w.nblk, B), dim3(EV_THREADS), 0, s, pred, gt, (unsigned)W, hw, w.hwp, cslab, qbuf);
-    hipLaunchKernelGGL(st_centroid_kernel, dim3(B), dim3(ES_CEN_THREADS), 0, s, (const char*)cslab, w.nblk, hist, info);
+    const auto count = pred_is_u8 ? st_count_kernel<true> : st_count_kernel<false>;
+    hipLaunchKernelGGL(count, dim3(w.nblk, B), dim3(EV_THREADS), 0, s, pred, gt, (unsigned)W, hw, w.hwp, cslab, qbuf);
+    hipLaunchKernelGGL(st_centroid_kernel, dim3(B), dim3(EV_FIN_THREADS), 0, s, (const char*)cslab, w.nblk, hist, info);
     hipLaunchKernelGGL(st_quad_kernel, dim3(w.nblk, B), dim3(EV_THREADS), 0, s, (const unsigned char*)qbuf, gt, (const u64*)info, (unsigned)W, hw, w.hwp,
                        qslab);
     hipLaunchKernelGGL(st_edt_col_kernel, dim3((W + ES_COL_THREADS - 1) / ES_COL_THREADS, B, 2), dim3(ES_COL_THREADS), 0, s, gt, H, W, w.hwp,

@@ -60,8 +60,7 @@ __global__ __launch_bounds__(MB_COL_THREADS) void mb_col_kernel(const void* __re
     const int x = cb * MB_COL_THREADS + threadIdx.x;
     if (x >= W) return;
     const long long b = blockIdx.y;
-    const float* af = U8 ? nullptr : (const float*)a_v + b * ((long long)H * W) + x;
-    const unsigned char* ab = U8 ? (const unsigned char*)a_v + b * ((long long)H * W) + x : nullptr;
+    const Pred8<U8> a(a_v, b * ((long long)H * W) + x);  // this lane's column
     ws += b * hwp + x;
     const int cap = rv + 1;
     const int y0 = sg * seg, y1 = y0 + seg < H ? y0 + seg : H;  // (seg <= 4096: no overflow)
@@ -73,7 +72,7 @@ __global__ __launch_bounds__(MB_COL_THREADS) void mb_col_kernel(const void* __re
 #pragma unroll
             for (int u = 0; u < MB_COL_BATCH; ++u) {
                 const int y = s0 + u < y1 ? s0 + u : y1 - 1;  // (past the end: the last row again, not used)
-                v[u] = U8 ? (int)ab[(long long)y * W] : (int)quantise8(af[(long long)y * W]);
+                v[u] = (int)a[(long long)y * W];
             }
 #pragma unroll
             for (int u = 0; u < MB_COL_BATCH; ++u) {
@@ -95,7 +94,7 @@ __global__ __launch_bounds__(MB_COL_THREADS) void mb_col_kernel(const void* __re
 #pragma unroll
             for (int u = 0; u < MB_COL_BATCH; ++u) {
                 const int y = s0 - u > y0 ? s0 - u : y0;
-                v[u] = U8 ? (int)ab[(long long)y * W] : (int)quantise8(af[(long long)y * W]);
+                v[u] = (int)a[(long long)y * W];
                 w[u] = y < y1 ? ws[(long long)y * W] : 0u;
             }
 #pragma unroll
@@ -210,11 +209,11 @@ gp_status gp_mask_band(const void* a, int a_is_u8, int B, int H, int W, int lo, 
                        unsigned char* band_out, unsigned char* fg_out, unsigned char* bg_out, unsigned char* inner_out, unsigned char* trimap_out,
                        void* workspace, long long workspace_bytes, void* stream) {
     if (!a || !workspace || !(band_out || fg_out || bg_out || inner_out || trimap_out)) return GP_ERR_INVALID;
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) return GP_ERR_INVALID;
-    if (a_is_u8 < 0 || a_is_u8 > 1 || metric < 0 || metric > 1 || border < 0 || border > 1) return GP_ERR_INVALID;
+    if (!eval_dims_ok(B, H, W)) return GP_ERR_INVALID;
+    if (metric < 0 || metric > 1 || border < 0 || border > 1) return GP_ERR_INVALID;
     if (lo < -1 || hi > 256 || lo >= hi) return GP_ERR_INVALID;
     if (reach < 0 || reach > (metric ? MB_MAX_RV : MB_MAX_RV * MB_MAX_RV)) return GP_ERR_INVALID;
-    if ((!a_is_u8 && ((uintptr_t)a & 3) != 0) || ((uintptr_t)workspace & 7) != 0) return GP_ERR_INVALID;
+    if (!eval_pred_ok(a, a_is_u8) || !eval_aligned8(workspace)) return GP_ERR_INVALID;
     const long long hwp = mb_hwp(H, W);
     if (workspace_bytes < (long long)B * hwp * 4) return GP_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
@@ -223,8 +222,8 @@ gp_status gp_mask_band(const void* a, int a_is_u8, int B, int H, int W, int lo, 
     const int seg = mb_segment(rv);
     const int ncb = (W + MB_COL_THREADS - 1) / MB_COL_THREADS, nseg = (H + seg - 1) / seg;  // ncb * nseg <= H * W / 64 + H + W
     const dim3 cgrid((unsigned)ncb * (unsigned)nseg, B);
-    if (a_is_u8) hipLaunchKernelGGL(mb_col_kernel<true>, cgrid, dim3(MB_COL_THREADS), 0, s, a, H, W, hwp, lo, hi, metric, reach, rv, seg, border, ncb, ws);
-    else hipLaunchKernelGGL(mb_col_kernel<false>, cgrid, dim3(MB_COL_THREADS), 0, s, a, H, W, hwp, lo, hi, metric, reach, rv, seg, border, ncb, ws);
+    const auto col = a_is_u8 ? mb_col_kernel<true> : mb_col_kernel<false>;
+    hipLaunchKernelGGL(col, cgrid, dim3(MB_COL_THREADS), 0, s, a, H, W, hwp, lo, hi, metric, reach, rv, seg, border, ncb, ws);
     // a column outside the image: never A; with border = 1 all of it is Bc (vertical distance 0), with border = 0 nothing is there.  No pixel
     // is more than W columns away from the outside, so a horizontal reach above W searches nothing new.
     const int rh = rv < W ? rv : W;

@@ -10,6 +10,9 @@ from typing import Dict, Iterable, List, Optional, Sequence
 import numpy as np
 import torch
 
+from .eval_metrics import (BAND_METRIC, BAND_PLANES, BOUNDARY_METRICS, MASK_METRICS, MATTING_METRICS, SEG_MAX_K, SEG_METRICS,  # noqa: F401
+                           STRUCTURE_METRICS, TRIMAP_METRICS)  # the names of the evaluators' values: one list each, stated in eval_metrics
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # One library per 16-bit element type (csrc/common.h): identical C-ABI, bf16 or IEEE fp16 activations / weights / MFMA operands.
 # "bf16" is the default (BASELINE.json's dtype); "fp16" is the reference's half precision (run.py --half_precision), 8x finer
@@ -918,6 +921,55 @@ def _eval_maps(x: torch.Tensor, name: str) -> torch.Tensor:
     return x
 
 
+def _mask_u8(m: torch.Tensor, name: str, shape) -> torch.Tensor:
+    """A validity mask or region as a contiguous uint8 plane [B, H, W] of `shape`: bool and uint8 as their bytes (every kernel tests the byte
+    against zero, eval.hip's depth passes included), any other dtype through `!= 0`."""
+    m = _eval_maps(m, name)
+    if tuple(m.shape) != tuple(shape):
+        raise ValueError(f"{name} {tuple(m.shape)} does not match the maps {tuple(shape)}")
+    assert m.is_cuda
+    return (m if m.dtype in (torch.bool, torch.uint8) else m != 0).contiguous().view(torch.uint8)
+
+
+def _map8(x: torch.Tensor, name: str):
+    """A float map in [0, 1] as contiguous fp32 (the kernel quantises it), or its uint8 quantisation as it is: (map, is_u8)."""
+    is_u8 = x.dtype == torch.uint8
+    if not is_u8 and not x.dtype.is_floating_point:
+        raise ValueError(f"{name}: a float map in [0, 1] or its uint8 quantisation, got {x.dtype}")
+    return (x if is_u8 else x.to(torch.float32)).contiguous(), is_u8
+
+
+def _pred_gt8(pred: torch.Tensor, gt: torch.Tensor):
+    """pred (`_map8`) and the 8-bit ground truth as contiguous [B, H, W] device maps of one shape: (pred, is_u8, gt, (b, h, w))."""
+    pred, gt = _eval_maps(pred, "pred"), _eval_maps(gt, "gt")
+    assert pred.is_cuda and gt.is_cuda
+    if gt.dtype != torch.uint8:
+        raise ValueError(f"gt: the ground truth is an 8-bit mask / alpha map (uint8), got {gt.dtype}")
+    if pred.shape != gt.shape:
+        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have one shape")
+    pred, is_u8 = _map8(pred, "pred")
+    return pred, is_u8, gt.contiguous(), tuple(int(v) for v in pred.shape)
+
+
+def _workspace(nbytes: int, device):
+    """(an 8-byte aligned device buffer for the `nbytes` a gp_*_workspace call asks for, nbytes)"""
+    nbytes = int(nbytes)
+    return torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=device), nbytes
+
+
+def _packed(b: int, n_out: int, n_cnt: int, device):
+    """One int64 device buffer that holds the float64 values [b, n_out] and then the int64 counts [b, n_cnt] (n_cnt = 0: None), so that one
+    copy brings both to the host: (buf, out, counts), the last two views of buf."""
+    buf = torch.empty((b * (n_out + n_cnt),), dtype=torch.int64, device=device)
+    return buf, buf[:b * n_out].view(torch.float64).view(b, n_out), buf[b * n_out:].view(b, n_cnt) if n_cnt else None
+
+
+def _unpacked(buf: torch.Tensor, b: int, n_out: int):
+    """The host copy of a `_packed` buffer with counts: (float64 numpy [b, n_out], int64 numpy [b, n_cnt])."""
+    host = buf.cpu().numpy()
+    return host[:b * n_out].view("float64").reshape(b, n_out), host[b * n_out:].reshape(b, -1)
+
+
 def eval_depth_raw(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, alignment: Optional[str] = "least_square",
                    alignment_max_res: Optional[int] = None, min_depth: float = 1e-3, max_depth: float = 10.0) -> torch.Tensor:
     """gp_eval_depth on device tensors: float64 [B, 14] ON THE DEVICE = s, t, n_valid, n_fit, then the ten metrics in eval_metrics.METRICS
@@ -926,12 +978,12 @@ def eval_depth_raw(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, ali
     if alignment not in EVAL_ALIGNMENT:
         raise NotImplementedError(alignment)
     lib = load_library()
-    pred, gt, mask = _eval_maps(pred, "pred"), _eval_maps(gt, "gt"), _eval_maps(mask, "mask")
-    assert pred.is_cuda and gt.is_cuda and mask.is_cuda
-    if not (pred.shape == gt.shape == mask.shape):
-        raise ValueError(f"pred {tuple(pred.shape)}, gt {tuple(gt.shape)} and mask {tuple(mask.shape)} must have one shape")
+    pred, gt = _eval_maps(pred, "pred"), _eval_maps(gt, "gt")
+    assert pred.is_cuda and gt.is_cuda
+    if pred.shape != gt.shape:
+        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have one shape")
+    mask = _mask_u8(mask, "mask", pred.shape)
     pred, gt = pred.to(torch.float32).contiguous(), gt.to(torch.float32).contiguous()
-    mask = (mask.contiguous().view(torch.uint8) if mask.dtype == torch.bool else (mask != 0).view(torch.uint8)).contiguous()
     b, h, w = (int(v) for v in pred.shape)
     fit_cols, fit_inv = 0, 0.0
     if alignment_max_res is not None and EVAL_ALIGNMENT[alignment]:  # alignment.py:43-55 as eval_metrics.align_depth_least_square restates it
@@ -941,12 +993,9 @@ def eval_depth_raw(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, ali
             if fit_cols < 1:
                 raise ValueError(f"alignment_max_res = {alignment_max_res} leaves no column of a {h} x {w} image to fit on")
     out = torch.empty((b, 14), dtype=torch.float64, device=pred.device)
-    nbytes = int(lib.gp_eval_depth_workspace(b, h, w))
-    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=pred.device)
-    st = lib.gp_eval_depth(pred.data_ptr(), gt.data_ptr(), mask.data_ptr(), b, h, w, EVAL_ALIGNMENT[alignment], fit_cols, fit_inv, float(min_depth),
-                           float(max_depth), out.data_ptr(), ws.data_ptr(), nbytes, _stream_ptr(pred.device))
-    if st != GP_OK:
-        raise RuntimeError(f"gp_eval_depth failed ({st})")
+    ws, nbytes = _workspace(lib.gp_eval_depth_workspace(b, h, w), pred.device)
+    _c_check(lib.gp_eval_depth(pred.data_ptr(), gt.data_ptr(), mask.data_ptr(), b, h, w, EVAL_ALIGNMENT[alignment], fit_cols, fit_inv, float(min_depth),
+                               float(max_depth), out.data_ptr(), ws.data_ptr(), nbytes, _stream_ptr(pred.device)), "gp_eval_depth")
     return out
 
 
@@ -992,19 +1041,12 @@ def eval_normal_raw(pred: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.T
     pred, gt = pred.to(torch.float32).contiguous(), gt.to(torch.float32).contiguous()
     b, _, h, w = (int(v) for v in pred.shape)
     if mask is not None:
-        mask = _eval_maps(mask, "mask")
-        assert mask.is_cuda
-        if tuple(mask.shape) != (b, h, w):
-            raise ValueError(f"mask {tuple(mask.shape)} does not match the maps {(b, h, w)}")
-        mask = (mask.contiguous().view(torch.uint8) if mask.dtype == torch.bool else (mask != 0).view(torch.uint8)).contiguous()
+        mask = _mask_u8(mask, "mask", (b, h, w))
     out = torch.empty((b, 8), dtype=torch.float64, device=pred.device)
     angles = torch.empty((b, h, w), dtype=torch.float64, device=pred.device) if want_angles else None
-    nbytes = int(lib.gp_eval_normal_workspace(b, h, w))
-    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=pred.device)
-    st = lib.gp_eval_normal(pred.data_ptr(), gt.data_ptr(), _ptr(mask), b, h, w, int(bool(pred_encoded)) | int(bool(gt_encoded)) << 1, out.data_ptr(),
-                            _ptr(angles), ws.data_ptr(), nbytes, _stream_ptr(pred.device))
-    if st != GP_OK:
-        raise RuntimeError(f"gp_eval_normal failed ({st})")
+    ws, nbytes = _workspace(lib.gp_eval_normal_workspace(b, h, w), pred.device)
+    _c_check(lib.gp_eval_normal(pred.data_ptr(), gt.data_ptr(), _ptr(mask), b, h, w, int(bool(pred_encoded)) | int(bool(gt_encoded)) << 1, out.data_ptr(),
+                                _ptr(angles), ws.data_ptr(), nbytes, _stream_ptr(pred.device)), "gp_eval_normal")
     return (out, angles) if want_angles else out
 
 
@@ -1019,8 +1061,7 @@ def eval_normal(pred: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.Tenso
     return [{k: float(row[1 + j]) for j, k in enumerate(NORMAL_METRICS)} for row in raw], raw[:, 0].astype("int64")
 
 
-MASK_METRICS = ["mae", "mse", "sad", "max_f", "mean_f", "adp_f", "iou"]  # gp_eval_mask's out[2 .. 8]; eval_metrics.mask_metrics_from_counts' keys
-MASK_OUT = 10      # n, n_fg, the seven metrics, t_max
+MASK_OUT = 10      # n, n_fg, MASK_METRICS (out[2 .. 8]), t_max
 MASK_COUNTS = 516  # n, sum_q, sad, sse, hist_bg[256], hist_fg[256]
 
 
@@ -1028,32 +1069,13 @@ def _eval_mask_launch(pred: torch.Tensor, gt: torch.Tensor, region: Optional[tor
     """The checks and the call of `eval_mask_raw`.  Returns (buf, out, counts): out float64 [B, 10] and counts int64 [B, 516] (or None) are
     views of the one int64 device buffer `buf`, so that one copy brings both to the host."""
     lib = load_library()
-    pred, gt = _eval_maps(pred, "pred"), _eval_maps(gt, "gt")
-    assert pred.is_cuda and gt.is_cuda
-    if gt.dtype != torch.uint8:
-        raise ValueError(f"gt: the ground truth is an 8-bit mask / alpha map (uint8), got {gt.dtype}")
-    if pred.shape != gt.shape:
-        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have one shape")
-    is_u8 = pred.dtype == torch.uint8
-    if not is_u8 and not pred.dtype.is_floating_point:
-        raise ValueError(f"pred: a float map in [0, 1] or its uint8 quantisation, got {pred.dtype}")
-    pred, gt = (pred if is_u8 else pred.to(torch.float32)).contiguous(), gt.contiguous()
-    b, h, w = (int(v) for v in pred.shape)
+    pred, is_u8, gt, (b, h, w) = _pred_gt8(pred, gt)
     if region is not None:
-        region = _eval_maps(region, "region")
-        assert region.is_cuda
-        if tuple(region.shape) != (b, h, w):
-            raise ValueError(f"region {tuple(region.shape)} does not match the maps {(b, h, w)}")
-        region = (region.contiguous().view(torch.uint8) if region.dtype in (torch.bool, torch.uint8) else (region != 0).view(torch.uint8)).contiguous()
-    buf = torch.empty((b * (MASK_OUT + (MASK_COUNTS if want_counts else 0)),), dtype=torch.int64, device=pred.device)
-    out = buf[:b * MASK_OUT].view(torch.float64).view(b, MASK_OUT)
-    counts = buf[b * MASK_OUT:].view(b, MASK_COUNTS) if want_counts else None
-    nbytes = int(lib.gp_eval_mask_workspace(b, h, w))
-    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=pred.device)
-    st = lib.gp_eval_mask(pred.data_ptr(), int(is_u8), gt.data_ptr(), _ptr(region), b, h, w, out.data_ptr(), _ptr(counts), ws.data_ptr(), nbytes,
-                          _stream_ptr(pred.device))
-    if st != GP_OK:
-        raise RuntimeError(f"gp_eval_mask failed ({st})")
+        region = _mask_u8(region, "region", (b, h, w))
+    buf, out, counts = _packed(b, MASK_OUT, MASK_COUNTS if want_counts else 0, pred.device)
+    ws, nbytes = _workspace(lib.gp_eval_mask_workspace(b, h, w), pred.device)
+    _c_check(lib.gp_eval_mask(pred.data_ptr(), int(is_u8), gt.data_ptr(), _ptr(region), b, h, w, out.data_ptr(), _ptr(counts), ws.data_ptr(), nbytes,
+                              _stream_ptr(pred.device)), "gp_eval_mask")
     return buf, out, counts
 
 
@@ -1072,9 +1094,7 @@ def eval_mask(pred: torch.Tensor, gt: torch.Tensor, region: Optional[torch.Tenso
     MASK_METRICS, "n", "n_fg", "t_max" and "counts" (int64 numpy [516]).  Raises ValueError naming the image when its region is empty.  One
     device -> host copy of B x (10 + 516) words."""
     buf, out, _ = _eval_mask_launch(pred, gt, region, True)
-    b = out.shape[0]
-    host = buf.cpu().numpy()
-    raw, counts = host[:b * MASK_OUT].view("float64").reshape(b, MASK_OUT), host[b * MASK_OUT:].reshape(b, MASK_COUNTS)
+    raw, counts = _unpacked(buf, out.shape[0], MASK_OUT)
     res = []
     for i, row in enumerate(raw):
         if row[0] == 0:
@@ -1085,10 +1105,9 @@ def eval_mask(pred: torch.Tensor, gt: torch.Tensor, region: Optional[torch.Tenso
     return res
 
 
-STRUCTURE_METRICS = ["s_alpha", "max_e", "mean_e", "adp_e", "wf"]  # gp_eval_structure's out[2], [5 .. 8]; eval_metrics.STRUCTURE_METRICS
 STRUCTURE_OUT_NAMES = ["n", "n_fg", "s_alpha", "s_object", "s_region", "max_e", "mean_e", "adp_e", "wf", "wf_precision", "wf_recall", "wf_sum_fg",
                        "wf_sum_bg", "cx", "cy"]
-STRUCTURE_OUT = 15       # the names above
+STRUCTURE_OUT = 15       # the names above (STRUCTURE_METRICS: out[2], [5 .. 8])
 STRUCTURE_COUNTS = 537   # n_fg, sum_fg x, sum_fg y, cx, cy, 4 x (N, a, a2, b, c), hist_bg[256], hist_fg[256]
 
 
@@ -1099,28 +1118,15 @@ def eval_structure_raw(pred: torch.Tensor, gt: torch.Tensor, want_counts: bool =
     [B, 1, H, W] or [H, W], a float map in [0, 1] (quantised to 8 bits by the kernel) or uint8; gt: uint8, same shape; H, W <= 32767.
     Enqueued on the current stream, no synchronisation."""
     lib = load_library()
-    pred, gt = _eval_maps(pred, "pred"), _eval_maps(gt, "gt")
-    assert pred.is_cuda and gt.is_cuda
-    if gt.dtype != torch.uint8:
-        raise ValueError(f"gt: the ground truth is an 8-bit mask (uint8), got {gt.dtype}")
-    if pred.shape != gt.shape:
-        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have one shape")
-    is_u8 = pred.dtype == torch.uint8
-    if not is_u8 and not pred.dtype.is_floating_point:
-        raise ValueError(f"pred: a float map in [0, 1] or its uint8 quantisation, got {pred.dtype}")
-    pred, gt = (pred if is_u8 else pred.to(torch.float32)).contiguous(), gt.contiguous()
-    b, h, w = (int(v) for v in pred.shape)
+    pred, is_u8, gt, (b, h, w) = _pred_gt8(pred, gt)
     if h > 32767 or w > 32767:
         raise ValueError(f"structure scores take maps of at most 32767 x 32767, got {h} x {w}")
     out = torch.empty((b, STRUCTURE_OUT), dtype=torch.float64, device=pred.device)
     counts = torch.empty((b, STRUCTURE_COUNTS), dtype=torch.int64, device=pred.device) if want_counts else None
     edt = torch.empty((b, h, w), dtype=torch.int64, device=pred.device) if want_edt else None
-    nbytes = int(lib.gp_eval_structure_workspace(b, h, w))
-    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=pred.device)
-    st = lib.gp_eval_structure(pred.data_ptr(), int(is_u8), gt.data_ptr(), b, h, w, out.data_ptr(), _ptr(counts), _ptr(edt), ws.data_ptr(), nbytes,
-                               _stream_ptr(pred.device))
-    if st != GP_OK:
-        raise RuntimeError(f"gp_eval_structure failed ({st})")
+    ws, nbytes = _workspace(lib.gp_eval_structure_workspace(b, h, w), pred.device)
+    _c_check(lib.gp_eval_structure(pred.data_ptr(), int(is_u8), gt.data_ptr(), b, h, w, out.data_ptr(), _ptr(counts), _ptr(edt), ws.data_ptr(), nbytes,
+                                   _stream_ptr(pred.device)), "gp_eval_structure")
     res = (out,) + ((counts,) if want_counts else ()) + ((edt,) if want_edt else ())
     return res if len(res) > 1 else out
 
@@ -1133,8 +1139,7 @@ def eval_structure(pred: torch.Tensor, gt: torch.Tensor):
     return [{k: (int(row[j]) if k in ints else float(row[j])) for j, k in enumerate(STRUCTURE_OUT_NAMES)} for row in raw]
 
 
-MATTING_METRICS = ["grad", "conn"]  # gp_eval_matting's out[1], [2]; eval_metrics.MATTING_METRICS
-MATTING_OUT_NAMES = ["n", "grad", "conn", "grad_sum"]
+MATTING_OUT_NAMES = ["n", "grad", "conn", "grad_sum"]  # MATTING_METRICS: out[1], [2]
 MATTING_OUT = 4       # the names above
 MATTING_COUNTS = 13   # n, conn_num, the counts of the levels 0..10 over the whole image
 
@@ -1148,33 +1153,16 @@ def eval_matting_raw(pred: torch.Tensor, gt: torch.Tensor, region: Optional[torc
     or [H, W], a float map in [0, 1] (quantised to 8 bits by the kernel) or uint8; gt: uint8, same shape; region: bool or integer, non-zero =
     scored, None = every pixel (it restricts only the sums).  Enqueued on the current stream, no synchronisation."""
     lib = load_library()
-    pred, gt = _eval_maps(pred, "pred"), _eval_maps(gt, "gt")
-    assert pred.is_cuda and gt.is_cuda
-    if gt.dtype != torch.uint8:
-        raise ValueError(f"gt: the ground truth is an 8-bit alpha map (uint8), got {gt.dtype}")
-    if pred.shape != gt.shape:
-        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have one shape")
-    is_u8 = pred.dtype == torch.uint8
-    if not is_u8 and not pred.dtype.is_floating_point:
-        raise ValueError(f"pred: a float map in [0, 1] or its uint8 quantisation, got {pred.dtype}")
-    pred, gt = (pred if is_u8 else pred.to(torch.float32)).contiguous(), gt.contiguous()
-    b, h, w = (int(v) for v in pred.shape)
+    pred, is_u8, gt, (b, h, w) = _pred_gt8(pred, gt)
     if region is not None:
-        region = _eval_maps(region, "region")
-        assert region.is_cuda
-        if tuple(region.shape) != (b, h, w):
-            raise ValueError(f"region {tuple(region.shape)} does not match the maps {(b, h, w)}")
-        region = (region.contiguous().view(torch.uint8) if region.dtype in (torch.bool, torch.uint8) else (region != 0).view(torch.uint8)).contiguous()
+        region = _mask_u8(region, "region", (b, h, w))
     out = torch.empty((b, MATTING_OUT), dtype=torch.float64, device=pred.device)
     counts = torch.empty((b, MATTING_COUNTS), dtype=torch.int64, device=pred.device) if want_counts else None
     levels = torch.empty((b, h, w), dtype=torch.uint8, device=pred.device) if want_levels else None
     grad_map = torch.empty((b, h, w), dtype=torch.float64, device=pred.device) if want_grad_map else None
-    nbytes = int(lib.gp_eval_matting_workspace(b, h, w))
-    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=pred.device)
-    st = lib.gp_eval_matting(pred.data_ptr(), int(is_u8), gt.data_ptr(), _ptr(region), b, h, w, out.data_ptr(), _ptr(counts), _ptr(levels),
-                             _ptr(grad_map), ws.data_ptr(), nbytes, _stream_ptr(pred.device))
-    if st != GP_OK:
-        raise RuntimeError(f"gp_eval_matting failed ({st})")
+    ws, nbytes = _workspace(lib.gp_eval_matting_workspace(b, h, w), pred.device)
+    _c_check(lib.gp_eval_matting(pred.data_ptr(), int(is_u8), gt.data_ptr(), _ptr(region), b, h, w, out.data_ptr(), _ptr(counts), _ptr(levels),
+                                 _ptr(grad_map), ws.data_ptr(), nbytes, _stream_ptr(pred.device)), "gp_eval_matting")
     res = (out,) + ((counts,) if want_counts else ()) + ((levels,) if want_levels else ()) + ((grad_map,) if want_grad_map else ())
     return res if len(res) > 1 else out
 
@@ -1188,12 +1176,6 @@ def eval_matting(pred: torch.Tensor, gt: torch.Tensor, region: Optional[torch.Te
         if row[0] == 0:
             raise ValueError(f"image {i}: no pixel to evaluate the alpha map on (n = 0)")
     return [{k: (int(row[j]) if k == "n" else float(row[j])) for j, k in enumerate(MATTING_OUT_NAMES)} for row in raw]
-
-
-TRIMAP_METRICS = ["mae_t", "mse_t", "sad_t", "sad_fg", "sad_bg"]  # eval_metrics.TRIMAP_METRICS
-BOUNDARY_METRICS = ["biou"]  # eval_metrics.BOUNDARY_METRICS
-BAND_PLANES = ["band", "fg", "bg", "inner", "trimap"]  # gp_mask_band's output planes, in argument order
-BAND_METRIC = {"euclidean": 0, "chebyshev": 1, 0: 0, 1: 1}
 
 
 def mask_band(a: torch.Tensor, lo: int, hi: int, reach: int, metric="euclidean", border: bool = False, want: Sequence[str] = ("band",)):
@@ -1211,21 +1193,16 @@ def mask_band(a: torch.Tensor, lo: int, hi: int, reach: int, metric="euclidean",
     want = list(want)
     if not want or any(k not in BAND_PLANES for k in want) or len(set(want)) != len(want):
         raise ValueError(f"want names one or more of {BAND_PLANES}, got {want}")
-    is_u8 = a.dtype == torch.uint8
-    if not is_u8 and not a.dtype.is_floating_point:
-        raise ValueError(f"a: a float map in [0, 1] or its uint8 quantisation, got {a.dtype}")
-    a = (a if is_u8 else a.to(torch.float32)).contiguous()
+    a, is_u8 = _map8(a, "a")
     b, h, w = (int(v) for v in a.shape)
     planes = torch.empty((len(want), b, h, w), dtype=torch.uint8, device=a.device)
     outs = [_ptr(planes[want.index(k)]) if k in want else None for k in BAND_PLANES]
-    nbytes = int(lib.gp_mask_band_workspace(b, h, w))
-    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=a.device)
+    ws, nbytes = _workspace(lib.gp_mask_band_workspace(b, h, w), a.device)
     st = lib.gp_mask_band(a.data_ptr(), int(is_u8), b, h, w, int(lo), int(hi), BAND_METRIC[metric], int(reach), int(bool(border)), *outs,
                           ws.data_ptr(), nbytes, _stream_ptr(a.device))
     if st == GP_ERR_INVALID:
         raise ValueError(f"gp_mask_band: invalid arguments (lo = {lo}, hi = {hi}, reach = {reach}, metric = {metric!r}, maps {(b, h, w)})")
-    if st != GP_OK:
-        raise RuntimeError(f"gp_mask_band failed ({st})")
+    _c_check(st, "gp_mask_band")
     return {k: planes[j] for j, k in enumerate(want)}
 
 
@@ -1252,39 +1229,27 @@ def eval_boundary_iou(pred: torch.Tensor, gt: torch.Tensor, ratio: float = 0.02)
     calls, their IoU from gp_eval_mask.  Returns one dict per image: "biou", "d", "n_gt_band", "n_pred_band".  One device -> host copy of
     B x (10 + 516) words."""
     from .eval_metrics import boundary_reach
-    pred, gt = _eval_maps(pred, "pred"), _eval_maps(gt, "gt")
-    if gt.dtype != torch.uint8:
-        raise ValueError(f"gt: the ground truth is an 8-bit mask (uint8), got {gt.dtype}")
-    if pred.shape != gt.shape:
-        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have one shape")
-    b, h, w = (int(v) for v in gt.shape)
+    pred, _, gt, (b, h, w) = _pred_gt8(pred, gt)
     d = boundary_reach(h, w, ratio)
     g_d = mask_band(gt, 128, 129, d, "chebyshev", True, want=("inner",))["inner"]
     p_d = mask_band(pred, 127, 128, d, "chebyshev", True, want=("inner",))["inner"]
-    buf, _, _ = _eval_mask_launch(p_d, g_d, None, True)
-    host = buf.cpu().numpy()
-    raw, counts = host[:b * MASK_OUT].view("float64").reshape(b, MASK_OUT), host[b * MASK_OUT:].reshape(b, MASK_COUNTS)
+    raw, counts = _unpacked(_eval_mask_launch(p_d, g_d, None, True)[0], b, MASK_OUT)
     return [dict(biou=float(raw[i, 8]), d=d, n_gt_band=int(raw[i, 1]), n_pred_band=int(counts[i, 1]) // 255) for i in range(b)]
 
 
-SEG_METRICS = ["pixel_acc", "mean_acc", "miou", "fwiou", "colour_rmse"]  # gp_eval_seg's out[2 .. 6]; eval_metrics.SEG_METRICS
-SEG_OUT = 8        # n, n_void, the five metrics, n_classes; iou[K] follows
+SEG_OUT = 8        # n, n_void, SEG_METRICS (out[2 .. 6]), n_classes; iou[K] follows
 SEG_NSUM = 3       # n, n_void, sum_d in front of the K x K matrix of counts_out
-SEG_MAX_K = 192
 
 
 def _seg_pred(pred: torch.Tensor):
     """pred [B, 3, H, W] or [3, H, W], float or uint8 -> (contiguous fp32 / uint8 [B, 3, H, W], is_u8)"""
     if not torch.is_tensor(pred) or pred.dim() not in (3, 4) or pred.shape[-3] != 3:
         raise ValueError(f"pred: expected [B, 3, H, W] or [3, H, W], got {tuple(pred.shape) if torch.is_tensor(pred) else type(pred)}")
-    is_u8 = pred.dtype == torch.uint8
-    if not is_u8 and not pred.dtype.is_floating_point:
-        raise ValueError(f"pred: a float colour map in [0, 1] or its uint8 quantisation, got {pred.dtype}")
     if pred.dim() == 3:
         pred = pred[None]
     if min(pred.shape) < 1:
         raise ValueError(f"pred: empty map {tuple(pred.shape)}")
-    return (pred if is_u8 else pred.to(torch.float32)).contiguous(), is_u8
+    return _map8(pred, "pred")
 
 
 def _seg_palette(palette, device) -> torch.Tensor:
@@ -1306,10 +1271,8 @@ def seg_decode(pred: torch.Tensor, palette, want_dist: bool = False):
     b, _, h, w = (int(v) for v in pred.shape)
     labels = torch.empty((b, h, w), dtype=torch.uint8, device=pred.device)
     dist = torch.empty((b, h, w), dtype=torch.int32, device=pred.device) if want_dist else None
-    st = load_library().gp_seg_decode(pred.data_ptr(), int(is_u8), pal.data_ptr(), int(pal.shape[0]), b, h, w, labels.data_ptr(), _ptr(dist),
-                                      _stream_ptr(pred.device))
-    if st != GP_OK:
-        raise RuntimeError(f"gp_seg_decode failed ({st})")
+    _c_check(load_library().gp_seg_decode(pred.data_ptr(), int(is_u8), pal.data_ptr(), int(pal.shape[0]), b, h, w, labels.data_ptr(), _ptr(dist),
+                                          _stream_ptr(pred.device)), "gp_seg_decode")
     return (labels, dist) if want_dist else labels
 
 
@@ -1337,23 +1300,14 @@ def _eval_seg_launch(pred, gt, palette, region, gt_tol, want_counts: bool, want_
     if gt_tol < 0:
         raise ValueError(f"gt_tol: a squared distance >= 0, got {gt_tol}")
     if region is not None:
-        region = _eval_maps(region, "region")
-        if tuple(region.shape) != (b, h, w):
-            raise ValueError(f"region {tuple(region.shape)} does not match the maps {(b, h, w)}")
-        region = (region.contiguous().view(torch.uint8) if region.dtype in (torch.bool, torch.uint8) else (region != 0).view(torch.uint8)).contiguous()
-    assert pred.is_cuda and gt.is_cuda and (region is None or region.is_cuda)
+        region = _mask_u8(region, "region", (b, h, w))
+    assert pred.is_cuda and gt.is_cuda
     lib = load_library()
-    n_out, n_cnt = SEG_OUT + k, SEG_NSUM + k * k
-    buf = torch.empty((b * (n_out + (n_cnt if want_counts else 0)),), dtype=torch.int64, device=pred.device)
-    out = buf[:b * n_out].view(torch.float64).view(b, n_out)
-    counts = buf[b * n_out:].view(b, n_cnt) if want_counts else None
+    buf, out, counts = _packed(b, SEG_OUT + k, SEG_NSUM + k * k if want_counts else 0, pred.device)
     labels = torch.empty((b, h, w), dtype=torch.uint8, device=pred.device) if want_labels else None
-    nbytes = int(lib.gp_eval_seg_workspace(b, h, w, k))
-    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.int64, device=pred.device)
-    st = lib.gp_eval_seg(pred.data_ptr(), int(is_u8), gt.data_ptr(), int(labels_gt), gt_tol, _ptr(region), pal.data_ptr(), k, b, h, w, out.data_ptr(),
-                         _ptr(counts), _ptr(labels), ws.data_ptr(), nbytes, _stream_ptr(pred.device))
-    if st != GP_OK:
-        raise RuntimeError(f"gp_eval_seg failed ({st})")
+    ws, nbytes = _workspace(lib.gp_eval_seg_workspace(b, h, w, k), pred.device)
+    _c_check(lib.gp_eval_seg(pred.data_ptr(), int(is_u8), gt.data_ptr(), int(labels_gt), gt_tol, _ptr(region), pal.data_ptr(), k, b, h, w, out.data_ptr(),
+                             _ptr(counts), _ptr(labels), ws.data_ptr(), nbytes, _stream_ptr(pred.device)), "gp_eval_seg")
     return buf, out, counts, labels
 
 
@@ -1375,11 +1329,9 @@ def eval_seg(pred: torch.Tensor, gt: torch.Tensor, palette, region: Optional[tor
     """eval_metrics.seg_metrics for a batch of maps that are on the device (arguments as `eval_seg_raw`).  Returns one dict per image:
     SEG_METRICS, "n", "n_void", "n_classes", "iou" (float64 numpy [K]) and "conf" (int64 numpy [K, K], row = ground truth).  Raises ValueError
     naming the image when it has no scored pixel.  One device -> host copy of B x (8 + K + 3 + K * K) words."""
-    buf, out, counts, _ = _eval_seg_launch(pred, gt, palette, region, gt_tol, True, False)
-    b, n_out, n_cnt = out.shape[0], out.shape[1], counts.shape[1]
-    k = n_out - SEG_OUT
-    host = buf.cpu().numpy()
-    raw, cnt = host[:b * n_out].view("float64").reshape(b, n_out), host[b * n_out:].reshape(b, n_cnt)
+    buf, out, _, _ = _eval_seg_launch(pred, gt, palette, region, gt_tol, True, False)
+    k = out.shape[1] - SEG_OUT
+    raw, cnt = _unpacked(buf, out.shape[0], out.shape[1])
     res = []
     for i, row in enumerate(raw):
         if row[0] == 0:
@@ -1431,8 +1383,7 @@ def ensemble_reduce(depth: torch.Tensor, scale=None, shift=None, reduction: str 
     lib = load_library()
     pred = torch.empty((b, h, w), dtype=torch.float32, device=depth.device)
     unc = torch.empty((b, h, w), dtype=torch.float32, device=depth.device) if output_uncertainty else None
-    nbytes = int(lib.gp_ensemble_workspace(b, e, h, w))
-    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=depth.device)
+    ws, nbytes = _workspace(lib.gp_ensemble_workspace(b, e, h, w), depth.device)
     st = lib.gp_ensemble_reduce(depth.data_ptr(), par[0].data_ptr(), par[1].data_ptr() if shift is not None else None, b, e, h, w,
                                 ENSEMBLE_REDUCTION[reduction], pred.data_ptr(), _ptr(unc), ws.data_ptr(), nbytes, _stream_ptr(depth.device))
     if st != GP_OK:

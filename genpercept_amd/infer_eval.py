@@ -220,28 +220,13 @@ def run_inference(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_
             for (smp, _), out in zip(group, outs):
                 written.append(save(smp[0], out.pred_np))
         return written
+    loaded = _decode_ahead(samples, lambda s: load(s[0]), prefetch)  # (a decode error surfaces at the image it belongs to)
     if prefetch <= 0 or len(samples) < 2:
-        for s in samples:
-            written.append(save(s[0], infer(load(s[0])).pred_np))
-        return written
-    from collections import deque
+        return [save(s[0], infer(img).pred_np) for s, img in loaded]
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=1) as loader, ThreadPoolExecutor(max_workers=1) as writer:
-        pending, saves = deque(), []
-        it = iter(samples)
-        for s in it:
-            pending.append((s[0], loader.submit(load, s[0])))
-            if len(pending) > prefetch:
-                break
-        while pending:
-            rgb_rel, fut = pending.popleft()
-            img = fut.result()                       # (a decode error surfaces here, at the image it belongs to)
-            nxt = next(it, None)
-            if nxt is not None:
-                pending.append((nxt[0], loader.submit(load, nxt[0])))
-            saves.append(writer.submit(save, rgb_rel, infer(img).pred_np))
-        written = [f.result() for f in saves]
-    return written
+    with ThreadPoolExecutor(max_workers=1) as writer:
+        saves = [writer.submit(save, s[0], infer(img).pred_np) for s, img in loaded]
+        return [f.result() for f in saves]
 
 
 def _write_metric_files(output_dir: str, tag: str, names: List[str], per_sample, result: Dict[str, float], header: str) -> None:
@@ -272,32 +257,65 @@ def _write_normal_eval_files(output_dir: str, names: List[str], per_sample, resu
     _write_metric_files(output_dir, "-normal", names, per_sample, result, header)
 
 
+def _gt_rel(s: Sequence[str], gt_column: int) -> Optional[str]:
+    """The ground-truth path of a filename-list line, None where the column is absent or "None"."""
+    return s[gt_column] if len(s) > gt_column and s[gt_column] != "None" else None
+
+
+def _pred_name(rgb_rel: str, name_mode: FileNameMode, suffix: str = ".npy") -> str:
+    return os.path.join(os.path.dirname(rgb_rel), get_pred_name(os.path.basename(rgb_rel), name_mode, suffix=suffix))
+
+
+def _same_size(smp: Sequence[str], pred_shape, gt_shape) -> None:
+    if tuple(pred_shape) != tuple(gt_shape):
+        raise ValueError(f"{smp[0]}: prediction {tuple(pred_shape)} and ground truth {tuple(gt_shape)} differ in size")
+
+
+def _region(region_of: Optional[Callable], smp: Sequence[str], gt: np.ndarray) -> Optional[np.ndarray]:
+    """`region_of(sample, gt)` as a bool array of the ground truth's height and width (None without region_of)."""
+    if region_of is None:
+        return None
+    r = np.asarray(region_of(smp, gt)) != 0
+    if r.shape != gt.shape[:2]:
+        raise ValueError(f"{smp[0]}: region {r.shape} and ground truth {gt.shape[:2]} differ in size")
+    return r
+
+
+def _evaluate_files(prediction_dir: str, samples: Sequence[Sequence[str]], gt_column: int, pred_name_of: Callable, score: Callable, names: List[str]):
+    """The skeleton of the file routes: samples without ground truth (column gt_column absent or "None") or without a prediction file are
+    skipped; `score(sample, ground-truth path, prediction path)` reads both, checks their sizes and returns the image's metric dict.
+    Returns (rows [(prediction name, values in `names` order)], the means of the per-image values: eval.py's reduction)."""
+    sums = {k: 0.0 for k in names}
+    per_sample = []
+    for s in samples:
+        rel = _gt_rel(s, gt_column)
+        if rel is None:
+            continue
+        pred_name = pred_name_of(s)
+        pred_path = os.path.join(prediction_dir, pred_name)
+        if not os.path.exists(pred_path):
+            continue
+        m = score(s, rel, pred_path)
+        for k in names:
+            sums[k] += m[k]
+        per_sample.append((pred_name, [m[k] for k in names]))
+    n = len(per_sample)
+    return per_sample, {k: (sums[k] / n if n else float("nan")) for k in names}
+
+
 def evaluate_predictions(prediction_dir: str, base_dir: str, samples: Sequence[Sequence[str]], dataset: str = "nyu",
                          alignment: str = "least_square", alignment_max_res: Optional[int] = None, output_dir: Optional[str] = None,
                          pred_suffix: str = ".npy", read_gt: Optional[Callable[[str], np.ndarray]] = None) -> Dict[str, float]:
     """eval.py:143-244: mean of the per-image metrics; optionally writes `eval_metrics-<alignment>.txt` and `per_sample_metrics-...csv`."""
     cfg = DATASETS[dataset]
     names = list(em.METRICS.keys())
-    sums = {k: 0.0 for k in names}
-    per_sample = []
-    n = 0
-    for s in samples:
-        rgb_rel, depth_rel = s[0], s[1]
-        if depth_rel == "None":
-            continue
+
+    def score(s, depth_rel, pred_path):
         gt = read_gt(os.path.join(base_dir, depth_rel)) if read_gt else read_gt_depth(os.path.join(base_dir, depth_rel), dataset)
         vm = dataset_valid_mask(gt, dataset, os.path.join(base_dir, s[2]) if cfg.get("mask_from_file") and len(s) > 2 else None)
-        pred_name = os.path.join(os.path.dirname(rgb_rel), get_pred_name(os.path.basename(rgb_rel), cfg["name_mode"], suffix=pred_suffix))
-        pred_path = os.path.join(prediction_dir, pred_name)
-        if not os.path.exists(pred_path):
-            continue
-        pred = np.load(pred_path)
-        m = em.evaluate_depth(pred, gt, vm, cfg["min_depth"], cfg["max_depth"], alignment=alignment, alignment_max_res=alignment_max_res)
-        for k in names:
-            sums[k] += m[k]
-        per_sample.append((pred_name, [m[k] for k in names]))
-        n += 1
-    result = {k: (sums[k] / n if n else float("nan")) for k in names}
+        return em.evaluate_depth(np.load(pred_path), gt, vm, cfg["min_depth"], cfg["max_depth"], alignment=alignment, alignment_max_res=alignment_max_res)
+
+    per_sample, result = _evaluate_files(prediction_dir, samples, 1, lambda s: _pred_name(s[0], cfg["name_mode"], pred_suffix), score, names)
     if output_dir is not None:
         _write_eval_files(output_dir, alignment, names, per_sample, result, prediction_dir, dataset)
     return result
@@ -326,14 +344,6 @@ def normal_valid_mask(gt: np.ndarray) -> np.ndarray:
     return (np.asarray(gt) != 0).any(axis=0)
 
 
-def _normal_path(s: Sequence[str], gt_column: int) -> Optional[str]:
-    return s[gt_column] if len(s) > gt_column and s[gt_column] != "None" else None
-
-
-def _normal_pred_name(rgb_rel: str, name_mode: FileNameMode) -> str:
-    return os.path.join(os.path.dirname(rgb_rel), get_pred_name(os.path.basename(rgb_rel), name_mode, suffix=".npy"))
-
-
 def evaluate_normal_predictions(prediction_dir: str, base_dir: str, samples: Sequence[Sequence[str]], name_mode: FileNameMode, gt_column: int = 3,
                                 output_dir: Optional[str] = None, read_gt: Optional[Callable[[str], np.ndarray]] = None) -> Dict[str, float]:
     """The `.npy` route for what `run_inference(mode="normal")` writes ([H, W, 3] in [0, 1]): per image decode_normals ->
@@ -341,27 +351,14 @@ def evaluate_normal_predictions(prediction_dir: str, base_dir: str, samples: Seq
     path (column gt_column absent or "None") or without a prediction file are skipped.  Optionally writes `eval_metrics-normal.txt` and
     `per_sample_metrics-normal.csv`."""
     names = list(NORMAL_METRICS)
-    sums = {k: 0.0 for k in names}
-    per_sample = []
-    n = 0
-    for s in samples:
-        rel = _normal_path(s, gt_column)
-        if rel is None:
-            continue
-        pred_name = _normal_pred_name(s[0], name_mode)
-        pred_path = os.path.join(prediction_dir, pred_name)
-        if not os.path.exists(pred_path):
-            continue
+
+    def score(s, rel, pred_path):
         gt = (read_gt or read_gt_normal)(os.path.join(base_dir, rel))
         pred = em.decode_normals(np.load(pred_path))
-        if tuple(pred.shape) != tuple(gt.shape):
-            raise ValueError(f"{s[0]}: prediction {tuple(pred.shape)} and ground truth {tuple(gt.shape)} differ in size")
-        m = em.normal_angular_error(pred, gt, normal_valid_mask(gt))
-        for k in names:
-            sums[k] += m[k]
-        per_sample.append((pred_name, [m[k] for k in names]))
-        n += 1
-    result = {k: (sums[k] / n if n else float("nan")) for k in names}
+        _same_size(s, pred.shape, gt.shape)
+        return em.normal_angular_error(pred, gt, normal_valid_mask(gt))
+
+    per_sample, result = _evaluate_files(prediction_dir, samples, gt_column, lambda s: _pred_name(s[0], name_mode), score, names)
     if output_dir is not None:
         _write_normal_eval_files(output_dir, names, per_sample, result, prediction_dir, gt_column)
     return result
@@ -382,7 +379,7 @@ def _all_reduce_sum(acc: np.ndarray) -> np.ndarray:
 
 def _evaluation_loop(samples: Sequence[Sequence[str]], keep: Callable, load: Callable, score_group: Callable, names: List[str], batch_size: int,
                      rank: int, world: int, prefetch: int):
-    """The skeleton `infer_and_evaluate` and `infer_and_evaluate_normals` share.  `samples` filtered by `keep`, then sharded
+    """The sharding and combining core under `_infer_and_score`.  `samples` filtered by `keep`, then sharded
     (`shard_range`), the index in the filtered list riding along; images decoded ahead by `load(sample)` and grouped by size, at most batch_size
     per group; `score_group([((index, sample), image), ...])` -> one list of metric values (in `names` order) per image.  With
     torch.distributed initialised the rows of all ranks are combined: float64 sums and a count by all_reduce, rows by all_gather_object.
@@ -416,9 +413,56 @@ def _evaluation_loop(samples: Sequence[Sequence[str]], keep: Callable, load: Cal
     return rows, result, writer
 
 
-def _save_prediction(prediction_dir: str, pred_name: str, pred_np: np.ndarray) -> None:
-    os.makedirs(os.path.dirname(os.path.join(prediction_dir, pred_name)), exist_ok=True)
-    np.save(os.path.join(prediction_dir, pred_name), pred_np)
+def _infer_options(denoise_steps, ensemble_size, processing_res, match_input_res, resample_method, fix_timesteps, prompt) -> dict:
+    """The inference options a device loop passes through, as the keyword arguments of `pipe.predict_batch_device`."""
+    return dict(processing_res=processing_res, match_input_res=match_input_res, resample_method=resample_method, fix_timesteps=fix_timesteps,
+                prompt=prompt, denoising_steps=denoise_steps, ensemble_size=ensemble_size)
+
+
+def _upload(arrays, device):
+    """the arrays of a batch stacked and sent to the device (one copy, not waited for)"""
+    import torch
+    return torch.from_numpy(np.stack(arrays)).to(device, non_blocking=True)
+
+
+def _infer_and_score(pipe, base_dir: str, samples, mode: str, channels: int, infer_options: dict, keep: Callable, read_gt: Callable, gt_dims: int,
+                     score_batch: Callable, names: List[str], pred_name_of: Callable, batch_size: int, rank: int, world: int, prefetch: int,
+                     save_predictions: bool, prediction_dir: Optional[str], output_dir: Optional[str], rgb_crop: Optional[Callable] = None):
+    """The skeleton of the device loops, on top of `_evaluation_loop`.  Per batch: `pipe.predict_batch_device(images, mode, **infer_options)`
+    gives [B, channels, H, W] maps that stay on the device; `read_gt(sample)` decodes each ground truth on the host, its first gt_dims
+    dimensions checked against the last gt_dims of the maps (2: H x W, 3: a [3, H, W] ground truth); `score_batch(pred, gts, samples,
+    indices)` uploads and scores them: one metric dict per image.  save_predictions: the maps are also written as `run_inference` would,
+    [H, W] or [H, W, 3] `.npy` under prediction_dir (default: output_dir).  Returns (means over all samples, the rows of the per-sample file
+    if this rank is to write the files -- output_dir given and rank 0 -- else None, prediction_dir, the number of images of all ranks)."""
+    if prediction_dir is None:
+        prediction_dir = output_dir
+    if save_predictions and prediction_dir is None:
+        raise ValueError("save_predictions needs prediction_dir or output_dir")
+
+    def score_group(group):
+        smps = [smp for (_, smp), _ in group]
+        pred = pipe.predict_batch_device([img for _, img in group], mode, **infer_options)
+        if pred.dim() != 4 or pred.shape[0] != len(group) or pred.shape[1] != channels:
+            raise ValueError(f"evaluation in mode {mode!r} needs {'one' if channels == 1 else 'three'}-channel maps [B, {channels}, H, W], got "
+                             f"{tuple(pred.shape)}")
+        gts = []
+        for smp in smps:
+            gt = np.asarray(read_gt(smp))
+            _same_size(smp, pred.shape[-gt_dims:], gt.shape[:gt_dims])
+            gts.append(gt)
+        metrics = score_batch(pred, gts, smps, [idx for (idx, _), _ in group])
+        assert len(metrics) == len(group)
+        if save_predictions:
+            pred_host = (pred[:, 0] if channels == 1 else pred).cpu().numpy()
+            for smp, p in zip(smps, pred_host):
+                os.makedirs(os.path.dirname(os.path.join(prediction_dir, pred_name_of(smp))), exist_ok=True)
+                np.save(os.path.join(prediction_dir, pred_name_of(smp)), p if channels == 1 else np.transpose(p, (1, 2, 0)))
+        return [[m[k] for k in names] for m in metrics]
+
+    rows, result, writer = _evaluation_loop(samples, keep, lambda smp: _load_rgb(base_dir, smp[0], rgb_crop), score_group, names, batch_size, rank,
+                                            world, prefetch)
+    per_sample = [(pred_name_of(smp), vals) for _, smp, vals in rows] if output_dir is not None and writer else None
+    return result, per_sample, prediction_dir, len(rows)
 
 
 def infer_and_evaluate(pipe, base_dir: str, samples: Sequence[Sequence[str]], dataset: str, output_dir: Optional[str] = None, batch_size: int = 4,
@@ -434,46 +478,24 @@ def infer_and_evaluate(pipe, base_dir: str, samples: Sequence[Sequence[str]], da
     under prediction_dir (default: output_dir).  With torch.distributed initialised the per-image rows of all ranks are combined (float64
     sums and a count by all_reduce, rows by all_gather_object); rank 0 writes `eval_metrics-<alignment>.txt` and
     `per_sample_metrics-<alignment>.csv` with rows in sample order; every rank returns the means over all samples."""
-    import torch
     cfg = DATASETS[dataset]
     names = list(em.METRICS.keys())
     if evaluator is None:
         from .engine import eval_depth as evaluator
-    if prediction_dir is None:
-        prediction_dir = output_dir
-    if save_predictions and prediction_dir is None:
-        raise ValueError("save_predictions needs prediction_dir or output_dir")
-    rgb_crop = kitti_benchmark_crop if cfg.get("kitti_bm_crop") else None
 
-    def pred_name_of(smp):
-        return os.path.join(os.path.dirname(smp[0]), get_pred_name(os.path.basename(smp[0]), cfg["name_mode"], suffix=".npy"))
+    def score_batch(pred, gts, smps, _):
+        vms = [dataset_valid_mask(gt, dataset, os.path.join(base_dir, smp[2]) if cfg.get("mask_from_file") and len(smp) > 2 else None)
+               for gt, smp in zip(gts, smps)]
+        return evaluator(pred[:, 0], _upload(gts, pred.device), _upload(vms, pred.device), alignment, alignment_max_res, cfg["min_depth"],
+                         cfg["max_depth"])[0]
 
-    def score_group(group):
-        pred = pipe.predict_batch_device([img for _, img in group], mode, processing_res=processing_res, match_input_res=match_input_res,
-                                         resample_method=resample_method, fix_timesteps=fix_timesteps, prompt=prompt,
-                                         denoising_steps=denoise_steps, ensemble_size=ensemble_size)
-        if pred.dim() != 4 or pred.shape[0] != len(group) or pred.shape[1] != 1:
-            raise ValueError(f"depth evaluation needs one-channel maps [B, 1, H, W], got {tuple(pred.shape)} for mode {mode!r}")
-        gts, vms = [], []
-        for (_, smp), _ in group:
-            gt = read_gt_depth(os.path.join(base_dir, smp[1]), dataset)
-            if tuple(gt.shape) != tuple(pred.shape[-2:]):
-                raise ValueError(f"{smp[0]}: prediction {tuple(pred.shape[-2:])} and ground truth {tuple(gt.shape)} differ in size")
-            gts.append(gt)
-            vms.append(dataset_valid_mask(gt, dataset, os.path.join(base_dir, smp[2]) if cfg.get("mask_from_file") and len(smp) > 2 else None))
-        gt_t = torch.from_numpy(np.stack(gts)).to(pred.device, non_blocking=True)
-        vm_t = torch.from_numpy(np.stack(vms)).to(pred.device, non_blocking=True)
-        metrics = evaluator(pred[:, 0], gt_t, vm_t, alignment, alignment_max_res, cfg["min_depth"], cfg["max_depth"])[0]
-        if save_predictions:
-            pred_host = pred[:, 0].cpu().numpy()
-            for j, ((_, smp), _) in enumerate(group):
-                _save_prediction(prediction_dir, pred_name_of(smp), pred_host[j])
-        return [[metrics[j][k] for k in names] for j in range(len(group))]
-
-    rows, result, writer = _evaluation_loop(samples, lambda s: len(s) < 2 or s[1] != "None", lambda smp: _load_rgb(base_dir, smp[0], rgb_crop),
-                                            score_group, names, batch_size, rank, world, prefetch)
-    if output_dir is not None and writer:
-        _write_eval_files(output_dir, alignment, names, [(pred_name_of(smp), vals) for _, smp, vals in rows], result, prediction_dir, dataset)
+    options = _infer_options(denoise_steps, ensemble_size, processing_res, match_input_res, resample_method, fix_timesteps, prompt)
+    result, per_sample, prediction_dir, _ = _infer_and_score(
+        pipe, base_dir, samples, mode, 1, options, lambda s: len(s) < 2 or s[1] != "None",
+        lambda smp: read_gt_depth(os.path.join(base_dir, smp[1]), dataset), 2, score_batch, names, lambda smp: _pred_name(smp[0], cfg["name_mode"]),
+        batch_size, rank, world, prefetch, save_predictions, prediction_dir, output_dir, kitti_benchmark_crop if cfg.get("kitti_bm_crop") else None)
+    if per_sample is not None:
+        _write_eval_files(output_dir, alignment, names, per_sample, result, prediction_dir, dataset)
     return result
 
 
@@ -490,40 +512,20 @@ def infer_and_evaluate_normals(pipe, base_dir: str, samples: Sequence[Sequence[s
     image is `evaluate_normal_predictions`' quantity; sharding, the torch.distributed combination, the rank-0 files (`eval_metrics-normal.txt`,
     `per_sample_metrics-normal.csv`) and the return value on every rank are `infer_and_evaluate`'s.  save_predictions: the maps are also
     written as `run_inference(mode="normal")` would, [H, W, 3] `.npy` under prediction_dir (default: output_dir)."""
-    import torch
     names = list(NORMAL_METRICS)
     if evaluator is None:
         from .engine import eval_normal as evaluator
-    if prediction_dir is None:
-        prediction_dir = output_dir
-    if save_predictions and prediction_dir is None:
-        raise ValueError("save_predictions needs prediction_dir or output_dir")
 
-    def score_group(group):
-        pred = pipe.predict_batch_device([img for _, img in group], "normal", processing_res=processing_res, match_input_res=match_input_res,
-                                         resample_method=resample_method, fix_timesteps=fix_timesteps, prompt=prompt,
-                                         denoising_steps=denoise_steps, ensemble_size=ensemble_size)
-        if pred.dim() != 4 or pred.shape[0] != len(group) or pred.shape[1] != 3:
-            raise ValueError(f"normal evaluation needs three-channel maps [B, 3, H, W], got {tuple(pred.shape)}")
-        gts = []
-        for (_, smp), _ in group:
-            gt = (read_gt or read_gt_normal)(os.path.join(base_dir, _normal_path(smp, gt_column)))
-            if tuple(gt.shape) != tuple(pred.shape[-3:]):
-                raise ValueError(f"{smp[0]}: prediction {tuple(pred.shape[-3:])} and ground truth {tuple(gt.shape)} differ in size")
-            gts.append(np.asarray(gt, dtype=np.float32))
-        gt_t = torch.from_numpy(np.stack(gts)).to(pred.device, non_blocking=True)
-        metrics = evaluator(pred, gt_t, None, True, False)[0]
-        if save_predictions:
-            pred_host = pred.cpu().numpy()
-            for j, ((_, smp), _) in enumerate(group):
-                _save_prediction(prediction_dir, _normal_pred_name(smp[0], name_mode), np.transpose(pred_host[j], (1, 2, 0)))
-        return [[metrics[j][k] for k in names] for j in range(len(group))]
+    def score_batch(pred, gts, smps, _):
+        return evaluator(pred, _upload([np.asarray(gt, dtype=np.float32) for gt in gts], pred.device), None, True, False)[0]
 
-    rows, result, writer = _evaluation_loop(samples, lambda s: _normal_path(s, gt_column) is not None, lambda smp: _load_rgb(base_dir, smp[0], None),
-                                            score_group, names, batch_size, rank, world, prefetch)
-    if output_dir is not None and writer:
-        _write_normal_eval_files(output_dir, names, [(_normal_pred_name(smp[0], name_mode), vals) for _, smp, vals in rows], result, prediction_dir,
-                                 gt_column)
+    options = _infer_options(denoise_steps, ensemble_size, processing_res, match_input_res, resample_method, fix_timesteps, prompt)
+    result, per_sample, prediction_dir, _ = _infer_and_score(
+        pipe, base_dir, samples, "normal", 3, options, lambda s: _gt_rel(s, gt_column) is not None,
+        lambda smp: (read_gt or read_gt_normal)(os.path.join(base_dir, _gt_rel(smp, gt_column))), 3, score_batch, names,
+        lambda smp: _pred_name(smp[0], name_mode), batch_size, rank, world, prefetch, save_predictions, prediction_dir, output_dir)
+    if per_sample is not None:
+        _write_normal_eval_files(output_dir, names, per_sample, result, prediction_dir, gt_column)
     return result
 
 
@@ -558,19 +560,6 @@ def _read_mask_prediction(path: str) -> np.ndarray:
     return read_gt_mask(path)
 
 
-def _mask_pred_name(rgb_rel: str, name_mode: FileNameMode, suffix: str = ".npy") -> str:
-    return os.path.join(os.path.dirname(rgb_rel), get_pred_name(os.path.basename(rgb_rel), name_mode, suffix=suffix))
-
-
-def _mask_region(region_of: Optional[Callable], smp: Sequence[str], gt: np.ndarray) -> Optional[np.ndarray]:
-    if region_of is None:
-        return None
-    r = np.asarray(region_of(smp, gt)) != 0
-    if r.shape != gt.shape:
-        raise ValueError(f"{smp[0]}: region {r.shape} and ground truth {gt.shape} differ in size")
-    return r
-
-
 def _max_f_of_mean_curves(curve_sums: np.ndarray, n: int) -> float:
     """The usual dis protocol: max_t F_t of the DATASET-MEAN precision and recall curves.  curve_sums: float64 [512] = the per-image precision
     curves summed, then the recall curves; n images."""
@@ -593,23 +582,55 @@ def _sum_curves(counts_in_order) -> np.ndarray:
     return acc
 
 
-def _band_options(trimap_radius, trimap_metric, boundary_iou: bool, boundary_ratio: float, region_of) -> Tuple[List[str], str]:
-    """The extra column names (trimap, then boundary) and the header line of the band options; checks them."""
-    names, note = [], ""
-    if trimap_radius is None and not boundary_iou:
-        return names, note
-    if region_of is not None:
+def _mask_options(region_of, structure: bool, matting: bool, trimap_radius, trimap_metric, boundary_iou: bool, boundary_ratio: float,
+                  evaluators: Optional[dict] = None):
+    """The optional mask metrics of one call, checked, in column order: ([(column names, score, prefix errors)], all the column names, the
+    header lines of the band options).  score(pred, gt, region) -> one dict per image of a batch.  evaluators None: the file route, a batch is
+    one image and eval_metrics scores it; else the device loop's evaluator arguments by option (None: engine's), which take the same
+    arguments.  prefix errors: the option derives its region from the ground truth, so its ValueError has to name the images."""
+    if structure and region_of is not None:
+        raise ValueError("structure scores are whole-image quantities: structure=True does not go with region_of")
+    if (trimap_radius is not None or boundary_iou) and region_of is not None:
         raise ValueError("trimap_radius / boundary_iou derive their regions from the ground truth: they do not go with region_of")
+    options, note = [], ""
+
+    def add(columns, host, device, args_of, prefix=False):
+        if evaluators is None:
+            fn = getattr(em, host)
+            options.append((list(columns), lambda p, g, r: [fn(*args_of(p, g, r))], prefix))
+        else:
+            from . import engine
+            fn = evaluators.get(device) or getattr(engine, device)
+            options.append((list(columns), lambda p, g, r: fn(*args_of(p, g, r)), prefix))
+
+    if structure:
+        add(STRUCTURE_METRICS, "structure_metrics", "eval_structure", lambda p, g, r: (p, g))
+    if matting:
+        add(MATTING_METRICS, "matting_metrics", "eval_matting", lambda p, g, r: (p, g, r))
     if trimap_radius is not None:
         em.band_reach(trimap_radius, trimap_metric)  # (raises on a bad radius or metric)
-        names += list(TRIMAP_METRICS)
+        add(TRIMAP_METRICS, "trimap_metrics", "eval_trimap", lambda p, g, r: (p, g, trimap_radius, trimap_metric), prefix=True)
         note += f"    trimap from the ground truth: radius {trimap_radius:g}, metric {trimap_metric}\n"
     if boundary_iou:
         if not boundary_ratio > 0:
             raise ValueError(f"boundary_ratio is > 0, got {boundary_ratio}")
-        names += list(BOUNDARY_METRICS)
+        add(BOUNDARY_METRICS, "boundary_iou", "eval_boundary_iou", lambda p, g, r: (p, g, boundary_ratio))
         note += f"    boundary IoU: band of {boundary_ratio:g} of the image diagonal\n"
-    return names, note
+    return options, list(MASK_METRICS) + [k for columns, _, _ in options for k in columns], note
+
+
+def _with_mask_options(metrics: List[dict], options, pred, gt, region, who: Callable[[], str]) -> List[dict]:
+    """`metrics` (one dict per image of the batch pred, gt, region) with the columns of `_mask_options` added; who(): the images' names."""
+    for columns, score, prefix in options:
+        try:
+            more = score(pred, gt, region)
+        except ValueError as e:
+            if not prefix:
+                raise
+            raise ValueError(f"{who()}: {e}") from None
+        assert len(more) == len(metrics)
+        metrics = [dict(m, **{k: v[k] for k in columns}) for m, v in zip(metrics, more)]
+    return metrics
 
 
 def _write_mask_eval_files(output_dir: str, names: List[str], per_sample, result: Dict[str, float], prediction_dir: Optional[str],
@@ -636,46 +657,22 @@ def evaluate_mask_predictions(prediction_dir: str, base_dir: str, samples: Seque
     TRIMAP_METRICS over the transition region and the two sides of the trimap that the ground-truth alpha gives with a disc -- trimap_metric
     "euclidean" -- or a square -- "chebyshev" -- of that radius) as five more columns.  boundary_iou: Boundary IoU (eval_metrics.boundary_iou
     with boundary_ratio of the diagonal) as one more column, last.  Neither goes with region_of; a header line states radius, metric, ratio."""
-    if structure and region_of is not None:
-        raise ValueError("structure scores are whole-image quantities: structure=True does not go with region_of")
-    band_names, note = _band_options(trimap_radius, trimap_metric, boundary_iou, boundary_ratio, region_of)
-    names = list(MASK_METRICS) + (list(STRUCTURE_METRICS) if structure else []) + (list(MATTING_METRICS) if matting else []) + band_names
-    sums = {k: 0.0 for k in names}
-    per_sample, counts = [], []
-    for s in samples:
-        if len(s) < 2 or s[1] == "None":
-            continue
-        pred_name = _mask_pred_name(s[0], name_mode, pred_suffix)
-        pred_path = os.path.join(prediction_dir, pred_name)
-        if not os.path.exists(pred_path):
-            continue
-        gt = (read_gt or read_gt_mask)(os.path.join(base_dir, s[1]))
+    options, names, note = _mask_options(region_of, structure, matting, trimap_radius, trimap_metric, boundary_iou, boundary_ratio)
+    counts = []
+
+    def score(s, rel, pred_path):
+        gt = (read_gt or read_gt_mask)(os.path.join(base_dir, rel))
         pred = _read_mask_prediction(pred_path)
-        if tuple(pred.shape) != tuple(gt.shape):
-            raise ValueError(f"{s[0]}: prediction {tuple(pred.shape)} and ground truth {tuple(gt.shape)} differ in size")
-        region = _mask_region(region_of, s, gt)
+        _same_size(s, pred.shape, gt.shape)
+        region = _region(region_of, s, gt)
         c = em.mask_counts(em.quantize_mask(pred), gt, region)
         if c[0] == 0:
             raise ValueError(f"{s[0]}: no pixel to evaluate the mask on (n = 0)")
-        m = em.mask_metrics_from_counts(c)
-        if structure:
-            m.update(em.structure_metrics(pred, gt))
-        if matting:
-            m.update(em.matting_metrics(pred, gt, region))
-        if trimap_radius is not None:
-            try:
-                m.update(em.trimap_metrics(pred, gt, trimap_radius, trimap_metric))
-            except ValueError as e:
-                raise ValueError(f"{s[0]}: {e}") from None
-        if boundary_iou:
-            m.update(em.boundary_iou(pred, gt, boundary_ratio))
-        for k in names:
-            sums[k] += m[k]
-        per_sample.append((pred_name, [m[k] for k in names]))
         counts.append(c)
-    n = len(per_sample)
-    result = {k: (sums[k] / n if n else float("nan")) for k in names}
-    result["max_f_dataset"] = _max_f_of_mean_curves(_sum_curves(counts), n)
+        return _with_mask_options([em.mask_metrics_from_counts(c)], options, pred, gt, region, lambda: s[0])[0]
+
+    per_sample, result = _evaluate_files(prediction_dir, samples, 1, lambda s: _pred_name(s[0], name_mode, pred_suffix), score, names)
+    result["max_f_dataset"] = _max_f_of_mean_curves(_sum_curves(counts), len(per_sample))
     if output_dir is not None:
         _write_mask_eval_files(output_dir, names, per_sample, result, prediction_dir, note)
     return result
@@ -706,81 +703,32 @@ def infer_and_evaluate_masks(pipe, base_dir: str, samples: Sequence[Sequence[str
     the uploaded ground truth -- `trimap_evaluator`, `engine.eval_trimap` unless given: (pred, gt, radius, metric) -> one dict per image.
     boundary_iou: Boundary IoU as one more column (BOUNDARY_METRICS, last) -- `boundary_evaluator`, `engine.eval_boundary_iou` unless given:
     (pred, gt, ratio) -> one dict per image.  Neither goes with region_of; a header line of the text file states radius, metric and ratio."""
-    import torch
     if mode not in ("dis", "matting"):
         raise ValueError(f"mask evaluation is for mode 'dis' or 'matting', got {mode!r}")
-    if structure and region_of is not None:
-        raise ValueError("structure scores are whole-image quantities: structure=True does not go with region_of")
-    band_names, note = _band_options(trimap_radius, trimap_metric, boundary_iou, boundary_ratio, region_of)
-    names = list(MASK_METRICS) + (list(STRUCTURE_METRICS) if structure else []) + (list(MATTING_METRICS) if matting else []) + band_names
+    options, names, note = _mask_options(region_of, structure, matting, trimap_radius, trimap_metric, boundary_iou, boundary_ratio,
+                                         dict(eval_structure=structure_evaluator, eval_matting=matting_evaluator, eval_trimap=trimap_evaluator,
+                                              eval_boundary_iou=boundary_evaluator))
     if evaluator is None:
         from .engine import eval_mask as evaluator
-    if structure and structure_evaluator is None:
-        from .engine import eval_structure as structure_evaluator
-    if matting and matting_evaluator is None:
-        from .engine import eval_matting as matting_evaluator
-    if trimap_radius is not None and trimap_evaluator is None:
-        from .engine import eval_trimap as trimap_evaluator
-    if boundary_iou and boundary_evaluator is None:
-        from .engine import eval_boundary_iou as boundary_evaluator
-    if prediction_dir is None:
-        prediction_dir = output_dir
-    if save_predictions and prediction_dir is None:
-        raise ValueError("save_predictions needs prediction_dir or output_dir")
     counts = []  # (sample index, counts) of this rank's images
 
-    def score_group(group):
-        pred = pipe.predict_batch_device([img for _, img in group], mode, processing_res=processing_res, match_input_res=match_input_res,
-                                         resample_method=resample_method, fix_timesteps=fix_timesteps, prompt=prompt,
-                                         denoising_steps=denoise_steps, ensemble_size=ensemble_size)
-        if pred.dim() != 4 or pred.shape[0] != len(group) or pred.shape[1] != 1:
-            raise ValueError(f"mask evaluation needs one-channel maps [B, 1, H, W], got {tuple(pred.shape)} for mode {mode!r}")
-        gts, regions = [], []
-        for (_, smp), _ in group:
-            gt = (read_gt or read_gt_mask)(os.path.join(base_dir, smp[1]))
-            if tuple(gt.shape) != tuple(pred.shape[-2:]):
-                raise ValueError(f"{smp[0]}: prediction {tuple(pred.shape[-2:])} and ground truth {tuple(gt.shape)} differ in size")
-            gts.append(gt)
-            regions.append(_mask_region(region_of, smp, gt))
-        gt_t = torch.from_numpy(np.stack(gts)).to(pred.device, non_blocking=True)
-        region_t = torch.from_numpy(np.stack(regions)).to(pred.device, non_blocking=True) if region_of is not None else None
+    def score_batch(pred, gts, smps, indices):
+        gt_t = _upload(gts, pred.device)
+        region_t = _upload([_region(region_of, smp, gt) for smp, gt in zip(smps, gts)], pred.device) if region_of is not None else None
         metrics = evaluator(pred[:, 0], gt_t, region_t)
-        assert len(metrics) == len(group)
-        if structure:
-            more = structure_evaluator(pred[:, 0], gt_t)
-            assert len(more) == len(group)
-            metrics = [dict(m, **{k: s[k] for k in STRUCTURE_METRICS}) for m, s in zip(metrics, more)]
-        if matting:
-            more = matting_evaluator(pred[:, 0], gt_t, region_t)
-            assert len(more) == len(group)
-            metrics = [dict(m, **{k: s[k] for k in MATTING_METRICS}) for m, s in zip(metrics, more)]
-        if trimap_radius is not None:
-            try:
-                more = trimap_evaluator(pred[:, 0], gt_t, trimap_radius, trimap_metric)
-            except ValueError as e:
-                raise ValueError(f"{', '.join(smp[0] for (_, smp), _ in group)}: {e}") from None
-            assert len(more) == len(group)
-            metrics = [dict(m, **{k: s[k] for k in TRIMAP_METRICS}) for m, s in zip(metrics, more)]
-        if boundary_iou:
-            more = boundary_evaluator(pred[:, 0], gt_t, boundary_ratio)
-            assert len(more) == len(group)
-            metrics = [dict(m, **{k: s[k] for k in BOUNDARY_METRICS}) for m, s in zip(metrics, more)]
-        for ((idx, _), _), m in zip(group, metrics):
-            counts.append((idx, np.asarray(m["counts"])))
-        if save_predictions:
-            pred_host = pred[:, 0].cpu().numpy()
-            for j, ((_, smp), _) in enumerate(group):
-                _save_prediction(prediction_dir, _mask_pred_name(smp[0], name_mode), pred_host[j])
-        return [[metrics[j][k] for k in names] for j in range(len(group))]
+        assert len(metrics) == len(smps)
+        counts.extend((idx, np.asarray(m["counts"])) for idx, m in zip(indices, metrics))
+        return _with_mask_options(metrics, options, pred[:, 0], gt_t, region_t, lambda: ", ".join(smp[0] for smp in smps))
 
-    rows, result, writer = _evaluation_loop(samples, lambda s: len(s) > 1 and s[1] != "None", lambda smp: _load_rgb(base_dir, smp[0], None),
-                                            score_group, names, batch_size, rank, world, prefetch)
+    infer_options = _infer_options(denoise_steps, ensemble_size, processing_res, match_input_res, resample_method, fix_timesteps, prompt)
+    result, per_sample, prediction_dir, n = _infer_and_score(
+        pipe, base_dir, samples, mode, 1, infer_options, lambda s: _gt_rel(s, 1) is not None,
+        lambda smp: (read_gt or read_gt_mask)(os.path.join(base_dir, smp[1])), 2, score_batch, names, lambda smp: _pred_name(smp[0], name_mode),
+        batch_size, rank, world, prefetch, save_predictions, prediction_dir, output_dir)
     counts.sort(key=lambda c: c[0])
-    curve_sums = _all_reduce_sum(_sum_curves([c for _, c in counts]))
-    result["max_f_dataset"] = _max_f_of_mean_curves(curve_sums, len(rows))
-    if output_dir is not None and writer:
-        _write_mask_eval_files(output_dir, names, [(_mask_pred_name(smp[0], name_mode), vals) for _, smp, vals in rows], result, prediction_dir,
-                               note)
+    result["max_f_dataset"] = _max_f_of_mean_curves(_all_reduce_sum(_sum_curves([c for _, c in counts])), n)
+    if per_sample is not None:
+        _write_mask_eval_files(output_dir, names, per_sample, result, prediction_dir, note)
     return result
 
 
@@ -853,19 +801,6 @@ def _palette_and_names(palette) -> Tuple[np.ndarray, List[str]]:
     return np.ascontiguousarray(pal), names
 
 
-def _seg_path(s: Sequence[str], gt_column: int) -> Optional[str]:
-    return s[gt_column] if len(s) > gt_column and s[gt_column] != "None" else None
-
-
-def _seg_region(region_of: Optional[Callable], smp: Sequence[str], gt: np.ndarray) -> Optional[np.ndarray]:
-    if region_of is None:
-        return None
-    r = np.asarray(region_of(smp, gt)) != 0
-    if r.shape != gt.shape[:2]:
-        raise ValueError(f"{smp[0]}: region {r.shape} and ground truth {gt.shape[:2]} differ in size")
-    return r
-
-
 def _seg_dataset_values(result: Dict, conf_sum: np.ndarray, K: int) -> None:
     """The usual protocol: scores of the SUMMED confusion matrix of all images (float64 [K * K], exact below 2^53) into `result`."""
     conf = [int(v) for v in conf_sum]
@@ -896,30 +831,19 @@ def evaluate_seg_predictions(prediction_dir: str, base_dir: str, samples: Sequen
     pal, class_names = _palette_and_names(palette)
     K = pal.shape[0]
     names = list(SEG_METRICS)
-    sums = {k: 0.0 for k in names}
-    per_sample = []
     conf_sum = np.zeros(K * K, dtype=np.float64)
-    for s in samples:
-        rel = _seg_path(s, gt_column)
-        if rel is None:
-            continue
-        pred_name = _mask_pred_name(s[0], name_mode, pred_suffix)
-        pred_path = os.path.join(prediction_dir, pred_name)
-        if not os.path.exists(pred_path):
-            continue
+
+    def score(s, rel, pred_path):
         gt = (read_gt or read_gt_seg)(os.path.join(base_dir, rel))
         pred = _read_seg_prediction(pred_path)
-        if tuple(pred.shape[:2]) != tuple(gt.shape[:2]):
-            raise ValueError(f"{s[0]}: prediction {tuple(pred.shape[:2])} and ground truth {tuple(gt.shape[:2])} differ in size")
-        m = em.seg_metrics(pred, gt, pal, _seg_region(region_of, s, gt), gt_tol)
+        _same_size(s, pred.shape[:2], gt.shape[:2])
+        m = em.seg_metrics(pred, gt, pal, _region(region_of, s, gt), gt_tol)
         if m["n"] == 0:
             raise ValueError(f"{s[0]}: no pixel to evaluate the segmentation on (n = 0)")
-        for k in names:
-            sums[k] += m[k]
-        per_sample.append((pred_name, [m[k] for k in names]))
-        conf_sum += m["conf"].reshape(-1)
-    n = len(per_sample)
-    result = {k: (sums[k] / n if n else float("nan")) for k in names}
+        conf_sum[:] += m["conf"].reshape(-1)
+        return m
+
+    per_sample, result = _evaluate_files(prediction_dir, samples, gt_column, lambda s: _pred_name(s[0], name_mode, pred_suffix), score, names)
     _seg_dataset_values(result, conf_sum, K)
     if output_dir is not None:
         _write_seg_eval_files(output_dir, names, per_sample, result, prediction_dir, gt_column, class_names)
@@ -947,46 +871,27 @@ def infer_and_evaluate_seg(pipe, base_dir: str, samples: Sequence[Sequence[str]]
     names = list(SEG_METRICS)
     if evaluator is None:
         from .engine import eval_seg as evaluator
-    if prediction_dir is None:
-        prediction_dir = output_dir
-    if save_predictions and prediction_dir is None:
-        raise ValueError("save_predictions needs prediction_dir or output_dir")
     conf_sum = np.zeros(K * K, dtype=np.float64)  # this rank's images
     pal_dev: dict = {}  # the palette goes up once per device
 
-    def score_group(group):
-        pred = pipe.predict_batch_device([img for _, img in group], "seg", processing_res=processing_res, match_input_res=match_input_res,
-                                         resample_method=resample_method, fix_timesteps=fix_timesteps, prompt=prompt,
-                                         denoising_steps=denoise_steps, ensemble_size=ensemble_size)
-        if pred.dim() != 4 or pred.shape[0] != len(group) or pred.shape[1] != 3:
-            raise ValueError(f"seg evaluation needs three-channel maps [B, 3, H, W], got {tuple(pred.shape)}")
-        gts, regions = [], []
-        for (_, smp), _ in group:
-            gt = np.asarray((read_gt or read_gt_seg)(os.path.join(base_dir, _seg_path(smp, gt_column))))
-            if tuple(gt.shape[:2]) != tuple(pred.shape[-2:]):
-                raise ValueError(f"{smp[0]}: prediction {tuple(pred.shape[-2:])} and ground truth {tuple(gt.shape[:2])} differ in size")
-            gts.append(gt)
-            regions.append(_seg_region(region_of, smp, gt))
+    def score_batch(pred, gts, smps, _):
+        regions = [_region(region_of, smp, gt) for smp, gt in zip(smps, gts)]
         if len({g.ndim for g in gts}) > 1:
             gts = [em.seg_gt_labels(g, pal, gt_tol) for g in gts]
         if pred.device not in pal_dev:
             pal_dev[pred.device] = torch.from_numpy(pal).to(pred.device)
-        gt_t = torch.from_numpy(np.stack(gts)).to(pred.device, non_blocking=True)
-        region_t = torch.from_numpy(np.stack(regions)).to(pred.device, non_blocking=True) if region_of is not None else None
-        metrics = evaluator(pred, gt_t, pal_dev[pred.device], region_t, gt_tol)
-        assert len(metrics) == len(group)
+        metrics = evaluator(pred, _upload(gts, pred.device), pal_dev[pred.device], _upload(regions, pred.device) if region_of is not None else None,
+                            gt_tol)
         for m in metrics:
             conf_sum[:] += np.asarray(m["conf"]).reshape(-1)
-        if save_predictions:
-            pred_host = pred.cpu().numpy()
-            for j, ((_, smp), _) in enumerate(group):
-                _save_prediction(prediction_dir, _mask_pred_name(smp[0], name_mode), np.transpose(pred_host[j], (1, 2, 0)))
-        return [[metrics[j][k] for k in names] for j in range(len(group))]
+        return metrics
 
-    rows, result, writer = _evaluation_loop(samples, lambda s: _seg_path(s, gt_column) is not None, lambda smp: _load_rgb(base_dir, smp[0], None),
-                                            score_group, names, batch_size, rank, world, prefetch)
+    options = _infer_options(denoise_steps, ensemble_size, processing_res, match_input_res, resample_method, fix_timesteps, prompt)
+    result, per_sample, prediction_dir, _ = _infer_and_score(
+        pipe, base_dir, samples, "seg", 3, options, lambda s: _gt_rel(s, gt_column) is not None,
+        lambda smp: (read_gt or read_gt_seg)(os.path.join(base_dir, _gt_rel(smp, gt_column))), 2, score_batch, names,
+        lambda smp: _pred_name(smp[0], name_mode), batch_size, rank, world, prefetch, save_predictions, prediction_dir, output_dir)
     _seg_dataset_values(result, _all_reduce_sum(conf_sum), K)
-    if output_dir is not None and writer:
-        _write_seg_eval_files(output_dir, names, [(_mask_pred_name(smp[0], name_mode), vals) for _, smp, vals in rows], result, prediction_dir,
-                              gt_column, class_names)
+    if per_sample is not None:
+        _write_seg_eval_files(output_dir, names, per_sample, result, prediction_dir, gt_column, class_names)
     return result

@@ -70,6 +70,20 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def time_events(call, iters):
+    """ms per call: device events around `iters` back-to-back calls after a warm-up of three"""
+    for _ in range(3):
+        call()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        call()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
 def case(b, h, w, seed):
     rng = np.random.default_rng(seed)
     yy, xx = np.meshgrid(np.linspace(0, 1, h, dtype=np.float32), np.linspace(0, 1, w, dtype=np.float32), indexing="ij")
@@ -86,16 +100,7 @@ def bench_eval(b, h, w, iters, host_runs):
     d = torch.device("cuda", 0)
     pred, gt, mask = case(b, h, w, 1)
     tp, tg, tm = (torch.from_numpy(x).to(d) for x in (pred, gt, mask))
-    for _ in range(3):
-        ge.eval_depth_raw(tp, tg, tm, "least_square", None, 1e-3, 10.0)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        ge.eval_depth_raw(tp, tg, tm, "least_square", None, 1e-3, 10.0)
-    e1.record()
-    torch.cuda.synchronize()
-    dev_ms = e0.elapsed_time(e1) / iters
+    dev_ms = time_events(lambda: ge.eval_depth_raw(tp, tg, tm, "least_square", None, 1e-3, 10.0), iters)
     t0 = time.perf_counter()
     metrics, _ = ge.eval_depth(tp, tg, tm, "least_square", None, 1e-3, 10.0)  # with the 14-double copy and the host synchronise
     call_ms = (time.perf_counter() - t0) * 1e3
@@ -135,16 +140,7 @@ def bench_eval_normal(b, h, w, iters, host_runs):
     d = torch.device("cuda", 0)
     enc, gt = normal_case(b, h, w, 2)
     tp, tg = (torch.from_numpy(x).to(d) for x in (enc, gt))
-    for _ in range(3):
-        ge.eval_normal_raw(tp, tg)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        ge.eval_normal_raw(tp, tg)
-    e1.record()
-    torch.cuda.synchronize()
-    dev_ms = e0.elapsed_time(e1) / iters
+    dev_ms = time_events(lambda: ge.eval_normal_raw(tp, tg), iters)
     t0 = time.perf_counter()
     metrics, n_valid = ge.eval_normal(tp, tg)  # with the 8-double copy and the host synchronise
     call_ms = (time.perf_counter() - t0) * 1e3
@@ -177,16 +173,7 @@ def mask_case(b, h, w, seed, kind):
 def copy_bandwidth(d, nbytes=1 << 28, iters=20):
     """Device-to-device copy of nbytes: GB/s of traffic (read + write), device events over `iters` copies after a warm-up."""
     src, dst = torch.empty(nbytes, dtype=torch.uint8, device=d).random_(0, 256), torch.empty(nbytes, dtype=torch.uint8, device=d)
-    for _ in range(3):
-        dst.copy_(src)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        dst.copy_(src)
-    e1.record()
-    torch.cuda.synchronize()
-    return 2 * nbytes / (e0.elapsed_time(e1) / iters) / 1e6
+    return 2 * nbytes / time_events(lambda: dst.copy_(src), iters) / 1e6
 
 
 def time_eval_mask(tp, tg, iters):
@@ -203,16 +190,7 @@ def time_eval_mask(tp, tg, iters):
         st = lib.gp_eval_mask(tp.data_ptr(), int(tp.dtype == torch.uint8), tg.data_ptr(), None, b, h, w, out.data_ptr(), None, ws.data_ptr(), nbytes, stream)
         assert st == ge.GP_OK, st
 
-    for _ in range(3):
-        call()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        call()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
+    return time_events(call, iters)
 
 
 def bench_eval_mask(b, h, w, kind, iters, host_runs, copy_gb_per_s):
@@ -266,16 +244,7 @@ def time_eval_structure(tp, tg, iters):
                                    stream)
         assert st == ge.GP_OK, st
 
-    for _ in range(3):
-        call()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        call()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
+    return time_events(call, iters)
 
 
 def bench_eval_structure(b, h, w, kind, iters, host):
@@ -338,16 +307,7 @@ def time_eval_matting(tp, tg, iters):
                                  ws.data_ptr(), nbytes, stream)
         assert st == ge.GP_OK, st
 
-    for _ in range(3):
-        call()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        call()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
+    return time_events(call, iters)
 
 
 def bench_eval_matting(b, h, w, iters, host):
@@ -387,19 +347,6 @@ def seg_case(b, h, w, K, seed):
     off = rng.rand(b, h, w) < 0.04
     gt[off] = rng.randint(0, 256, (int(off.sum()), 3)).astype(np.uint8)
     return pred, np.ascontiguousarray(gt), pal
-
-
-def time_events(call, iters):
-    for _ in range(3):
-        call()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        call()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
 
 
 def bench_eval_seg(b, h, w, K, iters, host):
