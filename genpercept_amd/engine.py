@@ -167,6 +167,8 @@ SYMBOLS = {
     "gp_eval_seg": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _ll, _vp]),
     "gp_mask_band_workspace": (_ll, [_i, _i, _i]),
     "gp_mask_band": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp]),
+    "gp_foreground_workspace": (_ll, [_i, _i, _i]),
+    "gp_foreground": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _ll, _vp]),
     "gp_ensemble_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gp_ensemble_workspace": (_ll, [_i, _i, _i, _i]),
     "gp_ensemble_reduce": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
@@ -1235,6 +1237,72 @@ def eval_boundary_iou(pred: torch.Tensor, gt: torch.Tensor, ratio: float = 0.02)
     p_d = mask_band(pred, 127, 128, d, "chebyshev", True, want=("inner",))["inner"]
     raw, counts = _unpacked(_eval_mask_launch(p_d, g_d, None, True)[0], b, MASK_OUT)
     return [dict(biou=float(raw[i, 8]), d=d, n_gt_band=int(raw[i, 1]), n_pred_band=int(counts[i, 1]) // 255) for i in range(b)]
+
+
+FOREGROUND_OUTPUTS = ["fg", "bg", "rgba", "comp"]
+
+
+def foreground(image: torch.Tensor, alpha: torch.Tensor, background=None, want: Sequence[str] = ("rgba",), reg: float = 1e-5, gw: float = 1.0,
+               n_small: int = 10, n_big: int = 2):
+    """gp_foreground on device tensors: image uint8 [B, 3, H, W] or [3, H, W]; alpha [B, H, W], [B, 1, H, W] or [H, W], a float map in [0, 1]
+    (quantised to 8 bits by the kernel) or uint8.  Returns a dict of the outputs named in `want` (FOREGROUND_OUTPUTS): fg, bg float32
+    [B, 3, H, W] (the estimated foreground and background colours), rgba uint8 [B, H, W, 4] (the cutout), comp uint8 [B, 3, H, W] (the
+    foreground over `background`: a uint8 [B, 3, H, W] / [3, H, W] device image or one colour of three bytes).  Definition in
+    include/genpercept_hip.h; genpercept_amd/foreground.py gives the same bits.  Enqueued on the current stream, no synchronisation."""
+    from .foreground import check_options
+    lib = load_library()
+    if not torch.is_tensor(image) or image.dtype != torch.uint8 or image.dim() not in (3, 4) or image.shape[-3] != 3:
+        raise ValueError(f"image: uint8 [B, 3, H, W] or [3, H, W], got {image.dtype if torch.is_tensor(image) else type(image)} "
+                         f"{tuple(image.shape) if torch.is_tensor(image) else ''}")
+    image = (image[None] if image.dim() == 3 else image).contiguous()
+    alpha = _eval_maps(alpha, "alpha")
+    assert image.is_cuda and alpha.is_cuda
+    b, _, h, w = (int(v) for v in image.shape)
+    if tuple(alpha.shape) != (b, h, w):
+        raise ValueError(f"alpha {tuple(alpha.shape)} does not match the images {(b, h, w)}")
+    if h > 16384 or w > 16384:
+        raise ValueError(f"cutouts take images of at most 16384 x 16384, got {h} x {w}")
+    reg, gw, n_small, n_big = check_options(reg, gw, n_small, n_big)
+    want = list(want)
+    if not want or any(k not in FOREGROUND_OUTPUTS for k in want) or len(set(want)) != len(want):
+        raise ValueError(f"want names one or more of {FOREGROUND_OUTPUTS}, got {want}")
+    new_bg, new_rgb = None, 0
+    if "comp" in want:
+        if background is None:
+            raise ValueError("the composite needs a background: a uint8 image or one colour")
+        if torch.is_tensor(background) and background.dim() >= 3:
+            new_bg = (background[None] if background.dim() == 3 else background)
+            if new_bg.dtype != torch.uint8 or tuple(new_bg.shape) != (b, 3, h, w) or new_bg.device != image.device:
+                raise ValueError(f"background: uint8 {(b, 3, h, w)} on the images' device, got {new_bg.dtype} {tuple(new_bg.shape)}")
+            new_bg = new_bg.contiguous()
+        else:
+            rgb = [int(v) for v in (background.tolist() if hasattr(background, "tolist") else background)]
+            if len(rgb) != 3 or any(not 0 <= v <= 255 for v in rgb):
+                raise ValueError(f"background: one colour is three bytes, got {background!r}")
+            new_rgb = rgb[0] << 16 | rgb[1] << 8 | rgb[2]
+    alpha, is_u8 = _map8(alpha, "alpha")
+    kinds = dict(fg=((b, 3, h, w), torch.float32), bg=((b, 3, h, w), torch.float32), rgba=((b, h, w, 4), torch.uint8), comp=((b, 3, h, w), torch.uint8))
+    outs = {k: torch.empty(kinds[k][0], dtype=kinds[k][1], device=image.device) for k in want}
+    ws, nbytes = _workspace(lib.gp_foreground_workspace(b, h, w), image.device)
+    st = lib.gp_foreground(image.data_ptr(), alpha.data_ptr(), int(is_u8), b, h, w, float(reg), float(gw), n_small, n_big, _ptr(new_bg), new_rgb,
+                           *[_ptr(outs.get(k)) for k in FOREGROUND_OUTPUTS], ws.data_ptr(), nbytes, _stream_ptr(image.device))
+    if st == GP_ERR_INVALID:
+        raise ValueError(f"gp_foreground: invalid arguments (images {(b, h, w)}, reg = {reg}, gw = {gw}, n_small = {n_small}, n_big = {n_big})")
+    _c_check(st, "gp_foreground")
+    return outs
+
+
+def estimate_foreground(image: torch.Tensor, alpha: torch.Tensor, reg: float = 1e-5, gw: float = 1.0, n_small: int = 10, n_big: int = 2):
+    """foreground.estimate_foreground for a batch on the device (arguments as `foreground`): (F, B), float32 [B, 3, H, W] each."""
+    o = foreground(image, alpha, want=("fg", "bg"), reg=reg, gw=gw, n_small=n_small, n_big=n_big)
+    return o["fg"], o["bg"]
+
+
+def cutout(image: torch.Tensor, alpha: torch.Tensor, background=None, reg: float = 1e-5, gw: float = 1.0, n_small: int = 10, n_big: int = 2):
+    """The cutout of a batch on the device (arguments as `foreground`): without a background the RGBA image uint8 [B, H, W, 4]
+    (foreground.cutout_rgba), with one the composite over it, uint8 [B, 3, H, W] (foreground.composite).  The float planes are not written."""
+    k = "rgba" if background is None else "comp"
+    return foreground(image, alpha, background, want=(k,), reg=reg, gw=gw, n_small=n_small, n_big=n_big)[k]
 
 
 SEG_OUT = 8        # n, n_void, SEG_METRICS (out[2 .. 6]), n_classes; iou[K] follows

@@ -229,6 +229,39 @@ def run_inference(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_
         return [f.result() for f in saves]
 
 
+def run_cutouts(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_dir: str, name_mode: FileNameMode, mode: str = "matting",
+                batch_size: int = 1, rank: int = 0, world: int = 1, background=None, prefetch: int = 2, foreground_options: Optional[dict] = None,
+                **inference_options) -> List[str]:
+    """One cutout per sample with `pipe.cutout_batch_device` (modes matting and dis): an RGBA `.png` whose colours are the estimated foreground
+    colours and whose A is the predicted alpha byte, or, with a `background` (one colour of three bytes, or a uint8 [3, H, W] image for samples of
+    that size), the RGB composite over it.  Batching and sharding as `run_inference`: consecutive samples of one image size go through one call,
+    up to batch_size of them; world > 1: this call handles `shard_range(len(samples), rank, world)` of the list.  Returns the paths written."""
+    import torch
+    if mode not in ("matting", "dis"):
+        raise ValueError(f"cutouts need an alpha map: mode 'matting' or 'dis', got {mode!r}")
+    if world > 1:
+        lo, hi = _shard(len(samples), rank, world)
+        samples = samples[lo:hi]
+    written = []
+    for group in _size_groups(_decode_ahead(samples, lambda s: _load_rgb(base_dir, s[0], None), prefetch), max(1, batch_size)):
+        bg = background
+        if torch.is_tensor(bg) and bg.dim() == 3:
+            bg = bg[None].expand(len(group), -1, -1, -1)
+        out, _ = pipe.cutout_batch_device([img for _, img in group], mode, bg, foreground_options, **inference_options)
+        out = out.cpu().numpy()
+        assert len(out) == len(group)
+        for (smp, _), px in zip(group, out):
+            scene_dir = os.path.join(output_dir, os.path.dirname(smp[0]))
+            os.makedirs(scene_dir, exist_ok=True)
+            save_to = os.path.join(scene_dir, get_pred_name(os.path.basename(smp[0]), name_mode, suffix=".png"))
+            if background is None:
+                Image.fromarray(px).save(save_to)
+            else:
+                Image.fromarray(np.ascontiguousarray(np.moveaxis(px, 0, -1))).save(save_to)
+            written.append(save_to)
+    return written
+
+
 def _write_metric_files(output_dir: str, tag: str, names: List[str], per_sample, result: Dict[str, float], header: str) -> None:
     """`per_sample_metrics<tag>.csv` (one row per prediction file) and `eval_metrics<tag>.txt` (header, metric names, means)."""
     os.makedirs(output_dir, exist_ok=True)

@@ -529,6 +529,42 @@ class GenPerceptPipeline:
         opts = dict(steps=steps, ensemble_size=int(ensemble_size), batch_size=max(1, int(ensemble_size)), generator=generator, ensemble_kwargs=None)
         return self._predict_device(images, processing_res, match_input_res, resample, fix_timesteps, prompt, opts)[0]
 
+    @torch.no_grad()
+    def cutout_batch_device(self, images: Union[Sequence[Image.Image], torch.Tensor], mode: str = "matting", background=None,
+                            foreground_options: Optional[dict] = None, **inference_options):
+        """What a user of a matting model does with the alpha, without a trip to the host: images of one common size (PIL images or a uint8
+        [B,3,H,W] tensor) -> (cutout, alpha), both ON THE DEVICE.  alpha is the fp32 [B,1,H,W] map of `predict_batch_device(images, mode,
+        **inference_options)` at the input size; cutout is the uint8 [B,H,W,4] RGBA image whose colours are the foreground colours estimated
+        under that alpha (engine.cutout, gp_foreground) or, with a `background` (a uint8 [B,3,H,W] / [3,H,W] image or one colour of three
+        bytes), the uint8 [B,3,H,W] composite over it.  foreground_options: reg, gw, n_small, n_big of engine.cutout.  Modes matting and dis."""
+        from . import engine as ge
+        if mode not in ("matting", "dis"):
+            raise ValueError(f"cutouts need an alpha map: mode 'matting' or 'dis', got {mode!r}")
+        if inference_options.get("match_input_res", True) is not True:
+            raise ValueError("cutouts are made at the input size: match_input_res stays True")
+        if not torch.is_tensor(images):
+            images = torch.stack([torch.from_numpy(np.asarray(im.convert("RGB")).copy()).permute(2, 0, 1) for im in images])
+        if images.dtype != torch.uint8:
+            raise ValueError(f"cutouts take 8-bit images, got {images.dtype}")
+        alpha = self.predict_batch_device(images, mode, **inference_options)
+        rgb = images.to(alpha.device, non_blocking=True)
+        if torch.is_tensor(background):
+            background = background.to(alpha.device, non_blocking=True)
+        return ge.cutout(rgb, alpha, background, **(foreground_options or {})), alpha
+
+    def cutout(self, image: Image.Image, mode: str = "matting", background=None, foreground_options: Optional[dict] = None,
+               **inference_options) -> Image.Image:
+        """`cutout_batch_device` for one PIL image: the RGBA cutout as a PIL image (an RGB composite when a background is given: a PIL image
+        of the same size, a uint8 [3,H,W] tensor or one colour)."""
+        if isinstance(background, Image.Image):
+            if background.size != image.size:
+                raise ValueError(f"the background {background.size} must have the image's size {image.size}")
+            background = torch.from_numpy(np.asarray(background.convert("RGB")).copy()).permute(2, 0, 1).contiguous()
+        out, _ = self.cutout_batch_device([image], mode, background, foreground_options, **inference_options)
+        if background is None:
+            return Image.fromarray(out[0].cpu().numpy())
+        return Image.fromarray(np.ascontiguousarray(out[0].permute(1, 2, 0).cpu().numpy()))
+
     def _run_device(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None) -> List[GenPerceptOutput]:
         """Pre / post processing on the GPU (gp_preprocess / gp_postprocess): the image goes up once, resize_max_res, the model, the
         resize back to the input size, clip, colour map and the 8-bit image all run on the device; pred_np and the coloured bytes come down.

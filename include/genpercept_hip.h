@@ -24,6 +24,8 @@
  *                       colour output against the RGB label image of column 6   src/dataset/base_dataset.py:333-346,366; run.py:449-455
  *   gp_mask_band      (no reference code) the trimap of a ground-truth alpha (dilate(alpha != 0) - erode(alpha == 255)) and the inner boundary
  *                       band of Boundary IoU, as region planes for gp_eval_mask
+ *   gp_foreground     (no reference code) what a user does with a matting / dis alpha: the foreground colours by multi-level foreground
+ *                       estimation (Germer et al. 2020), the RGBA cutout and the composite over a new background
  *   gp_ensemble_gather, gp_ensemble_reduce
  *                     ensemble_depth's tensor half (the BFGS fit stays on the host)   genpercept/util/ensemble.py:43-205;
  *                                                                   genpercept_pipeline.py:289-298
@@ -438,6 +440,42 @@ gp_status gp_mask_band(const void* a, int a_is_u8, int B, int H, int W, int lo, 
                        unsigned char* band_out, unsigned char* fg_out, unsigned char* bg_out, unsigned char* inner_out,
                        unsigned char* trimap_out /* each [B][H][W] or NULL, at least one non-NULL */, void* workspace,
                        long long workspace_bytes, void* stream);
+
+/* ---- matting cutouts on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation; csrc/foreground.hip) ----
+ * Multiplying the image by alpha is not a cutout: where 0 < a < 1 the pixel is a F + (1 - a) B and the old background bleeds in.  gp_foreground
+ * estimates the foreground colour F (and the background colour B) by the multi-level method of Germer et al. 2020 ("Fast Multi-Level Foreground
+ * Estimation", pymatting's estimate_foreground_ml).  genpercept_amd/foreground.py is the same definition on the host and gives the same bits.
+ * Inputs per image: image uint8 [3][H][W]; alpha uint8 [H][W] (alpha_is_u8 = 1) or fp32 [H][W] (alpha_is_u8 = 0), quantised first by
+ *   gp_eval_mask's rule, q = (unsigned char)(clamp(x, 0, 1) * 255.0f), NaN -> 0 (run.py:449-455).  I = byte / 255, a = byte / 255, one
+ *   float32 division each.  1 <= H, W <= 16384.
+ * Arithmetic: float32 throughout; the only operations are + - * / abs min max in exactly the order written below; no fused multiply-add;
+ *   division is correctly rounded.  max(v, 0) is (v > 0 ? v : 0) and min(v, 1) is (v < 1 ? v : 1).
+ * Levels: L = ceil(log2(max(H, W))), 0 for a 1 x 1 image.  Level l = 0 .. L has h_l = (H + 2^(L-l) - 1) >> (L-l) and w_l likewise (integers;
+ *   level 0 is 1 x 1, level L is H x W; pymatting's round(w0 ** (l / L)) is deliberately not used: no size depends on a pow).  Every level
+ *   samples image and alpha from the full-resolution bytes, nearest: src = ((y * H) / h_l, (x * W) / w_l).  F and B of level l start as the
+ *   nearest upsample of level l-1's result, ((y * h_{l-1}) / h_l, (x * w_{l-1}) / w_l); at level 0, F = B = I.
+ * Iterations: a level with h_l <= 32 and w_l <= 32 takes n_small (default 10, 0 .. 64), every other level n_big (default 2, 1 .. 4).  Jacobi:
+ *   each reads only the previous iterate.  One iteration at a pixel, neighbours in the order left, right, up, down, coordinates clamped to
+ *   the level:
+ *     a1 = 1 - a;  a00 = a*a;  a01 = a*a1;  a11 = a1*a1;  b0[c] = a*I[c];  b1[c] = a1*I[c]
+ *     for each neighbour n:  da = reg + gw*|a - a_n|;  a00 += da;  a11 += da;  b0[c] += da*F_n[c];  b1[c] += da*B_n[c]
+ *     det = a00*a11 - a01*a01;  inv = 1/det
+ *     F[c] = min(max(inv*(a11*b0[c] - a01*b1[c]), 0), 1);   B[c] = min(max(inv*(a00*b1[c] - a01*b0[c]), 0), 1)
+ *   reg: default 1e-5, range [1e-6, 1] (below it det is no longer safely positive in float32); gw: default 1, range [0, 100].
+ * Outputs, each optional, at least one given: fg_out, bg_out fp32 [B][3][H][W];  rgba_out uint8 [B][H][W][4], RGB = min(255, (int)(F*255 + 0.5f)),
+ *   A = the alpha byte;  comp_out uint8 [B][3][H][W] = (a*F) + ((1-a)*N) quantised the same way, N = byte / 255 of new_bg uint8 [B][3][H][W]
+ *   or, new_bg == NULL, of the one colour new_rgb = 0xRRGGBB.
+ * 1 + (levels above 32 x 32) kernel launches on `stream` for every B, no atomics, nothing read back; an image's result is bitwise the same
+ * from call to call and in every batch.  workspace: DEVICE scratch of at least the workspace entry's byte count (8-byte aligned), free again
+ * once the stream has passed the call.  image, a uint8 alpha, new_bg and comp_out may start at any byte.
+ * GP_ERR_INVALID before any HIP call: null image / alpha / workspace, all four outputs null, B < 1, B > 65535, H or W outside 1 .. 16384,
+ * alpha_is_u8 outside 0..1, reg, gw, n_small or n_big outside their ranges (NaN included), new_rgb outside 0 .. 0xffffff, a float alpha or
+ * fg_out / bg_out / rgba_out not 4-byte aligned, workspace not 8-byte aligned, workspace_bytes too small. */
+long long gp_foreground_workspace(int B, int H, int W);       /* bytes; 0 for B, H or W < 1 or H, W > 16384; proportional to B; multiple of 8 */
+gp_status gp_foreground(const unsigned char* image, const void* alpha, int alpha_is_u8, int B, int H, int W, float reg, float gw, int n_small,
+                        int n_big, const unsigned char* new_bg /* [B][3][H][W] or NULL */, int new_rgb, float* fg_out, float* bg_out,
+                        unsigned char* rgba_out, unsigned char* comp_out /* at least one non-NULL */, void* workspace,
+                        long long workspace_bytes, void* stream);
 
 /* ---- test-time ensembling on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation, no atomics; csrc/ensemble.hip) ----
  * The tensor half of ensemble_depth (genpercept/util/ensemble.py:43-205, called at genpercept_pipeline.py:289-298) for the E members of each of

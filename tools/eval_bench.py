@@ -55,6 +55,22 @@
    `eval_metrics.mask_band` / `trimap_metrics` / `boundary_iou` on the same arrays on the host (wall clock, one run).  Planes and values are
    compared on the spot (bit-equal).  The band call's bytes -- the 1 + planes per pixel it has to move, and the 18 + planes it does move with
    its scratch word -- are set against the device-to-device copy bandwidth measured in the same process.  `--no-host` skips the host route.
+
+  python tools/eval_bench.py --foreground --out profiles/<name>.json
+
+9. `--foreground` (instead of 1 and 2): the `gp_foreground` entry behind `engine.cutout` (multi-level foreground estimation: one coarse launch
+   and one launch per level above 32 x 32; the RGBA cutout alone is written) at 4 x 480 x 640 and 1 x 2048 x 2048 on the alpha-like input
+   of `--matting` under a two-gradient image: device events around `iters` back-to-back calls after a warm-up, for the C entry on
+   preallocated buffers and for `engine.cutout` itself, against `foreground.cutout_rgba` on the same arrays on the host (wall clock, one run);
+   the cutouts are compared on the spot (bit-equal).  Per-level kernel times come from a kernel trace taken in a run of its own,
+
+     rocprofv3 --kernel-trace --output-format csv -d <dir> -- python tools/eval_bench.py --foreground --trace-run
+     python tools/eval_bench.py --foreground --kernel-trace <dir>/.../<pid>_kernel_trace.csv --out profiles/<name>.json
+
+   (`--trace-run`: the device calls alone, nothing timed; `--kernel-trace`: the median duration of each launch of a call, per shape, and the
+   bytes the last level has to move -- image, alpha, the level below's F and B, the RGBA bytes -- over its time, next to the
+   device-to-device copy bandwidth measured in the same process).  Without a trace the per-level fields say "not measured".  `--n-big N`
+   sets the iterations of the levels above 32 x 32 (default 2); a level launch with N = 1 is what one launch of a plain, unfused form costs.
 Needs a GPU; there is no CPU fall-back."""
 import argparse
 import json
@@ -439,6 +455,96 @@ def bench_band(b, h, w, iters, host, copy_gb_per_s):
     return res
 
 
+FOREGROUND_SHAPES = ((4, 480, 640), (1, 2048, 2048))
+
+
+def foreground_case(b, h, w, seed):
+    """An image of two colour gradients mixed by the alpha-like map of `matting_case` (+ noise), and that map's bytes."""
+    from genpercept_amd import eval_metrics as em
+    rng = np.random.default_rng(seed)
+    _, gt = matting_case(b, h, w, seed)
+    a = gt.astype(np.float32)[:, None] / 255.0
+    yy, xx = np.meshgrid(np.linspace(0, 1, h, dtype=np.float32), np.linspace(0, 1, w, dtype=np.float32), indexing="ij")
+    fg = np.stack([0.75 + 0.2 * xx, 0.15 + 0.2 * xx, 0.1 + 0.1 * xx])[None]
+    bg = np.stack([0.1 + 0.1 * yy, 0.25 + 0.2 * yy, 0.65 + 0.3 * yy])[None]
+    img = a * fg + (1 - a) * bg + 0.01 * rng.standard_normal((b, 3, h, w), dtype=np.float32)
+    return em.quantize_mask(img), gt
+
+
+def foreground_level_times(trace_csv):
+    """{number of level launches of a call: [median ms of the coarse launch, of each level launch]} from a rocprofv3 kernel trace of
+    `--foreground --trace-run` (the first three calls of each shape are its warm-up)."""
+    import csv
+    rows = []
+    with open(trace_csv, newline="") as f:
+        for r in csv.DictReader(f):
+            name = r["Kernel_Name"]
+            if "fg_coarse_kernel" in name or "fg_level_kernel" in name:
+                rows.append((int(r["Start_Timestamp"]), "fg_coarse_kernel" in name, (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6))
+    rows.sort()
+    calls, cur = [], None
+    for _, coarse, ms in rows:
+        if coarse:
+            cur = [ms]
+            calls.append(cur)
+        elif cur is not None:
+            cur.append(ms)
+    out = {}
+    for n in sorted({len(c) - 1 for c in calls}):
+        timed = [c for c in calls if len(c) - 1 == n][3:]
+        if timed:
+            out[n] = [float(np.median([c[j] for c in timed])) for j in range(n + 1)]
+    return out
+
+
+def bench_foreground(b, h, w, iters, host, copy_gb_per_s, level_ms, trace_run, n_big=2):
+    from genpercept_amd import engine as ge
+    from genpercept_amd import foreground as fgh
+    d = torch.device("cuda", 0)
+    lib = ge.load_library()
+    img, a8 = foreground_case(b, h, w, 5)
+    ti, ta = torch.from_numpy(img).to(d), torch.from_numpy(a8).to(d)
+    nbytes = int(lib.gp_foreground_workspace(b, h, w))
+    ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=d)
+    rgba = torch.empty((b, h, w, 4), dtype=torch.uint8, device=d)
+    stream = int(torch.cuda.current_stream(d).cuda_stream)
+
+    def entry():
+        rc = lib.gp_foreground(ti.data_ptr(), ta.data_ptr(), 1, b, h, w, 1e-5, 1.0, 10, n_big, None, 0, None, None, rgba.data_ptr(), None, ws.data_ptr(), nbytes,
+                               stream)
+        assert rc == ge.GP_OK, rc
+
+    sizes = fgh.level_sizes(h, w)
+    above = [s for s in sizes if s[0] > fgh.SMALL or s[1] > fgh.SMALL]
+    if trace_run:
+        for _ in range(3 + iters):
+            entry()
+        torch.cuda.synchronize()
+        return dict(shape=[b, h, w], launches_per_call=1 + len(above))
+    entry_ms = time_events(entry, iters)
+    call_ms = time_events(lambda: ge.cutout(ti, ta, n_big=n_big), iters)
+    got = ge.cutout(ti, ta, n_big=n_big).cpu().numpy()
+    (hp, wp), (hl, wl) = sizes[-2], sizes[-1]
+    last_bytes = b * (hl * wl * (3 + 1 + 4) + hp * wp * 24)
+    res = dict(shape=[b, h, w], input="two gradients under an alpha-like map", options=dict(fgh.DEFAULTS, n_big=n_big), levels=[list(s) for s in sizes],
+               gp_foreground_ms_per_call=entry_ms, engine_cutout_ms_per_call=call_ms, device_iters=iters, launches_per_call=1 + len(above),
+               workspace_bytes=nbytes, last_level_bytes_needed=last_bytes, copy_gb_per_s=copy_gb_per_s,
+               last_level_bytes_alone_ms=last_bytes / copy_gb_per_s / 1e6)
+    ms = level_ms.get(len(above))
+    if ms:
+        res.update(coarse_launch_ms=ms[0], level_launch_ms=[dict(level=list(s), ms=t) for s, t in zip(above, ms[1:])], launches_sum_ms=float(sum(ms)),
+                   last_level_gb_per_s=last_bytes / ms[-1] / 1e6, last_level_over_copy_rate=last_bytes / ms[-1] / 1e6 / copy_gb_per_s)
+    else:
+        res.update(coarse_launch_ms="not measured", level_launch_ms="not measured", last_level_gb_per_s="not measured")
+    if host:
+        t0 = time.perf_counter()
+        ref = [fgh.cutout_rgba(img[i], a8[i], n_big=n_big) for i in range(b)]
+        host_ms = (time.perf_counter() - t0) * 1e3
+        assert all(np.array_equal(got[i], ref[i]) for i in range(b))
+        res.update(host_cutout_rgba_ms=host_ms, host_runs=1, host_over_engine_call=host_ms / call_ms, cutout_equals_host=True)
+    return res
+
+
 def bench_loop(n_images, batch_sizes, repeats):
     from PIL import Image
     from genpercept_amd import GenPerceptPipeline
@@ -495,11 +601,26 @@ def main():
     ap.add_argument("--matting", action="store_true", help="time gp_eval_matting against matting_metrics instead")
     ap.add_argument("--seg", action="store_true", help="time gp_eval_seg against seg_metrics instead")
     ap.add_argument("--band", action="store_true", help="time gp_mask_band, eval_trimap and eval_boundary_iou against their host routes instead")
-    ap.add_argument("--no-host", action="store_true", help="with --structure, --matting, --seg or --band: the device calls alone")
+    ap.add_argument("--foreground", action="store_true", help="time gp_foreground / engine.cutout against foreground.cutout_rgba instead")
+    ap.add_argument("--n-big", type=int, default=2, help="with --foreground: iterations of a level above 32 x 32 (1 .. 4)")
+    ap.add_argument("--trace-run", action="store_true", help="with --foreground: the device calls alone, for a kernel trace taken around this run")
+    ap.add_argument("--kernel-trace", default=None, help="with --foreground: the kernel trace csv of a --trace-run, for the per-level times")
+    ap.add_argument("--no-host", action="store_true", help="with --structure, --matting, --seg, --band or --foreground: the device calls alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU")
-    if a.band:
+    if a.foreground:
+        import bench
+        if a.trace_run:
+            print(json.dumps([bench_foreground(b, h, w, a.iters, False, 0.0, {}, True, a.n_big) for (b, h, w) in FOREGROUND_SHAPES]))
+            return
+        bw = copy_bandwidth(torch.device("cuda", 0))
+        level_ms = foreground_level_times(a.kernel_trace) if a.kernel_trace else {}
+        with bench.ClockPowerSampler("cuda:0") as clock:
+            rows = [bench_foreground(b, h, w, a.iters, not a.no_host, bw, level_ms, False, a.n_big) for (b, h, w) in FOREGROUND_SHAPES]
+        res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box", build_id=bench.source_build_id(), clock=clock.summary(),
+                   copy_gb_per_s=bw, per_level_times="rocprofv3 kernel trace of a separate run" if level_ms else "not measured", foreground=rows)
+    elif a.band:
         import bench
         bw = copy_bandwidth(torch.device("cuda", 0))
         with bench.ClockPowerSampler("cuda:0") as clock:
@@ -529,7 +650,7 @@ def main():
                    eval_normal=[bench_eval_normal(4, 480, 640, a.iters, 3), bench_eval_normal(1, 4032, 6048, a.iters, 1)])
     else:
         res = dict(device=torch.cuda.get_device_name(0), eval_depth=[bench_eval(1, 4032, 6048, a.iters, 1), bench_eval(4, 480, 640, a.iters, 3)])
-    if not a.skip_loop and not a.normals and not a.masks and not a.structure and not a.matting and not a.seg and not a.band:
+    if not a.skip_loop and not a.normals and not a.masks and not a.structure and not a.matting and not a.seg and not a.band and not a.foreground:
         res["infer_and_evaluate"] = bench_loop(16, (1, 4), 3)
     text = json.dumps(res, indent=1)
     print(text)
