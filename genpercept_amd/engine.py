@@ -169,6 +169,8 @@ SYMBOLS = {
     "gp_mask_band": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp]),
     "gp_foreground_workspace": (_ll, [_i, _i, _i]),
     "gp_foreground": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _ll, _vp]),
+    "gp_guided_upsample_workspace": (_ll, [_i, _i, _i, _i]),
+    "gp_guided_upsample": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, C.c_double, _vp, _vp, _ll, _vp]),
     "gp_ensemble_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gp_ensemble_workspace": (_ll, [_i, _i, _i, _i]),
     "gp_ensemble_reduce": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
@@ -1303,6 +1305,41 @@ def cutout(image: torch.Tensor, alpha: torch.Tensor, background=None, reg: float
     (foreground.cutout_rgba), with one the composite over it, uint8 [B, 3, H, W] (foreground.composite).  The float planes are not written."""
     k = "rgba" if background is None else "comp"
     return foreground(image, alpha, background, want=(k,), reg=reg, gw=gw, n_small=n_small, n_big=n_big)[k]
+
+
+def guided_upsample(guide_lo: torch.Tensor, pred: torch.Tensor, guide: torch.Tensor, radius: int = 4, eps: float = 1e-4) -> torch.Tensor:
+    """gp_guided_upsample on device tensors: guide_lo uint8 [B, 3, h, w] (the image at the processing size), pred float [B, C, h, w], C = 1 or
+    3 (the prediction at that size), guide uint8 [B, 3, H, W] (the image at the output size); a single image may come without the batch axis.
+    Returns float32 [B, C, H, W] in [0, 1]: the prediction upsampled with the image as guide (guided filter, window radius 1 .. 32, eps in
+    (0, 1]).  Definition in include/genpercept_hip.h; genpercept_amd/guided.py gives the same bits.  Allocates the workspace; enqueued on the
+    current stream, no synchronisation."""
+    from .guided import check_options
+    lib = load_library()
+    for name, g in (("guide_lo", guide_lo), ("guide", guide)):
+        if not torch.is_tensor(g) or g.dtype != torch.uint8 or g.dim() not in (3, 4) or g.shape[-3] != 3:
+            raise ValueError(f"{name}: uint8 [B, 3, H, W] or [3, H, W], got {g.dtype if torch.is_tensor(g) else type(g)} "
+                             f"{tuple(g.shape) if torch.is_tensor(g) else ''}")
+    if not torch.is_tensor(pred) or not pred.dtype.is_floating_point or pred.dim() not in (3, 4):
+        raise ValueError(f"pred: float [B, C, h, w] or [C, h, w], got {pred.dtype if torch.is_tensor(pred) else type(pred)}")
+    guide_lo = (guide_lo[None] if guide_lo.dim() == 3 else guide_lo).contiguous()
+    guide = (guide[None] if guide.dim() == 3 else guide).contiguous()
+    pred = (pred[None] if pred.dim() == 3 else pred).to(torch.float32).contiguous()
+    assert guide_lo.is_cuda and pred.is_cuda and guide.is_cuda
+    b, c, h, w = (int(v) for v in pred.shape)
+    hh, ww = int(guide.shape[-2]), int(guide.shape[-1])
+    if c not in (1, 3) or tuple(guide_lo.shape) != (b, 3, h, w) or guide.shape[0] != b:
+        raise ValueError(f"pred {tuple(pred.shape)} needs 1 or 3 channels, guide_lo {tuple(guide_lo.shape)} its size and guide {tuple(guide.shape)} its batch")
+    if max(h, w, hh, ww) > 16384 or min(h, w, hh, ww) < 1 or not 1 <= b <= 65535:
+        raise ValueError(f"guided upsampling takes 1 .. 65535 images with sides in 1 .. 16384, got {b} x {h} x {w} -> {hh} x {ww}")
+    radius, eps = check_options(radius, eps)
+    out = torch.empty((b, c, hh, ww), dtype=torch.float32, device=pred.device)
+    ws, nbytes = _workspace(lib.gp_guided_upsample_workspace(b, c, h, w), pred.device)
+    st = lib.gp_guided_upsample(guide_lo.data_ptr(), pred.data_ptr(), c, guide.data_ptr(), b, h, w, hh, ww, radius, eps, out.data_ptr(), ws.data_ptr(),
+                                nbytes, _stream_ptr(pred.device))
+    if st == GP_ERR_INVALID:
+        raise ValueError(f"gp_guided_upsample: invalid arguments ({(b, c, h, w)} -> {(hh, ww)}, radius = {radius}, eps = {eps})")
+    _c_check(st, "gp_guided_upsample")
+    return out
 
 
 SEG_OUT = 8        # n, n_void, SEG_METRICS (out[2 .. 6]), n_classes; iou[K] follows

@@ -385,7 +385,9 @@ class GenPerceptPipeline:
     def __call__(self, input_image: Union[Image.Image, torch.Tensor], denoising_steps: Optional[int] = None, ensemble_size: int = 1,
                  processing_res: Optional[int] = None, match_input_res: bool = True, resample_method: str = "bilinear", batch_size: int = 0,
                  generator=None, color_map: str = "Spectral", show_progress_bar: bool = True, ensemble_kwargs: Dict = None, mode=None,
-                 fix_timesteps=None, prompt="") -> GenPerceptOutput:
+                 fix_timesteps=None, prompt="", refine=None) -> GenPerceptOutput:
+        """genpercept_pipeline.py:146-337.  refine (new; None, True or dict(radius=..., eps=...)): the map is brought to the input size by the
+        guided filter with the image as guide (engine.guided_upsample) instead of the plain resize; uint8 images and match_input_res only."""
         assert mode is not None, "mode of GenPerceptPipeline can be chosen from ['depth', 'normal', 'seg', 'matting', 'dis']."
         self.mode = mode
         if denoising_steps is None:
@@ -420,7 +422,7 @@ class GenPerceptPipeline:
         assert batch_size >= 1
         opts = dict(steps=int(denoising_steps), ensemble_size=int(ensemble_size), batch_size=int(batch_size), generator=generator,
                     ensemble_kwargs=ensemble_kwargs)
-        outs = self._run(rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts)
+        outs = self._run(rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts, refine)
         return outs[0] if rgb.shape[0] == 1 else outs
 
     def _check_inference_step(self, n_step: int) -> None:
@@ -462,8 +464,9 @@ class GenPerceptPipeline:
 
     def infer_batch(self, images: Union[Sequence[Image.Image], torch.Tensor], mode: str, processing_res: Optional[int] = None,
                     match_input_res: bool = True, resample_method: str = "bilinear", color_map: Optional[str] = "Spectral", fix_timesteps=None,
-                    prompt="", denoising_steps: Optional[int] = None, ensemble_size: int = 1, generator=None) -> List[GenPerceptOutput]:
-        """Batch entry (new): images of one common size, one engine call; results are per image (DPT min-max per image)."""
+                    prompt="", denoising_steps: Optional[int] = None, ensemble_size: int = 1, generator=None, refine=None) -> List[GenPerceptOutput]:
+        """Batch entry (new): images of one common size, one engine call; results are per image (DPT min-max per image).  refine: as
+        `__call__`."""
         self.mode = mode
         if processing_res is None:
             processing_res = self.default_processing_resolution
@@ -474,24 +477,44 @@ class GenPerceptPipeline:
         if self.genpercept_pipeline:
             assert steps == 1 and ensemble_size == 1
         opts = dict(steps=steps, ensemble_size=int(ensemble_size), batch_size=max(1, int(ensemble_size)), generator=generator, ensemble_kwargs=None)
-        return self._run(images, processing_res, match_input_res, get_resample_method(resample_method), color_map, fix_timesteps, prompt, opts)
+        return self._run(images, processing_res, match_input_res, get_resample_method(resample_method), color_map, fix_timesteps, prompt, opts, refine)
 
-    def _run(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None) -> List[GenPerceptOutput]:
+    def _run(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None, refine=None) -> List[GenPerceptOutput]:
         from .engine import RESAMPLE_CODE
         # device pre / post for uint8 and fp32 images; fp16 / bf16 / fp64 tensors keep the host recipe, which -- like the reference
         # (genpercept_pipeline.py:240-247, image_util.py:75-105) -- resizes in the tensor's OWN dtype before the normalisation (the
         # device path would promote them to fp32 first and deviate slightly)
         if rgb.dtype in (torch.uint8, torch.float32) and resample in RESAMPLE_CODE and not os.environ.get("GENPERCEPT_HOST_PREPOST"):
-            return self._run_device(rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts)
-        return self._run_host(rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts)
+            return self._run_device(rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts, refine)
+        return self._run_host(rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts, refine)
 
-    def _predict_device(self, rgb, processing_res, match_input_res, resample, fix_timesteps, prompt, opts, color_map=None, q_bits=0):
+    @staticmethod
+    def _refine_options(refine, dtype, match_input_res) -> Optional[dict]:
+        """The `refine` argument of the entry points (None, True or dict(radius=..., eps=...)) as the options of `guided_upsample`, None when
+        absent.  The refinement works on the 8-bit image at the input size: float images and match_input_res=False are refused."""
+        if refine is None:
+            return None
+        from .guided import refine_options
+        opts = refine_options(refine)
+        if dtype != torch.uint8:
+            raise ValueError(f"refine takes 8-bit images (the image is the guide of the filter), got {dtype}")
+        if not match_input_res:
+            raise ValueError("refine upsamples the map to the input size: it needs match_input_res=True")
+        return opts
+
+    def _predict_device(self, rgb, processing_res, match_input_res, resample, fix_timesteps, prompt, opts, color_map=None, q_bits=0, refine=None):
         """The device half of __call__ up to the finished map: upload, gp_preprocess, the model, gp_postprocess to the output size (the input
         size with match_input_res), clip.  Returns (pred fp32 [B,C,H,W] in [0, 1], coloured uint8 [B,H,W,3] or None, quantised or None), all on
-        the device."""
+        the device.  refine: the map is brought to the input size by gp_guided_upsample instead -- the guide at the processing size is the
+        uint8 image gp_preprocess produced (what the model saw), the guide at the input size the uploaded image -- and gp_postprocess then runs
+        at that size (clip, colour map, quantisation).  A processing size that exceeds the input in either dimension: the map is resized to
+        the input size first and filtered there.  A map smaller than the processing size (the model rounds sides that are no multiple of its
+        latent stride down): the guide is the image resized to the map's size by gp_preprocess, as the plain resize takes the map to cover
+        the whole image."""
         from . import engine as ge
         input_size = rgb.shape
-        x = rgb.to(self._device, non_blocking=True)
+        refine = self._refine_options(refine, rgb.dtype, match_input_res)
+        full = x = rgb.to(self._device, non_blocking=True)
         size_in = tuple(int(v) for v in input_size[-2:])
         size_p = ge.resize_max_res_size(size_in[0], size_in[1], int(processing_res)) if processing_res > 0 else size_in
         if x.dtype == torch.uint8:
@@ -503,15 +526,24 @@ class GenPerceptPipeline:
         self._warn_if_saturated()
         size = tuple(int(v) for v in input_size[-2:]) if match_input_res else tuple(pred.shape[-2:])
         one_ch = pred.shape[1] == 1
+        if refine is not None:
+            guide_lo = x
+            if pred.shape[-2] > size_in[0] or pred.shape[-1] > size_in[1]:
+                pred, guide_lo = ge.postprocess(pred, size_in, resample)[0], full
+            elif tuple(pred.shape[-2:]) != tuple(x.shape[-2:]):  # the map covers the image on a grid of its own: the guide on that grid
+                guide_lo = ge.preprocess(full, tuple(int(v) for v in pred.shape[-2:]), resample)
+            pred = ge.guided_upsample(guide_lo, pred, full, **refine)
         return ge.postprocess(pred, size, resample, cmap=color_map if one_ch else None, q_bits=q_bits)
 
     @torch.no_grad()
     def predict_batch_device(self, images: Union[Sequence[Image.Image], torch.Tensor], mode: str, processing_res: Optional[int] = None,
                              match_input_res: bool = True, resample_method: str = "bilinear", fix_timesteps=None, prompt="",
-                             denoising_steps: Optional[int] = None, ensemble_size: int = 1, generator=None) -> torch.Tensor:
+                             denoising_steps: Optional[int] = None, ensemble_size: int = 1, generator=None, refine=None) -> torch.Tensor:
         """`infer_batch` without the trip to the host: images of one common size (PIL images, or a uint8 / fp32 [B,3,H,W] tensor) -> the
         finished maps as an fp32 [B,C,H,W] tensor ON THE DEVICE, resized to the input size (match_input_res) and clipped to [0, 1] -- the values
-        `infer_batch(...)[i].pred_np` holds.  For consumers that stay on the GPU (engine.eval_depth, infer_eval.infer_and_evaluate)."""
+        `infer_batch(...)[i].pred_np` holds.  For consumers that stay on the GPU (engine.eval_depth, infer_eval.infer_and_evaluate).  refine (None,
+        True or dict(radius=..., eps=...)): the maps come to the input size by engine.guided_upsample with the image as guide, not by the
+        plain resize (uint8 images and match_input_res only: ValueError otherwise)."""
         from .engine import RESAMPLE_CODE
         self.mode = mode
         if processing_res is None:
@@ -527,7 +559,7 @@ class GenPerceptPipeline:
         if self.genpercept_pipeline:
             assert steps == 1 and ensemble_size == 1
         opts = dict(steps=steps, ensemble_size=int(ensemble_size), batch_size=max(1, int(ensemble_size)), generator=generator, ensemble_kwargs=None)
-        return self._predict_device(images, processing_res, match_input_res, resample, fix_timesteps, prompt, opts)[0]
+        return self._predict_device(images, processing_res, match_input_res, resample, fix_timesteps, prompt, opts, refine=refine)[0]
 
     @torch.no_grad()
     def cutout_batch_device(self, images: Union[Sequence[Image.Image], torch.Tensor], mode: str = "matting", background=None,
@@ -536,7 +568,9 @@ class GenPerceptPipeline:
         [B,3,H,W] tensor) -> (cutout, alpha), both ON THE DEVICE.  alpha is the fp32 [B,1,H,W] map of `predict_batch_device(images, mode,
         **inference_options)` at the input size; cutout is the uint8 [B,H,W,4] RGBA image whose colours are the foreground colours estimated
         under that alpha (engine.cutout, gp_foreground) or, with a `background` (a uint8 [B,3,H,W] / [3,H,W] image or one colour of three
-        bytes), the uint8 [B,3,H,W] composite over it.  foreground_options: reg, gw, n_small, n_big of engine.cutout.  Modes matting and dis."""
+        bytes), the uint8 [B,3,H,W] composite over it.  foreground_options: reg, gw, n_small, n_big of engine.cutout.  Modes matting and dis.
+        inference_options may hold `refine` (True or dict(radius=..., eps=...)): the alpha then comes to the input size by the guided filter, and
+        the colours are estimated under that sharper alpha."""
         from . import engine as ge
         if mode not in ("matting", "dis"):
             raise ValueError(f"cutouts need an alpha map: mode 'matting' or 'dis', got {mode!r}")
@@ -565,7 +599,7 @@ class GenPerceptPipeline:
             return Image.fromarray(out[0].cpu().numpy())
         return Image.fromarray(np.ascontiguousarray(out[0].permute(1, 2, 0).cpu().numpy()))
 
-    def _run_device(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None) -> List[GenPerceptOutput]:
+    def _run_device(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None, refine=None) -> List[GenPerceptOutput]:
         """Pre / post processing on the GPU (gp_preprocess / gp_postprocess): the image goes up once, resize_max_res, the model, the
         resize back to the input size, clip, colour map and the 8-bit image all run on the device; pred_np and the coloured bytes come down.
         uint8 images (PIL input) stay uint8 up to the engine's prologue; float tensors (genpercept_trainer.py:1151-1165) are resized in fp32
@@ -573,7 +607,7 @@ class GenPerceptPipeline:
         if color_map is not None:
             assert self.mode in ["depth", "disparity"]
         pred_out, col, q8 = self._predict_device(rgb, processing_res, match_input_res, resample, fix_timesteps, prompt, opts, color_map,
-                                                 0 if color_map is not None else 8)
+                                                 0 if color_map is not None else 8, refine)
         pred_np = pred_out.cpu().numpy()
         col_np = col.cpu().numpy() if col is not None else None
         q8_np = q8.cpu().numpy() if q8 is not None else None
@@ -592,10 +626,12 @@ class GenPerceptPipeline:
             outs.append(GenPerceptOutput(pred_np=p, pred_colored=col_img))
         return outs
 
-    def _run_host(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None) -> List[GenPerceptOutput]:
+    def _run_host(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None, refine=None) -> List[GenPerceptOutput]:
         """The same steps with the resizes / colour map on the host (torch CPU + matplotlib): GENPERCEPT_HOST_PREPOST=1, and the A/B reference of
-        the device path in tests/test_prepost_gpu.py."""
+        the device path in tests/test_prepost_gpu.py.  refine: guided.guided_upsample (numpy) per image in place of the resize."""
         input_size = rgb.shape
+        refine = self._refine_options(refine, rgb.dtype, match_input_res)
+        full = rgb
         if processing_res > 0:
             rgb = resize_max_res(rgb, max_edge_resolution=processing_res, resample_method=resample)
         if rgb.dtype == torch.uint8:
@@ -605,7 +641,16 @@ class GenPerceptPipeline:
             assert rgb_in.min() >= -1.0 and rgb_in.max() <= 1.0
         pred = self._predict(rgb_in, fix_timesteps, prompt, opts)
         self._warn_if_saturated()
-        if match_input_res:
+        if refine is not None:
+            from .guided import guided_upsample
+            guide_lo = rgb
+            if pred.shape[-2] > input_size[-2] or pred.shape[-1] > input_size[-1]:
+                pred, guide_lo = resize_to(pred, input_size[-2:], resample), full
+            elif tuple(pred.shape[-2:]) != tuple(rgb.shape[-2:]):
+                guide_lo = resize_to(full, pred.shape[-2:], resample)
+            pred_np, lo_np, full_np = pred.float().cpu().numpy(), guide_lo.cpu().numpy(), full.cpu().numpy()
+            pred = torch.from_numpy(np.stack([guided_upsample(lo_np[i], pred_np[i], full_np[i], **refine) for i in range(pred_np.shape[0])]))
+        elif match_input_res:
             pred = resize_to(pred, input_size[-2:], resample)
         pred = pred.cpu().numpy().clip(0, 1)
         outs = []

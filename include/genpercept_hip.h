@@ -26,6 +26,9 @@
  *                       band of Boundary IoU, as region planes for gp_eval_mask
  *   gp_foreground     (no reference code) what a user does with a matting / dis alpha: the foreground colours by multi-level foreground
  *                       estimation (Germer et al. 2020), the RGBA cutout and the composite over a new background
+ *   gp_guided_upsample
+ *                     (no reference code: genpercept_pipeline.py:301-307 resizes the map) the prediction brought to the input size
+ *                       with the image as guide: the fast guided filter of He and Sun 2015
  *   gp_ensemble_gather, gp_ensemble_reduce
  *                     ensemble_depth's tensor half (the BFGS fit stays on the host)   genpercept/util/ensemble.py:43-205;
  *                                                                   genpercept_pipeline.py:289-298
@@ -476,6 +479,50 @@ gp_status gp_foreground(const unsigned char* image, const void* alpha, int alpha
                         int n_big, const unsigned char* new_bg /* [B][3][H][W] or NULL */, int new_rgb, float* fg_out, float* bg_out,
                         unsigned char* rgba_out, unsigned char* comp_out /* at least one non-NULL */, void* workspace,
                         long long workspace_bytes, void* stream);
+
+/* ---- edge-aware upsampling of a prediction (DEVICE pointers; stateless, stream-ordered, no host synchronisation; csrc/guided.hip) ----
+ * A map computed at the processing size and resized bilinearly has edges as wide as the resize factor.  gp_guided_upsample brings it to the
+ * input size with the image as guide: the guided filter of He, Sun and Tang (2010 / 2013) in its fast form (He and Sun 2015).  A local linear
+ * model q = a . I + b between the low-resolution image and the low-resolution prediction is fitted in every window, a and b are smoothed,
+ * upsampled and applied to the full-resolution image.  genpercept_amd/guided.py is the same definition on the host and gives the same bits;
+ * the per-pixel arithmetic stands once more in csrc/guided_solve.h.
+ * Inputs per image: guide_lo uint8 [3][h][w], the image at the processing size; pred fp32 [C][h][w], C = 1 or 3; guide uint8 [3][H][W], the
+ *   image at the output size; r = 1 .. 32, the window radius; eps in (0, 1], the regulariser in units of [0, 1]^2.  1 <= h, w, H, W <= 16384.
+ *   Output fp32 [C][H][W] in [0, 1].
+ * Quantise: p = (uint16)(clamp(pred, 0, 1) * 65535.0f), a float32 product, truncated, NaN -> 0: the 16-bit rule of gp_postprocess.
+ * Window sums: the window of pixel k is the (2 r + 1)^2 square around it clipped to the image, N its pixel count.  Over it S_I[c] (3 sums),
+ *   S_II[c][d] (6, c <= d) and per prediction channel S_p and S_Ip[c].  They are exact integers, and with r <= 32 every product below stays
+ *   under 2^53 (4225^2 * 255 * 65535 = 3.0e14), so any summation order in int64 or float64 gives the same bits.
+ * Solve: float64, the operations + - * / in exactly this order, no fused multiply-add, division correctly rounded.
+ *     cov[c] = (N * S_Ip[c] - S_I[c] * S_p) / (N * N)
+ *     s[c][d] = (N * S_II[c][d] - S_I[c] * S_I[d]) / (N * N), and + e on the diagonal, e = eps * 65025.0
+ *     c00 = s11 s22 - s12 s12;  c01 = s02 s12 - s01 s22;  c02 = s01 s12 - s02 s11
+ *     c11 = s00 s22 - s02 s02;  c12 = s01 s02 - s00 s12;  c22 = s00 s11 - s01 s01;  det = (s00 c00 + s01 c01) + s02 c02
+ *     a[0] = ((c00 cov[0] + c01 cov[1]) + c02 cov[2]) / det;  a[1] = ((c01 cov[0] + c11 cov[1]) + c12 cov[2]) / det
+ *     a[2] = ((c02 cov[0] + c12 cov[1]) + c22 cov[2]) / det
+ *     b = S_p / N - ((a[0] * (S_I[0] / N) + a[1] * (S_I[1] / N)) + a[2] * (S_I[2] / N))
+ * Smooth: the means of a[c] and b over the same clipped window.  These are float64 sums of non-integers, so the order is part of the
+ *   definition: each row of the window is summed left to right starting from +0.0, the row sums are summed top to bottom starting from +0.0,
+ *   then one division by N.  Every window is summed afresh; a running "add one, drop one" sum rounds differently and is not this definition.
+ * Upsample and apply: for output row Y, s = max(0, ((2 Y + 1) h - H) / (2 H)), one float64 division of the two integers; i0 = floor(s),
+ *   i1 = min(i0 + 1, h - 1), fy = s - i0; columns likewise (j0, j1, fx).  Each smoothed plane v of a[0], a[1], a[2], b is blended as
+ *     t0 = v[i0][j0] + fx * (v[i0][j1] - v[i0][j0]);  t1 = v[i1][j0] + fx * (v[i1][j1] - v[i1][j0]);  V = t0 + fy * (t1 - t0)
+ *   (a constant plane stays that constant), and q = (((A[0] * g[0] + A[1] * g[1]) + A[2] * g[2]) + B) / 65535.0 with g the three guide bytes
+ *   of the output pixel, clamped by comparisons, q > 0 ? (q < 1 ? q : 1) : 0 (so NaN -> 0), and rounded once to fp32.  With h = H and w = W
+ *   this is the plain guided filter; the formula holds for any pair of sizes, larger or smaller.
+ * C = 3: the channels are filtered independently and share the image sums.  Normals are NOT renormalised: the caller does that if it wants
+ *   unit vectors.  For eps near the lower end det is computed with cancellation (the eigenvalues of s are at least e, its entries reach
+ *   16256); the result is still the one the operations above give.
+ * Four kernel launches on `stream` for every B (model, row sums, column sums, apply), no atomics, nothing read back; an image's result is
+ * bitwise the same from call to call and in every batch.  workspace: DEVICE scratch of at least the workspace entry's byte count (two sets of
+ * 4 C float64 planes of h x w per image), 8-byte aligned, free again once the stream has passed the call.  guide_lo and guide may start at any
+ * byte.
+ * GP_ERR_INVALID before any HIP call: null guide_lo / pred / guide / out / workspace, B, h, w, H or W < 1, B > 65535, a side above 16384,
+ * C not 1 or 3, r outside 1 .. 32, eps outside (0, 1] (NaN included), pred or out not 4-byte aligned, workspace not 8-byte aligned,
+ * workspace_bytes too small. */
+long long gp_guided_upsample_workspace(int B, int C, int h, int w);  /* bytes; 0 for invalid B, C, h, w; proportional to B; multiple of 8 */
+gp_status gp_guided_upsample(const unsigned char* guide_lo, const float* pred, int C, const unsigned char* guide, int B, int h, int w, int H,
+                             int W, int r, double eps, float* out, void* workspace, long long workspace_bytes, void* stream);
 
 /* ---- test-time ensembling on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation, no atomics; csrc/ensemble.hip) ----
  * The tensor half of ensemble_depth (genpercept/util/ensemble.py:43-205, called at genpercept_pipeline.py:289-298) for the E members of each of

@@ -71,6 +71,14 @@
    bytes the last level has to move -- image, alpha, the level below's F and B, the RGBA bytes -- over its time, next to the
    device-to-device copy bandwidth measured in the same process).  Without a trace the per-level fields say "not measured".  `--n-big N`
    sets the iterations of the levels above 32 x 32 (default 2); a level launch with N = 1 is what one launch of a plain, unfused form costs.
+
+  python tools/eval_bench.py --guided --out profiles/<name>.json
+
+10. `--guided` (instead of 1 and 2): the `gp_guided_upsample` entry behind `engine.guided_upsample` (guided filter with the image as guide, four
+   launches) at 480 x 640 -> 1920 x 2560 and 768 x 768 -> 3072 x 3072, one channel, radius 4, eps 1e-4, on the `--foreground` image and its
+   alpha-like map box-reduced to the small size: device events around `iters` back-to-back calls after a warm-up, for the C entry on
+   preallocated buffers and for `engine.guided_upsample` itself, against `guided.guided_upsample` on the same arrays on the host (wall clock,
+   one run); the maps are compared on the spot (bit-equal).  `--no-host` skips the host route.
 Needs a GPU; there is no CPU fall-back."""
 import argparse
 import json
@@ -545,6 +553,45 @@ def bench_foreground(b, h, w, iters, host, copy_gb_per_s, level_ms, trace_run, n
     return res
 
 
+GUIDED_SHAPES = ((1, 480, 640, 1920, 2560), (1, 768, 768, 3072, 3072))
+
+
+def bench_guided(b, h, w, H, W, iters, host, radius=4, eps=1e-4):
+    """gp_guided_upsample on preallocated buffers and engine.guided_upsample itself against guided.guided_upsample on the host."""
+    from genpercept_amd import engine as ge
+    from genpercept_amd import guided as gd
+    d = torch.device("cuda", 0)
+    lib = ge.load_library()
+    img, a8 = foreground_case(b, H, W, 5)
+    k = H // h
+    lo = img.reshape(b, 3, h, k, w, k).astype(np.float32).mean(axis=(3, 5))
+    lo = np.floor(lo + 0.5).astype(np.uint8)
+    pred = (a8.reshape(b, 1, h, k, w, k).astype(np.float32).mean(axis=(3, 5)) / 255.0).astype(np.float32)
+    tl, tp, tg = torch.from_numpy(lo).to(d), torch.from_numpy(pred).to(d), torch.from_numpy(img).to(d)
+    nbytes = int(lib.gp_guided_upsample_workspace(b, 1, h, w))
+    ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=d)
+    out = torch.empty((b, 1, H, W), dtype=torch.float32, device=d)
+    stream = int(torch.cuda.current_stream(d).cuda_stream)
+
+    def entry():
+        rc = lib.gp_guided_upsample(tl.data_ptr(), tp.data_ptr(), 1, tg.data_ptr(), b, h, w, H, W, radius, eps, out.data_ptr(), ws.data_ptr(), nbytes, stream)
+        assert rc == ge.GP_OK, rc
+
+    entry_ms = time_events(entry, iters)
+    call_ms = time_events(lambda: ge.guided_upsample(tl, tp, tg, radius, eps), iters)
+    got = ge.guided_upsample(tl, tp, tg, radius, eps).cpu().numpy()
+    res = dict(shape=[b, h, w, H, W], channels=1, input="two gradients under an alpha-like map, box-reduced", options=dict(radius=radius, eps=eps),
+               gp_guided_upsample_ms_per_call=entry_ms, engine_guided_upsample_ms_per_call=call_ms, device_iters=iters, launches_per_call=4,
+               workspace_bytes=nbytes)
+    if host:
+        t0 = time.perf_counter()
+        ref = [gd.guided_upsample(lo[i], pred[i], img[i], radius, eps) for i in range(b)]
+        host_ms = (time.perf_counter() - t0) * 1e3
+        assert all(np.array_equal(got[i].view(np.uint32), ref[i].view(np.uint32)) for i in range(b))
+        res.update(host_guided_upsample_ms=host_ms, host_runs=1, host_over_engine_call=host_ms / call_ms, output_equals_host=True)
+    return res
+
+
 def bench_loop(n_images, batch_sizes, repeats):
     from PIL import Image
     from genpercept_amd import GenPerceptPipeline
@@ -605,11 +652,18 @@ def main():
     ap.add_argument("--n-big", type=int, default=2, help="with --foreground: iterations of a level above 32 x 32 (1 .. 4)")
     ap.add_argument("--trace-run", action="store_true", help="with --foreground: the device calls alone, for a kernel trace taken around this run")
     ap.add_argument("--kernel-trace", default=None, help="with --foreground: the kernel trace csv of a --trace-run, for the per-level times")
-    ap.add_argument("--no-host", action="store_true", help="with --structure, --matting, --seg, --band or --foreground: the device calls alone")
+    ap.add_argument("--guided", action="store_true", help="time gp_guided_upsample / engine.guided_upsample against guided.guided_upsample instead")
+    ap.add_argument("--no-host", action="store_true", help="with --structure, --matting, --seg, --band, --foreground or --guided: the device calls alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU")
-    if a.foreground:
+    if a.guided:
+        import bench
+        with bench.ClockPowerSampler("cuda:0") as clock:
+            rows = [bench_guided(*s, a.iters, not a.no_host) for s in GUIDED_SHAPES]
+        res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box", build_id=bench.source_build_id(), clock=clock.summary(),
+                   guided=rows)
+    elif a.foreground:
         import bench
         if a.trace_run:
             print(json.dumps([bench_foreground(b, h, w, a.iters, False, 0.0, {}, True, a.n_big) for (b, h, w) in FOREGROUND_SHAPES]))
@@ -650,7 +704,8 @@ def main():
                    eval_normal=[bench_eval_normal(4, 480, 640, a.iters, 3), bench_eval_normal(1, 4032, 6048, a.iters, 1)])
     else:
         res = dict(device=torch.cuda.get_device_name(0), eval_depth=[bench_eval(1, 4032, 6048, a.iters, 1), bench_eval(4, 480, 640, a.iters, 3)])
-    if not a.skip_loop and not a.normals and not a.masks and not a.structure and not a.matting and not a.seg and not a.band and not a.foreground:
+    if (not a.skip_loop and not a.normals and not a.masks and not a.structure and not a.matting and not a.seg and not a.band and not a.foreground
+            and not a.guided):
         res["infer_and_evaluate"] = bench_loop(16, (1, 4), 3)
     text = json.dumps(res, indent=1)
     print(text)
