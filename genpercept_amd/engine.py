@@ -171,6 +171,8 @@ SYMBOLS = {
     "gp_foreground": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _ll, _vp]),
     "gp_guided_upsample_workspace": (_ll, [_i, _i, _i, _i]),
     "gp_guided_upsample": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, C.c_double, _vp, _vp, _ll, _vp]),
+    "gp_tile_merge_workspace": (_ll, [_i] * 8),
+    "gp_tile_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
     "gp_ensemble_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gp_ensemble_workspace": (_ll, [_i, _i, _i, _i]),
     "gp_ensemble_reduce": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
@@ -1340,6 +1342,47 @@ def guided_upsample(guide_lo: torch.Tensor, pred: torch.Tensor, guide: torch.Ten
         raise ValueError(f"gp_guided_upsample: invalid arguments ({(b, c, h, w)} -> {(hh, ww)}, radius = {radius}, eps = {eps})")
     _c_check(st, "gp_guided_upsample")
     return out
+
+
+def tile_merge(base: torch.Tensor, tiles: torch.Tensor, ys, xs, overlap: int, align: str = "least_square", want_fit: bool = False):
+    """gp_tile_merge on device tensors: base float [B, C, H, W], C = 1 or 3 (the maps of the whole images at the input size), tiles float
+    [B, N, C, wh, ww] (the maps of the windows, N = ny * nx, numbered iy * nx + ix); a single image may come without the batch axis.  ys [ny],
+    xs [nx]: the origins of the grid as `tiled.tile_grid` gives them (host integers; they are checked against the grid rule); overlap: the
+    grid's; align: "least_square" (every tile is fitted onto the base by scale and shift) or "none".  Returns float32 [B, C, H, W] in [0, 1],
+    and with want_fit (out, fit) with fit float64 [B, N, 2] = (s, t) of every tile.  Definition in include/genpercept_hip.h;
+    genpercept_amd/tiled.py gives the same bits.  Allocates the workspace; enqueued on the current stream, no synchronisation."""
+    from .tiled import ALIGNMENTS
+    lib = load_library()
+    for name, v in (("base", base), ("tiles", tiles)):
+        if not torch.is_tensor(v) or not v.dtype.is_floating_point:
+            raise ValueError(f"{name}: a float tensor, got {v.dtype if torch.is_tensor(v) else type(v)}")
+    if base.dim() == 3 and tiles.dim() == 4:
+        base, tiles = base[None], tiles[None]
+    if base.dim() != 4 or tiles.dim() != 5 or tiles.shape[0] != base.shape[0] or tiles.shape[2] != base.shape[1] or base.shape[1] not in (1, 3):
+        raise ValueError(f"base [B, C, H, W] with C = 1 or 3 and tiles [B, N, C, wh, ww], got {tuple(base.shape)} and {tuple(tiles.shape)}")
+    if align not in ALIGNMENTS:
+        raise ValueError(f"align is one of {ALIGNMENTS}, got {align!r}")
+    assert base.is_cuda and tiles.is_cuda and base.device == tiles.device
+    base, tiles = base.to(torch.float32).contiguous(), tiles.to(torch.float32).contiguous()
+    ys_c, xs_c = (np.ascontiguousarray(np.asarray(v.cpu() if torch.is_tensor(v) else v)) for v in (ys, xs))
+    if any(v.ndim != 1 or v.dtype.kind not in "iu" or v.size < 1 for v in (ys_c, xs_c)):
+        raise ValueError("ys and xs are one-dimensional integer arrays")
+    ys_c, xs_c = ys_c.astype(np.int32), xs_c.astype(np.int32)
+    b, c, h, w = (int(v) for v in base.shape)
+    n, wh, ww = int(tiles.shape[1]), int(tiles.shape[3]), int(tiles.shape[4])
+    ny, nx = int(ys_c.size), int(xs_c.size)
+    if n != ny * nx:
+        raise ValueError(f"{ny} x {nx} origins do not number the {n} tiles")
+    out = torch.empty((b, c, h, w), dtype=torch.float32, device=base.device)
+    fit = torch.empty((b, n, 2), dtype=torch.float64, device=base.device) if want_fit else None
+    ws, nbytes = _workspace(lib.gp_tile_merge_workspace(b, c, h, w, ny, nx, wh, ww), base.device)
+    st = lib.gp_tile_merge(base.data_ptr(), tiles.data_ptr(), b, c, h, w, ys_c.ctypes.data, ny, xs_c.ctypes.data, nx, wh, ww, int(overlap),
+                           ALIGNMENTS.index(align), _ptr(fit), out.data_ptr(), ws.data_ptr(), nbytes, _stream_ptr(base.device))
+    if st == GP_ERR_INVALID:
+        raise ValueError(f"gp_tile_merge: invalid arguments (base {(b, c, h, w)}, {ny} x {nx} tiles of {wh} x {ww}, overlap = {overlap}, ys = "
+                         f"{ys_c.tolist()}, xs = {xs_c.tolist()}: not the grid of the rule, or outside its ranges)")
+    _c_check(st, "gp_tile_merge")
+    return (out, fit) if want_fit else out
 
 
 SEG_OUT = 8        # n, n_void, SEG_METRICS (out[2 .. 6]), n_classes; iou[K] follows

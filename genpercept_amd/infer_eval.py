@@ -184,9 +184,10 @@ def _load_rgb(base_dir: str, rgb_rel: str, rgb_crop: Optional[Callable[[np.ndarr
 def run_inference(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_dir: str, name_mode: FileNameMode, mode: str = "depth",
                   denoise_steps: int = 1, ensemble_size: int = 1, processing_res: int = 0, match_input_res: bool = True,
                   resample_method: str = "bilinear", fix_timesteps=None, prompt: str = "", rgb_crop: Optional[Callable[[np.ndarray], np.ndarray]] = None,
-                  prefetch: int = 2, batch_size: int = 1, rank: int = 0, world: int = 1, refine=None) -> List[str]:
+                  prefetch: int = 2, batch_size: int = 1, rank: int = 0, world: int = 1, refine=None, tiles=None) -> List[str]:
     """infer.py:408-447.  Returns the paths written.  rgb_crop: e.g. kitti_benchmark_crop (applied to the [3, H, W] image).
     refine (None, True or dict(radius=..., eps=...)): passed to the pipeline, which then brings each map to the input size by the guided filter.
+    tiles (None, True or dict(size=..., overlap=..., align=..., batch=...)): passed to the pipeline too, which then runs tiled inference.
     prefetch > 0: the next `prefetch` images are decoded (and cropped) by a helper thread while the engine works on the current one, and the .npy
     files are written by another -- the role the DataLoader workers play in the reference's loop; order and results are those of prefetch = 0.
     batch_size > 1: consecutive samples of one image size go through `pipe.infer_batch` together, up to batch_size per call (same file names,
@@ -207,7 +208,7 @@ def run_inference(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_
         np.save(save_to, pred_np)
         return save_to
 
-    extra = {} if refine is None else dict(refine=refine)
+    extra = {k: v for k, v in (("refine", refine), ("tiles", tiles)) if v is not None}
 
     def infer(img):
         return pipe(img, denoising_steps=denoise_steps, ensemble_size=ensemble_size, processing_res=processing_res, match_input_res=match_input_res,
@@ -240,7 +241,8 @@ def run_cutouts(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_di
     that size), the RGB composite over it.  Batching and sharding as `run_inference`: consecutive samples of one image size go through one call,
     up to batch_size of them; world > 1: this call handles `shard_range(len(samples), rank, world)` of the list.  Returns the paths written.
     inference_options go to `pipe.predict_batch_device`; `refine=True` (or dict(radius=..., eps=...)) among them sharpens the alpha with the
-    guided filter before the colours are estimated."""
+    guided filter before the colours are estimated, and `tiles=True` (or dict(size=..., overlap=..., align=..., batch=...)) makes it the alpha
+    of tiled inference."""
     import torch
     if mode not in ("matting", "dis"):
         raise ValueError(f"cutouts need an alpha map: mode 'matting' or 'dis', got {mode!r}")
@@ -451,12 +453,16 @@ def _evaluation_loop(samples: Sequence[Sequence[str]], keep: Callable, load: Cal
     return rows, result, writer
 
 
-def _infer_options(denoise_steps, ensemble_size, processing_res, match_input_res, resample_method, fix_timesteps, prompt, refine=None) -> dict:
-    """The inference options a device loop passes through, as the keyword arguments of `pipe.predict_batch_device` (`refine` only when set)."""
+def _infer_options(denoise_steps, ensemble_size, processing_res, match_input_res, resample_method, fix_timesteps, prompt, refine=None,
+                   tiles=None) -> dict:
+    """The inference options a device loop passes through, as the keyword arguments of `pipe.predict_batch_device` (`refine` and `tiles` only
+    when set)."""
     options = dict(processing_res=processing_res, match_input_res=match_input_res, resample_method=resample_method, fix_timesteps=fix_timesteps,
                    prompt=prompt, denoising_steps=denoise_steps, ensemble_size=ensemble_size)
     if refine is not None:
         options["refine"] = refine
+    if tiles is not None:
+        options["tiles"] = tiles
     return options
 
 
@@ -728,7 +734,7 @@ def infer_and_evaluate_masks(pipe, base_dir: str, samples: Sequence[Sequence[str
                              structure_evaluator: Optional[Callable] = None, matting: bool = False,
                              matting_evaluator: Optional[Callable] = None, trimap_radius: Optional[float] = None,
                              trimap_metric: str = "euclidean", trimap_evaluator: Optional[Callable] = None, boundary_iou: bool = False,
-                             boundary_ratio: float = 0.02, boundary_evaluator: Optional[Callable] = None, refine=None) -> Dict[str, float]:
+                             boundary_ratio: float = 0.02, boundary_evaluator: Optional[Callable] = None, refine=None, tiles=None) -> Dict[str, float]:
     """`infer_and_evaluate` for mode "dis" or "matting": batches go through `pipe.predict_batch_device(mode=mode)`, the float [B, 1, H, W] maps
     stay on the device, and `evaluator` -- `engine.eval_mask` unless given: (pred, gt, region) -> one dict per image with MASK_METRICS and
     "counts" -- quantises and scores them there against the 8-bit ground truth of column 1 (and `region_of(sample, gt)`, if given), decoded on
@@ -745,7 +751,8 @@ def infer_and_evaluate_masks(pipe, base_dir: str, samples: Sequence[Sequence[str
     boundary_iou: Boundary IoU as one more column (BOUNDARY_METRICS, last) -- `boundary_evaluator`, `engine.eval_boundary_iou` unless given:
     (pred, gt, ratio) -> one dict per image.  Neither goes with region_of; a header line of the text file states radius, metric and ratio.
     refine (None, True or dict(radius=..., eps=...)): the maps come to the input size by the guided filter with the image as guide, so that
-    a dataset can be scored with and without it; files and columns are the same."""
+    a dataset can be scored with and without it; files and columns are the same.  tiles (None, True or dict(size=..., overlap=..., align=...,
+    batch=...)): the maps are those of tiled inference (`pipe.predict_batch_device(..., tiles=...)`); files and columns are the same."""
     if mode not in ("dis", "matting"):
         raise ValueError(f"mask evaluation is for mode 'dis' or 'matting', got {mode!r}")
     options, names, note = _mask_options(region_of, structure, matting, trimap_radius, trimap_metric, boundary_iou, boundary_ratio,
@@ -763,7 +770,7 @@ def infer_and_evaluate_masks(pipe, base_dir: str, samples: Sequence[Sequence[str
         counts.extend((idx, np.asarray(m["counts"])) for idx, m in zip(indices, metrics))
         return _with_mask_options(metrics, options, pred[:, 0], gt_t, region_t, lambda: ", ".join(smp[0] for smp in smps))
 
-    infer_options = _infer_options(denoise_steps, ensemble_size, processing_res, match_input_res, resample_method, fix_timesteps, prompt, refine)
+    infer_options = _infer_options(denoise_steps, ensemble_size, processing_res, match_input_res, resample_method, fix_timesteps, prompt, refine, tiles)
     result, per_sample, prediction_dir, n = _infer_and_score(
         pipe, base_dir, samples, mode, 1, infer_options, lambda s: _gt_rel(s, 1) is not None,
         lambda smp: (read_gt or read_gt_mask)(os.path.join(base_dir, smp[1])), 2, score_batch, names, lambda smp: _pred_name(smp[0], name_mode),

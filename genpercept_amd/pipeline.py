@@ -385,9 +385,12 @@ class GenPerceptPipeline:
     def __call__(self, input_image: Union[Image.Image, torch.Tensor], denoising_steps: Optional[int] = None, ensemble_size: int = 1,
                  processing_res: Optional[int] = None, match_input_res: bool = True, resample_method: str = "bilinear", batch_size: int = 0,
                  generator=None, color_map: str = "Spectral", show_progress_bar: bool = True, ensemble_kwargs: Dict = None, mode=None,
-                 fix_timesteps=None, prompt="", refine=None) -> GenPerceptOutput:
+                 fix_timesteps=None, prompt="", refine=None, tiles=None) -> GenPerceptOutput:
         """genpercept_pipeline.py:146-337.  refine (new; None, True or dict(radius=..., eps=...)): the map is brought to the input size by the
-        guided filter with the image as guide (engine.guided_upsample) instead of the plain resize; uint8 images and match_input_res only."""
+        guided filter with the image as guide (engine.guided_upsample) instead of the plain resize; uint8 images and match_input_res only.
+        tiles (new; None, True or dict(size=..., overlap=..., align=..., batch=...)): tiled high-resolution inference -- the model runs once
+        more on overlapping windows of the image at native resolution and the windows' maps are merged onto the map of the whole image
+        (engine.tile_merge; `_predict_device`); uint8 images and match_input_res only."""
         assert mode is not None, "mode of GenPerceptPipeline can be chosen from ['depth', 'normal', 'seg', 'matting', 'dis']."
         self.mode = mode
         if denoising_steps is None:
@@ -422,7 +425,7 @@ class GenPerceptPipeline:
         assert batch_size >= 1
         opts = dict(steps=int(denoising_steps), ensemble_size=int(ensemble_size), batch_size=int(batch_size), generator=generator,
                     ensemble_kwargs=ensemble_kwargs)
-        outs = self._run(rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts, refine)
+        outs = self._run(rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts, refine, tiles)
         return outs[0] if rgb.shape[0] == 1 else outs
 
     def _check_inference_step(self, n_step: int) -> None:
@@ -464,9 +467,10 @@ class GenPerceptPipeline:
 
     def infer_batch(self, images: Union[Sequence[Image.Image], torch.Tensor], mode: str, processing_res: Optional[int] = None,
                     match_input_res: bool = True, resample_method: str = "bilinear", color_map: Optional[str] = "Spectral", fix_timesteps=None,
-                    prompt="", denoising_steps: Optional[int] = None, ensemble_size: int = 1, generator=None, refine=None) -> List[GenPerceptOutput]:
-        """Batch entry (new): images of one common size, one engine call; results are per image (DPT min-max per image).  refine: as
-        `__call__`."""
+                    prompt="", denoising_steps: Optional[int] = None, ensemble_size: int = 1, generator=None, refine=None,
+                    tiles=None) -> List[GenPerceptOutput]:
+        """Batch entry (new): images of one common size, one engine call; results are per image (DPT min-max per image).  refine, tiles:
+        as `__call__`."""
         self.mode = mode
         if processing_res is None:
             processing_res = self.default_processing_resolution
@@ -477,16 +481,18 @@ class GenPerceptPipeline:
         if self.genpercept_pipeline:
             assert steps == 1 and ensemble_size == 1
         opts = dict(steps=steps, ensemble_size=int(ensemble_size), batch_size=max(1, int(ensemble_size)), generator=generator, ensemble_kwargs=None)
-        return self._run(images, processing_res, match_input_res, get_resample_method(resample_method), color_map, fix_timesteps, prompt, opts, refine)
+        return self._run(images, processing_res, match_input_res, get_resample_method(resample_method), color_map, fix_timesteps, prompt, opts, refine,
+                         tiles)
 
-    def _run(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None, refine=None) -> List[GenPerceptOutput]:
+    def _run(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None, refine=None,
+             tiles=None) -> List[GenPerceptOutput]:
         from .engine import RESAMPLE_CODE
         # device pre / post for uint8 and fp32 images; fp16 / bf16 / fp64 tensors keep the host recipe, which -- like the reference
         # (genpercept_pipeline.py:240-247, image_util.py:75-105) -- resizes in the tensor's OWN dtype before the normalisation (the
         # device path would promote them to fp32 first and deviate slightly)
         if rgb.dtype in (torch.uint8, torch.float32) and resample in RESAMPLE_CODE and not os.environ.get("GENPERCEPT_HOST_PREPOST"):
-            return self._run_device(rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts, refine)
-        return self._run_host(rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts, refine)
+            return self._run_device(rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts, refine, tiles)
+        return self._run_host(rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts, refine, tiles)
 
     @staticmethod
     def _refine_options(refine, dtype, match_input_res) -> Optional[dict]:
@@ -502,7 +508,37 @@ class GenPerceptPipeline:
             raise ValueError("refine upsamples the map to the input size: it needs match_input_res=True")
         return opts
 
-    def _predict_device(self, rgb, processing_res, match_input_res, resample, fix_timesteps, prompt, opts, color_map=None, q_bits=0, refine=None):
+    def _tiles_options(self, tiles, dtype, match_input_res, processing_res) -> Optional[dict]:
+        """The `tiles` argument of the entry points (None, True or dict(size=..., overlap=..., align=..., batch=...)) as the checked options
+        of `tiled.tiles_options`, None when absent.  The windows are cut from the 8-bit image and merged at the input size: float images and
+        match_input_res=False are refused, and so is processing_res = 0 without an explicit size."""
+        if tiles is None:
+            return None
+        from .tiled import tiles_options
+        opts = tiles_options(tiles, int(processing_res), self.mode or "depth")
+        if dtype != torch.uint8:
+            raise ValueError(f"tiles takes 8-bit images (the windows are cut from the image as it came), got {dtype}")
+        if not match_input_res:
+            raise ValueError("tiles merges the windows at the input size: it needs match_input_res=True")
+        return opts
+
+    @staticmethod
+    def _tile_predictions(full, tiles: dict, predict):
+        """The windows of the grid of `tiles` cut from the uint8 images `full` [B, 3, H, W] (strided copies) and sent through `predict`
+        (uint8 [n, 3, wh, ww] -> float [n, C, wh, ww]) in tile order -- image after image, each image's windows numbered iy * nx + ix -- in
+        chunks of tiles["batch"] consecutive windows.  Returns (ys, xs, float [B, N, C, wh, ww])."""
+        from .tiled import tile_grid
+        b, _, h, w = (int(v) for v in full.shape)
+        ys, xs, wh, ww = tile_grid(h, w, tiles["size"], tiles["overlap"])
+        windows = [(i, int(y0), int(x0)) for i in range(b) for y0 in ys for x0 in xs]
+        preds = []
+        for j in range(0, len(windows), tiles["batch"]):
+            preds.append(predict(torch.stack([full[i, :, y0:y0 + wh, x0:x0 + ww] for i, y0, x0 in windows[j:j + tiles["batch"]]])))
+        preds = torch.cat(preds)
+        return ys, xs, preds.reshape(b, len(ys) * len(xs), preds.shape[1], wh, ww)
+
+    def _predict_device(self, rgb, processing_res, match_input_res, resample, fix_timesteps, prompt, opts, color_map=None, q_bits=0, refine=None,
+                        tiles=None):
         """The device half of __call__ up to the finished map: upload, gp_preprocess, the model, gp_postprocess to the output size (the input
         size with match_input_res), clip.  Returns (pred fp32 [B,C,H,W] in [0, 1], coloured uint8 [B,H,W,3] or None, quantised or None), all on
         the device.  refine: the map is brought to the input size by gp_guided_upsample instead -- the guide at the processing size is the
@@ -510,10 +546,14 @@ class GenPerceptPipeline:
         at that size (clip, colour map, quantisation).  A processing size that exceeds the input in either dimension: the map is resized to
         the input size first and filtered there.  A map smaller than the processing size (the model rounds sides that are no multiple of its
         latent stride down): the guide is the image resized to the map's size by gp_preprocess, as the plain resize takes the map to cover
-        the whole image."""
+        the whole image.  tiles: tiled high-resolution inference.  The map above (refined if `refine` is given too), resized to the input
+        size and clipped, is the base; the windows of `tiled.tile_grid` are cut from the uploaded image and go through this same function --
+        gp_preprocess, the model, gp_postprocess to the window's size -- without `refine` and `tiles`, in chunks of tiles["batch"] windows in
+        tile order; gp_tile_merge fits them onto the base and blends them, and gp_postprocess then runs at that size as above."""
         from . import engine as ge
         input_size = rgb.shape
         refine = self._refine_options(refine, rgb.dtype, match_input_res)
+        tiles = self._tiles_options(tiles, rgb.dtype, match_input_res, processing_res)
         full = x = rgb.to(self._device, non_blocking=True)
         size_in = tuple(int(v) for v in input_size[-2:])
         size_p = ge.resize_max_res_size(size_in[0], size_in[1], int(processing_res)) if processing_res > 0 else size_in
@@ -533,17 +573,24 @@ class GenPerceptPipeline:
             elif tuple(pred.shape[-2:]) != tuple(x.shape[-2:]):  # the map covers the image on a grid of its own: the guide on that grid
                 guide_lo = ge.preprocess(full, tuple(int(v) for v in pred.shape[-2:]), resample)
             pred = ge.guided_upsample(guide_lo, pred, full, **refine)
+        if tiles is not None:
+            base = ge.postprocess(pred, size, resample)[0]
+            ys, xs, tile_preds = self._tile_predictions(
+                full, tiles, lambda crops: self._predict_device(crops, processing_res, True, resample, fix_timesteps, prompt, opts)[0])
+            pred = ge.tile_merge(base, tile_preds, ys, xs, tiles["overlap"], tiles["align"])
         return ge.postprocess(pred, size, resample, cmap=color_map if one_ch else None, q_bits=q_bits)
 
     @torch.no_grad()
     def predict_batch_device(self, images: Union[Sequence[Image.Image], torch.Tensor], mode: str, processing_res: Optional[int] = None,
                              match_input_res: bool = True, resample_method: str = "bilinear", fix_timesteps=None, prompt="",
-                             denoising_steps: Optional[int] = None, ensemble_size: int = 1, generator=None, refine=None) -> torch.Tensor:
+                             denoising_steps: Optional[int] = None, ensemble_size: int = 1, generator=None, refine=None, tiles=None) -> torch.Tensor:
         """`infer_batch` without the trip to the host: images of one common size (PIL images, or a uint8 / fp32 [B,3,H,W] tensor) -> the
         finished maps as an fp32 [B,C,H,W] tensor ON THE DEVICE, resized to the input size (match_input_res) and clipped to [0, 1] -- the values
         `infer_batch(...)[i].pred_np` holds.  For consumers that stay on the GPU (engine.eval_depth, infer_eval.infer_and_evaluate).  refine (None,
         True or dict(radius=..., eps=...)): the maps come to the input size by engine.guided_upsample with the image as guide, not by the
-        plain resize (uint8 images and match_input_res only: ValueError otherwise)."""
+        plain resize (uint8 images and match_input_res only: ValueError otherwise).  tiles (None, True or dict(size=..., overlap=...,
+        align=..., batch=...)): tiled high-resolution inference, the windows' maps merged onto these maps by engine.tile_merge (the same two
+        conditions, and a tile size where processing_res is 0)."""
         from .engine import RESAMPLE_CODE
         self.mode = mode
         if processing_res is None:
@@ -559,7 +606,7 @@ class GenPerceptPipeline:
         if self.genpercept_pipeline:
             assert steps == 1 and ensemble_size == 1
         opts = dict(steps=steps, ensemble_size=int(ensemble_size), batch_size=max(1, int(ensemble_size)), generator=generator, ensemble_kwargs=None)
-        return self._predict_device(images, processing_res, match_input_res, resample, fix_timesteps, prompt, opts, refine=refine)[0]
+        return self._predict_device(images, processing_res, match_input_res, resample, fix_timesteps, prompt, opts, refine=refine, tiles=tiles)[0]
 
     @torch.no_grad()
     def cutout_batch_device(self, images: Union[Sequence[Image.Image], torch.Tensor], mode: str = "matting", background=None,
@@ -570,7 +617,7 @@ class GenPerceptPipeline:
         under that alpha (engine.cutout, gp_foreground) or, with a `background` (a uint8 [B,3,H,W] / [3,H,W] image or one colour of three
         bytes), the uint8 [B,3,H,W] composite over it.  foreground_options: reg, gw, n_small, n_big of engine.cutout.  Modes matting and dis.
         inference_options may hold `refine` (True or dict(radius=..., eps=...)): the alpha then comes to the input size by the guided filter, and
-        the colours are estimated under that sharper alpha."""
+        the colours are estimated under that sharper alpha; and `tiles` (as `predict_batch_device`): the alpha is that of tiled inference."""
         from . import engine as ge
         if mode not in ("matting", "dis"):
             raise ValueError(f"cutouts need an alpha map: mode 'matting' or 'dis', got {mode!r}")
@@ -599,7 +646,8 @@ class GenPerceptPipeline:
             return Image.fromarray(out[0].cpu().numpy())
         return Image.fromarray(np.ascontiguousarray(out[0].permute(1, 2, 0).cpu().numpy()))
 
-    def _run_device(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None, refine=None) -> List[GenPerceptOutput]:
+    def _run_device(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None, refine=None,
+                    tiles=None) -> List[GenPerceptOutput]:
         """Pre / post processing on the GPU (gp_preprocess / gp_postprocess): the image goes up once, resize_max_res, the model, the
         resize back to the input size, clip, colour map and the 8-bit image all run on the device; pred_np and the coloured bytes come down.
         uint8 images (PIL input) stay uint8 up to the engine's prologue; float tensors (genpercept_trainer.py:1151-1165) are resized in fp32
@@ -607,7 +655,7 @@ class GenPerceptPipeline:
         if color_map is not None:
             assert self.mode in ["depth", "disparity"]
         pred_out, col, q8 = self._predict_device(rgb, processing_res, match_input_res, resample, fix_timesteps, prompt, opts, color_map,
-                                                 0 if color_map is not None else 8, refine)
+                                                 0 if color_map is not None else 8, refine, tiles)
         pred_np = pred_out.cpu().numpy()
         col_np = col.cpu().numpy() if col is not None else None
         q8_np = q8.cpu().numpy() if q8 is not None else None
@@ -626,11 +674,9 @@ class GenPerceptPipeline:
             outs.append(GenPerceptOutput(pred_np=p, pred_colored=col_img))
         return outs
 
-    def _run_host(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None, refine=None) -> List[GenPerceptOutput]:
-        """The same steps with the resizes / colour map on the host (torch CPU + matplotlib): GENPERCEPT_HOST_PREPOST=1, and the A/B reference of
-        the device path in tests/test_prepost_gpu.py.  refine: guided.guided_upsample (numpy) per image in place of the resize."""
+    def _predict_host(self, rgb, processing_res, match_input_res, resample, fix_timesteps, prompt, opts, refine=None) -> np.ndarray:
+        """`_run_host` up to the finished maps: float32 [B, C, H, W] in [0, 1] as a numpy array."""
         input_size = rgb.shape
-        refine = self._refine_options(refine, rgb.dtype, match_input_res)
         full = rgb
         if processing_res > 0:
             rgb = resize_max_res(rgb, max_edge_resolution=processing_res, resample_method=resample)
@@ -652,7 +698,22 @@ class GenPerceptPipeline:
             pred = torch.from_numpy(np.stack([guided_upsample(lo_np[i], pred_np[i], full_np[i], **refine) for i in range(pred_np.shape[0])]))
         elif match_input_res:
             pred = resize_to(pred, input_size[-2:], resample)
-        pred = pred.cpu().numpy().clip(0, 1)
+        return pred.cpu().numpy().clip(0, 1)
+
+    def _run_host(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None, refine=None,
+                  tiles=None) -> List[GenPerceptOutput]:
+        """The same steps with the resizes / colour map on the host (torch CPU + matplotlib): GENPERCEPT_HOST_PREPOST=1, and the A/B reference of
+        the device path in tests/test_prepost_gpu.py.  refine: guided.guided_upsample (numpy) per image in place of the resize.  tiles: the
+        windows go through the same host steps and tiled.tile_merge (numpy) merges them per image."""
+        refine = self._refine_options(refine, rgb.dtype, match_input_res)
+        tiles = self._tiles_options(tiles, rgb.dtype, match_input_res, processing_res)
+        pred = self._predict_host(rgb, processing_res, match_input_res, resample, fix_timesteps, prompt, opts, refine)
+        if tiles is not None:
+            from .tiled import tile_merge
+            ys, xs, tile_preds = self._tile_predictions(rgb.cpu(), tiles, lambda crops: torch.from_numpy(
+                self._predict_host(crops, processing_res, True, resample, fix_timesteps, prompt, opts)))
+            tile_preds = tile_preds.numpy()
+            pred = np.stack([tile_merge(pred[i], tile_preds[i], ys, xs, tiles["overlap"], tiles["align"]) for i in range(pred.shape[0])])
         outs = []
         for i in range(pred.shape[0]):
             p = pred[i].squeeze()

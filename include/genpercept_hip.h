@@ -29,6 +29,8 @@
  *   gp_guided_upsample
  *                     (no reference code: genpercept_pipeline.py:301-307 resizes the map) the prediction brought to the input size
  *                       with the image as guide: the fast guided filter of He and Sun 2015
+ *   gp_tile_merge     (no reference code) tiled high-resolution inference: each window's prediction at native resolution fitted onto the
+ *                       whole-image prediction by least squares, the fitted windows blended across their overlaps
  *   gp_ensemble_gather, gp_ensemble_reduce
  *                     ensemble_depth's tensor half (the BFGS fit stays on the host)   genpercept/util/ensemble.py:43-205;
  *                                                                   genpercept_pipeline.py:289-298
@@ -523,6 +525,44 @@ gp_status gp_foreground(const unsigned char* image, const void* alpha, int alpha
 long long gp_guided_upsample_workspace(int B, int C, int h, int w);  /* bytes; 0 for invalid B, C, h, w; proportional to B; multiple of 8 */
 gp_status gp_guided_upsample(const unsigned char* guide_lo, const float* pred, int C, const unsigned char* guide, int B, int h, int w, int H,
                              int W, int r, double eps, float* out, void* workspace, long long workspace_bytes, void* stream);
+
+/* ---- the merge of tiled high-resolution inference (DEVICE pointers but ys / xs; stateless, stream-ordered, no host synchronisation; csrc/tile_merge.hip) ----
+ * Every map is computed at the processing size; a guided upsample sharpens its edges but adds no detail.  Tiled inference runs the model once on
+ * the whole image (the base, for the global layout) and again on overlapping windows at native resolution (the tiles).  gp_tile_merge puts
+ * each tile's affine-invariant prediction onto the base and blends the seams.  genpercept_amd/tiled.py is the same definition on the host and
+ * gives the same bits; the grid rule, the per-tile solve and the per-pixel steps stand once more in csrc/tile_merge_math.h.
+ * Grid: along an axis of length L with tile size T and overlap o the window is w = min(T, L); the tile count is n = 1 if L <= w, else
+ *   n = ceil((L - o) / (w - o)); the origins are y_k = (k * (L - w)) / (n - 1) in integers, rounded down (0 for n = 1).  Neighbours overlap by
+ *   at least o, the first tile starts at 0, the last ends at L, the origins increase strictly.  Tiles are numbered iy * nx + ix.  Ranges:
+ *   1 <= o <= w / 2 on both axes, ny * nx <= 1024, 1 <= H, W <= 16384, C = 1 or 3.  The kernels make the origins from this rule; ys [ny] and
+ *   xs [nx] are int32 arrays in HOST memory that have to hold exactly these origins (the caller crops its windows by them), and are checked.
+ * Inputs per image: base fp32 [C][H][W], the map of the whole image at the input size; tiles fp32 [N][C][wh][ww], N = ny * nx, the maps of the
+ *   windows; the overlap o; align = 0 (least_square) or 1 (none).  Output fp32 [C][H][W] in [0, 1].
+ * Fit, per image and tile, over all wh * ww * C values of the window (three channels share one fit):
+ *   P = quantise(tile), G = quantise(base window): (uint16)(clamp(x, 0, 1) * 65535.0f), a float32 product, truncated, NaN -> 0: the 16-bit rule of
+ *   gp_postprocess.  The sums n, S_P, S_G, S_PP = sum P^2, S_PG = sum P G are exact integers in 64 bits (at most 3 * 2^28 values of at most
+ *   65535^2: below 2^63).  Each is converted to float64 once, round to nearest.  Then float64, the operations + - * / in exactly this order, no
+ *   fused multiply-add, division correctly rounded:
+ *     mp = S_P / n;  mg = S_G / n;  var = S_PP / n - mp * mp;  cov = S_PG / n - mp * mg;  s = cov / var
+ *     if not (var >= 1.0) or not (s > 0):  s = 1     (a tile flat to within one 16-bit step, or anti-correlated with the base, is shifted only)
+ *     t = (mg - s * mp) / 65535
+ *   align = none: s = 1, t = 0 (matting, dis, seg and normal maps are not affine-invariant).
+ * Blend, per output pixel and channel: the tiles that cover the pixel are visited in ascending iy, then ascending ix.  The integer weight is
+ *   wgt = wy * wx with wy = min(y - y0 + 1, y0 + wh - y, o) and wx likewise, always >= 1.  acc starts at +0.0 and takes
+ *   acc += (double)wgt * (s * (double)p + t) -- product, sum, product, sum -- with p the tile's fp32 value as it stands (not quantised).
+ *   q = acc / (double)(sum of wgt), clamped by comparisons, q > 0 ? (q < 1 ? q : 1) : 0 (so NaN -> 0), and rounded once to fp32.
+ * C = 3: one (s, t) per tile for the three channels.  Normals are NOT renormalised: the caller does that if it wants unit vectors.
+ * fit_out (optional): fp64 [B][N][2] = (s, t) of every tile.
+ * Three kernel launches on `stream` for every B (fit, solve, blend; two for align = none), no atomics, nothing read back; an image's result is
+ * bitwise the same from call to call and in every batch.  workspace: DEVICE scratch of at least the workspace entry's byte count (the (s, t)
+ * table and the 64-bit partial sums), 8-byte aligned, free again once the stream has passed the call.
+ * GP_ERR_INVALID before any HIP call: null base / tiles / ys / xs / out / workspace, B < 1, B > 65535, C not 1 or 3, H or W outside
+ * 1 .. 16384, wh > H, ww > W, o outside 1 .. min(wh, ww) / 2, ny or nx not the rule's count, ny * nx > 1024, ys or xs not the rule's origins,
+ * align outside 0 .. 1, base, tiles or out not 4-byte aligned, fit_out or workspace not 8-byte aligned, workspace_bytes too small. */
+long long gp_tile_merge_workspace(int B, int C, int H, int W, int ny, int nx, int wh, int ww);  /* bytes; 0 for invalid sizes; proportional to B; multiple of 8 */
+gp_status gp_tile_merge(const float* base, const float* tiles, int B, int C, int H, int W, const int* ys /* HOST [ny] */, int ny,
+                        const int* xs /* HOST [nx] */, int nx, int wh, int ww, int overlap, int align, double* fit_out /* [B][N][2] or NULL */,
+                        float* out, void* workspace, long long workspace_bytes, void* stream);
 
 /* ---- test-time ensembling on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation, no atomics; csrc/ensemble.hip) ----
  * The tensor half of ensemble_depth (genpercept/util/ensemble.py:43-205, called at genpercept_pipeline.py:289-298) for the E members of each of

@@ -79,6 +79,16 @@
    alpha-like map box-reduced to the small size: device events around `iters` back-to-back calls after a warm-up, for the C entry on
    preallocated buffers and for `engine.guided_upsample` itself, against `guided.guided_upsample` on the same arrays on the host (wall clock,
    one run); the maps are compared on the spot (bit-equal).  `--no-host` skips the host route.
+
+  python tools/eval_bench.py --tiles --out profiles/<name>.json
+
+11. `--tiles` (instead of 1 and 2): the `gp_tile_merge` entry behind `engine.tile_merge` (the merge of tiled inference: fit, solve and blend
+   launches) at 2048 x 3072 and 4032 x 6048 with size = 768, overlap = 192, one channel, on a smooth map with noise as the base and affine
+   images of its windows with noise of their own as the tiles: device events around `iters` back-to-back calls after a warm-up, for the C
+   entry on preallocated buffers with the alignment `least_square` (three launches) and `none` (solve and blend alone, two launches) and for
+   `engine.tile_merge` itself, against `tiled.tile_merge` on the same arrays on the host (wall clock, one run); maps and fits are compared on
+   the spot (bit-equal).  The bytes the blend pass has to move (every tile once, the output once) over the time of the `none` call stand
+   next to the device-to-device copy bandwidth measured in the same process.  `--no-host` skips the host route.
 Needs a GPU; there is no CPU fall-back."""
 import argparse
 import json
@@ -592,6 +602,59 @@ def bench_guided(b, h, w, H, W, iters, host, radius=4, eps=1e-4):
     return res
 
 
+TILE_SHAPES = ((1, 2048, 3072), (1, 4032, 6048))
+
+
+def bench_tiles(b, h, w, iters, host, copy_gb_per_s, size=768, overlap=192):
+    """gp_tile_merge on preallocated buffers (least_square and none) and engine.tile_merge itself against tiled.tile_merge on the host."""
+    from genpercept_amd import engine as ge
+    from genpercept_amd import tiled
+    d = torch.device("cuda", 0)
+    lib = ge.load_library()
+    rng = np.random.default_rng(9)
+    base = case(b, h, w, 9)[0][:, None]
+    ys, xs, wh, ww = tiled.tile_grid(h, w, size, overlap)
+    n = len(ys) * len(xs)
+    tiles = np.empty((b, n, 1, wh, ww), np.float32)
+    for i in range(b):
+        for k, (y0, x0) in enumerate((y0, x0) for y0 in ys for x0 in xs):
+            s, t = rng.uniform(0.5, 2.0), rng.uniform(-0.25, 0.25)
+            tiles[i, k] = (base[i, :, y0:y0 + wh, x0:x0 + ww] - t) / s + 0.01 * rng.standard_normal((1, wh, ww), dtype=np.float32)
+    tb, tt = torch.from_numpy(base).to(d), torch.from_numpy(tiles).to(d)
+    ys32, xs32 = np.ascontiguousarray(ys, np.int32), np.ascontiguousarray(xs, np.int32)
+    nbytes = int(lib.gp_tile_merge_workspace(b, 1, h, w, len(ys), len(xs), wh, ww))
+    ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=d)
+    out = torch.empty((b, 1, h, w), dtype=torch.float32, device=d)
+    stream = int(torch.cuda.current_stream(d).cuda_stream)
+
+    def entry(align):
+        rc = lib.gp_tile_merge(tb.data_ptr(), tt.data_ptr(), b, 1, h, w, ys32.ctypes.data, len(ys), xs32.ctypes.data, len(xs), wh, ww, overlap, align, None,
+                               out.data_ptr(), ws.data_ptr(), nbytes, stream)
+        assert rc == ge.GP_OK, rc
+
+    fit_ms, none_ms = time_events(lambda: entry(0), iters), time_events(lambda: entry(1), iters)
+    call_ms = time_events(lambda: ge.tile_merge(tb, tt, ys, xs, overlap), iters)
+    got, fit = ge.tile_merge(tb, tt, ys, xs, overlap, want_fit=True)
+    got, fit = got.cpu().numpy(), fit.cpu().numpy()
+    blend_bytes = b * (n * wh * ww + h * w) * 4
+    fit_bytes = b * 2 * n * wh * ww * 4
+    res = dict(shape=[b, 1, h, w], grid=[len(ys), len(xs), wh, ww], options=dict(size=size, overlap=overlap), input="smooth map with noise; affine images of its windows",
+               gp_tile_merge_ms_per_call=fit_ms, gp_tile_merge_none_ms_per_call=none_ms, engine_tile_merge_ms_per_call=call_ms, device_iters=iters,
+               launches_per_call=3, launches_per_call_none=2, workspace_bytes=nbytes, blend_bytes_needed=blend_bytes, fit_bytes_needed=fit_bytes,
+               blend_gb_per_s=blend_bytes / none_ms / 1e6, copy_gb_per_s=copy_gb_per_s, blend_over_copy_rate=blend_bytes / none_ms / 1e6 / copy_gb_per_s,
+               blend_bytes_alone_ms=blend_bytes / copy_gb_per_s / 1e6, fit_pass_ms=fit_ms - none_ms, fit_gb_per_s=fit_bytes / max(fit_ms - none_ms, 1e-9) / 1e6,
+               note="blend time = the `none` call (solve + blend launches); fit time = the difference of the two calls")
+    if host:
+        t0 = time.perf_counter()
+        ref = [tiled.tile_merge(base[i], tiles[i], ys, xs, overlap) for i in range(b)]
+        host_ms = (time.perf_counter() - t0) * 1e3
+        ref_fit = [np.stack(tiled.tile_fit(base[i], tiles[i], ys, xs), axis=1) for i in range(b)]
+        assert all(np.array_equal(got[i].view(np.uint32), ref[i].view(np.uint32)) for i in range(b))
+        assert all(np.array_equal(fit[i].view(np.uint64), ref_fit[i].view(np.uint64)) for i in range(b))
+        res.update(host_tile_merge_ms=host_ms, host_runs=1, host_over_engine_call=host_ms / call_ms, output_equals_host=True)
+    return res
+
+
 def bench_loop(n_images, batch_sizes, repeats):
     from PIL import Image
     from genpercept_amd import GenPerceptPipeline
@@ -653,11 +716,19 @@ def main():
     ap.add_argument("--trace-run", action="store_true", help="with --foreground: the device calls alone, for a kernel trace taken around this run")
     ap.add_argument("--kernel-trace", default=None, help="with --foreground: the kernel trace csv of a --trace-run, for the per-level times")
     ap.add_argument("--guided", action="store_true", help="time gp_guided_upsample / engine.guided_upsample against guided.guided_upsample instead")
-    ap.add_argument("--no-host", action="store_true", help="with --structure, --matting, --seg, --band, --foreground or --guided: the device calls alone")
+    ap.add_argument("--tiles", action="store_true", help="time gp_tile_merge / engine.tile_merge against tiled.tile_merge instead")
+    ap.add_argument("--no-host", action="store_true", help="with --structure, --matting, --seg, --band, --foreground, --guided or --tiles: the device calls alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU")
-    if a.guided:
+    if a.tiles:
+        import bench
+        bw = copy_bandwidth(torch.device("cuda", 0))
+        with bench.ClockPowerSampler("cuda:0") as clock:
+            rows = [bench_tiles(*s, a.iters, not a.no_host, bw) for s in TILE_SHAPES]
+        res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box", build_id=bench.source_build_id(), clock=clock.summary(),
+                   copy_gb_per_s=bw, tiles=rows)
+    elif a.guided:
         import bench
         with bench.ClockPowerSampler("cuda:0") as clock:
             rows = [bench_guided(*s, a.iters, not a.no_host) for s in GUIDED_SHAPES]
@@ -705,7 +776,7 @@ def main():
     else:
         res = dict(device=torch.cuda.get_device_name(0), eval_depth=[bench_eval(1, 4032, 6048, a.iters, 1), bench_eval(4, 480, 640, a.iters, 3)])
     if (not a.skip_loop and not a.normals and not a.masks and not a.structure and not a.matting and not a.seg and not a.band and not a.foreground
-            and not a.guided):
+            and not a.guided and not a.tiles):
         res["infer_and_evaluate"] = bench_loop(16, (1, 4), 3)
     text = json.dumps(res, indent=1)
     print(text)
