@@ -16,8 +16,9 @@ Paths (gp_last_igemm_path): 1 halo 16-row tiles, 2 halo phases (x2 upsample), 3 
 reduce, 5 split-K igemm + reduce, 6 generic igemm, 7 halo 12-row tiles, 8 per-tile halo; 0 = no conv / GEMM launcher ran.
 
 The non-matrix 16-bit kernels (GroupNorm, LayerNorm, the cross-attention fold, row softmax, flash attention, the GroupNorm statistics of the
-conv epilogues), which exact operands cannot express, are held to per-element float64 intervals in tests/test_kernels_interval_gpu.py; its
-docstring lists what remains out of scope (the outputs of the GroupNorm-fused conv input and of the decoder tail among them).
+conv epilogues), which exact operands cannot express, are held to per-element float64 intervals in tests/test_kernels_interval_gpu.py, the
+outputs of the GroupNorm-fused conv input and of the decoder tail in tests/test_kernels_fused_gn_gpu.py; the former's docstring lists what
+remains out of scope.
 """
 import math
 import zlib

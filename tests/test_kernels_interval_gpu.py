@@ -22,10 +22,11 @@ instruction it pays for.  Shared conventions (E24 = 2^-24, one fp32 rounding):
 tests/test_kernels_interval_host.py proves on the CPU, on the same inputs, that a plain float32 evaluation in the well-conditioned order
 stays within HALF of every gate and that the nearest wrong variants fall outside.  Inputs are generated on the CPU (shared generators).
 
-Out of scope: the outputs of gp_conv2d_gn and gp_decoder_tail (the normalised operand is rounded to 16 bits before an MFMA; a rounding flip
-there moves the output by ulp16 * |w|, which no per-element interval expresses -- their statistics come from the launch_groupnorm_stats
-tested here), gp_bilinear, pre / post processing and the unfused VAE attention chain.  The elementwise and layout kernels (concat and its
-statistics, the DDIM state kernels, the prologue / epilogue and layout kernels) are in tests/test_kernels_glue_gpu.py.
+Out of scope: pre / post processing and the unfused VAE attention chain.  The outputs of gp_conv2d_gn and gp_decoder_tail (the normalised
+operand is rounded to 16 bits before an MFMA; a rounding flip there moves the output by ulp16 * |w|: the operand is carried as an interval) and
+the 16-bit gp_bilinear are in tests/test_kernels_fused_gn_gpu.py -- their statistics come from the launch_groupnorm_stats tested here.  The
+elementwise and layout kernels (concat and its statistics, the DDIM state kernels, the prologue / epilogue and layout kernels) are in
+tests/test_kernels_glue_gpu.py.
 """
 import math
 import zlib
