@@ -173,6 +173,8 @@ SYMBOLS = {
     "gp_guided_upsample": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, C.c_double, _vp, _vp, _ll, _vp]),
     "gp_tile_merge_workspace": (_ll, [_i] * 8),
     "gp_tile_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
+    "gp_depth_geometry_workspace": (_ll, [_i] * 4),
+    "gp_depth_geometry": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, _i, C.c_double, _i] + [_vp] * 9 + [_ll, _vp]),
     "gp_ensemble_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gp_ensemble_workspace": (_ll, [_i, _i, _i, _i]),
     "gp_ensemble_reduce": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
@@ -1383,6 +1385,61 @@ def tile_merge(base: torch.Tensor, tiles: torch.Tensor, ys, xs, overlap: int, al
                          f"{ys_c.tolist()}, xs = {xs_c.tolist()}: not the grid of the rule, or outside its ranges)")
     _c_check(st, "gp_tile_merge")
     return (out, fit) if want_fit else out
+
+
+def depth_geometry(pred: torch.Tensor, cameras=None, image: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, space: str = "depth",
+                   radius: int = 2, tau: float = 0.05, min_count: Optional[int] = None, min_cos: Optional[float] = None, stride: int = 1):
+    """gp_depth_geometry on device tensors: pred float [B, 1, H, W] ([B, H, W] and [H, W] too), a depth or disparity map in [0, 1]; cameras None
+    (`geometry.default_camera`, a viewing convention), eight values s, t, fx, fy, cx, cy, z_min, z_max for every image or a HOST [B, 8] array;
+    image uint8 [B, 3, H, W] or None (the points' colours); mask [B, H, W] or None (non-zero: usable); space "depth" or "disparity"; radius
+    1 .. 8, tau in (0, 1], min_count 3 .. (2 r + 1)^2 (default 2 r + 1), min_cos in [0, 1) (default cos 85 degrees), stride 1 .. 64.  Returns a
+    dict of device tensors: xyz float32 [B, 3, H, W] (NaN where the pixel is invalid), normal float32 [B, 3, H, W] (camera-facing unit
+    vectors, zero without a fit), keep uint8 [B, H, W], and the point cloud without flying pixels -- points float32 [n, 3],
+    point_normals float32 [n, 3], point_rgb uint8 [n, 3], point_index int32 [n] (v * W + u) -- with offsets, a HOST int64 [B + 1] array
+    (image k owns the points offsets[k] .. offsets[k + 1]): the point arrays are sliced by one read of it, the only synchronisation.
+    Definition in include/genpercept_hip.h; genpercept_amd/geometry.py gives the same bits.  Allocates the workspace and, for the point
+    arrays, the worst case B * ceil(H / stride) * ceil(W / stride)."""
+    from .geometry import SPACES, check_cameras, check_options
+    lib = load_library()
+    if not torch.is_tensor(pred) or not pred.dtype.is_floating_point:
+        raise ValueError(f"pred: a float tensor, got {pred.dtype if torch.is_tensor(pred) else type(pred)}")
+    pred = _eval_maps(pred, "pred").to(torch.float32).contiguous()
+    assert pred.is_cuda
+    b, h, w = (int(v) for v in pred.shape)
+    if space not in SPACES:
+        raise ValueError(f"space is one of {SPACES}, got {space!r}")
+    radius, tau, min_count, min_cos, stride = check_options(radius, tau, min_count, min_cos, stride)
+    if not (1 <= h <= 16384 and 1 <= w <= 16384 and 1 <= b <= 65535 and b * h * w < 2 ** 31):
+        raise ValueError(f"depth geometry takes 1 .. 65535 maps with sides in 1 .. 16384 and B * H * W < 2^31, got {(b, h, w)}")
+    cams = check_cameras(cameras.cpu().numpy() if torch.is_tensor(cameras) else cameras, b, h, w)
+    if image is not None:
+        if not torch.is_tensor(image) or image.dtype != torch.uint8 or image.dim() not in (3, 4):
+            raise ValueError(f"image: uint8 [B, 3, H, W] or [3, H, W], got {image.dtype if torch.is_tensor(image) else type(image)}")
+        image = (image[None] if image.dim() == 3 else image).contiguous()
+        if tuple(image.shape) != (b, 3, h, w) or image.device != pred.device:
+            raise ValueError(f"image: uint8 {(b, 3, h, w)} on the maps' device, got {tuple(image.shape)}")
+    if mask is not None:
+        mask = _mask_u8(mask, "mask", (b, h, w))
+    dev = pred.device
+    out = dict(xyz=torch.empty((b, 3, h, w), dtype=torch.float32, device=dev), normal=torch.empty((b, 3, h, w), dtype=torch.float32, device=dev),
+               keep=torch.empty((b, h, w), dtype=torch.uint8, device=dev))
+    cap = b * (-(-h // stride)) * (-(-w // stride))
+    pts = dict(points=torch.empty((cap, 3), dtype=torch.float32, device=dev), point_normals=torch.empty((cap, 3), dtype=torch.float32, device=dev),
+               point_rgb=torch.empty((cap, 3), dtype=torch.uint8, device=dev), point_index=torch.empty((cap,), dtype=torch.int32, device=dev),
+               offsets=torch.empty((b + 1,), dtype=torch.int64, device=dev))
+    ws, nbytes = _workspace(lib.gp_depth_geometry_workspace(b, h, w, stride), dev)
+    st = lib.gp_depth_geometry(pred.data_ptr(), _ptr(mask), _ptr(image), cams.ctypes.data, b, h, w, SPACES.index(space), radius, tau, min_count, min_cos,
+                               stride, out["xyz"].data_ptr(), out["normal"].data_ptr(), out["keep"].data_ptr(),
+                               *[pts[k].data_ptr() for k in ("points", "point_normals", "point_rgb", "point_index", "offsets")], ws.data_ptr(), nbytes,
+                               _stream_ptr(dev))
+    if st == GP_ERR_INVALID:
+        raise ValueError(f"gp_depth_geometry: invalid arguments (maps {(b, h, w)}, radius = {radius}, tau = {tau}, min_count = {min_count}, "
+                         f"min_cos = {min_cos}, stride = {stride})")
+    _c_check(st, "gp_depth_geometry")
+    offsets = pts["offsets"].cpu().numpy()   # (synchronises: `cams`, host memory the call reads in stream order, has been read by now)
+    n = int(offsets[-1])
+    out.update({k: pts[k][:n] for k in ("points", "point_normals", "point_rgb", "point_index")}, offsets=offsets)
+    return out
 
 
 SEG_OUT = 8        # n, n_void, SEG_METRICS (out[2 .. 6]), n_classes; iou[K] follows

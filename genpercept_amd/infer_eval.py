@@ -269,6 +269,36 @@ def run_cutouts(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_di
     return written
 
 
+def run_pointclouds(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_dir: str, name_mode: FileNameMode, mode: str = "depth",
+                    batch_size: int = 1, rank: int = 0, world: int = 1, cameras=None, pointcloud=True, prefetch: int = 2, **inference_options) -> List[str]:
+    """One point cloud per sample with `pipe.pointcloud_batch_device` (modes depth and disparity): a binary little-endian `.ply` with x y z
+    nx ny nz (float) and red green blue (uchar) per vertex, the kept pixels of the sample in row-major order (`geometry.write_ply`).
+    cameras: None (`geometry.default_camera`, a viewing convention) or eight values s, t, fx, fy, cx, cy, z_min, z_max used for every sample;
+    pointcloud: True or dict(radius=..., tau=..., min_count=..., min_cos=..., stride=...).  Batching, sharding and prefetch as `run_cutouts`.
+    Returns the paths written.  inference_options go to `pipe.predict_batch_device`, `refine` and `tiles` among them."""
+    from .geometry import write_ply
+    if mode not in ("depth", "disparity"):
+        raise ValueError(f"point clouds need a depth map: mode 'depth' or 'disparity', got {mode!r}")
+    if cameras is not None and np.asarray(cameras).shape != (8,):
+        raise ValueError(f"cameras: None or eight values used for every sample, got shape {np.asarray(cameras).shape}")
+    if world > 1:
+        lo, hi = _shard(len(samples), rank, world)
+        samples = samples[lo:hi]
+    written = []
+    for group in _size_groups(_decode_ahead(samples, lambda s: _load_rgb(base_dir, s[0], None), prefetch), max(1, batch_size)):
+        out = pipe.pointcloud_batch_device([img for _, img in group], mode, cameras, pointcloud, **inference_options)
+        off = out["offsets"]
+        assert len(off) == len(group) + 1
+        pts, nrm, rgb = (out[k].cpu().numpy() for k in ("points", "point_normals", "point_rgb"))
+        for i, (smp, _) in enumerate(group):
+            scene_dir = os.path.join(output_dir, os.path.dirname(smp[0]))
+            os.makedirs(scene_dir, exist_ok=True)
+            save_to = os.path.join(scene_dir, get_pred_name(os.path.basename(smp[0]), name_mode, suffix=".ply"))
+            write_ply(save_to, pts[off[i]:off[i + 1]], nrm[off[i]:off[i + 1]], rgb[off[i]:off[i + 1]])
+            written.append(save_to)
+    return written
+
+
 def _write_metric_files(output_dir: str, tag: str, names: List[str], per_sample, result: Dict[str, float], header: str) -> None:
     """`per_sample_metrics<tag>.csv` (one row per prediction file) and `eval_metrics<tag>.txt` (header, metric names, means)."""
     os.makedirs(output_dir, exist_ok=True)

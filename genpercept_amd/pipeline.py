@@ -646,6 +646,40 @@ class GenPerceptPipeline:
             return Image.fromarray(out[0].cpu().numpy())
         return Image.fromarray(np.ascontiguousarray(out[0].permute(1, 2, 0).cpu().numpy()))
 
+    @torch.no_grad()
+    def pointcloud_batch_device(self, images: Union[Sequence[Image.Image], torch.Tensor], mode: str = "depth", cameras=None, pointcloud=True,
+                                **inference_options):
+        """The scene in 3-D without a trip to the host: images of one common size (PIL images or a uint8 [B,3,H,W] tensor) -> the dict of
+        `engine.depth_geometry` (gp_depth_geometry) applied to the map of `predict_batch_device(images, mode, **inference_options)` at the input
+        size, which never leaves the GPU: xyz and normal float32 [B,3,H,W], keep uint8 [B,H,W], and the point cloud without the flying pixels
+        of depth edges -- points, point_normals float32 [n,3], point_rgb uint8 [n,3] (the images' colours), point_index int32 [n] -- all ON THE
+        DEVICE, with offsets, a host int64 [B+1] array (image k owns the points offsets[k] .. offsets[k+1]); the map itself comes back under
+        "pred".  mode: depth or disparity (the space the map is read in).  cameras: None, eight values s, t, fx, fy, cx, cy, z_min, z_max or a
+        [B,8] array of them; None is `geometry.default_camera`, a viewing convention that puts z in [1, 2] under a 55 degree field of view --
+        an affine-invariant map has no metric scale until the caller supplies s and t.  pointcloud: True or dict(radius=..., tau=...,
+        min_count=..., min_cos=..., stride=...).  inference_options may hold `refine` and `tiles` as in `cutout_batch_device`."""
+        from . import engine as ge
+        from .geometry import pointcloud_options
+        if mode not in ("depth", "disparity"):
+            raise ValueError(f"point clouds need a depth map: mode 'depth' or 'disparity', got {mode!r}")
+        if inference_options.get("match_input_res", True) is not True:
+            raise ValueError("point clouds are made at the input size: match_input_res stays True")
+        opts = pointcloud_options(pointcloud)
+        if not torch.is_tensor(images):
+            images = torch.stack([torch.from_numpy(np.asarray(im.convert("RGB")).copy()).permute(2, 0, 1) for im in images])
+        if images.dtype != torch.uint8:
+            raise ValueError(f"point clouds take 8-bit images, got {images.dtype}")
+        pred = self.predict_batch_device(images, mode, **inference_options)
+        out = ge.depth_geometry(pred, cameras, image=images.to(pred.device, non_blocking=True), space=mode, **opts)
+        out["pred"] = pred
+        return out
+
+    def pointcloud(self, image: Image.Image, mode: str = "depth", camera=None, pointcloud=True, **inference_options) -> Dict[str, np.ndarray]:
+        """`pointcloud_batch_device` for one PIL image: its cloud as numpy arrays, a dict of points, point_normals float32 [n,3], point_rgb
+        uint8 [n,3] and point_index int32 [n] (`geometry.write_ply` takes the first three)."""
+        out = self.pointcloud_batch_device([image], mode, camera, pointcloud, **inference_options)
+        return {k: out[k].cpu().numpy() for k in ("points", "point_normals", "point_rgb", "point_index")}
+
     def _run_device(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None, refine=None,
                     tiles=None) -> List[GenPerceptOutput]:
         """Pre / post processing on the GPU (gp_preprocess / gp_postprocess): the image goes up once, resize_max_res, the model, the

@@ -31,6 +31,9 @@
  *                       with the image as guide: the fast guided filter of He and Sun 2015
  *   gp_tile_merge     (no reference code) tiled high-resolution inference: each window's prediction at native resolution fitted onto the
  *                       whole-image prediction by least squares, the fitted windows blended across their overlaps
+ *   gp_depth_geometry (no reference code: genpercept/losses/metric3d_losses/VNL.py transfer_xyz unprojects with x = (u - u0) z / f and that
+ *                       is all) a depth or disparity prediction as a point map, edge-aware surface normals and a point cloud without the
+ *                       flying pixels of depth edges
  *   gp_ensemble_gather, gp_ensemble_reduce
  *                     ensemble_depth's tensor half (the BFGS fit stays on the host)   genpercept/util/ensemble.py:43-205;
  *                                                                   genpercept_pipeline.py:289-298
@@ -563,6 +566,59 @@ long long gp_tile_merge_workspace(int B, int C, int H, int W, int ny, int nx, in
 gp_status gp_tile_merge(const float* base, const float* tiles, int B, int C, int H, int W, const int* ys /* HOST [ny] */, int ny,
                         const int* xs /* HOST [nx] */, int nx, int wh, int ww, int overlap, int align, double* fit_out /* [B][N][2] or NULL */,
                         float* out, void* workspace, long long workspace_bytes, void* stream);
+
+/* ---- point maps, normals and point clouds from a depth prediction (DEVICE pointers but cameras; stateless, stream-ordered, no host synchronisation; csrc/depth_geometry.hip) ----
+ * The depth modes stop at a map; the scene in 3-D is a point per pixel, a surface normal per pixel and a point cloud.  Plain finite differences
+ * smear normals across every depth edge, and a resized prediction has "flying pixels" between foreground and background; both are dealt with
+ * here.  genpercept_amd/geometry.py is the same definition on the host and gives the same bits; the per-pixel arithmetic stands once more in
+ * csrc/depth_geometry_math.h.
+ * Inputs per image: pred fp32 [1][H][W]; mask uint8 [H][W] or NULL, non-zero means usable; image uint8 [3][H][W] or NULL; the camera, eight
+ *   float64 values s, t, fx, fy, cx, cy, z_min, z_max, all finite with fx, fy > 0 and 0 < z_min < z_max.  Per call: space = 0 (depth) or 1
+ *   (disparity); the window radius r = 1 .. 8; tau in (0, 1]; min_count in 3 .. (2 r + 1)^2; min_cos in [0, 1); stride = 1 .. 64.
+ *   1 <= H, W <= 16384 and B * H * W < 2^31.  The camera is OpenCV's: x right, y down, z forward, and pixel (u, v) has its centre at integer
+ *   (u, v).  Everything after the quantisation is float64, the operations + - * / sqrt in exactly the order written, no fused multiply-add,
+ *   division and square root correctly rounded.
+ * 1. Quantise: Q = (uint16)(clamp(pred, 0, 1) * 65535.0f), a float32 product, truncated: the 16-bit rule of gp_postprocess.
+ *    lin = s * (Q / 65535) + t;  z = lin for depth, 1 / lin for disparity.  A pixel is valid iff pred is not NaN, the mask is not 0, z is
+ *    finite and z_min <= z <= z_max.  w = 1 / z.
+ * 2. Point map: X = ((u - cx) / fx) * z, Y = ((v - cy) / fy) * z, Z = z, each rounded once to fp32; NaN for an invalid pixel.
+ * 3. Edge-aware plane fit in inverse depth.  A plane n . P = d seen by a pinhole camera has inverse depth affine in the pixel coordinates, so
+ *    the fit is linear and the depth step it must not cross is easy to state.  The members of a valid pixel i are the valid pixels j of its
+ *    (2 r + 1)^2 window, clipped to the image, with |z_j - z_i| <= tau * z_i.  They are visited in row-major order; with du = u_j - u_i and
+ *    dv = v_j - v_i the integers n, Su, Sv, Suu, Suv, Svv are exact, and the float64 sums Sw, Suw = sum du * w, Svw = sum dv * w start from
+ *    +0.0 and take one product and one add per member.  The symmetric system [[Suu, Suv, Su], [., Svv, Sv], [., ., n]] (a, b, c) =
+ *    (Suw, Svw, Sw) is solved by cofactors in the order of gp_guided_upsample's solve, s00 .. s22 the matrix:
+ *      c00 = s11 s22 - s12 s12;  c01 = s02 s12 - s01 s22;  c02 = s01 s12 - s02 s11;  c11 = s00 s22 - s02 s02;  c12 = s01 s02 - s00 s12
+ *      c22 = s00 s11 - s01 s01;  det = (s00 c00 + s01 c01) + s02 c02      (for r <= 8 every cofactor and det is an exact integer below 2^53)
+ *      a = ((c00 Suw + c01 Svw) + c02 Sw) / det;  b = ((c01 Suw + c11 Svw) + c12 Sw) / det;  c = ((c02 Suw + c12 Svw) + c22 Sw) / det
+ *    The fit is valid iff n >= min_count and det > 0.  m = (a * fx, b * fy, (c + a * (cx - u_i)) + b * (cy - v_i)).
+ * 4. Normal: N_k = -m_k / sqrt((m0^2 + m1^2) + m2^2), so the normal faces the camera; rounded once to fp32; (0, 0, 0) where the fit is invalid
+ *    or the norm is 0 or not finite.
+ * 5. Keep, the flying-pixel filter: a pixel is kept iff it is valid, its fit is valid, and with the view ray p = ((u - cx) / fx,
+ *    (v - cy) / fy, 1) and mp = (m0 p0 + m1 p1) + m2:  mp * mp >= ((min_cos * min_cos) * ((m0^2 + m1^2) + m2^2)) * ((p0^2 + p1^2) + 1)  and
+ *    mp > 0.
+ * 6. Compaction: the kept pixels with u % stride == 0 and v % stride == 0 in row-major order, image after image: points fp32 [n][3],
+ *    point_normals fp32 [n][3], point_rgb uint8 [n][3] (all 255 without an image), point_index int32 [n] = v * W + u, offsets int64 [B + 1]
+ *    (image k owns the points offsets[k] .. offsets[k + 1]; written on the device).  The caller sizes the four point arrays for the worst
+ *    case, B * ceil(H / stride) * ceil(W / stride) points.
+ * Outputs: xyz fp32 [B][3][H][W], normal fp32 [B][3][H][W], keep uint8 [B][H][W] and the arrays of step 6; each may be NULL, but at least one
+ *   of xyz, normal, keep, offsets is given, and a point array needs offsets.  With offsets alone the points are counted only.
+ * cameras: float64 [B][8] in HOST memory, checked before any HIP call and copied to the workspace on `stream`; it stays unchanged until the
+ * stream has passed the call.  After that copy four kernel launches for every B (geometry; count, scan, scatter: only with offsets, the last
+ * only with a point array), no atomics, nothing read back; an image's result is bitwise the same from call to call and in every batch.
+ * workspace: DEVICE scratch of at least the workspace entry's byte count (the cameras, the segment counts, a keep plane and the six planes
+ * the scatter reads when the caller gives none), 8-byte aligned, free again once the stream has passed the call.
+ * GP_ERR_INVALID before any HIP call: null pred / cameras / workspace, B < 1, B > 65535, H or W outside 1 .. 16384, B * H * W >= 2^31, space
+ * outside 0 .. 1, r outside 1 .. 8, tau outside (0, 1] (NaN included), min_count outside 3 .. (2 r + 1)^2, min_cos outside [0, 1), stride
+ * outside 1 .. 64, a camera with a non-finite value, fx or fy <= 0 or not 0 < z_min < z_max, no output at all, a point array without offsets,
+ * pred, xyz, normal, points, point_normals or point_index not 4-byte aligned, offsets or workspace not 8-byte aligned, workspace_bytes too
+ * small. */
+long long gp_depth_geometry_workspace(int B, int H, int W, int stride);  /* bytes; 0 for invalid sizes; proportional to B; multiple of 8 */
+gp_status gp_depth_geometry(const float* pred, const unsigned char* mask /* or NULL */, const unsigned char* image /* or NULL */,
+                            const double* cameras /* HOST [B][8] */, int B, int H, int W, int space, int r, double tau, int min_count,
+                            double min_cos, int stride, float* xyz, float* normal, unsigned char* keep, float* points, float* point_normals,
+                            unsigned char* point_rgb, int* point_index, long long* offsets, void* workspace, long long workspace_bytes,
+                            void* stream);
 
 /* ---- test-time ensembling on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation, no atomics; csrc/ensemble.hip) ----
  * The tensor half of ensemble_depth (genpercept/util/ensemble.py:43-205, called at genpercept_pipeline.py:289-298) for the E members of each of

@@ -89,6 +89,16 @@
    `engine.tile_merge` itself, against `tiled.tile_merge` on the same arrays on the host (wall clock, one run); maps and fits are compared on
    the spot (bit-equal).  The bytes the blend pass has to move (every tile once, the output once) over the time of the `none` call stand
    next to the device-to-device copy bandwidth measured in the same process.  `--no-host` skips the host route.
+
+  python tools/eval_bench.py --geometry --out profiles/<name>.json
+
+12. `--geometry` (instead of 1 and 2): the `gp_depth_geometry` entry behind `engine.depth_geometry` (point map, normals, keep bytes and the
+   compacted point cloud: four launches) at 1 x 768 x 768 and 1 x 2048 x 3072 with radius 2 and stride 1, depth space, the default camera,
+   on a smooth map with noise and a depth edge down the middle and a random image: the median of five repetitions, each device events
+   around `iters` back-to-back calls after a warm-up, for the C entry on preallocated buffers, and `engine.depth_geometry` itself
+   (allocations and its one read of the offsets included), against `geometry.depth_geometry` on the same arrays on the host (wall clock,
+   one run); every output is compared on the spot (bit-equal).  The bytes the call has to move (4 B/px read, 25 B/px planes, 31 B/point)
+   over the device time stand next to the device-to-device copy bandwidth measured in the same process.  `--no-host` skips the host route.
 Needs a GPU; there is no CPU fall-back."""
 import argparse
 import json
@@ -655,6 +665,60 @@ def bench_tiles(b, h, w, iters, host, copy_gb_per_s, size=768, overlap=192):
     return res
 
 
+GEOMETRY_SHAPES = ((1, 768, 768), (1, 2048, 3072))
+
+
+def bench_geometry(b, h, w, iters, host, copy_gb_per_s, radius=2, stride=1, repeats=5):
+    """gp_depth_geometry on preallocated buffers (every output, image and default camera) and engine.depth_geometry itself against
+    geometry.depth_geometry on the host."""
+    from genpercept_amd import engine as ge
+    from genpercept_amd import geometry as gm
+    d = torch.device("cuda", 0)
+    lib = ge.load_library()
+    rng = np.random.default_rng(13)
+    pred = case(b, h, w, 13)[0]
+    pred[:, :, w // 2:] = np.clip(pred[:, :, w // 2:] + 0.2, 0, 1)   # a depth edge down the middle
+    image = rng.integers(0, 256, (b, 3, h, w), dtype=np.uint8)
+    radius, tau, min_count, min_cos, stride = gm.check_options(radius, stride=stride)
+    cams = gm.check_cameras(None, b, h, w)
+    tp, ti = torch.from_numpy(pred).to(d), torch.from_numpy(image).to(d)
+    cap = b * (-(-h // stride)) * (-(-w // stride))
+    outs = [torch.empty(s, dtype=t, device=d) for s, t in (((b, 3, h, w), torch.float32), ((b, 3, h, w), torch.float32), ((b, h, w), torch.uint8),
+                                                          ((cap, 3), torch.float32), ((cap, 3), torch.float32), ((cap, 3), torch.uint8),
+                                                          ((cap,), torch.int32), ((b + 1,), torch.int64))]
+    nbytes = int(lib.gp_depth_geometry_workspace(b, h, w, stride))
+    ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=d)
+    stream = int(torch.cuda.current_stream(d).cuda_stream)
+
+    def entry():
+        rc = lib.gp_depth_geometry(tp.data_ptr(), None, ti.data_ptr(), cams.ctypes.data, b, h, w, 0, radius, tau, min_count, min_cos, stride,
+                                   *[o.data_ptr() for o in outs], ws.data_ptr(), nbytes, stream)
+        assert rc == ge.GP_OK, rc
+
+    runs = sorted(time_events(entry, iters) for _ in range(repeats))
+    entry_ms = runs[len(runs) // 2]
+    call_ms = sorted(time_events(lambda: ge.depth_geometry(tp, None, ti, radius=radius, stride=stride), max(1, iters // 5)) for _ in range(3))[1]
+    got = ge.depth_geometry(tp, None, ti, radius=radius, stride=stride)
+    n = int(got["offsets"][-1])
+    need = b * h * w * (4 + 25) + 31 * n
+    res = dict(shape=[b, 1, h, w], options=dict(radius=radius, tau=tau, min_count=min_count, min_cos=min_cos, stride=stride, space="depth"),
+               input="smooth map with noise and a depth edge down the middle; random image; default camera", points=n, points_worst_case=cap,
+               gp_depth_geometry_us_per_call=1e3 * entry_ms, gp_depth_geometry_us_per_call_runs=[1e3 * r for r in runs], device_iters=iters,
+               repeats=repeats, statistic="median of the repeats; each is device events around `device_iters` back-to-back calls after a warm-up",
+               engine_depth_geometry_ms_per_call=call_ms, launches_per_call=4, workspace_bytes=nbytes, bytes_needed=need,
+               bytes_needed_rule="4 B/px read, 25 B/px planes, 31 B/point", gb_per_s=need / entry_ms / 1e6, copy_gb_per_s=copy_gb_per_s,
+               over_copy_rate=need / entry_ms / 1e6 / copy_gb_per_s, bytes_alone_us=need / copy_gb_per_s / 1e3)
+    if host:
+        t0 = time.perf_counter()
+        ref = gm.depth_geometry(pred[:, None], None, image, radius=radius, stride=stride)
+        host_ms = (time.perf_counter() - t0) * 1e3
+        for k, v in ref.items():
+            g = got[k].cpu().numpy() if torch.is_tensor(got[k]) else got[k]
+            assert g.dtype == v.dtype and g.shape == v.shape and np.array_equal(g.view(np.uint8), v.view(np.uint8)), k
+        res.update(host_depth_geometry_ms=host_ms, host_runs=1, host_over_engine_call=host_ms / call_ms, output_equals_host=True)
+    return res
+
+
 def bench_loop(n_images, batch_sizes, repeats):
     from PIL import Image
     from genpercept_amd import GenPerceptPipeline
@@ -717,11 +781,20 @@ def main():
     ap.add_argument("--kernel-trace", default=None, help="with --foreground: the kernel trace csv of a --trace-run, for the per-level times")
     ap.add_argument("--guided", action="store_true", help="time gp_guided_upsample / engine.guided_upsample against guided.guided_upsample instead")
     ap.add_argument("--tiles", action="store_true", help="time gp_tile_merge / engine.tile_merge against tiled.tile_merge instead")
-    ap.add_argument("--no-host", action="store_true", help="with --structure, --matting, --seg, --band, --foreground, --guided or --tiles: the device calls alone")
+    ap.add_argument("--geometry", action="store_true", help="time gp_depth_geometry / engine.depth_geometry against geometry.depth_geometry instead")
+    ap.add_argument("--no-host", action="store_true",
+                    help="with --structure, --matting, --seg, --band, --foreground, --guided, --tiles or --geometry: the device calls alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU")
-    if a.tiles:
+    if a.geometry:
+        import bench
+        bw = copy_bandwidth(torch.device("cuda", 0))
+        with bench.ClockPowerSampler("cuda:0") as clock:
+            rows = [bench_geometry(*s, a.iters, not a.no_host, bw) for s in GEOMETRY_SHAPES]
+        res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box", build_id=bench.source_build_id(), clock=clock.summary(),
+                   copy_gb_per_s=bw, geometry=rows)
+    elif a.tiles:
         import bench
         bw = copy_bandwidth(torch.device("cuda", 0))
         with bench.ClockPowerSampler("cuda:0") as clock:
@@ -776,7 +849,7 @@ def main():
     else:
         res = dict(device=torch.cuda.get_device_name(0), eval_depth=[bench_eval(1, 4032, 6048, a.iters, 1), bench_eval(4, 480, 640, a.iters, 3)])
     if (not a.skip_loop and not a.normals and not a.masks and not a.structure and not a.matting and not a.seg and not a.band and not a.foreground
-            and not a.guided and not a.tiles):
+            and not a.guided and not a.tiles and not a.geometry):
         res["infer_and_evaluate"] = bench_loop(16, (1, 4), 3)
     text = json.dumps(res, indent=1)
     print(text)
