@@ -175,6 +175,7 @@ SYMBOLS = {
     "gp_tile_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
     "gp_depth_geometry_workspace": (_ll, [_i] * 4),
     "gp_depth_geometry": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, _i, C.c_double, _i] + [_vp] * 9 + [_ll, _vp]),
+    "gp_lens_blur": (_i, [_vp] * 6 + [_i] * 5 + [_vp] * 3),
     "gp_ensemble_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gp_ensemble_workspace": (_ll, [_i, _i, _i, _i]),
     "gp_ensemble_reduce": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
@@ -1440,6 +1441,77 @@ def depth_geometry(pred: torch.Tensor, cameras=None, image: Optional[torch.Tenso
     n = int(offsets[-1])
     out.update({k: pts[k][:n] for k in ("points", "point_normals", "point_rgb", "point_index")}, offsets=offsets)
     return out
+
+
+_LENS_TABLES: Dict = {}   # (device, the tables' bytes) -> (to_lin, from_lin) on that device
+
+
+def _lens_tables(tables, device):
+    from .lens_blur import check_tables
+    to_lin, from_lin = check_tables(tables)
+    key = (str(device), to_lin.tobytes(), from_lin.tobytes())
+    if key not in _LENS_TABLES:
+        if len(_LENS_TABLES) >= 16:
+            _LENS_TABLES.clear()
+        # (uint16 has no torch dtype everywhere: the table travels as int16 bits)
+        _LENS_TABLES[key] = (torch.from_numpy(to_lin.view(np.int16).copy()).to(device), torch.from_numpy(from_lin.copy()).to(device))
+    return _LENS_TABLES[key]
+
+
+def lens_blur(image: torch.Tensor, pred: torch.Tensor, focus=None, focus_at=None, aperture=8.0, max_radius=16.0, dof=0.0, space: str = "depth",
+              sharp: Optional[torch.Tensor] = None, tables=None, want_coc: bool = False):
+    """gp_lens_blur on device tensors: the images refocused under their maps, synthetic depth of field.  image uint8 [B, 3, H, W] ([3, H, W]: one
+    image); pred float [B, 1, H, W] ([B, H, W] and [H, W] too), a depth or disparity map in [0, 1]; exactly one of focus (a value of the map in
+    [0, 1]) and focus_at (a pixel (u, v): the focus is that pixel's nearness, read on the device); aperture, the blur radius in pixels at the
+    far end of the scale; max_radius <= 32 pixels; dof, the half-width of the sharp zone in map units -- each one value or one per image;
+    space "depth" or "disparity"; sharp [B, H, W] or None (non-zero pins the pixel sharp); tables None (`lens_blur.srgb_tables`) or a HOST
+    pair (to_lin uint16 [256], from_lin uint8 [4096]).  Returns uint8 [B, 3, H, W] on the device, and with want_coc (out, coc) with coc the
+    circle of confusion in eighths of a pixel, int16 [B, H, W] (0 .. 256).  Definition in include/genpercept_hip.h;
+    genpercept_amd/lens_blur.py gives the same bits.  Enqueued on the current stream, no synchronisation, nothing read back."""
+    from .lens_blur import SPACES, lens_blur_options
+    lib = load_library()
+    if not torch.is_tensor(image) or image.dtype != torch.uint8 or image.dim() not in (3, 4) or image.shape[-3] != 3:
+        raise ValueError(f"image: uint8 [B, 3, H, W] or [3, H, W], got {image.dtype if torch.is_tensor(image) else type(image)} "
+                         f"{tuple(image.shape) if torch.is_tensor(image) else ''}")
+    if not torch.is_tensor(pred) or not pred.dtype.is_floating_point:
+        raise ValueError(f"pred: a float tensor, got {pred.dtype if torch.is_tensor(pred) else type(pred)}")
+    image = (image[None] if image.dim() == 3 else image).contiguous()
+    pred = _eval_maps(pred, "pred").to(torch.float32).contiguous()
+    assert image.is_cuda and pred.is_cuda
+    b, h, w = (int(v) for v in pred.shape)
+    dev = pred.device
+    if tuple(image.shape) != (b, 3, h, w) or image.device != dev:
+        raise ValueError(f"image {tuple(image.shape)} and pred {tuple(pred.shape)}: one map per image, same size, same device")
+    if space not in SPACES:
+        raise ValueError(f"space is one of {SPACES}, got {space!r}")
+    if not (1 <= h <= 16384 and 1 <= w <= 16384 and 1 <= b <= 65535 and b * h * w < 2 ** 31):
+        raise ValueError(f"lens blur takes 1 .. 65535 images with sides in 1 .. 16384 and B * H * W < 2^31, got {(b, h, w)}")
+    o = lens_blur_options(b, focus, focus_at, aperture, max_radius, dof)
+    if sharp is not None:
+        sharp = _mask_u8(sharp, "sharp", (b, h, w))
+    to_lin, from_lin = _lens_tables(tables, dev)
+    host = np.stack([np.zeros(b, np.int64), o["gain"], o["cmax8"], o["dz"]], 1).astype(np.int32)
+    if o["focus"] is not None:
+        at = torch.from_numpy(o["focus"]).to(dev, non_blocking=True)
+    else:
+        u, v = o["focus_at"][:, 0], o["focus_at"][:, 1]
+        if (u >= w).any() or (v >= h).any():
+            raise ValueError(f"focus_at = (u, v) lies inside the {w} x {h} image, got {o['focus_at'].tolist()}")
+        at = pred.view(b, h * w).gather(1, torch.from_numpy(v * w + u).to(dev, non_blocking=True)[:, None])[:, 0]
+    # the nearness of b values, the 16-bit rule in float32: plumbing on the device, so that a focus picked from the map is not read back
+    q = (at.clamp(0.0, 1.0) * 65535.0).nan_to_num(0.0).to(torch.int32)
+    near = torch.where(at.isnan(), torch.zeros_like(q), q if space == "disparity" else 65535 - q)
+    params = torch.from_numpy(host).to(dev, non_blocking=True)
+    params[:, 0] = near
+    out = torch.empty((b, 3, h, w), dtype=torch.uint8, device=dev)
+    coc = torch.empty((b, h, w), dtype=torch.int16, device=dev) if want_coc else None
+    max_c8 = int(o["cmax8"].max())
+    st = lib.gp_lens_blur(image.data_ptr(), pred.data_ptr(), _ptr(sharp), params.data_ptr(), to_lin.data_ptr(), from_lin.data_ptr(), b, h, w,
+                          SPACES.index(space), max_c8, out.data_ptr(), _ptr(coc), _stream_ptr(dev))
+    if st == GP_ERR_INVALID:
+        raise ValueError(f"gp_lens_blur: invalid arguments (images {(b, h, w)}, space = {space}, max_c8 = {max_c8})")
+    _c_check(st, "gp_lens_blur")
+    return (out, coc) if want_coc else out
 
 
 SEG_OUT = 8        # n, n_void, SEG_METRICS (out[2 .. 6]), n_classes; iou[K] follows

@@ -299,6 +299,36 @@ def run_pointclouds(pipe, base_dir: str, samples: Sequence[Sequence[str]], outpu
     return written
 
 
+def run_refocus(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_dir: str, name_mode: FileNameMode, mode: str = "depth",
+                batch_size: int = 1, rank: int = 0, world: int = 1, focus=None, focus_at=None, aperture=8.0, max_radius=16.0, dof=0.0, tables=None,
+                prefetch: int = 2, **inference_options) -> List[str]:
+    """One refocused photograph per sample with `pipe.refocus_batch_device` (modes depth and disparity): an RGB `.png`, synthetic depth of
+    field under the sample's own prediction.  focus (a value of the map in [0, 1]) or focus_at (a pixel (u, v)), aperture, max_radius and dof
+    are one value each, used for every sample.  Batching, sharding and prefetch as `run_cutouts`.  Returns the paths written.
+    inference_options go to `pipe.predict_batch_device`, `refine` and `tiles` among them."""
+    from .lens_blur import lens_blur_options
+    if mode not in ("depth", "disparity"):
+        raise ValueError(f"a refocus needs a depth map: mode 'depth' or 'disparity', got {mode!r}")
+    if any(np.ndim(v) != 0 for v in (focus if focus is not None else 0.0, aperture, max_radius, dof)) or (focus_at is not None and np.shape(focus_at) != (2,)):
+        raise ValueError("focus, aperture, max_radius and dof are one value each and focus_at one pixel (u, v), used for every sample")
+    lens_blur_options(1, focus, focus_at, aperture, max_radius, dof)
+    if world > 1:
+        lo, hi = _shard(len(samples), rank, world)
+        samples = samples[lo:hi]
+    written = []
+    for group in _size_groups(_decode_ahead(samples, lambda s: _load_rgb(base_dir, s[0], None), prefetch), max(1, batch_size)):
+        out = pipe.refocus_batch_device([img for _, img in group], mode, focus, focus_at, aperture, max_radius, dof, None, tables, **inference_options)
+        out = out.cpu().numpy()
+        assert len(out) == len(group)
+        for (smp, _), px in zip(group, out):
+            scene_dir = os.path.join(output_dir, os.path.dirname(smp[0]))
+            os.makedirs(scene_dir, exist_ok=True)
+            save_to = os.path.join(scene_dir, get_pred_name(os.path.basename(smp[0]), name_mode, suffix=".png"))
+            Image.fromarray(np.ascontiguousarray(np.moveaxis(px, 0, -1))).save(save_to)
+            written.append(save_to)
+    return written
+
+
 def _write_metric_files(output_dir: str, tag: str, names: List[str], per_sample, result: Dict[str, float], header: str) -> None:
     """`per_sample_metrics<tag>.csv` (one row per prediction file) and `eval_metrics<tag>.txt` (header, metric names, means)."""
     os.makedirs(output_dir, exist_ok=True)

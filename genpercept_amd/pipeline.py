@@ -680,6 +680,41 @@ class GenPerceptPipeline:
         out = self.pointcloud_batch_device([image], mode, camera, pointcloud, **inference_options)
         return {k: out[k].cpu().numpy() for k in ("points", "point_normals", "point_rgb", "point_index")}
 
+    @torch.no_grad()
+    def refocus_batch_device(self, images: Union[Sequence[Image.Image], torch.Tensor], mode: str = "depth", focus=None, focus_at=None,
+                             aperture=8.0, max_radius=16.0, dof=0.0, sharp=None, tables=None, **inference_options) -> torch.Tensor:
+        """Synthetic depth of field without a trip to the host: images of one common size (PIL images or a uint8 [B,3,H,W] tensor) -> the
+        images refocused, uint8 [B,3,H,W] ON THE DEVICE: `engine.lens_blur` (gp_lens_blur) applied under the map of
+        `predict_batch_device(images, mode, **inference_options)` at the input size, which never leaves the GPU.  mode: depth or disparity
+        (the space the map is read in).  Exactly one of focus (a value of the map in [0, 1]) and focus_at (a pixel (u, v), whose value is read
+        on the device); aperture: the blur radius in pixels at the far end of the scale; max_radius <= 32; dof: the half-width of the sharp
+        zone in map units; each one value or one per image.  sharp: None or a [B,H,W] tensor, non-zero pins a pixel sharp (a thresholded
+        matting alpha keeps the subject in focus).  tables: None (sRGB to 12-bit linear light) or a host pair (to_lin, from_lin).
+        inference_options may hold `refine` and `tiles` as in `cutout_batch_device`: a refocus shows errors exactly at the depth edge, which
+        `refine` gives the photograph's own edge."""
+        from . import engine as ge
+        from .lens_blur import lens_blur_options
+        if mode not in ("depth", "disparity"):
+            raise ValueError(f"a refocus needs a depth map: mode 'depth' or 'disparity', got {mode!r}")
+        if inference_options.get("match_input_res", True) is not True:
+            raise ValueError("a refocus is made at the input size: match_input_res stays True")
+        if not torch.is_tensor(images):
+            images = torch.stack([torch.from_numpy(np.asarray(im.convert("RGB")).copy()).permute(2, 0, 1) for im in images])
+        if images.dtype != torch.uint8:
+            raise ValueError(f"a refocus takes 8-bit images, got {images.dtype}")
+        lens_blur_options(int(images.shape[0]), focus, focus_at, aperture, max_radius, dof)   # (refused before the model runs)
+        pred = self.predict_batch_device(images, mode, **inference_options)
+        if torch.is_tensor(sharp):
+            sharp = sharp.to(pred.device, non_blocking=True)
+        return ge.lens_blur(images.to(pred.device, non_blocking=True), pred, focus, focus_at, aperture, max_radius, dof, space=mode, sharp=sharp,
+                            tables=tables)
+
+    def refocus(self, image: Image.Image, mode: str = "depth", focus=None, focus_at=None, aperture=8.0, max_radius=16.0, dof=0.0, sharp=None,
+                tables=None, **inference_options) -> Image.Image:
+        """`refocus_batch_device` for one PIL image: the refocused photograph as a PIL image."""
+        out = self.refocus_batch_device([image], mode, focus, focus_at, aperture, max_radius, dof, sharp, tables, **inference_options)
+        return Image.fromarray(np.ascontiguousarray(out[0].permute(1, 2, 0).cpu().numpy()))
+
     def _run_device(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None, refine=None,
                     tiles=None) -> List[GenPerceptOutput]:
         """Pre / post processing on the GPU (gp_preprocess / gp_postprocess): the image goes up once, resize_max_res, the model, the

@@ -34,6 +34,8 @@
  *   gp_depth_geometry (no reference code: genpercept/losses/metric3d_losses/VNL.py transfer_xyz unprojects with x = (u - u0) z / f and that
  *                       is all) a depth or disparity prediction as a point map, edge-aware surface normals and a point cloud without the
  *                       flying pixels of depth edges
+ *   gp_lens_blur      (no reference code) the photograph refocused under its depth or disparity prediction: a variable-radius,
+ *                       occlusion-aware disc gather in integer arithmetic
  *   gp_ensemble_gather, gp_ensemble_reduce
  *                     ensemble_depth's tensor half (the BFGS fit stays on the host)   genpercept/util/ensemble.py:43-205;
  *                                                                   genpercept_pipeline.py:289-298
@@ -619,6 +621,46 @@ gp_status gp_depth_geometry(const float* pred, const unsigned char* mask /* or N
                             double min_cos, int stride, float* xyz, float* normal, unsigned char* keep, float* points, float* point_normals,
                             unsigned char* point_rgb, int* point_index, long long* offsets, void* workspace, long long workspace_bytes,
                             void* stream);
+
+/* ---- synthetic depth of field: the photograph refocused under its depth prediction (DEVICE pointers; stateless, stream-ordered, no host synchronisation, no atomics; csrc/lens_blur.hip) ----
+ * The image-space use of a monocular depth map: the defocus blur of a wide aperture, driven by the map.  Framework ops give the two classic
+ * defects -- blurred background bleeds over the sharp subject's outline, and a blurred foreground is cut off at its own silhouette instead of
+ * spreading over what lies behind it.  Here every output pixel is a variable-radius, occlusion-aware gather.  The whole definition is integer
+ * arithmetic, so the result does not depend on the order of the gather and the device equals the host route genpercept_amd/lens_blur.py bit
+ * for bit; the arithmetic stands once more in csrc/lens_blur_math.h.
+ * Inputs per image: image uint8 [3][H][W]; pred fp32 [1][H][W]; sharp uint8 [H][W] or NULL, non-zero pins the pixel sharp (a matting alpha,
+ *   thresholded, keeps the subject in focus); a row of four int32 parameters F, gain, cmax8, dz.  Per call: space = 0 (depth) or 1 (disparity);
+ *   to_lin uint16 [256], strictly increasing with values <= 4095, the bytes of the image as linear light; from_lin uint8 [4096], its inverse,
+ *   from_lin[to_lin[v]] == v for every v.  1 <= H, W <= 16384 and B * H * W < 2^31; 0 <= F, dz <= 65535; 0 <= gain <= 32768;
+ *   0 <= cmax8 <= max_c8 <= 256 (a blur radius of at most 32 pixels, in eighths of a pixel).
+ * 1. Nearness: Q = (uint16)(clamp(pred, 0, 1) * 65535.0f), the 16-bit rule of gp_postprocess.  D = Q in disparity space and D = 65535 - Q in
+ *    depth space, so a larger D is nearer.  A NaN pixel has D = 0.
+ * 2. Circle of confusion in eighths of a pixel: e = max(0, |D - F| - dz); c = min(cmax8, (e * gain + 32768) >> 16); c = 0 where pred is NaN or
+ *    sharp is non-zero.  F is the nearness in focus, dz the half-width of the sharp zone around it.  The radius is LINEAR IN THE MAP'S VALUE:
+ *    for a disparity map that is the thin-lens law (the circle of confusion of a thin lens is proportional to |1 / z - 1 / z_focus|), whatever
+ *    the unknown scale and shift of an affine-invariant disparity; for an affine-invariant depth map it is a stated convention, not optics.
+ * 3. Disc sizes: n(c) = the number of integer offsets (dx, dy) with 64 (dx^2 + dy^2) <= (c + 4)^2, a disc of radius c / 8 + 1 / 2 pixels;
+ *    w(c) = floor(2^20 / n(c)).  n(0) = n(3) = 1, n(4) = 5, n(8) = 9, n(16) = 21, n(64) = 225, n(256) = 3313, w(256) = 316.
+ * 4. Gather: for the output pixel p, a source pixel q inside the image at offset (dx, dy) has the reach r = c_q if D_q >= D_p -- a nearer or
+ *    equally near source spreads over p -- and r = min(c_q, c_p) otherwise: a source behind p is seen through p only as far as p itself is
+ *    blurred.  q contributes iff 64 (dx^2 + dy^2) <= (r + 4)^2, with the weight w(r).  Sw = sum w, S_k = sum w * to_lin[image_k(q)]: exact
+ *    integers that fit in 64 bits (at most 65^2 sources * 2^20 * 4095).  p always contributes to itself, so Sw > 0.  Pixels outside the image
+ *    do not exist; nothing is replicated.
+ * 5. Output: out_k(p) = from_lin[(2 S_k + Sw) / (2 Sw)], integer division.  coc(p) = c_p.
+ * Outputs: out uint8 [B][3][H][W] (not the image itself); coc uint16 [B][H][W] or NULL.
+ * params: int32 [B][4] in DEVICE memory, so that a focus picked from the map on the device needs no read-back; for the same reason its values
+ * cannot be refused, and one outside its range is clamped into it (cmax8 into 0 .. max_c8).  max_c8, a host value, sizes the apron every
+ * tile is staged with.  to_lin and from_lin are DEVICE tables; their monotonicity and round trip are the caller's to check
+ * (genpercept_amd/lens_blur.py check_tables does); the kernel reads 12 bits of a to_lin value, so a wrong table gives wrong colours and no
+ * wild access.  One kernel launch for every B: a workgroup stages its 32 x 16 tile and the apron in LDS as one 64-bit word per pixel and
+ * bounds its search by the largest c of the staged region; no workspace, nothing read back; an image's bytes are the same from call to call
+ * and in every batch.
+ * GP_ERR_INVALID before any HIP call: null image / pred / params / to_lin / from_lin / out, B < 1, B > 65535, H or W outside 1 .. 16384,
+ * B * H * W >= 2^31, space outside 0 .. 1, max_c8 outside 0 .. 256, pred or params not 4-byte aligned, to_lin or coc not 2-byte aligned,
+ * out == image. */
+gp_status gp_lens_blur(const unsigned char* image, const float* pred, const unsigned char* sharp /* or NULL */, const int* params /* [B][4] */,
+                       const unsigned short* to_lin /* [256] */, const unsigned char* from_lin /* [4096] */, int B, int H, int W, int space,
+                       int max_c8, unsigned char* out, unsigned short* coc /* or NULL */, void* stream);
 
 /* ---- test-time ensembling on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation, no atomics; csrc/ensemble.hip) ----
  * The tensor half of ensemble_depth (genpercept/util/ensemble.py:43-205, called at genpercept_pipeline.py:289-298) for the E members of each of

@@ -99,6 +99,19 @@
    (allocations and its one read of the offsets included), against `geometry.depth_geometry` on the same arrays on the host (wall clock,
    one run); every output is compared on the spot (bit-equal).  The bytes the call has to move (4 B/px read, 25 B/px planes, 31 B/point)
    over the device time stand next to the device-to-device copy bandwidth measured in the same process.  `--no-host` skips the host route.
+
+  python tools/eval_bench.py --lens-blur --out profiles/<name>.json
+
+13. `--lens-blur` (instead of 1 and 2): the `gp_lens_blur` entry behind `engine.lens_blur` (synthetic depth of field, one launch) at
+   1 x 768 x 768 and 1 x 2048 x 3072 with aperture = max_radius = 16, depth space, sRGB tables, on three maps: a scene (a smooth map with
+   noise and a depth edge down the middle, focus 0.5), the worst case (every pixel at the full radius) and a map in focus everywhere but a
+   64 x 64 patch, which shows what the search bound over the staged region saves; the output bits are the same either way.  The median of
+   25 consecutive calls, each between two device events, after 0.3 s of the same call as warm-up, for the C entry on preallocated buffers and for `engine.lens_blur` itself,
+   against `lens_blur.lens_blur` on the same arrays on the host (wall clock, one run; compared on the spot, bit-equal).  The host route is
+   timed at a size only while the rate of the size before predicts a minute or less; otherwise the row says so.  Offsets per second are
+   counted twice, tested (what the kernel walks) and contributing (what the definition sums), and the vector-ALU instructions of the
+   tested offsets over the time stand next to the issue rate of the card (one wave64 instruction per SIMD every 2 cycles).  `--no-host`
+   skips the host route.
 Needs a GPU; there is no CPU fall-back."""
 import argparse
 import json
@@ -719,6 +732,129 @@ def bench_geometry(b, h, w, iters, host, copy_gb_per_s, radius=2, stride=1, repe
     return res
 
 
+LENS_SHAPES = ((1, 768, 768), (1, 2048, 3072))
+LENS_VALU_PER_TAP = 18          # vector-ALU instructions per tested offset in the compiled gather loop of lb_gather_kernel (its ISA, -O3, gfx950)
+LENS_VALU_ISSUE_CYCLES = 2      # a SIMD issues one wave64 vector instruction per 2 cycles (MI355X_MICROARCH.md, per-instruction constants)
+LENS_SIMDS = 256 * 4
+LENS_CLOCK_MHZ = 2400.0         # the nominal shader clock the issue rate is stated at (the sampled mean also covers the host route's idle time)
+
+
+def lens_taps(pred, rows, space, d):
+    """(tested, contributing) offsets of one gp_lens_blur call, counted with torch ops on the device (a count for the benchmark, not a product
+    path).  tested: per 32 x 16 tile n(cm) for the largest c of its staged region, times the tile's pixels inside the image.  contributing: the
+    sources of step 4 over all output pixels."""
+    import torch.nn.functional as F
+    from genpercept_amd import lens_blur as lb
+    b, h, w = pred.shape
+    tested = contributing = 0
+    counts = torch.tensor([lb.disc_count(c) for c in range(lb.MAX_C8 + 1)], device=d)
+    R = (int(rows[:, 2].max()) + 4) >> 3
+    for k in range(b):
+        Dn = lb.nearness(pred[k], space)
+        D = torch.from_numpy(Dn).to(d)
+        c = torch.from_numpy(lb.circle_of_confusion(Dn, np.isnan(pred[k]), rows[k])).to(d)
+        ph, pw = -(-h // 16) * 16, -(-w // 32) * 32
+        padded = F.pad(c[None, None].float(), (R, R + pw - w, R, R + ph - h))
+        cm = F.max_pool2d(padded, (16 + 2 * R, 32 + 2 * R), stride=(16, 32))[0, 0].long()
+        inside = F.avg_pool2d(F.pad(torch.ones((1, 1, h, w), device=d), (0, pw - w, 0, ph - h)), (16, 32), divisor_override=1)[0, 0].long()
+        tested += int((counts[cm] * inside).sum())
+        Dp, cp = F.pad(D, (R, R, R, R)), F.pad(c, (R, R, R, R))
+        cmax = int(c.max())
+        total = torch.zeros((), dtype=torch.int64, device=d)
+        for dy in range(-R, R + 1):
+            for dx in range(-R, R + 1):
+                d2 = 64 * (dx * dx + dy * dy)
+                if d2 > (cmax + 4) ** 2:
+                    continue
+                Dq, cq = Dp[R + dy:R + dy + h, R + dx:R + dx + w], cp[R + dy:R + dy + h, R + dx:R + dx + w]
+                # (an offset that leaves the image has c = 0 there and contributes only at d2 = 0, which stays inside)
+                r = torch.where(Dq >= D, cq, torch.minimum(cq, c))
+                total += (d2 <= (r + 4) ** 2).sum()
+        contributing += int(total)
+    return tested, contributing
+
+
+def lens_timed_calls(call, n, warm_s=0.3):
+    """ms of each of n consecutive calls, a device event between every two, after warm_s seconds of the same call: a window of a few calls
+    after the host route has kept the card idle would measure the clock coming up."""
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < warm_s:
+        for _ in range(10):
+            call()
+        torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(n + 1)]
+    ev[0].record()
+    for k in range(n):
+        call()
+        ev[k + 1].record()
+    torch.cuda.synchronize()
+    return [ev[k].elapsed_time(ev[k + 1]) for k in range(n)]
+
+
+def bench_lens_blur(b, h, w, iters, host, host_budget_s=60.0, radius=16.0, timed=25):
+    """gp_lens_blur on preallocated buffers and engine.lens_blur itself at aperture = max_radius = `radius`, sRGB tables, depth space, on three
+    maps -- a scene (smooth map with noise and a depth edge down the middle, focus 0.5), the worst case (every pixel at the full radius) and a
+    map in focus everywhere but a 64 x 64 patch -- against lens_blur.lens_blur on the host.  The output bits are compared where the host
+    runs."""
+    from genpercept_amd import engine as ge
+    from genpercept_amd import lens_blur as lb
+    d = torch.device("cuda", 0)
+    lib = ge.load_library()
+    rng = np.random.default_rng(17)
+    image = rng.integers(0, 256, (b, 3, h, w), dtype=np.uint8)
+    scene = case(b, h, w, 17)[0]
+    scene[:, :, w // 2:] = np.clip(scene[:, :, w // 2:] + 0.2, 0, 1)
+    patch = np.zeros((b, h, w), np.float32)
+    patch[:, h // 2 - 32:h // 2 + 32, w // 2 - 32:w // 2 + 32] = 1.0
+    maps = dict(scene=(scene, 0.5), worst_case=(np.ones((b, h, w), np.float32), 0.0), in_focus_but_a_patch=(patch, 0.0))
+    ti = torch.from_numpy(image).to(d)
+    to_lin, from_lin = ge._lens_tables(None, d)
+    out = torch.empty((b, 3, h, w), dtype=torch.uint8, device=d)
+    stream = int(torch.cuda.current_stream(d).cuda_stream)
+    res = dict(shape=[b, 3, h, w], options=dict(aperture=radius, max_radius=radius, dof=0.0, space="depth", tables="srgb"), launches_per_call=1,
+               workspace_bytes=0, timed_calls=timed, statistic="median of `timed_calls` consecutive calls, each between two device events, after 0.3 s of the same call as warm-up",
+               valu_rule=f"tested offsets / 64 lanes * {LENS_VALU_PER_TAP} vector instructions (the compiled gather loop) * {LENS_VALU_ISSUE_CYCLES} cycles "
+                         f"/ ({LENS_SIMDS} SIMDs * the shader clock * the time)", maps={})
+    host_s = 0.0
+    for name, (pred, focus) in maps.items():
+        tp = torch.from_numpy(pred).to(d)
+        rows = lb.lens_params(pred[:, None], "depth", focus=focus, aperture=radius, max_radius=radius)
+        params = torch.from_numpy(rows).to(d)
+        max_c8 = int(rows[:, 2].max())
+
+        def entry():
+            rc = lib.gp_lens_blur(ti.data_ptr(), tp.data_ptr(), None, params.data_ptr(), to_lin.data_ptr(), from_lin.data_ptr(), b, h, w, 0, max_c8,
+                                  out.data_ptr(), None, stream)
+            assert rc == ge.GP_OK, rc
+
+        entry_runs = sorted(lens_timed_calls(entry, timed))
+        entry_ms = entry_runs[len(entry_runs) // 2]
+        call = lambda: ge.lens_blur(ti, tp, focus=focus, aperture=radius, max_radius=radius)  # noqa: E731
+        call_ms = float(np.median(lens_timed_calls(call, timed)))
+        got = call().cpu().numpy()
+        tested, contributing = lens_taps(pred, rows, "depth", d)
+        row = dict(focus=focus, gp_lens_blur_us_per_call=1e3 * entry_ms, gp_lens_blur_us_min_max=[1e3 * entry_runs[0], 1e3 * entry_runs[-1]], engine_lens_blur_us_per_call=1e3 * call_ms, tested_offsets=tested,
+                   contributing_offsets=contributing, tested_offsets_per_s=tested / entry_ms * 1e3, contributing_offsets_per_s=contributing / entry_ms * 1e3,
+                   valu_instructions=tested / 64 * LENS_VALU_PER_TAP)
+        predicted_s = LENS_HOST_S_PER_PIXEL[0] * h * w   # (0 at the first size)
+        if host and predicted_s <= host_budget_s:
+            t0 = time.perf_counter()
+            ref = lb.lens_blur(image, pred[:, None], focus=focus, aperture=radius, max_radius=radius)
+            host_ms = (time.perf_counter() - t0) * 1e3
+            assert got.dtype == ref.dtype and got.shape == ref.shape and np.array_equal(got, ref), name
+            row.update(host_lens_blur_ms=host_ms, host_runs=1, host_over_engine_call=host_ms / call_ms, output_equals_host=True)
+            host_s = max(host_s, host_ms / 1e3)
+        elif host:
+            row["host"] = f"not timed at this size: about {predicted_s:.0f} s by the rate of the smaller size, above the budget of {host_budget_s:.0f} s"
+        res["maps"][name] = row
+    if host_s:
+        LENS_HOST_S_PER_PIXEL[0] = host_s / (h * w)
+    return res
+
+
+LENS_HOST_S_PER_PIXEL = [0.0]   # the host route's rate at the last size it ran at, to decide whether the next size is timed
+
+
 def bench_loop(n_images, batch_sizes, repeats):
     from PIL import Image
     from genpercept_amd import GenPerceptPipeline
@@ -782,12 +918,24 @@ def main():
     ap.add_argument("--guided", action="store_true", help="time gp_guided_upsample / engine.guided_upsample against guided.guided_upsample instead")
     ap.add_argument("--tiles", action="store_true", help="time gp_tile_merge / engine.tile_merge against tiled.tile_merge instead")
     ap.add_argument("--geometry", action="store_true", help="time gp_depth_geometry / engine.depth_geometry against geometry.depth_geometry instead")
+    ap.add_argument("--lens-blur", action="store_true", help="time gp_lens_blur / engine.lens_blur against lens_blur.lens_blur instead")
     ap.add_argument("--no-host", action="store_true",
-                    help="with --structure, --matting, --seg, --band, --foreground, --guided, --tiles or --geometry: the device calls alone")
+                    help="with --structure, --matting, --seg, --band, --foreground, --guided, --tiles, --geometry or --lens-blur: the device calls alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU")
-    if a.geometry:
+    if a.lens_blur:
+        import bench
+        with bench.ClockPowerSampler("cuda:0") as clock:
+            rows = [bench_lens_blur(*s, a.iters, not a.no_host) for s in LENS_SHAPES]
+        summary = clock.summary()
+        mhz = LENS_CLOCK_MHZ
+        for r in rows:
+            for m in r["maps"].values():
+                m["valu_issue_share"] = m["valu_instructions"] * LENS_VALU_ISSUE_CYCLES / (LENS_SIMDS * mhz * 1e6 * m["gp_lens_blur_us_per_call"] * 1e-6)
+        res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box", build_id=bench.source_build_id(), clock=summary,
+                   shader_clock_mhz_used=mhz, lens_blur=rows)
+    elif a.geometry:
         import bench
         bw = copy_bandwidth(torch.device("cuda", 0))
         with bench.ClockPowerSampler("cuda:0") as clock:
@@ -849,7 +997,7 @@ def main():
     else:
         res = dict(device=torch.cuda.get_device_name(0), eval_depth=[bench_eval(1, 4032, 6048, a.iters, 1), bench_eval(4, 480, 640, a.iters, 3)])
     if (not a.skip_loop and not a.normals and not a.masks and not a.structure and not a.matting and not a.seg and not a.band and not a.foreground
-            and not a.guided and not a.tiles and not a.geometry):
+            and not a.guided and not a.tiles and not a.geometry and not a.lens_blur):
         res["infer_and_evaluate"] = bench_loop(16, (1, 4), 3)
     text = json.dumps(res, indent=1)
     print(text)
