@@ -12,6 +12,7 @@ import torch
 
 from .eval_metrics import (BAND_METRIC, BAND_PLANES, BOUNDARY_METRICS, MASK_METRICS, MATTING_METRICS, SEG_MAX_K, SEG_METRICS,  # noqa: F401
                            STRUCTURE_METRICS, TRIMAP_METRICS)  # the names of the evaluators' values: one list each, stated in eval_metrics
+from .post_common import MAX_DIM, SPACES
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # One library per 16-bit element type (csrc/common.h): identical C-ABI, bf16 or IEEE fp16 activations / weights / MFMA operands.
@@ -979,6 +980,55 @@ def _unpacked(buf: torch.Tensor, b: int, n_out: int):
     return host[:b * n_out].view("float64").reshape(b, n_out), host[b * n_out:].reshape(b, -1)
 
 
+# ---- what the post-processing ops (foreground, guided_upsample, tile_merge, depth_geometry, lens_blur) share -------------------------------
+def _images_u8(x, name: str) -> torch.Tensor:
+    """8-bit RGB images as a contiguous uint8 [B, 3, H, W] tensor (one image may come without the batch axis)."""
+    if not torch.is_tensor(x) or x.dtype != torch.uint8 or x.dim() not in (3, 4) or x.shape[-3] != 3:
+        raise ValueError(f"{name}: uint8 [B, 3, H, W] or [3, H, W], got {x.dtype if torch.is_tensor(x) else type(x)} "
+                         f"{tuple(x.shape) if torch.is_tensor(x) else ''}")
+    return (x[None] if x.dim() == 3 else x).contiguous()
+
+
+def _float32(x, name: str) -> torch.Tensor:
+    """A prediction of any float dtype as float32 (the kernels read float32)."""
+    if not torch.is_tensor(x) or not x.dtype.is_floating_point:
+        raise ValueError(f"{name}: a float tensor, got {x.dtype if torch.is_tensor(x) else type(x)}")
+    return x.to(torch.float32)
+
+
+def _float_maps(x, name: str) -> torch.Tensor:
+    """One-channel float maps as contiguous float32 [B, H, W] (`_eval_maps` shapes)."""
+    return _eval_maps(_float32(x, name), name).contiguous()
+
+
+def _same_batch(image: torch.Tensor, shape, device, name: str) -> torch.Tensor:
+    """`image` ([B, 3, H, W], of `_images_u8`) goes with maps of `shape` = (B, H, W) on `device`: one map per image, same size, same device."""
+    b, h, w = shape
+    if tuple(image.shape) != (b, 3, h, w) or image.device != device:
+        raise ValueError(f"{name} {tuple(image.shape)} on {image.device} and the maps {(b, h, w)} on {device}: one map per image, same size, same device")
+    return image
+
+
+def _post_dims(b: int, h: int, w: int, what: str, count_limit: bool = True) -> None:
+    """The range every post-processing entry takes: 1 .. 65535 images, sides in 1 .. MAX_DIM and, where the kernels index the batch with
+    32 bits (count_limit), B * H * W < 2^31."""
+    if not (1 <= b <= 65535 and 1 <= h <= MAX_DIM and 1 <= w <= MAX_DIM) or (count_limit and b * h * w >= 2 ** 31):
+        raise ValueError(f"{what} takes 1 .. 65535 images with sides in 1 .. {MAX_DIM}{' and B * H * W < 2^31' if count_limit else ''}, got {(b, h, w)}")
+
+
+def _op_workspace(name: str, device, *dims):
+    """`_workspace` of what the entry `name` asks for through its `name`_workspace(*dims)."""
+    return _workspace(getattr(load_library(), name + "_workspace")(*dims), device)
+
+
+def _launch(name: str, describe: str, *args) -> None:
+    """Call the entry `name`; the status of refused arguments is a ValueError that says what was passed, any other failure a RuntimeError."""
+    st = getattr(load_library(), name)(*args)
+    if st == GP_ERR_INVALID:
+        raise ValueError(f"{name}: invalid arguments ({describe})")
+    _c_check(st, name)
+
+
 def eval_depth_raw(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, alignment: Optional[str] = "least_square",
                    alignment_max_res: Optional[int] = None, min_depth: float = 1e-3, max_depth: float = 10.0) -> torch.Tensor:
     """gp_eval_depth on device tensors: float64 [B, 14] ON THE DEVICE = s, t, n_valid, n_fit, then the ten metrics in eval_metrics.METRICS
@@ -1194,7 +1244,6 @@ def mask_band(a: torch.Tensor, lo: int, hi: int, reach: int, metric="euclidean",
     (0 / 128 / 255).  metric "euclidean": reach is a squared radius (<= 2^24); "chebyshev": a radius (<= 4096).  border: the outside of the
     image counts as Bc.  Definitions in include/genpercept_hip.h; eval_metrics.mask_band gives the same bits.  Enqueued on the current
     stream, no synchronisation."""
-    lib = load_library()
     a = _eval_maps(a, "a")
     assert a.is_cuda
     if metric not in BAND_METRIC:
@@ -1206,12 +1255,9 @@ def mask_band(a: torch.Tensor, lo: int, hi: int, reach: int, metric="euclidean",
     b, h, w = (int(v) for v in a.shape)
     planes = torch.empty((len(want), b, h, w), dtype=torch.uint8, device=a.device)
     outs = [_ptr(planes[want.index(k)]) if k in want else None for k in BAND_PLANES]
-    ws, nbytes = _workspace(lib.gp_mask_band_workspace(b, h, w), a.device)
-    st = lib.gp_mask_band(a.data_ptr(), int(is_u8), b, h, w, int(lo), int(hi), BAND_METRIC[metric], int(reach), int(bool(border)), *outs,
-                          ws.data_ptr(), nbytes, _stream_ptr(a.device))
-    if st == GP_ERR_INVALID:
-        raise ValueError(f"gp_mask_band: invalid arguments (lo = {lo}, hi = {hi}, reach = {reach}, metric = {metric!r}, maps {(b, h, w)})")
-    _c_check(st, "gp_mask_band")
+    ws, nbytes = _op_workspace("gp_mask_band", a.device, b, h, w)
+    _launch("gp_mask_band", f"lo = {lo}, hi = {hi}, reach = {reach}, metric = {metric!r}, maps {(b, h, w)}", a.data_ptr(), int(is_u8), b, h, w, int(lo),
+            int(hi), BAND_METRIC[metric], int(reach), int(bool(border)), *outs, ws.data_ptr(), nbytes, _stream_ptr(a.device))
     return {k: planes[j] for j, k in enumerate(want)}
 
 
@@ -1251,24 +1297,17 @@ FOREGROUND_OUTPUTS = ["fg", "bg", "rgba", "comp"]
 
 def foreground(image: torch.Tensor, alpha: torch.Tensor, background=None, want: Sequence[str] = ("rgba",), reg: float = 1e-5, gw: float = 1.0,
                n_small: int = 10, n_big: int = 2):
-    """gp_foreground on device tensors: image uint8 [B, 3, H, W] or [3, H, W]; alpha [B, H, W], [B, 1, H, W] or [H, W], a float map in [0, 1]
+    """gp_foreground on device tensors: image uint8 [B, 3, H, W] ([3, H, W]: one image); alpha [B, H, W], [B, 1, H, W] or [H, W], a float map in [0, 1]
     (quantised to 8 bits by the kernel) or uint8.  Returns a dict of the outputs named in `want` (FOREGROUND_OUTPUTS): fg, bg float32
     [B, 3, H, W] (the estimated foreground and background colours), rgba uint8 [B, H, W, 4] (the cutout), comp uint8 [B, 3, H, W] (the
     foreground over `background`: a uint8 [B, 3, H, W] / [3, H, W] device image or one colour of three bytes).  Definition in
     include/genpercept_hip.h; genpercept_amd/foreground.py gives the same bits.  Enqueued on the current stream, no synchronisation."""
     from .foreground import check_options
-    lib = load_library()
-    if not torch.is_tensor(image) or image.dtype != torch.uint8 or image.dim() not in (3, 4) or image.shape[-3] != 3:
-        raise ValueError(f"image: uint8 [B, 3, H, W] or [3, H, W], got {image.dtype if torch.is_tensor(image) else type(image)} "
-                         f"{tuple(image.shape) if torch.is_tensor(image) else ''}")
-    image = (image[None] if image.dim() == 3 else image).contiguous()
-    alpha = _eval_maps(alpha, "alpha")
-    assert image.is_cuda and alpha.is_cuda
-    b, _, h, w = (int(v) for v in image.shape)
-    if tuple(alpha.shape) != (b, h, w):
-        raise ValueError(f"alpha {tuple(alpha.shape)} does not match the images {(b, h, w)}")
-    if h > 16384 or w > 16384:
-        raise ValueError(f"cutouts take images of at most 16384 x 16384, got {h} x {w}")
+    image = _images_u8(image, "image")
+    alpha, is_u8 = _map8(_eval_maps(alpha, "alpha"), "alpha")
+    b, h, w = (int(v) for v in alpha.shape)
+    _same_batch(image, (b, h, w), alpha.device, "image")
+    _post_dims(b, h, w, "a cutout", count_limit=False)
     reg, gw, n_small, n_big = check_options(reg, gw, n_small, n_big)
     want = list(want)
     if not want or any(k not in FOREGROUND_OUTPUTS for k in want) or len(set(want)) != len(want):
@@ -1278,24 +1317,19 @@ def foreground(image: torch.Tensor, alpha: torch.Tensor, background=None, want: 
         if background is None:
             raise ValueError("the composite needs a background: a uint8 image or one colour")
         if torch.is_tensor(background) and background.dim() >= 3:
-            new_bg = (background[None] if background.dim() == 3 else background)
-            if new_bg.dtype != torch.uint8 or tuple(new_bg.shape) != (b, 3, h, w) or new_bg.device != image.device:
-                raise ValueError(f"background: uint8 {(b, 3, h, w)} on the images' device, got {new_bg.dtype} {tuple(new_bg.shape)}")
-            new_bg = new_bg.contiguous()
+            new_bg = _same_batch(_images_u8(background, "background"), (b, h, w), image.device, "background")
         else:
             rgb = [int(v) for v in (background.tolist() if hasattr(background, "tolist") else background)]
             if len(rgb) != 3 or any(not 0 <= v <= 255 for v in rgb):
                 raise ValueError(f"background: one colour is three bytes, got {background!r}")
             new_rgb = rgb[0] << 16 | rgb[1] << 8 | rgb[2]
-    alpha, is_u8 = _map8(alpha, "alpha")
+    assert image.is_cuda
     kinds = dict(fg=((b, 3, h, w), torch.float32), bg=((b, 3, h, w), torch.float32), rgba=((b, h, w, 4), torch.uint8), comp=((b, 3, h, w), torch.uint8))
     outs = {k: torch.empty(kinds[k][0], dtype=kinds[k][1], device=image.device) for k in want}
-    ws, nbytes = _workspace(lib.gp_foreground_workspace(b, h, w), image.device)
-    st = lib.gp_foreground(image.data_ptr(), alpha.data_ptr(), int(is_u8), b, h, w, float(reg), float(gw), n_small, n_big, _ptr(new_bg), new_rgb,
-                           *[_ptr(outs.get(k)) for k in FOREGROUND_OUTPUTS], ws.data_ptr(), nbytes, _stream_ptr(image.device))
-    if st == GP_ERR_INVALID:
-        raise ValueError(f"gp_foreground: invalid arguments (images {(b, h, w)}, reg = {reg}, gw = {gw}, n_small = {n_small}, n_big = {n_big})")
-    _c_check(st, "gp_foreground")
+    ws, nbytes = _op_workspace("gp_foreground", image.device, b, h, w)
+    _launch("gp_foreground", f"images {(b, h, w)}, reg = {reg}, gw = {gw}, n_small = {n_small}, n_big = {n_big}", image.data_ptr(), alpha.data_ptr(),
+            int(is_u8), b, h, w, float(reg), float(gw), n_small, n_big, _ptr(new_bg), new_rgb, *[_ptr(outs.get(k)) for k in FOREGROUND_OUTPUTS],
+            ws.data_ptr(), nbytes, _stream_ptr(image.device))
     return outs
 
 
@@ -1319,31 +1353,24 @@ def guided_upsample(guide_lo: torch.Tensor, pred: torch.Tensor, guide: torch.Ten
     (0, 1]).  Definition in include/genpercept_hip.h; genpercept_amd/guided.py gives the same bits.  Allocates the workspace; enqueued on the
     current stream, no synchronisation."""
     from .guided import check_options
-    lib = load_library()
-    for name, g in (("guide_lo", guide_lo), ("guide", guide)):
-        if not torch.is_tensor(g) or g.dtype != torch.uint8 or g.dim() not in (3, 4) or g.shape[-3] != 3:
-            raise ValueError(f"{name}: uint8 [B, 3, H, W] or [3, H, W], got {g.dtype if torch.is_tensor(g) else type(g)} "
-                             f"{tuple(g.shape) if torch.is_tensor(g) else ''}")
-    if not torch.is_tensor(pred) or not pred.dtype.is_floating_point or pred.dim() not in (3, 4):
-        raise ValueError(f"pred: float [B, C, h, w] or [C, h, w], got {pred.dtype if torch.is_tensor(pred) else type(pred)}")
-    guide_lo = (guide_lo[None] if guide_lo.dim() == 3 else guide_lo).contiguous()
-    guide = (guide[None] if guide.dim() == 3 else guide).contiguous()
-    pred = (pred[None] if pred.dim() == 3 else pred).to(torch.float32).contiguous()
-    assert guide_lo.is_cuda and pred.is_cuda and guide.is_cuda
+    guide_lo, guide, pred = _images_u8(guide_lo, "guide_lo"), _images_u8(guide, "guide"), _float32(pred, "pred")
+    if pred.dim() not in (3, 4):
+        raise ValueError(f"pred: float [B, C, h, w] or [C, h, w], got {tuple(pred.shape)}")
+    pred = (pred[None] if pred.dim() == 3 else pred).contiguous()
     b, c, h, w = (int(v) for v in pred.shape)
     hh, ww = int(guide.shape[-2]), int(guide.shape[-1])
-    if c not in (1, 3) or tuple(guide_lo.shape) != (b, 3, h, w) or guide.shape[0] != b:
-        raise ValueError(f"pred {tuple(pred.shape)} needs 1 or 3 channels, guide_lo {tuple(guide_lo.shape)} its size and guide {tuple(guide.shape)} its batch")
-    if max(h, w, hh, ww) > 16384 or min(h, w, hh, ww) < 1 or not 1 <= b <= 65535:
-        raise ValueError(f"guided upsampling takes 1 .. 65535 images with sides in 1 .. 16384, got {b} x {h} x {w} -> {hh} x {ww}")
+    if c not in (1, 3):
+        raise ValueError(f"pred {tuple(pred.shape)} needs 1 or 3 channels")
+    _same_batch(guide_lo, (b, h, w), pred.device, "guide_lo")
+    _same_batch(guide, (b, hh, ww), pred.device, "guide")
+    _post_dims(b, h, w, "guided upsampling", count_limit=False)
+    _post_dims(b, hh, ww, "guided upsampling", count_limit=False)
     radius, eps = check_options(radius, eps)
+    assert pred.is_cuda
     out = torch.empty((b, c, hh, ww), dtype=torch.float32, device=pred.device)
-    ws, nbytes = _workspace(lib.gp_guided_upsample_workspace(b, c, h, w), pred.device)
-    st = lib.gp_guided_upsample(guide_lo.data_ptr(), pred.data_ptr(), c, guide.data_ptr(), b, h, w, hh, ww, radius, eps, out.data_ptr(), ws.data_ptr(),
-                                nbytes, _stream_ptr(pred.device))
-    if st == GP_ERR_INVALID:
-        raise ValueError(f"gp_guided_upsample: invalid arguments ({(b, c, h, w)} -> {(hh, ww)}, radius = {radius}, eps = {eps})")
-    _c_check(st, "gp_guided_upsample")
+    ws, nbytes = _op_workspace("gp_guided_upsample", pred.device, b, c, h, w)
+    _launch("gp_guided_upsample", f"{(b, c, h, w)} -> {(hh, ww)}, radius = {radius}, eps = {eps}", guide_lo.data_ptr(), pred.data_ptr(), c, guide.data_ptr(),
+            b, h, w, hh, ww, radius, eps, out.data_ptr(), ws.data_ptr(), nbytes, _stream_ptr(pred.device))
     return out
 
 
@@ -1355,18 +1382,14 @@ def tile_merge(base: torch.Tensor, tiles: torch.Tensor, ys, xs, overlap: int, al
     and with want_fit (out, fit) with fit float64 [B, N, 2] = (s, t) of every tile.  Definition in include/genpercept_hip.h;
     genpercept_amd/tiled.py gives the same bits.  Allocates the workspace; enqueued on the current stream, no synchronisation."""
     from .tiled import ALIGNMENTS
-    lib = load_library()
-    for name, v in (("base", base), ("tiles", tiles)):
-        if not torch.is_tensor(v) or not v.dtype.is_floating_point:
-            raise ValueError(f"{name}: a float tensor, got {v.dtype if torch.is_tensor(v) else type(v)}")
+    base, tiles = _float32(base, "base"), _float32(tiles, "tiles")
     if base.dim() == 3 and tiles.dim() == 4:
         base, tiles = base[None], tiles[None]
     if base.dim() != 4 or tiles.dim() != 5 or tiles.shape[0] != base.shape[0] or tiles.shape[2] != base.shape[1] or base.shape[1] not in (1, 3):
         raise ValueError(f"base [B, C, H, W] with C = 1 or 3 and tiles [B, N, C, wh, ww], got {tuple(base.shape)} and {tuple(tiles.shape)}")
     if align not in ALIGNMENTS:
         raise ValueError(f"align is one of {ALIGNMENTS}, got {align!r}")
-    assert base.is_cuda and tiles.is_cuda and base.device == tiles.device
-    base, tiles = base.to(torch.float32).contiguous(), tiles.to(torch.float32).contiguous()
+    base, tiles = base.contiguous(), tiles.contiguous()
     ys_c, xs_c = (np.ascontiguousarray(np.asarray(v.cpu() if torch.is_tensor(v) else v)) for v in (ys, xs))
     if any(v.ndim != 1 or v.dtype.kind not in "iu" or v.size < 1 for v in (ys_c, xs_c)):
         raise ValueError("ys and xs are one-dimensional integer arrays")
@@ -1376,15 +1399,13 @@ def tile_merge(base: torch.Tensor, tiles: torch.Tensor, ys, xs, overlap: int, al
     ny, nx = int(ys_c.size), int(xs_c.size)
     if n != ny * nx:
         raise ValueError(f"{ny} x {nx} origins do not number the {n} tiles")
+    assert base.is_cuda and tiles.is_cuda and base.device == tiles.device
     out = torch.empty((b, c, h, w), dtype=torch.float32, device=base.device)
     fit = torch.empty((b, n, 2), dtype=torch.float64, device=base.device) if want_fit else None
-    ws, nbytes = _workspace(lib.gp_tile_merge_workspace(b, c, h, w, ny, nx, wh, ww), base.device)
-    st = lib.gp_tile_merge(base.data_ptr(), tiles.data_ptr(), b, c, h, w, ys_c.ctypes.data, ny, xs_c.ctypes.data, nx, wh, ww, int(overlap),
-                           ALIGNMENTS.index(align), _ptr(fit), out.data_ptr(), ws.data_ptr(), nbytes, _stream_ptr(base.device))
-    if st == GP_ERR_INVALID:
-        raise ValueError(f"gp_tile_merge: invalid arguments (base {(b, c, h, w)}, {ny} x {nx} tiles of {wh} x {ww}, overlap = {overlap}, ys = "
-                         f"{ys_c.tolist()}, xs = {xs_c.tolist()}: not the grid of the rule, or outside its ranges)")
-    _c_check(st, "gp_tile_merge")
+    ws, nbytes = _op_workspace("gp_tile_merge", base.device, b, c, h, w, ny, nx, wh, ww)
+    _launch("gp_tile_merge", f"base {(b, c, h, w)}, {ny} x {nx} tiles of {wh} x {ww}, overlap = {overlap}, ys = {ys_c.tolist()}, xs = {xs_c.tolist()}: "
+            "not the grid of the rule, or outside its ranges", base.data_ptr(), tiles.data_ptr(), b, c, h, w, ys_c.ctypes.data, ny, xs_c.ctypes.data, nx,
+            wh, ww, int(overlap), ALIGNMENTS.index(align), _ptr(fit), out.data_ptr(), ws.data_ptr(), nbytes, _stream_ptr(base.device))
     return (out, fit) if want_fit else out
 
 
@@ -1400,43 +1421,31 @@ def depth_geometry(pred: torch.Tensor, cameras=None, image: Optional[torch.Tenso
     (image k owns the points offsets[k] .. offsets[k + 1]): the point arrays are sliced by one read of it, the only synchronisation.
     Definition in include/genpercept_hip.h; genpercept_amd/geometry.py gives the same bits.  Allocates the workspace and, for the point
     arrays, the worst case B * ceil(H / stride) * ceil(W / stride)."""
-    from .geometry import SPACES, check_cameras, check_options
-    lib = load_library()
-    if not torch.is_tensor(pred) or not pred.dtype.is_floating_point:
-        raise ValueError(f"pred: a float tensor, got {pred.dtype if torch.is_tensor(pred) else type(pred)}")
-    pred = _eval_maps(pred, "pred").to(torch.float32).contiguous()
-    assert pred.is_cuda
+    from .geometry import check_cameras, check_options
+    pred = _float_maps(pred, "pred")
     b, h, w = (int(v) for v in pred.shape)
+    dev = pred.device
+    if image is not None:
+        image = _same_batch(_images_u8(image, "image"), (b, h, w), dev, "image")
     if space not in SPACES:
         raise ValueError(f"space is one of {SPACES}, got {space!r}")
     radius, tau, min_count, min_cos, stride = check_options(radius, tau, min_count, min_cos, stride)
-    if not (1 <= h <= 16384 and 1 <= w <= 16384 and 1 <= b <= 65535 and b * h * w < 2 ** 31):
-        raise ValueError(f"depth geometry takes 1 .. 65535 maps with sides in 1 .. 16384 and B * H * W < 2^31, got {(b, h, w)}")
+    _post_dims(b, h, w, "depth geometry")
     cams = check_cameras(cameras.cpu().numpy() if torch.is_tensor(cameras) else cameras, b, h, w)
-    if image is not None:
-        if not torch.is_tensor(image) or image.dtype != torch.uint8 or image.dim() not in (3, 4):
-            raise ValueError(f"image: uint8 [B, 3, H, W] or [3, H, W], got {image.dtype if torch.is_tensor(image) else type(image)}")
-        image = (image[None] if image.dim() == 3 else image).contiguous()
-        if tuple(image.shape) != (b, 3, h, w) or image.device != pred.device:
-            raise ValueError(f"image: uint8 {(b, 3, h, w)} on the maps' device, got {tuple(image.shape)}")
+    assert pred.is_cuda
     if mask is not None:
         mask = _mask_u8(mask, "mask", (b, h, w))
-    dev = pred.device
     out = dict(xyz=torch.empty((b, 3, h, w), dtype=torch.float32, device=dev), normal=torch.empty((b, 3, h, w), dtype=torch.float32, device=dev),
                keep=torch.empty((b, h, w), dtype=torch.uint8, device=dev))
     cap = b * (-(-h // stride)) * (-(-w // stride))
     pts = dict(points=torch.empty((cap, 3), dtype=torch.float32, device=dev), point_normals=torch.empty((cap, 3), dtype=torch.float32, device=dev),
                point_rgb=torch.empty((cap, 3), dtype=torch.uint8, device=dev), point_index=torch.empty((cap,), dtype=torch.int32, device=dev),
                offsets=torch.empty((b + 1,), dtype=torch.int64, device=dev))
-    ws, nbytes = _workspace(lib.gp_depth_geometry_workspace(b, h, w, stride), dev)
-    st = lib.gp_depth_geometry(pred.data_ptr(), _ptr(mask), _ptr(image), cams.ctypes.data, b, h, w, SPACES.index(space), radius, tau, min_count, min_cos,
-                               stride, out["xyz"].data_ptr(), out["normal"].data_ptr(), out["keep"].data_ptr(),
-                               *[pts[k].data_ptr() for k in ("points", "point_normals", "point_rgb", "point_index", "offsets")], ws.data_ptr(), nbytes,
-                               _stream_ptr(dev))
-    if st == GP_ERR_INVALID:
-        raise ValueError(f"gp_depth_geometry: invalid arguments (maps {(b, h, w)}, radius = {radius}, tau = {tau}, min_count = {min_count}, "
-                         f"min_cos = {min_cos}, stride = {stride})")
-    _c_check(st, "gp_depth_geometry")
+    ws, nbytes = _op_workspace("gp_depth_geometry", dev, b, h, w, stride)
+    _launch("gp_depth_geometry", f"maps {(b, h, w)}, radius = {radius}, tau = {tau}, min_count = {min_count}, min_cos = {min_cos}, stride = {stride}",
+            pred.data_ptr(), _ptr(mask), _ptr(image), cams.ctypes.data, b, h, w, SPACES.index(space), radius, tau, min_count, min_cos, stride,
+            out["xyz"].data_ptr(), out["normal"].data_ptr(), out["keep"].data_ptr(),
+            *[pts[k].data_ptr() for k in ("points", "point_normals", "point_rgb", "point_index", "offsets")], ws.data_ptr(), nbytes, _stream_ptr(dev))
     offsets = pts["offsets"].cpu().numpy()   # (synchronises: `cams`, host memory the call reads in stream order, has been read by now)
     n = int(offsets[-1])
     out.update({k: pts[k][:n] for k in ("points", "point_normals", "point_rgb", "point_index")}, offsets=offsets)
@@ -1468,25 +1477,16 @@ def lens_blur(image: torch.Tensor, pred: torch.Tensor, focus=None, focus_at=None
     pair (to_lin uint16 [256], from_lin uint8 [4096]).  Returns uint8 [B, 3, H, W] on the device, and with want_coc (out, coc) with coc the
     circle of confusion in eighths of a pixel, int16 [B, H, W] (0 .. 256).  Definition in include/genpercept_hip.h;
     genpercept_amd/lens_blur.py gives the same bits.  Enqueued on the current stream, no synchronisation, nothing read back."""
-    from .lens_blur import SPACES, lens_blur_options
-    lib = load_library()
-    if not torch.is_tensor(image) or image.dtype != torch.uint8 or image.dim() not in (3, 4) or image.shape[-3] != 3:
-        raise ValueError(f"image: uint8 [B, 3, H, W] or [3, H, W], got {image.dtype if torch.is_tensor(image) else type(image)} "
-                         f"{tuple(image.shape) if torch.is_tensor(image) else ''}")
-    if not torch.is_tensor(pred) or not pred.dtype.is_floating_point:
-        raise ValueError(f"pred: a float tensor, got {pred.dtype if torch.is_tensor(pred) else type(pred)}")
-    image = (image[None] if image.dim() == 3 else image).contiguous()
-    pred = _eval_maps(pred, "pred").to(torch.float32).contiguous()
-    assert image.is_cuda and pred.is_cuda
+    from .lens_blur import lens_blur_options
+    image, pred = _images_u8(image, "image"), _float_maps(pred, "pred")
     b, h, w = (int(v) for v in pred.shape)
     dev = pred.device
-    if tuple(image.shape) != (b, 3, h, w) or image.device != dev:
-        raise ValueError(f"image {tuple(image.shape)} and pred {tuple(pred.shape)}: one map per image, same size, same device")
+    _same_batch(image, (b, h, w), dev, "image")
     if space not in SPACES:
         raise ValueError(f"space is one of {SPACES}, got {space!r}")
-    if not (1 <= h <= 16384 and 1 <= w <= 16384 and 1 <= b <= 65535 and b * h * w < 2 ** 31):
-        raise ValueError(f"lens blur takes 1 .. 65535 images with sides in 1 .. 16384 and B * H * W < 2^31, got {(b, h, w)}")
+    _post_dims(b, h, w, "lens blur")
     o = lens_blur_options(b, focus, focus_at, aperture, max_radius, dof)
+    assert pred.is_cuda
     if sharp is not None:
         sharp = _mask_u8(sharp, "sharp", (b, h, w))
     to_lin, from_lin = _lens_tables(tables, dev)
@@ -1506,11 +1506,8 @@ def lens_blur(image: torch.Tensor, pred: torch.Tensor, focus=None, focus_at=None
     out = torch.empty((b, 3, h, w), dtype=torch.uint8, device=dev)
     coc = torch.empty((b, h, w), dtype=torch.int16, device=dev) if want_coc else None
     max_c8 = int(o["cmax8"].max())
-    st = lib.gp_lens_blur(image.data_ptr(), pred.data_ptr(), _ptr(sharp), params.data_ptr(), to_lin.data_ptr(), from_lin.data_ptr(), b, h, w,
-                          SPACES.index(space), max_c8, out.data_ptr(), _ptr(coc), _stream_ptr(dev))
-    if st == GP_ERR_INVALID:
-        raise ValueError(f"gp_lens_blur: invalid arguments (images {(b, h, w)}, space = {space}, max_c8 = {max_c8})")
-    _c_check(st, "gp_lens_blur")
+    _launch("gp_lens_blur", f"images {(b, h, w)}, space = {space}, max_c8 = {max_c8}", image.data_ptr(), pred.data_ptr(), _ptr(sharp), params.data_ptr(),
+            to_lin.data_ptr(), from_lin.data_ptr(), b, h, w, SPACES.index(space), max_c8, out.data_ptr(), _ptr(coc), _stream_ptr(dev))
     return (out, coc) if want_coc else out
 
 

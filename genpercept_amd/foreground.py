@@ -29,8 +29,8 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from .eval_metrics import quantize_mask
+from .post_common import MAX_DIM
 
-MAX_DIM = 16384
 SMALL = 32
 DEFAULTS = dict(reg=1e-5, gw=1.0, n_small=10, n_big=2)
 f32 = np.float32

@@ -40,37 +40,31 @@ from typing import Dict, Optional, Tuple
 
 import numpy as np
 
-from .guided import quantize16
+from .post_common import MAX_DIM, SPACES, is_int, options_from, quantize16  # noqa: F401
 
-MAX_DIM = 16384
 MAX_R = 8
 MAX_STRIDE = 64
-SPACES = ("depth", "disparity")
 DEFAULTS = dict(radius=2, tau=0.05, min_count=None, min_cos=None, stride=1)
 DEFAULT_MIN_COS = math.cos(math.radians(85.0))
 CAMERA_FIELDS = ("s", "t", "fx", "fy", "cx", "cy", "z_min", "z_max")
 f32, f64 = np.float32, np.float64
 
 
-def _is_int(v) -> bool:
-    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
-
-
 def check_options(radius=2, tau=0.05, min_count=None, min_cos=None, stride=1) -> Tuple[int, float, int, float, int]:
     """The ranges of the definition (ValueError outside them), with the defaults filled in: (radius, tau, min_count, min_cos, stride)."""
-    if not _is_int(radius) or not 1 <= radius <= MAX_R:
+    if not is_int(radius) or not 1 <= radius <= MAX_R:
         raise ValueError(f"radius is an integer in 1 .. {MAX_R}, got {radius!r}")
     tau = float(tau)
     if not (0.0 < tau <= 1.0):
         raise ValueError(f"tau is in (0, 1], got {tau}")
     if min_count is None:
         min_count = 2 * radius + 1
-    if not _is_int(min_count) or not 3 <= min_count <= (2 * radius + 1) ** 2:
+    if not is_int(min_count) or not 3 <= min_count <= (2 * radius + 1) ** 2:
         raise ValueError(f"min_count is an integer in 3 .. (2 r + 1)^2 = {(2 * radius + 1) ** 2}, got {min_count!r}")
     min_cos = DEFAULT_MIN_COS if min_cos is None else float(min_cos)
     if not (0.0 <= min_cos < 1.0):
         raise ValueError(f"min_cos is in [0, 1), got {min_cos}")
-    if not _is_int(stride) or not 1 <= stride <= MAX_STRIDE:
+    if not is_int(stride) or not 1 <= stride <= MAX_STRIDE:
         raise ValueError(f"stride is an integer in 1 .. {MAX_STRIDE}, got {stride!r}")
     return int(radius), tau, int(min_count), min_cos, int(stride)
 
@@ -78,18 +72,13 @@ def check_options(radius=2, tau=0.05, min_count=None, min_cos=None, stride=1) ->
 def pointcloud_options(pointcloud) -> Dict:
     """The `pointcloud` argument of the pipeline entries -- True or a dict with the keys radius, tau, min_count, min_cos, stride -- as the
     checked options of `depth_geometry`."""
-    opts = dict(DEFAULTS)
-    if pointcloud is not True:
-        if not isinstance(pointcloud, dict) or any(k not in DEFAULTS for k in pointcloud):
-            raise ValueError(f"pointcloud is True or a dict with the keys {sorted(DEFAULTS)}, got {pointcloud!r}")
-        opts.update(pointcloud)
-    return dict(zip(("radius", "tau", "min_count", "min_cos", "stride"), check_options(**opts)))
+    return options_from(pointcloud, DEFAULTS, "pointcloud", lambda o: dict(zip(DEFAULTS, check_options(**o))))
 
 
 def intrinsics_from_fov(H: int, W: int, fov_deg: float = 55.0) -> Tuple[float, float, float, float]:
     """(fx, fy, cx, cy) of a pinhole camera with the horizontal field of view fov_deg and its principal point at the image centre:
     fx = fy = (W / 2) / tan(fov / 2), cx = (W - 1) / 2, cy = (H - 1) / 2."""
-    if not (_is_int(H) and _is_int(W)) or H < 1 or W < 1 or not 0.0 < float(fov_deg) < 180.0:
+    if not (is_int(H) and is_int(W)) or H < 1 or W < 1 or not 0.0 < float(fov_deg) < 180.0:
         raise ValueError(f"sizes are positive integers and the field of view is in (0, 180) degrees, got {H!r}, {W!r}, {fov_deg!r}")
     f = (W / 2.0) / math.tan(math.radians(float(fov_deg)) / 2.0)
     return f, f, (W - 1) / 2.0, (H - 1) / 2.0

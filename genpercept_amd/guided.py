@@ -29,7 +29,8 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-MAX_DIM = 16384
+from .post_common import MAX_DIM, options_from, quantize16  # noqa: F401  (quantize16: re-exported, the rule was first stated here)
+
 MAX_R = 32
 DEFAULTS = dict(radius=4, eps=1e-4)
 f32, f64 = np.float32, np.float64
@@ -48,20 +49,7 @@ def check_options(radius, eps) -> Tuple[int, float]:
 
 def refine_options(refine) -> Dict:
     """The `refine` argument of the pipeline entries -- True or dict(radius=..., eps=...) -- as the checked options of `guided_upsample`."""
-    opts = dict(DEFAULTS)
-    if refine is not True:
-        if not isinstance(refine, dict) or any(k not in DEFAULTS for k in refine):
-            raise ValueError(f"refine is None, True or a dict with the keys {sorted(DEFAULTS)}, got {refine!r}")
-        opts.update(refine)
-    opts["radius"], opts["eps"] = check_options(opts["radius"], opts["eps"])
-    return opts
-
-
-def quantize16(pred) -> np.ndarray:
-    """(uint16)(clamp(pred, 0, 1) * 65535.0f): a float32 product, truncated, NaN -> 0"""
-    x = np.asarray(pred, dtype=f32)
-    c = np.where(x > f32(0.0), np.where(x < f32(1.0), x, f32(1.0)), f32(0.0)).astype(f32)
-    return (c * f32(65535.0)).astype(np.int64).astype(np.uint16)
+    return options_from(refine, DEFAULTS, "refine", lambda o: dict(zip(("radius", "eps"), check_options(**o))))
 
 
 def _window(n: int, r: int) -> Tuple[np.ndarray, np.ndarray]:

@@ -30,15 +30,13 @@ from typing import Dict, Optional, Tuple
 
 import numpy as np
 
-from .guided import quantize16
+from .post_common import MAX_DIM, SPACES, quantize16  # noqa: F401
 
-MAX_DIM = 16384
 MAX_C8 = 256
 MAX_RADIUS = 32.0
 MAX_GAIN = 32768
 ONE = 1 << 20
 LIN_MAX = 4095
-SPACES = ("depth", "disparity")
 PARAM_FIELDS = ("F", "gain", "cmax8", "dz")
 PARAM_MAX = (65535, MAX_GAIN, MAX_C8, 65535)
 DEFAULTS = dict(focus=None, focus_at=None, aperture=8.0, max_radius=16.0, dof=0.0)

@@ -33,6 +33,21 @@ from .batchsize import find_batch_size
 from .weights import merge_lora_state_dict
 
 
+def _pil_to_chw(im: Image.Image) -> torch.Tensor:
+    """A PIL image as a uint8 [3, H, W] tensor of its RGB bytes."""
+    return torch.from_numpy(np.asarray(im.convert("RGB")).copy()).permute(2, 0, 1)
+
+
+def _chw_to_pil(t: torch.Tensor) -> Image.Image:
+    """A uint8 [3, H, W] tensor (on any device) as a PIL RGB image."""
+    return Image.fromarray(np.ascontiguousarray(t.permute(1, 2, 0).cpu().numpy()))
+
+
+def _batch_of(images) -> torch.Tensor:
+    """The images of a batch entry as one tensor: a tensor as it is, PIL images of one size stacked to uint8 [B, 3, H, W]."""
+    return images if torch.is_tensor(images) else torch.stack([_pil_to_chw(im) for im in images])
+
+
 @dataclass
 class GenPerceptOutput:
     """genpercept_pipeline.py:50-62.  pred_np: [H,W] (1-channel modes) or [H,W,3], values in [0,1]; pred_colored: PIL image."""
@@ -474,8 +489,7 @@ class GenPerceptPipeline:
         self.mode = mode
         if processing_res is None:
             processing_res = self.default_processing_resolution
-        if not torch.is_tensor(images):
-            images = torch.stack([torch.from_numpy(np.asarray(im.convert("RGB")).copy()).permute(2, 0, 1) for im in images])
+        images = _batch_of(images)
         assert images.dim() == 4 and images.shape[1] == 3
         steps = self.default_denoising_steps if denoising_steps is None else int(denoising_steps)
         if self.genpercept_pipeline:
@@ -501,11 +515,16 @@ class GenPerceptPipeline:
         if refine is None:
             return None
         from .guided import refine_options
-        opts = refine_options(refine)
+        return GenPerceptPipeline._at_input_size(refine_options(refine), "refine", "the image is the guide of the filter",
+                                                 "upsamples the map to the input size", dtype, match_input_res)
+
+    @staticmethod
+    def _at_input_size(opts: dict, name: str, why_u8: str, why_size: str, dtype, match_input_res) -> dict:
+        """What `refine` and `tiles` share: the checked options pass when the images are 8-bit and the map comes back at the input size."""
         if dtype != torch.uint8:
-            raise ValueError(f"refine takes 8-bit images (the image is the guide of the filter), got {dtype}")
+            raise ValueError(f"{name} takes 8-bit images ({why_u8}), got {dtype}")
         if not match_input_res:
-            raise ValueError("refine upsamples the map to the input size: it needs match_input_res=True")
+            raise ValueError(f"{name} {why_size}: it needs match_input_res=True")
         return opts
 
     def _tiles_options(self, tiles, dtype, match_input_res, processing_res) -> Optional[dict]:
@@ -515,12 +534,8 @@ class GenPerceptPipeline:
         if tiles is None:
             return None
         from .tiled import tiles_options
-        opts = tiles_options(tiles, int(processing_res), self.mode or "depth")
-        if dtype != torch.uint8:
-            raise ValueError(f"tiles takes 8-bit images (the windows are cut from the image as it came), got {dtype}")
-        if not match_input_res:
-            raise ValueError("tiles merges the windows at the input size: it needs match_input_res=True")
-        return opts
+        return self._at_input_size(tiles_options(tiles, int(processing_res), self.mode or "depth"), "tiles",
+                                   "the windows are cut from the image as it came", "merges the windows at the input size", dtype, match_input_res)
 
     @staticmethod
     def _tile_predictions(full, tiles: dict, predict):
@@ -595,8 +610,7 @@ class GenPerceptPipeline:
         self.mode = mode
         if processing_res is None:
             processing_res = self.default_processing_resolution
-        if not torch.is_tensor(images):
-            images = torch.stack([torch.from_numpy(np.asarray(im.convert("RGB")).copy()).permute(2, 0, 1) for im in images])
+        images = _batch_of(images)
         assert images.dim() == 4 and images.shape[1] == 3
         resample = get_resample_method(resample_method)
         if images.dtype not in (torch.uint8, torch.float32) or resample not in RESAMPLE_CODE:
@@ -607,6 +621,22 @@ class GenPerceptPipeline:
             assert steps == 1 and ensemble_size == 1
         opts = dict(steps=steps, ensemble_size=int(ensemble_size), batch_size=max(1, int(ensemble_size)), generator=generator, ensemble_kwargs=None)
         return self._predict_device(images, processing_res, match_input_res, resample, fix_timesteps, prompt, opts, refine=refine, tiles=tiles)[0]
+
+    def _post_inputs(self, images, mode: str, modes, what: str, needs: str, inference_options: dict, preflight=None):
+        """The shared opening of the post-processing entries: `what` (a cutout, a point cloud, a refocus) is made from 8-bit images of one
+        size under the map of one of `modes` at the input size.  preflight(images), if given, checks the op's own arguments on the stacked
+        images before the model runs.  Returns (the uint8 [B,3,H,W] images on the map's device, the map of `predict_batch_device`)."""
+        if mode not in modes:
+            raise ValueError(f"{what} needs {needs}: mode {modes[0]!r} or {modes[1]!r}, got {mode!r}")
+        if inference_options.get("match_input_res", True) is not True:
+            raise ValueError(f"{what} is made at the input size: match_input_res stays True")
+        images = _batch_of(images)
+        if images.dtype != torch.uint8:
+            raise ValueError(f"{what} takes 8-bit images, got {images.dtype}")
+        if preflight is not None:
+            preflight(images)
+        pred = self.predict_batch_device(images, mode, **inference_options)
+        return images.to(pred.device, non_blocking=True), pred
 
     @torch.no_grad()
     def cutout_batch_device(self, images: Union[Sequence[Image.Image], torch.Tensor], mode: str = "matting", background=None,
@@ -619,16 +649,7 @@ class GenPerceptPipeline:
         inference_options may hold `refine` (True or dict(radius=..., eps=...)): the alpha then comes to the input size by the guided filter, and
         the colours are estimated under that sharper alpha; and `tiles` (as `predict_batch_device`): the alpha is that of tiled inference."""
         from . import engine as ge
-        if mode not in ("matting", "dis"):
-            raise ValueError(f"cutouts need an alpha map: mode 'matting' or 'dis', got {mode!r}")
-        if inference_options.get("match_input_res", True) is not True:
-            raise ValueError("cutouts are made at the input size: match_input_res stays True")
-        if not torch.is_tensor(images):
-            images = torch.stack([torch.from_numpy(np.asarray(im.convert("RGB")).copy()).permute(2, 0, 1) for im in images])
-        if images.dtype != torch.uint8:
-            raise ValueError(f"cutouts take 8-bit images, got {images.dtype}")
-        alpha = self.predict_batch_device(images, mode, **inference_options)
-        rgb = images.to(alpha.device, non_blocking=True)
+        rgb, alpha = self._post_inputs(images, mode, ("matting", "dis"), "a cutout", "an alpha map", inference_options)
         if torch.is_tensor(background):
             background = background.to(alpha.device, non_blocking=True)
         return ge.cutout(rgb, alpha, background, **(foreground_options or {})), alpha
@@ -640,11 +661,9 @@ class GenPerceptPipeline:
         if isinstance(background, Image.Image):
             if background.size != image.size:
                 raise ValueError(f"the background {background.size} must have the image's size {image.size}")
-            background = torch.from_numpy(np.asarray(background.convert("RGB")).copy()).permute(2, 0, 1).contiguous()
+            background = _pil_to_chw(background)
         out, _ = self.cutout_batch_device([image], mode, background, foreground_options, **inference_options)
-        if background is None:
-            return Image.fromarray(out[0].cpu().numpy())
-        return Image.fromarray(np.ascontiguousarray(out[0].permute(1, 2, 0).cpu().numpy()))
+        return Image.fromarray(out[0].cpu().numpy()) if background is None else _chw_to_pil(out[0])
 
     @torch.no_grad()
     def pointcloud_batch_device(self, images: Union[Sequence[Image.Image], torch.Tensor], mode: str = "depth", cameras=None, pointcloud=True,
@@ -660,17 +679,9 @@ class GenPerceptPipeline:
         min_count=..., min_cos=..., stride=...).  inference_options may hold `refine` and `tiles` as in `cutout_batch_device`."""
         from . import engine as ge
         from .geometry import pointcloud_options
-        if mode not in ("depth", "disparity"):
-            raise ValueError(f"point clouds need a depth map: mode 'depth' or 'disparity', got {mode!r}")
-        if inference_options.get("match_input_res", True) is not True:
-            raise ValueError("point clouds are made at the input size: match_input_res stays True")
-        opts = pointcloud_options(pointcloud)
-        if not torch.is_tensor(images):
-            images = torch.stack([torch.from_numpy(np.asarray(im.convert("RGB")).copy()).permute(2, 0, 1) for im in images])
-        if images.dtype != torch.uint8:
-            raise ValueError(f"point clouds take 8-bit images, got {images.dtype}")
-        pred = self.predict_batch_device(images, mode, **inference_options)
-        out = ge.depth_geometry(pred, cameras, image=images.to(pred.device, non_blocking=True), space=mode, **opts)
+        opts = pointcloud_options(pointcloud)   # (refused before the model runs)
+        rgb, pred = self._post_inputs(images, mode, ("depth", "disparity"), "a point cloud", "a depth map", inference_options)
+        out = ge.depth_geometry(pred, cameras, image=rgb, space=mode, **opts)
         out["pred"] = pred
         return out
 
@@ -694,26 +705,16 @@ class GenPerceptPipeline:
         `refine` gives the photograph's own edge."""
         from . import engine as ge
         from .lens_blur import lens_blur_options
-        if mode not in ("depth", "disparity"):
-            raise ValueError(f"a refocus needs a depth map: mode 'depth' or 'disparity', got {mode!r}")
-        if inference_options.get("match_input_res", True) is not True:
-            raise ValueError("a refocus is made at the input size: match_input_res stays True")
-        if not torch.is_tensor(images):
-            images = torch.stack([torch.from_numpy(np.asarray(im.convert("RGB")).copy()).permute(2, 0, 1) for im in images])
-        if images.dtype != torch.uint8:
-            raise ValueError(f"a refocus takes 8-bit images, got {images.dtype}")
-        lens_blur_options(int(images.shape[0]), focus, focus_at, aperture, max_radius, dof)   # (refused before the model runs)
-        pred = self.predict_batch_device(images, mode, **inference_options)
+        rgb, pred = self._post_inputs(images, mode, ("depth", "disparity"), "a refocus", "a depth map", inference_options,
+                                      lambda images: lens_blur_options(int(images.shape[0]), focus, focus_at, aperture, max_radius, dof))
         if torch.is_tensor(sharp):
             sharp = sharp.to(pred.device, non_blocking=True)
-        return ge.lens_blur(images.to(pred.device, non_blocking=True), pred, focus, focus_at, aperture, max_radius, dof, space=mode, sharp=sharp,
-                            tables=tables)
+        return ge.lens_blur(rgb, pred, focus, focus_at, aperture, max_radius, dof, space=mode, sharp=sharp, tables=tables)
 
     def refocus(self, image: Image.Image, mode: str = "depth", focus=None, focus_at=None, aperture=8.0, max_radius=16.0, dof=0.0, sharp=None,
                 tables=None, **inference_options) -> Image.Image:
         """`refocus_batch_device` for one PIL image: the refocused photograph as a PIL image."""
-        out = self.refocus_batch_device([image], mode, focus, focus_at, aperture, max_radius, dof, sharp, tables, **inference_options)
-        return Image.fromarray(np.ascontiguousarray(out[0].permute(1, 2, 0).cpu().numpy()))
+        return _chw_to_pil(self.refocus_batch_device([image], mode, focus, focus_at, aperture, max_radius, dof, sharp, tables, **inference_options)[0])
 
     def _run_device(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None, refine=None,
                     tiles=None) -> List[GenPerceptOutput]:

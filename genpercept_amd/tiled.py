@@ -31,9 +31,8 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-from .guided import quantize16
+from .post_common import MAX_DIM, is_int, options_from, quantize16
 
-MAX_DIM = 16384
 MAX_TILES = 1024
 ALIGNMENTS = ("least_square", "none")
 AFFINE_INVARIANT_MODES = ("depth", "disparity")
@@ -42,13 +41,9 @@ DEFAULT_BATCH = 4
 f32, f64 = np.float32, np.float64
 
 
-def _is_int(v) -> bool:
-    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
-
-
 def axis_origins(L: int, size: int, overlap: int) -> Tuple[np.ndarray, int]:
     """One axis of the grid: (origins int32 [n], window w)."""
-    if not (_is_int(L) and _is_int(size) and _is_int(overlap)):
+    if not (is_int(L) and is_int(size) and is_int(overlap)):
         raise ValueError(f"lengths, tile sizes and overlaps are integers, got {L!r}, {size!r}, {overlap!r}")
     L, size, o = int(L), int(size), int(overlap)
     if not 1 <= L <= MAX_DIM or size < 1:
@@ -74,26 +69,22 @@ def tiles_options(tiles, processing_res=None, mode: str = "depth") -> Dict:
     """The `tiles` argument of the pipeline entries -- True or a dict with the keys size, overlap, align, batch -- as checked options.  The
     defaults: size = the processing resolution, overlap = size // 4, align = "least_square" for depth and disparity and "none" otherwise,
     batch = 4 tiles per model pass."""
-    opts = dict(size=None, overlap=None, align=None, batch=DEFAULT_BATCH)
-    if tiles is not True:
-        if not isinstance(tiles, dict) or any(k not in OPTION_KEYS for k in tiles):
-            raise ValueError(f"tiles is None, True or a dict with the keys {sorted(OPTION_KEYS)}, got {tiles!r}")
-        opts.update(tiles)
+    opts = options_from(tiles, dict(size=None, overlap=None, align=None, batch=DEFAULT_BATCH), "tiles")
     if opts["size"] is None:
         if not processing_res:
             raise ValueError("tiles: without a processing resolution (processing_res = 0) the tile size has to be given")
         opts["size"] = processing_res
-    if not _is_int(opts["size"]) or not 2 <= opts["size"] <= MAX_DIM:
+    if not is_int(opts["size"]) or not 2 <= opts["size"] <= MAX_DIM:
         raise ValueError(f"tiles: size is an integer in 2 .. {MAX_DIM}, got {opts['size']!r}")
     if opts["overlap"] is None:
         opts["overlap"] = opts["size"] // 4
-    if not _is_int(opts["overlap"]) or not 1 <= opts["overlap"] <= opts["size"] // 2:
+    if not is_int(opts["overlap"]) or not 1 <= opts["overlap"] <= opts["size"] // 2:
         raise ValueError(f"tiles: overlap is an integer in 1 .. size / 2 = {opts['size'] // 2}, got {opts['overlap']!r}")
     if opts["align"] is None:
         opts["align"] = "least_square" if mode in AFFINE_INVARIANT_MODES else "none"
     if opts["align"] not in ALIGNMENTS:
         raise ValueError(f"tiles: align is one of {ALIGNMENTS}, got {opts['align']!r}")
-    if not _is_int(opts["batch"]) or opts["batch"] < 1:
+    if not is_int(opts["batch"]) or opts["batch"] < 1:
         raise ValueError(f"tiles: batch is a positive integer, got {opts['batch']!r}")
     return {k: (opts[k] if k == "align" else int(opts[k])) for k in OPTION_KEYS}
 

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../genpercept_amd/csrc/foreground_update.h"
+#include "check_io.h"
 
 int main(int argc, char** argv) {
     if (argc != 3) return 2;
@@ -14,12 +15,12 @@ int main(int argc, char** argv) {
     if (!f) return 3;
     int hd[4];
     float rg[2];
-    if (std::fread(hd, 4, 4, f) != 4 || std::fread(rg, 4, 2, f) != 2) return 4;
+    if (!get(hd, 4, 4, f) || !get(rg, 4, 2, f)) return 4;
     const int H = hd[0], W = hd[1], n_small = hd[2], n_big = hd[3];
     if (H < 1 || W < 1 || H > FG_MAX_DIM || W > FG_MAX_DIM) return 5;
     const size_t HW = (size_t)H * W;
     std::vector<unsigned char> img(3 * HW), alpha(HW);
-    if (std::fread(img.data(), 1, 3 * HW, f) != 3 * HW || std::fread(alpha.data(), 1, HW, f) != HW) return 6;
+    if (!get(img.data(), 1, 3 * HW, f) || !get(alpha.data(), 1, HW, f)) return 6;
     std::fclose(f);
 
     const int L = fg_num_levels(H, W);
@@ -66,7 +67,7 @@ int main(int argc, char** argv) {
     }
     f = std::fopen(argv[2], "wb");
     if (!f) return 8;
-    if (std::fwrite(prev.data(), 4, 6 * HW, f) != 6 * HW) return 9;
+    if (!put(prev.data(), 4, 6 * HW, f)) return 9;
     std::fclose(f);
     // the byte rules, for the test to compare with foreground.to_bytes
     std::printf("%d %d %d %d\n", (int)fg_byte(0.0f), (int)fg_byte(0.5f), (int)fg_byte(1.0f), (int)fg_byte(fg_composite(0.25f, 1.0f, 0.2f)));

@@ -11,9 +11,7 @@
 #include <vector>
 
 #include "../genpercept_amd/csrc/depth_geometry_math.h"
-
-static bool get(void* p, size_t size, size_t n, FILE* f) { return n == 0 || std::fread(p, size, n, f) == n; }
-static bool put(const void* p, size_t size, size_t n, FILE* f) { return n == 0 || std::fwrite(p, size, n, f) == n; }
+#include "check_io.h"
 
 int main(int argc, char** argv) {
     if (argc != 3) return 2;
@@ -21,7 +19,7 @@ int main(int argc, char** argv) {
     if (!f) return 3;
     int hd[8];
     double opt[2 + DG_CAMERA];
-    if (std::fread(hd, 4, 8, f) != 8 || std::fread(opt, 8, 2 + DG_CAMERA, f) != 2 + DG_CAMERA) return 4;
+    if (!get(hd, 4, 8, f) || !get(opt, 8, 2 + DG_CAMERA, f)) return 4;
     const int H = hd[0], W = hd[1], space = hd[2], r = hd[3], min_count = hd[4], stride = hd[5], has_mask = hd[6], has_image = hd[7];
     const double tau = opt[0], min_cos = opt[1];
     if (H < 1 || W < 1 || H > DG_MAX_DIM || W > DG_MAX_DIM || !dg_options_ok(space, r, tau, min_count, min_cos, stride) || !dg_camera_ok(opt + 2)) return 5;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../genpercept_amd/csrc/guided_solve.h"
+#include "check_io.h"
 
 typedef unsigned long long u64;
 
@@ -18,16 +19,15 @@ int main(int argc, char** argv) {
     if (!f) return 3;
     int hd[6];
     double eps;
-    if (std::fread(hd, 4, 6, f) != 6 || std::fread(&eps, 8, 1, f) != 1) return 4;
+    if (!get(hd, 4, 6, f) || !get(&eps, 8, 1, f)) return 4;
     const int h = hd[0], w = hd[1], H = hd[2], W = hd[3], r = hd[4], C = hd[5];
     if (h < 1 || w < 1 || H < 1 || W < 1 || h > GS_MAX_DIM || w > GS_MAX_DIM || H > GS_MAX_DIM || W > GS_MAX_DIM) return 5;
     if (r < 1 || r > GS_MAX_R || (C != 1 && C != 3) || !(eps > 0.0 && eps <= 1.0)) return 5;
     const size_t hw = (size_t)h * w, HW = (size_t)H * W;
     std::vector<u64> N(hw), sI(3 * hw), sII(6 * hw), sp(C * hw), sIp(3 * C * hw);
     std::vector<unsigned char> guide(3 * HW);
-    if (std::fread(N.data(), 8, hw, f) != hw || std::fread(sI.data(), 8, 3 * hw, f) != 3 * hw || std::fread(sII.data(), 8, 6 * hw, f) != 6 * hw ||
-        std::fread(sp.data(), 8, C * hw, f) != C * hw || std::fread(sIp.data(), 8, 3 * C * hw, f) != 3 * C * hw ||
-        std::fread(guide.data(), 1, 3 * HW, f) != 3 * HW)
+    if (!get(N.data(), 8, hw, f) || !get(sI.data(), 8, 3 * hw, f) || !get(sII.data(), 8, 6 * hw, f) || !get(sp.data(), 8, C * hw, f) ||
+        !get(sIp.data(), 8, 3 * C * hw, f) || !get(guide.data(), 1, 3 * HW, f))
         return 6;
     std::fclose(f);
 
@@ -81,7 +81,7 @@ int main(int argc, char** argv) {
     }
     f = std::fopen(argv[2], "wb");
     if (!f) return 9;
-    if (std::fwrite(ab.data(), 8, ab.size(), f) != ab.size() || std::fwrite(q.data(), 4, q.size(), f) != q.size()) return 10;
+    if (!put(ab.data(), 8, ab.size(), f) || !put(q.data(), 4, q.size(), f)) return 10;
     std::fclose(f);
     // the 16-bit rule, for the test to compare with guided.quantize16: 0, 1, NaN, -0.25, 1.5, 0.5
     std::printf("%u %u %u %u %u %u\n", gs_quant16(0.0f), gs_quant16(1.0f), gs_quant16(0.0f / 1.0f * __builtin_nanf("")), gs_quant16(-0.25f),

@@ -10,16 +10,14 @@
 #include <vector>
 
 #include "../genpercept_amd/csrc/lens_blur_math.h"
-
-static bool get(void* p, size_t size, size_t n, FILE* f) { return n == 0 || std::fread(p, size, n, f) == n; }
-static bool put(const void* p, size_t size, size_t n, FILE* f) { return n == 0 || std::fwrite(p, size, n, f) == n; }
+#include "check_io.h"
 
 int main(int argc, char** argv) {
     if (argc != 3) return 2;
     FILE* f = std::fopen(argv[1], "rb");
     if (!f) return 3;
     int hd[8];
-    if (std::fread(hd, 4, 8, f) != 8) return 4;
+    if (!get(hd, 4, 8, f)) return 4;
     const int H = hd[0], W = hd[1], space = hd[2], has_sharp = hd[3];
     if (!lb_dims_ok(1, H, W) || !lb_options_ok(space, LB_MAX_C8)) return 5;
     const LbParams prm = lb_params(hd + 4, LB_MAX_C8);

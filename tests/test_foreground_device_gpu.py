@@ -12,7 +12,8 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_foreground_host import GP_ERR_INVALID, call_foreground, invalid_cases, random_inputs, same_bits  # noqa: E402
+from post_support import assert_refused_with_real_buffers, tiny_weights_dict, unaligned  # noqa: E402
+from test_foreground_host import call_foreground, invalid_cases, random_inputs, same_bits  # noqa: E402
 
 gpu = pytest.mark.gpu
 
@@ -21,14 +22,6 @@ OUTPUTS = ["fg", "bg", "rgba", "comp"]
 DEFAULT = dict(reg=1e-5, gw=1.0, n_small=10, n_big=2)
 GRID = [dict(DEFAULT, n_big=nb, n_small=ns) for nb in (1, 2, 4) for ns in (0, 10)] + [dict(reg=2e-3, gw=30.0, n_small=10, n_big=2)]
 FEW = [dict(DEFAULT), dict(reg=2e-3, gw=30.0, n_small=0, n_big=4), dict(DEFAULT, n_big=1), dict(DEFAULT, n_big=4)]
-
-
-def unaligned(x: np.ndarray) -> torch.Tensor:
-    """The array on the device as a contiguous view that starts one byte (one element of a float array) into its buffer."""
-    flat = torch.empty(x.size + 1, dtype=torch.from_numpy(x[:0]).dtype, device="cuda")
-    v = flat[1:].view(x.shape)
-    v.copy_(torch.from_numpy(np.ascontiguousarray(x)))
-    return v
 
 
 def inputs(b, h, w, seed):
@@ -215,9 +208,7 @@ def test_refuses_invalid_arguments_before_touching_the_device():
     lib, t, ok = _device_call_args(2, 40, 40)
     cases = [c for c in invalid_cases(ok, int(lib.gp_foreground_workspace(1, 40, 40))) if "u8" not in c or "alpha" not in c]
     cases.append(dict(u8=0, alpha=t["af"].data_ptr() + 2))
-    for kw in cases:
-        assert call_foreground(lib, dict(ok, **kw)) == GP_ERR_INVALID, kw
-    torch.cuda.synchronize()
+    assert_refused_with_real_buffers(call_foreground, lib, ok, cases)
     assert bool((t["fg"] == -7.0).all() and (t["bg"] == -7.0).all() and (t["rgba"] == 99).all() and (t["comp"] == 99).all() and (t["ws"] == 0x5A).all())
     assert call_foreground(lib, ok) == 0                             # ... and the valid set goes through
     torch.cuda.synchronize()
@@ -226,9 +217,7 @@ def test_refuses_invalid_arguments_before_touching_the_device():
 
 @pytest.fixture(scope="module")
 def tiny_weights():
-    from oracle import sd21 as osd
-    uc, vc = osd.UNetCfg.tiny(), osd.VAECfg.tiny()
-    return dict(uc=uc, vc=vc, usd=osd.synth_state_dict(osd.unet_manifest(uc), 1), vsd=osd.synth_state_dict(osd.vae_manifest(vc), 2))
+    return tiny_weights_dict()
 
 
 @gpu

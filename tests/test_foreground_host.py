@@ -4,24 +4,20 @@ the whole multi-level loop over the kernels' own update text (csrc/foreground_up
 bit-equal to the host route; the quality of the estimate on a synthetic composite with known colours; degenerate alphas; the header, the two
 libraries and the ctypes table carry the new entry; its argument checks (they come before the first HIP call, so they run without a GPU)."""
 import ctypes as C
+import functools
 import os
-import re
-import shutil
-import subprocess
+import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "foreground_check.cpp")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import post_support as ps  # noqa: E402
+from post_support import GP_ERR_INVALID, libs as _libs  # noqa: E402,F401
+
 NAMES = ("gp_foreground_workspace", "gp_foreground")
-GP_ERR_INVALID = 1
 f32 = np.float32
-
-
-def same_bits(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.dtype == b.dtype == np.float32 and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+same_bits = functools.partial(ps.same_bits, dtype=np.float32)
 
 
 def random_inputs(rng, h, w):
@@ -140,23 +136,9 @@ def test_host_route_equals_plain_loops(shape):
 
 
 # ---- the kernels' update text on the CPU ----------------------------------------------------------------------------------------------------------------
-def _clangxx():
-    for cand in ("/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++", shutil.which("amdclang++")):
-        if cand and os.path.exists(cand):
-            return cand
-    return None
-
-
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    cxx = _clangxx()
-    if cxx is None:
-        pytest.skip("the ROCm clang++ is not on this machine: foreground_check.cpp cannot be built")
-    exe = tmp_path_factory.mktemp("fgcheck") / "foreground_check"
-    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
-                        "-Werror", SRC, "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(exe)
+    return ps.build_check(tmp_path_factory, "foreground_check.cpp")
 
 
 @pytest.mark.parametrize("shape", [(7, 5), (33, 32), (37, 70)], ids=lambda s: "x".join(map(str, s)))
@@ -170,13 +152,12 @@ def test_cpu_build_of_the_kernel_update_equals_the_host_route(check_exe, shape, 
         with open(src, "wb") as f:
             f.write(np.array([h, w, kw["n_small"], kw["n_big"]], np.int32).tobytes() + np.array([kw["reg"], kw["gw"]], np.float32).tobytes())
             f.write(img.tobytes() + a8.tobytes())
-        r = subprocess.run([check_exe, src, dst], capture_output=True, text=True, timeout=60)
-        assert r.returncode == 0 and r.stdout.splitlines()[-1] == "ok", (r.returncode, r.stdout, r.stderr)
-        got = np.fromfile(dst, np.float32).reshape(2, 3, h, w)
+        lines, raw = ps.run_check(check_exe, src, dst)
+        got = np.frombuffer(raw, np.float32).reshape(2, 3, h, w)
         F, B = fgh.estimate_foreground(img, a8, **kw)
         assert same_bits(got[0], F) and same_bits(got[1], B), (shape, kw)
         want = [int(v) for v in fgh.to_bytes(np.array([0.0, 0.5, 1.0, f32(0.25) * f32(1.0) + (f32(1.0) - f32(0.25)) * f32(0.2)], np.float32))]
-        assert [int(v) for v in r.stdout.splitlines()[0].split()] == want == [0, 128, 255, 102]
+        assert [int(v) for v in lines[0].split()] == want == [0, 128, 255, 102]
 
 
 # ---- quality ----------------------------------------------------------------------------------------------------------------------------------------------
@@ -239,28 +220,11 @@ def test_cutout_and_composite_follow_the_definition():
 
 
 # ---- symbols and arguments -------------------------------------------------------------------------------------------------------------------------------
-def _libs():
-    """Both element-type libraries as they stand in the tree (a missing one is an error, not a skip)."""
-    from genpercept_amd import engine
-    return [engine.load_library(p) for p in ("bf16", "fp16")]
-
-
 def test_entries_are_declared_exported_and_bound():
     from genpercept_amd import engine
-    from genpercept_amd.build import SOURCES
-    hdr = open(os.path.join(ROOT, "include", "genpercept_hip.h")).read()
-    declared = set(re.findall(r"\b(gp_[a-z0-9_]+)\s*\(", hdr))
-    for lib in _libs():
-        for name in NAMES:
-            assert name in declared and name in engine.SYMBOLS
-            fn = getattr(lib, name)
-            assert fn.restype is engine.SYMBOLS[name][0] and list(fn.argtypes) == list(engine.SYMBOLS[name][1])
-        assert lib.gp_abi_version() == 3
-    assert "foreground.hip" in SOURCES and "#define GP_ABI_VERSION 3" in hdr
+    ps.assert_entries_bound(NAMES, "foreground.hip")
     assert len(engine.SYMBOLS["gp_foreground"][1]) == 19 and engine.SYMBOLS["gp_foreground_workspace"] == (C.c_longlong, [C.c_int] * 3)
     assert callable(engine.estimate_foreground) and callable(engine.cutout) and callable(engine.foreground)
-    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    assert all(f"`{n}`" in text for n in NAMES)
 
 
 def test_workspace_size():
@@ -302,5 +266,4 @@ def test_invalid_arguments_are_refused_without_a_gpu():
         need = lib.gp_foreground_workspace(2, 40, 40)
         ok = dict(image=0x1001, alpha=0x2003, u8=1, B=2, H=40, W=40, reg=1e-5, gw=1.0, n_small=10, n_big=2, new_bg=None, rgb=0, fg=0x3000, bg=0x4000,
                   rgba=0x5000, comp=0x6001, ws=0x8000, nbytes=need)
-        for kw in invalid_cases(ok, lib.gp_foreground_workspace(1, 40, 40)):
-            assert call_foreground(lib, dict(ok, **kw)) == GP_ERR_INVALID, kw
+        ps.assert_all_refused(call_foreground, lib, ok, invalid_cases(ok, lib.gp_foreground_workspace(1, 40, 40)))

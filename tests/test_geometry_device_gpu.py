@@ -12,23 +12,13 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_geometry_host import GP_ERR_INVALID, PLANES, POINTS, call_geometry, geometry_args, invalid_cases, random_case, same_bits  # noqa: E402
+from post_support import GP_ERR_INVALID, assert_refused_with_real_buffers, offset4, same_bits, tiny_weights_dict  # noqa: E402
+from test_geometry_host import PLANES, POINTS, call_geometry, geometry_args, invalid_cases, random_case  # noqa: E402
 
 gpu = pytest.mark.gpu
 
 # B, H, W, r, stride
 CASES = [(1, 17, 23, 1, 1), (2, 40, 70, 2, 1), (1, 33, 200, 8, 3), (1, 64, 48, 2, 2), (3, 16, 16, 1, 1)]
-
-
-def offset4(x: np.ndarray) -> torch.Tensor:
-    """The array on the device as a contiguous view that starts four bytes into a 16-byte aligned buffer."""
-    x = np.ascontiguousarray(x)
-    per = 4 // x.dtype.itemsize
-    flat = torch.empty(x.size + per, dtype=torch.from_numpy(x).dtype, device="cuda")
-    v = flat[per:].view(x.shape)
-    v.copy_(torch.from_numpy(x))
-    assert v.data_ptr() % 16 == 4
-    return v
 
 
 def batch_case(seed, b, h, w, middle_invalid=False):
@@ -125,11 +115,8 @@ def test_null_outputs_and_invalid_arguments_with_real_buffers():
     ws = torch.full((ok["nbytes"],), 0x5A, dtype=torch.uint8, device="cuda")
     ok["ws"], ok["cams"] = ws.data_ptr(), cams.ctypes.data
     keep = [cams_ok]
-    for kw in invalid_cases(ok, cams, keep):
-        assert call_geometry(lib, dict(ok, **kw)) == GP_ERR_INVALID, kw
-    torch.cuda.synchronize()
-    untouched = fresh()
-    assert all(torch.equal(bufs[k], untouched[k]) for k in bufs) and bool((ws == 0x5A).all())
+    assert_refused_with_real_buffers(call_geometry, lib, ok, invalid_cases(ok, cams, keep), bufs, fresh)
+    assert bool((ws == 0x5A).all())
     want = gm.depth_geometry(pred, cams, image, mask, "depth", ok["r"], ok["tau"], ok["min_count"], ok["min_cos"], stride)
     n = int(want["offsets"][-1])
     assert 0 < n < cap
@@ -157,9 +144,7 @@ def test_null_outputs_and_invalid_arguments_with_real_buffers():
 
 @pytest.fixture(scope="module")
 def tiny_weights():
-    from oracle import sd21 as osd
-    uc, vc = osd.UNetCfg.tiny(), osd.VAECfg.tiny()
-    return dict(uc=uc, vc=vc, usd=osd.synth_state_dict(osd.unet_manifest(uc), 1), vsd=osd.synth_state_dict(osd.vae_manifest(vc), 2))
+    return tiny_weights_dict()
 
 
 def read_ply(path):

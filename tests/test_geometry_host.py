@@ -7,29 +7,21 @@ and the ctypes table carry the new entries; their argument checks (they come bef
 import ctypes as C
 import math
 import os
-import re
-import shutil
-import subprocess
+import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "geometry_check.cpp")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import post_support as ps  # noqa: E402
+from post_support import GP_ERR_INVALID, libs as _libs, q16, same_bits  # noqa: E402,F401
+
 NAMES = ("gp_depth_geometry_workspace", "gp_depth_geometry")
-GP_ERR_INVALID = 1
 f32, f64 = np.float32, np.float64
 # H, W, r
 CASES = [(9, 13, 1), (17, 11, 2), (12, 12, 8), (5, 23, 4)]
 PLANES = ("xyz", "normal", "keep")
 POINTS = ("points", "point_normals", "point_rgb", "point_index")
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    if a.dtype != b.dtype or a.shape != b.shape:
-        return False
-    return np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 def random_case(rng, h, w):
@@ -49,12 +41,6 @@ def random_case(rng, h, w):
 
 
 # ---- the definition as plain loops ---------------------------------------------------------------------------------------------------------------
-def q16(v):
-    v = f32(v)
-    v = (v if v < f32(1.0) else f32(1.0)) if v > f32(0.0) else f32(0.0)
-    return int(v * f32(65535.0))
-
-
 def div(a, b):
     """IEEE float64 a / b without Python's ZeroDivisionError"""
     with np.errstate(all="ignore"):
@@ -154,23 +140,9 @@ def test_host_route_equals_plain_loops(case, space):
 
 
 # ---- the kernels' arithmetic on the CPU -------------------------------------------------------------------------------------------------------------
-def _clangxx():
-    for cand in ("/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++", shutil.which("amdclang++")):
-        if cand and os.path.exists(cand):
-            return cand
-    return None
-
-
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    cxx = _clangxx()
-    if cxx is None:
-        pytest.skip("the ROCm clang++ is not on this machine: geometry_check.cpp cannot be built")
-    exe = tmp_path_factory.mktemp("dgcheck") / "geometry_check"
-    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
-                        "-Werror", SRC, "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(exe)
+    return ps.build_check(tmp_path_factory, "geometry_check.cpp")
 
 
 @pytest.mark.parametrize("case", CASES + [(40, 70, 2), (33, 100, 3)], ids=lambda s: "%dx%d-r%d" % s)
@@ -187,9 +159,7 @@ def test_cpu_build_of_the_kernel_arithmetic_equals_the_host_route(check_exe, cas
             with open(src, "wb") as f:
                 f.write(np.array([h, w, sp, r, min_count, stride, use_mask, not use_mask], np.int32).tobytes() + np.array([tau, min_cos], f64).tobytes()
                         + cam.tobytes() + pred.tobytes() + (mask.tobytes() if use_mask else image.tobytes()))
-            run = subprocess.run([check_exe, src, dst], capture_output=True, text=True, timeout=60)
-            assert run.returncode == 0 and run.stdout.splitlines()[-1] == "ok", (run.returncode, run.stdout, run.stderr)
-            raw, hw = open(dst, "rb").read(), h * w
+            raw, hw = ps.run_check(check_exe, src, dst)[1], h * w
             want = gm.depth_geometry(pred, cam, None if use_mask else image, mask if use_mask else None, space, r, stride=stride)
             assert same_bits(np.frombuffer(raw[:12 * hw], f32).reshape(3, h, w), want["xyz"][0]), (case, space)
             assert same_bits(np.frombuffer(raw[12 * hw:24 * hw], f32).reshape(3, h, w), want["normal"][0]), (case, space)
@@ -385,31 +355,13 @@ def test_options_cameras_and_shapes_are_checked():
 
 
 # ---- symbols and arguments -------------------------------------------------------------------------------------------------------------------------------
-def _libs():
-    """Both element-type libraries as they stand in the tree (a missing one is an error, not a skip)."""
-    from genpercept_amd import engine
-    return [engine.load_library(p) for p in ("bf16", "fp16")]
-
-
 def test_entries_are_declared_exported_and_bound():
     from genpercept_amd import engine
-    from genpercept_amd.build import SOURCES
-    hdr = open(os.path.join(ROOT, "include", "genpercept_hip.h")).read()
-    declared = set(re.findall(r"\b(gp_[a-z0-9_]+)\s*\(", hdr))
-    for lib in _libs():
-        for name in NAMES:
-            assert name in declared and name in engine.SYMBOLS
-            fn = getattr(lib, name)
-            assert fn.restype is engine.SYMBOLS[name][0] and list(fn.argtypes) == list(engine.SYMBOLS[name][1])
-        assert lib.gp_abi_version() == 3
-    assert "depth_geometry.hip" in SOURCES and "#define GP_ABI_VERSION 3" in hdr
+    _, math_h = ps.assert_entries_bound(NAMES, "depth_geometry.hip", "depth_geometry_math.h")
     args = engine.SYMBOLS["gp_depth_geometry"][1]
     assert len(args) == 24 and args[9] is C.c_double and args[11] is C.c_double and engine.SYMBOLS["gp_depth_geometry_workspace"] == (C.c_longlong, [C.c_int] * 4)
     assert callable(engine.depth_geometry)
-    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    assert all(f"`{n}`" in text for n in NAMES)
-    assert "#pragma clang fp contract(off)" in open(os.path.join(ROOT, "genpercept_amd", "csrc", "depth_geometry_math.h")).read()
-    assert "hip_runtime" not in open(os.path.join(ROOT, "genpercept_amd", "csrc", "depth_geometry_math.h")).read()
+    assert "hip_runtime" not in math_h
 
 
 def test_workspace_size():
@@ -476,5 +428,4 @@ def test_invalid_arguments_are_refused_without_a_gpu():
         ok, cams = geometry_args(lib, 2, 40, 70)
         keep = [cams]
         assert ok["nbytes"] > 0
-        for kw in invalid_cases(ok, cams, keep):
-            assert call_geometry(lib, dict(ok, **kw)) == GP_ERR_INVALID, kw
+        ps.assert_all_refused(call_geometry, lib, ok, invalid_cases(ok, cams, keep))

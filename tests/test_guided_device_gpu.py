@@ -12,21 +12,14 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_guided_host import GP_ERR_INVALID, call_guided, invalid_cases, random_inputs, same_bits  # noqa: E402
+from post_support import assert_refused_with_real_buffers, bits, tiny_weights_dict, unaligned  # noqa: E402
+from test_guided_host import call_guided, invalid_cases, random_inputs, same_bits  # noqa: E402
 
 gpu = pytest.mark.gpu
 
 SHAPES = [(1, 1, 1, 1, 1), (1, 1, 7, 3, 20), (2, 16, 32, 16, 32), (1, 17, 33, 70, 131), (3, 37, 61, 149, 243), (1, 96, 130, 257, 300)]
 GRID = [(r, eps) for r in (1, 4, 32) for eps in (1e-6, 1e-4, 1.0)]
 KINDS = ["random blocks", "all 0", "all 255 / 1.0", "checkerboard", "soft ramp", "one bright pixel", "odd values"]
-
-
-def unaligned(x: np.ndarray) -> torch.Tensor:
-    """The array on the device as a contiguous view that starts one byte (one element of a float array) into its buffer."""
-    flat = torch.empty(x.size + 1, dtype=torch.from_numpy(x[:0]).dtype, device="cuda")
-    v = flat[1:].view(x.shape)
-    v.copy_(torch.from_numpy(np.ascontiguousarray(x)))
-    return v
 
 
 def inputs(kind, b, c, h, w, H, W, seed):
@@ -125,9 +118,7 @@ def test_refuses_invalid_arguments_before_touching_the_device():
     ws = torch.full((need,), 0x5A, dtype=torch.uint8, device="cuda")
     ok = dict(guide_lo=lo_d.data_ptr(), pred=p_d.data_ptr(), C=c, guide=hi_d.data_ptr(), B=b, h=h, w=w, H=H, W=W, r=4, eps=1e-4, out=out.data_ptr(),
               ws=ws.data_ptr(), nbytes=need)
-    for kw in invalid_cases(ok, int(lib.gp_guided_upsample_workspace(1, c, h, w))):
-        assert call_guided(lib, dict(ok, **kw)) == GP_ERR_INVALID, kw
-    torch.cuda.synchronize()
+    assert_refused_with_real_buffers(call_guided, lib, ok, invalid_cases(ok, int(lib.gp_guided_upsample_workspace(1, c, h, w))))
     assert bool((out == -7.0).all() and (ws == 0x5A).all())
     assert call_guided(lib, ok) == 0                                 # ... and the valid set goes through
     torch.cuda.synchronize()
@@ -138,13 +129,7 @@ def test_refuses_invalid_arguments_before_touching_the_device():
 
 @pytest.fixture(scope="module")
 def tiny_weights():
-    from oracle import sd21 as osd
-    uc, vc = osd.UNetCfg.tiny(), osd.VAECfg.tiny()
-    return dict(uc=uc, vc=vc, usd=osd.synth_state_dict(osd.unet_manifest(uc), 1), vsd=osd.synth_state_dict(osd.vae_manifest(vc), 2))
-
-
-def bits(t: torch.Tensor) -> torch.Tensor:
-    return t.contiguous().view(torch.int32)
+    return tiny_weights_dict()
 
 
 @gpu

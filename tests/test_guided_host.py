@@ -4,25 +4,21 @@ implementation written here from the definition; tests/guided_check.cpp, a stand
 that the cap on r buys; the quality of the refinement on a synthetic matte; constant predictions and constant images; the header, the two
 libraries and the ctypes table carry the new entry; its argument checks (they come before the first HIP call, so they run without a GPU)."""
 import ctypes as C
+import functools
 import os
-import re
-import shutil
-import subprocess
+import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "guided_check.cpp")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import post_support as ps  # noqa: E402
+from post_support import GP_ERR_INVALID, libs as _libs  # noqa: E402,F401
+
 NAMES = ("gp_guided_upsample_workspace", "gp_guided_upsample")
-GP_ERR_INVALID = 1
 f32 = np.float32
 SIZES = [(1, 1, 1, 1), (1, 7, 3, 20), (5, 4, 5, 4), (9, 13, 35, 50)]
-
-
-def same_bits(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.dtype == b.dtype == np.float32 and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+same_bits = functools.partial(ps.same_bits, dtype=np.float32)
 
 
 def random_inputs(rng, c, h, w, H, W):
@@ -147,23 +143,9 @@ def test_host_route_equals_plain_loops(size, r, c):
 
 
 # ---- the kernels' arithmetic on the CPU -------------------------------------------------------------------------------------------------------------
-def _clangxx():
-    for cand in ("/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++", shutil.which("amdclang++")):
-        if cand and os.path.exists(cand):
-            return cand
-    return None
-
-
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    cxx = _clangxx()
-    if cxx is None:
-        pytest.skip("the ROCm clang++ is not on this machine: guided_check.cpp cannot be built")
-    exe = tmp_path_factory.mktemp("gdcheck") / "guided_check"
-    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
-                        "-Werror", SRC, "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(exe)
+    return ps.build_check(tmp_path_factory, "guided_check.cpp")
 
 
 @pytest.mark.parametrize("case", [(1, 1, 1, 1, 1, 1), (1, 7, 3, 20, 32, 3), (9, 13, 35, 50, 3, 3), (37, 29, 80, 61, 4, 1), (20, 31, 9, 14, 2, 1)],
@@ -182,16 +164,14 @@ def test_cpu_build_of_the_kernel_arithmetic_equals_the_host_route(check_exe, cas
                 assert sums[k].dtype == np.int64
                 f.write(np.ascontiguousarray(sums[k]).tobytes())
             f.write(hi.tobytes())
-        run = subprocess.run([check_exe, src, dst], capture_output=True, text=True, timeout=60)
-        assert run.returncode == 0 and run.stdout.splitlines()[-1] == "ok", (run.returncode, run.stdout, run.stderr)
-        raw = open(dst, "rb").read()
+        lines, raw = ps.run_check(check_exe, src, dst)
         ab = np.frombuffer(raw[:c * 4 * h * w * 8], np.float64).reshape(c, 4, h, w)
         q = np.frombuffer(raw[c * 4 * h * w * 8:], np.float32).reshape(c, H, W)
         want_ab = gd.solve(sums, eps)
         assert np.array_equal(ab.view(np.uint64), want_ab.view(np.uint64)), (case, eps)
         assert same_bits(q, gd.guided_upsample(lo, p, hi, r, eps)), (case, eps)
         want = [int(v) for v in gd.quantize16(np.array([0.0, 1.0, np.nan, -0.25, 1.5, 0.5], np.float32))]
-        assert [int(v) for v in run.stdout.splitlines()[0].split()] == want == [0, 65535, 0, 0, 65535, 32767]
+        assert [int(v) for v in lines[0].split()] == want == [0, 65535, 0, 0, 65535, 32767]
 
 
 # ---- what the cap on r is for ---------------------------------------------------------------------------------------------------------------------------
@@ -304,30 +284,12 @@ def test_options_and_shapes_are_checked():
 
 
 # ---- symbols and arguments -------------------------------------------------------------------------------------------------------------------------------
-def _libs():
-    """Both element-type libraries as they stand in the tree (a missing one is an error, not a skip)."""
-    from genpercept_amd import engine
-    return [engine.load_library(p) for p in ("bf16", "fp16")]
-
-
 def test_entries_are_declared_exported_and_bound():
     from genpercept_amd import engine
-    from genpercept_amd.build import SOURCES
-    hdr = open(os.path.join(ROOT, "include", "genpercept_hip.h")).read()
-    declared = set(re.findall(r"\b(gp_[a-z0-9_]+)\s*\(", hdr))
-    for lib in _libs():
-        for name in NAMES:
-            assert name in declared and name in engine.SYMBOLS
-            fn = getattr(lib, name)
-            assert fn.restype is engine.SYMBOLS[name][0] and list(fn.argtypes) == list(engine.SYMBOLS[name][1])
-        assert lib.gp_abi_version() == 3
-    assert "guided.hip" in SOURCES and "#define GP_ABI_VERSION 3" in hdr
+    ps.assert_entries_bound(NAMES, "guided.hip", "guided_solve.h")
     assert len(engine.SYMBOLS["gp_guided_upsample"][1]) == 15 and engine.SYMBOLS["gp_guided_upsample"][1][10] is C.c_double
     assert engine.SYMBOLS["gp_guided_upsample_workspace"] == (C.c_longlong, [C.c_int] * 4)
     assert callable(engine.guided_upsample)
-    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    assert all(f"`{n}`" in text for n in NAMES)
-    assert "#pragma clang fp contract(off)" in open(os.path.join(ROOT, "genpercept_amd", "csrc", "guided_solve.h")).read()
 
 
 def test_workspace_size():
@@ -365,5 +327,4 @@ def test_invalid_arguments_are_refused_without_a_gpu():
     for lib in _libs():
         need = lib.gp_guided_upsample_workspace(2, 1, 24, 40)
         ok = dict(guide_lo=0x1001, pred=0x2000, C=1, guide=0x3003, B=2, h=24, w=40, H=96, W=160, r=4, eps=1e-4, out=0x5000, ws=0x8000, nbytes=need)
-        for kw in invalid_cases(ok, lib.gp_guided_upsample_workspace(1, 1, 24, 40)):
-            assert call_guided(lib, dict(ok, **kw)) == GP_ERR_INVALID, kw
+        ps.assert_all_refused(call_guided, lib, ok, invalid_cases(ok, lib.gp_guided_upsample_workspace(1, 1, 24, 40)))

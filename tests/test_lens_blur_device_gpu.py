@@ -13,23 +13,13 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_lens_blur_host import GP_ERR_INVALID, all_tables, call_lens, invalid_cases, lens_args, random_case, same_bits  # noqa: E402
+from post_support import assert_refused_with_real_buffers, offset4, same_bits, tiny_weights_dict  # noqa: E402
+from test_lens_blur_host import all_tables, call_lens, invalid_cases, lens_args, random_case  # noqa: E402
 
 gpu = pytest.mark.gpu
 
 # B, H, W, max_radius, with a sharp mask and dz > 0
 CASES = [(1, 17, 23, 2, False), (2, 40, 70, 8, False), (1, 33, 200, 32, False), (1, 64, 48, 5, True), (3, 16, 16, 32, False)]
-
-
-def offset4(x: np.ndarray) -> torch.Tensor:
-    """The array on the device as a contiguous view that starts four bytes into a 16-byte aligned buffer."""
-    x = np.ascontiguousarray(x)
-    per = 4 // x.dtype.itemsize
-    flat = torch.empty(x.size + per, dtype=torch.from_numpy(x).dtype, device="cuda")
-    v = flat[per:].view(x.shape)
-    v.copy_(torch.from_numpy(x))
-    assert v.data_ptr() % 16 == 4
-    return v
 
 
 def batch_case(seed, b, h, w, middle_nan=False):
@@ -157,11 +147,7 @@ def test_invalid_arguments_with_real_buffers_and_the_clamped_table():
     bufs = fresh()
     ok = lens_args(b, h, w, image=image_d.data_ptr(), pred=pred_d.data_ptr(), sharp=sharp_d.data_ptr(), params=params_d.data_ptr(),
                    to_lin=to_lin_d.data_ptr(), from_lin=from_lin_d.data_ptr(), **{k: v.data_ptr() for k, v in bufs.items()})
-    for kw in invalid_cases(ok):
-        assert call_lens(lib, dict(ok, **kw)) == GP_ERR_INVALID, kw
-    torch.cuda.synchronize()
-    untouched = fresh()
-    assert all(torch.equal(bufs[k], untouched[k]) for k in bufs)
+    untouched = assert_refused_with_real_buffers(call_lens, lib, ok, invalid_cases(ok), bufs, fresh)
     want, want_coc = lb.lens_blur_params(image, pred, rows, "depth", sharp, tables, want_coc=True)
     for with_coc in (True, False):
         bufs = fresh()
@@ -181,9 +167,7 @@ def test_invalid_arguments_with_real_buffers_and_the_clamped_table():
 
 @pytest.fixture(scope="module")
 def tiny_weights():
-    from oracle import sd21 as osd
-    uc, vc = osd.UNetCfg.tiny(), osd.VAECfg.tiny()
-    return dict(uc=uc, vc=vc, usd=osd.synth_state_dict(osd.unet_manifest(uc), 1), vsd=osd.synth_state_dict(osd.vae_manifest(vc), 2))
+    return tiny_weights_dict()
 
 
 @gpu

@@ -5,23 +5,17 @@ for, with exact expectations; the tables and the user's terms; the entry declare
 buffers.  There is no tolerance in this file."""
 import ctypes as C
 import os
-import re
-import shutil
-import subprocess
+import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "lens_blur_check.cpp")
-GP_ERR_INVALID = 1
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import post_support as ps  # noqa: E402
+from post_support import GP_ERR_INVALID, libs as _libs, same_bits  # noqa: E402,F401
+
 # H, W, (F, gain, cmax8, dz)
 CASES = [(9, 13, (30000, 2000, 24, 0)), (17, 11, (50000, 700, 40, 3000)), (7, 9, (0, 32768, 256, 0)), (5, 23, (65535, 300, 13, 100))]
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 def random_case(rng, h, w, nan=True):
@@ -123,23 +117,9 @@ def test_disc_sizes():
 
 
 # ---- the kernel's arithmetic on the CPU ---------------------------------------------------------------------------------------------------------------
-def _clangxx():
-    for cand in ("/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++", shutil.which("amdclang++")):
-        if cand and os.path.exists(cand):
-            return cand
-    return None
-
-
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    cxx = _clangxx()
-    if cxx is None:
-        pytest.skip("the ROCm clang++ is not on this machine: lens_blur_check.cpp cannot be built")
-    exe = tmp_path_factory.mktemp("lbcheck") / "lens_blur_check"
-    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra", "-Werror", SRC,
-                        "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(exe)
+    return ps.build_check(tmp_path_factory, "lens_blur_check.cpp", extra_flags=())   # (the one program built without -ffp-contract=off)
 
 
 @pytest.mark.parametrize("case", CASES + [(40, 70, (20000, 4000, 64, 500)), (33, 50, (40000, 32768, 256, 0))], ids=lambda s: "%dx%d" % s[:2])
@@ -157,9 +137,7 @@ def test_cpu_build_of_the_kernel_arithmetic_equals_the_host_route(check_exe, cas
             with open(src, "wb") as f:
                 f.write(np.array([h, w, sp, use_sharp] + list(row), np.int32).tobytes() + to_lin.astype(np.uint16).tobytes() + from_lin.tobytes()
                         + pred.tobytes() + image.tobytes() + (sharp.tobytes() if use_sharp else b""))
-            run = subprocess.run([check_exe, src, dst], capture_output=True, text=True, timeout=120)
-            assert run.returncode == 0 and run.stdout.splitlines()[-1] == "ok", (run.returncode, run.stdout, run.stderr)
-            raw, hw = open(dst, "rb").read(), h * w
+            raw, hw = ps.run_check(check_exe, src, dst, timeout=120)[1], h * w
             assert len(raw) == 5 * hw + 4 * 257
             want, coc = lb.lens_blur_params(image, pred, row, space, sharp if use_sharp else None, tables[name], want_coc=True)
             assert same_bits(np.frombuffer(raw[:3 * hw], np.uint8).reshape(3, h, w), want[0]), (case, space, name)
@@ -332,30 +310,14 @@ def test_tables_and_terms_are_checked():
 
 
 # ---- symbols and arguments ----------------------------------------------------------------------------------------------------------------------------
-def _libs():
-    """Both element-type libraries as they stand in the tree (a missing one is an error, not a skip)."""
-    from genpercept_amd import engine
-    return [engine.load_library(p) for p in ("bf16", "fp16")]
-
-
 def test_entry_is_declared_exported_and_bound():
     from genpercept_amd import engine, infer_eval
-    from genpercept_amd.build import SOURCES
     from genpercept_amd.pipeline import GenPerceptPipeline
-    hdr = open(os.path.join(ROOT, "include", "genpercept_hip.h")).read()
-    declared = set(re.findall(r"\b(gp_[a-z0-9_]+)\s*\(", hdr))
-    for lib in _libs():
-        assert "gp_lens_blur" in declared and "gp_lens_blur" in engine.SYMBOLS
-        fn = lib.gp_lens_blur
-        assert fn.restype is engine.SYMBOLS["gp_lens_blur"][0] and list(fn.argtypes) == list(engine.SYMBOLS["gp_lens_blur"][1])
-        assert lib.gp_abi_version() == 3
-    assert "lens_blur.hip" in SOURCES and "#define GP_ABI_VERSION 3" in hdr
+    hdr, math_h = ps.assert_entries_bound(("gp_lens_blur",), "lens_blur.hip", "lens_blur_math.h", contract_off=False)
     args = engine.SYMBOLS["gp_lens_blur"][1]
     assert len(args) == 14 and args[6:11] == [C.c_int] * 5 and engine.SYMBOLS["gp_lens_blur"][0] is C.c_int
     assert callable(engine.lens_blur) and callable(infer_eval.run_refocus)
     assert callable(GenPerceptPipeline.refocus_batch_device) and callable(GenPerceptPipeline.refocus)
-    assert "`gp_lens_blur`" in open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    math_h = open(os.path.join(ROOT, "genpercept_amd", "csrc", "lens_blur_math.h")).read()
     assert "hip_runtime" not in math_h and "thin-lens" in hdr
 
 
@@ -388,5 +350,4 @@ def test_invalid_arguments_are_refused_without_a_gpu():
         ok = lens_args(2, 40, 70)
         cases = invalid_cases(ok)
         assert len(cases) == 26
-        for kw in cases:
-            assert call_lens(lib, dict(ok, **kw)) == GP_ERR_INVALID, kw
+        ps.assert_all_refused(call_lens, lib, ok, cases)

@@ -14,6 +14,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from test_mask_band_host import (BOUNDARY_METRICS, GP_ERR_INVALID, MASK_METRICS, PLANES, REACHES, THRESHOLDS, TRIMAP_METRICS, call_band,  # noqa: E402
                                  invalid_cases, random_map)
+from post_support import tiny_weights_dict, unaligned  # noqa: E402
 
 gpu = pytest.mark.gpu
 
@@ -25,14 +26,6 @@ FEW = [(0, 8), (1, 3), (0, 10 ** 6), (1, 1100)]
 
 def same_bits(a, b):
     return np.array_equal(np.asarray(a, dtype=np.float64).view(np.uint64), np.asarray(b, dtype=np.float64).view(np.uint64))
-
-
-def unaligned(x: np.ndarray) -> torch.Tensor:
-    """The array on the device as a contiguous view that starts one element into its buffer."""
-    flat = torch.empty(x.size + 1, dtype=torch.from_numpy(x[:0]).dtype, device="cuda")
-    v = flat[1:].view(x.shape)
-    v.copy_(torch.from_numpy(np.ascontiguousarray(x)))
-    return v
 
 
 def inputs(b, h, w, seed):
@@ -192,9 +185,7 @@ def test_mask_band_refuses_invalid_arguments_before_touching_the_device():
 
 @pytest.fixture(scope="module")
 def tiny_weights():
-    from oracle import sd21 as osd
-    uc, vc = osd.UNetCfg.tiny(), osd.VAECfg.tiny()
-    return dict(uc=uc, vc=vc, usd=osd.synth_state_dict(osd.unet_manifest(uc), 1), vsd=osd.synth_state_dict(osd.vae_manifest(vc), 2))
+    return tiny_weights_dict()
 
 
 @gpu

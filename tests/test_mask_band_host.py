@@ -14,6 +14,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import test_eval_mask_host as tm  # noqa: E402  (make_tree, FakePipe, numpy_evaluator, trimap_region: the mask loop's fixtures)
+from post_support import libs as _libs  # noqa: E402
 
 NAMES = ("gp_mask_band_workspace", "gp_mask_band")
 MASK_METRICS = ["mae", "mse", "sad", "max_f", "mean_f", "adp_f", "iou"]
@@ -23,12 +24,6 @@ PLANES = ["band", "fg", "bg", "inner", "trimap"]
 GP_ERR_INVALID = 1
 THRESHOLDS = [(0, 255), (128, 129), (127, 128), (-1, 256)]
 REACHES = [(0, 0), (0, 1), (0, 2), (0, 8), (0, 10 ** 6), (1, 1), (1, 3)]  # (metric, reach)
-
-
-def _libs():
-    """Both element-type libraries as they stand in the tree (a missing one is an error, not a skip)."""
-    from genpercept_amd import engine
-    return [engine.load_library(p) for p in ("bf16", "fp16")]
 
 
 def random_map(rng, h, w):

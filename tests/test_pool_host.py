@@ -6,20 +6,16 @@ program checks the reuse policy, the handle's move / reset semantics, the outsta
 `h = f(h)` ordering rule; the sanitizers report a double free, a use after free or a leak in the handle itself.
 """
 import os
-import shutil
 import subprocess
+import sys
 
 import pytest
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from post_support import clangxx as _clangxx  # noqa: E402
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "pool_check.cpp")
-
-
-def _clangxx():
-    for cand in ("/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++", shutil.which("amdclang++")):
-        if cand and os.path.exists(cand):
-            return cand
-    return None
 
 
 def test_pool_and_handle_under_sanitizers(tmp_path):

@@ -11,22 +11,14 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_tiled_host import GP_ERR_INVALID, call_merge, invalid_cases, merge_args, random_case, same_bits, same_bits64  # noqa: E402
+from post_support import assert_refused_with_real_buffers, bits, offset4, same_bits64, tiny_weights_dict  # noqa: E402
+from test_tiled_host import call_merge, invalid_cases, merge_args, random_case, same_bits  # noqa: E402
 
 gpu = pytest.mark.gpu
 
 # B, C, H, W, T, o, align
 CASES = [(1, 1, 40, 40, 40, 8, "least_square"), (2, 1, 70, 101, 32, 8, "least_square"), (1, 3, 65, 130, 64, 32, "none"), (1, 1, 96, 96, 16, 8, "least_square"),
          (1, 1, 33, 200, 33, 16, "least_square"), (2, 3, 50, 77, 24, 5, "least_square")]
-
-
-def offset4(x: np.ndarray) -> torch.Tensor:
-    """The array on the device as a contiguous view that starts one element (4 bytes) into a 16-byte aligned buffer."""
-    flat = torch.empty(x.size + 1, dtype=torch.float32, device="cuda")
-    v = flat[1:].view(x.shape)
-    v.copy_(torch.from_numpy(np.ascontiguousarray(x)))
-    assert v.data_ptr() % 16 == 4 and v.storage_offset() == 1
-    return v
 
 
 def batch_case(seed, b, c, h, w, size, o, odd=True):
@@ -120,9 +112,7 @@ def test_refuses_invalid_arguments_before_touching_the_device():
     ws = torch.full((ok["nbytes"],), 0x5A, dtype=torch.uint8, device="cuda")
     ok["ws"] = ws.data_ptr()
     keep = list(keep)
-    for kw in invalid_cases(ok, keep):
-        assert call_merge(lib, dict(ok, **kw)) == GP_ERR_INVALID, kw
-    torch.cuda.synchronize()
+    assert_refused_with_real_buffers(call_merge, lib, ok, invalid_cases(ok, keep))
     assert bool((out_buf == -7.0).all() and (ws == 0x5A).all() and (fit == -7.0).all())
     assert out.data_ptr() % 16 == 4 and call_merge(lib, ok) == 0      # ... and the valid set goes through
     torch.cuda.synchronize()
@@ -137,13 +127,7 @@ def test_refuses_invalid_arguments_before_touching_the_device():
 
 @pytest.fixture(scope="module")
 def tiny_weights():
-    from oracle import sd21 as osd
-    uc, vc = osd.UNetCfg.tiny(), osd.VAECfg.tiny()
-    return dict(uc=uc, vc=vc, usd=osd.synth_state_dict(osd.unet_manifest(uc), 1), vsd=osd.synth_state_dict(osd.vae_manifest(vc), 2))
-
-
-def bits(t: torch.Tensor) -> torch.Tensor:
-    return t.contiguous().view(torch.int32)
+    return tiny_weights_dict()
 
 
 @gpu

@@ -4,31 +4,22 @@ program over the kernels' own arithmetic (csrc/tile_merge_math.h, contraction of
 route; tiles that are affine images of the base merge back to it; the degenerate branches of the fit; the header, the two libraries and the
 ctypes table carry the new entries; their argument checks (they come before the first HIP call, so they run without a GPU)."""
 import ctypes as C
+import functools
 import os
-import re
-import shutil
-import subprocess
+import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "tile_check.cpp")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import post_support as ps  # noqa: E402
+from post_support import GP_ERR_INVALID, libs as _libs, q16, same_bits64  # noqa: E402,F401
+
 NAMES = ("gp_tile_merge_workspace", "gp_tile_merge")
-GP_ERR_INVALID = 1
 f32 = np.float32
 # C, H, W, T, o
 CASES = [(1, 9, 13, 6, 2), (3, 17, 11, 8, 4), (1, 12, 12, 12, 3), (1, 20, 7, 4, 2), (3, 5, 23, 9, 1), (1, 16, 16, 4, 2)]
-
-
-def same_bits(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.dtype == b.dtype == np.float32 and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def same_bits64(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype == np.float64 and a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+same_bits = functools.partial(ps.same_bits, dtype=np.float32)
 
 
 def random_case(rng, c, h, w, size, o, odd=True):
@@ -87,12 +78,6 @@ def test_grid_rule_over_an_exhaustive_sweep():
 
 
 # ---- the definition as plain loops ---------------------------------------------------------------------------------------------------------------
-def q16(v):
-    v = f32(v)
-    v = (v if v < f32(1.0) else f32(1.0)) if v > f32(0.0) else f32(0.0)
-    return int(v * f32(65535.0))
-
-
 def loops_fit(base, tiles, ys, xs, align):
     """The fit of the definition, literally: Python integers for the sums, Python floats (IEEE float64, one operation at a time) after them."""
     N, Cn, wh, ww = tiles.shape
@@ -162,23 +147,9 @@ def test_host_route_equals_plain_loops(case, align):
 
 
 # ---- the kernels' arithmetic on the CPU -------------------------------------------------------------------------------------------------------------
-def _clangxx():
-    for cand in ("/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++", shutil.which("amdclang++")):
-        if cand and os.path.exists(cand):
-            return cand
-    return None
-
-
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    cxx = _clangxx()
-    if cxx is None:
-        pytest.skip("the ROCm clang++ is not on this machine: tile_check.cpp cannot be built")
-    exe = tmp_path_factory.mktemp("tmcheck") / "tile_check"
-    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
-                        "-Werror", SRC, "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(exe)
+    return ps.build_check(tmp_path_factory, "tile_check.cpp")
 
 
 @pytest.mark.parametrize("case", CASES + [(1, 70, 101, 32, 8), (3, 50, 77, 24, 5), (1, 33, 200, 33, 16)], ids=lambda s: "c%d-%dx%d-T%d-o%d" % s)
@@ -190,9 +161,7 @@ def test_cpu_build_of_the_kernel_arithmetic_equals_the_host_route(check_exe, cas
         src, dst = str(tmp_path / f"in{a}.bin"), str(tmp_path / f"out{a}.bin")
         with open(src, "wb") as f:
             f.write(np.array([c, h, w, size, o, a], np.int32).tobytes() + base.tobytes() + tiles.tobytes())
-        run = subprocess.run([check_exe, src, dst], capture_output=True, text=True, timeout=60)
-        assert run.returncode == 0 and run.stdout.splitlines()[-1] == "ok", (run.returncode, run.stdout, run.stderr)
-        raw = open(dst, "rb").read()
+        raw = ps.run_check(check_exe, src, dst)[1]
         ny, nx, wh, ww = (int(v) for v in np.frombuffer(raw[:16], np.int32))
         assert (ny, nx, wh, ww) == (len(ys), len(xs)) + tiles.shape[2:]
         pos = 16
@@ -320,29 +289,11 @@ def test_options_and_shapes_are_checked():
 
 
 # ---- symbols and arguments -------------------------------------------------------------------------------------------------------------------------------
-def _libs():
-    """Both element-type libraries as they stand in the tree (a missing one is an error, not a skip)."""
-    from genpercept_amd import engine
-    return [engine.load_library(p) for p in ("bf16", "fp16")]
-
-
 def test_entries_are_declared_exported_and_bound():
     from genpercept_amd import engine
-    from genpercept_amd.build import SOURCES
-    hdr = open(os.path.join(ROOT, "include", "genpercept_hip.h")).read()
-    declared = set(re.findall(r"\b(gp_[a-z0-9_]+)\s*\(", hdr))
-    for lib in _libs():
-        for name in NAMES:
-            assert name in declared and name in engine.SYMBOLS
-            fn = getattr(lib, name)
-            assert fn.restype is engine.SYMBOLS[name][0] and list(fn.argtypes) == list(engine.SYMBOLS[name][1])
-        assert lib.gp_abi_version() == 3
-    assert "tile_merge.hip" in SOURCES and "#define GP_ABI_VERSION 3" in hdr
+    ps.assert_entries_bound(NAMES, "tile_merge.hip", "tile_merge_math.h")
     assert len(engine.SYMBOLS["gp_tile_merge"][1]) == 19 and engine.SYMBOLS["gp_tile_merge_workspace"] == (C.c_longlong, [C.c_int] * 8)
     assert callable(engine.tile_merge)
-    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    assert all(f"`{n}`" in text for n in NAMES)
-    assert "#pragma clang fp contract(off)" in open(os.path.join(ROOT, "genpercept_amd", "csrc", "tile_merge_math.h")).read()
 
 
 def test_workspace_size():
@@ -406,5 +357,4 @@ def test_invalid_arguments_are_refused_without_a_gpu():
         ok, keep = merge_args(lib, 2, 1, 70, 101, 32, 8)
         keep = list(keep)
         assert ok["ny"] == 3 and ok["nx"] == 4 and ok["nbytes"] > 0
-        for kw in invalid_cases(ok, keep):
-            assert call_merge(lib, dict(ok, **kw)) == GP_ERR_INVALID, kw
+        ps.assert_all_refused(call_merge, lib, ok, invalid_cases(ok, keep))

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../genpercept_amd/csrc/tile_merge_math.h"
+#include "check_io.h"
 
 typedef unsigned long long u64;
 
@@ -17,7 +18,7 @@ int main(int argc, char** argv) {
     FILE* f = std::fopen(argv[1], "rb");
     if (!f) return 3;
     int hd[6];
-    if (std::fread(hd, 4, 6, f) != 6) return 4;
+    if (!get(hd, 4, 6, f)) return 4;
     const int C = hd[0], H = hd[1], W = hd[2], T = hd[3], o = hd[4], align = hd[5];
     if ((C != 1 && C != 3) || H < 1 || W < 1 || H > TM_MAX_DIM || W > TM_MAX_DIM || T < 1) return 5;
     const int wh = T < H ? T : H, ww = T < W ? T : W;
@@ -29,7 +30,7 @@ int main(int argc, char** argv) {
     for (int k = 0; k < nx; ++k) xs[k] = tm_origin(k, W, ww, nx);
     const size_t HW = (size_t)H * W, tsz = (size_t)wh * ww;
     std::vector<float> base(C * HW), tiles((size_t)N * C * tsz);
-    if (std::fread(base.data(), 4, base.size(), f) != base.size() || std::fread(tiles.data(), 4, tiles.size(), f) != tiles.size()) return 6;
+    if (!get(base.data(), 4, base.size(), f) || !get(tiles.data(), 4, tiles.size(), f)) return 6;
     std::fclose(f);
 
     std::vector<double> fit(2 * (size_t)N);
@@ -71,8 +72,8 @@ int main(int argc, char** argv) {
     f = std::fopen(argv[2], "wb");
     if (!f) return 9;
     const int out_hd[4] = {ny, nx, wh, ww};
-    if (std::fwrite(out_hd, 4, 4, f) != 4 || std::fwrite(ys.data(), 4, ys.size(), f) != ys.size() || std::fwrite(xs.data(), 4, xs.size(), f) != xs.size() ||
-        std::fwrite(fit.data(), 8, fit.size(), f) != fit.size() || std::fwrite(q.data(), 4, q.size(), f) != q.size())
+    if (!put(out_hd, 4, 4, f) || !put(ys.data(), 4, ys.size(), f) || !put(xs.data(), 4, xs.size(), f) || !put(fit.data(), 8, fit.size(), f) ||
+        !put(q.data(), 4, q.size(), f))
         return 10;
     std::fclose(f);
     std::printf("ok\n");
