@@ -233,6 +233,9 @@ void launch_normalize_rgb(const float* in, float* out, long long n, hipStream_t 
 void launch_colorize_lut(const float* x, const unsigned char* lut, unsigned char* rgb, long long n, hipStream_t s);
 void launch_quantize(const float* x, void* q, long long n, int bits, hipStream_t s);
 
+// stereo.hip: gp_stereo_views and gp_stereo_views_workspace (declared in include/genpercept_hip.h, like the entries of the other
+// post-processing sources: they have no launcher of their own behind the C-ABI).  Arithmetic: stereo_math.h.
+
 // contract.hip: the kernels between the matrix products of the contract-precision mode (fp32 storage, split-bf16 MFMA operands:
 // A order [hi | lo | hi], B order [hi | hi | lo] over a tripled K).  Split tensors have 3 * C elements per row.
 void launch_c_split3(const float* x, int ldx, h16_t* out, long long rows, int C, int b_order, int act, float scale, hipStream_t s);

@@ -177,6 +177,8 @@ SYMBOLS = {
     "gp_depth_geometry_workspace": (_ll, [_i] * 4),
     "gp_depth_geometry": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, _i, C.c_double, _i] + [_vp] * 9 + [_ll, _vp]),
     "gp_lens_blur": (_i, [_vp] * 6 + [_i] * 5 + [_vp] * 3),
+    "gp_stereo_views_workspace": (_ll, [_i] * 4),
+    "gp_stereo_views": (_i, [_vp] * 4 + [_i] * 9 + [_vp] * 4 + [_ll, _vp]),
     "gp_ensemble_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gp_ensemble_workspace": (_ll, [_i, _i, _i, _i]),
     "gp_ensemble_reduce": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
@@ -1511,7 +1513,58 @@ def lens_blur(image: torch.Tensor, pred: torch.Tensor, focus=None, focus_at=None
     return (out, coc) if want_coc else out
 
 
-SEG_OUT = 8        # n, n_void, SEG_METRICS (out[2 .. 6]), n_classes; iou[K] follows
+def stereo_views(image: torch.Tensor, pred: torch.Tensor, layout="sbs", views=2, separation=16.0, converge=None, converge_at=None, edge=0.04,
+                 space: str = "depth", want_holes: bool = False, want_near: bool = False, canvas: Optional[torch.Tensor] = None):
+    """gp_stereo_views on device tensors: the images re-rendered from viewpoints shifted sideways under their maps -- a stereo pair, an
+    anaglyph, a quilt.  image uint8 [B, 3, H, W] ([3, H, W]: one image); pred float [B, 1, H, W] ([B, H, W] and [H, W] too), a depth or
+    disparity map in [0, 1]; layout "pair", "sbs", "over_under", "anaglyph" or "quilt" with views a count or, for a quilt, (ny, nx);
+    separation, the parallax in pixels between the outermost views at the two ends of the nearness scale; at most one of converge (a value of
+    the map in [0, 1]) and converge_at (a pixel (u, v), read on the device) -- each one value or one per image --, the zero-parallax plane,
+    the middle of the scale with neither; edge, the fraction of the map's range beyond which neighbours are cut apart (0.04: a convention);
+    space "depth" or "disparity"; canvas None or a uint8 [B, 3, CH, CW] tensor of the layout's size to write into (bytes no view writes
+    keep what they held).  Returns the canvas uint8 [B, 3, CH, CW] on the device, and with want_holes / want_near a tuple with holes uint8
+    [B, V, H, W] (1: a disocclusion) and near int16 [B, V, H, W] (the bits of the uint16 nearness of the new view) after it.  Definition in
+    include/genpercept_hip.h; genpercept_amd/stereo.py gives the same bits and states the rule from these terms to the call's integers.
+    Allocates the workspace; enqueued on the current stream, no synchronisation, nothing read back."""
+    from .stereo import F_DEFAULT, plan
+    image, pred = _images_u8(image, "image"), _float_maps(pred, "pred")
+    b, h, w = (int(v) for v in pred.shape)
+    dev = pred.device
+    _same_batch(image, (b, h, w), dev, "image")
+    if space not in SPACES:
+        raise ValueError(f"space is one of {SPACES}, got {space!r}")
+    _post_dims(b, h, w, "stereo views")
+    o = plan(b, h, w, layout, views, separation, converge, converge_at, edge)
+    table, (ch, cw), n_views = o["table"], o["size"], int(o["table"].shape[0])
+    if canvas is not None and (not torch.is_tensor(canvas) or canvas.dtype != torch.uint8 or tuple(canvas.shape) != (b, 3, ch, cw) or canvas.device != dev
+                               or not canvas.is_contiguous()):
+        raise ValueError(f"canvas: a contiguous uint8 {(b, 3, ch, cw)} tensor on {dev}, got {canvas.dtype if torch.is_tensor(canvas) else type(canvas)} "
+                         f"{tuple(canvas.shape) if torch.is_tensor(canvas) else ''}")
+    assert pred.is_cuda
+    if o["converge"] is None and o["converge_at"] is None:
+        conv = torch.full((b,), F_DEFAULT, dtype=torch.int32, device=dev)
+    else:
+        if o["converge"] is not None:
+            at = torch.from_numpy(o["converge"]).to(dev, non_blocking=True)
+        else:
+            u, v = o["converge_at"][:, 0], o["converge_at"][:, 1]
+            at = pred.view(b, h * w).gather(1, torch.from_numpy(v * w + u).to(dev, non_blocking=True)[:, None])[:, 0]
+        # the nearness of b values, the 16-bit rule in float32: plumbing on the device, so that a plane picked from the map is not read back
+        q = (at.clamp(0.0, 1.0) * 65535.0).nan_to_num(0.0).to(torch.int32)
+        conv = torch.where(at.isnan(), torch.zeros_like(q), q if space == "disparity" else 65535 - q).contiguous()
+    if canvas is None:
+        canvas = torch.empty((b, 3, ch, cw), dtype=torch.uint8, device=dev)   # (the views of every layout cover it)
+    holes = torch.empty((b, n_views, h, w), dtype=torch.uint8, device=dev) if want_holes else None
+    near = torch.empty((b, n_views, h, w), dtype=torch.int16, device=dev) if want_near else None
+    ws, nbytes = _op_workspace("gp_stereo_views", dev, b, n_views, h, w)
+    _launch("gp_stereo_views", f"images {(b, h, w)}, {n_views} views in a canvas of {(ch, cw)}, space = {space}, edge = {o['edge']}, max_s8 = {o['max_s8']}",
+            image.data_ptr(), pred.data_ptr(), conv.data_ptr(), table.ctypes.data, b, n_views, h, w, ch, cw, SPACES.index(space), o["edge"], o["max_s8"],
+            canvas.data_ptr(), _ptr(holes), _ptr(near), ws.data_ptr(), nbytes, _stream_ptr(dev))
+    extra = ((holes,) if want_holes else ()) + ((near,) if want_near else ())
+    return (canvas,) + extra if extra else canvas
+
+
+SEG_OUT = 8       # n, n_void, SEG_METRICS (out[2 .. 6]), n_classes; iou[K] follows
 SEG_NSUM = 3       # n, n_void, sum_d in front of the K x K matrix of counts_out
 
 

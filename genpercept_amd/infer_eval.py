@@ -329,6 +329,37 @@ def run_refocus(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_di
     return written
 
 
+def run_stereo(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_dir: str, name_mode: FileNameMode, mode: str = "depth",
+               batch_size: int = 1, rank: int = 0, world: int = 1, layout="sbs", views=2, separation=16.0, converge=None, converge_at=None, edge=0.04,
+               prefetch: int = 2, **inference_options) -> List[str]:
+    """One stereo frame per sample with `pipe.stereo_batch_device` (modes depth and disparity): the canvas of the layout -- a side-by-side
+    pair, an anaglyph, a quilt -- as an RGB `.png`, rendered under the sample's own prediction.  separation, converge (a value of the map in
+    [0, 1]) or converge_at (a pixel (u, v)) and edge are one value each, used for every sample.  Batching, sharding and prefetch as
+    `run_cutouts`.  Returns the paths written.  inference_options go to `pipe.predict_batch_device`, `refine` and `tiles` among them."""
+    from .stereo import stereo_options, view_table
+    if mode not in ("depth", "disparity"):
+        raise ValueError(f"a stereo view needs a depth map: mode 'depth' or 'disparity', got {mode!r}")
+    if any(np.ndim(v) != 0 for v in (converge if converge is not None else 0.0, separation, edge)) or (converge_at is not None and np.shape(converge_at) != (2,)):
+        raise ValueError("separation, converge and edge are one value each and converge_at one pixel (u, v), used for every sample")
+    stereo_options(1, converge, converge_at, edge)
+    view_table(layout, views, separation, 1, 1)
+    if world > 1:
+        lo, hi = _shard(len(samples), rank, world)
+        samples = samples[lo:hi]
+    written = []
+    for group in _size_groups(_decode_ahead(samples, lambda s: _load_rgb(base_dir, s[0], None), prefetch), max(1, batch_size)):
+        out = pipe.stereo_batch_device([img for _, img in group], mode, layout, views, separation, converge, converge_at, edge, **inference_options)
+        out = out.cpu().numpy()
+        assert len(out) == len(group)
+        for (smp, _), px in zip(group, out):
+            scene_dir = os.path.join(output_dir, os.path.dirname(smp[0]))
+            os.makedirs(scene_dir, exist_ok=True)
+            save_to = os.path.join(scene_dir, get_pred_name(os.path.basename(smp[0]), name_mode, suffix=".png"))
+            Image.fromarray(np.ascontiguousarray(np.moveaxis(px, 0, -1))).save(save_to)
+            written.append(save_to)
+    return written
+
+
 def _write_metric_files(output_dir: str, tag: str, names: List[str], per_sample, result: Dict[str, float], header: str) -> None:
     """`per_sample_metrics<tag>.csv` (one row per prediction file) and `eval_metrics<tag>.txt` (header, metric names, means)."""
     os.makedirs(output_dir, exist_ok=True)

@@ -716,6 +716,30 @@ class GenPerceptPipeline:
         """`refocus_batch_device` for one PIL image: the refocused photograph as a PIL image."""
         return _chw_to_pil(self.refocus_batch_device([image], mode, focus, focus_at, aperture, max_radius, dof, sharp, tables, **inference_options)[0])
 
+    @torch.no_grad()
+    def stereo_batch_device(self, images: Union[Sequence[Image.Image], torch.Tensor], mode: str = "depth", layout="sbs", views=2, separation=16.0,
+                            converge=None, converge_at=None, edge=0.04, **inference_options) -> torch.Tensor:
+        """The second eye without a trip to the host: images of one common size (PIL images or a uint8 [B,3,H,W] tensor) -> the canvas of
+        the layout, uint8 [B,3,CH,CW] ON THE DEVICE: `engine.stereo_views` (gp_stereo_views) applied under the map of
+        `predict_batch_device(images, mode, **inference_options)` at the input size, which never leaves the GPU.  mode: depth or disparity
+        (the space the map is read in).  layout: "pair", "sbs", "over_under", "anaglyph" or "quilt", with views a count or, for a quilt,
+        (ny, nx); separation: the parallax in pixels between the outermost views at the two ends of the nearness scale (a shift of more than
+        64 pixels is refused); at most one of converge (a value of the map in [0, 1]) and converge_at (a pixel (u, v), whose value is read
+        on the device), the zero-parallax plane -- the middle of the scale with neither; edge: the fraction of the map's range beyond which
+        neighbours are cut apart.  inference_options may hold `refine` and `tiles` as in `cutout_batch_device`: a new view shows errors
+        exactly at the depth edge, which `refine` gives the photograph's own edge."""
+        from . import engine as ge
+        from .stereo import plan
+        rgb, pred = self._post_inputs(images, mode, ("depth", "disparity"), "a stereo view", "a depth map", inference_options,
+                                      lambda images: plan(int(images.shape[0]), int(images.shape[-2]), int(images.shape[-1]), layout, views, separation,
+                                                          converge, converge_at, edge))
+        return ge.stereo_views(rgb, pred, layout, views, separation, converge, converge_at, edge, space=mode)
+
+    def stereo(self, image: Image.Image, mode: str = "depth", layout="sbs", views=2, separation=16.0, converge=None, converge_at=None, edge=0.04,
+               **inference_options) -> Image.Image:
+        """`stereo_batch_device` for one PIL image: the canvas of the layout as a PIL image."""
+        return _chw_to_pil(self.stereo_batch_device([image], mode, layout, views, separation, converge, converge_at, edge, **inference_options)[0])
+
     def _run_device(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None, refine=None,
                     tiles=None) -> List[GenPerceptOutput]:
         """Pre / post processing on the GPU (gp_preprocess / gp_postprocess): the image goes up once, resize_max_res, the model, the

@@ -36,6 +36,8 @@
  *                       flying pixels of depth edges
  *   gp_lens_blur      (no reference code) the photograph refocused under its depth or disparity prediction: a variable-radius,
  *                       occlusion-aware disc gather in integer arithmetic
+ *   gp_stereo_views   (no reference code) stereo pairs, anaglyphs and quilts from a depth or disparity prediction: a forward warp of every
+ *                       row, cut at depth edges, nearest surface first, disocclusions filled from the background side
  *   gp_ensemble_gather, gp_ensemble_reduce
  *                     ensemble_depth's tensor half (the BFGS fit stays on the host)   genpercept/util/ensemble.py:43-205;
  *                                                                   genpercept_pipeline.py:289-298
@@ -661,6 +663,64 @@ gp_status gp_depth_geometry(const float* pred, const unsigned char* mask /* or N
 gp_status gp_lens_blur(const unsigned char* image, const float* pred, const unsigned char* sharp /* or NULL */, const int* params /* [B][4] */,
                        const unsigned short* to_lin /* [256] */, const unsigned char* from_lin /* [4096] */, int B, int H, int W, int space,
                        int max_c8, unsigned char* out, unsigned short* coc /* or NULL */, void* stream);
+
+/* ---- stereo and parallax views: the photograph re-rendered from viewpoints shifted sideways (DEVICE pointers but the view table; stateless, stream-ordered, no host synchronisation, no atomics; csrc/stereo.hip) ----
+ * The second eye of a monocular depth map: side-by-side frames, anaglyphs, "wiggle" pairs and the 9 to 48 view quilts of lenticular and
+ * light-field displays.  With framework ops this is a grid_sample by the disparity, a BACKWARD warp that smears the foreground across every
+ * depth edge and cannot tell an occlusion from a disocclusion.  Here it is a forward warp (depth-image-based rendering): each row of the
+ * picture is a 1-D surface that is cut at depth edges and rasterised, the nearest surface wins where two land on one pixel, and the holes a
+ * new viewpoint opens are filled from the background side.  The whole definition is integer arithmetic, so the result does not depend on the
+ * order of evaluation and the device equals the host route genpercept_amd/stereo.py bit for bit; the arithmetic stands once more in
+ * csrc/stereo_math.h.
+ * Inputs per image: image uint8 [3][H][W]; pred fp32 [1][H][W]; one int32 F of conv [B], the nearness of the zero-parallax plane.  Per call:
+ *   space = 0 (depth) or 1 (disparity); edge 0 .. 65535; max_s8 0 .. 512, the largest shift in eighths of a pixel (at most 64 pixels), which
+ *   sizes the apron; a HOST table views int32 [V][4] = (g, ox, oy, cmask) per view, 1 <= V <= 64, |g| <= 131072, (ox, oy) the origin of the
+ *   view's H x W rectangle in the canvas, cmask in 1 .. 7 the channels the view writes (bit k: channel k).  1 <= H, W, CH, CW <= 16384 and
+ *   B * V * H * W < 2^31.
+ * 1. Nearness: Q = (uint16)(clamp(pred, 0, 1) * 65535.0f); D = Q in disparity space and D = 65535 - Q in depth space.  A NaN pixel has D = 0.
+ *    This is step 1 of gp_lens_blur.
+ * 2. Shift of source column x for view k in eighths of a pixel: s = ((int64)(D - F) * g + 2^23) >> 24, an arithmetic shift, that is a floor,
+ *    then clamped to -max_s8 .. max_s8.  t_x = 8 x + s.  Rows are independent and shifts are horizontal only.
+ * 3. Surface: neighbours x and x + 1 of a row are CONNECTED iff |D_x - D_{x+1}| <= edge.  The pieces that can cover output column p, at
+ *    P = 8 p, are
+ *      the span of a connected pair with L = t_{x+1} - t_x > 0 and t_x <= P < t_{x+1}: with a = P - t_x the nearness
+ *        (D_x (L - a) + D_{x+1} a + (L >> 1)) / L and per channel the colour (c_x (L - a) + c_{x+1} a + (L >> 1)) / L, integer divisions,
+ *        everything below 2^27;
+ *      the left cap of x, t_x - 4 <= P < t_x, which exists iff x = 0 or (x - 1, x) is not connected;
+ *      the right cap of x, t_x <= P < t_x + 4, which exists iff x = W - 1 or (x, x + 1) is not connected; both caps carry D_x and c_x.
+ *    A connected pair with L <= 0 (a fold) covers nothing.  Pixels outside the image do not exist.
+ * 4. Visibility: among the pieces that cover p the largest nearness wins; ties go to the smallest x (no two pieces of one x cover one P).
+ * 5. Holes: a column that no piece covers is a disocclusion.  Let l and r be the nearest covered columns of the same output row to its left
+ *    and to its right, looked for within R = max_s8 / 4 + 1 columns.  The hole takes the colour and nearness of the one with the SMALLER
+ *    nearness -- the background continues behind the foreground --, l on a tie; the one that exists if only one does; colour 0 and nearness 0
+ *    if neither does, as in a row with nothing covered.
+ *    Why R: a hole opens where the surface is cut.  Between the right cap of source x, which ends at t_x + 4, and the left cap of source
+ *    x + 1, which begins at t_{x+1} - 4, lie s_{x+1} - s_x <= 2 max_s8 eighths, that is at most max_s8 / 4 columns; the same holds between a
+ *    border of the row and the cap of its first or last source, |s| <= max_s8 eighths away from where it came from.  Every connected stretch
+ *    of sources that moves forwards covers all it passes over.  So on a surface of planar pieces -- piecewise-planar rows of W = 1 .. 89 with
+ *    max_s8 0 .. 512 and every edge showed no exception -- each existing neighbour lies within R columns.  The bound is nevertheless part of
+ *    the DEFINITION and not only of the search: a row that alternates folds and cuts at sub-pixel phases (a left cap, a fold back by more
+ *    than a pixel, a right cap, each four eighths wide and between two sample positions) covers no column over any length, and there a
+ *    column further than R from everything covered takes colour 0 and nearness 0, on the host route as on the device.
+ * 6. Outputs: canvas uint8 [B][3][CH][CW] (not the image itself): view k writes the bytes of its cmask channels at (oy + y, ox + x); bytes no
+ *    view writes keep what they held.  holes uint8 [B][V][H][W] or NULL: 1 marks a disocclusion, for a user's own inpainting.  near uint16
+ *    [B][V][H][W] or NULL: the winning or copied nearness, the new view's own map (a disparity map for gp_lens_blur).
+ * The table of rectangles and channel masks expresses a pair ([3][H][2 W]), side by side, over / under, an anaglyph (both views at (0, 0),
+ * masks 1 and 6) and a quilt of ny x nx views in one call, with no copy afterwards.  F is DEVICE memory so that a convergence plane picked
+ * from the map needs no read-back; for the same reason it cannot be refused, and a value outside 0 .. 65535 is clamped.
+ * Two launches for any B and V: a warp pass (a workgroup stages 256 source columns of a row and the apron in LDS, bounds its search by the
+ * largest |s| of the staged region and gathers every view's columns) and a fill pass.  No atomics, nothing read back; an image's bytes are
+ * the same from call to call and in every batch.  workspace: DEVICE scratch of at least the workspace entry's byte count (the nearness-and-
+ * covered plane between the two passes), 8-byte aligned, free again once the stream has passed the call.
+ * GP_ERR_INVALID before any HIP call: null image / pred / conv / views / canvas / workspace, B < 1, B > 65535, V outside 1 .. 64, H, W, CH or
+ * CW outside 1 .. 16384, B * V * H * W >= 2^31, space outside 0 .. 1, edge outside 0 .. 65535, max_s8 outside 0 .. 512, |g| > 131072, cmask
+ * outside 1 .. 7, a rectangle that leaves the canvas, two rectangles that overlap and share a channel (a race), pred or conv not 4-byte
+ * aligned, near not 2-byte aligned, workspace not 8-byte aligned, workspace_bytes too small, canvas == image. */
+long long gp_stereo_views_workspace(int B, int V, int H, int W);  /* bytes; 0 for invalid sizes; proportional to B; multiple of 8 */
+gp_status gp_stereo_views(const unsigned char* image, const float* pred, const int* conv /* [B] */, const int* views /* HOST [V][4] */, int B,
+                          int V, int H, int W, int CH, int CW, int space, int edge, int max_s8, unsigned char* canvas,
+                          unsigned char* holes /* or NULL */, unsigned short* near /* or NULL */, void* workspace, long long workspace_bytes,
+                          void* stream);
 
 /* ---- test-time ensembling on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation, no atomics; csrc/ensemble.hip) ----
  * The tensor half of ensemble_depth (genpercept/util/ensemble.py:43-205, called at genpercept_pipeline.py:289-298) for the E members of each of

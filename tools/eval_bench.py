@@ -112,6 +112,18 @@
    counted twice, tested (what the kernel walks) and contributing (what the definition sums), and the vector-ALU instructions of the
    tested offsets over the time stand next to the issue rate of the card (one wave64 instruction per SIMD every 2 cycles).  `--no-host`
    skips the host route.
+
+  python tools/eval_bench.py --stereo --out profiles/<name>.json
+
+14. `--stereo` (instead of 1 and 2): the `gp_stereo_views` entry behind `engine.stereo_views` (stereo and parallax views, two launches) at
+   1 x 768 x 768 and 1 x 2048 x 3072 for `sbs` with two views and a 3 x 3 quilt, separation 32, depth space, the default edge and
+   convergence plane, on the scene of `--lens-blur` (a smooth map with noise and a depth edge down the middle) and a random image.  The
+   median of 25 consecutive calls, each between two device events, after 0.3 s of the same call as warm-up, for the C entry on
+   preallocated buffers and for `engine.stereo_views` itself, against `stereo.stereo_views` on the same arrays on the host (wall clock,
+   one run; compared on the spot, bit-equal).  The host route is timed at a size only while its rate per pixel and view at the size
+   before predicts a minute or less; otherwise the row says so.  The bytes the call has to move (image and map read once, every view's
+   three colour bytes written, the plane of four bytes written and read) over the device time stand in the row.  `--no-host` skips the
+   host route.
 Needs a GPU; there is no CPU fall-back."""
 import argparse
 import json
@@ -854,6 +866,65 @@ def bench_lens_blur(b, h, w, iters, host, host_budget_s=60.0, radius=16.0, timed
 
 LENS_HOST_S_PER_PIXEL = [0.0]   # the host route's rate at the last size it ran at, to decide whether the next size is timed
 
+STEREO_SHAPES = ((1, 768, 768), (1, 2048, 3072))
+STEREO_LAYOUTS = (("sbs", 2), ("quilt", (3, 3)))
+STEREO_HOST_S_PER_PIXEL_VIEW = [0.0]   # as above, per pixel and view
+
+
+def bench_stereo(b, h, w, host, host_budget_s=60.0, separation=32.0, timed=25):
+    """gp_stereo_views on preallocated buffers and engine.stereo_views itself for the layouts of STEREO_LAYOUTS at `separation`, depth space,
+    the default edge and convergence plane, on a scene (smooth map with noise and a depth edge down the middle) and a random image, against
+    stereo.stereo_views on the host.  The output bits are compared where the host runs."""
+    from genpercept_amd import engine as ge
+    from genpercept_amd import stereo as st
+    d = torch.device("cuda", 0)
+    lib = ge.load_library()
+    rng = np.random.default_rng(17)
+    image = rng.integers(0, 256, (b, 3, h, w), dtype=np.uint8)
+    pred = case(b, h, w, 17)[0]
+    pred[:, :, w // 2:] = np.clip(pred[:, :, w // 2:] + 0.2, 0, 1)
+    ti, tp = torch.from_numpy(image).to(d), torch.from_numpy(pred).to(d)
+    stream = int(torch.cuda.current_stream(d).cuda_stream)
+    res = dict(shape=[b, 3, h, w], options=dict(separation=separation, edge=st.EDGE_DEFAULT, converge=None, space="depth"), launches_per_call=2, timed_calls=timed,
+               statistic="median of `timed_calls` consecutive calls, each between two device events, after 0.3 s of the same call as warm-up", layouts={})
+    host_rate = 0.0
+    for layout, views in STEREO_LAYOUTS:
+        o = st.plan(b, h, w, layout, views, separation)
+        table, (ch, cw), v = o["table"], o["size"], int(o["table"].shape[0])
+        conv = torch.full((b,), st.F_DEFAULT, dtype=torch.int32, device=d)
+        canvas = torch.empty((b, 3, ch, cw), dtype=torch.uint8, device=d)
+        nbytes = lib.gp_stereo_views_workspace(b, v, h, w)
+        ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=d)
+
+        def entry():
+            rc = lib.gp_stereo_views(ti.data_ptr(), tp.data_ptr(), conv.data_ptr(), table.ctypes.data, b, v, h, w, ch, cw, 0, o["edge"], o["max_s8"],
+                                     canvas.data_ptr(), None, None, ws.data_ptr(), nbytes, stream)
+            assert rc == ge.GP_OK, rc
+
+        entry_runs = sorted(lens_timed_calls(entry, timed))
+        entry_ms = entry_runs[len(entry_runs) // 2]
+        call = lambda: ge.stereo_views(ti, tp, layout, views, separation)  # noqa: E731
+        call_ms = float(np.median(lens_timed_calls(call, timed)))
+        got, holes = (t.cpu().numpy() for t in ge.stereo_views(ti, tp, layout, views, separation, want_holes=True))
+        moved = b * h * w * (7 + v * (3 + 8))   # image 3 + map 4 read once; per view 3 colour bytes written, the plane written and read
+        row = dict(views=v, canvas=[ch, cw], max_s8=o["max_s8"], workspace_bytes=int(nbytes), gp_stereo_views_us_per_call=1e3 * entry_ms,
+                   gp_stereo_views_us_min_max=[1e3 * entry_runs[0], 1e3 * entry_runs[-1]], engine_stereo_views_us_per_call=1e3 * call_ms,
+                   hole_share=float(holes.mean()), bytes_moved=moved, gb_per_s=moved / entry_ms / 1e6)
+        predicted_s = STEREO_HOST_S_PER_PIXEL_VIEW[0] * h * w * v   # (0 at the first size)
+        if host and predicted_s <= host_budget_s:
+            t0 = time.perf_counter()
+            ref = st.stereo_views(image, pred[:, None], layout, views, separation)
+            host_ms = (time.perf_counter() - t0) * 1e3
+            assert got.dtype == ref.dtype and got.shape == ref.shape and np.array_equal(got, ref), layout
+            row.update(host_stereo_views_ms=host_ms, host_runs=1, host_over_engine_call=host_ms / call_ms, output_equals_host=True)
+            host_rate = max(host_rate, host_ms / 1e3 / (h * w * v))
+        elif host:
+            row["host"] = f"not timed at this size: about {predicted_s:.0f} s by the rate of the smaller size, above the budget of {host_budget_s:.0f} s"
+        res["layouts"][layout] = row
+    if host_rate:
+        STEREO_HOST_S_PER_PIXEL_VIEW[0] = host_rate
+    return res
+
 
 def bench_loop(n_images, batch_sizes, repeats):
     from PIL import Image
@@ -919,12 +990,19 @@ def main():
     ap.add_argument("--tiles", action="store_true", help="time gp_tile_merge / engine.tile_merge against tiled.tile_merge instead")
     ap.add_argument("--geometry", action="store_true", help="time gp_depth_geometry / engine.depth_geometry against geometry.depth_geometry instead")
     ap.add_argument("--lens-blur", action="store_true", help="time gp_lens_blur / engine.lens_blur against lens_blur.lens_blur instead")
+    ap.add_argument("--stereo", action="store_true", help="time gp_stereo_views / engine.stereo_views against stereo.stereo_views instead")
     ap.add_argument("--no-host", action="store_true",
-                    help="with --structure, --matting, --seg, --band, --foreground, --guided, --tiles, --geometry or --lens-blur: the device calls alone")
+                    help="with --structure, --matting, --seg, --band, --foreground, --guided, --tiles, --geometry, --lens-blur or --stereo: the device calls alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU")
-    if a.lens_blur:
+    if a.stereo:
+        import bench
+        with bench.ClockPowerSampler("cuda:0") as clock:
+            rows = [bench_stereo(*s, not a.no_host) for s in STEREO_SHAPES]
+        res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box", build_id=bench.source_build_id(), clock=clock.summary(),
+                   stereo=rows)
+    elif a.lens_blur:
         import bench
         with bench.ClockPowerSampler("cuda:0") as clock:
             rows = [bench_lens_blur(*s, a.iters, not a.no_host) for s in LENS_SHAPES]
@@ -997,7 +1075,7 @@ def main():
     else:
         res = dict(device=torch.cuda.get_device_name(0), eval_depth=[bench_eval(1, 4032, 6048, a.iters, 1), bench_eval(4, 480, 640, a.iters, 3)])
     if (not a.skip_loop and not a.normals and not a.masks and not a.structure and not a.matting and not a.seg and not a.band and not a.foreground
-            and not a.guided and not a.tiles and not a.geometry and not a.lens_blur):
+            and not a.guided and not a.tiles and not a.geometry and not a.lens_blur and not a.stereo):
         res["infer_and_evaluate"] = bench_loop(16, (1, 4), 3)
     text = json.dumps(res, indent=1)
     print(text)
