@@ -179,6 +179,8 @@ SYMBOLS = {
     "gp_lens_blur": (_i, [_vp] * 6 + [_i] * 5 + [_vp] * 3),
     "gp_stereo_views_workspace": (_ll, [_i] * 4),
     "gp_stereo_views": (_i, [_vp] * 4 + [_i] * 9 + [_vp] * 4 + [_ll, _vp]),
+    "gp_parallax_frames_workspace": (_ll, [_i] * 4),
+    "gp_parallax_frames": (_i, [_vp] * 4 + [_i] * 7 + [_vp] * 4 + [_ll, _vp]),
     "gp_ensemble_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gp_ensemble_workspace": (_ll, [_i, _i, _i, _i]),
     "gp_ensemble_reduce": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
@@ -1562,6 +1564,60 @@ def stereo_views(image: torch.Tensor, pred: torch.Tensor, layout="sbs", views=2,
             canvas.data_ptr(), _ptr(holes), _ptr(near), ws.data_ptr(), nbytes, _stream_ptr(dev))
     extra = ((holes,) if want_holes else ()) + ((near,) if want_near else ())
     return (canvas,) + extra if extra else canvas
+
+
+def parallax_frames(image: torch.Tensor, pred: torch.Tensor, path="orbit", frames: int = 16, amount: float = 16.0, push: float = 0.0,
+                    zoom: float = 1.0, pan: bool = False, focus=None, focus_at=None, edge=0.04, overscan: bool = True, frame_range=None,
+                    space: str = "depth", want_holes: bool = False, want_near: bool = False, out: Optional[torch.Tensor] = None):
+    """gp_parallax_frames on device tensors: the frames of a camera move from one photograph -- the "3-D photo".  image uint8 [B, 3, H, W]
+    ([3, H, W]: one image); pred float [B, 1, H, W] ([B, H, W] and [H, W] too), a depth or disparity map in [0, 1]; path "swing", "orbit"
+    or "dolly" with `frames` frames, `amount` (the parallax in pixels between the two ends of the nearness scale), and for the dolly `push`,
+    `zoom` and `pan`, or an explicit [V, 4] array of (shift_x, shift_y, push, zoom) per frame; at most one of focus (a value of the map in
+    [0, 1]) and focus_at (a pixel (u, v), read on the device) -- each one value or one per image --, the plane that stays put, the middle of
+    the scale with neither; edge, the fraction of the map's range beyond which neighbours are cut apart; overscan, which zooms each frame in
+    by its largest displacement so that no border shows; frame_range = (first, end), the frames of the path this call renders (at most 64;
+    all of them without it); space "depth" or "disparity"; out None or a contiguous uint8 [B, V, 3, H, W] tensor to write into.  Returns the
+    frames uint8 [B, V, 3, H, W] on the device, and with want_holes / want_near a tuple with holes uint8 [B, V, H, W] (1: a disocclusion)
+    and near int16 [B, V, H, W] (the bits of the uint16 nearness of the frame) after it.  Definition in include/genpercept_hip.h;
+    genpercept_amd/parallax.py gives the same bits and states the rule from these terms to the call's integers.  Allocates the workspace;
+    enqueued on the current stream, no synchronisation, nothing read back."""
+    from .parallax import plan
+    from .stereo import F_DEFAULT
+    image, pred = _images_u8(image, "image"), _float_maps(pred, "pred")
+    b, h, w = (int(v) for v in pred.shape)
+    dev = pred.device
+    _same_batch(image, (b, h, w), dev, "image")
+    if space not in SPACES:
+        raise ValueError(f"space is one of {SPACES}, got {space!r}")
+    _post_dims(b, h, w, "parallax frames")
+    o = plan(b, h, w, path, frames, amount, push, zoom, pan, focus, focus_at, edge, overscan, frame_range)
+    table, n_frames = o["table"], int(o["table"].shape[0])
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != (b, n_frames, 3, h, w) or out.device != dev
+                            or not out.is_contiguous()):
+        raise ValueError(f"out: a contiguous uint8 {(b, n_frames, 3, h, w)} tensor on {dev}, got {out.dtype if torch.is_tensor(out) else type(out)} "
+                         f"{tuple(out.shape) if torch.is_tensor(out) else ''}")
+    assert pred.is_cuda
+    if o["focus"] is None and o["focus_at"] is None:
+        plane = torch.full((b,), F_DEFAULT, dtype=torch.int32, device=dev)
+    else:
+        if o["focus"] is not None:
+            at = torch.from_numpy(o["focus"]).to(dev, non_blocking=True)
+        else:
+            u, v = o["focus_at"][:, 0], o["focus_at"][:, 1]
+            at = pred.view(b, h * w).gather(1, torch.from_numpy(v * w + u).to(dev, non_blocking=True)[:, None])[:, 0]
+        # the nearness of b values, the 16-bit rule in float32: plumbing on the device, so that a plane picked from the map is not read back
+        q = (at.clamp(0.0, 1.0) * 65535.0).nan_to_num(0.0).to(torch.int32)
+        plane = torch.where(at.isnan(), torch.zeros_like(q), q if space == "disparity" else 65535 - q).contiguous()
+    if out is None:
+        out = torch.empty((b, n_frames, 3, h, w), dtype=torch.uint8, device=dev)   # (every byte is written)
+    holes = torch.empty((b, n_frames, h, w), dtype=torch.uint8, device=dev) if want_holes else None
+    near = torch.empty((b, n_frames, h, w), dtype=torch.int16, device=dev) if want_near else None
+    ws, nbytes = _op_workspace("gp_parallax_frames", dev, b, n_frames, h, w)
+    _launch("gp_parallax_frames", f"images {(b, h, w)}, {n_frames} frames, space = {space}, edge = {o['edge']}, max_s8 = {o['max_s8']}",
+            image.data_ptr(), pred.data_ptr(), plane.data_ptr(), table.ctypes.data, b, n_frames, h, w, SPACES.index(space), o["edge"], o["max_s8"],
+            out.data_ptr(), _ptr(holes), _ptr(near), ws.data_ptr(), nbytes, _stream_ptr(dev))
+    extra = ((holes,) if want_holes else ()) + ((near,) if want_near else ())
+    return (out,) + extra if extra else out
 
 
 SEG_OUT = 8       # n, n_void, SEG_METRICS (out[2 .. 6]), n_classes; iou[K] follows

@@ -360,6 +360,55 @@ def run_stereo(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_dir
     return written
 
 
+def run_parallax(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_dir: str, name_mode: FileNameMode, mode: str = "depth",
+                 batch_size: int = 1, rank: int = 0, world: int = 1, path="orbit", frames: int = 16, amount: float = 16.0, push: float = 0.0,
+                 zoom: float = 1.0, pan: bool = False, focus=None, focus_at=None, edge=0.04, overscan: bool = True, animate: Optional[str] = None,
+                 frame_ms: int = 40, prefetch: int = 2, **inference_options) -> List[List[str]]:
+    """A camera move per sample with `engine.parallax_frames` under the sample's own prediction (modes depth and disparity): the frames as
+    numbered RGB files `<name>_0000.png`, `<name>_0001.png`, ... and, with animate="gif", one looping `<name>.gif` of them (PIL, `frame_ms`
+    per frame) after them.  The model runs once per batch; a path longer than the 64 frames of one call is rendered in parts under that
+    one map (`frame_range`).  amount, push, zoom, focus (a value of the map in [0, 1]) or focus_at (a pixel (u, v)) and edge are one value
+    each, used for every sample.  Batching, sharding and prefetch as `run_stereo`.  Returns the paths written, one list per sample.
+    inference_options go to `pipe.predict_batch_device`, `refine` and `tiles` among them."""
+    from . import engine as ge
+    from .parallax import MAX_FRAMES, camera_path, plan
+    from .stereo import stereo_options
+    if mode not in ("depth", "disparity"):
+        raise ValueError(f"a camera move needs a depth map: mode 'depth' or 'disparity', got {mode!r}")
+    if animate not in (None, "gif"):
+        raise ValueError(f"animate is None or 'gif', got {animate!r}")
+    if any(np.ndim(v) != 0 for v in (focus if focus is not None else 0.0, amount, push, zoom, edge)) or (focus_at is not None and np.shape(focus_at) != (2,)):
+        raise ValueError("amount, push, zoom, focus and edge are one value each and focus_at one pixel (u, v), used for every sample")
+    terms = (path, frames, amount, push, zoom, pan, focus, focus_at, edge, overscan)
+    stereo_options(1, focus, focus_at, edge)
+    n_path = len(camera_path(path, frames, amount, push, zoom, pan))      # (the terms that need no image size are checked before any is read)
+    if world > 1:
+        lo, hi = _shard(len(samples), rank, world)
+        samples = samples[lo:hi]
+    written = []
+    for group in _size_groups(_decode_ahead(samples, lambda s: _load_rgb(base_dir, s[0], None), prefetch), max(1, batch_size)):
+        rgb, pred = pipe._post_inputs([img for _, img in group], mode, ("depth", "disparity"), "a camera move", "a depth map", inference_options,
+                                      lambda images: plan(int(images.shape[0]), int(images.shape[-2]), int(images.shape[-1]), *terms,
+                                                          (0, min(n_path, MAX_FRAMES))))
+        parts = [ge.parallax_frames(rgb, pred, *terms, (first, min(first + MAX_FRAMES, n_path)), space=mode).cpu().numpy()
+                 for first in range(0, n_path, MAX_FRAMES)]
+        out = np.concatenate(parts, 1)
+        assert len(out) == len(group) and out.shape[1] == n_path
+        for (smp, _), clip in zip(group, out):
+            scene_dir = os.path.join(output_dir, os.path.dirname(smp[0]))
+            os.makedirs(scene_dir, exist_ok=True)
+            stem = os.path.splitext(get_pred_name(os.path.basename(smp[0]), name_mode, suffix=".png"))[0]
+            stills = [Image.fromarray(np.ascontiguousarray(np.moveaxis(px, 0, -1))) for px in clip]
+            paths = [os.path.join(scene_dir, f"{stem}_{k:04d}.png") for k in range(n_path)]
+            for still, save_to in zip(stills, paths):
+                still.save(save_to)
+            if animate == "gif":
+                paths.append(os.path.join(scene_dir, stem + ".gif"))
+                stills[0].save(paths[-1], save_all=True, append_images=stills[1:], duration=int(frame_ms), loop=0)
+            written.append(paths)
+    return written
+
+
 def _write_metric_files(output_dir: str, tag: str, names: List[str], per_sample, result: Dict[str, float], header: str) -> None:
     """`per_sample_metrics<tag>.csv` (one row per prediction file) and `eval_metrics<tag>.txt` (header, metric names, means)."""
     os.makedirs(output_dir, exist_ok=True)

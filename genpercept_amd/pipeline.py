@@ -740,6 +740,35 @@ class GenPerceptPipeline:
         """`stereo_batch_device` for one PIL image: the canvas of the layout as a PIL image."""
         return _chw_to_pil(self.stereo_batch_device([image], mode, layout, views, separation, converge, converge_at, edge, **inference_options)[0])
 
+    @torch.no_grad()
+    def parallax_batch_device(self, images: Union[Sequence[Image.Image], torch.Tensor], mode: str = "depth", path="orbit", frames: int = 16,
+                              amount: float = 16.0, push: float = 0.0, zoom: float = 1.0, pan: bool = False, focus=None, focus_at=None, edge=0.04,
+                              overscan: bool = True, frame_range=None, **inference_options) -> torch.Tensor:
+        """The "3-D photo" without a trip to the host: images of one common size (PIL images or a uint8 [B,3,H,W] tensor) -> the frames of
+        a camera move, uint8 [B,V,3,H,W] ON THE DEVICE: `engine.parallax_frames` (gp_parallax_frames) applied under the map of
+        `predict_batch_device(images, mode, **inference_options)` at the input size, which never leaves the GPU.  mode: depth or disparity
+        (the space the map is read in).  path: "swing", "orbit" or "dolly" with `frames` frames and `amount`, the parallax in pixels between
+        the two ends of the nearness scale (for the dolly `push`, `zoom` and `pan` too), or an explicit [V,4] array of (shift_x, shift_y,
+        push, zoom) per frame; a displacement of more than 32 pixels is refused; at most one of focus (a value of the map in [0, 1]) and
+        focus_at (a pixel (u, v), whose value is read on the device), the plane that stays put -- the middle of the scale with neither; edge:
+        the fraction of the map's range beyond which neighbours are cut apart; overscan zooms each frame in so that no border shows;
+        frame_range = (first, end) renders those frames of the path (at most 64 in one call).  inference_options may hold `refine` and
+        `tiles` as in `stereo_batch_device`."""
+        from . import engine as ge
+        from .parallax import plan
+        rgb, pred = self._post_inputs(images, mode, ("depth", "disparity"), "a camera move", "a depth map", inference_options,
+                                      lambda images: plan(int(images.shape[0]), int(images.shape[-2]), int(images.shape[-1]), path, frames, amount, push,
+                                                          zoom, pan, focus, focus_at, edge, overscan, frame_range))
+        return ge.parallax_frames(rgb, pred, path, frames, amount, push, zoom, pan, focus, focus_at, edge, overscan, frame_range, space=mode)
+
+    def parallax(self, image: Image.Image, mode: str = "depth", path="orbit", frames: int = 16, amount: float = 16.0, push: float = 0.0,
+                 zoom: float = 1.0, pan: bool = False, focus=None, focus_at=None, edge=0.04, overscan: bool = True, frame_range=None,
+                 **inference_options) -> List[Image.Image]:
+        """`parallax_batch_device` for one PIL image: the frames as a list of PIL images."""
+        out = self.parallax_batch_device([image], mode, path, frames, amount, push, zoom, pan, focus, focus_at, edge, overscan, frame_range,
+                                         **inference_options)[0]
+        return [_chw_to_pil(frame) for frame in out]
+
     def _run_device(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None, refine=None,
                     tiles=None) -> List[GenPerceptOutput]:
         """Pre / post processing on the GPU (gp_preprocess / gp_postprocess): the image goes up once, resize_max_res, the model, the

@@ -38,6 +38,8 @@
  *                       occlusion-aware disc gather in integer arithmetic
  *   gp_stereo_views   (no reference code) stereo pairs, anaglyphs and quilts from a depth or disparity prediction: a forward warp of every
  *                       row, cut at depth edges, nearest surface first, disocclusions filled from the background side
+ *   gp_parallax_frames (no reference code) the frames of a camera move -- orbit, swing, dolly -- from one photograph and its depth or
+ *                       disparity prediction: a forward warp of a triangle mesh cut at depth edges, with a z-test
  *   gp_ensemble_gather, gp_ensemble_reduce
  *                     ensemble_depth's tensor half (the BFGS fit stays on the host)   genpercept/util/ensemble.py:43-205;
  *                                                                   genpercept_pipeline.py:289-298
@@ -721,6 +723,58 @@ gp_status gp_stereo_views(const unsigned char* image, const float* pred, const i
                           int V, int H, int W, int CH, int CW, int space, int edge, int max_s8, unsigned char* canvas,
                           unsigned char* holes /* or NULL */, unsigned short* near /* or NULL */, void* workspace, long long workspace_bytes,
                           void* stream);
+
+/* ---- camera moves from one photograph: the frames of a "3-D photo" (DEVICE pointers but the frame table; stateless, stream-ordered, no host synchronisation, no global atomics; csrc/parallax.hip) ----
+ * The best-known use of a monocular depth map: a short clip in which the camera orbits, swings or pushes into a single still (the 3-D Ken
+ * Burns effect).  gp_stereo_views stops at shifts along a row; this entry has parallax in both directions, a zoom per frame, a
+ * depth-dependent magnification for the dolly, and a 2-D surface: a triangle mesh over the pixel grid, cut at depth edges, with a z-test.
+ * With framework ops this is a grid_sample by the flow, a BACKWARD warp that smears the subject across every depth edge, which is where the
+ * eye looks in a moving clip.  The whole definition is integer arithmetic, so the result does not depend on the order of evaluation and the
+ * device equals the host route genpercept_amd/parallax.py bit for bit; the arithmetic stands once more in csrc/parallax_math.h.
+ * Inputs per image: image uint8 [3][H][W]; pred fp32 [1][H][W]; one int32 F of focus [B], the nearness of the plane that stays put.  Per call:
+ *   space = 0 (depth) or 1 (disparity); edge 0 .. 65535; max_s8 0 .. 256, a displacement of at most 32 pixels in eighths of a pixel, which
+ *   sizes the staged sources; a HOST table frames int32 [V][4] = (gx, gy, gz, Z) per frame, 1 <= V <= 64, |gx|, |gy| <= 2^17, |gz| <= 2^24,
+ *   Z in 65536 .. 131072, a zoom of 1 x to 2 x in units of 1 / 65536.  1 <= H, W <= 16384 and B * V * H * W < 2^31.
+ *   Why 32 pixels: a 32 x 32 output tile under displacements of up to A pixels can be reached from (32 + 2 A + 4)^2 sources, 100 x 100 at
+ *   A = 32; at 12 bytes each that is 117 KiB, and with the 8 KiB z-buffer it fits the 160 KiB of LDS of a compute unit.  A = 64 does not.
+ * 1. Nearness: Q = (uint16)(clamp(pred, 0, 1) * 65535.0f); D = Q in disparity space and D = 65535 - Q in depth space.  A NaN pixel has D = 0.
+ *    This is step 1 of gp_stereo_views.
+ * 2. Position of source (x, y) in a frame, in eighths of a pixel, with 64-bit intermediates and arithmetic shifts, that is floors:
+ *      Cx = 4 (W - 1), Cy = 4 (H - 1); rx = 8 x - Cx, ry = 8 y - Cy; e = D - F; dz = (e gz + 2^23) >> 24;
+ *      dx = ((e gx + 2^23) >> 24) + ((rx dz + 2^15) >> 16), clamped to -max_s8 .. max_s8; dy likewise with gy and ry;
+ *      tx = Cx + ((rx Z + 2^15) >> 16) + dx; ty = Cy + ((ry Z + 2^15) >> 16) + dy.
+ *    Z + dz is the magnification of a pixel: a camera pushed forward magnifies near things more.
+ * 3. Pieces.  Two pixels are CONNECTED iff |D_a - D_b| <= edge.  Output pixel (p, q) sits at P = (8 p, 8 q).
+ *      Cap: every source has one, the square tx - h <= Px < tx + h, ty - h <= Py < ty + h with h = (4 Z + 65535) >> 16.  It carries D and c
+ *        of the source and has the piece id 3 (y W + x).
+ *      Triangles: each quad with x + 1 < W and y + 1 < H gives T0 = (x, y), (x + 1, y), (x, y + 1) with id 3 (y W + x) + 1 and
+ *        T1 = (x + 1, y), (x + 1, y + 1), (x, y + 1) with id 3 (y W + x) + 2.  A triangle exists iff its three vertex pairs are all
+ *        connected.  With the vertices a, b, c in that order A = (b - a) x (c - a); a triangle with A <= 0 covers nothing: it is folded.
+ *        wa = (c - b) x (P - b), wb = (a - c) x (P - c), wc = A - wa - wb; the triangle covers P iff all three are >= 0.  The nearness there
+ *        is (wa D_a + wb D_b + wc D_c + (A >> 1)) / A and each colour channel likewise, integer divisions.
+ * 4. Visibility: the piece with the largest nearness wins; on a tie the smallest piece id.
+ * 5. Holes: a pixel that nothing covers looks outwards along its row and its column and takes the nearest covered pixel in each of the four
+ *    directions within R = max_s8 / 4 + 1.  Of those it takes the one with the SMALLEST nearness -- the background continues behind the
+ *    subject --, ties in the order left, right, up, down, and copies that pixel's colour and nearness; colour 0 and nearness 0 where none
+ *    exists.  R is part of the definition, as in gp_stereo_views.
+ * 6. Outputs: out uint8 [B][V][3][H][W] (not the image itself); holes uint8 [B][V][H][W] or NULL: 1 marks a disocclusion; near uint16
+ *    [B][V][H][W] or NULL: the winning or copied nearness, the frame's own map.
+ * F is DEVICE memory so that a plane picked from the map needs no read-back; for the same reason it cannot be refused, and a value outside
+ * 0 .. 65535 is clamped.  How a swing, an orbit or a dolly becomes rows of the table is the host's business (parallax.py: camera_path, plan).
+ * Two launches for any B and V: a warp pass (a workgroup per 32 x 32 output pixels of a frame stages the sources that can reach the tile in
+ * LDS and rasterises their caps and triangles into a z-buffer in LDS by a 64-bit LDS atomic maximum on a packed key -- nearness, inverted
+ * piece id, colours --, which is step 4 whatever the order) and a fill pass.  No global atomics, nothing read back; an image's bytes are the
+ * same from call to call and in every batch.  workspace: DEVICE scratch of at least the workspace entry's byte count (the
+ * nearness-and-covered plane between the two passes), 8-byte aligned, free again once the stream has passed the call.
+ * GP_ERR_INVALID before any HIP call: null image / pred / focus / frames / out / workspace, B < 1, B > 65535, V outside 1 .. 64, H or W
+ * outside 1 .. 16384, B * V * H * W >= 2^31, space outside 0 .. 1, edge outside 0 .. 65535, max_s8 outside 0 .. 256, |gx| or |gy| > 2^17,
+ * |gz| > 2^24, Z outside 65536 .. 131072, pred or focus not 4-byte aligned, near not 2-byte aligned, workspace not 8-byte aligned,
+ * workspace_bytes too small, out == image. */
+long long gp_parallax_frames_workspace(int B, int V, int H, int W);  /* bytes; 0 for invalid sizes; proportional to B; multiple of 8 */
+gp_status gp_parallax_frames(const unsigned char* image, const float* pred, const int* focus /* [B] */, const int* frames /* HOST [V][4] */,
+                             int B, int V, int H, int W, int space, int edge, int max_s8, unsigned char* out,
+                             unsigned char* holes /* or NULL */, unsigned short* near /* or NULL */, void* workspace,
+                             long long workspace_bytes, void* stream);
 
 /* ---- test-time ensembling on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation, no atomics; csrc/ensemble.hip) ----
  * The tensor half of ensemble_depth (genpercept/util/ensemble.py:43-205, called at genpercept_pipeline.py:289-298) for the E members of each of

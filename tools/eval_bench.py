@@ -124,6 +124,16 @@
    before predicts a minute or less; otherwise the row says so.  The bytes the call has to move (image and map read once, every view's
    three colour bytes written, the plane of four bytes written and read) over the device time stand in the row.  `--no-host` skips the
    host route.
+  python tools/eval_bench.py --parallax --out profiles/<name>.json
+
+15. `--parallax` (instead of 1 and 2): the `gp_parallax_frames` entry behind `engine.parallax_frames` (camera moves from one photograph,
+   two launches) at 1 x 768 x 768 and 1 x 2048 x 3072 for a 16-frame orbit with amount 16 and a 16-frame dolly to 1.25 x (push 0.02),
+   depth space, the default edge and plane, with overscan, on the scene and image of `--stereo`.  The median of 25 consecutive calls, each
+   between two device events, after 0.3 s of the same call as warm-up, for the C entry on preallocated buffers and for
+   `engine.parallax_frames` itself, against `parallax.parallax_frames` on the host for the first two frames of the path (wall clock, one
+   run; compared on the spot, bit-equal; timed at a size only while the rate at the size before predicts a minute or less).  In the same
+   run the `gp_stereo_views` side-by-side pair at separation 16 on the same arrays, so that a frame's time stands next to a view's.
+   `--no-host` skips the host route.
 Needs a GPU; there is no CPU fall-back."""
 import argparse
 import json
@@ -926,6 +936,84 @@ def bench_stereo(b, h, w, host, host_budget_s=60.0, separation=32.0, timed=25):
     return res
 
 
+PARALLAX_SHAPES = STEREO_SHAPES
+PARALLAX_PATHS = (("orbit", dict(path="orbit", frames=16, amount=16.0)), ("dolly", dict(path="dolly", frames=16, push=0.02, zoom=1.25)))
+PARALLAX_HOST_FRAMES = 2                 # the host route renders the first frames of a path only
+PARALLAX_HOST_S_PER_PIXEL_FRAME = [0.0]  # as above, per pixel and frame
+
+
+def bench_parallax(b, h, w, host, host_budget_s=60.0, timed=25):
+    """gp_parallax_frames on preallocated buffers and engine.parallax_frames itself for the paths of PARALLAX_PATHS, depth space, the default
+    edge and plane, with overscan, on the scene and image of bench_stereo, against parallax.parallax_frames on the host (its first
+    PARALLAX_HOST_FRAMES frames); next to them gp_stereo_views for a side-by-side pair at separation 16 on the same arrays in the same run."""
+    from genpercept_amd import engine as ge
+    from genpercept_amd import parallax as pv
+    from genpercept_amd import stereo as st
+    d = torch.device("cuda", 0)
+    lib = ge.load_library()
+    rng = np.random.default_rng(17)
+    image = rng.integers(0, 256, (b, 3, h, w), dtype=np.uint8)
+    pred = case(b, h, w, 17)[0]
+    pred[:, :, w // 2:] = np.clip(pred[:, :, w // 2:] + 0.2, 0, 1)
+    ti, tp = torch.from_numpy(image).to(d), torch.from_numpy(pred).to(d)
+    stream = int(torch.cuda.current_stream(d).cuda_stream)
+    plane = torch.full((b,), st.F_DEFAULT, dtype=torch.int32, device=d)
+    res = dict(shape=[b, 3, h, w], options=dict(edge=st.EDGE_DEFAULT, focus=None, space="depth", overscan=True), launches_per_call=2, timed_calls=timed,
+               statistic="median of `timed_calls` consecutive calls, each between two device events, after 0.3 s of the same call as warm-up", paths={})
+
+    so = st.plan(b, h, w, "sbs", 2, 16.0)
+    canvas = torch.empty((b, 3) + tuple(so["size"]), dtype=torch.uint8, device=d)
+    sbytes = lib.gp_stereo_views_workspace(b, 2, h, w)
+    sws = torch.empty((sbytes // 8,), dtype=torch.int64, device=d)
+
+    def stereo_entry():
+        rc = lib.gp_stereo_views(ti.data_ptr(), tp.data_ptr(), plane.data_ptr(), so["table"].ctypes.data, b, 2, h, w, so["size"][0], so["size"][1], 0, so["edge"],
+                                 so["max_s8"], canvas.data_ptr(), None, None, sws.data_ptr(), sbytes, stream)
+        assert rc == ge.GP_OK, rc
+
+    stereo_ms = float(np.median(lens_timed_calls(stereo_entry, timed)))
+    res["stereo_sbs_separation_16"] = dict(gp_stereo_views_us_per_call=1e3 * stereo_ms, us_per_view=1e3 * stereo_ms / 2, max_s8=so["max_s8"])
+    host_rate = 0.0
+    for name, kw in PARALLAX_PATHS:
+        o = pv.plan(b, h, w, **kw)
+        table, v = o["table"], int(o["table"].shape[0])
+        out = torch.empty((b, v, 3, h, w), dtype=torch.uint8, device=d)
+        nbytes = lib.gp_parallax_frames_workspace(b, v, h, w)
+        ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=d)
+
+        def entry():
+            rc = lib.gp_parallax_frames(ti.data_ptr(), tp.data_ptr(), plane.data_ptr(), table.ctypes.data, b, v, h, w, 0, o["edge"], o["max_s8"],
+                                        out.data_ptr(), None, None, ws.data_ptr(), nbytes, stream)
+            assert rc == ge.GP_OK, rc
+
+        entry_runs = sorted(lens_timed_calls(entry, timed))
+        entry_ms = entry_runs[len(entry_runs) // 2]
+        call = lambda: ge.parallax_frames(ti, tp, **kw)  # noqa: E731
+        call_ms = float(np.median(lens_timed_calls(call, timed)))
+        got, holes = (t.cpu().numpy() for t in ge.parallax_frames(ti, tp, want_holes=True, **kw))
+        us_per_frame = 1e3 * entry_ms / v
+        row = dict(frames=v, max_s8=o["max_s8"], zoom_first_last=[int(table[0, 3]), int(table[-1, 3])], workspace_bytes=int(nbytes),
+                   gp_parallax_frames_us_per_call=1e3 * entry_ms, gp_parallax_frames_us_min_max=[1e3 * entry_runs[0], 1e3 * entry_runs[-1]],
+                   us_per_frame=us_per_frame, frame_over_stereo_view=us_per_frame / (1e3 * stereo_ms / 2), engine_parallax_frames_us_per_call=1e3 * call_ms,
+                   hole_share=float(holes.mean()))
+        n_host = min(PARALLAX_HOST_FRAMES, v)
+        predicted_s = PARALLAX_HOST_S_PER_PIXEL_FRAME[0] * h * w * n_host   # (0 at the first size)
+        if host and predicted_s <= host_budget_s:
+            t0 = time.perf_counter()
+            ref = pv.parallax_frames(image, pred[:, None], frame_range=(0, n_host), **kw)
+            host_ms = (time.perf_counter() - t0) * 1e3
+            assert got.dtype == ref.dtype and np.array_equal(got[:, :n_host], ref), name
+            row.update(host_parallax_frames_ms=host_ms, host_frames=n_host, host_runs=1, host_ms_per_frame=host_ms / n_host,
+                       host_frame_over_device_frame=host_ms / n_host / (entry_ms / v), output_equals_host=True)
+            host_rate = max(host_rate, host_ms / 1e3 / (h * w * n_host))
+        elif host:
+            row["host"] = f"not timed at this size: about {predicted_s:.0f} s by the rate of the smaller size, above the budget of {host_budget_s:.0f} s"
+        res["paths"][name] = row
+    if host_rate:
+        PARALLAX_HOST_S_PER_PIXEL_FRAME[0] = host_rate
+    return res
+
+
 def bench_loop(n_images, batch_sizes, repeats):
     from PIL import Image
     from genpercept_amd import GenPerceptPipeline
@@ -991,12 +1079,20 @@ def main():
     ap.add_argument("--geometry", action="store_true", help="time gp_depth_geometry / engine.depth_geometry against geometry.depth_geometry instead")
     ap.add_argument("--lens-blur", action="store_true", help="time gp_lens_blur / engine.lens_blur against lens_blur.lens_blur instead")
     ap.add_argument("--stereo", action="store_true", help="time gp_stereo_views / engine.stereo_views against stereo.stereo_views instead")
+    ap.add_argument("--parallax", action="store_true", help="time gp_parallax_frames / engine.parallax_frames against parallax.parallax_frames instead")
     ap.add_argument("--no-host", action="store_true",
-                    help="with --structure, --matting, --seg, --band, --foreground, --guided, --tiles, --geometry, --lens-blur or --stereo: the device calls alone")
+                    help="with --structure, --matting, --seg, --band, --foreground, --guided, --tiles, --geometry, --lens-blur, --stereo or --parallax: the device "
+                         "calls alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU")
-    if a.stereo:
+    if a.parallax:
+        import bench
+        with bench.ClockPowerSampler("cuda:0") as clock:
+            rows = [bench_parallax(*s, not a.no_host) for s in PARALLAX_SHAPES]
+        res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box", build_id=bench.source_build_id(), clock=clock.summary(),
+                   parallax=rows)
+    elif a.stereo:
         import bench
         with bench.ClockPowerSampler("cuda:0") as clock:
             rows = [bench_stereo(*s, not a.no_host) for s in STEREO_SHAPES]
@@ -1075,7 +1171,7 @@ def main():
     else:
         res = dict(device=torch.cuda.get_device_name(0), eval_depth=[bench_eval(1, 4032, 6048, a.iters, 1), bench_eval(4, 480, 640, a.iters, 3)])
     if (not a.skip_loop and not a.normals and not a.masks and not a.structure and not a.matting and not a.seg and not a.band and not a.foreground
-            and not a.guided and not a.tiles and not a.geometry and not a.lens_blur and not a.stereo):
+            and not a.guided and not a.tiles and not a.geometry and not a.lens_blur and not a.stereo and not a.parallax):
         res["infer_and_evaluate"] = bench_loop(16, (1, 4), 3)
     text = json.dumps(res, indent=1)
     print(text)
