@@ -12,7 +12,7 @@ import torch
 
 from .eval_metrics import (BAND_METRIC, BAND_PLANES, BOUNDARY_METRICS, MASK_METRICS, MATTING_METRICS, SEG_MAX_K, SEG_METRICS,  # noqa: F401
                            STRUCTURE_METRICS, TRIMAP_METRICS)  # the names of the evaluators' values: one list each, stated in eval_metrics
-from .post_common import MAX_DIM, SPACES
+from .post_common import F_DEFAULT, MAX_DIM, SPACES, _pixel_inside, _with_planes
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # One library per 16-bit element type (csrc/common.h): identical C-ABI, bf16 or IEEE fp16 activations / weights / MFMA operands.
@@ -1033,6 +1033,52 @@ def _launch(name: str, describe: str, *args) -> None:
     _c_check(st, name)
 
 
+# ---- what the ops that render a photograph under one plane of its map (lens_blur, stereo_views, parallax_frames) share ---------------------------
+def _image_and_maps(image, pred, space: str, what: str):
+    """The opening of the three bindings: (image uint8 [B, 3, H, W], pred float32 [B, H, W], (B, H, W), their device), checked -- one map per
+    image, same size, same device, a known space, the range of `_post_dims`."""
+    image, pred = _images_u8(image, "image"), _float_maps(pred, "pred")
+    shape = tuple(int(v) for v in pred.shape)
+    _same_batch(image, shape, pred.device, "image")
+    if space not in SPACES:
+        raise ValueError(f"space is one of {SPACES}, got {space!r}")
+    _post_dims(*shape, what)
+    return image, pred, shape, pred.device
+
+
+def _nearness_plane(pred: torch.Tensor, value, at, space: str, default: Optional[int] = None) -> torch.Tensor:
+    """The plane of every image as its nearness, int32 [B] on the maps' device: of `value` (host float32 [B]), of the pixels `at` (host
+    int64 [B, 2] = (u, v)) of the maps pred [B, H, W], or `default` with neither.  The 16-bit rule in float32 (`post_common.nearness`):
+    plumbing on the device, so that a plane picked from the map is not read back."""
+    b, h, w = pred.shape
+    if value is None and at is None:
+        return torch.full((b,), default, dtype=torch.int32, device=pred.device)
+    if value is not None:
+        v = torch.from_numpy(value).to(pred.device, non_blocking=True)
+    else:
+        v = pred.view(b, h * w).gather(1, torch.from_numpy(at[:, 1] * w + at[:, 0]).to(pred.device, non_blocking=True)[:, None])[:, 0]
+    q = (v.clamp(0.0, 1.0) * 65535.0).nan_to_num(0.0).to(torch.int32)
+    return torch.where(v.isnan(), torch.zeros_like(q), q if space == "disparity" else 65535 - q).contiguous()
+
+
+def _output_u8(out, name: str, shape, device) -> torch.Tensor:
+    """The output a caller supplies, checked -- a contiguous uint8 tensor of `shape` on `device` --, or with None a new one."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+    if not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or out.device != device or not out.is_contiguous():
+        raise ValueError(f"{name}: a contiguous uint8 {tuple(shape)} tensor on {device}, got {out.dtype if torch.is_tensor(out) else type(out)} "
+                         f"{tuple(out.shape) if torch.is_tensor(out) else ''}")
+    return out
+
+
+def _warp_planes(out: torch.Tensor, shape, want_holes: bool, want_near: bool):
+    """The planes a warp writes next to `out`, where wanted: (holes uint8 `shape` or None, near int16 `shape` or None, what the binding
+    returns -- `out` alone or a tuple with the wanted planes after it)."""
+    holes = torch.empty(shape, dtype=torch.uint8, device=out.device) if want_holes else None
+    near = torch.empty(shape, dtype=torch.int16, device=out.device) if want_near else None
+    return holes, near, _with_planes(out, holes, near, want_holes, want_near)
+
+
 def eval_depth_raw(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, alignment: Optional[str] = "least_square",
                    alignment_max_res: Optional[int] = None, min_depth: float = 1e-3, max_depth: float = 10.0) -> torch.Tensor:
     """gp_eval_depth on device tensors: float64 [B, 14] ON THE DEVICE = s, t, n_valid, n_fit, then the ten metrics in eval_metrics.METRICS
@@ -1482,29 +1528,15 @@ def lens_blur(image: torch.Tensor, pred: torch.Tensor, focus=None, focus_at=None
     circle of confusion in eighths of a pixel, int16 [B, H, W] (0 .. 256).  Definition in include/genpercept_hip.h;
     genpercept_amd/lens_blur.py gives the same bits.  Enqueued on the current stream, no synchronisation, nothing read back."""
     from .lens_blur import lens_blur_options
-    image, pred = _images_u8(image, "image"), _float_maps(pred, "pred")
-    b, h, w = (int(v) for v in pred.shape)
-    dev = pred.device
-    _same_batch(image, (b, h, w), dev, "image")
-    if space not in SPACES:
-        raise ValueError(f"space is one of {SPACES}, got {space!r}")
-    _post_dims(b, h, w, "lens blur")
+    image, pred, (b, h, w), dev = _image_and_maps(image, pred, space, "lens blur")
     o = lens_blur_options(b, focus, focus_at, aperture, max_radius, dof)
+    _pixel_inside(o["focus_at"], "focus_at", h, w)
     assert pred.is_cuda
     if sharp is not None:
         sharp = _mask_u8(sharp, "sharp", (b, h, w))
     to_lin, from_lin = _lens_tables(tables, dev)
     host = np.stack([np.zeros(b, np.int64), o["gain"], o["cmax8"], o["dz"]], 1).astype(np.int32)
-    if o["focus"] is not None:
-        at = torch.from_numpy(o["focus"]).to(dev, non_blocking=True)
-    else:
-        u, v = o["focus_at"][:, 0], o["focus_at"][:, 1]
-        if (u >= w).any() or (v >= h).any():
-            raise ValueError(f"focus_at = (u, v) lies inside the {w} x {h} image, got {o['focus_at'].tolist()}")
-        at = pred.view(b, h * w).gather(1, torch.from_numpy(v * w + u).to(dev, non_blocking=True)[:, None])[:, 0]
-    # the nearness of b values, the 16-bit rule in float32: plumbing on the device, so that a focus picked from the map is not read back
-    q = (at.clamp(0.0, 1.0) * 65535.0).nan_to_num(0.0).to(torch.int32)
-    near = torch.where(at.isnan(), torch.zeros_like(q), q if space == "disparity" else 65535 - q)
+    near = _nearness_plane(pred, o["focus"], o["focus_at"], space)
     params = torch.from_numpy(host).to(dev, non_blocking=True)
     params[:, 0] = near
     out = torch.empty((b, 3, h, w), dtype=torch.uint8, device=dev)
@@ -1528,42 +1560,19 @@ def stereo_views(image: torch.Tensor, pred: torch.Tensor, layout="sbs", views=2,
     [B, V, H, W] (1: a disocclusion) and near int16 [B, V, H, W] (the bits of the uint16 nearness of the new view) after it.  Definition in
     include/genpercept_hip.h; genpercept_amd/stereo.py gives the same bits and states the rule from these terms to the call's integers.
     Allocates the workspace; enqueued on the current stream, no synchronisation, nothing read back."""
-    from .stereo import F_DEFAULT, plan
-    image, pred = _images_u8(image, "image"), _float_maps(pred, "pred")
-    b, h, w = (int(v) for v in pred.shape)
-    dev = pred.device
-    _same_batch(image, (b, h, w), dev, "image")
-    if space not in SPACES:
-        raise ValueError(f"space is one of {SPACES}, got {space!r}")
-    _post_dims(b, h, w, "stereo views")
+    from .stereo import plan
+    image, pred, (b, h, w), dev = _image_and_maps(image, pred, space, "stereo views")
     o = plan(b, h, w, layout, views, separation, converge, converge_at, edge)
     table, (ch, cw), n_views = o["table"], o["size"], int(o["table"].shape[0])
-    if canvas is not None and (not torch.is_tensor(canvas) or canvas.dtype != torch.uint8 or tuple(canvas.shape) != (b, 3, ch, cw) or canvas.device != dev
-                               or not canvas.is_contiguous()):
-        raise ValueError(f"canvas: a contiguous uint8 {(b, 3, ch, cw)} tensor on {dev}, got {canvas.dtype if torch.is_tensor(canvas) else type(canvas)} "
-                         f"{tuple(canvas.shape) if torch.is_tensor(canvas) else ''}")
+    canvas = _output_u8(canvas, "canvas", (b, 3, ch, cw), dev)   # (a new one holds no bytes to keep: the views of every layout cover it)
     assert pred.is_cuda
-    if o["converge"] is None and o["converge_at"] is None:
-        conv = torch.full((b,), F_DEFAULT, dtype=torch.int32, device=dev)
-    else:
-        if o["converge"] is not None:
-            at = torch.from_numpy(o["converge"]).to(dev, non_blocking=True)
-        else:
-            u, v = o["converge_at"][:, 0], o["converge_at"][:, 1]
-            at = pred.view(b, h * w).gather(1, torch.from_numpy(v * w + u).to(dev, non_blocking=True)[:, None])[:, 0]
-        # the nearness of b values, the 16-bit rule in float32: plumbing on the device, so that a plane picked from the map is not read back
-        q = (at.clamp(0.0, 1.0) * 65535.0).nan_to_num(0.0).to(torch.int32)
-        conv = torch.where(at.isnan(), torch.zeros_like(q), q if space == "disparity" else 65535 - q).contiguous()
-    if canvas is None:
-        canvas = torch.empty((b, 3, ch, cw), dtype=torch.uint8, device=dev)   # (the views of every layout cover it)
-    holes = torch.empty((b, n_views, h, w), dtype=torch.uint8, device=dev) if want_holes else None
-    near = torch.empty((b, n_views, h, w), dtype=torch.int16, device=dev) if want_near else None
+    conv = _nearness_plane(pred, o["converge"], o["converge_at"], space, F_DEFAULT)
+    holes, near, result = _warp_planes(canvas, (b, n_views, h, w), want_holes, want_near)
     ws, nbytes = _op_workspace("gp_stereo_views", dev, b, n_views, h, w)
     _launch("gp_stereo_views", f"images {(b, h, w)}, {n_views} views in a canvas of {(ch, cw)}, space = {space}, edge = {o['edge']}, max_s8 = {o['max_s8']}",
             image.data_ptr(), pred.data_ptr(), conv.data_ptr(), table.ctypes.data, b, n_views, h, w, ch, cw, SPACES.index(space), o["edge"], o["max_s8"],
             canvas.data_ptr(), _ptr(holes), _ptr(near), ws.data_ptr(), nbytes, _stream_ptr(dev))
-    extra = ((holes,) if want_holes else ()) + ((near,) if want_near else ())
-    return (canvas,) + extra if extra else canvas
+    return result
 
 
 def parallax_frames(image: torch.Tensor, pred: torch.Tensor, path="orbit", frames: int = 16, amount: float = 16.0, push: float = 0.0,
@@ -1582,42 +1591,18 @@ def parallax_frames(image: torch.Tensor, pred: torch.Tensor, path="orbit", frame
     genpercept_amd/parallax.py gives the same bits and states the rule from these terms to the call's integers.  Allocates the workspace;
     enqueued on the current stream, no synchronisation, nothing read back."""
     from .parallax import plan
-    from .stereo import F_DEFAULT
-    image, pred = _images_u8(image, "image"), _float_maps(pred, "pred")
-    b, h, w = (int(v) for v in pred.shape)
-    dev = pred.device
-    _same_batch(image, (b, h, w), dev, "image")
-    if space not in SPACES:
-        raise ValueError(f"space is one of {SPACES}, got {space!r}")
-    _post_dims(b, h, w, "parallax frames")
+    image, pred, (b, h, w), dev = _image_and_maps(image, pred, space, "parallax frames")
     o = plan(b, h, w, path, frames, amount, push, zoom, pan, focus, focus_at, edge, overscan, frame_range)
     table, n_frames = o["table"], int(o["table"].shape[0])
-    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != (b, n_frames, 3, h, w) or out.device != dev
-                            or not out.is_contiguous()):
-        raise ValueError(f"out: a contiguous uint8 {(b, n_frames, 3, h, w)} tensor on {dev}, got {out.dtype if torch.is_tensor(out) else type(out)} "
-                         f"{tuple(out.shape) if torch.is_tensor(out) else ''}")
+    out = _output_u8(out, "out", (b, n_frames, 3, h, w), dev)   # (every byte is written)
     assert pred.is_cuda
-    if o["focus"] is None and o["focus_at"] is None:
-        plane = torch.full((b,), F_DEFAULT, dtype=torch.int32, device=dev)
-    else:
-        if o["focus"] is not None:
-            at = torch.from_numpy(o["focus"]).to(dev, non_blocking=True)
-        else:
-            u, v = o["focus_at"][:, 0], o["focus_at"][:, 1]
-            at = pred.view(b, h * w).gather(1, torch.from_numpy(v * w + u).to(dev, non_blocking=True)[:, None])[:, 0]
-        # the nearness of b values, the 16-bit rule in float32: plumbing on the device, so that a plane picked from the map is not read back
-        q = (at.clamp(0.0, 1.0) * 65535.0).nan_to_num(0.0).to(torch.int32)
-        plane = torch.where(at.isnan(), torch.zeros_like(q), q if space == "disparity" else 65535 - q).contiguous()
-    if out is None:
-        out = torch.empty((b, n_frames, 3, h, w), dtype=torch.uint8, device=dev)   # (every byte is written)
-    holes = torch.empty((b, n_frames, h, w), dtype=torch.uint8, device=dev) if want_holes else None
-    near = torch.empty((b, n_frames, h, w), dtype=torch.int16, device=dev) if want_near else None
+    plane = _nearness_plane(pred, o["focus"], o["focus_at"], space, F_DEFAULT)
+    holes, near, result = _warp_planes(out, (b, n_frames, h, w), want_holes, want_near)
     ws, nbytes = _op_workspace("gp_parallax_frames", dev, b, n_frames, h, w)
     _launch("gp_parallax_frames", f"images {(b, h, w)}, {n_frames} frames, space = {space}, edge = {o['edge']}, max_s8 = {o['max_s8']}",
             image.data_ptr(), pred.data_ptr(), plane.data_ptr(), table.ctypes.data, b, n_frames, h, w, SPACES.index(space), o["edge"], o["max_s8"],
             out.data_ptr(), _ptr(holes), _ptr(near), ws.data_ptr(), nbytes, _stream_ptr(dev))
-    extra = ((holes,) if want_holes else ()) + ((near,) if want_near else ())
-    return (out,) + extra if extra else out
+    return result
 
 
 SEG_OUT = 8       # n, n_void, SEG_METRICS (out[2 .. 6]), n_classes; iou[K] follows

@@ -181,6 +181,52 @@ def _load_rgb(base_dir: str, rgb_rel: str, rgb_crop: Optional[Callable[[np.ndarr
     return img
 
 
+def _pred_name(rgb_rel: str, name_mode: FileNameMode, suffix: str = ".npy") -> str:
+    return os.path.join(os.path.dirname(rgb_rel), get_pred_name(os.path.basename(rgb_rel), name_mode, suffix=suffix))
+
+
+def _save_path(output_dir: str, rgb_rel: str, name_mode: FileNameMode, suffix: str) -> str:
+    """Where a sample's result goes, `output_dir/<scene>/<get_pred_name>`; the scene directory is made."""
+    save_to = os.path.join(output_dir, _pred_name(rgb_rel, name_mode, suffix))
+    os.makedirs(os.path.dirname(save_to), exist_ok=True)
+    return save_to
+
+
+def _chw_image(px: np.ndarray) -> Image.Image:
+    """A uint8 [3, H, W] array as a PIL RGB image."""
+    return Image.fromarray(np.ascontiguousarray(np.moveaxis(px, 0, -1)))
+
+
+def _write_rgb(px: np.ndarray, save_to: str) -> str:
+    _chw_image(px).save(save_to)
+    return save_to
+
+
+def _one_value_each(values: Dict, at_name: str, at) -> None:
+    """The terms a dataset loop uses for every sample: each of `values` (name -> value) is one number or None, `at` one pixel (u, v) or None."""
+    if any(np.ndim(v) != 0 for v in values.values()) or (at is not None and np.shape(at) != (2,)):
+        names = list(values)
+        raise ValueError(f"{', '.join(names[:-1])} and {names[-1]} are one value each and {at_name} one pixel (u, v), used for every sample")
+
+
+def _post_loop(base_dir: str, samples: Sequence[Sequence[str]], output_dir: str, name_mode: FileNameMode, suffix: str, batch_size: int, rank: int,
+               world: int, prefetch: int, run_group: Callable, write: Callable) -> list:
+    """The loop of the post-processing runs (`run_cutouts` ... `run_parallax`): this rank's `shard_range` of the samples, decoded `prefetch`
+    ahead, consecutive images of one size together, at most batch_size of them.  `run_group(images)` gives the results of a group on the
+    host, one per image in order; `write(result, save_to)` saves one of them, save_to being `output_dir/<scene>/<get_pred_name>` with
+    `suffix`, and returns what the run reports for the sample: that path or a list of paths.  Returns those, in sample order."""
+    if world > 1:
+        lo, hi = _shard(len(samples), rank, world)
+        samples = samples[lo:hi]
+    written = []
+    for group in _size_groups(_decode_ahead(samples, lambda s: _load_rgb(base_dir, s[0], None), prefetch), max(1, batch_size)):
+        results = run_group([img for _, img in group])
+        assert len(results) == len(group)
+        for (smp, _), result in zip(group, results):
+            written.append(write(result, _save_path(output_dir, smp[0], name_mode, suffix)))
+    return written
+
+
 def run_inference(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_dir: str, name_mode: FileNameMode, mode: str = "depth",
                   denoise_steps: int = 1, ensemble_size: int = 1, processing_res: int = 0, match_input_res: bool = True,
                   resample_method: str = "bilinear", fix_timesteps=None, prompt: str = "", rgb_crop: Optional[Callable[[np.ndarray], np.ndarray]] = None,
@@ -202,9 +248,7 @@ def run_inference(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_
         return _load_rgb(base_dir, rgb_rel, rgb_crop)
 
     def save(rgb_rel, pred_np):
-        scene_dir = os.path.join(output_dir, os.path.dirname(rgb_rel))
-        os.makedirs(scene_dir, exist_ok=True)
-        save_to = os.path.join(scene_dir, get_pred_name(os.path.basename(rgb_rel), name_mode, suffix=".npy"))
+        save_to = _save_path(output_dir, rgb_rel, name_mode, ".npy")
         np.save(save_to, pred_np)
         return save_to
 
@@ -246,27 +290,18 @@ def run_cutouts(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_di
     import torch
     if mode not in ("matting", "dis"):
         raise ValueError(f"cutouts need an alpha map: mode 'matting' or 'dis', got {mode!r}")
-    if world > 1:
-        lo, hi = _shard(len(samples), rank, world)
-        samples = samples[lo:hi]
-    written = []
-    for group in _size_groups(_decode_ahead(samples, lambda s: _load_rgb(base_dir, s[0], None), prefetch), max(1, batch_size)):
+
+    def cutouts(images):
         bg = background
         if torch.is_tensor(bg) and bg.dim() == 3:
-            bg = bg[None].expand(len(group), -1, -1, -1)
-        out, _ = pipe.cutout_batch_device([img for _, img in group], mode, bg, foreground_options, **inference_options)
-        out = out.cpu().numpy()
-        assert len(out) == len(group)
-        for (smp, _), px in zip(group, out):
-            scene_dir = os.path.join(output_dir, os.path.dirname(smp[0]))
-            os.makedirs(scene_dir, exist_ok=True)
-            save_to = os.path.join(scene_dir, get_pred_name(os.path.basename(smp[0]), name_mode, suffix=".png"))
-            if background is None:
-                Image.fromarray(px).save(save_to)
-            else:
-                Image.fromarray(np.ascontiguousarray(np.moveaxis(px, 0, -1))).save(save_to)
-            written.append(save_to)
-    return written
+            bg = bg[None].expand(len(images), -1, -1, -1)
+        return pipe.cutout_batch_device(images, mode, bg, foreground_options, **inference_options)[0].cpu().numpy()
+
+    def write(px, save_to):
+        (Image.fromarray(px) if background is None else _chw_image(px)).save(save_to)
+        return save_to
+
+    return _post_loop(base_dir, samples, output_dir, name_mode, ".png", batch_size, rank, world, prefetch, cutouts, write)
 
 
 def run_pointclouds(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_dir: str, name_mode: FileNameMode, mode: str = "depth",
@@ -281,22 +316,18 @@ def run_pointclouds(pipe, base_dir: str, samples: Sequence[Sequence[str]], outpu
         raise ValueError(f"point clouds need a depth map: mode 'depth' or 'disparity', got {mode!r}")
     if cameras is not None and np.asarray(cameras).shape != (8,):
         raise ValueError(f"cameras: None or eight values used for every sample, got shape {np.asarray(cameras).shape}")
-    if world > 1:
-        lo, hi = _shard(len(samples), rank, world)
-        samples = samples[lo:hi]
-    written = []
-    for group in _size_groups(_decode_ahead(samples, lambda s: _load_rgb(base_dir, s[0], None), prefetch), max(1, batch_size)):
-        out = pipe.pointcloud_batch_device([img for _, img in group], mode, cameras, pointcloud, **inference_options)
+
+    def clouds(images):
+        out = pipe.pointcloud_batch_device(images, mode, cameras, pointcloud, **inference_options)
         off = out["offsets"]
-        assert len(off) == len(group) + 1
-        pts, nrm, rgb = (out[k].cpu().numpy() for k in ("points", "point_normals", "point_rgb"))
-        for i, (smp, _) in enumerate(group):
-            scene_dir = os.path.join(output_dir, os.path.dirname(smp[0]))
-            os.makedirs(scene_dir, exist_ok=True)
-            save_to = os.path.join(scene_dir, get_pred_name(os.path.basename(smp[0]), name_mode, suffix=".ply"))
-            write_ply(save_to, pts[off[i]:off[i + 1]], nrm[off[i]:off[i + 1]], rgb[off[i]:off[i + 1]])
-            written.append(save_to)
-    return written
+        arrays = [out[k].cpu().numpy() for k in ("points", "point_normals", "point_rgb")]
+        return [[a[off[i]:off[i + 1]] for a in arrays] for i in range(len(off) - 1)]
+
+    def write(cloud, save_to):
+        write_ply(save_to, *cloud)
+        return save_to
+
+    return _post_loop(base_dir, samples, output_dir, name_mode, ".ply", batch_size, rank, world, prefetch, clouds, write)
 
 
 def run_refocus(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_dir: str, name_mode: FileNameMode, mode: str = "depth",
@@ -309,24 +340,13 @@ def run_refocus(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_di
     from .lens_blur import lens_blur_options
     if mode not in ("depth", "disparity"):
         raise ValueError(f"a refocus needs a depth map: mode 'depth' or 'disparity', got {mode!r}")
-    if any(np.ndim(v) != 0 for v in (focus if focus is not None else 0.0, aperture, max_radius, dof)) or (focus_at is not None and np.shape(focus_at) != (2,)):
-        raise ValueError("focus, aperture, max_radius and dof are one value each and focus_at one pixel (u, v), used for every sample")
+    _one_value_each(dict(focus=focus, aperture=aperture, max_radius=max_radius, dof=dof), "focus_at", focus_at)
     lens_blur_options(1, focus, focus_at, aperture, max_radius, dof)
-    if world > 1:
-        lo, hi = _shard(len(samples), rank, world)
-        samples = samples[lo:hi]
-    written = []
-    for group in _size_groups(_decode_ahead(samples, lambda s: _load_rgb(base_dir, s[0], None), prefetch), max(1, batch_size)):
-        out = pipe.refocus_batch_device([img for _, img in group], mode, focus, focus_at, aperture, max_radius, dof, None, tables, **inference_options)
-        out = out.cpu().numpy()
-        assert len(out) == len(group)
-        for (smp, _), px in zip(group, out):
-            scene_dir = os.path.join(output_dir, os.path.dirname(smp[0]))
-            os.makedirs(scene_dir, exist_ok=True)
-            save_to = os.path.join(scene_dir, get_pred_name(os.path.basename(smp[0]), name_mode, suffix=".png"))
-            Image.fromarray(np.ascontiguousarray(np.moveaxis(px, 0, -1))).save(save_to)
-            written.append(save_to)
-    return written
+
+    def refocused(images):
+        return pipe.refocus_batch_device(images, mode, focus, focus_at, aperture, max_radius, dof, None, tables, **inference_options).cpu().numpy()
+
+    return _post_loop(base_dir, samples, output_dir, name_mode, ".png", batch_size, rank, world, prefetch, refocused, _write_rgb)
 
 
 def run_stereo(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_dir: str, name_mode: FileNameMode, mode: str = "depth",
@@ -339,25 +359,14 @@ def run_stereo(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_dir
     from .stereo import stereo_options, view_table
     if mode not in ("depth", "disparity"):
         raise ValueError(f"a stereo view needs a depth map: mode 'depth' or 'disparity', got {mode!r}")
-    if any(np.ndim(v) != 0 for v in (converge if converge is not None else 0.0, separation, edge)) or (converge_at is not None and np.shape(converge_at) != (2,)):
-        raise ValueError("separation, converge and edge are one value each and converge_at one pixel (u, v), used for every sample")
+    _one_value_each(dict(separation=separation, converge=converge, edge=edge), "converge_at", converge_at)
     stereo_options(1, converge, converge_at, edge)
     view_table(layout, views, separation, 1, 1)
-    if world > 1:
-        lo, hi = _shard(len(samples), rank, world)
-        samples = samples[lo:hi]
-    written = []
-    for group in _size_groups(_decode_ahead(samples, lambda s: _load_rgb(base_dir, s[0], None), prefetch), max(1, batch_size)):
-        out = pipe.stereo_batch_device([img for _, img in group], mode, layout, views, separation, converge, converge_at, edge, **inference_options)
-        out = out.cpu().numpy()
-        assert len(out) == len(group)
-        for (smp, _), px in zip(group, out):
-            scene_dir = os.path.join(output_dir, os.path.dirname(smp[0]))
-            os.makedirs(scene_dir, exist_ok=True)
-            save_to = os.path.join(scene_dir, get_pred_name(os.path.basename(smp[0]), name_mode, suffix=".png"))
-            Image.fromarray(np.ascontiguousarray(np.moveaxis(px, 0, -1))).save(save_to)
-            written.append(save_to)
-    return written
+
+    def canvases(images):
+        return pipe.stereo_batch_device(images, mode, layout, views, separation, converge, converge_at, edge, **inference_options).cpu().numpy()
+
+    return _post_loop(base_dir, samples, output_dir, name_mode, ".png", batch_size, rank, world, prefetch, canvases, _write_rgb)
 
 
 def run_parallax(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_dir: str, name_mode: FileNameMode, mode: str = "depth",
@@ -372,41 +381,39 @@ def run_parallax(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_d
     inference_options go to `pipe.predict_batch_device`, `refine` and `tiles` among them."""
     from . import engine as ge
     from .parallax import MAX_FRAMES, camera_path, plan
-    from .stereo import stereo_options
+    from .post_common import _edge16, _plane
     if mode not in ("depth", "disparity"):
         raise ValueError(f"a camera move needs a depth map: mode 'depth' or 'disparity', got {mode!r}")
     if animate not in (None, "gif"):
         raise ValueError(f"animate is None or 'gif', got {animate!r}")
-    if any(np.ndim(v) != 0 for v in (focus if focus is not None else 0.0, amount, push, zoom, edge)) or (focus_at is not None and np.shape(focus_at) != (2,)):
-        raise ValueError("amount, push, zoom, focus and edge are one value each and focus_at one pixel (u, v), used for every sample")
+    _one_value_each(dict(amount=amount, push=push, zoom=zoom, focus=focus, edge=edge), "focus_at", focus_at)
     terms = (path, frames, amount, push, zoom, pan, focus, focus_at, edge, overscan)
-    stereo_options(1, focus, focus_at, edge)
+    _plane(1, focus, focus_at, "focus", "focus_at", exactly_one=False)
+    _edge16(edge)
     n_path = len(camera_path(path, frames, amount, push, zoom, pan))      # (the terms that need no image size are checked before any is read)
-    if world > 1:
-        lo, hi = _shard(len(samples), rank, world)
-        samples = samples[lo:hi]
-    written = []
-    for group in _size_groups(_decode_ahead(samples, lambda s: _load_rgb(base_dir, s[0], None), prefetch), max(1, batch_size)):
-        rgb, pred = pipe._post_inputs([img for _, img in group], mode, ("depth", "disparity"), "a camera move", "a depth map", inference_options,
+
+    def clips(images):
+        rgb, pred = pipe._post_inputs(images, mode, ("depth", "disparity"), "a camera move", "a depth map", inference_options,
                                       lambda images: plan(int(images.shape[0]), int(images.shape[-2]), int(images.shape[-1]), *terms,
                                                           (0, min(n_path, MAX_FRAMES))))
         parts = [ge.parallax_frames(rgb, pred, *terms, (first, min(first + MAX_FRAMES, n_path)), space=mode).cpu().numpy()
                  for first in range(0, n_path, MAX_FRAMES)]
         out = np.concatenate(parts, 1)
-        assert len(out) == len(group) and out.shape[1] == n_path
-        for (smp, _), clip in zip(group, out):
-            scene_dir = os.path.join(output_dir, os.path.dirname(smp[0]))
-            os.makedirs(scene_dir, exist_ok=True)
-            stem = os.path.splitext(get_pred_name(os.path.basename(smp[0]), name_mode, suffix=".png"))[0]
-            stills = [Image.fromarray(np.ascontiguousarray(np.moveaxis(px, 0, -1))) for px in clip]
-            paths = [os.path.join(scene_dir, f"{stem}_{k:04d}.png") for k in range(n_path)]
-            for still, save_to in zip(stills, paths):
-                still.save(save_to)
-            if animate == "gif":
-                paths.append(os.path.join(scene_dir, stem + ".gif"))
-                stills[0].save(paths[-1], save_all=True, append_images=stills[1:], duration=int(frame_ms), loop=0)
-            written.append(paths)
-    return written
+        assert out.shape[1] == n_path
+        return out
+
+    def write(clip, save_to):
+        stem = os.path.splitext(save_to)[0]
+        stills = [_chw_image(px) for px in clip]
+        paths = [f"{stem}_{k:04d}.png" for k in range(n_path)]
+        for still, path_k in zip(stills, paths):
+            still.save(path_k)
+        if animate == "gif":
+            paths.append(stem + ".gif")
+            stills[0].save(paths[-1], save_all=True, append_images=stills[1:], duration=int(frame_ms), loop=0)
+        return paths
+
+    return _post_loop(base_dir, samples, output_dir, name_mode, ".png", batch_size, rank, world, prefetch, clips, write)
 
 
 def _write_metric_files(output_dir: str, tag: str, names: List[str], per_sample, result: Dict[str, float], header: str) -> None:
@@ -440,10 +447,6 @@ def _write_normal_eval_files(output_dir: str, names: List[str], per_sample, resu
 def _gt_rel(s: Sequence[str], gt_column: int) -> Optional[str]:
     """The ground-truth path of a filename-list line, None where the column is absent or "None"."""
     return s[gt_column] if len(s) > gt_column and s[gt_column] != "None" else None
-
-
-def _pred_name(rgb_rel: str, name_mode: FileNameMode, suffix: str = ".npy") -> str:
-    return os.path.join(os.path.dirname(rgb_rel), get_pred_name(os.path.basename(rgb_rel), name_mode, suffix=suffix))
 
 
 def _same_size(smp: Sequence[str], pred_shape, gt_shape) -> None:

@@ -30,7 +30,7 @@ from typing import Dict, Optional, Tuple
 
 import numpy as np
 
-from .post_common import MAX_DIM, SPACES, quantize16  # noqa: F401
+from .post_common import MAX_DIM, SPACES, _check_space, _per_image, _pixel_inside, _plane, _plane_F, nearness, quantize16  # noqa: F401
 
 MAX_C8 = 256
 MAX_RADIUS = 32.0
@@ -104,39 +104,10 @@ def disc_weights() -> np.ndarray:
 
 
 # ---- the user's terms ---------------------------------------------------------------------------------------------------------------------------------
-def _per_image(v, B: int, name: str, width: int = 0) -> np.ndarray:
-    a = np.asarray(v, np.float64)
-    shape = (B, width) if width else (B,)
-    if a.ndim == len(shape) - 1:
-        a = np.broadcast_to(a[None], (B,) + a.shape)
-    if a.shape != shape or not np.isfinite(a).all():
-        raise ValueError(f"{name}: finite, one value for every image or {list(shape)}, got {np.shape(v)}")
-    return a
-
-
-def nearness(pred, space: str) -> np.ndarray:
-    """Step 1: D int64 of pred float32 of any shape."""
-    pred = np.asarray(pred, np.float32)
-    q = quantize16(pred).astype(i64)
-    return np.where(np.isnan(pred), 0, q if space == "disparity" else 65535 - q)
-
-
 def lens_blur_options(B: int, focus=None, focus_at=None, aperture=8.0, max_radius=16.0, dof=0.0) -> Dict:
     """The user's terms checked (ValueError outside their ranges) and spread over the B images: a dict of focus float32 [B] or None, focus_at
     int64 [B, 2] = (u, v) or None -- exactly one of the two is given --, and the integers gain, cmax8, dz, int64 [B] each."""
-    if (focus is None) == (focus_at is None):
-        raise ValueError("exactly one of focus (a value of the map) and focus_at (a pixel (u, v)) is given")
-    out = dict(focus=None, focus_at=None)
-    if focus is not None:
-        f = _per_image(focus, B, "focus")
-        if (f < 0.0).any() or (f > 1.0).any():
-            raise ValueError(f"focus is a value of the map in [0, 1], got {focus!r}")
-        out["focus"] = f.astype(np.float32)
-    else:
-        at = _per_image(focus_at, B, "focus_at", 2)
-        if (at != np.floor(at)).any() or (at < 0).any() or (at >= MAX_DIM).any():
-            raise ValueError(f"focus_at is a pixel (u, v) of the image, got {focus_at!r}")
-        out["focus_at"] = at.astype(i64)
+    out = dict(zip(("focus", "focus_at"), _plane(B, focus, focus_at, "focus", "focus_at", exactly_one=True)))
     a, m, d = _per_image(aperture, B, "aperture"), _per_image(max_radius, B, "max_radius"), _per_image(dof, B, "dof")
     if (a < 0.0).any() or (a > MAX_GAIN / 8.0).any():
         raise ValueError(f"aperture is a radius in pixels in [0, {MAX_GAIN // 8}], got {aperture!r}")
@@ -153,13 +124,8 @@ def lens_params(pred, space: str, focus=None, focus_at=None, aperture=8.0, max_r
     pred = np.asarray(pred)
     B, H, W = pred.shape[0], pred.shape[-2], pred.shape[-1]
     o = lens_blur_options(B, focus, focus_at, aperture, max_radius, dof)
-    if o["focus"] is not None:
-        F = nearness(o["focus"], space)
-    else:
-        u, v = o["focus_at"][:, 0], o["focus_at"][:, 1]
-        if (u >= W).any() or (v >= H).any():
-            raise ValueError(f"focus_at = (u, v) lies inside the {W} x {H} image, got {o['focus_at'].tolist()}")
-        F = nearness(pred.reshape(B, H, W)[np.arange(B), v, u], space)
+    _pixel_inside(o["focus_at"], "focus_at", H, W)
+    F = _plane_F(pred.reshape(B, H, W), space, o["focus"], o["focus_at"])
     return np.stack([F, o["gain"], o["cmax8"], o["dz"]], 1).astype(np.int32)
 
 
@@ -214,8 +180,7 @@ def lens_blur_params(image, pred, params, space: str = "depth", sharp=None, tabl
     """A batch by the definition above from the four integers of every image.  image uint8 [B, 3, H, W] ([3, H, W]: one image); pred float
     [B, 1, H, W] ([B, H, W] with B images, [H, W] with one); params integers [B, 4] or [4]; sharp [B, H, W] or None; tables (to_lin, from_lin)
     or None (`srgb_tables`).  Returns out uint8 [B, 3, H, W], and with want_coc (out, coc) with coc uint16 [B, H, W]."""
-    if space not in SPACES:
-        raise ValueError(f"space is one of {SPACES}, got {space!r}")
+    _check_space(space)
     image = np.asarray(image)
     image = image[None] if image.ndim == 3 else image
     if image.dtype != np.uint8 or image.ndim != 4 or image.shape[1] != 3:
@@ -249,8 +214,7 @@ def lens_blur(image, pred, focus=None, focus_at=None, aperture=8.0, max_radius=1
     """`lens_blur_params` from the user's terms (module docstring): exactly one of focus and focus_at; every term one value or one per image."""
     image = np.asarray(image)
     B = 1 if image.ndim == 3 else image.shape[0]
-    if space not in SPACES:
-        raise ValueError(f"space is one of {SPACES}, got {space!r}")
+    _check_space(space)
     pred = np.asarray(pred)
     if image.ndim not in (3, 4) or pred.size != B * image.shape[-2] * image.shape[-1] or tuple(pred.shape[-2:]) != tuple(image.shape[-2:]):
         raise ValueError(f"image [B, 3, H, W] and pred [B, 1, H, W], got {image.shape} and {pred.shape}")

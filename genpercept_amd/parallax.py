@@ -9,7 +9,7 @@ Definition (restated in include/genpercept_hip.h; the arithmetic once more in cs
     space "depth" or "disparity"; edge 0 .. 65535; max_s8 0 .. 256 (a displacement of at most 32 pixels, in eighths); a table of V rows
     (gx, gy, gz, Z), 1 <= V <= 64, |gx|, |gy| <= 2^17, |gz| <= 2^24, Z in 65536 .. 131072 (a zoom of 1 x to 2 x in units of 1 / 65536).
     1 <= H, W <= 16384 and B * V * H * W < 2^31.
-  1. Nearness: D = `lens_blur.nearness`(pred, space), larger is nearer, 0 for a NaN pixel.
+  1. Nearness: D = `post_common.nearness`(pred, space), larger is nearer, 0 for a NaN pixel.
   2. Position of source (x, y) in a frame, in eighths of a pixel: Cx = 4 (W - 1), Cy = 4 (H - 1); rx = 8 x - Cx, ry = 8 y - Cy; e = D - F;
      dz = (e gz + 2^23) >> 24; dx = ((e gx + 2^23) >> 24) + ((rx dz + 2^15) >> 16), clamped to -max_s8 .. max_s8, dy likewise with gy and ry;
      tx = Cx + ((rx Z + 2^15) >> 16) + dx, ty likewise.  Every shift is a floor.  Z + dz is the magnification of a pixel: a camera pushed
@@ -39,8 +39,8 @@ integers reach the entry.  A frame's largest possible displacement along an axis
 with span = 65535, or max(F, 65535 - F) where F is known on the host; max_s8 is the largest over the axes and frames of the WHOLE path.
 `overscan` (the default) raises each frame's Z to at least 65536 + ceil(16384 s8_k / (min(H, W) - 1)), that is a zoom of
 1 + 2 S_k / (min(H, W) - 1) for the frame's largest displacement S_k = s8_k / 8 pixels, so that the borders a move would expose stay outside
-the frame.  ValueError for a bound over 256 eighths, a zoom over 2 and a zoom under 1.  `focus` / `focus_at`, `edge` and their defaults are
-`converge` / `converge_at` / `edge` of `stereo.stereo_options`.  A path may be longer than one call's 64 frames: `frame_range` picks the rows
+the frame.  ValueError for a bound over 256 eighths, a zoom over 2 and a zoom under 1.  `focus` / `focus_at`, `edge` and their defaults follow the
+rules of `converge` / `converge_at` / `edge` in `stereo.py`.  A path may be longer than one call's 64 frames: `frame_range` picks the rows
 of a call, and max_s8 and the rows are those of the whole path whichever range is taken.
 """
 from __future__ import annotations
@@ -49,9 +49,8 @@ from typing import Dict, Optional, Tuple
 
 import numpy as np
 
-from .lens_blur import nearness
-from .post_common import MAX_DIM, SPACES, is_int, quantize16
-from .stereo import EDGE_DEFAULT, F_DEFAULT, _images_and_maps, stereo_options
+from .post_common import (EDGE_DEFAULT, F_DEFAULT, MAX_DIM, SPACES, _check_space, _count_limit, _edge16, _images_and_maps, _pixel_inside,  # noqa: F401
+                          _plane, _plane_F, _plane_span, _warp_integers, _with_planes, is_int, nearness)
 
 MAX_FRAMES = 64            # the rows of one call
 MAX_PATH = 4096            # the frames of a path, taken MAX_FRAMES at a time
@@ -132,18 +131,13 @@ def plan(B: int, H: int, W: int, path="orbit", frames: int = 16, amount: float =
     [V, 4] of the frames `frame_range` = (first, end) picks from the path (all of them without it), n_path, the length of the whole path, and
     max_s8, the largest displacement bound over the whole path.  ValueError for a bound over 32 pixels, a zoom outside 1 .. 2 (after
     `overscan`), a focus_at outside the image, more than 64 frames in one call, B * V * H * W >= 2^31."""
-    o = stereo_options(B, focus, focus_at, edge)
-    o = dict(focus=o["converge"], focus_at=o["converge_at"], edge=o["edge"])
+    value, at = _plane(B, focus, focus_at, "focus", "focus_at", exactly_one=False)
+    o = dict(focus=value, focus_at=at, edge=_edge16(edge))
     if not (1 <= H <= MAX_DIM and 1 <= W <= MAX_DIM) or B < 1:
         raise ValueError(f"images with sides in 1 .. {MAX_DIM}, got {(B, H, W)}")
-    if o["focus_at"] is not None and ((o["focus_at"][:, 0] >= W).any() or (o["focus_at"][:, 1] >= H).any()):
-        raise ValueError(f"focus_at = (u, v) lies inside the {W} x {H} image, got {o['focus_at'].tolist()}")
+    _pixel_inside(at, "focus_at", H, W)
     rows = camera_path(path, frames, amount, push, zoom, pan)
-    span = 65535
-    if o["focus_at"] is None:
-        q = quantize16(o["focus"]).astype(i64) if o["focus"] is not None else np.full(B, F_DEFAULT, i64)
-        span = int(np.maximum(q, 65535 - q).max())      # (the same for both spaces: F is q or 65535 - q)
-    s8 = frame_bounds8(rows, H, W, span)
+    s8 = frame_bounds8(rows, H, W, _plane_span(B, value, at, F_DEFAULT))
     max_s8 = int(s8.max())
     if max_s8 > MAX_S8:
         raise ValueError(f"the path needs a displacement of {max_s8 / 8:g} pixels, more than {MAX_S8 // 8}")
@@ -157,20 +151,14 @@ def plan(B: int, H: int, W: int, path="orbit", frames: int = 16, amount: float =
         raise ValueError(f"frame_range = (first, end) within the {n_path} frames of the path, got {frame_range!r}")
     if end - first > MAX_FRAMES:
         raise ValueError(f"at most {MAX_FRAMES} frames in one call, got {end - first}: take the path in parts with frame_range")
-    if B * (end - first) * H * W >= 2 ** 31:
-        raise ValueError(f"B * V * H * W < 2^31, got {(B, end - first, H, W)}")
+    _count_limit(B, end - first, H, W)
     o.update(table=np.ascontiguousarray(rows[first:end].astype(np.int32)), n_path=n_path, max_s8=max_s8)
     return o
 
 
 def focus_plane(pred, space: str, o: Dict) -> np.ndarray:
     """F int64 [B] of the options `o` and, for focus_at, the maps pred [B, H, W]."""
-    B = pred.shape[0]
-    if o["focus"] is not None:
-        return nearness(o["focus"], space)
-    if o["focus_at"] is not None:
-        return nearness(pred[np.arange(B), o["focus_at"][:, 1], o["focus_at"][:, 0]], space)
-    return np.full(B, F_DEFAULT, i64)
+    return _plane_F(pred, space, o["focus"], o["focus_at"], F_DEFAULT)
 
 
 # ---- the definition ---------------------------------------------------------------------------------------------------------------------------------
@@ -359,20 +347,13 @@ def parallax_frames_table(image, pred, F, table, space: str = "depth", edge: int
     ([B, H, W] with B images, [H, W] with one); F integers [B] or one; table integers [V, 4].  Returns (frames uint8 [B, V, 3, H, W], holes
     uint8 [B, V, H, W], near uint16 [B, V, H, W]), and with want_stats also a list [B][V] of the dicts of `warp_frame` with `filled_from`
     int64 [H, W] of `fill_holes` added."""
-    if space not in SPACES:
-        raise ValueError(f"space is one of {SPACES}, got {space!r}")
+    _check_space(space)
     image, pred = _images_and_maps(image, pred)
     B, _, H, W = image.shape
-    if not is_int(edge) or not 0 <= edge <= 65535 or not is_int(max_s8) or not 0 <= max_s8 <= MAX_S8:
-        raise ValueError(f"edge in 0 .. 65535 and max_s8 in 0 .. {MAX_S8}, got {edge!r} and {max_s8!r}")
+    F = _warp_integers(F, B, edge, max_s8, MAX_S8)
     table = check_table(table)
     V = table.shape[0]
-    if B * V * H * W >= 2 ** 31:
-        raise ValueError(f"B * V * H * W < 2^31, got {(B, V, H, W)}")
-    F = np.asarray(F)
-    if F.dtype.kind not in "iu" or F.shape not in ((), (B,)):
-        raise ValueError(f"F: one integer or [{B}], got {F.dtype} {F.shape}")
-    F = np.clip(np.broadcast_to(F.astype(i64), (B,)), 0, 65535)
+    _count_limit(B, V, H, W)
     frames, holes, near = np.empty((B, V, 3, H, W), np.uint8), np.empty((B, V, H, W), np.uint8), np.empty((B, V, H, W), np.uint16)
     stats = [[None] * V for _ in range(B)]
     for b in range(B):
@@ -391,11 +372,9 @@ def parallax_frames(image, pred, path="orbit", frames: int = 16, amount: float =
                     want_holes: bool = False, want_near: bool = False):
     """`parallax_frames_table` from the user's terms (module docstring).  Returns the frames uint8 [B, V, 3, H, W], and with want_holes /
     want_near a tuple with those planes after them."""
-    if space not in SPACES:
-        raise ValueError(f"space is one of {SPACES}, got {space!r}")
+    _check_space(space)
     image, pred = _images_and_maps(image, pred)
     B, _, H, W = image.shape
     o = plan(B, H, W, path, frames, amount, push, zoom, pan, focus, focus_at, edge, overscan, frame_range)
     out, holes, near = parallax_frames_table(image, pred, focus_plane(pred, space, o), o["table"], space, o["edge"], o["max_s8"])
-    extra = ((holes,) if want_holes else ()) + ((near,) if want_near else ())
-    return (out,) + extra if extra else out
+    return _with_planes(out, holes, near, want_holes, want_near)

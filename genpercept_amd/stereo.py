@@ -9,7 +9,7 @@ Definition (restated in include/genpercept_hip.h; the arithmetic once more in cs
     space "depth" or "disparity"; edge 0 .. 65535; max_s8 0 .. 512 (a shift of at most 64 pixels, in eighths); a table of V rows
     (g, ox, oy, cmask), 1 <= V <= 64, |g| <= 131072, (ox, oy) the origin of the view's H x W rectangle in the canvas, cmask in 1 .. 7 the
     channels it writes.  1 <= H, W <= 16384 and B * V * H * W < 2^31.
-  1. Nearness: Q = quantize16(pred); D = Q in disparity space, D = 65535 - Q in depth space; a NaN pixel has D = 0 (`lens_blur.nearness`).
+  1. Nearness: Q = quantize16(pred); D = Q in disparity space, D = 65535 - Q in depth space; a NaN pixel has D = 0 (`post_common.nearness`).
   2. Shift of source column x for a view, in eighths of a pixel: s = ((D - F) * g + 2^23) >> 24, a floor, clamped to -max_s8 .. max_s8;
      t_x = 8 x + s.
   3. x and x + 1 are connected iff |D_x - D_{x+1}| <= edge.  Output column p, at P = 8 p, is covered by the span of a connected pair with
@@ -39,15 +39,13 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-from .lens_blur import _per_image, nearness
-from .post_common import MAX_DIM, SPACES, is_int, quantize16
+from .post_common import (EDGE_DEFAULT, F_DEFAULT, MAX_DIM, SPACES, _check_space, _count_limit, _edge16, _images_and_maps,  # noqa: F401
+                          _pixel_inside, _plane, _plane_F, _plane_span, _warp_integers, _with_planes, is_int, nearness, quantize16)
 
 MAX_VIEWS = 64
 MAX_S8 = 512
 MAX_G = 131072
 CAP = 4
-F_DEFAULT = 32768
-EDGE_DEFAULT = 0.04        # a convention: neighbours further apart than 4 % of the map's range are cut
 LAYOUTS = ("pair", "sbs", "over_under", "anaglyph", "quilt")
 i64 = np.int64
 
@@ -108,23 +106,8 @@ def view_table(layout: str, views, separation: float, H: int, W: int) -> Tuple[n
 def stereo_options(B: int, converge=None, converge_at=None, edge=EDGE_DEFAULT) -> Dict:
     """converge, converge_at and edge checked (ValueError outside their ranges) and spread over the B images: a dict of converge float32 [B]
     or None, converge_at int64 [B, 2] = (u, v) or None -- at most one of the two is given --, and the integer edge."""
-    if converge is not None and converge_at is not None:
-        raise ValueError("at most one of converge (a value of the map) and converge_at (a pixel (u, v)) is given")
-    out = dict(converge=None, converge_at=None)
-    if converge is not None:
-        c = _per_image(converge, B, "converge")
-        if (c < 0.0).any() or (c > 1.0).any():
-            raise ValueError(f"converge is a value of the map in [0, 1], got {converge!r}")
-        out["converge"] = c.astype(np.float32)
-    if converge_at is not None:
-        at = _per_image(converge_at, B, "converge_at", 2)
-        if (at != np.floor(at)).any() or (at < 0).any() or (at >= MAX_DIM).any():
-            raise ValueError(f"converge_at is a pixel (u, v) of the image, got {converge_at!r}")
-        out["converge_at"] = at.astype(i64)
-    if isinstance(edge, bool) or np.ndim(edge) != 0 or not np.isfinite(float(edge)) or not 0.0 <= float(edge) <= 1.0:
-        raise ValueError(f"edge is a fraction of the map's range in [0, 1], got {edge!r}")
-    out["edge"] = int(np.floor(65535.0 * float(edge) + 0.5))
-    return out
+    value, at = _plane(B, converge, converge_at, "converge", "converge_at", exactly_one=False)
+    return dict(converge=value, converge_at=at, edge=_edge16(edge))
 
 
 def plan(B: int, H: int, W: int, layout="sbs", views=2, separation=16.0, converge=None, converge_at=None, edge=EDGE_DEFAULT) -> Dict:
@@ -133,29 +116,18 @@ def plan(B: int, H: int, W: int, layout="sbs", views=2, separation=16.0, converg
     ValueError where that shift exceeds 64 pixels, or where converge_at lies outside the image."""
     o = stereo_options(B, converge, converge_at, edge)
     table, size = view_table(layout, views, separation, H, W)
-    if o["converge_at"] is not None and ((o["converge_at"][:, 0] >= W).any() or (o["converge_at"][:, 1] >= H).any()):
-        raise ValueError(f"converge_at = (u, v) lies inside the {W} x {H} image, got {o['converge_at'].tolist()}")
-    span = 65535
-    if o["converge_at"] is None:
-        q = quantize16(o["converge"]).astype(i64) if o["converge"] is not None else np.full(B, F_DEFAULT, i64)
-        span = int(np.maximum(q, 65535 - q).max())    # (the same for both spaces: F is q or 65535 - q)
-    max_s8 = max_shift8(table[:, 0], span)
+    _pixel_inside(o["converge_at"], "converge_at", H, W)
+    max_s8 = max_shift8(table[:, 0], _plane_span(B, o["converge"], o["converge_at"], F_DEFAULT))
     if max_s8 > MAX_S8:
         raise ValueError(f"separation {separation!r} needs a shift of {max_s8 / 8:g} pixels, more than 64")
-    if B * table.shape[0] * H * W >= 2 ** 31:
-        raise ValueError(f"B * V * H * W < 2^31, got {(B, table.shape[0], H, W)}")
+    _count_limit(B, table.shape[0], H, W)
     o.update(table=table, size=size, max_s8=max_s8)
     return o
 
 
 def convergence(pred, space: str, o: Dict) -> np.ndarray:
     """F int64 [B] of the options `o` and, for converge_at, the maps pred [B, H, W]."""
-    B = pred.shape[0]
-    if o["converge"] is not None:
-        return nearness(o["converge"], space)
-    if o["converge_at"] is not None:
-        return nearness(pred[np.arange(B), o["converge_at"][:, 1], o["converge_at"][:, 0]], space)
-    return np.full(B, F_DEFAULT, i64)
+    return _plane_F(pred, space, o["converge"], o["converge_at"], F_DEFAULT)
 
 
 # ---- the definition ---------------------------------------------------------------------------------------------------------------------------------
@@ -218,20 +190,6 @@ def fill_holes(near, colours, max_s8: int):
     return filled, np.where(holes[None], taken, colours), holes
 
 
-def _images_and_maps(image, pred):
-    image = np.asarray(image)
-    image = image[None] if image.ndim == 3 else image
-    if image.dtype != np.uint8 or image.ndim != 4 or image.shape[1] != 3:
-        raise ValueError(f"image: uint8 [B, 3, H, W] or [3, H, W], got {image.dtype} {image.shape}")
-    B, _, H, W = image.shape
-    if not (1 <= H <= MAX_DIM and 1 <= W <= MAX_DIM) or B < 1:
-        raise ValueError(f"image: sides in 1 .. {MAX_DIM}, got {image.shape}")
-    pred = np.asarray(pred)
-    if pred.dtype.kind != "f" or pred.size != B * H * W or tuple(pred.shape[-2:]) != (H, W):
-        raise ValueError(f"pred: float {(B, 1, H, W)}, got {pred.dtype} {pred.shape}")
-    return image, pred.reshape(B, H, W).astype(np.float32)
-
-
 def check_table(table, H: int, W: int, CH: int, CW: int) -> np.ndarray:
     """The view table as a checked contiguous int32 [V, 4] array: the ranges of the definition, every rectangle inside the canvas, and no
     two rectangles that overlap and share a channel."""
@@ -258,24 +216,17 @@ def stereo_views_table(image, pred, F, table, canvas, space: str = "depth", edge
     ([B, H, W] with B images, [H, W] with one); F integers [B] or one; table integers [V, 4]; canvas: uint8 [B, 3, CH, CW], written IN PLACE,
     or its size (CH, CW), a canvas of zeros.  Returns (canvas, holes uint8 [B, V, H, W], near uint16 [B, V, H, W]), and with want_cover also
     the number of pieces that cover each column, int64 [B, V, H, W]."""
-    if space not in SPACES:
-        raise ValueError(f"space is one of {SPACES}, got {space!r}")
+    _check_space(space)
     image, pred = _images_and_maps(image, pred)
     B, _, H, W = image.shape
-    if not is_int(edge) or not 0 <= edge <= 65535 or not is_int(max_s8) or not 0 <= max_s8 <= MAX_S8:
-        raise ValueError(f"edge in 0 .. 65535 and max_s8 in 0 .. {MAX_S8}, got {edge!r} and {max_s8!r}")
+    F = _warp_integers(F, B, edge, max_s8, MAX_S8)
     if not isinstance(canvas, np.ndarray):
         canvas = np.zeros((B, 3) + tuple(int(v) for v in canvas), np.uint8)
     if canvas.dtype != np.uint8 or canvas.ndim != 4 or canvas.shape[:2] != (B, 3):
         raise ValueError(f"canvas: uint8 {(B, 3, 'CH', 'CW')}, got {canvas.dtype} {canvas.shape}")
     table = check_table(table, H, W, canvas.shape[2], canvas.shape[3])
     V = table.shape[0]
-    if B * V * H * W >= 2 ** 31:
-        raise ValueError(f"B * V * H * W < 2^31, got {(B, V, H, W)}")
-    F = np.asarray(F)
-    if F.dtype.kind not in "iu" or F.shape not in ((), (B,)):
-        raise ValueError(f"F: one integer or [{B}], got {F.dtype} {F.shape}")
-    F = np.clip(np.broadcast_to(F.astype(i64), (B,)), 0, 65535)
+    _count_limit(B, V, H, W)
     holes, near, cover = np.empty((B, V, H, W), np.uint8), np.empty((B, V, H, W), np.uint16), np.empty((B, V, H, W), i64)
     for b in range(B):
         D, rgb = nearness(pred[b], space), image[b].astype(i64)
@@ -293,11 +244,9 @@ def stereo_views(image, pred, layout="sbs", views=2, separation=16.0, converge=N
                  want_holes: bool = False, want_near: bool = False):
     """`stereo_views_table` from the user's terms (module docstring).  Returns the canvas uint8 [B, 3, CH, CW], and with want_holes /
     want_near a tuple with those planes after it."""
-    if space not in SPACES:
-        raise ValueError(f"space is one of {SPACES}, got {space!r}")
+    _check_space(space)
     image, pred = _images_and_maps(image, pred)
     B, _, H, W = image.shape
     o = plan(B, H, W, layout, views, separation, converge, converge_at, edge)
     canvas, holes, near = stereo_views_table(image, pred, convergence(pred, space, o), o["table"], o["size"], space, o["edge"], o["max_s8"])
-    extra = ((holes,) if want_holes else ()) + ((near,) if want_near else ())
-    return (canvas,) + extra if extra else canvas
+    return _with_planes(canvas, holes, near, want_holes, want_near)

@@ -1,7 +1,8 @@
-"""What the host and GPU tests of the post-processing ops (foreground, guided, tiled, geometry, lens_blur) share: the sanitizer build of a
-stand-alone check program and its run, bit comparisons, the scalar 16-bit quantiser, both libraries, the drivers of the "declared, exported,
-bound" and "refused without a GPU" tests, and for the GPU tests misaligned device views, the tiny model weights and the "refused with real
-buffers around it" driver.  A plain module: the tests import it the way they import one another (their directory is put on sys.path)."""
+"""What the host and GPU tests of the post-processing ops (foreground, guided, tiled, geometry, lens_blur, stereo, parallax) share: the
+sanitizer build of a stand-alone check program and its run, bit comparisons, the scalar 16-bit quantiser, both libraries, the drivers of the
+"declared, exported, bound" and "refused without a GPU" tests, the library handle that records every call, the nearness in plain loops and
+the batch of scenes, and for the GPU tests misaligned device views, the tiny model weights, the tiny pipeline, the three-PNG dataset and
+the "refused with real buffers around it" driver.  A plain module: the tests import it the way they import one another (their directory is put on sys.path)."""
 import os
 import re
 import shutil
@@ -100,6 +101,49 @@ def assert_all_refused(call, lib, ok, cases):
         assert call(lib, dict(ok, **kw)) == GP_ERR_INVALID, kw
 
 
+def library_calls(monkeypatch):
+    """engine.load_library gives a handle whose every entry records its name and fails; the list of those names.  (The test files wrap
+    this in a fixture of the same name.)"""
+    from genpercept_amd import engine
+    calls = []
+
+    class Handle:
+        def __getattr__(self, name):
+            def entry(*args):
+                calls.append(name)
+                raise AssertionError(f"{name} was called")
+            return entry
+
+    monkeypatch.setattr(engine, "load_library", lambda *a, **k: Handle())
+    return calls
+
+
+# ---- scenes -----------------------------------------------------------------------------------------------------------------------------
+def loops_nearness(pred, space):
+    """The nearness of a map [h, w] in plain loops, as lists [h][w]: the scalar quantiser, mirrored in depth space, 0 for a NaN."""
+    h, w = pred.shape
+    D = [[0] * w for _ in range(h)]
+    for y in range(h):
+        for x in range(w):
+            v = np.float32(pred[y, x])
+            if np.isnan(v):
+                continue
+            q = q16(v)
+            D[y][x] = q if space == "disparity" else 65535 - q
+    return D
+
+
+def batch_case(scene, seed, b, h, w, middle_nan=False):
+    """b images of `scene(rng, h, w)`, which returns (pred [h, w], further arrays of the image ...): (pred [b, 1, h, w], the further
+    arrays stacked ...); middle_nan makes the middle map all NaN."""
+    rng = np.random.RandomState(seed)
+    per = [scene(rng, h, w) for _ in range(b)]
+    pred, *rest = (np.stack([p[k] for p in per]) for k in range(len(per[0])))
+    if middle_nan:
+        pred[b // 2] = np.nan
+    return (pred[:, None], *rest)
+
+
 # ---- GPU tests (torch is imported where it is used: the host tests above need none) ------------------------------------------------------
 def offset4(x):
     """The array on the device as a contiguous view that starts four bytes into a 16-byte aligned buffer."""
@@ -133,6 +177,37 @@ def tiny_weights_dict():
     from oracle import sd21 as osd
     uc, vc = osd.UNetCfg.tiny(), osd.VAECfg.tiny()
     return dict(uc=uc, vc=vc, usd=osd.synth_state_dict(osd.unet_manifest(uc), 1), vsd=osd.synth_state_dict(osd.vae_manifest(vc), 2))
+
+
+def tiny_pipeline(tw, seed):
+    """The one-step bf16 pipeline over the weights `tw` of `tiny_weights_dict`, on the GPU, its text embedding drawn from a generator
+    seeded with `seed`: (the pipeline, that generator, for the test's images)."""
+    import torch
+    from genpercept_amd import GenPerceptPipeline
+    g = torch.Generator().manual_seed(seed)
+    ctx = torch.randn(2, tw["uc"].cross_attention_dim, generator=g)
+    pipe = GenPerceptPipeline(unet=tw["usd"], vae=tw["vsd"], scheduler=dict(beta_start=1.0, beta_end=1.0, prediction_type="v_prediction", clip_sample=False,
+                                                                                       steps_offset=1, timestep_spacing="leading"),
+                              text_encoder=ctx, tokenizer=None, torch_dtype=torch.bfloat16)
+    pipe.to("cuda")
+    return pipe, g
+
+
+def write_png_dataset(data, g, n, h, w):
+    """n random h x w images from the generator `g`, each with a darker left part and a weaker green below a row of its own, written as
+    `data`/set0/im/0000.png ...: (the samples of a filename list, the images as one uint8 [n, 3, h, w] tensor)."""
+    import torch
+    from PIL import Image
+    samples, images = [], []
+    os.makedirs(os.path.join(data, "set0", "im"), exist_ok=True)
+    for i in range(n):
+        rgb = torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8)
+        rgb[:, : 40 + 10 * i] //= 2
+        rgb[30 + 5 * i:, :, 1] //= 3
+        Image.fromarray(rgb.numpy()).save(os.path.join(data, "set0", "im", f"{i:04d}.png"))
+        samples.append([f"set0/im/{i:04d}.png"])
+        images.append(rgb.permute(2, 0, 1).contiguous())
+    return samples, torch.stack(images)
 
 
 def assert_refused_with_real_buffers(call, lib, ok, cases, bufs=None, fresh=None):

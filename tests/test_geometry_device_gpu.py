@@ -12,6 +12,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import post_support as ps  # noqa: E402
 from post_support import GP_ERR_INVALID, assert_refused_with_real_buffers, offset4, same_bits, tiny_weights_dict  # noqa: E402
 from test_geometry_host import PLANES, POINTS, call_geometry, geometry_args, invalid_cases, random_case  # noqa: E402
 
@@ -163,27 +164,11 @@ def test_pointclouds_with_the_pipeline(tiny_weights, tmp_path):
     camera and with one camera per image; `pointcloud` gives one image's cloud; `run_pointclouds` writes those points; what the entry does
     not take is refused."""
     from PIL import Image
-    from genpercept_amd import GenPerceptPipeline
     from genpercept_amd import geometry as gm
     from genpercept_amd import infer_eval as ie
-    tw = tiny_weights
-    g = torch.Generator().manual_seed(51)
-    ctx = torch.randn(2, tw["uc"].cross_attention_dim, generator=g)
-    pipe = GenPerceptPipeline(unet=tw["usd"], vae=tw["vsd"], scheduler=dict(beta_start=1.0, beta_end=1.0, prediction_type="v_prediction", clip_sample=False,
-                                                                                       steps_offset=1, timestep_spacing="leading"),
-                              text_encoder=ctx, tokenizer=None, torch_dtype=torch.bfloat16)
-    pipe.to("cuda")
+    pipe, g = ps.tiny_pipeline(tiny_weights, 51)
     data = str(tmp_path / "data")
-    samples, images = [], []
-    os.makedirs(os.path.join(data, "set0", "im"), exist_ok=True)
-    for i in range(3):
-        rgb = torch.randint(0, 256, (96, 128, 3), generator=g, dtype=torch.uint8)
-        rgb[:, : 40 + 10 * i] //= 2
-        rgb[30 + 5 * i:, :, 1] //= 3
-        Image.fromarray(rgb.numpy()).save(os.path.join(data, "set0", "im", f"{i:04d}.png"))
-        samples.append([f"set0/im/{i:04d}.png"])
-        images.append(rgb.permute(2, 0, 1).contiguous())
-    batch = torch.stack(images)
+    samples, batch = ps.write_png_dataset(data, g, 3, 96, 128)
     tiles = dict(size=48, overlap=16, batch=4)
     cams = np.stack([gm.default_camera(96, 128, 40.0 + 10.0 * i) for i in range(3)])
     cams[:, 0], cams[:, 1] = (2.0, 0.5, 1.0), (0.5, 1.0, 0.25)

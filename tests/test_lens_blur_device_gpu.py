@@ -5,6 +5,7 @@ per image, a `sharp` mask and a sharp zone, a batch whose middle map is all NaN,
 four bytes into their buffers (the kernel allows it for every one); batch independence and repeatability; the parameter table's clamping;
 the argument checks with real buffers around them; the pipeline and the dataset loop with `refine` and `tiles` at tiny widths.  There is no
 tolerance in this file."""
+import functools
 import os
 import sys
 
@@ -13,6 +14,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import post_support as ps  # noqa: E402
 from post_support import assert_refused_with_real_buffers, offset4, same_bits, tiny_weights_dict  # noqa: E402
 from test_lens_blur_host import all_tables, call_lens, invalid_cases, lens_args, random_case  # noqa: E402
 
@@ -22,13 +24,7 @@ gpu = pytest.mark.gpu
 CASES = [(1, 17, 23, 2, False), (2, 40, 70, 8, False), (1, 33, 200, 32, False), (1, 64, 48, 5, True), (3, 16, 16, 32, False)]
 
 
-def batch_case(seed, b, h, w, middle_nan=False):
-    rng = np.random.RandomState(seed)
-    per = [random_case(rng, h, w) for _ in range(b)]
-    pred, image, sharp = (np.stack([p[k] for p in per]) for k in range(3))
-    if middle_nan:
-        pred[b // 2] = np.nan
-    return pred[:, None], image, sharp
+batch_case = functools.partial(ps.batch_case, random_case)
 
 
 def terms(b, max_radius, dz):
@@ -176,27 +172,11 @@ def test_refocus_with_the_pipeline(tiny_weights, tmp_path):
     returns, bit for bit, for depth and disparity, plain, with `refine`, with `tiles` and with both; `focus_at` equals the same focus passed
     as a value; `refocus` gives one image; `run_refocus` writes those bytes; what the entry does not take is refused."""
     from PIL import Image
-    from genpercept_amd import GenPerceptPipeline
     from genpercept_amd import infer_eval as ie
     from genpercept_amd import lens_blur as lb
-    tw = tiny_weights
-    g = torch.Generator().manual_seed(51)
-    ctx = torch.randn(2, tw["uc"].cross_attention_dim, generator=g)
-    pipe = GenPerceptPipeline(unet=tw["usd"], vae=tw["vsd"], scheduler=dict(beta_start=1.0, beta_end=1.0, prediction_type="v_prediction", clip_sample=False,
-                                                                                       steps_offset=1, timestep_spacing="leading"),
-                              text_encoder=ctx, tokenizer=None, torch_dtype=torch.bfloat16)
-    pipe.to("cuda")
+    pipe, g = ps.tiny_pipeline(tiny_weights, 51)
     data = str(tmp_path / "data")
-    samples, images = [], []
-    os.makedirs(os.path.join(data, "set0", "im"), exist_ok=True)
-    for i in range(3):
-        rgb = torch.randint(0, 256, (96, 128, 3), generator=g, dtype=torch.uint8)
-        rgb[:, : 40 + 10 * i] //= 2
-        rgb[30 + 5 * i:, :, 1] //= 3
-        Image.fromarray(rgb.numpy()).save(os.path.join(data, "set0", "im", f"{i:04d}.png"))
-        samples.append([f"set0/im/{i:04d}.png"])
-        images.append(rgb.permute(2, 0, 1).contiguous())
-    batch = torch.stack(images)
+    samples, batch = ps.write_png_dataset(data, g, 3, 96, 128)
     tiles = dict(size=48, overlap=16, batch=4)
     sharp = torch.zeros((3, 96, 128), dtype=torch.uint8)
     sharp[:, 20:50, 30:70] = 255

@@ -5,6 +5,7 @@ zooms of 1 x to 2 x, swings, orbits and dollies, both spaces, a plane per image,
 the widest apron, a flat tile next to one with a step, tensors that start four bytes or one byte into their buffers; batch independence
 and repeatability; `focus_at` read on the device; the argument checks with real buffers around them; the pipeline and the dataset loop with
 `refine` and `tiles` at tiny widths, with frames and a GIF written.  There is no tolerance in this file."""
+import functools
 import os
 import sys
 
@@ -13,6 +14,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import post_support as ps  # noqa: E402
 from post_support import assert_refused_with_real_buffers, offset4, same_bits, tiny_weights_dict, unaligned  # noqa: E402
 from test_parallax_host import ZOOMS, call_parallax, frames_array, invalid_cases, parallax_args, scene  # noqa: E402
 
@@ -22,13 +24,7 @@ gpu = pytest.mark.gpu
 CASES = [(2, 33, 65, 40, 2600), (2, 70, 40, 256, 2600), (1, 1, 1, 8, 0), (1, 5, 7, 40, 65535)]
 
 
-def batch_case(seed, b, h, w, middle_nan=False):
-    rng = np.random.RandomState(seed)
-    per = [scene(rng, h, w) for _ in range(b)]
-    pred, image = np.stack([p[0] for p in per]), np.stack([p[1] for p in per])
-    if middle_nan:
-        pred[b // 2] = np.nan
-    return pred[:, None], image
+batch_case = functools.partial(ps.batch_case, scene)
 
 
 def table_for(h, w, max_s8):
@@ -245,27 +241,11 @@ def test_parallax_with_the_pipeline(tiny_weights, tmp_path):
     the frames as images; `run_parallax` writes those bytes as numbered frames and a looping GIF, a path of 70 frames in two parts; what the
     entry does not take is refused."""
     from PIL import Image
-    from genpercept_amd import GenPerceptPipeline
     from genpercept_amd import infer_eval as ie
     from genpercept_amd import parallax as pv
-    tw = tiny_weights
-    g = torch.Generator().manual_seed(51)
-    ctx = torch.randn(2, tw["uc"].cross_attention_dim, generator=g)
-    pipe = GenPerceptPipeline(unet=tw["usd"], vae=tw["vsd"], scheduler=dict(beta_start=1.0, beta_end=1.0, prediction_type="v_prediction", clip_sample=False,
-                                                                                       steps_offset=1, timestep_spacing="leading"),
-                              text_encoder=ctx, tokenizer=None, torch_dtype=torch.bfloat16)
-    pipe.to("cuda")
+    pipe, g = ps.tiny_pipeline(tiny_weights, 51)
     data = str(tmp_path / "data")
-    samples, images = [], []
-    os.makedirs(os.path.join(data, "set0", "im"), exist_ok=True)
-    for i in range(3):
-        rgb = torch.randint(0, 256, (96, 128, 3), generator=g, dtype=torch.uint8)
-        rgb[:, : 40 + 10 * i] //= 2
-        rgb[30 + 5 * i:, :, 1] //= 3
-        Image.fromarray(rgb.numpy()).save(os.path.join(data, "set0", "im", f"{i:04d}.png"))
-        samples.append([f"set0/im/{i:04d}.png"])
-        images.append(rgb.permute(2, 0, 1).contiguous())
-    batch = torch.stack(images)
+    samples, batch = ps.write_png_dataset(data, g, 3, 96, 128)
     tiles = dict(size=48, overlap=16, batch=4)
     try:
         done = {}

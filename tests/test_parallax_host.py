@@ -58,24 +58,11 @@ def case_inputs(case):
 
 
 # ---- the definition once more, in plain loops ---------------------------------------------------------------------------------------------------------
-def loops_nearness(pred, space):
-    h, w = pred.shape
-    D = [[0] * w for _ in range(h)]
-    for y in range(h):
-        for x in range(w):
-            v = np.float32(pred[y, x])
-            if np.isnan(v):
-                continue
-            q = ps.q16(v)
-            D[y][x] = q if space == "disparity" else 65535 - q
-    return D
-
-
 def loops_frames(image, pred, F, table, space, edge, max_s8):
     """Steps 1 to 6 for one image [3, h, w]: every cap and every triangle is scattered over the pixels between the smallest and the largest
     coordinates of its corners.  Returns (frames [V][3][h][w], holes, near, cover, piece [V][h][w])."""
     _, h, w = image.shape
-    D = loops_nearness(pred, space)
+    D = ps.loops_nearness(pred, space)
     img = image.astype(int).tolist()
     R = max_s8 // 4 + 1
     Cx, Cy = 4 * (w - 1), 4 * (h - 1)
@@ -440,19 +427,7 @@ def test_invalid_arguments_are_refused_without_a_gpu():
 
 @pytest.fixture
 def library_calls(monkeypatch):
-    """engine.load_library gives a handle whose every entry records its name and fails; the list of those names."""
-    from genpercept_amd import engine
-    calls = []
-
-    class Handle:
-        def __getattr__(self, name):
-            def entry(*args):
-                calls.append(name)
-                raise AssertionError(f"{name} was called")
-            return entry
-
-    monkeypatch.setattr(engine, "load_library", lambda *a, **k: Handle())
-    return calls
+    return ps.library_calls(monkeypatch)
 
 
 def test_the_binding_refuses_bad_tensors_and_options_before_the_library_is_touched(library_calls):

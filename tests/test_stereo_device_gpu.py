@@ -4,6 +4,7 @@ sizes that are multiples of nothing, shifts up to 64 pixels (an apron wider than
 image), both spaces, a pair, an anaglyph and a quilt, a convergence plane per image, a batch whose middle map is all NaN, a flat tile next
 to one with a step edge, tensors that start four bytes into their buffers; batch independence and repeatability; the argument checks with
 real buffers around them; the pipeline and the dataset loop with `refine` and `tiles` at tiny widths.  There is no tolerance in this file."""
+import functools
 import os
 import sys
 
@@ -12,6 +13,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import post_support as ps  # noqa: E402
 from post_support import assert_refused_with_real_buffers, offset4, same_bits, tiny_weights_dict  # noqa: E402
 from test_stereo_host import call_stereo, fold_and_cut_row, invalid_cases, scene, stereo_args, views_array  # noqa: E402
 
@@ -22,13 +24,7 @@ CASES = [(1, 5, 7, 1, 2600), (2, 19, 70, 5, 2600), (1, 9, 300, 64, 2600), (3, 6,
 LAYOUTS = [("pair", 2), ("anaglyph", 2), ("quilt", (3, 3))]
 
 
-def batch_case(seed, b, h, w, middle_nan=False):
-    rng = np.random.RandomState(seed)
-    per = [scene(rng, h, w) for _ in range(b)]
-    pred, image = np.stack([p[0] for p in per]), np.stack([p[1] for p in per])
-    if middle_nan:
-        pred[b // 2] = np.nan
-    return pred[:, None], image
+batch_case = functools.partial(ps.batch_case, scene)
 
 
 def device_views(image_d, pred_d, F, table, size, space, edge, max_s8, with_planes=True, fill=0x5A):
@@ -200,27 +196,11 @@ def test_stereo_with_the_pipeline(tiny_weights, tmp_path):
     returns, bit for bit, for depth and disparity, plain, with `refine`, with `tiles` and with both; `stereo` gives one image of the canvas
     size; `run_stereo` writes those bytes; what the entry does not take is refused."""
     from PIL import Image
-    from genpercept_amd import GenPerceptPipeline
     from genpercept_amd import infer_eval as ie
     from genpercept_amd import stereo as st
-    tw = tiny_weights
-    g = torch.Generator().manual_seed(51)
-    ctx = torch.randn(2, tw["uc"].cross_attention_dim, generator=g)
-    pipe = GenPerceptPipeline(unet=tw["usd"], vae=tw["vsd"], scheduler=dict(beta_start=1.0, beta_end=1.0, prediction_type="v_prediction", clip_sample=False,
-                                                                                       steps_offset=1, timestep_spacing="leading"),
-                              text_encoder=ctx, tokenizer=None, torch_dtype=torch.bfloat16)
-    pipe.to("cuda")
+    pipe, g = ps.tiny_pipeline(tiny_weights, 51)
     data = str(tmp_path / "data")
-    samples, images = [], []
-    os.makedirs(os.path.join(data, "set0", "im"), exist_ok=True)
-    for i in range(3):
-        rgb = torch.randint(0, 256, (96, 128, 3), generator=g, dtype=torch.uint8)
-        rgb[:, : 40 + 10 * i] //= 2
-        rgb[30 + 5 * i:, :, 1] //= 3
-        Image.fromarray(rgb.numpy()).save(os.path.join(data, "set0", "im", f"{i:04d}.png"))
-        samples.append([f"set0/im/{i:04d}.png"])
-        images.append(rgb.permute(2, 0, 1).contiguous())
-    batch = torch.stack(images)
+    samples, batch = ps.write_png_dataset(data, g, 3, 96, 128)
     tiles = dict(size=48, overlap=16, batch=4)
     try:
         done = {}

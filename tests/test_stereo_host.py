@@ -43,24 +43,11 @@ def gain_for(max_s8, rng):
 
 
 # ---- the definition once more, in plain loops ---------------------------------------------------------------------------------------------------------
-def loops_nearness(pred, space):
-    h, w = pred.shape
-    D = [[0] * w for _ in range(h)]
-    for y in range(h):
-        for x in range(w):
-            v = np.float32(pred[y, x])
-            if np.isnan(v):
-                continue
-            q = ps.q16(v)
-            D[y][x] = q if space == "disparity" else 65535 - q
-    return D
-
-
 def loops_views(image, pred, F, table, canvas, space, edge, max_s8, bounded=True):
     """Steps 1 to 6 for one image [3, h, w]: every piece of every source is scattered over the columns it covers.  canvas [3, CH, CW] is
     written in place; returns (holes, near, cover) as lists [V][h][w].  bounded=False: the hole search has no limit."""
     _, h, w = image.shape
-    D = loops_nearness(pred, space)
+    D = ps.loops_nearness(pred, space)
     R = max_s8 // 4 + 1 if bounded else w
     holes, near, cover = [], [], []
     for g, ox, oy, cmask in table:
@@ -466,19 +453,7 @@ def test_invalid_arguments_are_refused_without_a_gpu():
 
 @pytest.fixture
 def library_calls(monkeypatch):
-    """engine.load_library gives a handle whose every entry records its name and fails; the list of those names."""
-    from genpercept_amd import engine
-    calls = []
-
-    class Handle:
-        def __getattr__(self, name):
-            def entry(*args):
-                calls.append(name)
-                raise AssertionError(f"{name} was called")
-            return entry
-
-    monkeypatch.setattr(engine, "load_library", lambda *a, **k: Handle())
-    return calls
+    return ps.library_calls(monkeypatch)
 
 
 def test_the_binding_refuses_bad_tensors_and_options_before_the_library_is_touched(library_calls):

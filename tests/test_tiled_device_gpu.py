@@ -11,6 +11,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import post_support as ps  # noqa: E402
 from post_support import assert_refused_with_real_buffers, bits, offset4, same_bits64, tiny_weights_dict  # noqa: E402
 from test_tiled_host import call_merge, invalid_cases, merge_args, random_case, same_bits  # noqa: E402
 
@@ -138,31 +139,17 @@ def test_tiles_with_the_pipeline(tiny_weights, tmp_path, monkeypatch):
     `infer_batch`, `__call__` and the host route agree; the cutouts are those of the tiled alpha; `run_inference` writes those values; with
     `refine` the base is the refined map; what `tiles` does not take is refused."""
     from PIL import Image
-    from genpercept_amd import GenPerceptPipeline
     from genpercept_amd import foreground as fgh
     from genpercept_amd import infer_eval as ie
     from genpercept_amd import tiled
-    tw = tiny_weights
-    g = torch.Generator().manual_seed(51)
-    ctx = torch.randn(2, tw["uc"].cross_attention_dim, generator=g)
-    pipe = GenPerceptPipeline(unet=tw["usd"], vae=tw["vsd"], scheduler=dict(beta_start=1.0, beta_end=1.0, prediction_type="v_prediction", clip_sample=False,
-                                                                                       steps_offset=1, timestep_spacing="leading"),
-                              text_encoder=ctx, tokenizer=None, torch_dtype=torch.bfloat16)
-    pipe.to("cuda")
+    pipe, g = ps.tiny_pipeline(tiny_weights, 51)
     data, npy, ev0, ev1 = (str(tmp_path / d) for d in ("data", "npy", "ev0", "ev1"))
-    samples, images = [], []
-    for i in range(3):
-        for sub in ("im", "gt"):
-            os.makedirs(os.path.join(data, "set0", sub), exist_ok=True)
-        rgb = torch.randint(0, 256, (96, 128, 3), generator=g, dtype=torch.uint8)
-        rgb[:, : 40 + 10 * i] //= 2
-        rgb[30 + 5 * i:, :, 1] //= 3
-        Image.fromarray(rgb.numpy()).save(os.path.join(data, "set0", "im", f"{i:04d}.png"))
+    samples, batch = ps.write_png_dataset(data, g, 3, 96, 128)
+    os.makedirs(os.path.join(data, "set0", "gt"), exist_ok=True)
+    for i, smp in enumerate(samples):
         xx = np.arange(128)[None].repeat(96, 0)
         Image.fromarray(np.clip((xx - (40 + 10 * i)) * 6 + 128, 0, 255).astype(np.uint8)).save(os.path.join(data, "set0", "gt", f"{i:04d}.png"))
-        samples.append([f"set0/im/{i:04d}.png", f"set0/gt/{i:04d}.png"])
-        images.append(rgb.permute(2, 0, 1).contiguous())
-    batch = torch.stack(images)
+        smp.append(f"set0/gt/{i:04d}.png")
     opts = dict(size=48, overlap=16, batch=4)
     ys, xs, wh, ww = tiled.tile_grid(96, 128, 48, 16)
     assert (len(ys), len(xs), wh, ww) == (3, 4, 48, 48)
