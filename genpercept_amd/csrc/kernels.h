@@ -236,6 +236,7 @@ void launch_quantize(const float* x, void* q, long long n, int bits, hipStream_t
 // stereo.hip: gp_stereo_views and gp_stereo_views_workspace (declared in include/genpercept_hip.h, like the entries of the other
 // post-processing sources: they have no launcher of their own behind the C-ABI).  Arithmetic: stereo_math.h.
 // parallax.hip: gp_parallax_frames and gp_parallax_frames_workspace, declared there too.  Arithmetic: parallax_math.h over stereo_math.h.
+// relight.hip: gp_relight, declared there too.  Arithmetic: relight_math.h.
 
 // contract.hip: the kernels between the matrix products of the contract-precision mode (fp32 storage, split-bf16 MFMA operands:
 // A order [hi | lo | hi], B order [hi | hi | lo] over a tripled K).  Split tensors have 3 * C elements per row.

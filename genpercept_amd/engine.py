@@ -181,6 +181,7 @@ SYMBOLS = {
     "gp_stereo_views": (_i, [_vp] * 4 + [_i] * 9 + [_vp] * 4 + [_ll, _vp]),
     "gp_parallax_frames_workspace": (_ll, [_i] * 4),
     "gp_parallax_frames": (_i, [_vp] * 4 + [_i] * 7 + [_vp] * 4 + [_ll, _vp]),
+    "gp_relight": (_i, [_vp] * 7 + [_i] * 8 + [_vp] * 3),
     "gp_ensemble_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gp_ensemble_workspace": (_ll, [_i, _i, _i, _i]),
     "gp_ensemble_reduce": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
@@ -1603,6 +1604,53 @@ def parallax_frames(image: torch.Tensor, pred: torch.Tensor, path="orbit", frame
             image.data_ptr(), pred.data_ptr(), plane.data_ptr(), table.ctypes.data, b, n_frames, h, w, SPACES.index(space), o["edge"], o["max_s8"],
             out.data_ptr(), _ptr(holes), _ptr(near), ws.data_ptr(), nbytes, _stream_ptr(dev))
     return result
+
+
+def relight(image: torch.Tensor, normal: torch.Tensor, pred: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None, lights=True,
+            ambient=0.35, relief=64.0, encoded: bool = True, flip=(False, False, False), space: str = "depth", tables=None,
+            want_shadow: bool = False):
+    """gp_relight on device tensors: the images under new directional lights, shaded by their normal maps with cast shadows from their depth
+    or disparity maps.  image uint8 [B, 3, H, W] ([3, H, W]: one image); normal float [B, 3, H, W], encoded in [0, 1] (the pipeline's normal
+    mode) or raw in [-1, 1] (`depth_geometry`'s normals: encoded=False); pred float [B, 1, H, W] ([B, H, W] and [H, W] too) or None (no
+    shadows); weight uint8 [B, H, W] or None (255: relit, 0: the image; a matting alpha as bytes relights the subject only); lights True
+    (`relight.DEFAULT_LIGHT`), a dict over its keys or up to 8 of them, or a HOST integer table [L + 1, 20] (`relight.relight_lights`), with
+    which ambient and relief are not read; ambient one value or three; relief, the height in pixels of the map's full range; flip, a sign
+    per axis; space "depth" or "disparity"; tables None (`lens_blur.srgb_tables`) or a HOST pair (to_lin, from_lin).  Returns uint8
+    [B, 3, H, W] on the device, and with want_shadow (out, shadow) with shadow uint8 [B, H, W], the darkest shade over the lights.
+    Definition in include/genpercept_hip.h; genpercept_amd/relight.py gives the same bits.  Enqueued on the current stream, no
+    synchronisation, nothing read back."""
+    from .relight import REACH, check_flip, check_rows, check_tables, relight_lights
+    image = _images_u8(image, "image")
+    b, _, h, w = (int(v) for v in image.shape)
+    dev = image.device
+    normal = _float32(normal, "normal")
+    normal = (normal[None] if normal.dim() == 3 else normal).contiguous()
+    if tuple(normal.shape) != (b, 3, h, w) or normal.device != dev:
+        raise ValueError(f"normal {tuple(normal.shape)} on {normal.device} and image {(b, 3, h, w)} on {dev}: three planes per image, same size, same device")
+    if pred is not None:
+        pred = _float_maps(pred, "pred")
+        _same_batch(image, tuple(int(v) for v in pred.shape), pred.device, "image")
+    if space not in SPACES:
+        raise ValueError(f"space is one of {SPACES}, got {space!r}")
+    _post_dims(b, h, w, "relight")
+    if weight is not None:
+        if not torch.is_tensor(weight) or weight.dtype != torch.uint8 or weight.device != dev:
+            raise ValueError(f"weight: a uint8 tensor on {dev}, got {weight.dtype if torch.is_tensor(weight) else type(weight)}")
+        weight = _eval_maps(weight, "weight").contiguous()   # (its bytes are weights, not a mask: `_mask_u8` would take any dtype through != 0)
+        if tuple(weight.shape) != (b, h, w):
+            raise ValueError(f"weight {tuple(weight.shape)} does not match the images {(b, h, w)}")
+    rows = check_rows(lights) if isinstance(lights, np.ndarray) else relight_lights(lights, ambient, relief)
+    bits = check_flip(flip)
+    check_tables(tables)   # (refused before the device is asked for)
+    n_lights, max_reach = int(rows.shape[0]) - 1, int(rows[:-1, REACH].max())
+    assert image.is_cuda
+    to_lin, from_lin = _lens_tables(tables, dev)
+    out = torch.empty((b, 3, h, w), dtype=torch.uint8, device=dev)
+    shadow = torch.empty((b, h, w), dtype=torch.uint8, device=dev) if want_shadow else None
+    _launch("gp_relight", f"images {(b, h, w)}, {n_lights} lights, space = {space}, max_reach = {max_reach}", image.data_ptr(), normal.data_ptr(),
+            _ptr(pred), _ptr(weight), rows.ctypes.data, to_lin.data_ptr(), from_lin.data_ptr(), b, h, w, n_lights, int(bool(encoded)), bits,
+            SPACES.index(space), max_reach, out.data_ptr(), _ptr(shadow), _stream_ptr(dev))
+    return (out, shadow) if want_shadow else out
 
 
 SEG_OUT = 8       # n, n_void, SEG_METRICS (out[2 .. 6]), n_classes; iou[K] follows

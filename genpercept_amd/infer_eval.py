@@ -202,6 +202,20 @@ def _write_rgb(px: np.ndarray, save_to: str) -> str:
     return save_to
 
 
+def _write_frames(clip: np.ndarray, save_to: str, animate: Optional[str], frame_ms: int) -> List[str]:
+    """The frames uint8 [V, 3, H, W] of one sample as numbered files `<stem>_0000.png`, ... next to `save_to` and, with animate="gif", one
+    looping `<stem>.gif` of them after those; the paths written."""
+    stem = os.path.splitext(save_to)[0]
+    stills = [_chw_image(px) for px in clip]
+    paths = [f"{stem}_{k:04d}.png" for k in range(len(stills))]
+    for still, path_k in zip(stills, paths):
+        still.save(path_k)
+    if animate == "gif":
+        paths.append(stem + ".gif")
+        stills[0].save(paths[-1], save_all=True, append_images=stills[1:], duration=int(frame_ms), loop=0)
+    return paths
+
+
 def _one_value_each(values: Dict, at_name: str, at) -> None:
     """The terms a dataset loop uses for every sample: each of `values` (name -> value) is one number or None, `at` one pixel (u, v) or None."""
     if any(np.ndim(v) != 0 for v in values.values()) or (at is not None and np.shape(at) != (2,)):
@@ -402,16 +416,41 @@ def run_parallax(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_d
         assert out.shape[1] == n_path
         return out
 
+    return _post_loop(base_dir, samples, output_dir, name_mode, ".png", batch_size, rank, world, prefetch, clips,
+                      lambda clip, save_to: _write_frames(clip, save_to, animate, frame_ms))
+
+
+def run_relight(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_dir: str, name_mode: FileNameMode, mode: str = "normal",
+                batch_size: int = 1, rank: int = 0, world: int = 1, lights=True, ambient=0.35, relief=64.0, flip=(False, False, False), tables=None,
+                sweep: Optional[int] = None, animate: Optional[str] = None, frame_ms: int = 40, prefetch: int = 2, **inference_options):
+    """One relit photograph per sample with `pipe.relight_batch_device` (mode normal: shading only; modes depth and disparity: the normals
+    fitted to the sample's own prediction and its cast shadows): an RGB `.png`.  lights, ambient, relief, flip and tables as that entry takes
+    them, used for every sample.  With sweep=n every sample gives n frames in which every light's azimuth goes once round (frame i adds
+    360 i / n degrees), numbered `<name>_0000.png`, ... and, with animate="gif", one looping `<name>.gif` after them (`frame_ms` per frame):
+    the model runs once per batch and `engine.relight` n times under that one prediction.  Batching, sharding and prefetch as `run_refocus`.
+    Returns the paths written -- with sweep a list of paths per sample.  inference_options go to `pipe.predict_batch_device`, `refine` and
+    `tiles` among them."""
+    from . import engine as ge
+    from .relight import check_flip, relight_lights, relight_options
+    if mode not in ("normal", "depth", "disparity"):
+        raise ValueError(f"a relight needs a normal map or a depth map: mode 'normal', 'depth' or 'disparity', got {mode!r}")
+    if animate not in (None, "gif") or (animate is not None and sweep is None):
+        raise ValueError(f"animate is None or, with a sweep, 'gif', got {animate!r}")
+    if sweep is not None and (isinstance(sweep, bool) or not isinstance(sweep, (int, np.integer)) or not 1 <= sweep <= 3600):
+        raise ValueError(f"sweep is None or a number of frames in 1 .. 3600, got {sweep!r}")
+    check_flip(flip)
+    opts = relight_options(lights)
+    turned = [[dict(o, azimuth=o["azimuth"] + 360.0 * i / sweep) for o in opts] for i in range(sweep)] if sweep is not None else [opts]
+    for frame in turned:
+        relight_lights(frame, ambient, relief)      # (every frame's terms are checked before any image is read)
+
+    def clips(images):
+        maps = pipe._relight_maps(images, mode, None, "depth", inference_options)
+        frames = [ge.relight(lights=frame, ambient=ambient, relief=relief, flip=flip, tables=tables, **maps).cpu().numpy() for frame in turned]
+        return np.stack(frames, 1)
+
     def write(clip, save_to):
-        stem = os.path.splitext(save_to)[0]
-        stills = [_chw_image(px) for px in clip]
-        paths = [f"{stem}_{k:04d}.png" for k in range(n_path)]
-        for still, path_k in zip(stills, paths):
-            still.save(path_k)
-        if animate == "gif":
-            paths.append(stem + ".gif")
-            stills[0].save(paths[-1], save_all=True, append_images=stills[1:], duration=int(frame_ms), loop=0)
-        return paths
+        return _write_rgb(clip[0], save_to) if sweep is None else _write_frames(clip, save_to, animate, frame_ms)
 
     return _post_loop(base_dir, samples, output_dir, name_mode, ".png", batch_size, rank, world, prefetch, clips, write)
 

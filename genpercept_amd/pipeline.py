@@ -769,6 +769,51 @@ class GenPerceptPipeline:
                                          **inference_options)[0]
         return [_chw_to_pil(frame) for frame in out]
 
+    def _relight_maps(self, images, mode: str, depth, depth_space: str, inference_options: dict, preflight=None) -> dict:
+        """What `engine.relight` shades the images with, as its keyword arguments image, normal, pred, encoded and space: with mode normal
+        the prediction itself, encoded, and `depth` (a device map in `depth_space`, or None) for the shadows; with mode depth or disparity
+        the raw normals `engine.depth_geometry` fits to the prediction, and the prediction for the shadows."""
+        from . import engine as ge
+        modes = ("normal", "depth", "disparity")
+        if mode not in modes:
+            raise ValueError(f"a relight needs a normal map or a depth map: mode 'normal', 'depth' or 'disparity', got {mode!r}")
+        if mode != "normal" and depth is not None:
+            raise ValueError(f"depth= goes with mode 'normal'; in mode {mode!r} the shadows come from the prediction itself")
+        rgb, pred = self._post_inputs(images, mode, modes, "a relight", "a normal or a depth map", inference_options, preflight)
+        if mode == "normal":
+            if torch.is_tensor(depth):
+                depth = depth.to(pred.device, non_blocking=True)
+            return dict(image=rgb, normal=pred, pred=depth, encoded=True, space=depth_space)
+        return dict(image=rgb, normal=ge.depth_geometry(pred, space=mode)["normal"], pred=pred, encoded=False, space=mode)
+
+    @torch.no_grad()
+    def relight_batch_device(self, images: Union[Sequence[Image.Image], torch.Tensor], mode: str = "normal", lights=True, depth=None, weight=None,
+                             ambient=0.35, relief=64.0, flip=(False, False, False), depth_space: str = "depth", tables=None,
+                             want_shadow: bool = False, **inference_options):
+        """New light on a photograph without a trip to the host: images of one common size (PIL images or a uint8 [B,3,H,W] tensor) -> the
+        images relit, uint8 [B,3,H,W] ON THE DEVICE: `engine.relight` (gp_relight) applied under the map of
+        `predict_batch_device(images, mode, **inference_options)` at the input size, which never leaves the GPU.  mode normal: the
+        prediction is the normal map; depth, a float [B,1,H,W] device map of another pipeline's `predict_batch_device` read in
+        `depth_space`, gives the cast shadows (none without it).  mode depth or disparity: the normals are those `engine.depth_geometry`
+        fits to the prediction and the shadows come from the prediction itself.  lights: True (`relight.DEFAULT_LIGHT`), a dict over its
+        keys -- azimuth, elevation, intensity, colour, specular, shininess, shadows, reach, softness, strength, bias -- or up to 8 of them;
+        ambient one value or three; relief, the height in pixels of the map's full range; flip, a sign per axis of the normal; weight,
+        None or a uint8 [B,H,W] tensor (a matting alpha as bytes relights the subject only); tables as `refocus_batch_device`.  With
+        want_shadow (out, shadow), shadow uint8 [B,H,W].  inference_options may hold `refine` and `tiles` as in `cutout_batch_device`."""
+        from . import engine as ge
+        from .relight import check_flip, relight_lights
+        maps = self._relight_maps(images, mode, depth, depth_space, inference_options,
+                                  lambda images: (relight_lights(lights, ambient, relief), check_flip(flip)))
+        if torch.is_tensor(weight):
+            weight = weight.to(maps["image"].device, non_blocking=True)
+        return ge.relight(weight=weight, lights=lights, ambient=ambient, relief=relief, flip=flip, tables=tables, want_shadow=want_shadow, **maps)
+
+    def relight(self, image: Image.Image, mode: str = "normal", lights=True, depth=None, weight=None, ambient=0.35, relief=64.0,
+                flip=(False, False, False), depth_space: str = "depth", tables=None, **inference_options) -> Image.Image:
+        """`relight_batch_device` for one PIL image: the relit photograph as a PIL image."""
+        return _chw_to_pil(self.relight_batch_device([image], mode, lights, depth, weight, ambient, relief, flip, depth_space, tables, False,
+                                                     **inference_options)[0])
+
     def _run_device(self, rgb, processing_res, match_input_res, resample, color_map, fix_timesteps, prompt, opts=None, refine=None,
                     tiles=None) -> List[GenPerceptOutput]:
         """Pre / post processing on the GPU (gp_preprocess / gp_postprocess): the image goes up once, resize_max_res, the model, the

@@ -40,6 +40,8 @@
  *                       row, cut at depth edges, nearest surface first, disocclusions filled from the background side
  *   gp_parallax_frames (no reference code) the frames of a camera move -- orbit, swing, dolly -- from one photograph and its depth or
  *                       disparity prediction: a forward warp of a triangle mesh cut at depth edges, with a z-test
+ *   gp_relight        (no reference code) the photograph under new directional lights: diffuse and specular shading from its normal map,
+ *                       screen-space cast shadows marched over its depth or disparity map, in integer arithmetic
  *   gp_ensemble_gather, gp_ensemble_reduce
  *                     ensemble_depth's tensor half (the BFGS fit stays on the host)   genpercept/util/ensemble.py:43-205;
  *                                                                   genpercept_pipeline.py:289-298
@@ -775,6 +777,56 @@ gp_status gp_parallax_frames(const unsigned char* image, const float* pred, cons
                              int B, int V, int H, int W, int space, int edge, int max_s8, unsigned char* out,
                              unsigned char* holes /* or NULL */, unsigned short* near /* or NULL */, void* workspace,
                              long long workspace_bytes, void* stream);
+
+/* ---- relighting: the photograph under new lights, from its normal and depth maps (DEVICE pointers but the light table; stateless, stream-ordered, no host synchronisation, no atomics; csrc/relight.hip) ----
+ * What surface normals are for in a photograph: "portrait lighting", "studio light".  Framework ops do the Lambert term; what makes a relit
+ * image look right is that a light from the side is blocked by what stands in front of it -- a nose shadows a cheek, a person the wall --,
+ * a march over the depth map per pixel and light.  Here the image is shaded under up to 8 directional lights and an ambient term, diffuse
+ * and specular, with screen-space cast shadows, and blended with the original under an optional weight (a matting alpha relights the
+ * subject only).  The whole definition is integer arithmetic, so the order of evaluation is free and the device equals the host route
+ * genpercept_amd/relight.py bit for bit; the arithmetic stands once more in csrc/relight_math.h.
+ * Axes: those of gp_depth_geometry (x right, y down, z away from the camera).  A camera-facing normal has N_z < 0; a light in front of the
+ *   scene has L_z < 0.  The projection is orthographic and the view direction (0, 0, -1) at every pixel, a stated convention: an
+ *   affine-invariant map has no camera.
+ * Inputs per image: image uint8 [3][H][W]; normal fp32 [3][H][W]; pred fp32 [H][W] or NULL (no shadows without it); weight uint8 [H][W] or
+ *   NULL.  Per call: encoded = 1 (values in [0, 1], as the pipeline's normal mode writes them) or 0 (values in [-1, 1], as
+ *   gp_depth_geometry writes them); flip, 3 bits, bit k negates N_k (a checkpoint trained in another convention); space = 0 (depth) or 1
+ *   (disparity); to_lin and from_lin, the DEVICE tables of gp_lens_blur under the same conditions; lights, a HOST table of L + 1 rows of
+ *   20 int32 -- L light rows (1 <= L <= 8), then the ambient row; max_reach 0 .. 64, the longest march a row may ask for.  1 <= H, W <=
+ *   16384, B <= 65535 and B * H * W < 2^31.
+ * A light row: L_x, L_y, L_z, the unit vector TOWARDS the light * 16384; H_x, H_y, H_z, the unit half vector between L and the view
+ *   direction * 16384; col_r, col_g, col_b and spc_r, spc_g, spc_b, the diffuse and specular gains in Q8 (256 = 1.0, at most 4096); k, the
+ *   specular term is raised to the power 2^k (0 .. 7); ux, uy, the screen step towards the light in 1 / 256 pixel, max(|ux|, |uy|) = 256
+ *   where the row has a reach; rise >= 0, the nearness the ray gains per step (at most 65535); bias 0 .. 65535; soft, strength 0 .. 256;
+ *   reach 0 .. max_reach steps.  The ambient row: amb_r, amb_g, amb_b in Q12 (4096 = 1.0, at most 65536); its other entries are not read.
+ * 1. Normal: N_k = 2 Q(v_k) - 65535 (encoded), Q the 16-bit rule of gp_postprocess, or N_k = (int)(clamp(v_k, -1, 1) * 65535.0f),
+ *    truncated (raw); then the sign flips.  m = floor(sqrt(N_x^2 + N_y^2 + N_z^2)), exact (the argument is below 2^34).  A pixel with a NaN
+ *    channel or m < 256 has no usable normal and is shaded as facing the camera, N = (0, 0, -65535), m = 65535: the smooth fallback for the
+ *    pixels gp_depth_geometry leaves without a fit.
+ * 2. Per light j: cos12 = clamp(floor(N . L_j / (4 m)), 0, 4096); s = clamp(floor(N . H_j / (4 m)), 0, 4096), then k_j times
+ *    s = (s s + 2048) >> 12.  A light with cos12 = 0 contributes nothing, neither diffuse nor specular nor to the shadow plane.
+ * 3. Shadow of light j, where pred is given, the row has a reach, cos12 > 0 and the pixel's pred is not NaN: D is the nearness of
+ *    gp_lens_blur step 1 (a NaN pixel has D = 0 and neither casts nor receives a shadow).  For t = 1 .. reach the sample is
+ *    q_t = (x + ((t ux + 128) >> 8), y + ((t uy + 128) >> 8)) (floor shifts); samples outside the image do not exist.
+ *    e_t = D(q_t) - D(p) - bias - t rise; E = max(0, max_t e_t).  dark = min(256, (E soft + 128) >> 8), or with soft = 0 dark = 256 iff
+ *    E > 0 (a hard shadow); shade_j = (dark strength) >> 8; vis_j = 256 - shade_j.  Everywhere else shade_j = 0.
+ * 4. Combination in linear light, lin_k = to_lin[image_k]: G_k = amb_k + ((sum_j col_jk cos12_j vis_j) >> 16);
+ *    S_k = (sum_j spc_jk s_j vis_j) >> 16; lin'_k = min(4095, ((lin_k G_k + 2048) >> 12) + min(S_k, 4095)); relit_k = from_lin[lin'_k];
+ *    out_k = (w relit_k + (255 - w) image_k + 127) / 255 with w the weight, 255 without one.  The image is taken as albedo times its own
+ *    light, a convention: ambient 1.0 keeps it and the lights add to it; one white light of gain 1.0 from the camera on a camera-facing
+ *    surface with ambient 0 gives G = 4096 and returns the image.
+ * Outputs: out uint8 [B][3][H][W] (not the image itself); shadow uint8 [B][H][W] or NULL: min(255, max_j shade_j).
+ * One kernel launch for every B and L: a workgroup stages the nearness of its 32 x 16 tile and an apron of the rows' longest reach in LDS as
+ * 16-bit words and ends a march where D(p) + bias + t rise reaches the largest D it staged; without pred, or with no row that has a reach,
+ * nothing is staged.  No workspace, nothing read back; an image's bytes are the same from call to call and in every batch.
+ * GP_ERR_INVALID before any HIP call: null image / normal / lights / to_lin / from_lin / out, B < 1, B > 65535, H or W outside 1 .. 16384,
+ * B * H * W >= 2^31, L outside 1 .. 8, encoded outside 0 .. 1, flip outside 0 .. 7, space outside 0 .. 1, max_reach outside 0 .. 64, normal,
+ * pred or lights not 4-byte aligned, to_lin not 2-byte aligned, out == image, a value of a light row or of amb outside its range (the table
+ * is host memory, so it can be refused). */
+gp_status gp_relight(const unsigned char* image, const float* normal, const float* pred /* or NULL */, const unsigned char* weight /* or NULL */,
+                     const int* lights /* HOST [L + 1][20] */, const unsigned short* to_lin /* [256] */, const unsigned char* from_lin /* [4096] */,
+                     int B, int H, int W, int L, int encoded, int flip, int space, int max_reach, unsigned char* out,
+                     unsigned char* shadow /* or NULL */, void* stream);
 
 /* ---- test-time ensembling on the device (DEVICE pointers; stateless, stream-ordered, no host synchronisation, no atomics; csrc/ensemble.hip) ----
  * The tensor half of ensemble_depth (genpercept/util/ensemble.py:43-205, called at genpercept_pipeline.py:289-298) for the E members of each of

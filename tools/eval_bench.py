@@ -134,6 +134,16 @@
    run; compared on the spot, bit-equal; timed at a size only while the rate at the size before predicts a minute or less).  In the same
    run the `gp_stereo_views` side-by-side pair at separation 16 on the same arrays, so that a frame's time stands next to a view's.
    `--no-host` skips the host route.
+  python tools/eval_bench.py --relight --out profiles/<name>.json
+
+16. `--relight` (instead of 1 and 2): the `gp_relight` entry behind `engine.relight` (new lights on a photograph, one launch) at
+   1 x 768 x 768 and 1 x 2048 x 3072, disparity space, sRGB tables, for one light without shadows (the streaming form: 18 bytes per pixel,
+   whose rate stands next to the device-to-device copy bandwidth measured in the same process), one light with reach 32 and three lights
+   with reach 64 on the scene of `--stereo` with its normals by central differences, and the worst case: three lights with reach 64 over a
+   ramp that rises towards them faster than their rays, so that no march ends early.  The median of 25 consecutive calls, each between two
+   device events, after 0.3 s of the same call as warm-up, for the C entry on preallocated buffers and for `engine.relight` itself,
+   against `relight.relight` on the same arrays on the host (wall clock, one run; compared on the spot, bit-equal; timed at a size only
+   while the same case's rate per pixel at the size before predicts a minute or less).  `--no-host` skips the host route.
 Needs a GPU; there is no CPU fall-back."""
 import argparse
 import json
@@ -1014,6 +1024,78 @@ def bench_parallax(b, h, w, host, host_budget_s=60.0, timed=25):
     return res
 
 
+RELIGHT_SHAPES = STEREO_SHAPES
+RELIGHT_HOST_S_PER_PIXEL = {}   # as above, per pixel, for every case by its name (shading and marching cost differently)
+
+
+def relight_cases():
+    """name -> (the lights, whether the map is passed, which map)."""
+    side = dict(azimuth=150.0, elevation=35.0, specular=0.5)
+    three = [dict(side, reach=64), dict(azimuth=20.0, elevation=50.0, intensity=0.6, reach=64, softness=0.02), dict(azimuth=270.0, elevation=30.0, intensity=0.4, reach=64)]
+    towards = [dict(azimuth=a, elevation=2.0, intensity=0.5, reach=64, softness=0.05) for a in (-30.0, 0.0, 30.0)]
+    return dict(one_light_shading_only=([dict(side, shadows=False)], False, "scene"), one_light_reach_32=([dict(side, reach=32)], True, "scene"),
+                three_lights_reach_64=(three, True, "scene"), worst_case_ramp_three_lights_reach_64=(towards, True, "ramp"))
+
+
+def bench_relight(b, h, w, host, copy_gb_per_s, host_budget_s=60.0, timed=25):
+    """gp_relight on preallocated buffers and engine.relight itself for the cases of `relight_cases`, disparity space, sRGB tables, ambient
+    0.35, relief 256, on a scene (the smooth map with noise and an edge down the middle of `--stereo`, its normals by central differences,
+    encoded) and on a ramp that rises towards its three lights faster than their rays, so that no march ends early, against relight.relight
+    on the host.  The output bits are compared where the host runs."""
+    from genpercept_amd import engine as ge
+    from genpercept_amd import relight as rl
+    d = torch.device("cuda", 0)
+    lib = ge.load_library()
+    rng = np.random.default_rng(17)
+    image = rng.integers(0, 256, (b, 3, h, w), dtype=np.uint8)
+    scene = case(b, h, w, 17)[0]
+    scene[:, :, w // 2:] = np.clip(scene[:, :, w // 2:] + 0.2, 0, 1)
+    ramp = np.broadcast_to(np.linspace(0.02, 0.98, w, dtype=np.float32)[None, None], (b, h, w)).copy()
+    gy, gx = np.gradient(scene.astype(np.float64), axis=(1, 2))
+    n = np.stack([256.0 * gx, 256.0 * gy, -np.ones_like(gx)], 1)     # (disparity space: nearer is larger, the surface tilts away from the rise)
+    normal = (0.5 * n / np.sqrt((n * n).sum(1, keepdims=True)) + 0.5).astype(np.float32)
+    maps = dict(scene=scene, ramp=ramp)
+    ti, tn = torch.from_numpy(image).to(d), torch.from_numpy(normal).to(d)
+    tm = {k: torch.from_numpy(v).to(d) for k, v in maps.items()}
+    to_lin, from_lin = ge._lens_tables(None, d)
+    out = torch.empty((b, 3, h, w), dtype=torch.uint8, device=d)
+    stream = int(torch.cuda.current_stream(d).cuda_stream)
+    opts = dict(ambient=0.35, relief=256.0, space="disparity")
+    res = dict(shape=[b, 3, h, w], options=dict(opts, tables="srgb", encoded=True), launches_per_call=1, workspace_bytes=0, timed_calls=timed,
+               statistic="median of `timed_calls` consecutive calls, each between two device events, after 0.3 s of the same call as warm-up", cases={})
+    for name, (lights, with_map, which) in relight_cases().items():
+        rows = rl.relight_lights(lights, opts["ambient"], opts["relief"])
+        n_lights, reach = len(rows) - 1, int(rows[:-1, rl.REACH].max())
+        tp = tm[which] if with_map else None
+
+        def entry():
+            rc = lib.gp_relight(ti.data_ptr(), tn.data_ptr(), tp.data_ptr() if with_map else None, None, rows.ctypes.data, to_lin.data_ptr(),
+                                from_lin.data_ptr(), b, h, w, n_lights, 1, 0, 1, reach, out.data_ptr(), None, stream)
+            assert rc == ge.GP_OK, rc
+
+        entry_runs = sorted(lens_timed_calls(entry, timed))
+        entry_ms = entry_runs[len(entry_runs) // 2]
+        call = lambda: ge.relight(ti, tn, tp, lights=lights, want_shadow=True, **opts)  # noqa: E731
+        call_ms = float(np.median(lens_timed_calls(call, timed)))
+        got, shadow = (t.cpu().numpy() for t in call())
+        moved = b * h * w * (18 + (4 if with_map else 0))    # three float planes and three bytes read, three bytes written, the map once
+        row = dict(lights=n_lights, max_reach=reach, map=which if with_map else None, gp_relight_us_per_call=1e3 * entry_ms,
+                   gp_relight_us_min_max=[1e3 * entry_runs[0], 1e3 * entry_runs[-1]], engine_relight_us_per_call=1e3 * call_ms,
+                   shadowed_share=float((shadow > 0).mean()), bytes_moved=moved, gb_per_s=moved / entry_ms / 1e6, copy_gb_per_s=copy_gb_per_s)
+        predicted_s = RELIGHT_HOST_S_PER_PIXEL.get(name, 0.0) * h * w   # (0 at the first size)
+        if host and predicted_s <= host_budget_s:
+            t0 = time.perf_counter()
+            ref = rl.relight(image, normal, maps[which] if with_map else None, lights=lights, **opts)
+            host_ms = (time.perf_counter() - t0) * 1e3
+            assert got.dtype == ref.dtype and got.shape == ref.shape and np.array_equal(got, ref), name
+            row.update(host_relight_ms=host_ms, host_runs=1, host_over_engine_call=host_ms / call_ms, output_equals_host=True)
+            RELIGHT_HOST_S_PER_PIXEL[name] = host_ms / 1e3 / (h * w)
+        elif host:
+            row["host"] = f"not timed at this size: about {predicted_s:.0f} s by the rate of the smaller size, above the budget of {host_budget_s:.0f} s"
+        res["cases"][name] = row
+    return res
+
+
 def bench_loop(n_images, batch_sizes, repeats):
     from PIL import Image
     from genpercept_amd import GenPerceptPipeline
@@ -1080,13 +1162,21 @@ def main():
     ap.add_argument("--lens-blur", action="store_true", help="time gp_lens_blur / engine.lens_blur against lens_blur.lens_blur instead")
     ap.add_argument("--stereo", action="store_true", help="time gp_stereo_views / engine.stereo_views against stereo.stereo_views instead")
     ap.add_argument("--parallax", action="store_true", help="time gp_parallax_frames / engine.parallax_frames against parallax.parallax_frames instead")
+    ap.add_argument("--relight", action="store_true", help="time gp_relight / engine.relight against relight.relight instead")
     ap.add_argument("--no-host", action="store_true",
-                    help="with --structure, --matting, --seg, --band, --foreground, --guided, --tiles, --geometry, --lens-blur, --stereo or --parallax: the device "
-                         "calls alone")
+                    help="with --structure, --matting, --seg, --band, --foreground, --guided, --tiles, --geometry, --lens-blur, --stereo, --parallax or "
+                         "--relight: the device calls alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU")
-    if a.parallax:
+    if a.relight:
+        import bench
+        bw = copy_bandwidth(torch.device("cuda", 0))
+        with bench.ClockPowerSampler("cuda:0") as clock:
+            rows = [bench_relight(*s, not a.no_host, bw) for s in RELIGHT_SHAPES]
+        res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box", build_id=bench.source_build_id(), clock=clock.summary(),
+                   copy_gb_per_s=bw, relight=rows)
+    elif a.parallax:
         import bench
         with bench.ClockPowerSampler("cuda:0") as clock:
             rows = [bench_parallax(*s, not a.no_host) for s in PARALLAX_SHAPES]
@@ -1171,7 +1261,7 @@ def main():
     else:
         res = dict(device=torch.cuda.get_device_name(0), eval_depth=[bench_eval(1, 4032, 6048, a.iters, 1), bench_eval(4, 480, 640, a.iters, 3)])
     if (not a.skip_loop and not a.normals and not a.masks and not a.structure and not a.matting and not a.seg and not a.band and not a.foreground
-            and not a.guided and not a.tiles and not a.geometry and not a.lens_blur and not a.stereo and not a.parallax):
+            and not a.guided and not a.tiles and not a.geometry and not a.lens_blur and not a.stereo and not a.parallax and not a.relight):
         res["infer_and_evaluate"] = bench_loop(16, (1, 4), 3)
     text = json.dumps(res, indent=1)
     print(text)
