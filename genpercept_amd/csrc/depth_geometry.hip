@@ -10,7 +10,8 @@
 //   count     one wave per segment: 64 consecutive columns of one row of the stride grid.  The kept pixels of a segment are counted by a
 //             ballot and a population count.
 //   scan      one workgroup turns the counts of all segments of all images into exclusive offsets, in place (four per thread and step,
-//             shuffles inside a wave, LDS across the waves), and writes offsets[B + 1] from them.
+//             shuffles inside a wave, LDS across the waves), and writes offsets[B + 1] from them (depth_grid.h, shared with depth_mesh.hip,
+//             as are the grid and the addressing of its segments).
 //   scatter   a wave per segment again: a kept pixel's place is its segment's offset plus its rank inside the ballot, so the points stand
 //             in row-major order, image after image.
 // Four launches for any batch after one copy of the cameras (HOST memory) into the workspace, stream-ordered, no atomics, nothing read back.
@@ -22,29 +23,17 @@
 #include "../../include/genpercept_hip.h"
 #include "eval_common.h"
 #include "depth_geometry_math.h"
+#include "depth_grid.h"
 
 namespace {
 
 constexpr int DG_TW = 32, DG_TH = 16;        // the tile of the geometry pass
 constexpr int DG_THREADS = DG_TW * DG_TH;    // 512: one thread per pixel of the tile
-constexpr int DG_SCAN_THREADS = 1024;
-constexpr int DG_SCAN_WAVES = DG_SCAN_THREADS / 64;
-constexpr int DG_SCAN_PER = 4;               // counts per thread and step of the scan
 
 struct DgCall {
     int H, W, space, r, min_count;
     double tau, min_cos;
 };
-
-// the stride grid: gh x gw pixels, a row of it in nseg segments of 64
-struct DgGrid {
-    int H, W, stride, gh, gw, nseg;
-};
-
-inline DgGrid dg_grid(int H, int W, int stride) {
-    const int gh = (H + stride - 1) / stride, gw = (W + stride - 1) / stride;
-    return {H, W, stride, gh, gw, (gw + 63) / 64};
-}
 
 // grid (ceil(W / 32), ceil(H / 16), B).  Dynamic LDS: 16 (32 + 2 r) (16 + 2 r) bytes.  xyz, normal: [B][3][H][W] or NULL; keep_a, keep_b: [B][H][W] or NULL.
 __global__ __launch_bounds__(DG_THREADS) void dg_geometry_kernel(const float* __restrict__ pred, const unsigned char* __restrict__ mask,
@@ -108,10 +97,9 @@ struct DgLane {
     int pix;    // v W + u
     bool kept;
     __device__ __forceinline__ DgLane(const unsigned char* __restrict__ keep, const DgGrid& g, int seg, int lane) {
-        const int sx = seg % g.nseg, t = seg / g.nseg, gv = t % g.gh, gu = sx * 64 + lane;
-        b = t / g.gh;
-        pix = gv * g.stride * g.W + gu * g.stride;   // (gv stride < H; gu stride < W where gu < gw)
-        kept = gu < g.gw && keep[b * g.H * g.W + pix] != 0;
+        const DgNode n(g, seg, lane);
+        b = n.b, pix = n.pix;
+        kept = n.exists && keep[b * g.H * g.W + pix] != 0;
     }
 };
 
@@ -123,49 +111,6 @@ __global__ __launch_bounds__(EV_THREADS) void dg_count_kernel(const unsigned cha
     const DgLane l(keep, g, (int)seg, lane);
     const u64 m = __builtin_amdgcn_ballot_w64(l.kept);
     if (lane == 0) counts[seg] = (unsigned)__popcll(m);
-}
-
-// one workgroup.  counts [total] become their exclusive prefix sums (below 2^31); offsets[k] = the prefix of image k's first segment,
-// offsets[B] = the sum.
-__global__ __launch_bounds__(DG_SCAN_THREADS) void dg_scan_kernel(unsigned* __restrict__ counts, int total, int per_image, int B, long long* __restrict__ offsets) {
-    __shared__ unsigned s_wave[DG_SCAN_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned carry = 0;
-    for (long long base = 0; base < total; base += DG_SCAN_THREADS * DG_SCAN_PER) {
-        const long long i0 = base + (long long)threadIdx.x * DG_SCAN_PER;
-        unsigned v[DG_SCAN_PER], mine = 0;
-#pragma unroll
-        for (int k = 0; k < DG_SCAN_PER; ++k) {
-            v[k] = i0 + k < total ? counts[i0 + k] : 0u;
-            mine += v[k];
-        }
-        unsigned incl = mine;  // the inclusive sum of the wave's lanes up to this one
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned up = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += up;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        unsigned before = 0, all = 0;
-#pragma unroll
-        for (int k = 0; k < DG_SCAN_WAVES; ++k) {
-            const unsigned t = s_wave[k];
-            before += k < wave ? t : 0u;
-            all += t;
-        }
-        unsigned run = carry + before + (incl - mine);
-#pragma unroll
-        for (int k = 0; k < DG_SCAN_PER; ++k) {
-            if (i0 + k < total) counts[i0 + k] = run;
-            run += v[k];
-        }
-        carry += all;
-        __syncthreads();  // s_wave is written again in the next step
-    }
-    // (the barrier above orders this workgroup's own stores before these loads)
-    for (int k = threadIdx.x; k < B; k += DG_SCAN_THREADS) offsets[k] = (long long)counts[(long long)k * per_image];
-    if (threadIdx.x == 0) offsets[B] = (long long)carry;
 }
 
 // one wave per segment.  first: [total], the exclusive prefix sums.  xyz, normal: the planes [B][3][H][W].
@@ -195,13 +140,6 @@ __global__ __launch_bounds__(EV_THREADS) void dg_scatter_kernel(const unsigned c
     }
     if (point_index) point_index[dst] = l.pix;
 }
-
-inline bool dg_dims_ok(int B, int H, int W, int stride) {
-    return B >= 1 && B <= 65535 && H >= 1 && W >= 1 && H <= DG_MAX_DIM && W <= DG_MAX_DIM && (long long)B * H * W <= 0x7fffffffLL && stride >= 1 &&
-           stride <= DG_MAX_STRIDE;
-}
-
-inline long long dg_round8(long long n) { return (n + 7) / 8 * 8; }
 
 // Per image: its camera (64 bytes), the counts of its segments, its keep bytes, its two sets of three float planes; every part a multiple of
 // 8 bytes.  The parts of all images stand together: cameras, counts, keep, xyz planes, normal planes.
@@ -259,7 +197,7 @@ gp_status gp_depth_geometry(const float* pred, const unsigned char* mask, const 
         const int per_image = g.gh * g.nseg, total = B * per_image;  // (at most B H W < 2^31)
         const unsigned nblk = (unsigned)((total + EV_WAVES - 1) / EV_WAVES);
         hipLaunchKernelGGL(dg_count_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, (const unsigned char*)keep_w, g, total, counts);
-        hipLaunchKernelGGL(dg_scan_kernel, dim3(1), dim3(DG_SCAN_THREADS), 0, s, counts, total, per_image, B, offsets);
+        hipLaunchKernelGGL(dg_scan_kernel, dim3(1), dim3(DG_SCAN_THREADS), 0, s, counts, 0LL, total, per_image, B, offsets, (long long*)nullptr);
         if (any_points)
             hipLaunchKernelGGL(dg_scatter_kernel, dim3(nblk), dim3(EV_THREADS), 0, s, (const unsigned char*)keep_w, (const unsigned*)counts, g, total,
                                (const float*)xyz_w, (const float*)normal_w, image, points, point_normals, point_rgb, point_index);

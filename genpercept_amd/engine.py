@@ -176,6 +176,8 @@ SYMBOLS = {
     "gp_tile_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
     "gp_depth_geometry_workspace": (_ll, [_i] * 4),
     "gp_depth_geometry": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, _i, C.c_double, _i] + [_vp] * 9 + [_ll, _vp]),
+    "gp_depth_mesh_workspace": (_ll, [_i] * 4),
+    "gp_depth_mesh": (_i, [_vp] * 4 + [_i] * 4 + [C.c_double] + [_vp] * 9 + [_ll, _vp]),
     "gp_lens_blur": (_i, [_vp] * 6 + [_i] * 5 + [_vp] * 3),
     "gp_stereo_views_workspace": (_ll, [_i] * 4),
     "gp_stereo_views": (_i, [_vp] * 4 + [_i] * 9 + [_vp] * 4 + [_ll, _vp]),
@@ -1500,6 +1502,56 @@ def depth_geometry(pred: torch.Tensor, cameras=None, image: Optional[torch.Tenso
     offsets = pts["offsets"].cpu().numpy()   # (synchronises: `cams`, host memory the call reads in stream order, has been read by now)
     n = int(offsets[-1])
     out.update({k: pts[k][:n] for k in ("points", "point_normals", "point_rgb", "point_index")}, offsets=offsets)
+    return out
+
+
+def depth_mesh(pred: torch.Tensor, cameras=None, image: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, space: str = "depth",
+               radius: int = 2, tau: float = 0.05, min_count: Optional[int] = None, min_cos: Optional[float] = None, stride: int = 1, cut: float = 0.05):
+    """gp_depth_geometry for the three planes (no point arrays), then gp_depth_mesh on them, on one stream: the arguments of `depth_geometry`
+    and cut in (0, 1] (0.05, a convention): grid nodes whose depths differ by more than cut times the nearer one are not joined.  Returns a
+    dict of device tensors: xyz, normal float32 [B, 3, H, W], keep uint8 [B, H, W] and the triangle mesh cut at depth edges -- vertices,
+    vertex_normals float32 [n, 3], vertex_rgb uint8 [n, 3] (255 without an image), vertex_uv float32 [n, 2], vertex_index int32 [n] (v * W + u),
+    faces int32 [m, 3] (indices local to the image) -- with vertex_offsets and face_offsets, HOST int64 [B + 1] arrays (image k owns the
+    vertices vertex_offsets[k] .. vertex_offsets[k + 1] and the faces likewise): the arrays are sliced by one read of the two, the only
+    synchronisation.  Definition in include/genpercept_hip.h; genpercept_amd/mesh.py gives the same bits.  Allocates both workspaces and,
+    for the arrays, the worst case B * gh * gw vertices and 2 * B * (gh - 1) * (gw - 1) faces."""
+    from .geometry import check_cameras
+    from .mesh import MAX_NODES, check_mesh_options
+    pred = _float_maps(pred, "pred")
+    b, h, w = (int(v) for v in pred.shape)
+    dev = pred.device
+    if image is not None:
+        image = _same_batch(_images_u8(image, "image"), (b, h, w), dev, "image")
+    if space not in SPACES:
+        raise ValueError(f"space is one of {SPACES}, got {space!r}")
+    o = check_mesh_options(radius, tau, min_count, min_cos, stride, cut)
+    _post_dims(b, h, w, "a depth mesh")
+    gh, gw = -(-h // o["stride"]), -(-w // o["stride"])
+    if b * gh * gw >= MAX_NODES:
+        raise ValueError(f"a depth mesh takes B * gh * gw < 2^30 grid nodes, got {(b, gh, gw)}")
+    cams = check_cameras(cameras.cpu().numpy() if torch.is_tensor(cameras) else cameras, b, h, w)
+    assert pred.is_cuda
+    if mask is not None:
+        mask = _mask_u8(mask, "mask", (b, h, w))
+    out = dict(xyz=torch.empty((b, 3, h, w), dtype=torch.float32, device=dev), normal=torch.empty((b, 3, h, w), dtype=torch.float32, device=dev),
+               keep=torch.empty((b, h, w), dtype=torch.uint8, device=dev))
+    n_cap, m_cap = b * gh * gw, 2 * b * (gh - 1) * (gw - 1)
+    arrays = dict(vertices=torch.empty((n_cap, 3), dtype=torch.float32, device=dev), vertex_normals=torch.empty((n_cap, 3), dtype=torch.float32, device=dev),
+                  vertex_rgb=torch.empty((n_cap, 3), dtype=torch.uint8, device=dev), vertex_uv=torch.empty((n_cap, 2), dtype=torch.float32, device=dev),
+                  vertex_index=torch.empty((n_cap,), dtype=torch.int32, device=dev), faces=torch.empty((m_cap, 3), dtype=torch.int32, device=dev))
+    both = torch.empty((2, b + 1), dtype=torch.int64, device=dev)    # vertex_offsets, face_offsets: one copy brings both to the host
+    ws_g, nbytes_g = _op_workspace("gp_depth_geometry", dev, b, h, w, o["stride"])
+    ws_m, nbytes_m = _op_workspace("gp_depth_mesh", dev, b, h, w, o["stride"])
+    describe = f"maps {(b, h, w)}, " + ", ".join(f"{k} = {v}" for k, v in o.items())
+    _launch("gp_depth_geometry", describe, pred.data_ptr(), _ptr(mask), _ptr(image), cams.ctypes.data, b, h, w, SPACES.index(space), o["radius"], o["tau"],
+            o["min_count"], o["min_cos"], o["stride"], out["xyz"].data_ptr(), out["normal"].data_ptr(), out["keep"].data_ptr(), None, None, None, None, None,
+            ws_g.data_ptr(), nbytes_g, _stream_ptr(dev))
+    _launch("gp_depth_mesh", describe, out["xyz"].data_ptr(), out["normal"].data_ptr(), out["keep"].data_ptr(), _ptr(image), b, h, w, o["stride"], o["cut"],
+            *[arrays[k].data_ptr() for k in ("vertices", "vertex_normals", "vertex_rgb", "vertex_uv", "vertex_index", "faces")],
+            both[0].data_ptr(), both[1].data_ptr(), ws_m.data_ptr(), nbytes_m, _stream_ptr(dev))
+    offsets = both.cpu().numpy()   # (synchronises: `cams`, host memory the first call reads in stream order, has been read by now)
+    n, m = int(offsets[0, -1]), int(offsets[1, -1])
+    out.update({k: arrays[k][:m if k == "faces" else n] for k in arrays}, vertex_offsets=offsets[0].copy(), face_offsets=offsets[1].copy())
     return out
 
 

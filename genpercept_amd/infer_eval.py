@@ -344,6 +344,43 @@ def run_pointclouds(pipe, base_dir: str, samples: Sequence[Sequence[str]], outpu
     return _post_loop(base_dir, samples, output_dir, name_mode, ".ply", batch_size, rank, world, prefetch, clouds, write)
 
 
+MESH_FORMATS = ("glb", "ply")
+
+
+def run_meshes(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_dir: str, name_mode: FileNameMode, mode: str = "depth",
+               batch_size: int = 1, rank: int = 0, world: int = 1, cameras=None, mesh=True, format: str = "glb", prefetch: int = 2,
+               **inference_options) -> List[str]:
+    """One triangle mesh per sample with `pipe.mesh_batch_device` (modes depth and disparity), cut at the depth edges: a binary glTF `.glb`
+    textured with the sample's own image (`mesh.write_glb`), or with format "ply" a binary little-endian `.ply` with the vertex record of
+    `run_pointclouds` and a face list (`mesh.write_mesh_ply`).  cameras: None (`geometry.default_camera`, a viewing convention) or eight values
+    used for every sample; mesh: True or dict(radius=..., tau=..., min_count=..., min_cos=..., stride=..., cut=...).  Batching, sharding and
+    prefetch as `run_cutouts`.  Returns the paths written.  inference_options go to `pipe.predict_batch_device`, `refine` and `tiles` among them."""
+    from .mesh import mesh_options, write_glb, write_mesh_ply
+    if mode not in ("depth", "disparity"):
+        raise ValueError(f"meshes need a depth map: mode 'depth' or 'disparity', got {mode!r}")
+    if format not in MESH_FORMATS:
+        raise ValueError(f"format is one of {MESH_FORMATS}, got {format!r}")
+    if cameras is not None and np.asarray(cameras).shape != (8,):
+        raise ValueError(f"cameras: None or eight values used for every sample, got shape {np.asarray(cameras).shape}")
+    mesh_options(mesh)
+
+    def meshes(images):
+        out = pipe.mesh_batch_device(images, mode, cameras, mesh, **inference_options)
+        v, f = out["vertex_offsets"], out["face_offsets"]
+        a = {k: out[k].cpu().numpy() for k in ("vertices", "vertex_normals", "vertex_rgb", "vertex_uv", "faces")}
+        return [dict({k: a[k][v[i]:v[i + 1]] for k in a if k != "faces"}, faces=a["faces"][f[i]:f[i + 1]], image=np.moveaxis(np.asarray(img), -1, 0))
+                for i, img in enumerate(images)]
+
+    def write(m, save_to):
+        if format == "glb":
+            write_glb(save_to, m["vertices"], m["vertex_normals"], m["vertex_uv"], m["faces"], image=m["image"])
+        else:
+            write_mesh_ply(save_to, m["vertices"], m["vertex_normals"], m["vertex_rgb"], m["faces"])
+        return save_to
+
+    return _post_loop(base_dir, samples, output_dir, name_mode, "." + format, batch_size, rank, world, prefetch, meshes, write)
+
+
 def run_refocus(pipe, base_dir: str, samples: Sequence[Sequence[str]], output_dir: str, name_mode: FileNameMode, mode: str = "depth",
                 batch_size: int = 1, rank: int = 0, world: int = 1, focus=None, focus_at=None, aperture=8.0, max_radius=16.0, dof=0.0, tables=None,
                 prefetch: int = 2, **inference_options) -> List[str]:

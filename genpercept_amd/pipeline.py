@@ -692,6 +692,31 @@ class GenPerceptPipeline:
         return {k: out[k].cpu().numpy() for k in ("points", "point_normals", "point_rgb", "point_index")}
 
     @torch.no_grad()
+    def mesh_batch_device(self, images: Union[Sequence[Image.Image], torch.Tensor], mode: str = "depth", cameras=None, mesh=True, **inference_options):
+        """The scene as a textured surface without a trip to the host: images of one common size (PIL images or a uint8 [B,3,H,W] tensor) ->
+        the dict of `engine.depth_mesh` (gp_depth_geometry, then gp_depth_mesh) applied to the map of `predict_batch_device(images, mode,
+        **inference_options)` at the input size, which never leaves the GPU: xyz and normal float32 [B,3,H,W], keep uint8 [B,H,W], and the
+        triangle mesh cut at depth edges -- vertices, vertex_normals float32 [n,3], vertex_rgb uint8 [n,3] (the images' colours), vertex_uv
+        float32 [n,2], vertex_index int32 [n], faces int32 [m,3] (indices local to the image) -- all ON THE DEVICE, with vertex_offsets and
+        face_offsets, host int64 [B+1] arrays; the map itself comes back under "pred".  mode: depth or disparity.  cameras: as
+        `pointcloud_batch_device` (None is a viewing convention).  mesh: True or dict(radius=..., tau=..., min_count=..., min_cos=...,
+        stride=..., cut=...).  inference_options may hold `refine` and `tiles` as in `cutout_batch_device`."""
+        from . import engine as ge
+        from .mesh import mesh_options
+        opts = mesh_options(mesh)   # (refused before the model runs)
+        rgb, pred = self._post_inputs(images, mode, ("depth", "disparity"), "a mesh", "a depth map", inference_options)
+        out = ge.depth_mesh(pred, cameras, image=rgb, space=mode, **opts)
+        out["pred"] = pred
+        return out
+
+    def mesh(self, image: Image.Image, mode: str = "depth", camera=None, mesh=True, **inference_options) -> Dict[str, np.ndarray]:
+        """`mesh_batch_device` for one PIL image: its mesh as numpy arrays, a dict of vertices, vertex_normals, vertex_rgb, vertex_uv,
+        vertex_index and faces (`mesh.write_glb` and `mesh.write_mesh_ply` take them)."""
+        from .mesh import MESH_ARRAYS
+        out = self.mesh_batch_device([image], mode, camera, mesh, **inference_options)
+        return {k: out[k].cpu().numpy() for k in MESH_ARRAYS}
+
+    @torch.no_grad()
     def refocus_batch_device(self, images: Union[Sequence[Image.Image], torch.Tensor], mode: str = "depth", focus=None, focus_at=None,
                              aperture=8.0, max_radius=16.0, dof=0.0, sharp=None, tables=None, **inference_options) -> torch.Tensor:
         """Synthetic depth of field without a trip to the host: images of one common size (PIL images or a uint8 [B,3,H,W] tensor) -> the

@@ -34,6 +34,8 @@
  *   gp_depth_geometry (no reference code: genpercept/losses/metric3d_losses/VNL.py transfer_xyz unprojects with x = (u - u0) z / f and that
  *                       is all) a depth or disparity prediction as a point map, edge-aware surface normals and a point cloud without the
  *                       flying pixels of depth edges
+ *   gp_depth_mesh     (no reference code) that point map as a triangle mesh: the grid's nodes joined where the surface is continuous, cut at
+ *                       depth edges, compacted into vertices and faces for .glb and .ply export
  *   gp_lens_blur      (no reference code) the photograph refocused under its depth or disparity prediction: a variable-radius,
  *                       occlusion-aware disc gather in integer arithmetic
  *   gp_stereo_views   (no reference code) stereo pairs, anaglyphs and quilts from a depth or disparity prediction: a forward warp of every
@@ -627,6 +629,48 @@ gp_status gp_depth_geometry(const float* pred, const unsigned char* mask /* or N
                             double min_cos, int stride, float* xyz, float* normal, unsigned char* keep, float* points, float* point_normals,
                             unsigned char* point_rgb, int* point_index, long long* offsets, void* workspace, long long workspace_bytes,
                             void* stream);
+
+/* ---- triangle meshes from the point map of a depth prediction (DEVICE pointers only; stateless, stream-ordered, no host synchronisation, no atomics; csrc/depth_mesh.hip) ----
+ * A point cloud has holes as soon as the camera moves and no viewer lights or textures it; joining every pixel to its neighbours draws a
+ * "rubber sheet" across every depth edge.  Here the nodes of the stride grid are joined only where both are kept by gp_depth_geometry's
+ * flying-pixel filter and their depths are close, so the surface is cut at depth edges.  genpercept_amd/mesh.py is the same definition on the
+ * host and gives the same bits; the per-cell arithmetic stands once more in csrc/depth_mesh_math.h.
+ * Inputs per image: xyz fp32 [3][H][W] as gp_depth_geometry writes them; normal fp32 [3][H][W] or NULL; keep uint8 [H][W]; image uint8
+ *   [3][H][W] or NULL.  Per call: stride = 1 .. 64; cut, float64 in (0, 1] (a NaN is refused; the bindings' default 0.05 is a convention, not
+ *   a measurement).  1 <= H, W <= 16384, 1 <= B <= 65535, B * H * W < 2^31 and B * gh * gw < 2^30, so the triangle count stays below 2^31.
+ * Grid: gh = ceil(H / stride), gw = ceil(W / stride); node (gy, gx) is the pixel (v, u) = (gy * stride, gx * stride), its k is keep != 0 and
+ *   its z is plane 2 of xyz, promoted to float64.
+ * Link: two nodes p, q are linked iff both are kept and |z_p - z_q| <= cut * min(z_p, z_q), in float64 and in that order: one subtraction,
+ *   fabs, one min, one product, one compare, no fused multiply-add.  A NaN fails the test.
+ * Cell (cy, cx), for cy < gh - 1 and cx < gw - 1, has the corners a = (cy, cx), b = (cy, cx + 1), c = (cy + 1, cx), d = (cy + 1, cx + 1) and
+ *   the candidate triangles T0 = (a, c, d), T1 = (a, d, b) on diagonal a-d and T2 = (a, c, b), T3 = (b, c, d) on diagonal b-c.  A triangle is
+ *   sound iff each of its three edges is linked.  The cell uses diagonal a-d iff k_a and k_d hold and also one of these: k_b and k_c do not
+ *   both hold, or |z_a - z_d| <= |z_b - z_c| (a tie goes to a-d); otherwise it uses b-c.  It emits the sound triangles of its diagonal and
+ *   nothing from the other one; there is no fallback.  So one foreground corner over a background leaves the one background triangle, and
+ *   a cell with three kept corners leaves at most that triangle.  The cell's code is T0 | T1 << 1 | T2 << 2 | T3 << 3: 0, 1, 2, 3, 4, 8 or 12.
+ * Winding: the corner orders make (v1 - v0) x (v2 - v0) point to the camera: its dot product with v0 is negative, with the camera at the
+ *   origin, x right, y down and z forward (the front face is counter-clockwise seen from the camera in a y-up viewer).
+ * Vertices: a node is a vertex iff an emitted triangle uses it (kept pixels that end up in no triangle are not exported), in row-major node
+ *   order, image after image: vertices fp32 [n][3] from xyz; vertex_normals fp32 [n][3] from normal (needs the normal input); vertex_rgb
+ *   uint8 [n][3], all 255 without an image; vertex_uv fp32 [n][2] = ((u + 0.5) / W, (v + 0.5) / H), float64, each rounded once;
+ *   vertex_index int32 [n] = v * W + u.
+ * Faces: cells in row-major order, image after image, within a cell T0 before T1 or T2 before T3: faces int32 [m][3], indices local to the
+ *   image (the global vertex index minus vertex_offsets[b]), so each image's mesh stands alone.
+ * Offsets: vertex_offsets and face_offsets, int64 [B + 1], written on the device, both required.  Every other output may be NULL; with all
+ *   of them NULL the call only counts.  The caller sizes the arrays for the worst case, B * gh * gw vertices and 2 * B * (gh - 1) * (gw - 1) faces.
+ * Four kernel launches for every B (codes, count, one scan over both count arrays, scatter: the last only with an output array), nothing
+ * read back; an image's mesh is bitwise the same from call to call and in every batch.
+ * workspace: DEVICE scratch of at least the workspace entry's byte count (a code byte per node; two counts and a 64-bit used mask per
+ * segment of 64 nodes), 8-byte aligned, free again once the stream has passed the call.
+ * GP_ERR_INVALID before any HIP call: null xyz / keep / vertex_offsets / face_offsets / workspace, B < 1, B > 65535, H or W outside
+ * 1 .. 16384, B * H * W >= 2^31, B * gh * gw >= 2^30, stride outside 1 .. 64, cut outside (0, 1] (NaN included), vertex_normals without normal,
+ * xyz, normal, vertices, vertex_normals, vertex_uv, vertex_index or faces not 4-byte aligned, the offsets or workspace not 8-byte aligned,
+ * workspace_bytes too small. */
+long long gp_depth_mesh_workspace(int B, int H, int W, int stride);  /* bytes; 0 for invalid sizes; proportional to B; multiple of 8 */
+gp_status gp_depth_mesh(const float* xyz, const float* normal /* or NULL */, const unsigned char* keep, const unsigned char* image /* or NULL */,
+                        int B, int H, int W, int stride, double cut, float* vertices, float* vertex_normals, unsigned char* vertex_rgb,
+                        float* vertex_uv, int* vertex_index, int* faces, long long* vertex_offsets, long long* face_offsets, void* workspace,
+                        long long workspace_bytes, void* stream);
 
 /* ---- synthetic depth of field: the photograph refocused under its depth prediction (DEVICE pointers; stateless, stream-ordered, no host synchronisation, no atomics; csrc/lens_blur.hip) ----
  * The image-space use of a monocular depth map: the defocus blur of a wide aperture, driven by the map.  Framework ops give the two classic

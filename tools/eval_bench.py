@@ -144,6 +144,17 @@
    device events, after 0.3 s of the same call as warm-up, for the C entry on preallocated buffers and for `engine.relight` itself,
    against `relight.relight` on the same arrays on the host (wall clock, one run; compared on the spot, bit-equal; timed at a size only
    while the same case's rate per pixel at the size before predicts a minute or less).  `--no-host` skips the host route.
+  python tools/eval_bench.py --mesh --out profiles/<name>.json
+
+17. `--mesh` (instead of 1 and 2): the `gp_depth_mesh` entry behind `engine.depth_mesh` (triangle meshes cut at depth edges: four launches)
+   at 1 x 768 x 768 and 1 x 2048 x 3072 with stride 1 and 2 and cut 0.05, depth space, the default camera, on the scene and image of
+   `--geometry`.  The median of 25 consecutive calls, each between two device events, after 0.3 s of the same call as warm-up, for the C
+   entry alone on preallocated buffers with the planes given, and for the whole `engine.depth_mesh` (both entries, allocations and its one
+   read of the offsets), against `mesh.depth_mesh` on the host (wall clock, one run; every plane, array and offset compared on the spot,
+   bit-equal).  In the same run, as the yardstick, the point-cloud call `engine.depth_geometry` at the same shapes, and `gp_depth_geometry`
+   with and without its point arrays, whose difference is its count, scan and scatter launches.  The vertex and face counts and the bytes
+   the call has to move (5 B/node read, 27 B/vertex read, 39 B/vertex and 12 B/face written) stand next to each time and to the
+   device-to-device copy bandwidth measured in the same process.  `--no-host` skips the host route.
 Needs a GPU; there is no CPU fall-back."""
 import argparse
 import json
@@ -1096,6 +1107,87 @@ def bench_relight(b, h, w, host, copy_gb_per_s, host_budget_s=60.0, timed=25):
     return res
 
 
+MESH_SHAPES = GEOMETRY_SHAPES
+MESH_STRIDES = (1, 2)
+
+
+def bench_mesh(b, h, w, stride, host, copy_gb_per_s, cut=0.05, radius=2, timed=25):
+    """gp_depth_mesh alone on preallocated buffers with the planes given, and the whole engine.depth_mesh, against mesh.depth_mesh on the
+    host; the point-cloud call of engine.depth_geometry and the compaction launches of gp_depth_geometry in the same run as the yardstick."""
+    from genpercept_amd import engine as ge
+    from genpercept_amd import geometry as gm
+    from genpercept_amd import mesh as ms
+    d = torch.device("cuda", 0)
+    lib = ge.load_library()
+    rng = np.random.default_rng(13)
+    pred = case(b, h, w, 13)[0]
+    pred[:, :, w // 2:] = np.clip(pred[:, :, w // 2:] + 0.2, 0, 1)   # a depth edge down the middle
+    image = rng.integers(0, 256, (b, 3, h, w), dtype=np.uint8)
+    o = ms.check_mesh_options(radius, stride=stride, cut=cut)
+    cams = gm.check_cameras(None, b, h, w)
+    tp, ti = torch.from_numpy(pred).to(d), torch.from_numpy(image).to(d)
+    gh, gw = -(-h // stride), -(-w // stride)
+    n_cap, m_cap = b * gh * gw, 2 * b * (gh - 1) * (gw - 1)
+    planes = [torch.empty(s, dtype=t, device=d) for s, t in (((b, 3, h, w), torch.float32), ((b, 3, h, w), torch.float32), ((b, h, w), torch.uint8))]
+    points = [torch.empty(s, dtype=t, device=d) for s, t in (((n_cap, 3), torch.float32), ((n_cap, 3), torch.float32), ((n_cap, 3), torch.uint8),
+                                                            ((n_cap,), torch.int32), ((b + 1,), torch.int64))]
+    arrays = [torch.empty(s, dtype=t, device=d) for s, t in (((n_cap, 3), torch.float32), ((n_cap, 3), torch.float32), ((n_cap, 3), torch.uint8),
+                                                            ((n_cap, 2), torch.float32), ((n_cap,), torch.int32), ((m_cap, 3), torch.int32),
+                                                            ((b + 1,), torch.int64), ((b + 1,), torch.int64))]
+    g_bytes, m_bytes = int(lib.gp_depth_geometry_workspace(b, h, w, stride)), int(lib.gp_depth_mesh_workspace(b, h, w, stride))
+    ws_g, ws_m = (torch.empty((n // 8,), dtype=torch.int64, device=d) for n in (g_bytes, m_bytes))
+    stream = int(torch.cuda.current_stream(d).cuda_stream)
+
+    def geometry_entry(with_points):
+        rc = lib.gp_depth_geometry(tp.data_ptr(), None, ti.data_ptr(), cams.ctypes.data, b, h, w, 0, o["radius"], o["tau"], o["min_count"], o["min_cos"], stride,
+                                   *[p.data_ptr() for p in planes], *[p.data_ptr() if with_points else None for p in points], ws_g.data_ptr(), g_bytes, stream)
+        assert rc == ge.GP_OK, rc
+
+    def mesh_entry():
+        rc = lib.gp_depth_mesh(planes[0].data_ptr(), planes[1].data_ptr(), planes[2].data_ptr(), ti.data_ptr(), b, h, w, stride, o["cut"],
+                               *[a.data_ptr() for a in arrays], ws_m.data_ptr(), m_bytes, stream)
+        assert rc == ge.GP_OK, rc
+
+    def median_ms(call):
+        runs = sorted(lens_timed_calls(call, timed))
+        return runs[len(runs) // 2], [runs[0], runs[-1]]
+
+    geometry_entry(False)
+    mesh_ms, mesh_min_max = median_ms(mesh_entry)
+    planes_ms, _ = median_ms(lambda: geometry_entry(False))
+    cloud_ms, _ = median_ms(lambda: geometry_entry(True))
+    kw = dict(radius=radius, stride=stride)
+    call_ms, _ = median_ms(lambda: ge.depth_mesh(tp, None, ti, cut=cut, **kw))
+    yard_ms, _ = median_ms(lambda: ge.depth_geometry(tp, None, ti, **kw))
+    got = ge.depth_mesh(tp, None, ti, cut=cut, **kw)
+    n, m, points_n = int(got["vertex_offsets"][-1]), int(got["face_offsets"][-1]), int(ge.depth_geometry(tp, None, ti, **kw)["offsets"][-1])
+    read, written = 5 * n_cap + 27 * n, 39 * n + 12 * m
+    compact_ms, compact_bytes = cloud_ms - planes_ms, n_cap + 27 * points_n + 31 * points_n
+    res = dict(shape=[b, 1, h, w], options=dict(o, space="depth"), input="smooth map with noise and a depth edge down the middle; random image; default camera",
+               grid=[gh, gw], vertices=n, faces=m, vertices_worst_case=n_cap, faces_worst_case=m_cap, kept_grid_pixels=points_n,
+               gp_depth_mesh_us_per_call=1e3 * mesh_ms, gp_depth_mesh_us_min_max=[1e3 * v for v in mesh_min_max], timed_calls=timed,
+               statistic="median of `timed_calls` consecutive calls, each between two device events, after 0.3 s of the same call as warm-up",
+               launches_per_call=4, workspace_bytes=m_bytes, bytes_read=read, bytes_written=written,
+               bytes_rule="read 5 B/node and 27 B/vertex; written 39 B/vertex and 12 B/face; the workspace (1 B/node twice, 16 B/segment) not counted",
+               gb_per_s=(read + written) / mesh_ms / 1e6, copy_gb_per_s=copy_gb_per_s, over_copy_rate=(read + written) / mesh_ms / 1e6 / copy_gb_per_s,
+               bytes_alone_us=(read + written) / copy_gb_per_s / 1e3, engine_depth_mesh_us_per_call=1e3 * call_ms,
+               yardstick=dict(engine_depth_geometry_us_per_call=1e3 * yard_ms, gp_depth_geometry_planes_only_us=1e3 * planes_ms,
+                              gp_depth_geometry_with_points_us=1e3 * cloud_ms, count_scan_scatter_us=1e3 * compact_ms, count_scan_scatter_bytes=compact_bytes,
+                              count_scan_scatter_gb_per_s=compact_bytes / max(compact_ms, 1e-9) / 1e6,
+                              bytes_rule="read 1 B/node and 27 B/point, written 31 B/point",
+                              mesh_over_compaction_time=mesh_ms / max(compact_ms, 1e-9),
+                              mesh_over_compaction_time_per_byte=(mesh_ms / (read + written)) / (max(compact_ms, 1e-9) / compact_bytes)))
+    if host:
+        t0 = time.perf_counter()
+        ref = ms.depth_mesh(pred[:, None], None, image, cut=cut, **kw)
+        host_ms = (time.perf_counter() - t0) * 1e3
+        for k, v in ref.items():
+            g = got[k].cpu().numpy() if torch.is_tensor(got[k]) else got[k]
+            assert g.dtype == v.dtype and g.shape == v.shape and np.array_equal(g.view(np.uint8), v.view(np.uint8)), k
+        res.update(host_depth_mesh_ms=host_ms, host_runs=1, host_over_engine_call=host_ms / call_ms, output_equals_host=True)
+    return res
+
+
 def bench_loop(n_images, batch_sizes, repeats):
     from PIL import Image
     from genpercept_amd import GenPerceptPipeline
@@ -1163,13 +1255,21 @@ def main():
     ap.add_argument("--stereo", action="store_true", help="time gp_stereo_views / engine.stereo_views against stereo.stereo_views instead")
     ap.add_argument("--parallax", action="store_true", help="time gp_parallax_frames / engine.parallax_frames against parallax.parallax_frames instead")
     ap.add_argument("--relight", action="store_true", help="time gp_relight / engine.relight against relight.relight instead")
+    ap.add_argument("--mesh", action="store_true", help="time gp_depth_mesh / engine.depth_mesh against mesh.depth_mesh instead")
     ap.add_argument("--no-host", action="store_true",
-                    help="with --structure, --matting, --seg, --band, --foreground, --guided, --tiles, --geometry, --lens-blur, --stereo, --parallax or "
-                         "--relight: the device calls alone")
+                    help="with --structure, --matting, --seg, --band, --foreground, --guided, --tiles, --geometry, --lens-blur, --stereo, --parallax, "
+                         "--relight or --mesh: the device calls alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench needs a GPU")
-    if a.relight:
+    if a.mesh:
+        import bench
+        bw = copy_bandwidth(torch.device("cuda", 0))
+        with bench.ClockPowerSampler("cuda:0") as clock:
+            rows = [bench_mesh(*s, stride, not a.no_host, bw) for s in MESH_SHAPES for stride in MESH_STRIDES]
+        res = dict(device=torch.cuda.get_device_name(0), note="measured once on one pool box", build_id=bench.source_build_id(), clock=clock.summary(),
+                   copy_gb_per_s=bw, mesh=rows)
+    elif a.relight:
         import bench
         bw = copy_bandwidth(torch.device("cuda", 0))
         with bench.ClockPowerSampler("cuda:0") as clock:
@@ -1261,7 +1361,7 @@ def main():
     else:
         res = dict(device=torch.cuda.get_device_name(0), eval_depth=[bench_eval(1, 4032, 6048, a.iters, 1), bench_eval(4, 480, 640, a.iters, 3)])
     if (not a.skip_loop and not a.normals and not a.masks and not a.structure and not a.matting and not a.seg and not a.band and not a.foreground
-            and not a.guided and not a.tiles and not a.geometry and not a.lens_blur and not a.stereo and not a.parallax and not a.relight):
+            and not a.guided and not a.tiles and not a.geometry and not a.lens_blur and not a.stereo and not a.parallax and not a.relight and not a.mesh):
         res["infer_and_evaluate"] = bench_loop(16, (1, 4), 3)
     text = json.dumps(res, indent=1)
     print(text)
